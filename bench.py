@@ -13,10 +13,17 @@ asynchronously so that it runs under the next step.
 rank (`distributed.shard_samples`), value = 8 * steps / time; the weak-scaling number (8 samples on
 every rank, value = N * 8 * steps / time) rides along under "weak".
 
-Timing: `--windows` (default 25) repetitions of the timed window of `--steps` steps (barrier + synchronize around every
-window) inside one run; `value` / `ms_per_step` are the MEDIAN window, `timing` holds the fastest and slowest.
+Timing: `--warmup` untimed steps, then ONE timed window of exactly `--steps` steps (barrier + synchronize on both sides);
+`ms_per_step` = the window / `--steps`.  The headline arrangement follows from the arguments alone: with graphs and
+`--inflight` > 1 (default 4, N = 1 forward) the pipelined steps (`PipelinedSteps`), else the single-stream step; next to a
+pipelined headline the single-stream step is timed too (the latency of one step, `config.pipeline`).
 A run whose oracle check fails, or that leaves the device error word set, prints its line with a `failed` list and exits
 non-zero.
+
+`--dump-outputs DIR` (rank 0): after the timed window, what the headline path computed in its LAST timed step, as
+DIR/<name>.npy in float32 -- forward: `predictive_mean` (512 x 10), `kl_sums` (one per posterior tensor) and `kl` (the
+KLDivergence scalar); `--mode train`: `loss` and every parameter after the last Adam update.  Inputs, posteriors and seeds
+are fixed, so runs with the same arguments draw the same noise and two builds can be compared output for output.
 
 Prints ONE JSON line (rank 0).  Extra keys: `checked` / `checked_f32` (one more replay of the timed object compared
 with the CPU oracle on the replay's own draw keys -- a checker, never timed; N > 1: the all-reduced buffer against global
@@ -290,6 +297,10 @@ class Step:
             return self.comm
         return self.packed
 
+    def result(self):
+        """The buffer `run` returned for the last step (complete after finish() and a synchronize)."""
+        return self.comm if self.world > 1 and not self.private else self.packed
+
     def finish(self):
         if self.pending is not None:
             self.pending.wait()
@@ -326,6 +337,10 @@ class PipelinedSteps:
         self.i += 1
         with torch.cuda.stream(self.streams[k]):
             return self.steps[k].run()
+
+    def result(self):
+        """The result buffer of the step replayed last."""
+        return self.steps[(self.i - 1) % len(self.steps)].result()
 
     def finish(self):
         for k, st in enumerate(self.steps):
@@ -400,10 +415,7 @@ def oracle_evaluate(got, keys, e_dev, e_after, post, x_cpu, mode, nsamples, worl
     for mw, rw, mb, rb in post:
         tensors += [(mw.numpy(), rw.numpy(), 0.0, 0.1), (mb.numpy(), rb.numpy(), 0.0, 0.1)]
     kl_ref = orc.kl_divergence(tensors)
-    if world == 1:
-        kl_got = float(got[T])
-    else:
-        kl_got = float(np.mean([float(got[t]) / tensors[t][0].size for t in range(T)]))
+    kl_got = kl_scalar(got, world)
     pm = got[T + 1:].reshape(BATCH, DIMS[-1])[:rows].astype(np.float64)
     rms = float(np.sqrt((pred ** 2).mean()))
     tol = TOL_BF16 if mode == "bf16" else TOL_F32
@@ -422,6 +434,34 @@ def oracle_evaluate(got, keys, e_dev, e_after, post, x_cpu, mode, nsamples, worl
         ok = ok and bool((np.abs(t - ref) <= res["h2_tol_abs"] + ulp).all())
     res["ok"] = bool(ok)
     return res
+
+
+def kl_scalar(got, world):
+    """The KLDivergence scalar of a step's packed result (numpy): slot T for N = 1; for N > 1 (the all-reduced buffer: slots
+    0 .. T-1 hold each tensor's KL SUM over all ranks' shards) formed as the reference does -- mean over the tensor, mean over
+    the tensors (loss.py:28,38)."""
+    import numpy as np
+    sizes = [n for i, o in zip(DIMS[:-1], DIMS[1:]) for n in (i * o, o)]
+    T = len(sizes)
+    if world == 1:
+        return float(got[T])
+    return float(np.mean([float(got[t]) / sizes[t] for t in range(T)]))
+
+
+def step_outputs(buf, world):
+    """What a caller of the step receives, from its packed result buffer [T KL sums | KL scalar | B x 10 predictive mean]."""
+    T = 2 * (len(DIMS) - 1)
+    got = buf.detach().float().cpu().numpy()
+    return {"predictive_mean": got[T + 1:].reshape(BATCH, DIMS[-1]), "kl_sums": got[:T], "kl": kl_scalar(got, world)}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array (tensor, numpy array or number) as out_dir/<name>.npy in float32."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def oracle_check(step, post, x_cpu, mode, rows=64, tap=None, replay=True, evaluate=True):
@@ -517,22 +557,6 @@ def time_steps(step, steps, warmup, world, dev):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = t.item()
     return dt
-
-
-def time_windows(step, steps, warmup, world, dev, windows):
-    """`windows` repetitions of the timed window of time_steps (the warm-up before the first only) -> the list of their
-    durations.  A 20-step window is ~1 ms: one window is one sample of a noisy quantity, so the line reports the MEDIAN
-    window (and the fastest and slowest next to it); every window is `steps` complete steps between barriers."""
-    out = [time_steps(step, steps, warmup, world, dev)]
-    for _ in range(max(1, windows) - 1):
-        out.append(time_steps(step, steps, 0, world, dev))
-    return out
-
-
-def _median(v):
-    v = sorted(v)
-    n = len(v)
-    return v[n // 2] if n % 2 else 0.5 * (v[n // 2 - 1] + v[n // 2])
 
 
 def _time_launches(fn, dev, iters, warm=5):
@@ -911,8 +935,8 @@ def main(argv=None):
                     help="N > 1 headline: strong = the 8 global MC samples sharded 8/N per GPU (SURVEY 8e); weak = 8 per GPU")
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("BNN_BENCH_INFLIGHT", "4")),
                     help="N = 1 forward: independent steps in flight on separate streams (1 = one stream)")
-    ap.add_argument("--windows", type=int, default=int(os.environ.get("BNN_BENCH_WINDOWS", "25")),
-                    help="repetitions of the timed window of --steps steps inside this run; the line reports the median window")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the headline path computed in its last timed step to DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="skip the configs[2..4] / K1 / K3 roofline legs")
@@ -952,15 +976,14 @@ def main(argv=None):
     bnn.manual_seed(2)
 
     strong = world > 1 and args.scaling == "strong" and SAMPLES % world == 0
-    results, checked, weak, pipeline, spread = {}, {}, None, None, {}
+    results, checked, weak, pipeline = {}, {}, None, None
     failures = []
+    dump = args.dump_outputs if rank == 0 else None
 
-    def summarise(dts, total, steps):
-        """median / fastest / slowest window -> (value, ms_per_step, steps), {window statistics}"""
-        med, lo, hi = _median(dts), min(dts), max(dts)
-        return (total * steps / med, med / steps * 1e3, steps), {
-            "windows": len(dts), "steps_per_window": steps, "ms_per_step_median": round(med / steps * 1e3, 4),
-            "ms_per_step_min": round(lo / steps * 1e3, 4), "ms_per_step_max": round(hi / steps * 1e3, 4)}
+    def timed(step, steps, warmup, total):
+        """ONE window of exactly `steps` timed steps -> (value, ms_per_step, steps)"""
+        dt = time_steps(step, steps, warmup, world, dev)
+        return total * steps / dt, dt / steps * 1e3, steps
 
     for mode in ([args.dtype] + (["f32"] if (args.dtype != "f32" and world == 1) else [])):
         bnn.set_compute(mode)
@@ -975,8 +998,9 @@ def main(argv=None):
         step = Step(net, x_in, rank, world, not args.no_graph, **skw)
         steps = args.steps if mode == args.dtype else max(10, args.steps // 4)
         total = SAMPLES if strong else world * SAMPLES
-        windows = args.windows if mode == args.dtype else max(3, args.windows // 5)
-        results[mode], spread[mode] = summarise(time_windows(step, steps, args.warmup, world, dev, windows), total, steps)
+        results[mode] = timed(step, steps, args.warmup, total)
+        if dump and mode == args.dtype and args.mode == "forward" and not use_pipe:
+            dump_outputs(dump, step_outputs(step.result(), world))
         # one more replay of the TIMED object against the oracle -- both modes, every N (N > 1: the all-reduced buffer, global
         # sample ids; every rank replays, rank 0 compares)
         chk = oracle_check(step, post, x_cpu, mode, evaluate=(rank == 0))
@@ -985,21 +1009,18 @@ def main(argv=None):
             if not chk["ok"]:
                 failures.append("oracle check of the timed step failed (%s mode)" % mode)
         if use_pipe:
-            # throughput pipeline: `inflight` steps on as many streams; the single-stream number above becomes the latency
-            single, single_spread = results[mode], spread[mode]
+            # throughput pipeline: `inflight` steps on as many streams -- the headline; the single-stream number above is the
+            # latency of one step
+            single = results[mode]
             pipe = PipelinedSteps(net, x_in, args.inflight, rank, world, **skw)
-            piped, pipe_spread = summarise(time_windows(pipe, steps, args.warmup, world, dev, windows), total, steps)
-            # both are windows of K timed steps between barriers (max over ranks, so every rank decides alike): the line reports
-            # the higher throughput and says which arrangement it was
-            use_piped = piped[0] >= single[0]
-            results[mode], spread[mode] = (piped, pipe_spread) if use_piped else (single, single_spread)
+            results[mode] = piped = timed(pipe, steps, args.warmup, total)
+            if dump:
+                dump_outputs(dump, step_outputs(pipe.result(), world))
             pipeline = {"steps_in_flight": args.inflight, "untimed_preroll_steps": int(os.environ.get("BNN_BENCH_PREROLL", "256")),
-                        "reported": "pipelined" if use_piped else "single_stream",
+                        "reported": "pipelined",
                         "pipelined_value": round(piped[0], 1), "pipelined_ms_per_step": round(piped[1], 4),
-                        "pipelined_windows": pipe_spread,
                         "single_stream_value": round(single[0], 1),
                         "single_stream_ms_per_step": round(single[1], 4),
-                        "single_stream_windows": single_spread,
                         "note": "pipelined = `steps_in_flight` complete steps in flight on as many streams: THROUGHPUT (K complete "
                                 "steps / wall time); one step's LATENCY is single_stream_ms_per_step"}
             if world == 1:
@@ -1016,8 +1037,7 @@ def main(argv=None):
                 wstep = PipelinedSteps(net, x_in, args.inflight, rank, world)
             else:
                 wstep = Step(net, x_in, rank, world, not args.no_graph)
-            wres, _ = summarise(time_windows(wstep, steps, args.warmup, world, dev, max(3, windows // 5)), world * SAMPLES, steps)
-            weak = (wres[0], wres[1])
+            weak = timed(wstep, steps, args.warmup, world * SAMPLES)[:2]
             del wstep
         del step
     bnn.set_compute(args.dtype)
@@ -1037,6 +1057,10 @@ def main(argv=None):
         tstep = TrainStep(tnet, x.bfloat16() if args.dtype == "bf16" else x, rank, world, not args.no_graph)   # (dense rows: autograd saves x)
         dt = time_steps(tstep, tsteps, args.warmup, world, dev)
         train = (world * SAMPLES * tsteps / dt, dt / tsteps * 1e3, tsteps, float(tstep.loss))
+        if dump and args.mode == "train":
+            outs = {"loss": tstep.loss}
+            outs.update((name, p) for name, p in tnet.named_parameters())     # after the last step's Adam update
+            dump_outputs(dump, outs)
         del tstep, tnet
 
     if rank == 0:
@@ -1061,8 +1085,8 @@ def main(argv=None):
         if weak is not None:
             line["weak"] = {"value": round(weak[0], 1), "ms_per_step": round(weak[1], 4), "samples_per_step_per_gpu": SAMPLES,
                             "note": "weak scaling: 8 MC samples on every GPU (global predictive mean over 8 N)"}
-        line["timing"] = dict(spread[args.dtype], note="value / ms_per_step = the MEDIAN of `windows` timed windows of `steps` steps each "
-                              "(barrier + synchronize around every window)")
+        line["timing"] = {"note": "value / ms_per_step = ONE timed window of exactly `steps` steps after `warmup` untimed steps "
+                                  "(barrier + synchronize on both sides)"}
         line["device_error_word"] = device_word
         if args.dtype in checked:
             line["checked"] = checked[args.dtype]

@@ -100,6 +100,27 @@ def test_multi_gpu_check_arithmetic_on_an_emulated_all_reduce():
     assert not stale["ok"]                                       # the replay did not advance the device epoch
 
 
+def test_dump_outputs_unpack_the_packed_step_result(tmp_path):
+    """`bench.py --dump-outputs DIR`: a step's packed result [6 KL sums | KL scalar | 512 x 10 predictive mean] is written as
+    predictive_mean.npy, kl_sums.npy and kl.npy in float32 (N > 1: the scalar formed from the all-reduced sums); a bf16
+    tensor (a parameter of the training step) is written as float32 too."""
+    sys.path.insert(0, ROOT)
+    import bench
+    T = 2 * (len(bench.DIMS) - 1)
+    buf = torch.randn(T + 1 + bench.BATCH * bench.DIMS[-1], generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(str(tmp_path), bench.step_outputs(buf, 1))
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert sorted(got) == ["kl", "kl_sums", "predictive_mean"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["predictive_mean"], buf[T + 1:].reshape(bench.BATCH, bench.DIMS[-1]).numpy())
+    assert np.array_equal(got["kl_sums"], buf[:T].numpy()) and got["kl"] == buf[T].item()
+    sizes = [n for i, o in zip(bench.DIMS[:-1], bench.DIMS[1:]) for n in (i * o, o)]          # weight, bias of each layer
+    assert np.isclose(bench.step_outputs(buf, 2)["kl"], np.mean(buf[:T].double().numpy() / sizes), rtol=1e-12)
+    bench.dump_outputs(str(tmp_path), {"w": torch.ones(3, 2, dtype=torch.bfloat16)})
+    w = np.load(os.path.join(tmp_path, "w.npy"))
+    assert w.dtype == np.float32 and w.shape == (3, 2)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode,fuse_head", [("bf16", False), ("bf16", True), ("f32", False), ("f32", True)])
 def test_timed_graph_replays_match_oracle(mode, fuse_head):
