@@ -18,6 +18,7 @@ FLAG_RELU = 1
 FLAG_X_BF16 = 2
 E_ALIGN, E_UNSUPPORTED, E_DEVICE = -4, -6, -7     # BNN_E_ALIGN, BNN_E_UNSUPPORTED, BNN_E_DEVICE (include/bnn_hip.h)
 FLAG_Y_BF16 = 4
+UNC_LOGITS, UNC_PROBS = 0, 1                     # BNN_UNC_* (bnn_mc_uncertainty)
 
 
 class BnnHipError(RuntimeError):
@@ -150,6 +151,8 @@ SIGNATURES = {
     "bnn_mc_sum": (_int, [_p, _i64, _int, _i64, _f, _p, _int, _p, ctypes.c_uint32, _p]),
     "bnn_mc_sum_kl": (_int, [_p, _i64, _int, _i64, _f, _p, _int, _p, ctypes.c_uint32, ctypes.POINTER(KlTensor), _int, _f,
                              _p, _p, _p]),
+    "bnn_mc_uncertainty": (_int, [_p, _i64, _int, _int, _i64, _int, _int, _p, _p, _p, _p, _p, ctypes.c_uint32,
+                                  ctypes.POINTER(KlTensor), _int, _f, _p, _p, _p]),
 }
 
 _lib = None

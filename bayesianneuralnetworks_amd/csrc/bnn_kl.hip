@@ -18,37 +18,6 @@ __global__ __launch_bounds__(kKlThreads) void k_kl_partial(KlLaunch L, double *_
     kl_partial_block<PT, REP>(L.t[t], (int)blockIdx.x, L.partial_base + (int)blockIdx.x, partials);
 }
 
-// One workgroup: wave w adds the partials of tensors w, w + 4, ... in a fixed order (lane-strided,
-// then the shuffle tree: no barrier per tensor); then the scalar of KLDivergence.forward
-// (loss.py:38): mean over tensors of (sum_t / n_t), / n_batches, added in tensor order.
-__device__ __forceinline__ void kl_final_body(const KlFinal &F, const double *__restrict__ partials, float *__restrict__ out)
-{
-    __shared__ double means[kKlMaxTensors];
-    const int lane = threadIdx.x & 63;
-    for (int t = threadIdx.x >> 6; t < F.ntensors; t += kKlThreads / 64) {
-        // four independent lane-strided chains: the loop is a chain of dependent-latency loads otherwise (703 partials
-        // of the MLP's largest tensor = 11 round trips; now 3); fixed order all the same
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        int i = F.first[t] + lane;
-        const int end = F.first[t + 1];
-        for (; i + 192 < end; i += 256) {
-            a0 += partials[i]; a1 += partials[i + 64]; a2 += partials[i + 128]; a3 += partials[i + 192];
-        }
-        for (; i < end; i += 64) a0 += partials[i];
-        double a = wave_sum((a0 + a1) + (a2 + a3));
-        if (lane == 0) {
-            out[t] = (float)a;
-            means[t] = (double)(float)(a / (double)F.n[t]);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double total = 0.0;
-        for (int t = 0; t < F.ntensors; ++t) total += means[t];
-        out[F.ntensors] = (float)((total / (double)F.ntensors) / (double)F.n_batches);
-    }
-}
-
 __global__ __launch_bounds__(kKlThreads) void k_kl_final(KlFinal F, const double *__restrict__ partials,
                                                          float *__restrict__ out)
 {
@@ -208,6 +177,19 @@ bool kl_plan_piggy(const bnn_kl_tensor_t *tensors, int ntensors, void *workspace
     P.pt = pt;
     P.partials = reinterpret_cast<double *>(workspace);
     return true;
+}
+
+int kl_final_plan(const bnn_kl_tensor_t *tensors, int ntensors, float n_batches, const float *kl_out, const void *workspace,
+                  KlFinal &F, const char *who)
+{
+    int rc = validate(tensors, ntensors, who);
+    if (rc) return rc;
+    if (!kl_out || !workspace) { set_error("%s: NULL kl_out / workspace", who); return BNN_E_NULL; }
+    if (!(n_batches > 0.f)) { set_error("%s: n_batches <= 0", who); return BNN_E_RANGE; }
+    F = KlFinal{};
+    F.ntensors = ntensors;
+    F.n_batches = n_batches;
+    return kl_first_pass(tensors, ntensors, nullptr, nullptr, F, false, who);
 }
 }  // namespace bnn
 

@@ -159,6 +159,37 @@ __device__ __forceinline__ void kl_block_reduce(float thread_sum, int partial_in
     }
 }
 
+// Second pass (k_kl_final, and the extra workgroup of the MC-reduction tails k_mc_sum_kl / k_mc_uncertainty).  One workgroup: wave w adds the partials of tensors w, w + 4, ... in a fixed order (lane-strided,
+// then the shuffle tree: no barrier per tensor); then the scalar of KLDivergence.forward
+// (loss.py:38): mean over tensors of (sum_t / n_t), / n_batches, added in tensor order.
+__device__ __forceinline__ void kl_final_body(const KlFinal &F, const double *__restrict__ partials, float *__restrict__ out)
+{
+    __shared__ double means[kKlMaxTensors];
+    const int lane = threadIdx.x & 63;
+    for (int t = threadIdx.x >> 6; t < F.ntensors; t += kKlThreads / 64) {
+        // four independent lane-strided chains: the loop is a chain of dependent-latency loads otherwise (703 partials
+        // of the MLP's largest tensor = 11 round trips; now 3); fixed order all the same
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        int i = F.first[t] + lane;
+        const int end = F.first[t + 1];
+        for (; i + 192 < end; i += 256) {
+            a0 += partials[i]; a1 += partials[i + 64]; a2 += partials[i + 128]; a3 += partials[i + 192];
+        }
+        for (; i < end; i += 64) a0 += partials[i];
+        double a = wave_sum((a0 + a1) + (a2 + a3));
+        if (lane == 0) {
+            out[t] = (float)a;
+            means[t] = (double)(float)(a / (double)F.n[t]);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = 0.0;
+        for (int t = 0; t < F.ntensors; ++t) total += means[t];
+        out[F.ntensors] = (float)((total / (double)F.ntensors) / (double)F.n_batches);
+    }
+}
+
 // The KL first pass carried by another kernel's launch (<= kKlPiggyMax tensors, 2048- or 4096-scalar workgroups).
 constexpr int kKlPiggyMax = 8;
 struct KlPiggy {
@@ -184,5 +215,10 @@ __device__ __forceinline__ void kl_piggy_block(const KlPiggy &P, int block)
 
 // host: plan of a piggyback first pass (bnn_kl.hip); false = not eligible (caller launches bnn_kl_forward_partial)
 bool kl_plan_piggy(const bnn_kl_tensor_t *tensors, int ntensors, void *workspace, KlPiggy &P);
+
+// host: checks the arguments of a second pass run as a tail of another launch (tensors, kl_out, workspace, n_batches) and
+// fills F as bnn_kl_forward_partial laid the partials out; BNN_OK or the BNN_E_* code (error text set)
+int kl_final_plan(const bnn_kl_tensor_t *tensors, int ntensors, float n_batches, const float *kl_out, const void *workspace,
+                  KlFinal &F, const char *who);
 
 }  // namespace bnn

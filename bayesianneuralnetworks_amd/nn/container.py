@@ -95,6 +95,29 @@ class BayesianNetworkModule(Module):
         y = self._forward_batched_stacked(x, samples, sample0, *args, _lazy_head=True, **kwargs)
         return ops.mc_mean(y, out=out, scale=(1.0 / samples) if scale is None else scale, advance=advance, kl=kl)
 
+    def predictive_uncertainty(self, x, samples=None, sample0=0, *, inputs, advance=None, kl=None, **kwargs):
+        """Predictive mean and uncertainty of `samples` MC draws of `_forward(x)` -> ops.PredictiveUncertainty(mean, total,
+        aleatoric, epistemic): total = H(mean), aleatoric = mean over samples of H(p_s), epistemic = total - aleatoric (the
+        mutual information, BALD).  inputs: 'logits' (p_s = softmax of the outputs) or 'probs' (outputs used as given, e.g. a
+        net ending in torch.nn.Softmax) -- required.  Draws are consumed as by predictive_mean with the same arguments.
+          mc_batched on CUDA: one batched pass (a hidden layer fused with its head hands on partial logits) + ONE
+                              bnn_mc_uncertainty launch, which also runs the `advance` / `kl` tails (as ops.mc_mean);
+          other CUDA:         forward_stacked (the serial loop), then the same launch;
+          CPU:                forward_stacked, then ops.uncertainty_f64 (the same formulas in float64)."""
+        from .. import ops
+        ops._unc_kind(inputs, "predictive_uncertainty", kl)         # before a draw is consumed
+        if samples is None:
+            samples = self.samples
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            if advance is not None or kl is not None:
+                raise ops.BnnHipError("predictive_uncertainty: advance / kl are tails of the device launch; x is not on the device")
+            return ops.uncertainty_f64(self.forward_stacked(x, samples, sample0, **kwargs), inputs)
+        if self.mc_batched:
+            y = self._forward_batched_stacked(x, samples, sample0, _lazy_head=True, **kwargs)
+        else:
+            y = self.forward_stacked(x, samples, sample0, **kwargs)
+        return ops.mc_uncertainty(y, inputs, advance=advance, kl=kl)
+
     def _forward_batched_stacked(self, x, samples, sample0, *args, _lazy_head=False, **kwargs):
         B = x.shape[0]
         with _mc.McContext(samples, B, sample0) as ctx:

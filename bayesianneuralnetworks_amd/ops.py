@@ -7,6 +7,7 @@ torch.bmm / torch's conv backward on the GPU (library GEMMs on already-drawn wei
 
 Every function here requires CUDA (HIP) tensors and raises BnnHipError otherwise.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -1503,6 +1504,99 @@ def mc_mean(y, out=None, scale=None, advance=None, kl=None):
         return out
     check(_lib.load().bnn_mc_sum(ptr(y), n, nadd, n, sc, ptr(out), 0, adv, 1, stream_ptr(y.device)), "bnn_mc_sum")
     return out
+
+
+# --------------------------------------------------------------------------- predictive uncertainty
+PredictiveUncertainty = collections.namedtuple("PredictiveUncertainty", ("mean", "total", "aleatoric", "epistemic"))
+PredictiveUncertainty.__doc__ = """What mc_uncertainty returns: mean (*rows, C), the predictive mean of the per-sample probabilities;
+total (*rows), its entropy; aleatoric (*rows), the mean per-sample entropy; epistemic (*rows) = total - aleatoric, the mutual
+information between the prediction and the weights (the BALD score)."""
+
+_UNC_INPUTS = {"logits": _lib.UNC_LOGITS, "probs": _lib.UNC_PROBS}
+
+
+def _unc_kind(inputs, who, kl=None):
+    """BNN_UNC_* of `inputs`.  Raises ValueError for anything but 'logits' / 'probs' (whether the outputs are logits or
+    probabilities cannot be told safely from their values) -- and then leaves no KL pending for a later launch to carry."""
+    if isinstance(inputs, str) and inputs in _UNC_INPUTS:
+        return _UNC_INPUTS[inputs]
+    if kl is not None and _tls.kl_carry is kl:
+        _tls.kl_carry = None
+    raise ValueError("%s: inputs must be 'logits' or 'probs', got %r" % (who, inputs))
+
+
+def uncertainty_f64(ys, inputs):
+    """The formulas of mc_uncertainty in float64 torch, rounded to float32 at the end (the CPU path of
+    BayesianNetworkModule.predictive_uncertainty): ys (S, *rows, C), the stacked MC outputs.
+    logits: p_s = softmax(z_s), H(p_s) = logsumexp(z_s) - sum p_s z_s, total = -sum mean log mean (0 log 0 = 0);
+    probs:  p_s = ys[s] as given, H(p) = -sum p log(p + 1e-10) for both (nn.Entropy's convention)."""
+    kind = _unc_kind(inputs, "uncertainty_f64")
+    y = ys.detach().to(torch.float64)
+    if kind == _lib.UNC_LOGITS:
+        p = torch.softmax(y, -1)
+        h = torch.logsumexp(y, -1) - (p * y).sum(-1)
+        mean = p.mean(0)
+        total = -torch.xlogy(mean, mean).sum(-1)
+    else:
+        h = -(y * torch.log(y + 1e-10)).sum(-1)
+        mean = y.mean(0)
+        total = -(mean * torch.log(mean + 1e-10)).sum(-1)
+    ale = h.mean(0)
+    f32 = lambda t: t.to(torch.float32)         # noqa: E731
+    return PredictiveUncertainty(f32(mean), f32(total), f32(ale), f32(total - ale))
+
+
+def mc_uncertainty(y, inputs=None, advance=None, kl=None):
+    """Predictive uncertainty over the leading MC axis in ONE launch (bnn_mc_uncertainty) -> PredictiveUncertainty.
+    y: CUDA fp32 (S, *rows, C), class axis last (made contiguous if it is not), or a HeadPartials (a hidden layer fused with
+    its classifier head: the launch adds the partial logits itself, bit for bit as y.logits() would).
+    inputs: 'logits' (p_s = softmax) or 'probs' (p_s as given, e.g. a net ending in torch.nn.Softmax) -- required.
+    advance / kl: as mc_mean (the device epoch bumped, a KlDeferred's second pass run, in the same launch).
+    The sums over samples are fp64 in a fixed order: bitwise reproducible."""
+    kind = _unc_kind(inputs, "mc_uncertainty", kl)
+    try:
+        if isinstance(y, HeadPartials):
+            yy = y.p
+            require_cuda_f32(yy, "y")
+            nparts, S, M, C = yy.shape
+            rows_shape = (M,)
+        else:
+            if not y.is_cuda:
+                raise BnnHipError("y must be a CUDA/HIP tensor")
+            if y.dtype != torch.float32:
+                raise BnnHipError("y must be float32, got %s" % y.dtype)
+            if y.dim() < 2:
+                raise BnnHipError("mc_uncertainty: y must be (S, *rows, classes), got %s" % (tuple(y.shape),))
+            yy = y.detach().contiguous()
+            nparts, S, C = 1, yy.shape[0], yy.shape[-1]
+            rows_shape = tuple(yy.shape[1:-1])
+        rows = 1
+        for d in rows_shape:
+            rows *= d
+        dev = yy.device
+        mean = torch.empty(rows_shape + (C,), dtype=torch.float32, device=dev)
+        total, ale, epi = (torch.empty(rows_shape, dtype=torch.float32, device=dev) for _ in range(3))
+        adv = ptr(advance) if advance is not None else None
+        karr, kT, kn, kout, kws = None, 0, 1.0, None, None
+        if kl is not None:
+            # second pass of a KL begun by kl_normal_begin, as one extra workgroup of this launch (as in mc_mean)
+            if kl.done:
+                raise BnnHipError("mc_uncertainty: this KlDeferred has already been finished")
+            if not kl.launched:                     # no narrow layer took it along
+                if _tls.kl_carry is kl:
+                    _tls.kl_carry = None
+                check(_lib.load().bnn_kl_forward_partial(kl.arr, kl.T, ptr(kl.ws), stream_ptr(dev)), "bnn_kl_forward_partial")
+                kl.launched = True
+            karr, kT, kn, kout, kws = kl.arr, kl.T, kl.n_batches, ptr(kl.out), ptr(kl.ws)
+        check(_lib.load().bnn_mc_uncertainty(ptr(yy), rows * C, nparts, S, rows, C, kind, ptr(mean), ptr(total), ptr(ale),
+                                             ptr(epi), adv, 1, karr, kT, kn, kout, kws, stream_ptr(dev)), "bnn_mc_uncertainty")
+        if kl is not None:
+            kl.done = True
+    except BnnHipError:
+        if kl is not None and _tls.kl_carry is kl:
+            _tls.kl_carry = None                    # the launch that was to finish it failed: nothing may carry it later
+        raise
+    return PredictiveUncertainty(mean, total, ale, epi)
 
 
 # --------------------------------------------------------------------------- training-loop callers

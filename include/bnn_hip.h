@@ -557,6 +557,36 @@ int bnn_mc_sum_kl(const float *y, int64_t y_sample_stride, int nsamples, int64_t
                   uint32_t advance_inc, const bnn_kl_tensor_t *tensors, int ntensors,
                   float n_batches, float *kl_out, const void *workspace, void *stream);
 
+/* Predictive uncertainty of an MC forward in ONE launch: the predictive mean and the split of its entropy into an aleatoric
+ * (expected per-sample entropy) and an epistemic part (mutual information, the BALD score).
+ * replaces  agg = torch.stack(preds).mean(0); Entropy(dim=-1)(agg)   examples/MNIST/uncertainty.py:47-52
+ *   y: nparts * nsamples addends of rows x classes fp32 (row-major, contiguous); addend v = part * nsamples + s starts at
+ *   y + v * addend_stride.  A stacked output (S, rows, classes) has nparts = 1; a fused head's partial logits
+ *   (bnn_dense_forward_head: parts, S, rows, classes) are first summed over the parts in the order bnn_mc_sum adds `parts`
+ *   addends, so the values are bit-identical to bnn_mc_sum over the parts followed by this call.
+ *   p_s = softmax(z_s) (kind BNN_UNC_LOGITS, max subtracted first) or z_s as given (BNN_UNC_PROBS, not renormalised);
+ *   mean[r, c]   = (1/S) sum_s p_s[c]                 (rows x classes)
+ *   aleatoric[r] = (1/S) sum_s H(p_s)                 (rows)
+ *   total[r]     = H(mean[r, :])                      (rows)
+ *   epistemic[r] = total - aleatoric, taken before the outputs are rounded to fp32
+ *   H: BNN_UNC_PROBS  -sum_c p log(p + 1e-10), the convention of Entropy (nn/loss.py), so that total.mean() is
+ *                     Entropy(-1)(mean);
+ *      BNN_UNC_LOGITS exact Shannon entropy: H(p_s) = lse(z_s) - sum_c p_s[c] z_s[c] (one log per sample and row), and
+ *                     0 log 0 = 0 in total.  The two conventions differ by at most classes * 1e-10.
+ *   The sums over samples are fp64, in a fixed sample order, without float atomics: bitwise reproducible run to run, and
+ *   their error does not grow with S.  1 <= nsamples <= 65536, 1 <= classes <= 4096, 1 <= nparts <= 256,
+ *   1 <= rows <= 2^31 - 1 (BNN_E_SHAPE / BNN_E_RANGE otherwise).
+ * Tails, as in bnn_mc_sum_kl: advance_epoch (may be NULL) += advance_inc in the same launch; kl_tensors != NULL: the second
+ * pass of a KL begun by bnn_kl_forward_partial(kl_tensors, kl_ntensors, kl_workspace) runs as one extra workgroup, kl_out
+ * as `out` of bnn_kl_forward (kl_ntensors + 1 floats, bit-identical). */
+enum { BNN_UNC_LOGITS = 0, BNN_UNC_PROBS = 1 };
+int bnn_mc_uncertainty(const float *y, int64_t addend_stride, int nparts, int nsamples, int64_t rows, int classes,
+                       int kind /* BNN_UNC_LOGITS 0 | BNN_UNC_PROBS 1 */,
+                       float *mean, float *total, float *aleatoric, float *epistemic,
+                       uint32_t *advance_epoch, uint32_t advance_inc,
+                       const bnn_kl_tensor_t *kl_tensors, int kl_ntensors, float kl_n_batches,
+                       float *kl_out, const void *kl_workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
