@@ -497,6 +497,11 @@ struct DenseParams {
     float *P;
     int32_t Nh;
     int64_t wh_plane_stride;    // x3: the head's weights are three bf16 planes too
+    // MC dropout in the epilogue (bnn_dense_forward_dropout, DROP): y = keep ? act(x w^T + b) * drop_scale : 0 with the mask of
+    // the RNG contract's mask part for output sample s + c, c < drop_fan copies of the tile (fan-out: S = 1, drop_fan = samples)
+    RngDev drop_rng;
+    float drop_p, drop_scale;
+    int32_t drop_fan;
 };
 
 constexpr int kDenseLoaderPrio = 1 << 21;   // internal flag (BNN_DENSE_LOADER_PRIO=1): loader waves at priority 2 (experiment)
@@ -525,9 +530,10 @@ __device__ __forceinline__ void dma_piece(const void *base, uint32_t voff, uint3
 // DIAG (BNN_DENSE_DIAG): timing-only builds whose outputs are wrong: 1 = consumers skip reads and MFMAs, 2 = loaders skip the
 // DMA, 5 = no DMA and no per-step barriers either (2 vs 5 = what the barriers cost: layer 2 13.85 vs 11.9 us, ~200 cycles per
 // step); correct builds for A/B runs of the read interleave: 3 = one MFMA per interleaved fragment read, 4 = two.
-template <int TM, int TN, int NWM, int NWN, int ST, int YM, bool RELU, int DIAG = 0>
+template <int TM, int TN, int NWM, int NWN, int ST, int YM, bool RELU, int DIAG = 0, bool DROP = false>
 __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
 {
+    static_assert(!DROP || YM <= 1, "the dropout epilogue stores fp32 or bf16");
     constexpr int NWV = 4;                              // consumer waves = loader waves
     constexpr bool INTERLEAVE = true;
     constexpr int MPR = DIAG == 3 ? 1 : DIAG == 4 ? 2 : TN >= 8 ? 2 : 1;                // MFMAs per interleaved fragment read (measured: 64 x 80 wave tile 15.9 / 16.9 us with 1 / 2, 64 x 128 at 4096^3 171 / 140 us)
@@ -783,6 +789,7 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
             }
     };
     if constexpr (BIAS_PRE) load_bias();
+    const uint32_t drop_ed = DROP ? rng_epoch_dev(p.drop_rng) : 0u;      // (requested with the bias: its latency hides behind the loop)
     if (DIAG == 0 && (nw >= p.N || mw >= p.M)) {
         // This wave's whole 16 TM x 16 TN tile lies in the padding of the grid (the BASELINE layers: N = 1200 is 7.5 column
         // panels of 160 -- the second wave column of the last panel, 6.25 % of the launch's MFMAs, LDS reads and energy): it keeps
@@ -831,13 +838,40 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
 
     // ---- epilogue: bias, activation, store (accumulator lane (i, q), register r = output row i, column 4 q + r of a 16 x 16 block)
     if constexpr (!BIAS_PRE) load_bias();               // (the fragment registers are dead here: one exposed round trip)
-    const int64_t ybase = (int64_t)s * p.y_sample_stride * ESZ;
-    // the lane's four values of block (a, b) after bias and activation
-    auto vals = [&](int a, int b, float (&v)[4]) {
+    if constexpr (DROP) {
+        // bias, activation and the 1 / (1 - p) scale once, IN PLACE (one rounding of the product, as the contract has it): what a
+        // copy stores is then acc or 0, and no value of the tile stays live beside the accumulators across the copy loop (the
+        // scaled values hoisted out of that loop beside the accumulators were what spilled the first version of this epilogue)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            v[r] = acc[a][b][r] + bv[b][r];
-            if (RELU) v[r] = fmaxf(v[r], 0.f);
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int b = 0; b < TN; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float v = acc[a][b][r] + bv[b][r];
+                    if (RELU) v = fmaxf(v, 0.f);
+                    acc[a][b][r] = v * p.drop_scale;
+                }
+    }
+    // the lane's four values of block (a, b) after bias and activation -- and, DROP, the mask of output sample `so`: row
+    // mw + 16 a + fi, columns nw + 16 b + 4 fq + r, one aligned quad of the mask index (the launcher sends N % 4 != 0 elsewhere)
+    auto vals = [&](int a, int b, float (&v)[4], int so = 0) {
+        if constexpr (DROP) {
+            uint32_t q = ((uint32_t)(mw + a * 16 + fi) * (uint32_t)p.N + (uint32_t)(nw + b * 16 + fq * 4)) >> 2;
+            RngDev rk = p.drop_rng;
+            // per block and copy: keeps the Philox work of the tile's blocks (and its round keys) from being hoisted out of the
+            // copy loop, where it would stay live beside the accumulators
+            asm volatile("" : "+v"(q), "+s"(rk.key0), "+s"(rk.key1));
+            const float4 u4 = drop_u4(rk, drop_ed, q, p.drop_rng.sample0 + (uint32_t)so);
+            const float u[4] = {u4.x, u4.y, u4.z, u4.w};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = (u[r] < p.drop_p || p.drop_scale == 0.f) ? 0.f : acc[a][b][r];
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v[r] = acc[a][b][r] + bv[b][r];
+                if (RELU) v[r] = fmaxf(v[r], 0.f);
+            }
         }
     };
     if constexpr (YM == 3) {
@@ -969,8 +1003,13 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
         return f2bf(r - __uint_as_float((uint32_t)m << 16));
     };
     constexpr int NP = YM == 2 ? 3 : 1;
+    const int ncopy = DROP ? p.drop_fan : 1;
     const bool wide = nw + WN <= p.N && mw + WM <= p.M && (p.ldy * ESZ) % 16 == 0 && (nw * ESZ) % 16 == 0 &&
-                      ((reinterpret_cast<uintptr_t>(p.Y) + ybase) & 15u) == 0 && (NP == 1 || (p.y_plane_stride * ESZ) % 16 == 0);
+                      ((reinterpret_cast<uintptr_t>(p.Y) + (int64_t)s * p.y_sample_stride * ESZ) & 15u) == 0 &&
+                      (NP == 1 || (p.y_plane_stride * ESZ) % 16 == 0) && (!DROP || ncopy == 1 || (p.y_sample_stride * ESZ) % 16 == 0);
+    for (int cp = 0; cp < ncopy; ++cp) {
+    const int so = s + cp;                              // output sample (DROP fan-out: copy c of the one computed tile)
+    const int64_t ybase = (int64_t)so * p.y_sample_stride * ESZ;
     if (wide) {
         char *T = lds + wave * EPI_BYTES;
         constexpr int row_bytes = WN * ESZ;
@@ -986,7 +1025,7 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
 #pragma unroll
                     for (int a = a0; a < a0 + EPI_A && a < TM; ++a) {
                         float v[4];
-                        vals(a, b, v);
+                        vals(a, b, v, so);
                         char *q = T + ((a - a0) * 16 + fi) * pitch + (b * 16 + fq * 4) * ESZ;
                         if (YM == 2)
                             *reinterpret_cast<uint2 *>(q) = make_uint2((uint32_t)plane_of(v[0], pl) | ((uint32_t)plane_of(v[1], pl) << 16),
@@ -1006,11 +1045,10 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
                 __builtin_amdgcn_wave_barrier();
             }
         }
-        leave_stamps();
-        return;
+        continue;
     }
-    float *Yf = reinterpret_cast<float *>(p.Y) + (int64_t)s * p.y_sample_stride;
-    uint16_t *Yh = reinterpret_cast<uint16_t *>(p.Y) + (int64_t)s * p.y_sample_stride;
+    float *Yf = reinterpret_cast<float *>(p.Y) + (int64_t)so * p.y_sample_stride;
+    uint16_t *Yh = reinterpret_cast<uint16_t *>(p.Y) + (int64_t)so * p.y_sample_stride;
 #pragma unroll
     for (int a = 0; a < TM; ++a) {
         const int m = mw + a * 16 + fi;
@@ -1018,7 +1056,7 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
 #pragma unroll
         for (int b = 0; b < TN; ++b) {
             float v[4];
-            vals(a, b, v);
+            vals(a, b, v, so);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int n = nw + b * 16 + fq * 4 + r;
@@ -1031,6 +1069,8 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
             }
         }
     }
+    }
+    if (wide) leave_stamps();
 }
 
 // ------------------------------------------------------------------------------------------------ (3) narrow head
@@ -1519,6 +1559,14 @@ struct HeadArgs {
     int64_t nh;
 };
 
+// the dropout epilogue's operands (dense_launch's `drop`, NULL = no mask).  fan: x, w and b are shared by every sample -- the
+// GEMM runs once (one sample) and its epilogue stores `nsamples` masked copies
+struct DropArgs {
+    float p;
+    const bnn_rng_t *rng;
+    bool fan;
+};
+
 // tile of a dense launch: 0 (256 x 80), 1 (128 x 160), 2 (256 x 128), 3 (64 x 160), 4 (32 x 160) -- see dense_launch
 static int dense_pick_tile(int64_t M, int64_t N, int nsamples)
 {
@@ -1538,7 +1586,8 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
                         const void *w, int64_t w_plane_stride, int64_t w_sample_stride, int64_t ldw,
                         const float *b, int64_t b_sample_stride,
                         void *y, int64_t y_plane_stride, int64_t y_sample_stride, int64_t ldy,
-                        int64_t M, int64_t N, int64_t K, int nsamples, int flags, bool x3, void *stream, const HeadArgs *head = nullptr)
+                        int64_t M, int64_t N, int64_t K, int nsamples, int flags, bool x3, void *stream, const HeadArgs *head = nullptr,
+                        const DropArgs *drop = nullptr)
 {
     if (M == 0 && N >= 1 && K >= 1 && nsamples >= 1) return BNN_OK;
     if (head) { y = head->partials; ldy = N; }           // (no output tensor: the checks below see the partials)
@@ -1588,12 +1637,30 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
         p.wh_plane_stride = head->wh_plane_stride;
     }
     hipStream_t st = (hipStream_t)stream;
+    const int full_samples = nsamples;
+    if (drop) {
+        if (x3 || head) { set_error("%s: the dropout epilogue takes plain bf16 operands", who); return BNN_E_UNSUPPORTED; }
+        p.drop_rng = make_rng(drop->rng);
+        p.drop_p = drop->p;
+        p.drop_scale = drop->p < 1.f ? 1.f / (1.f - drop->p) : 0.f;
+        p.drop_fan = drop->fan ? nsamples : 1;
+        if (drop->fan) nsamples = p.S = 1;              // one GEMM; the epilogue writes the copies
+    }
     if (N <= 16 && K <= 4 * kHeadMaxSteps * 32) {
         p.ntm = (int32_t)((M + 15) / 16);
         p.ntn = 1;
         hipLaunchKernelGGL(k_head_bf16, dim3((unsigned)((int64_t)p.ntm * nsamples)), dim3(256), 0, st, p);
-        return check_launch(who);
+        int rc = check_launch(who);
+        // the narrow kernel has no dropout epilogue: the mask runs after it, in place (a fan-out reads sample 0's slot once per
+        // element and writes every copy from it)
+        if (rc == BNN_OK && drop)
+            rc = mc_dropout_launch(who, y, drop->fan ? 0 : y_sample_stride, ldy, y, y_sample_stride, ldy, M, N, full_samples, drop->fan,
+                                   drop->p, ybf ? BNN_BF16 : BNN_F32, drop->rng, st);
+        return rc;
     }
+    // the dropout epilogue takes a lane's four columns as one aligned quad of the mask index: N % 4 == 0.  Otherwise the plain
+    // kernel stores and the mask launch runs after it, in place, as for the narrow kernel
+    const bool fused_drop = drop && N % 4 == 0;
     static const bool no_xcd = [] { const char *e = getenv("BNN_DENSE_XCD"); return e && e[0] == '0'; }();
     if (no_xcd) p.flags |= kDenseNoXcdMap;
     static const bool lprio = [] { const char *e = getenv("BNN_DENSE_LOADER_PRIO"); return e && e[0] == '1'; }();
@@ -1601,7 +1668,10 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
     // tile: the BASELINE-shaped layers (N % 80 == 0: 1200 = 7.5 x 160) take 128 x 160 with a 4-stage ring -- 36 KiB per
     // 64-k step instead of 256 x 80's 42 for the same MFMAs, 4 x 8 x 8 = 256 workgroups; wide layers 256 x 128.
     // BNN_DENSE_TILE = 0 (256 x 80), 1 (128 x 160), 2 (256 x 128), 3 (64 x 160), 4 (32 x 160) forces one for A/B runs.
-    const int tile = dense_pick_tile(M, N, nsamples);
+    int tile = dense_pick_tile(M, N, nsamples);
+    // (the dropout epilogue runs on the 80- and 160-column tiles: the 256 x 128 tile's 128 accumulators per lane leave the mask
+    // no registers, so its wide layers take 128 x 160)
+    if (fused_drop && tile == 2) tile = 1;
     // few samples (a rank of a sharded MC job runs 8 / G of them): 64- and 32-row versions of the 128 x 160 tile, the largest
     // that still gives >= 128 workgroups -- a dense launch over ONE sample (32 workgroups) took as long as over eight.
     // Measured at the BASELINE layers, one stream / three steps in flight, us per step: 4 samples 54.2 / 28.3 (128 rows),
@@ -1614,15 +1684,17 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
     const int64_t grid = (int64_t)p.ntm * p.ntn * nsamples;
     if (grid > 0x7FFFFFFF) { set_error("%s: grid too large", who); return BNN_E_RANGE; }
     static const int diag = [] { const char *e = getenv("BNN_DENSE_DIAG"); return e ? atoi(e) : 0; }();
-    if (diag >= 6 && diag <= 9 && !head) {
+    if (diag >= 6 && diag <= 9 && !head && !drop) {
         static const uint64_t stamps = [] { const char *e = getenv("BNN_DENSE_STAMPS"); return e ? strtoull(e, nullptr, 0) : 0ull; }();
         p.P = reinterpret_cast<float *>(stamps);
     }
     const bool relu = (flags & BNN_FLAG_RELU) != 0;
     const dim3 g((unsigned)grid), blk(512);
-#define BNN_DENSE_LAUNCH(TM_, TN_, NWM_, NWN_, ST_, RELU_) \
+#define BNN_DENSE_LAUNCH(TM_, TN_, NWM_, NWN_, ST_, RELU_, DROP_) \
     do { \
-        if (head) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 3, RELU_>), g, blk, 0, st, p); \
+        if (fused_drop && ybf) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 0, DROP_>), g, blk, 0, st, p); \
+        else if (fused_drop) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 0, RELU_, 0, DROP_>), g, blk, 0, st, p); \
+        else if (head) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 3, RELU_>), g, blk, 0, st, p); \
         else if (x3 && ybf) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 2, RELU_>), g, blk, 0, st, p); \
         else if (!ybf) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 0, RELU_>), g, blk, 0, st, p); \
         else if (diag == 1) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 1>), g, blk, 0, st, p); \
@@ -1636,18 +1708,22 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
         else if (diag == 9) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 9>), g, blk, 0, st, p); \
         else hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_>), g, blk, 0, st, p); \
     } while (0)
-#define BNN_DENSE_PICK(TM_, TN_, NWM_, NWN_, ST_) \
+#define BNN_DENSE_PICK(TM_, TN_, NWM_, NWN_, ST_, DROP_) \
     do { \
-        if (relu) BNN_DENSE_LAUNCH(TM_, TN_, NWM_, NWN_, ST_, true); else BNN_DENSE_LAUNCH(TM_, TN_, NWM_, NWN_, ST_, false); \
+        if (relu) BNN_DENSE_LAUNCH(TM_, TN_, NWM_, NWN_, ST_, true, DROP_); else BNN_DENSE_LAUNCH(TM_, TN_, NWM_, NWN_, ST_, false, DROP_); \
     } while (0)
-    if (tile == 0) BNN_DENSE_PICK(4, 5, 4, 1, 3);
-    else if (tile == 1) BNN_DENSE_PICK(4, 5, 2, 2, 4);
-    else if (tile == 3) BNN_DENSE_PICK(2, 5, 2, 2, 4);
-    else if (tile == 4) BNN_DENSE_PICK(1, 5, 2, 2, 4);
-    else BNN_DENSE_PICK(4, 8, 4, 1, 3);
+    if (tile == 0) BNN_DENSE_PICK(4, 5, 4, 1, 3, true);
+    else if (tile == 1) BNN_DENSE_PICK(4, 5, 2, 2, 4, true);
+    else if (tile == 3) BNN_DENSE_PICK(2, 5, 2, 2, 4, true);
+    else if (tile == 4) BNN_DENSE_PICK(1, 5, 2, 2, 4, true);
+    else BNN_DENSE_PICK(4, 8, 4, 1, 3, false);     // (no dropout epilogue: fused_drop never picks this tile)
 #undef BNN_DENSE_PICK
 #undef BNN_DENSE_LAUNCH
-    return check_launch(who);
+    int rc = check_launch(who);
+    if (rc == BNN_OK && drop && !fused_drop)
+        rc = mc_dropout_launch(who, y, drop->fan ? 0 : y_sample_stride, ldy, y, y_sample_stride, ldy, M, N, full_samples, drop->fan,
+                               drop->p, ybf ? BNN_BF16 : BNN_F32, drop->rng, st);
+    return rc;
 }
 
 
@@ -1761,6 +1837,23 @@ int bnn_dense_forward(const void *x, int64_t x_sample_stride, int64_t ldx,
 {
     return dense_launch("bnn_dense_forward", x, 0, x_sample_stride, ldx, w, 0, w_sample_stride, ldw, b, b_sample_stride,
                         y, 0, y_sample_stride, ldy, M, N, K, nsamples, flags, false, stream);
+}
+
+int bnn_dense_forward_dropout(const void *x, int64_t x_sample_stride, int64_t ldx,
+                              const void *w, int64_t w_sample_stride, int64_t ldw,
+                              const float *b, int64_t b_sample_stride,
+                              void *y, int64_t y_sample_stride, int64_t ldy,
+                              int64_t M, int64_t N, int64_t K, int nsamples, int flags, float p, const bnn_rng_t *rng, void *stream)
+{
+    const char *who = "bnn_dense_forward_dropout";
+    if (!x || !w || !y) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    int rc = check_dropout_args(who, M, N, nsamples, p, rng);
+    if (rc) return rc;
+    if (x_sample_stride < 0 || w_sample_stride < 0 || b_sample_stride < 0 || y_sample_stride < 0 ||
+        (nsamples > 1 && y_sample_stride < (M - 1) * ldy + N)) { set_error("%s: bad sample stride", who); return BNN_E_SHAPE; }
+    const DropArgs d{p, rng, x_sample_stride == 0 && w_sample_stride == 0 && (b == nullptr || b_sample_stride == 0)};
+    return dense_launch(who, x, 0, x_sample_stride, ldx, w, 0, w_sample_stride, ldw, b, b_sample_stride,
+                        y, 0, y_sample_stride, ldy, M, N, K, nsamples, flags, false, stream, nullptr, &d);
 }
 
 int bnn_dense_head_parts(int64_t M, int64_t N, int nsamples)

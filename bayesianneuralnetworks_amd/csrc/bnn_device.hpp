@@ -13,6 +13,11 @@ namespace bnn {
 void set_error(const char *fmt, ...);
 void count_launch();
 int check_launch(const char *what);
+// bnn_dropout.hip: the mask entries' shared argument checks, and the mask launch with row pitches (no checks)
+int check_dropout_args(const char *who, int64_t rows, int64_t F, int nsamples, float p, const bnn_rng_t *rng);
+int mc_dropout_launch(const char *who, const void *x, int64_t x_sample_stride, int64_t ldx, void *y, int64_t y_sample_stride,
+                      int64_t ldy, int64_t rows, int64_t F, int nsamples, bool fan, float p, int dtype, const bnn_rng_t *rng,
+                      hipStream_t st);
 
 // Device view of a bnn_rng_t.
 struct RngDev {
@@ -251,6 +256,40 @@ __device__ __forceinline__ float eps1(const RngDev &r, uint32_t epoch_dev, uint6
     const float4 z = eps4(r, epoch_dev, (uint32_t)(elem >> 2), sample);
     const uint32_t j = (uint32_t)elem & 3u;
     return j == 0 ? z.x : j == 1 ? z.y : j == 2 ? z.z : z.w;
+}
+
+// ----- dropout mask (RNG contract, mask part: include/bnn_hip.h) --------------------------------------------------------
+// The four mask uniforms of quad q (elements 4 q .. 4 q + 3 of one sample's r * F + f index), before Box-Muller:
+//   BNN_GEN_PHILOX10_U24: the four words of Philox4x32-10 block q, u = ((x >> 8) + 0.5) 2^-24 (u01);
+//   BNN_GEN_PHILOX7_U16:  half of Philox4x32-7 block q / 2 -- words 0, 1 (q even) or 2, 3 (q odd), low half then high half
+//                         of each, u = (h + 0.5) 2^-16.
+// Every kernel that applies or re-creates a mask calls THIS function, so the mask does not depend on who computes it.
+__device__ __forceinline__ float4 drop_u4(const RngDev &r, uint32_t epoch_dev, uint32_t q, uint32_t sample)
+{
+    const uint32_t c1 = r.stream_hi | (sample & 0xFFFFu);
+    if (r.gen == BNN_GEN_PHILOX7_U16) {
+        const uint4 x = philox4x32_r<7>(make_uint4(q >> 1, c1, r.epoch_host, epoch_dev), r.key0, r.key1);
+        const uint32_t a = (q & 1u) ? x.z : x.x, b = (q & 1u) ? x.w : x.y;
+        return make_float4(__builtin_fmaf((float)(a & 0xFFFFu), 0x1p-16f, 0x1p-17f), __builtin_fmaf((float)(a >> 16), 0x1p-16f, 0x1p-17f),
+                           __builtin_fmaf((float)(b & 0xFFFFu), 0x1p-16f, 0x1p-17f), __builtin_fmaf((float)(b >> 16), 0x1p-16f, 0x1p-17f));
+    }
+    const uint4 x = philox4x32_10(make_uint4(q, c1, r.epoch_host, epoch_dev), r.key0, r.key1);
+    return make_float4(u01(x.x), u01(x.y), u01(x.z), u01(x.w));
+}
+
+// The mask uniform of one element e (a caller whose four values do not form one aligned quad: ragged F)
+__device__ __forceinline__ float drop_u1(const RngDev &r, uint32_t epoch_dev, uint32_t e, uint32_t sample)
+{
+    const float4 u = drop_u4(r, epoch_dev, e >> 2, sample);
+    const uint32_t j = e & 3u;
+    return j == 0 ? u.x : j == 1 ? u.y : j == 2 ? u.z : u.w;
+}
+
+// y = keep ? v * scale : 0;  dropped iff u < p, and every element when p == 1 (scale = 1 / (1 - p) in fp32, 0 for p == 1: the
+// 24-bit uniform can round up to 1.0)
+__device__ __forceinline__ float drop_apply(float v, float u, float p, float scale)
+{
+    return (u < p || scale == 0.f) ? 0.f : v * scale;
 }
 
 // sigma = 1e-10 + softplus(rho), torch semantics (beta 1, threshold 20), for the DRAW:

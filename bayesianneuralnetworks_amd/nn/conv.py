@@ -3,7 +3,8 @@
 NormalConv2d is the hot path: an implicit-GEMM MFMA kernel whose B-operand loader draws the
 filter bank (bnn_conv2d_forward_sampled).  NormalConv1d/3d have no configuration in
 BASELINE.json: they take their weights from the fused HIP sampler (K1) and contract with the
-PyTorch-ROCm convNd op.  FlipOut / MC-dropout variants are PyTorch ops.
+PyTorch-ROCm convNd op.  FlipOut variants are PyTorch ops; the MC-dropout variants run their torch
+conv once and apply the keyed masks of a network's MC-batched device pass in HIP (bnn_mc_dropout).
 """
 import torch
 from torch.distributions import Normal
@@ -13,7 +14,7 @@ from . import _settings
 from ..utils import _single, _pair, _triple
 from .container import BayesianModule
 from .core import WeightNormal
-from .dense import _NormalSampling, _init_normal_posterior
+from .dense import _NormalSampling, _init_normal_posterior, _mc_dropout_plan, _mc_dropout_key
 
 
 class BayesianConvNd(BayesianModule):
@@ -210,6 +211,8 @@ class MCDropoutConvNd(BayesianModule):
     def __init__(self, in_channels, out_channels, drop_prob):
         super().__init__(in_channels, out_channels, None)
         self.drop_prob = drop_prob
+        self.dropout_key = None         # DrawKey of the last MC-batched device mask (nn.dense._mc_dropout_key)
+        self._dropout_stream = None
 
 
 def _mcdropout(name, conv_cls):
@@ -225,7 +228,14 @@ def _mcdropout(name, conv_cls):
             self.bias = self.conv.bias
 
         def forward(self, x, sample=True):
-            return torch.nn.functional.dropout(self.conv(x), self.drop_prob, sample, False)
+            plan = _mc_dropout_plan(self, x, sample)
+            if plan is None:
+                return torch.nn.functional.dropout(self.conv(x), self.drop_prob, sample, False)
+            # MC-batched pass on the device: the conv runs once on the rows it is given (B when the input is shared), then
+            # the keyed masks of every sample (bnn_mc_dropout: fan-out to S * B rows, or one mask per sample)
+            ctx, shared = plan
+            ops.check_drop_prob(self.drop_prob)
+            return ops.mc_dropout(self.conv(x), self.drop_prob, _mc_dropout_key(self, ctx), shared)
     _MCDropout.__name__ = _MCDropout.__qualname__ = name
     return _MCDropout
 

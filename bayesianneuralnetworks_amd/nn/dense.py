@@ -5,8 +5,9 @@ all S MC samples of the call by bnn_draw_multi (ONE launch for every NormalLinea
 BayesianNetworkModule's draw plan runs first), then contracted by bnn_dense_forward (bf16 mode: bf16 operands, fp32
 accumulate) or bnn_dense_forward_x3 (fp32 parity mode at inference: three bf16 planes per operand).  Training-time fp32
 forwards, narrow fp32 layers and A/B runs take the round-1 fused kernel (bnn_linear_forward_sampled: the draw inside the
-B-operand loader of the GEMM).  The other classes (Flipout, multivariate, evidential, MC-dropout)
-are outside the HIP scope and run as PyTorch-ROCm ops with the
+B-operand loader of the GEMM).  MCDropoutLinear runs on HIP in a network's MC-batched device pass (keyed masks,
+bnn_dense_forward_dropout / bnn_mc_dropout) and keeps F.dropout elsewhere.  The other classes (Flipout, multivariate,
+evidential) are outside the HIP scope and run as PyTorch-ROCm ops with the
 reference's semantics so that its examples keep working.
 """
 import math
@@ -354,13 +355,74 @@ class NormalInverseGaussianLinear(BayesianModule):
         return Normal(gamma.clone(), torch.sqrt(beta / (upsilon * (alpha - 1))))
 
 
+def _mc_dropout_plan(layer, x, sample):
+    """Inside a BayesianNetworkModule's MC-batched pass (an McContext) on a device tensor with `sample`: -> (ctx, shared), shared =
+    x holds the un-replicated batch (ctx.base_batch rows: the layer fans out to S * B rows) rather than S * B rows (one mask per
+    sample, sample = row // B).  None: the reference's F.dropout path (serial loop, CPU, sample=False)."""
+    ctx = _mc.current()
+    if not sample or ctx is None or not isinstance(x, torch.Tensor) or not x.is_cuda:
+        return None
+    if x.dim() >= 2 and x.shape[0] == ctx.base_batch:
+        return ctx, True
+    if x.dim() >= 2 and x.shape[0] == ctx.base_batch * ctx.samples:
+        return ctx, False
+    # F.dropout here would draw ONE mask from torch's generator for what the pass treats as S samples
+    raise RuntimeError("mc_batched: %s got an input of shape %s; expected (%d, ...) or (%d, ...) rows (batch %d x %d samples)"
+                       % (type(layer).__name__, tuple(x.shape), ctx.base_batch, ctx.base_batch * ctx.samples,
+                          ctx.base_batch, ctx.samples))
+
+
+def _mc_dropout_key(layer, ctx):
+    """A fresh DrawKey for the masks of this MC-batched forward (the RNG contract's mask part), recorded as layer.dropout_key.
+    The stream id is taken at the layer's first MC-batched device forward, so that a model's existing layers keep their ids."""
+    from .._rng import DrawKey, new_stream_id
+    if getattr(layer, "_dropout_stream", None) is None:
+        layer._dropout_stream = new_stream_id()
+    key = DrawKey(default_generator.seed, layer._dropout_stream, ctx.sample0, ctx.samples, default_generator.next_epoch(),
+                  gen=generator_for(_settings.get_compute()))
+    layer.dropout_key = key
+    return key
+
+
 class MCDropoutLinear(BayesianModule):
-    """dense.py:165-179: dropout stays active while `sample` is true."""
+    """dense.py:165-179: dropout stays active while `sample` is true.
+
+    In a BayesianNetworkModule's MC-batched pass on the device (mc_batched = True) every MC sample gets a mask of its own, keyed
+    like a posterior draw (layer.dropout_key; mask contract in include/bnn_hip.h): the first such layer sees the un-replicated
+    batch, runs its GEMM ONCE and fans out S masked copies; later ones run one GEMM over S * B rows.  bf16 compute mode: one
+    bnn_dense_forward_dropout launch (mask in the epilogue); fp32 parity mode and K % 8 != 0: the HIP linear, then bnn_mc_dropout.
+    The serial loop, CPU tensors and sample=False keep the reference's F.dropout."""
 
     def __init__(self, in_features, out_features, bias=True, drop_prob=0.5):
         super().__init__(in_features, out_features, None)
         self.drop_prob = drop_prob
         self.linear = torch.nn.Linear(in_features, out_features, bias)
+        self.dropout_key = None
+        self._dropout_stream = None
+        self._w_bf16 = None
+
+    def _weight_bf16(self):
+        """The weight as the dense kernel's bf16 operand, converted again only when the weight has changed."""
+        w = self.linear.weight
+        tag = (w.data_ptr(), w._version, tuple(w.shape))
+        if self._w_bf16 is None or self._w_bf16[0] != tag:
+            self._w_bf16 = (tag, ops.mean_bf16(w.detach()))
+        return self._w_bf16[1]
 
     def forward(self, x, sample=True):
-        return torch.nn.functional.dropout(self.linear(x), self.drop_prob, sample, False)
+        plan = _mc_dropout_plan(self, x, sample)
+        if plan is None:
+            return torch.nn.functional.dropout(self.linear(x), self.drop_prob, sample, False)
+        ctx, shared = plan
+        ops.check_drop_prob(self.drop_prob)
+        key = _mc_dropout_key(self, ctx)
+        compute = _settings.get_compute()
+        w, b = self.linear.weight, self.linear.bias
+        if x.dim() == 2:
+            wb = self._weight_bf16() if ops.linear_mc_dropout_fusable(x, w, compute) else None
+            return ops.linear_mc_dropout(x, w, b, self.drop_prob, key, shared, compute, w_bf16=wb)
+        # (rows, ..., K): the HIP linear over every position, then the masks over (rows, ... * N)
+        K = x.shape[-1]
+        x2 = x.reshape(-1, K).float()
+        h = ops.linear_plain(x2, w.unsqueeze(0), None if b is None else b.unsqueeze(0), True, compute)
+        return ops.mc_dropout(h.view(*x.shape[:-1], w.shape[0]), self.drop_prob, key, shared)

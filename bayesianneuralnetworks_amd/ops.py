@@ -867,6 +867,165 @@ def linear_plain(x, w, b, shared_x, compute="f32"):
                               shared_x, _compute_code(compute))
 
 
+# --------------------------------------------------------------------------- MC dropout
+def check_drop_prob(p):
+    """F.dropout's argument check (same ValueError)."""
+    if not (0.0 <= p <= 1.0):
+        raise ValueError("dropout probability has to be between 0 and 1, but got {}".format(p))
+
+
+def _drop_rows(y, S, shared):
+    """(rows per sample, features per row) of an MC-dropout operand: y (B, ...) shared, or (S * B, ...) stacked."""
+    if y.dim() < 2:
+        raise BnnHipError("mc_dropout: the input needs a batch dimension and features")
+    R = y.shape[0] if shared else y.shape[0] // S
+    if not shared and R * S != y.shape[0]:
+        raise BnnHipError("mc_dropout: %d rows are not %d samples of equal batches" % (y.shape[0], S))
+    F = 1
+    for d in y.shape[1:]:
+        F *= d
+    return R, F
+
+
+def _mc_dropout_bwd_raw(gy, R, F, p, key, shared):
+    """mask (.) gy / (1 - p) for gy (S * R, ...) fp32 -> same shape, or (R, ...) summed over the samples (shared)."""
+    S = key.nsamples
+    gy = gy.contiguous().float()
+    gx = torch.empty(((R,) if shared else (S * R,)) + tuple(gy.shape[1:]), dtype=torch.float32, device=gy.device)
+    r = _rng_struct(key, gy.device)
+    check(_lib.load().bnn_mc_dropout_backward(ptr(gy), R * F, ptr(gx), R * F, R, F, S, float(p), 1 if shared else 0,
+                                              ctypes.byref(r), stream_ptr(gy.device)), "bnn_mc_dropout_backward")
+    return gx
+
+
+class _McDropout(torch.autograd.Function):
+    """MC dropout under the mask contract (include/bnn_hip.h), F.dropout(y, p, True) of pytorch_bayesian/nn/dense.py:174-179 and
+    nn/conv.py:277-326 with the keyed mask of every MC sample: bnn_mc_dropout forward, bnn_mc_dropout_backward backward."""
+
+    @staticmethod
+    def forward(ctx, y, p, key, shared):
+        require_cuda_act(y, "y")
+        S = key.nsamples
+        R, F = _drop_rows(y, S, shared)
+        out = torch.empty((S * R,) + tuple(y.shape[1:]), dtype=y.dtype, device=y.device)
+        r = _rng_struct(key, y.device)
+        dt = _lib.BF16 if y.dtype == torch.bfloat16 else _lib.F32
+        check(_lib.load().bnn_mc_dropout(ptr(y), 0 if shared else R * F, ptr(out), R * F, R, F, S, float(p), dt,
+                                         ctypes.byref(r), stream_ptr(y.device)), "bnn_mc_dropout")
+        ctx.p, ctx.key, ctx.shared, ctx.R, ctx.F, ctx.dtype = p, key, shared, R, F, y.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        g = _mc_dropout_bwd_raw(gy, ctx.R, ctx.F, ctx.p, ctx.key, ctx.shared)
+        return g.to(ctx.dtype), None, None, None
+
+
+def mc_dropout(y, p, key, shared):
+    """Masks of the key's `nsamples` MC samples (key.sample0 + s) on y: shared -- y (B, ...) computed once for every sample
+    -> (S * B, ...) fanned out; else y (S * B, ...), sample s = row // B -> (S * B, ...).  fp32 or bf16.  The mask depends on
+    (sample, row within the sample, flattened feature) only."""
+    check_drop_prob(p)
+    return _McDropout.apply(y.contiguous(), float(p), key, bool(shared))
+
+
+def mean_bf16(w):
+    """The fp32 weight (N, K) as the dense kernel's operand: (1, N, roundup(K, 64)) bf16 zero-padded (bnn_draw_multi kind 1)."""
+    require_cuda_f32(w, "weight")
+    N, K = w.shape
+    kp = _pad64(K)
+    out = torch.empty((1, N, kp), dtype=torch.bfloat16, device=w.device)
+    arr = (_lib.DrawTensor * 1)()
+    t = arr[0]
+    t.mu, t.rho, t.rows, t.cols = w.data_ptr(), w.data_ptr(), N, K
+    t.out, t.ld, t.out_sample_stride, t.out_dtype = out.data_ptr(), kp, N * kp, _lib.BF16
+    t.kind, t.taps = 1, 0
+    check(_lib.load().bnn_draw_multi(arr, 1, 1, None, 0, None, stream_ptr(w.device)), "bnn_draw_multi")
+    return out
+
+
+def linear_mc_dropout_fusable(x, w, compute):
+    """bf16 mode, and a shape the dense kernel takes (K % 8 == 0: whole 16-B rows of bf16)."""
+    return _compute_code(compute) == _lib.COMPUTE_BF16 and w.dim() == 2 and w.shape[1] % 8 == 0 and x.dim() == 2
+
+
+class _LinearMcDropout(torch.autograd.Function):
+    """F.dropout(F.linear(x, w, b), p, True) for every MC sample in ONE bnn_dense_forward_dropout launch (bf16 operands, fp32
+    accumulate and output): the mask is applied in the GEMM's epilogue.  (x arrives fp32 and is cast to bf16 by a torch op first:
+    one pass over the layer's input that bnn_launch_count does not see.)  shared: x (B, K) is the same for every sample -- the
+    GEMM runs once and the epilogue stores S masked copies.  Backward: the masked gradient (summed over the samples first when
+    shared), then ONE contraction over the rows (bnn_linear_backward_input / _weight, bnn_colsum) in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, p, key, shared, w_bf16):
+        require_cuda_f32(x, "x")
+        require_cuda_f32(w, "weight")
+        S = key.nsamples
+        N, K = w.shape
+        if x.shape[-1] != K:
+            raise BnnHipError("linear: input has %d features, weight expects %d" % (x.shape[-1], K))
+        B = x.shape[0] if shared else x.shape[0] // S
+        if w_bf16 is None:
+            w_bf16 = mean_bf16(w)
+        kp = w_bf16.shape[-1]
+        xb = x.to(torch.bfloat16).contiguous()
+        if b is not None:
+            require_cuda_f32(b, "bias")
+        y = torch.empty((S * B, N), dtype=torch.float32, device=x.device)
+        r = _rng_struct(key, x.device)
+        check(_lib.load().bnn_dense_forward_dropout(ptr(xb), 0 if shared else B * K, K, ptr(w_bf16), 0, kp, ptr(b), 0,
+                                                    ptr(y), B * N, N, B, N, K, S, 0, float(p), ctypes.byref(r),
+                                                    stream_ptr(x.device)), "bnn_dense_forward_dropout")
+        ctx.save_for_backward(x, w)
+        ctx.p, ctx.key, ctx.shared, ctx.B, ctx.has_b = p, key, shared, B, b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        N, K = w.shape
+        g = _mc_dropout_bwd_raw(gy, ctx.B, N, ctx.p, ctx.key, ctx.shared)       # (B or S * B, N): one contraction below
+        return _plain_linear_bwd(ctx, x, w, g) + (None, None, None, None)
+
+
+def _plain_linear_bwd(ctx, x, w, g):
+    """(gx, gw, gb) of y = x w^T + b for ONE weight over all rows of x (M, K) / g (M, N), fp32."""
+    N, K = w.shape
+    M = x.shape[0]
+    lib = _lib.load()
+    gx = gw = gb = None
+    g3 = g.view(1, M, N)
+    if ctx.needs_input_grad[0]:
+        gx = _dgrad_plain_raw(g3, w.view(1, N, K), torch.float32).view(M, K)
+    if ctx.needs_input_grad[1]:
+        gw = torch.empty_like(w)
+        check(lib.bnn_linear_backward_weight(ptr(x), M * K, K, ptr(g), M * N, N, ptr(gw), N * K, M, N, K, 1,
+                                             _lib.COMPUTE_F32, 0, 0, stream_ptr(g.device)), "bnn_linear_backward_weight")
+    if ctx.has_b and ctx.needs_input_grad[2]:
+        gb = _colsum_raw(g3).view(N)
+    return gx, gw, gb
+
+
+def linear_mc_dropout(x, w, b, p, key, shared, compute="f32", w_bf16=None):
+    """MCDropoutLinear on the MC-batched path: F.dropout(F.linear(x, w, b), p, True) with the keyed mask of each of the key's
+    nsamples samples.  shared: x (B, K) -> (S * B, N) fanned out; else x (S * B, K), sample s = row // B -> (S * B, N).
+      bf16 mode, K % 8 == 0: ONE fused launch (bnn_dense_forward_dropout; w_bf16: the weight as mean_bf16 returns it, drawn
+                             here when None);
+      otherwise (the fp32 parity mode, K % 8 != 0): the HIP linear (bnn_linear_forward) once over all rows, then bnn_mc_dropout."""
+    check_drop_prob(p)
+    x = x.contiguous()
+    w = w.contiguous()
+    b = None if b is None else b.contiguous()
+    S = key.nsamples
+    if linear_mc_dropout_fusable(x, w, compute):
+        return _LinearMcDropout.apply(x.float() if x.dtype != torch.float32 else x, w, b, float(p), key, bool(shared), w_bf16)
+    if x.dim() != 2:
+        raise BnnHipError("linear_mc_dropout: x must be (rows, features)")
+    M = x.shape[0]
+    h = linear_plain(x.float(), w.unsqueeze(0), None if b is None else b.unsqueeze(0), True, compute)     # (1, M, N)
+    return mc_dropout(h.view(M, -1), p, key, shared)
+
+
 # --------------------------------------------------------------------------- K2 conv2d
 def _conv_shape(x_shape, w_shape, stride, padding, dilation, groups):
     sh = Conv2dShape()

@@ -39,6 +39,20 @@
  *         z_even = r(ua) cos(2 pi ub), z_odd = r(ua) sin(2 pi ub);  |eps| <= r(2^-17) = 4.86.
  *       Philox4x32-7 is the 7-round member of the same family (Random123's kat_vectors hold its known answers, checked in
  *       tests/test_oracle_golden.py); CPU twin: orc_eps_fill_gen.
+ *
+ * Dropout-mask contract (MC dropout on the MC-batched path: bnn_mc_dropout, bnn_dense_forward_dropout, their backward)
+ *   A mask is a keyed draw like eps, on the same bnn_rng_t fields -- seed, stream, sample, epoch_host, epoch_dev, generator -- from the
+ *   UNIFORMS above, before Box-Muller.  Element index e = r * F + f: row r within the sample, F features per row (N of a
+ *   linear, C * H * W of a conv).
+ *     BNN_GEN_PHILOX10_U24: u = word e % 4 of block e / 4 (the counter above, block = e / 4), u = ((x >> 8) + 0.5) * 2^-24
+ *                           rounded once to fp32 (it can round up to 1.0);
+ *     BNN_GEN_PHILOX7_U16:  word k of block e / 8: its low half for element 8 (e / 8) + 2 k, its high half for + 2 k + 1,
+ *                           u = (h + 0.5) * 2^-16.
+ *   The element is DROPPED iff u < p (p as fp32), or p == 1 (every element).  A kept element is multiplied by
+ *   scale = 1 / (1 - p), computed in fp32: y = x * scale, one rounding.  p = 0 is the identity.
+ *   The mask depends only on the key and (sample, r, f): not on tiling, grid, fusion or dtype -- every kernel that applies or
+ *   re-creates it uses one device function (drop_u4), so the fused and the standalone mask are the same bit for bit.
+ *   rows * F < 2^32 per sample.  CPU twin: tests/test_mc_dropout.py (mask_twin), on the oracle's Philox.
  */
 #ifndef BNN_HIP_H
 #define BNN_HIP_H
@@ -263,6 +277,22 @@ int bnn_dense_forward(const void *x, int64_t x_sample_stride, int64_t ldx,
                       const float *b, int64_t b_sample_stride,
                       void *y, int64_t y_sample_stride, int64_t ldy,
                       int64_t M, int64_t N, int64_t K, int nsamples, int flags, void *stream);
+/* bnn_dense_forward with MC dropout in the epilogue: y[s] = mask_s (.) act(x[s] . w[s]^T + b[s]) * 1 / (1 - p) -- bias, activation,
+ * then mask and scale, then the store (dropout-mask contract above, F = N, sample rng->sample0 + s).  Same operands, strides and
+ * flags as bnn_dense_forward.
+ *   FAN-OUT: x, w and b all shared (x_sample_stride = w_sample_stride = 0, b_sample_stride = 0 or b NULL) -- every output tile is
+ *   computed ONCE and its epilogue stores the nsamples masked copies (the first MC-dropout layer of a net: until the first mask
+ *   every sample computes the same thing).  Otherwise one launch over the samples (w_sample_stride = 0 for shared weights).
+ *   Fused (one launch) when N % 4 == 0 and N > 16, on the 256 x 80, 128 x 160, 64 x 160 and 32 x 160 tiles, fp32 or bf16 output
+ *   (a layer the plain launch would give the 256 x 128 tile takes 128 x 160).  Otherwise -- the narrow N <= 16 kernel, or N % 4 != 0
+ *   -- the plain kernel stores and the mask launch of bnn_mc_dropout runs after it, in place (two launches, the same values).
+ *   nsamples <= 65535, 0 <= p <= 1 (BNN_E_RANGE), M * N < 2^32.
+ * replaces  F.dropout(self.linear(x), self.drop_prob, sample, False)  pytorch_bayesian/nn/dense.py:174-179 */
+int bnn_dense_forward_dropout(const void *x, int64_t x_sample_stride, int64_t ldx,
+                              const void *w, int64_t w_sample_stride, int64_t ldw,
+                              const float *b, int64_t b_sample_stride,
+                              void *y, int64_t y_sample_stride, int64_t ldy,
+                              int64_t M, int64_t N, int64_t K, int nsamples, int flags, float p, const bnn_rng_t *rng, void *stream);
 /* A hidden layer AND the classifier head behind it in ONE launch (bf16 compute mode, inference): the hidden layer's output
  * act(x[s] w[s]^T + b[s]) is never stored -- every wave of the GEMM rounds its tile to bf16 (exactly what a stored bf16 hidden
  * activation holds) and contracts it with the matching columns of the head's drawn weights w_head (S x n_head x ldwh bf16, rows
@@ -538,6 +568,21 @@ int bnn_softmax_xent(const float *logits, const int64_t *target, int64_t rows, i
  *   out[i] = log N(0; mu[i], sigma(rho[i])) = -mu^2 / (2 sigma^2) - ln sigma - ln sqrt(2 pi)
  * (the top-k selection and the masked assignment of prune.py:12-17 stay torch ops on the device). */
 int bnn_prune_score(const float *mu, const float *rho, float *out, int64_t n, void *stream);
+
+/* ---- MC dropout (dropout-mask contract above) -------------------------------------
+ * replaces  F.dropout(self.linear(x), p, sample, False)  pytorch_bayesian/nn/dense.py:174-179
+ *           F.dropout(self.conv(x), p, sample, False)    pytorch_bayesian/nn/conv.py:277-326 (MCDropoutConv{1,2,3}d)
+ *   y[s][r][f] = keep(s, r, f) ? x[s | 0][r][f] * 1 / (1 - p) : 0,   s < nsamples
+ * x: (S, rows, F) at x_sample_stride elements, or SHARED (x_sample_stride = 0: the fan-out of a layer that ran once on the
+ * un-replicated batch); y: (S, rows, F) at y_sample_stride.  Contiguous rows.  dtype BNN_F32 or BNN_BF16 (x and y alike; the
+ * scaling is fp32).  y may alias x (in place; with x shared, y[0] may be x).  Graph-capturable, no allocation. */
+int bnn_mc_dropout(const void *x, int64_t x_sample_stride, void *y, int64_t y_sample_stride, int64_t rows, int64_t features,
+                   int nsamples, float p, int dtype, const bnn_rng_t *rng, void *stream);
+/* Backward, the mask re-created from the key (never stored): gx[s] = mask_s (.) gy[s] * 1 / (1 - p), fp32.
+ * sum_samples != 0 (the input was shared): gx (rows, F) = sum over s = 0 .. nsamples - 1 in that order, fp32 -- bitwise
+ * reproducible. */
+int bnn_mc_dropout_backward(const float *gy, int64_t gy_sample_stride, float *gx, int64_t gx_sample_stride, int64_t rows,
+                            int64_t features, int nsamples, float p, int sum_samples, const bnn_rng_t *rng, void *stream);
 
 /* ---- MC reduction ----------------------------------------------------------
  * replaces  torch.stack(preds).mean(0)   examples/MNIST/uncertainty.py:50
