@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BNN_HIP_LIB") or os.path.join(_HERE, "libbnn_hip.so")
 
 F32, BF16, BF16X3 = 0, 1, 2
+DRAW_FLIPOUT = 16         # bnn_draw_tensor_t.kind of a Flipout draw (BNN_DRAW_FLIPOUT)
 COMPUTE_F32, COMPUTE_BF16 = 0, 1
 FLAG_RELU = 1
 FLAG_X_BF16 = 2
@@ -111,6 +112,8 @@ SIGNATURES = {
     "bnn_dense_forward_dropout": (_int, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _int, _int,
                                          _f, _rngp, _p]),
     "bnn_mc_dropout": (_int, [_p, _i64, _p, _i64, _i64, _i64, _int, _f, _int, _rngp, _p]),
+    "bnn_flipout_signs": (_int, [_p, _i64, _i64, _i64, _int, _rngp, _p]),
+    "bnn_flipout_weight_backward": (_int, [_p, _i64, _p, _p, _p, _i64, _i64, _int, _rngp, _p]),
     "bnn_mc_dropout_backward": (_int, [_p, _i64, _p, _i64, _i64, _i64, _int, _f, _int, _rngp, _p]),
     "bnn_dense_head_parts": (_int, [_i64, _i64, _int]),
     "bnn_dense_forward_head": (_int, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, _i64, _p, _i64, _i64,
@@ -124,6 +127,7 @@ SIGNATURES = {
     "bnn_conv2d_dense_forward_x3": (_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, ctypes.POINTER(Conv2dShape), _int, _int, _p]),
     "bnn_conv2d_dense_forward": (_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, ctypes.POINTER(Conv2dShape), _int, _int, _p]),
     "bnn_conv2d_flipout_forward": (_int, [_p, _p, _i64, _p, _p, _p, ctypes.POINTER(Conv2dShape), _int, _p]),
+    "bnn_conv2d_flipout_forward_mc": (_int, [_p, _i64, _p, _i64, _p, _i64, ctypes.POINTER(Conv2dShape), _int, _rngp, _int, _p]),
     "bnn_conv2d_flipout_forward_x3": (_int, [_p, _p, _i64, _i64, _p, _p, _p, ctypes.POINTER(Conv2dShape), _int, _p]),
     "bnn_linear_forward": (_int, [_p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64,
                                   _int, _int, _int, _p]),

@@ -308,6 +308,47 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
     char *const dst0 = t_out + orow * esz;
     const int64_t sbytes = t_stride * esz;
     const int64_t pbytes = sbytes * (t_kind == 3 ? 1 : L.nsamples);     // (three-plane output; kind 3: one copy, planes out_sample_stride apart)
+    if (t_kind == BNN_DRAW_FLIPOUT) {
+        // Flipout (a linear weight, fp32 or bf16, no taps): w = mu + sigma R[row] S[c], the signs of the layer's ONE row of
+        // rows + cols uniforms (sign contract).  A block of its own with a sample loop that is NOT unrolled: its sign blocks
+        // stay out of the unrolled loop below, whose register budget every other draw of the launch pays for.
+        float m[8], sg[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const bool v = c0 + j < t_cols;
+            m[j] = v ? t_mu[(int64_t)row * t_cols + c0 + j] : 0.f;
+            sg[j] = v ? sigma_draw(t_rho[(int64_t)row * t_cols + c0 + j]) : 0.f;
+        }
+        const uint32_t edev = rng_epoch_dev(rng);
+        const uint32_t e0 = (uint32_t)t_rows + (uint32_t)c0, q0 = e0 >> 2, off = e0 & 3u;     // S[c0] is uniform e0
+#pragma unroll 1
+        for (int s = s_lo; s < s_hi; s += s_step) {
+            const uint32_t sample = rng.sample0 + (uint32_t)s;
+            const float r = flip_sign(drop_u1(rng, edev, (uint32_t)row, sample));
+            // S[c0 .. c0 + 7] = uniforms off .. off + 7 of the three quads from q0
+            const float4 ua = drop_u4(rng, edev, q0, sample), ub = drop_u4(rng, edev, q0 + 1u, sample), uc = drop_u4(rng, edev, q0 + 2u, sample);
+            const float u[12] = {ua.x, ua.y, ua.z, ua.w, ub.x, ub.y, ub.z, ub.w, uc.x, uc.y, uc.z, uc.w};
+            float w[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float uj = off == 0u ? u[j] : off == 1u ? u[j + 1] : off == 2u ? u[j + 2] : u[j + 3];
+                w[j] = fmaf(sg[j], r * flip_sign(uj), m[j]);
+            }
+            char *dst = dst0 + (int64_t)s * sbytes;
+            if (t_bf16) {
+                // (bf16 rows are whole 16-B chunks: ld % 8 == 0, 16-B aligned output; zeros beyond cols)
+                uint4 o;
+                o.x = pack_bf16x2(w[0], w[1]); o.y = pack_bf16x2(w[2], w[3]);
+                o.z = pack_bf16x2(w[4], w[5]); o.w = pack_bf16x2(w[6], w[7]);
+                *reinterpret_cast<uint4 *>(dst) = o;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (c0 + j < t_ld) reinterpret_cast<float *>(dst)[j] = w[j];
+            }
+        }
+        return;
+    }
     // ---- the regular case, where the time goes: a weight matrix drawn as bf16 (or as three bf16 planes) whose rows are whole,
     // 16-B aligned 8-column groups.  What decides the code path is wave-uniform (read off the tensor's descriptor), the sample
     // loop is straight-line code, and the groups in the zero padding run the same loop with mean = sigma = 0 (a few % of wasted
@@ -1177,6 +1218,9 @@ struct ConvParams {
     // resident images are split into three planes in LDS, and every 64-k block is walked on the six plane pairs of
     // k_dense_bf16's parity mode -- the five small pairs for every block first, then (h, h) over all of K
     int64_t w_plane_stride;
+    // keyed Flipout (NS > 0 instantiations, bnn_conv2d_flipout_forward_mc): the signs of MC sample sample0 + s come from this key
+    // (sign contract, conv layout) instead of sgn_in / sgn_out; NS samples per workgroup share the mean contraction
+    RngDev rng;
 };
 
 constexpr int kConvLds = 78 * 1024;      // two workgroups per CU (O = 64)
@@ -1185,10 +1229,19 @@ constexpr int kConvLdsBig = 136 * 1024;  // one workgroup per CU with a 6-stage 
 // FLIP: the Flipout estimator in ONE launch -- the tile's columns are [O means | O stddevs] (TN = 2 O / 16), both
 // contractions share the A fragment: the second one takes it with the sign bits of S flipped in (a 16-B mask per
 // (image, 8-channel chunk), built in LDS next to the images), and R multiplies its accumulator in the epilogue.
-template <int TN, int ST, int LDSB, bool FLIP = false, bool X3 = false>
+// NS > 0 (keyed Flipout, the MC-batched path): a workgroup runs NS MC samples of one image tile.  The signs are made from the key
+// in phase 0 -- S as the samples' 16-B masks next to the images, R as +-1 floats at the top of the LDS block -- the mean
+// columns are contracted ONCE per tile and every sample adds only its stddev contraction (the A fragment XOR its mask):
+// (1 + NS) O instead of 2 NS O columns of MFMA work.  Accumulators: [mean | stddev of sample 0 | ... | of sample NS - 1].
+template <int TN, int ST, int LDSB, bool FLIP = false, bool X3 = false, int NS = 0>
 __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(const ConvParams p)
 {
     // (FLIP && X3: the Flipout launch of the fp32 parity mode -- the sign mask flips every plane of the A fragment alike)
+    constexpr bool KEYED = NS > 0;
+    static_assert(!KEYED || (FLIP && !X3), "keyed signs: the bf16 Flipout launch");
+    constexpr int NSX = KEYED ? NS : 1;                         // sign masks per image (samples of the workgroup)
+    constexpr int TO = FLIP ? TN / 2 : TN;                      // 16-column blocks of the output channels
+    constexpr int NACC = FLIP ? TO * (1 + NSX) : TN;            // accumulator blocks per 16-row block
     constexpr int NWV = 4, TM = 2, WM = 32, BN = 16 * TN;
     constexpr int B_TOTAL = BN / 8, NBP = B_TOTAL / NWV;        // B pieces per loader per stage (TN = 4: 2, TN = 8: 4)
     constexpr int B_STAGE = BN * 128;
@@ -1197,7 +1250,8 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
     __shared__ __attribute__((aligned(16))) char lds[LDSB];
     const int P = p.OH * p.OW, HW = p.H * p.Wd;
     const int CPX = p.C >> 3;                                   // 16-B chunks per pixel
-    const int mask_region = FLIP ? p.IMG * CPX * 16 : 0;        // sign masks [image][chunk]
+    const int mask_stride = FLIP ? p.IMG * CPX * 16 : 0;        // sign masks [sample][image][chunk]
+    const int mask_region = mask_stride * NSX;
     const int img_region = p.IMG * p.img_bytes;        // one plane of this tile's images
     constexpr int NPL = X3 ? 3 : 1;
     char *masks = lds + NPL * img_region;
@@ -1205,11 +1259,14 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
     constexpr int NOUT = FLIP ? BN / 2 : BN;                    // output channels of the tile
 
     int s, t;
+    const int SG = KEYED ? (p.S + NSX - 1) / NSX : p.S;         // sample groups
     {
         const int L = (int)blockIdx.x;
-        if (p.S % 8 == 0) { const int idx = L >> 3; s = (L & 7) + 8 * (idx / p.ntiles); t = idx % p.ntiles; }
+        if (SG % 8 == 0) { const int idx = L >> 3; s = (L & 7) + 8 * (idx / p.ntiles); t = idx % p.ntiles; }
         else { s = L / p.ntiles; t = L % p.ntiles; }
     }
+    if constexpr (KEYED) s *= NSX;                              // the group's first sample
+    const int nvalid = KEYED ? (p.S - s < NSX ? p.S - s : NSX) : 1;
     const int b0 = t * p.IMG;
     const int imgs = (p.B - b0 < p.IMG) ? p.B - b0 : p.IMG;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1260,7 +1317,38 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
         const float *xs = p.X + (int64_t)s * p.x_sample_stride + (int64_t)b0 * p.C * HW;
         const int Q = (HW + 3) >> 2, CH2 = p.C >> 1;
         const int per_img = (p.flags & 1) ? 0 : CH2 * Q;
-        if constexpr (FLIP) {
+        if constexpr (KEYED) {
+            // the samples' signs from the key: masks (bit 15 of element j set where S_s[b][8 chunk + j] = -1) and R_s as floats
+            const uint32_t ed = rng_epoch_dev(p.rng);
+            const uint32_t row_w = (uint32_t)(p.O + p.C);
+            float *rs = reinterpret_cast<float *>(lds + LDSB) - NSX * p.IMG * p.O;
+            for (int i = tid; i < NSX * imgs * CPX; i += 512) {
+                const int n = i / (imgs * CPX), r = i - n * imgs * CPX, il = r / CPX, ch = r - il * CPX;
+                uint32_t w4[4] = {0u, 0u, 0u, 0u};
+                if (n < nvalid) {
+                    const uint32_t smp = p.rng.sample0 + (uint32_t)(s + n);
+                    const uint32_t e0 = (uint32_t)(b0 + il) * row_w + (uint32_t)p.O + 8u * (uint32_t)ch;      // a multiple of 8
+                    const float4 ua = drop_u4(p.rng, ed, e0 >> 2, smp), ub = drop_u4(p.rng, ed, (e0 >> 2) + 1u, smp);
+                    const float u[8] = {ua.x, ua.y, ua.z, ua.w, ub.x, ub.y, ub.z, ub.w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        w4[j] = (flip_sign(u[2 * j]) < 0.f ? 0x8000u : 0u) | (flip_sign(u[2 * j + 1]) < 0.f ? 0x80000000u : 0u);
+                }
+                *reinterpret_cast<uint4 *>(masks + n * mask_stride + (il * CPX + ch) * 16) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+            }
+            const int OQ = p.O >> 2;
+            for (int i = tid; i < NSX * imgs * OQ; i += 512) {
+                const int n = i / (imgs * OQ), r = i - n * imgs * OQ, il = r / OQ, q = r - il * OQ;
+                float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
+                if (n < nvalid) {
+                    const uint32_t smp = p.rng.sample0 + (uint32_t)(s + n);
+                    const uint32_t e0 = (uint32_t)(b0 + il) * row_w + 4u * (uint32_t)q;
+                    const float4 u = drop_u4(p.rng, ed, e0 >> 2, smp);
+                    v = make_float4(flip_sign(u.x), flip_sign(u.y), flip_sign(u.z), flip_sign(u.w));
+                }
+                *reinterpret_cast<float4 *>(rs + (n * p.IMG + il) * p.O + 4 * q) = v;
+            }
+        } else if constexpr (FLIP) {
             // sign masks: bit 15 of element j set where S[b][8 chunk + j] < 0
             for (int i = tid; i < imgs * CPX; i += 512) {
                 const int il = i / CPX, ch = i - il * CPX;
@@ -1322,11 +1410,11 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
         __syncthreads();
     }
 
-    f32x4 acc[TM][TN];
+    f32x4 acc[TM][NACC];
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
-        for (int b = 0; b < TN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < NACC; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int fi = lane & 15, fq = lane >> 4;
 
     const int nk_run = (p.flags & 2) ? 0 : nk;
@@ -1366,7 +1454,7 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
         // step t, as in k_dense_bf16: [reads (t, h1) || MFMAs (t, h0)] [reads done -> barrier t + 1] [reads (t + 1, h0) || MFMAs
         // (t, h1)] -- every group of fragment reads is in flight under the previous group's MFMAs.  (Round 2 read the 2 + TN
         // fragments of a half and then multiplied: at O = 128 a step was 0.61 us for 0.24 us of MFMA issue.)
-        uint4 fa[2][TM], fbr[2][TN], fmk[2][FLIP ? TM : 1];
+        uint4 fa[2][TM], fbr[2][TN], fmk[2][FLIP ? TM * NSX : 1];
         // (tap row, tap column, 64-channel block) of the step whose h0 half is read next: advanced by rd(.., h0), no divisions
         // in the loop; the step's fragment addresses are kept for its h1 half
         int s_kh = 0, s_kw = 0, s_cb = 0, s_stage = 0, cur_cb = 0;
@@ -1405,23 +1493,33 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
                 // chunk (cb 8 + 4 h + fq) ^ swz: h flips bit 2 of the chunk index, i.e. 64 bytes of the address
                 const uint4 v = *reinterpret_cast<const uint4 *>(lds + (h ? (aoff[a] ^ 64) : aoff[a]));
                 fa[buf][a] = okk[a] ? v : make_uint4(0u, 0u, 0u, 0u);
-                if constexpr (FLIP) fmk[buf][a] = *reinterpret_cast<const uint4 *>(masks + mb[a] + (cur_cb * 8 + 4 * h + fq) * 16);
+                if constexpr (FLIP) {
+#pragma unroll
+                    for (int n = 0; n < NSX; ++n)
+                        fmk[buf][n * TM + a] = *reinterpret_cast<const uint4 *>(masks + n * mask_stride + mb[a] + (cur_cb * 8 + 4 * h + fq) * 16);
+                }
             }
         };
         auto mm = [&](auto buf_c) {
             constexpr int buf = decltype(buf_c)::value;
 #pragma unroll
             for (int a = 0; a < TM; ++a) {
-                uint4 afs = fa[buf][a];
-                if constexpr (FLIP) {
-                    const uint4 m = fmk[buf][a];
-                    afs = make_uint4(afs.x ^ m.x, afs.y ^ m.y, afs.z ^ m.z, afs.w ^ m.w);
-                }
+                // the mean columns (all of them without FLIP) on the plain fragment ...
 #pragma unroll
-                for (int b = 0; b < TN; ++b) {
-                    const uint4 av = (FLIP && b >= TN / 2) ? afs : fa[buf][a];
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av),
+                for (int b = 0; b < TO; ++b)
+                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[buf][a]),
                                                                         __builtin_bit_cast(bf16x8, fbr[buf][b]), acc[a][b], 0, 0, 0);
+                if constexpr (FLIP) {
+                    // ... the stddev columns once per sample, on the fragment with that sample's S in its sign bits
+#pragma unroll
+                    for (int n = 0; n < NSX; ++n) {
+                        const uint4 m = fmk[buf][n * TM + a], f = fa[buf][a];
+                        const uint4 afs = make_uint4(f.x ^ m.x, f.y ^ m.y, f.z ^ m.z, f.w ^ m.w);
+#pragma unroll
+                        for (int b = 0; b < TO; ++b)
+                            acc[a][TO + n * TO + b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                                __builtin_bit_cast(bf16x8, afs), __builtin_bit_cast(bf16x8, fbr[buf][TO + b]), acc[a][TO + n * TO + b], 0, 0, 0);
+                    }
                 }
             }
         };
@@ -1451,6 +1549,41 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
     // ---- epilogue: stage the tile as [image][channel][pixel] (its NCHW block is contiguous), then whole 16-B chunks
     __syncthreads();                                    // every wave is done with the images and the weight ring
     float *T = reinterpret_cast<float *>(lds);
+    if constexpr (KEYED) {
+        // one sample after the other through the staging block: mean + R_s (.) stddev contraction of sample s
+        const float *rs = reinterpret_cast<const float *>(lds + LDSB) - NSX * p.IMG * p.O;
+#pragma unroll
+        for (int n = 0; n < NSX; ++n) {
+            if (n >= nvalid) break;
+            if (n > 0) __syncthreads();                 // the previous sample's copy has read the staging block
+            if (wave < NWV) {
+#pragma unroll
+                for (int b = 0; b < TO; ++b) {
+                    const int o = b * 16 + fi;
+#pragma unroll
+                    for (int a = 0; a < TM; ++a) {
+                        const int row0 = wave * WM + a * 16 + fq * 4;
+                        int il = row0 / P, pix = row0 - il * P;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (row0 + r < imgs * P && o < p.O)
+                                T[(il * p.O + o) * P + pix] = fmaf(rs[(n * p.IMG + il) * p.O + o], acc[a][TO + n * TO + b][r], acc[a][b][r]);
+                            if (++pix == P) { pix = 0; ++il; }
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            float *Yt = p.Y + (int64_t)(s + n) * p.y_sample_stride + (int64_t)b0 * p.O * P;
+            const int nn = (p.flags & 4) ? 0 : imgs * p.O * P;
+            if ((nn & 3) == 0 && (reinterpret_cast<uintptr_t>(Yt) & 15u) == 0) {
+                for (int i = tid; i < (nn >> 2); i += 512) reinterpret_cast<uint4 *>(Yt)[i] = reinterpret_cast<const uint4 *>(T)[i];
+            } else {
+                for (int i = tid; i < nn; i += 512) Yt[i] = T[i];
+            }
+        }
+        return;
+    }
     if (wave < NWV) {
         const float *bias = p.bias ? p.bias + (int64_t)s * p.bias_sample_stride : nullptr;
 #pragma unroll
@@ -1750,14 +1883,15 @@ int bnn_draw_multi(const bnn_draw_tensor_t *tensors, int ntensors, int nsamples,
         if (t.ld % 8 != 0 && t.rows > 1) { set_error("%s: tensor %d: ld %% 8 != 0", who, i); return BNN_E_UNSUPPORTED; }
         if (t.out_dtype != BNN_F32 && (!al16(t.out) || t.out_sample_stride % 8 != 0 || t.ld % 8 != 0)) { set_error("%s: tensor %d: bf16 output needs 16-B aligned rows", who, i); return BNN_E_ALIGN; }
         if ((reinterpret_cast<uintptr_t>(t.mu) | reinterpret_cast<uintptr_t>(t.rho) | reinterpret_cast<uintptr_t>(t.out)) & 3u) { set_error("%s: tensor %d: misaligned pointer", who, i); return BNN_E_ALIGN; }
-        const int rc = t.kind == 0 ? check_rng(&t.rng, nsamples) : BNN_OK;
+        const int rc = (t.kind == 0 || t.kind == BNN_DRAW_FLIPOUT) ? check_rng(&t.rng, nsamples) : BNN_OK;
         if (rc) { set_error("%s: tensor %d: bad rng", who, i); return rc; }
         DrawTensorDev &d = L.t[i];
         d.mu = t.mu; d.rho = t.rho; d.out = t.out; d.out_sample_stride = t.out_sample_stride;
         d.rows = (int32_t)t.rows; d.cols = (int32_t)t.cols; d.ld = (int32_t)t.ld; d.bf16 = t.out_dtype == BNN_BF16 ? 1 : t.out_dtype == BNN_BF16X3 ? 2 : 0;
         d.perm_taps = t.taps > 1 ? t.taps : 1;
         d.kind = t.kind;
-        if (t.kind < 0 || t.kind > 3) { set_error("%s: tensor %d: kind must be 0 (draw), 1 (mean), 2 (stddev) or 3 (as it is, once)", who, i); return BNN_E_RANGE; }
+        if ((t.kind < 0 || t.kind > 3) && t.kind != BNN_DRAW_FLIPOUT) { set_error("%s: tensor %d: kind must be 0 (draw), 1 (mean), 2 (stddev), 3 (as it is, once) or BNN_DRAW_FLIPOUT", who, i); return BNN_E_RANGE; }
+        if (t.kind == BNN_DRAW_FLIPOUT && (t.taps > 1 || t.out_dtype == BNN_BF16X3 || t.rows + t.cols > 0xFFFFFFFFll)) { set_error("%s: tensor %d: a Flipout draw is a linear weight (no taps, fp32 or bf16 output, rows + cols < 2^32)", who, i); return BNN_E_SHAPE; }
         if (t.taps > 1 && (t.cols % t.taps != 0 || t.out_dtype == BNN_F32)) { set_error("%s: tensor %d: taps must divide cols (bf16 or three-plane output)", who, i); return BNN_E_SHAPE; }
         d.first_item = (int32_t)items;
         d.rng = make_rng(&t.rng);
@@ -1941,11 +2075,12 @@ int bnn_transpose_bf16(const void *in, int64_t in_batch_stride, int64_t ld_in, v
 static int conv_dense_launch(const float *x, int64_t x_sample_stride, const void *w, int64_t w_sample_stride, int64_t ldw,
                              const float *b, int64_t b_sample_stride, const float *sgn_in, const float *sgn_out,
                              float *y, int64_t y_sample_stride, const bnn_conv2d_shape_t *sh, int nsamples, int flags,
-                             void *stream, const char *who, int64_t w_plane_stride = 0)
+                             void *stream, const char *who, int64_t w_plane_stride = 0, const bnn_rng_t *rng = nullptr)
 {
-    const bool flip = sgn_in != nullptr;
+    const bool keyed = rng != nullptr;                  // Flipout with signs from the key (bnn_conv2d_flipout_forward_mc)
+    const bool flip = sgn_in != nullptr || keyed;
     const bool x3 = w_plane_stride != 0;
-    if (!x || !w || !y || !sh || (flip && !sgn_out)) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if (!x || !w || !y || !sh || (flip && !keyed && !sgn_out)) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
     if (sh->B < 1 || sh->C < 1 || sh->H < 1 || sh->W < 1 || sh->O < 1 || sh->KH < 1 || sh->KW < 1 || sh->stride_h < 1 ||
         sh->stride_w < 1 || sh->pad_h < 0 || sh->pad_w < 0 || sh->dil_h < 1 || sh->dil_w < 1 || nsamples < 1) { set_error("%s: bad shape", who); return BNN_E_SHAPE; }
     if (flags != 0) { set_error("%s: unknown flags", who); return BNN_E_UNSUPPORTED; }
@@ -1959,16 +2094,24 @@ static int conv_dense_launch(const float *x, int64_t x_sample_stride, const void
                     ldw >= K && ldw % 8 == 0 && w_sample_stride % 8 == 0 && al16(w) &&
                     (reinterpret_cast<uintptr_t>(x) & 3u) == 0 && (reinterpret_cast<uintptr_t>(y) & 3u) == 0;
     if (!ok) { set_error("%s: needs groups = 1, C = 64 or a multiple of 128, O = 64 or 128 (Flipout: 32 or 64), tap-major bf16 weights with 16-B aligned rows", who); return BNN_E_UNSUPPORTED; }
+    // keyed: samples per workgroup (the mean contraction is shared by them; a per-sample input takes one)
+    // (2 O = 128 keeps two: with four its 40 accumulator blocks + the samples' masks spill, 192 VGPRs per lane)
+    const int ns = !keyed ? 0 : (x_sample_stride != 0 || nsamples == 1) ? 1 : (nsamples == 2 || bn == 128) ? 2 : 4;
+    if (keyed) {
+        const int rc = check_flip_args(who, sh->B, (int64_t)sh->O + sh->C, nsamples, rng);
+        if (rc) return rc;
+    }
     ConvParams p{};
-    const int64_t img_bytes = (int64_t)sh->H * sh->W * sh->C * 2 + (flip ? (sh->C / 8) * 16 : 0);   // + the image's sign masks
+    const int64_t img_bytes = (int64_t)sh->H * sh->W * sh->C * 2 + (flip ? (sh->C / 8) * 16 * (keyed ? ns : 1) : 0);   // + sign masks
+    const int64_t rsign = keyed ? (int64_t)ns * sh->O * 4 : 0;      // keyed: an image's R_s of the workgroup's samples, fp32
     const int P = OH * OW;
     if (x3 && (w_plane_stride % 8 != 0 || w_plane_stride < (int64_t)bn * ldw)) { set_error("%s: bad plane stride", who); return BNN_E_SHAPE; }
     // ring stages (8 KB / 16 KB each); three-plane operands: the big block for both widths (three image planes), 4 / 3 stages
     const int st = bn == 64 ? 4 : (x3 ? 3 : flip ? 4 : 6);
-    const int64_t lds_block = (bn == 64 && !x3) ? kConvLds : kConvLdsBig;
+    const int64_t lds_block = (bn == 64 && !x3 && !keyed) ? kConvLds : kConvLdsBig;
     const int64_t ring = (int64_t)st * bn * 128;
     int img = 128 / P;                                  // rows per workgroup <= 128
-    while (img > 0 && (img * img_bytes * (x3 ? 3 : 1) + ring > lds_block || (int64_t)img * sh->O * P * 4 > lds_block)) --img;
+    while (img > 0 && (img * (img_bytes * (x3 ? 3 : 1) + rsign) + ring > lds_block || (int64_t)img * (sh->O * P * 4 + rsign) > lds_block)) --img;
     if (img > sh->B) img = sh->B;
     if (img < 1 || (int64_t)bn * ldw * 2 >= ((int64_t)1 << 32)) { set_error("%s: one image (%lld B bf16) + the weight ring do not fit the LDS block, or more than 128 output pixels per image", who, (long long)img_bytes); return BNN_E_UNSUPPORTED; }
     p.X = x; p.x_sample_stride = x_sample_stride;
@@ -1983,11 +2126,21 @@ static int conv_dense_launch(const float *x, int64_t x_sample_stride, const void
     p.flags = cdiag;
     p.OH = OH; p.OW = OW; p.S = nsamples; p.IMG = img; p.ntiles = (sh->B + img - 1) / img;
     p.img_bytes = (int32_t)((int64_t)sh->H * sh->W * sh->C * 2);
-    const int64_t grid = (int64_t)p.ntiles * nsamples;
+    if (keyed) p.rng = make_rng(rng);
+    const int64_t grid = (int64_t)p.ntiles * (keyed ? (nsamples + ns - 1) / ns : nsamples);
     if (grid > 0x7FFFFFFF) { set_error("%s: grid too large", who); return BNN_E_RANGE; }
     const dim3 g((unsigned)grid), blk(512);
     hipStream_t stq = (hipStream_t)stream;
-    if (x3 && flip) {
+    if (keyed) {
+        if (bn == 64) {
+            if (ns == 1) hipLaunchKernelGGL((k_conv_bf16<4, 4, kConvLdsBig, true, false, 1>), g, blk, 0, stq, p);
+            else if (ns == 2) hipLaunchKernelGGL((k_conv_bf16<4, 4, kConvLdsBig, true, false, 2>), g, blk, 0, stq, p);
+            else hipLaunchKernelGGL((k_conv_bf16<4, 4, kConvLdsBig, true, false, 4>), g, blk, 0, stq, p);
+        } else {
+            if (ns == 1) hipLaunchKernelGGL((k_conv_bf16<8, 4, kConvLdsBig, true, false, 1>), g, blk, 0, stq, p);
+            else hipLaunchKernelGGL((k_conv_bf16<8, 4, kConvLdsBig, true, false, 2>), g, blk, 0, stq, p);
+        }
+    } else if (x3 && flip) {
         if (bn == 64) hipLaunchKernelGGL((k_conv_bf16<4, 4, kConvLdsBig, true, true>), g, blk, 0, stq, p);
         else hipLaunchKernelGGL((k_conv_bf16<8, 3, kConvLdsBig, true, true>), g, blk, 0, stq, p);
     } else if (x3) {
@@ -2031,6 +2184,22 @@ int bnn_conv2d_flipout_forward(const float *x, const void *w, int64_t ldw, const
 {
     if (!sign_in || !sign_out) { set_error("bnn_conv2d_flipout_forward: NULL sign tensor"); return BNN_E_NULL; }
     return conv_dense_launch(x, 0, w, 0, ldw, nullptr, 0, sign_in, sign_out, y, 0, sh, 1, flags, stream, "bnn_conv2d_flipout_forward");
+}
+
+int bnn_conv2d_flipout_forward_mc(const float *x, int64_t x_sample_stride, const void *w, int64_t ldw, float *y,
+                                  int64_t y_sample_stride, const bnn_conv2d_shape_t *sh, int nsamples, const bnn_rng_t *rng,
+                                  int flags, void *stream)
+{
+    const char *who = "bnn_conv2d_flipout_forward_mc";
+    if (!rng) { set_error("%s: NULL rng", who); return BNN_E_NULL; }
+    if (!sh) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    const int64_t n_img = (int64_t)sh->B * sh->C * sh->H * sh->W;
+    if (x_sample_stride < 0 || (x_sample_stride != 0 && nsamples > 1 && x_sample_stride < n_img) || y_sample_stride < 0) {
+        set_error("%s: bad sample stride", who);
+        return BNN_E_SHAPE;
+    }
+    return conv_dense_launch(x, x_sample_stride, w, 0, ldw, nullptr, 0, nullptr, nullptr, y, y_sample_stride, sh, nsamples, flags, stream,
+                             who, 0, rng);
 }
 
 int bnn_conv2d_flipout_forward_x3(const float *x, const void *w, int64_t w_plane_stride, int64_t ldw, const float *sign_in,

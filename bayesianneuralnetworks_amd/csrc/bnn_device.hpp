@@ -18,6 +18,8 @@ int check_dropout_args(const char *who, int64_t rows, int64_t F, int nsamples, f
 int mc_dropout_launch(const char *who, const void *x, int64_t x_sample_stride, int64_t ldx, void *y, int64_t y_sample_stride,
                       int64_t ldy, int64_t rows, int64_t F, int nsamples, bool fan, float p, int dtype, const bnn_rng_t *rng,
                       hipStream_t st);
+// bnn_flipout.hip: the sign entries' shared argument checks
+int check_flip_args(const char *who, int64_t rows, int64_t width, int nsamples, const bnn_rng_t *rng);
 
 // Device view of a bnn_rng_t.
 struct RngDev {
@@ -290,6 +292,14 @@ __device__ __forceinline__ float drop_u1(const RngDev &r, uint32_t epoch_dev, ui
 __device__ __forceinline__ float drop_apply(float v, float u, float p, float scale)
 {
     return (u < p || scale == 0.f) ? 0.f : v * scale;
+}
+
+// ----- Flipout signs (RNG contract, sign part: include/bnn_hip.h) -------------------------------------------------------
+// The sign of one uniform of the mask stream: -1 iff u < 0.5 ((rand - .5).sign() of conv.py:154-161 / dense.py:70-75), +1
+// otherwise -- never 0.  Every kernel that makes or re-creates a Flipout sign calls THIS function on drop_u4 / drop_u1.
+__device__ __forceinline__ float flip_sign(float u)
+{
+    return u < 0.5f ? -1.f : 1.f;
 }
 
 // sigma = 1e-10 + softplus(rho), torch semantics (beta 1, threshold 20), for the DRAW:

@@ -150,12 +150,20 @@ class BayesianNetworkModule(Module):
         records them -- exactly as its own sample() would -- when it uses the entry.  Returns the layers it drew for."""
         from .. import ops
         from . import _settings
-        from .dense import NormalLinear
+        from .. import _lib
+        from .dense import NormalLinear, FlipoutNormalLinear, _flipout_fresh_key
         if not ops.DRAW_ONCE_BF16:
             return []
-        todo, todo3 = [], []
+        todo, todo3, flips = [], [], []
         infer = not torch.is_grad_enabled()
         for m in self.modules():
+            if type(m) is FlipoutNormalLinear and m.weight.mean.is_cuda and ops.flipout_drawable(m.weight.mean) and \
+                    m._compute_mode() == "bf16":
+                # its per-sample weights mu + sigma R_s S_s^T ride in the same launch (BNN_DRAW_FLIPOUT).  Like a NormalLinear's, the
+                # draw is made on a fresh key before `_forward` runs: a layer then called with sample=False (or not at all) does not
+                # use it -- it keeps its recorded flip_key -- and the draw (one item of this launch) is wasted work, not a wrong result
+                flips.append(m)
+                continue
             if type(m) is not NormalLinear or not m.weight.mean.is_cuda or not ops.dense_eligible(m.weight.mean):
                 continue
             if (m.compute or _settings.get_compute()) == "bf16":
@@ -163,7 +171,7 @@ class BayesianNetworkModule(Module):
             elif ops.DENSE_X3_F32 and (infer or not m._trainable()) and ctx.base_batch >= 64 and \
                     (m.weight.mean.shape[0] > 16 or m.weight.mean.shape[1] <= 2048):
                 todo3.append(m)         # fp32 parity mode, inference: the same plan with three-plane draws (ops.linear_sampled_x3)
-        if not todo and not todo3:
+        if not todo and not todo3 and not flips:
             return []
 
         def specs_of(mods):
@@ -180,8 +188,10 @@ class BayesianNetworkModule(Module):
 
         kl = ops._tls.kl_carry
         pre = []
-        if todo:
-            specs = specs_of(todo)
+        if todo or flips:
+            specs = specs_of(todo) + [(m.weight.mean.detach(), m.weight.scale.detach(), None, None, _flipout_fresh_key(m, ctx), None, 0, _lib.DRAW_FLIPOUT)
+                                      for m in flips]
+            todo = todo + flips
             if ops.DRAW_SIDE_STREAM and len(specs) > 1:
                 # the first layer's weights on the main stream; the rest (and the KL's first pass) on a side stream, where the
                 # VALU-bound draw runs beside the first layer's draw and DMA / MFMA-bound contraction

@@ -3,8 +3,9 @@
 NormalConv2d is the hot path: an implicit-GEMM MFMA kernel whose B-operand loader draws the
 filter bank (bnn_conv2d_forward_sampled).  NormalConv1d/3d have no configuration in
 BASELINE.json: they take their weights from the fused HIP sampler (K1) and contract with the
-PyTorch-ROCm convNd op.  FlipOut variants are PyTorch ops; the MC-dropout variants run their torch
-conv once and apply the keyed masks of a network's MC-batched device pass in HIP (bnn_mc_dropout).
+PyTorch-ROCm convNd op.  The FlipOut variants run on HIP on the device (2-d, and 1-d as 2-d at height 1); in a network's
+MC-batched device pass their signs are keyed per MC sample (bnn_conv2d_flipout_forward_mc, bnn_flipout_signs).  The MC-dropout
+variants run their torch conv once and apply the keyed masks of a network's MC-batched device pass in HIP (bnn_mc_dropout).
 """
 import torch
 from torch.distributions import Normal
@@ -14,7 +15,7 @@ from . import _settings
 from ..utils import _single, _pair, _triple
 from .container import BayesianModule
 from .core import WeightNormal
-from .dense import _NormalSampling, _init_normal_posterior, _mc_dropout_plan, _mc_dropout_key
+from .dense import _NormalSampling, _init_normal_posterior, _mc_dropout_plan, _mc_dropout_key, _flipout_plan, _flipout_mc_key
 
 
 class BayesianConvNd(BayesianModule):
@@ -134,8 +135,39 @@ class NormalConv3d(NormalConvNd):
         return self._torch_conv(torch.nn.functional.conv3d, x, sample)
 
 
+def _flipout_conv2d_device(layer, x, R, S, view, stride, padding, dilation):
+    """conv.py:207-221 on the device for a 4-d x and sign tensors R (B, O, 1, 1), S (B, C, 1, 1) broadcast over its rows; `view`
+    turns the layer's weight tensors into (O, C, KH, KW)."""
+    # both contractions are the HIP implicit GEMM (the sign tensors are per EXAMPLE, conv.py:154-161, so they cannot be folded
+    # into the weight)
+    comp = _settings.get_compute()
+    geo = (stride, padding, dilation, layer.groups)
+    mean, scale = view(layer.weight.mean), view(layer.weight.scale)
+    needs_grad = torch.is_grad_enabled() and (x.requires_grad or layer._trainable())
+    if comp == "bf16" and not needs_grad and ops.conv2d_flipout_eligible(x, mean, *geo):
+        # one launch for both contractions: shared A tile, S in the fragment's sign bits, R in the epilogue
+        return ops.conv2d_flipout(x, mean, scale, R, S, *geo[:3])
+    if comp == "f32" and not needs_grad and layer.groups == 1 and ops.conv2d_flipout_x3_fused_eligible(x, mean, *geo[:3]):
+        # fp32 parity mode, inference: ONE contraction launch on three-plane operands (S in the sign bits, R in the epilogue)
+        return ops.conv2d_flipout_x3_fused(x, mean, view(layer.weight.stddev), R, S, *geo[:3])
+    if (comp == "f32" and not needs_grad and mean.data_ptr() % 16 == 0 and
+            ops.conv2d_plain_x3_eligible(x, mean.detach().unsqueeze(0), *geo, comp)):
+        # fp32 parity mode, inference: both contractions as implicit GEMMs on three-plane operands, no im2col panel
+        return ops.conv2d_flipout_x3(x, mean, view(layer.weight.stddev), R, S, *geo[:3])
+    out = ops.conv2d_plain(x, mean.unsqueeze(0), None, True, *geo, comp)[0]
+    noise = ops.conv2d_plain(x * S.expand_as(x), view(layer.weight.stddev).unsqueeze(0), None, True, *geo, comp)[0]
+    return out + noise * R.expand_as(out)
+
+
 class FlipOutNormalConvNd(NormalConvNd):
-    """conv.py:145-161: per-example sign tensors R (B, out, 1..) and S (B, in/groups.., 1..); no bias."""
+    """conv.py:145-161: per-example sign tensors R (B, out, 1..) and S (B, in/groups.., 1..); no bias.
+
+    In a BayesianNetworkModule's MC-batched pass on the device (mc_batched = True) every MC sample gets signs of its own, keyed
+    like a posterior draw (layer.flip_key; sign contract in include/bnn_hip.h, conv layout).  2-d (and 1-d, as 2-d at height 1):
+    in the bf16 mode at inference ONE keyed launch for all S samples (bnn_conv2d_flipout_forward_mc: the mean contraction of a
+    shared input computed once, no sign tensor in memory); otherwise the signs are materialized (bnn_flipout_signs), a shared
+    input is fanned out to S * B rows and the launches above run on it.  3-d: materialized signs and torch conv3d.
+    sample=False in such a pass reuses flip_key.  layer.R / layer.S keep the values of the last serial-loop (torch.rand) call."""
 
     _op = None
     _ones = ()
@@ -144,6 +176,8 @@ class FlipOutNormalConvNd(NormalConvNd):
                  transposed, groups, prior):
         super().__init__(in_channels, out_channels, _single(kernel_size), stride, padding, dilation,
                          transposed, groups, False, prior)
+        self.flip_key = None            # DrawKey of the last MC-batched device signs
+        self._flip_stream = None
 
     def sample(self, batch_size=1, additional_dims=()):
         dev = self.weight.device
@@ -156,33 +190,57 @@ class FlipOutNormalConvNd(NormalConvNd):
 
     def forward(self, x, sample=True):
         # conv.py:182-196 (1d), 213-227 (2d), 244-258 (3d)
+        plan = _flipout_plan(self, x)
+        if plan is not None:
+            return self._forward_mc(x, sample, *plan)
         if sample:
             self.sample(x.size(0), self._ones)
         if x.is_cuda and x.dim() == 4 and type(self)._op is torch.nn.functional.conv2d:
-            # device, 2-d: both contractions are the HIP implicit GEMM (the sign tensors are per EXAMPLE,
-            # conv.py:154-161, so they cannot be folded into the weight)
-            comp = _settings.get_compute()
-            geo = (self.stride, self.padding, self.dilation, self.groups)
-            needs_grad = torch.is_grad_enabled() and (x.requires_grad or self._trainable())
-            if comp == "bf16" and not needs_grad and ops.conv2d_flipout_eligible(x, self.weight.mean, *geo):
-                # one launch for both contractions: shared A tile, S in the fragment's sign bits, R in the epilogue
-                return ops.conv2d_flipout(x, self.weight.mean, self.weight.scale, self.R, self.S, *geo[:3])
-            if comp == "f32" and not needs_grad and self.groups == 1 and ops.conv2d_flipout_x3_fused_eligible(x, self.weight.mean, *geo[:3]):
-                # fp32 parity mode, inference: ONE contraction launch on three-plane operands (S in the sign bits, R in the epilogue)
-                return ops.conv2d_flipout_x3_fused(x, self.weight.mean, self.weight.stddev, self.R, self.S, *geo[:3])
-            if (comp == "f32" and not needs_grad and self.weight.mean.data_ptr() % 16 == 0 and
-                    ops.conv2d_plain_x3_eligible(x, self.weight.mean.detach().unsqueeze(0), *geo, comp)):
-                # fp32 parity mode, inference: both contractions as implicit GEMMs on three-plane operands, no im2col panel
-                return ops.conv2d_flipout_x3(x, self.weight.mean, self.weight.stddev, self.R, self.S, *geo[:3])
-            out = ops.conv2d_plain(x, self.weight.mean.unsqueeze(0), None, True, *geo, comp)[0]
-            noise = ops.conv2d_plain(x * self.S.expand_as(x), self.weight.stddev.unsqueeze(0), None, True, *geo, comp)[0]
-            return out + noise * self.R.expand_as(out)
+            return _flipout_conv2d_device(self, x, self.R, self.S, lambda t: t, self.stride, self.padding, self.dilation)
         conv = type(self)._op
         out = conv(x, self.weight.mean, self.bias, self.stride, self.padding, self.dilation, self.groups)
         noise = conv(x * self.S.expand_as(x), self.weight.stddev, self.bias, self.stride, self.padding,
                      self.dilation, self.groups)
         out += noise * self.R.expand_as(out)
         return out
+
+    def _forward_mc(self, x, sample, ctx, shared):
+        nd = len(self._ones)
+        if x.dim() != nd + 2:
+            raise RuntimeError("mc_batched: %s needs a batched (N, C, ...) input, got shape %s" % (type(self).__name__, tuple(x.shape)))
+        key = _flipout_mc_key(self, ctx, sample)
+        S = key.nsamples
+        O, C = self.weight.size(0), self.weight.size(1)
+        B = x.shape[0] if shared else x.shape[0] // S
+        if nd == 1:
+            # a 1-d convolution is the 2-d one on images of height 1 (as NormalConv1d): the same launches, the same signs
+            geo = ((1,) + tuple(self.stride), (0,) + tuple(self.padding), (1,) + tuple(self.dilation))
+            return self._mc2d(x.unsqueeze(2), key, shared, B, lambda t: t.unsqueeze(2), geo).squeeze(2)
+        if nd == 2:
+            return self._mc2d(x, key, shared, B, lambda t: t, (self.stride, self.padding, self.dilation))
+        # 3-d: the reference expression (conv.py:244-258) on materialized keyed signs and the fanned-out input
+        sg = ops.flipout_signs(key, B, O + C, x.device).reshape(S * B, O + C)
+        R, Sg = sg[:, :O].reshape(S * B, O, 1, 1, 1), sg[:, O:].reshape(S * B, C, 1, 1, 1)
+        xf = x.unsqueeze(0).expand(S, *x.shape).reshape(S * B, *x.shape[1:]) if shared else x
+        conv = type(self)._op
+        out = conv(xf, self.weight.mean, None, self.stride, self.padding, self.dilation, self.groups)
+        noise = conv(xf * Sg, self.weight.stddev, None, self.stride, self.padding, self.dilation, self.groups)
+        return out + noise * R
+
+    def _mc2d(self, x, key, shared, B, view, geo):
+        S = key.nsamples
+        O, C = self.weight.size(0), self.weight.size(1)
+        comp = _settings.get_compute()
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or self._trainable())
+        if comp == "bf16" and not needs_grad and \
+                ops.conv2d_flipout_mc_eligible(x, view(self.weight.mean), *geo, self.groups, S, shared):
+            # ONE launch for all S samples, the signs made from the key inside it
+            return ops.conv2d_flipout_mc(x, view(self.weight.mean), view(self.weight.scale), key, shared, *geo)
+        # materialized keyed signs on the fanned-out input, the launches of the serial device path
+        sg = ops.flipout_signs(key, B, O + C, x.device).reshape(S * B, O + C)
+        R, Sg = sg[:, :O].reshape(S * B, O, 1, 1), sg[:, O:].reshape(S * B, C, 1, 1)
+        xf = x.unsqueeze(0).expand(S, *x.shape).reshape(S * B, *x.shape[1:]) if shared else x
+        return _flipout_conv2d_device(self, xf, R, Sg, view, *geo)
 
 
 def _flipout(ntuple, op, ones):

@@ -6,7 +6,8 @@ BayesianNetworkModule's draw plan runs first), then contracted by bnn_dense_forw
 accumulate) or bnn_dense_forward_x3 (fp32 parity mode at inference: three bf16 planes per operand).  Training-time fp32
 forwards, narrow fp32 layers and A/B runs take the round-1 fused kernel (bnn_linear_forward_sampled: the draw inside the
 B-operand loader of the GEMM).  MCDropoutLinear runs on HIP in a network's MC-batched device pass (keyed masks,
-bnn_dense_forward_dropout / bnn_mc_dropout) and keeps F.dropout elsewhere.  The other classes (Flipout, multivariate,
+bnn_dense_forward_dropout / bnn_mc_dropout) and keeps F.dropout elsewhere.  FlipoutNormalLinear draws mu + sigma R S^T
+with keyed signs per MC sample in that pass (bnn_draw_multi kind BNN_DRAW_FLIPOUT).  The other classes (multivariate,
 evidential) are outside the HIP scope and run as PyTorch-ROCm ops with the
 reference's semantics so that its examples keep working.
 """
@@ -266,11 +267,58 @@ class NormalLinear(_NormalSampling, BayesianLinear):
         return y.reshape(S * per, *lead, y.shape[-1])
 
 
+def _flipout_plan(layer, x):
+    """Inside a BayesianNetworkModule's MC-batched pass (an McContext) on a device tensor: -> (ctx, shared), shared = x holds the
+    un-replicated batch (ctx.base_batch rows) rather than S * B rows (sample = row // B).  None: the reference's torch.rand signs
+    (serial loop, CPU, no context).  Unlike _mc_dropout_plan this holds for sample=False too: the recorded flip_key is reused."""
+    ctx = _mc.current()
+    if ctx is None or not isinstance(x, torch.Tensor) or not x.is_cuda:
+        return None
+    if x.dim() >= 2 and x.shape[0] == ctx.base_batch:
+        return ctx, True
+    if x.dim() >= 2 and x.shape[0] == ctx.base_batch * ctx.samples:
+        return ctx, False
+    # torch.rand here would draw ONE set of signs for what the pass treats as S samples
+    raise RuntimeError("mc_batched: %s got an input of shape %s; expected (%d, ...) or (%d, ...) rows (batch %d x %d samples)"
+                       % (type(layer).__name__, tuple(x.shape), ctx.base_batch, ctx.base_batch * ctx.samples,
+                          ctx.base_batch, ctx.samples))
+
+
+def _flipout_fresh_key(layer, ctx):
+    """A fresh DrawKey for the Flipout signs of this MC-batched forward (the RNG contract's sign part), NOT recorded.  The stream id
+    is taken at the layer's first MC-batched device forward, so that a model's existing layers keep their ids and draws."""
+    from .._rng import DrawKey, new_stream_id
+    if getattr(layer, "_flip_stream", None) is None:
+        layer._flip_stream = new_stream_id()
+    return DrawKey(default_generator.seed, layer._flip_stream, ctx.sample0, ctx.samples, default_generator.next_epoch(),
+                   gen=generator_for(_settings.get_compute()))
+
+
+def _flipout_mc_key(layer, ctx, sample):
+    """sample: a fresh key, recorded as layer.flip_key.  sample=False: the recorded key, which must have the pass's S samples."""
+    if sample:
+        layer.flip_key = _flipout_fresh_key(layer, ctx)
+        return layer.flip_key
+    key = getattr(layer, "flip_key", None)
+    if key is None or key.nsamples != ctx.samples:
+        raise RuntimeError("sample=False: %s has %s Flipout signs recorded, this MC-batched pass needs %d samples"
+                           % (type(layer).__name__, "no" if key is None else "%d samples of" % key.nsamples, ctx.samples))
+    return key
+
+
 class FlipoutNormalLinear(NormalLinear):
-    """dense.py:63-83: y = x mu^T + ((x * S) sigma^T) * R with random sign vectors; no bias."""
+    """dense.py:63-83: y = x mu^T + ((x * S) sigma^T) * R with random sign vectors; no bias.
+
+    In a BayesianNetworkModule's MC-batched pass on the device (mc_batched = True) every MC sample gets signs of its own, keyed
+    like a posterior draw (layer.flip_key; sign contract in include/bnn_hip.h): per sample the layer is w_s = mu + sigma (.) R_s
+    S_s^T, drawn by bnn_draw_multi (kind BNN_DRAW_FLIPOUT; in the bf16 mode inside the network's one draw launch) and contracted by the dense
+    kernel (bf16) or bnn_linear_forward (fp32).  sample=False in such a pass reuses flip_key.  layer.R / layer.S keep the values
+    of the last serial-loop (torch.rand) call: the batched pass never materializes them."""
 
     def __init__(self, in_features, out_features, prior=Normal(0, .1)):
         super().__init__(in_features, out_features, False, prior)
+        self.flip_key = None            # DrawKey of the last MC-batched device signs
+        self._flip_stream = None
 
     def sample(self, *unused):
         dev = self.weight.device
@@ -282,6 +330,9 @@ class FlipoutNormalLinear(NormalLinear):
         return (self.R, self.S)
 
     def forward(self, x, sample=True):
+        plan = _flipout_plan(self, x)
+        if plan is not None:
+            return self._forward_mc(x, sample, *plan)
         if sample:
             self.sample()
         if not x.is_cuda:
@@ -296,6 +347,32 @@ class FlipoutNormalLinear(NormalLinear):
         K = x.shape[-1]
         y = ops.linear_plain(x.reshape(-1, K).float(), w.unsqueeze(0), None, True, self._compute_mode())
         return y.reshape(*x.shape[:-1], y.shape[-1])
+
+    def _forward_mc(self, x, sample, ctx, shared):
+        predrawn = None
+        pd = getattr(self, "_predrawn", None)
+        if pd is not None:
+            self._predrawn = None
+            if sample and pd[0] is ctx:
+                predrawn = pd[1]                    # drawn by the network's plan (container._draw_plan) on this key
+                self.flip_key = predrawn.key_w
+        key = predrawn.key_w if predrawn is not None else _flipout_mc_key(self, ctx, sample)
+        S = key.nsamples
+        O, K = self.weight.mean.shape
+        x2 = x.reshape(-1, K)
+        mode = self._compute_mode()
+        if ops.flipout_drawable(self.weight.mean):
+            y = ops.linear_flipout_mc(x2, self.weight.mean, self.weight.scale, key, shared, mode,
+                                      predrawn if mode == "bf16" else None)
+        else:
+            # K % 8 != 0: the reference expression on materialized keyed signs, both contractions on the HIP linear
+            sg = ops.flipout_signs(key, 1, O + K, x.device)
+            R, Sg = sg[:, :, :O], sg[:, :, O:]                                                # (S, 1, O), (S, 1, K)
+            xs = x2.float().reshape(1 if shared else S, -1, K)
+            out = ops.linear_plain(xs.reshape(-1, K), self.weight.mean.unsqueeze(0), None, True, mode).reshape(xs.shape[0], -1, O)
+            noise = ops.linear_plain(xs * Sg, self.weight.stddev.unsqueeze(0).expand(S, O, K), None, False, mode)
+            y = out + noise * R
+        return y.reshape(-1, *x.shape[1:-1], O)
 
 
 class MultivariateNormalLinear(BayesianLinear):

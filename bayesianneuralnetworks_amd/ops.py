@@ -215,6 +215,7 @@ def draw_layers(layers, nsamples, kl=None, stream=None, x3=False, split=None):
         for spec in group:
             mu_w, rho_w, mu_b, rho_b, key_w, key_b = spec[:6]
             taps = spec[6] if len(spec) > 6 else 0      # KH * KW: a conv weight, written tap-major
+            kind = spec[7] if len(spec) > 7 else 0      # _lib.DRAW_FLIPOUT (16): a Flipout draw (eps = the key's sign outer product)
             require_cuda_f32(mu_w, "weight.mean")
             require_cuda_f32(rho_w, "weight.scale")
             N, K = mu_w.shape
@@ -223,7 +224,7 @@ def draw_layers(layers, nsamples, kl=None, stream=None, x3=False, split=None):
             t = arr[n]
             t.mu, t.rho, t.rows, t.cols = mu_w.data_ptr(), rho_w.data_ptr(), N, K
             t.out, t.ld, t.out_sample_stride, t.out_dtype = w.data_ptr(), kp, N * kp, (_lib.BF16X3 if x3 else _lib.BF16)
-            t.taps = taps
+            t.taps, t.kind = taps, kind
             t.rng = _rng_struct(key_w, dev)
             n += 1
             b = None
@@ -1024,6 +1025,143 @@ def linear_mc_dropout(x, w, b, p, key, shared, compute="f32", w_bf16=None):
     M = x.shape[0]
     h = linear_plain(x.float(), w.unsqueeze(0), None if b is None else b.unsqueeze(0), True, compute)     # (1, M, N)
     return mc_dropout(h.view(M, -1), p, key, shared)
+
+
+# --------------------------------------------------------------------------- Flipout, MC-batched
+def flipout_signs(key, rows, width, device):
+    """The keyed Flipout signs of the key's nsamples MC samples (sign contract, include/bnn_hip.h) -> (S, rows, width) fp32 +-1:
+    conv rows = B, width = O + C (R = [..., :O], S = [..., O:]); linear rows = 1, width = O + K (bnn_flipout_signs)."""
+    out = torch.empty((key.nsamples, rows, width), dtype=torch.float32, device=device)
+    r = _rng_struct(key, device)
+    check(_lib.load().bnn_flipout_signs(ptr(out), rows * width, rows, width, key.nsamples, ctypes.byref(r), stream_ptr(device)),
+          "bnn_flipout_signs")
+    return out
+
+
+def flipout_draw(mu, rho, key, out_dtype=torch.float32, pad=False):
+    """w_s = mu + sigma(rho) (.) R_s S_s^T for the key's samples (bnn_draw_multi kind BNN_DRAW_FLIPOUT) -> (S, O, K) fp32, or with pad (S, O,
+    roundup(K, 64)) zero-padded -- the dense kernel's operand in bf16.  Needs K % 4 == 0 (K % 8 == 0 for an unpadded fp32 draw)."""
+    require_cuda_f32(mu, "weight.mean")
+    require_cuda_f32(rho, "weight.scale")
+    O, K = mu.shape
+    ld = _pad64(K) if pad else K
+    S = key.nsamples
+    w = torch.empty((S, O, ld), dtype=out_dtype, device=mu.device)
+    arr = (_lib.DrawTensor * 1)()
+    t = arr[0]
+    t.mu, t.rho, t.rows, t.cols = mu.data_ptr(), rho.data_ptr(), O, K
+    t.out, t.ld, t.out_sample_stride = w.data_ptr(), ld, O * ld
+    t.out_dtype = _lib.F32 if out_dtype == torch.float32 else _lib.BF16
+    t.kind, t.taps = _lib.DRAW_FLIPOUT, 0
+    t.rng = _rng_struct(key, mu.device)
+    check(_lib.load().bnn_draw_multi(arr, 1, S, None, 0, None, stream_ptr(mu.device)), "bnn_draw_multi")
+    return w
+
+
+def flipout_drawable(mu):
+    """The sign-outer-product draw takes this (O, K) posterior (whole rows of 8 columns, 16-B aligned)."""
+    return mu.dim() == 2 and mu.shape[1] % 8 == 0 and mu.data_ptr() % 16 == 0
+
+
+class _FlipoutLinear(torch.autograd.Function):
+    """FlipoutNormalLinear on the MC-batched path: y[s] = x[s] (mu + sigma (.) R_s S_s^T)^T -- exactly x mu^T + ((x * S_s) sigma^T)
+    * R_s of dense.py:70-83 -- with the keyed signs of every sample (bnn_draw_multi kind BNN_DRAW_FLIPOUT).  bf16 mode: the dense kernel on the
+    bf16 draw (`predrawn`: drawn by the network's plan); fp32 mode: bnn_linear_forward on the fp32 draw.  Backward: the fp32 draw
+    again (never stored), bnn_linear_backward_input / _weight, and bnn_flipout_weight_backward for d/d mu and d/d rho."""
+
+    @staticmethod
+    def forward(ctx, x, mu, rho, key, shared, compute, predrawn):
+        require_cuda_f32(x, "x")
+        S = key.nsamples
+        O, K = mu.shape
+        B = x.shape[0] if shared else x.shape[0] // S
+        if x.shape[-1] != K:
+            raise BnnHipError("linear: input has %d features, weight expects %d" % (x.shape[-1], K))
+        if compute == _lib.COMPUTE_BF16:
+            pre = predrawn
+            if pre is None:
+                pre = Predrawn(flipout_draw(mu, rho, key, torch.bfloat16, pad=True), None, key, None)
+            pre.wait()
+            xb = x.to(torch.bfloat16).contiguous()
+            y = _dense_raw(xb, 0 if shared else B * K, B, pre, K, False, torch.float32)
+        else:
+            w = flipout_draw(mu, rho, key)
+            y = torch.empty((S, B, O), dtype=torch.float32, device=x.device)
+            check(_lib.load().bnn_linear_forward(ptr(x), 0 if shared else B * K, K, ptr(w), O * K, None, 0, ptr(y), B * O, O,
+                                                  B, O, K, S, compute, 0, stream_ptr(x.device)), "bnn_linear_forward")
+        ctx.save_for_backward(x, mu, rho)
+        ctx.key, ctx.shared, ctx.B = key, shared, B
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, mu, rho = ctx.saved_tensors
+        key, B = ctx.key, ctx.B
+        S = key.nsamples
+        O, K = mu.shape
+        dev = gy.device
+        lib = _lib.load()
+        gy = gy.contiguous().float()
+        gx = g_mu = g_rho = None
+        if ctx.needs_input_grad[0]:
+            gx = _dgrad_plain_raw(gy, flipout_draw(mu, rho, key), torch.float32)       # (S, B, K)
+            gx = _sum_samples(gx) if ctx.shared else gx.reshape(S * B, K)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gw = torch.empty((S, O, K), dtype=torch.float32, device=dev)
+            check(lib.bnn_linear_backward_weight(ptr(x), 0 if ctx.shared else B * K, K, ptr(gy), B * O, O, ptr(gw), O * K, B, O, K,
+                                                 S, _lib.COMPUTE_F32, 0, 0, stream_ptr(dev)), "bnn_linear_backward_weight")
+            g_mu, g_rho = torch.empty_like(mu), torch.empty_like(rho)
+            r = _rng_struct(key, dev)
+            check(lib.bnn_flipout_weight_backward(ptr(gw), O * K, ptr(rho), ptr(g_mu), ptr(g_rho), O, K, S, ctypes.byref(r),
+                                                  stream_ptr(dev)), "bnn_flipout_weight_backward")
+        return gx, g_mu, g_rho, None, None, None, None
+
+
+def linear_flipout_mc(x, mu, rho, key, shared, compute="f32", predrawn=None):
+    """FlipoutNormalLinear on the MC-batched path -> (S, B, O).  x (B, K) shared by the samples or (S * B, K), fp32; the
+    caller checked flipout_drawable(mu)."""
+    return _FlipoutLinear.apply(x.contiguous().float(), mu.contiguous(), rho.contiguous(), key, bool(shared),
+                                _compute_code(compute), predrawn)
+
+
+def conv2d_flipout_mc_eligible(x, mean, stride, padding, dilation, groups, S, shared):
+    """bf16 compute, inference: the keyed one-launch Flipout conv (bnn_conv2d_flipout_forward_mc) takes this layer -- the shapes
+    of bnn_conv2d_flipout_forward, with the samples' masks and R signs in the LDS block too."""
+    if not (DRAW_ONCE_BF16 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and groups == 1):
+        return False
+    O, C, KH, KW = mean.shape
+    if not ((C == 64 or C % 128 == 0) and O in (32, 64) and mean.data_ptr() % 16 == 0):
+        return False
+    B = x.shape[0] if shared else x.shape[0] // S
+    sh, OH, OW = _conv_shape((B,) + tuple(x.shape[1:]), mean.shape, stride, padding, dilation, groups)
+    if OH < 1 or OW < 1 or OH * OW > 128 or B * (O + C) >= 2 ** 32 or S > 0xFFFF:
+        return False
+    ns = 1 if (not shared or S == 1) else 2 if (S == 2 or O == 64) else 4          # (as bnn_dense.hip chooses)
+    block = 136 * 1024
+    rsign = ns * O * 4
+    return sh.H * sh.W * C * 2 + ns * (C // 8) * 16 + rsign + 4 * 2 * O * 128 <= block and O * OH * OW * 4 + rsign <= block
+
+
+def conv2d_flipout_mc(x, mean, scale, key, shared, stride, padding, dilation):
+    """FlipOutNormalConv2d on the MC-batched path (conv.py:207-221 with the keyed signs of every sample) in two launches: mean and
+    stddev written tap-major as bf16 (bnn_draw_multi, kinds 1 / 2), then ONE keyed implicit GEMM for all S samples
+    (bnn_conv2d_flipout_forward_mc; no sign tensor, no fanned-out x).  x (B, C, H, W) shared or (S * B, ...) -> (S * B, O, OH, OW).
+    No autograd (inference path)."""
+    x = x.contiguous()
+    require_cuda_f32(x, "x")
+    S = key.nsamples
+    O = mean.shape[0]
+    B = x.shape[0] if shared else x.shape[0] // S
+    dev = x.device
+    w2 = flipout_conv_weights(mean, scale)
+    kp = w2.shape[1]
+    sh, OH, OW = _conv_shape((B,) + tuple(x.shape[1:]), mean.shape, stride, padding, dilation, 1)
+    y = torch.empty((S * B, O, OH, OW), dtype=torch.float32, device=dev)
+    r = _rng_struct(key, dev)
+    check(_lib.load().bnn_conv2d_flipout_forward_mc(ptr(x), 0 if shared else B * x[0].numel(), ptr(w2), kp, ptr(y),
+                                                    B * O * OH * OW, ctypes.byref(sh), S, ctypes.byref(r), 0, stream_ptr(dev)),
+          "bnn_conv2d_flipout_forward_mc")
+    return y
 
 
 # --------------------------------------------------------------------------- K2 conv2d

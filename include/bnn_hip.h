@@ -53,6 +53,17 @@
  *   The mask depends only on the key and (sample, r, f): not on tiling, grid, fusion or dtype -- every kernel that applies or
  *   re-creates it uses one device function (drop_u4), so the fused and the standalone mask are the same bit for bit.
  *   rows * F < 2^32 per sample.  CPU twin: tests/test_mc_dropout.py (mask_twin), on the oracle's Philox.
+ *
+ * Flipout-sign contract (Flipout layers on the MC-batched path: bnn_flipout_signs, bnn_conv2d_flipout_forward_mc, bnn_draw_multi
+ * BNN_DRAW_FLIPOUT, bnn_flipout_weight_backward)
+ *   A Flipout sign is a keyed draw on the same UNIFORMS as the dropout mask above (same fields, both generators, before
+ *   Box-Muller), one stream per layer, sample sample0 + s.  The sign of uniform u is -1 iff u < 0.5, +1 otherwise: the
+ *   reference's (rand - .5).sign().  A 16-bit uniform is never 0.5; a 24-bit one is 0.5 when ((x >> 8) + 0.5) 2^-24 rounds to it
+ *   (x >> 8 = 2^23), and that gives +1 -- so no sign is ever 0.  Element layout within one sample:
+ *     conv (B images, O output and C input channels): e = b (O + C) + j; j < O is R[b][j], the rest is S[b][j - O];
+ *     linear (O x K weight): one row of O + K elements, R = v[0 : O], S = v[O : O + K], eps[o][k] = R[o] S[k].
+ *   rows (O + C) < 2^32 per sample.  Every kernel computes a sign with one device function (flip_sign on drop_u4).
+ *   CPU twin: tests/test_flipout_mc.py (sign_twin), on the oracle's Philox.
  */
 #ifndef BNN_HIP_H
 #define BNN_HIP_H
@@ -244,6 +255,7 @@ int bnn_linear_forward_sampled_kl(const void *x, int64_t x_sample_stride, int64_
  * replaces  WeightNormal.sample  pytorch_bayesian/nn/core.py:44-45, called weight-then-bias by
  *           NormalLinear.sample  pytorch_bayesian/nn/dense.py:46-54, once per MC sample by the loop at
  *           pytorch_bayesian/nn/container.py:36-37 */
+enum { BNN_DRAW_FLIPOUT = 16 };  /* bnn_draw_tensor_t.kind of a Flipout draw (sign contract below) */
 typedef struct bnn_draw_tensor {
     const float *mu;
     const float *rho;
@@ -253,7 +265,9 @@ typedef struct bnn_draw_tensor {
     int64_t out_sample_stride;  /* elements */
     int out_dtype;              /* BNN_F32, BNN_BF16, or BNN_BF16X3: three planes, plane p of draw s at
                                  * out + (p * nsamples + s) * out_sample_stride (kinds 0, 1, 2) */
-    int kind;                   /* 0: draw mu + sigma(rho) eps (rng used); 1: mu itself; 2: sigma(rho) itself (no eps: Flipout's
+    int kind;                   /* 0: draw mu + sigma(rho) eps (rng used); BNN_DRAW_FLIPOUT: the same with eps[r][c] = R[r] S[c], the
+                                 * Flipout signs of rng (sign contract above, linear layout with O = rows, K = cols; no taps);
+                                 * 1: mu itself; 2: sigma(rho) itself (no eps: Flipout's
                                  * two operands, nsamples = 1); 3: `mu` as it is, written ONCE whatever nsamples is (rho ignored,
                                  * pass mu) -- with BNN_BF16X3 (planes out_sample_stride apart) this is bnn_split_bf16x3 of an
                                  * activation riding in the draw launch: the fp32 parity mode's input planes */
@@ -507,6 +521,18 @@ int bnn_conv2d_flipout_forward(const float *x, const void *w, int64_t ldw, const
 int bnn_conv2d_flipout_forward_x3(const float *x, const void *w, int64_t w_plane_stride, int64_t ldw, const float *sign_in,
                                   const float *sign_out, float *y, const bnn_conv2d_shape_t *sh, int flags, void *stream);
 
+/* Flipout conv2d of the MC-batched path in ONE launch for nsamples samples, the signs keyed (Flipout-sign contract above, conv
+ * layout, sample rng->sample0 + s) and made inside the kernel -- no sign tensor in memory:
+ *   y[s][b] = conv(x[s | 0][b], mean) + R_s[b] * conv(x[s | 0][b] * S_s[b], stddev)           (conv.py:207-221 per MC sample)
+ * x fp32 NCHW: SHARED (x_sample_stride = 0: the first Bayesian layer of a net sees the un-replicated batch) -- the mean contraction
+ * of a tile runs ONCE and is reused by every sample of the workgroup; only the stddev contraction, S_s XOR-ed into the A
+ * fragment's sign bits, runs per sample -- or per sample (x_sample_stride = B C H W: a Bayesian layer earlier in the net).
+ * y: nsamples x B x O x OH x OW fp32 (y_sample_stride elements).  w, ldw, shapes: as bnn_conv2d_flipout_forward.
+ * nsamples <= 65535, B (O + C) < 2^32.  BNN_E_UNSUPPORTED (nothing launched) where bnn_conv2d_flipout_forward would refuse. */
+int bnn_conv2d_flipout_forward_mc(const float *x, int64_t x_sample_stride, const void *w, int64_t ldw, float *y,
+                                  int64_t y_sample_stride, const bnn_conv2d_shape_t *shape, int nsamples, const bnn_rng_t *rng,
+                                  int flags, void *stream);
+
 /* ---- backward of K2 conv2d through the panel ------------------
  * replaces  autograd through F.conv2d (conv.py:116) for groups == 1, C*KH*KW % 8 == 0.  With
  * M = B*OH*OW rows, K = C*KH*KW, N = O:
@@ -583,6 +609,18 @@ int bnn_mc_dropout(const void *x, int64_t x_sample_stride, void *y, int64_t y_sa
  * reproducible. */
 int bnn_mc_dropout_backward(const float *gy, int64_t gy_sample_stride, float *gx, int64_t gx_sample_stride, int64_t rows,
                             int64_t features, int nsamples, float p, int sum_samples, const bnn_rng_t *rng, void *stream);
+
+/* ---- Flipout signs (Flipout-sign contract above) ---------------------------------
+ * out[s][r][j] = sign of element r * width + j of sample rng->sample0 + s, as +-1 fp32, s < nsamples, r < rows, j < width
+ * (conv: rows = B, width = O + C; linear: rows = 1, width = O + K); out_sample_stride >= rows * width elements.
+ * replaces  (torch.rand(B, O / C, ...) - .5).sign()  pytorch_bayesian/nn/conv.py:154-161, dense.py:70-75, one draw per MC sample */
+int bnn_flipout_signs(float *out, int64_t out_sample_stride, int64_t rows, int64_t width, int nsamples, const bnn_rng_t *rng,
+                      void *stream);
+/* Backward of bnn_draw_multi's BNN_DRAW_FLIPOUT draw (w_s = mu + sigma(rho) (.) R_s S_s^T, O x K), the signs re-created from the key (never stored):
+ *   g_mu = sum_s g_w[s],  g_rho = sum_s g_w[s] (.) R_s S_s^T (.) sigmoid(rho),  s = 0 .. nsamples - 1 in that order, fp32.
+ * g_w: nsamples x O x K fp32 at g_w_sample_stride elements. */
+int bnn_flipout_weight_backward(const float *g_w, int64_t g_w_sample_stride, const float *rho, float *g_mu, float *g_rho,
+                                int64_t O, int64_t K, int nsamples, const bnn_rng_t *rng, void *stream);
 
 /* ---- MC reduction ----------------------------------------------------------
  * replaces  torch.stack(preds).mean(0)   examples/MNIST/uncertainty.py:50
