@@ -218,6 +218,8 @@ __global__ __launch_bounds__(kThreads) void k_prune_score(const float *__restric
 __global__ void k_rng_advance(uint32_t *epoch_dev, uint32_t inc) { epoch_dev[0] += inc; }
 
 // ---------------------------------------------------------------- MC reduction
+// CHUNKED: more than 4 * kMcSplitMax addends per output (its own instantiation: the code of the common counts stays as it is)
+template <bool CHUNKED>
 __global__ __launch_bounds__(kMcThreads) void k_mc_sum(const float *__restrict__ y,
                                                        int64_t y_sample_stride, int nsamples,
                                                        int64_t n, float scale,
@@ -225,7 +227,8 @@ __global__ __launch_bounds__(kMcThreads) void k_mc_sum(const float *__restrict__
                                                        uint32_t *advance_epoch, uint32_t advance_inc)
 {
     if (advance_epoch && blockIdx.x == 0 && threadIdx.x == 0) advance_epoch[0] += advance_inc;   // nothing in this kernel draws
-    if (nsamples > kMcSplitAbove) mc_sum_split_body(y, y_sample_stride, nsamples, n, scale, out, accumulate, (int)blockIdx.x);
+    if constexpr (CHUNKED) mc_sum_split_body<true>(y, y_sample_stride, nsamples, n, scale, out, accumulate, (int)blockIdx.x);
+    else if (nsamples > kMcSplitAbove) mc_sum_split_body<false>(y, y_sample_stride, nsamples, n, scale, out, accumulate, (int)blockIdx.x);
     else mc_sum_body(y, y_sample_stride, nsamples, n, scale, out, accumulate, (int)blockIdx.x, (int)gridDim.x);
 }
 
@@ -408,11 +411,15 @@ int bnn_mc_sum(const float *y, int64_t y_sample_stride, int nsamples, int64_t n,
     if (n == 0) return advance_epoch ? bnn_rng_advance(advance_epoch, advance_inc, stream) : BNN_OK;
     unsigned grid = grid_for(n);
     if (nsamples > kMcSplitAbove) {
-        if (nsamples > 4 * kMcSplitMax || (n + 63) / 64 > 0x7FFFFFF0) { set_error("bnn_mc_sum: more than %d addends per output (or too many outputs)", 4 * kMcSplitMax); return BNN_E_RANGE; }
+        if ((n + 63) / 64 > 0x7FFFFFF0) { set_error("bnn_mc_sum: too many outputs"); return BNN_E_RANGE; }
         grid = (unsigned)((n + 63) / 64);
     }
-    hipLaunchKernelGGL(k_mc_sum, dim3(grid), dim3(kMcThreads), 0, (hipStream_t)stream, y, y_sample_stride,
-                       nsamples, n, scale, out, accumulate, advance_epoch, advance_inc);
+    if (nsamples > 4 * kMcSplitMax)
+        hipLaunchKernelGGL(k_mc_sum<true>, dim3(grid), dim3(kMcThreads), 0, (hipStream_t)stream, y, y_sample_stride,
+                           nsamples, n, scale, out, accumulate, advance_epoch, advance_inc);
+    else
+        hipLaunchKernelGGL(k_mc_sum<false>, dim3(grid), dim3(kMcThreads), 0, (hipStream_t)stream, y, y_sample_stride,
+                           nsamples, n, scale, out, accumulate, advance_epoch, advance_inc);
     return check_launch("bnn_mc_sum");
 }
 

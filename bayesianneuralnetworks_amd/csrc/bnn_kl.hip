@@ -27,7 +27,9 @@ __global__ __launch_bounds__(kKlThreads) void k_kl_final(KlFinal F, const double
 // Tail of an MC step in ONE launch: workgroups [0, gridDim.x - 1) run the MC reduction (and bump the device epoch), the
 // last one runs KL's second pass over the partials an earlier bnn_kl_forward_partial left in the workspace.  A launch
 // costs >= 4 us on MI355X whatever it does (k_rng_advance, 1 thread: 4.1 us); the BASELINE step had three such tails.
+// CHUNKED: as k_mc_sum.
 static_assert(kMcThreads == kKlThreads, "one block shape for both bodies");
+template <bool CHUNKED>
 __global__ __launch_bounds__(kKlThreads) void k_mc_sum_kl(const float *__restrict__ y, int64_t y_sample_stride, int nsamples,
                                                           int64_t n, float scale, float *__restrict__ out, int accumulate,
                                                           uint32_t *advance_epoch, uint32_t advance_inc,
@@ -39,7 +41,8 @@ __global__ __launch_bounds__(kKlThreads) void k_mc_sum_kl(const float *__restric
         return;
     }
     if (advance_epoch && blockIdx.x == 0 && threadIdx.x == 0) advance_epoch[0] += advance_inc;
-    if (nsamples > kMcSplitAbove) mc_sum_split_body(y, y_sample_stride, nsamples, n, scale, out, accumulate, (int)blockIdx.x);   // (uniform)
+    if constexpr (CHUNKED) mc_sum_split_body<true>(y, y_sample_stride, nsamples, n, scale, out, accumulate, (int)blockIdx.x);
+    else if (nsamples > kMcSplitAbove) mc_sum_split_body<false>(y, y_sample_stride, nsamples, n, scale, out, accumulate, (int)blockIdx.x);   // (uniform)
     else mc_sum_body(y, y_sample_stride, nsamples, n, scale, out, accumulate, (int)blockIdx.x, nmc);
 }
 
@@ -240,12 +243,15 @@ int bnn_mc_sum_kl(const float *y, int64_t y_sample_stride, int nsamples, int64_t
     int64_t b = (n + kMcThreads - 1) / kMcThreads;
     if (b > 2048) b = 2048;
     if (nsamples > kMcSplitAbove) {
-        if (nsamples > 4 * kMcSplitMax) { set_error("bnn_mc_sum_kl: more than %d addends per output", 4 * kMcSplitMax); return BNN_E_RANGE; }
         b = (n + 63) / 64;
         if (b > 0x7FFFFFF0) { set_error("bnn_mc_sum_kl: too many outputs"); return BNN_E_RANGE; }
     }
-    hipLaunchKernelGGL(k_mc_sum_kl, dim3((unsigned)b + 1), dim3(kKlThreads), 0, (hipStream_t)stream, y, y_sample_stride, nsamples, n,
-                       scale, out, accumulate, advance_epoch, advance_inc, F, reinterpret_cast<const double *>(workspace), kl_out);
+    if (nsamples > 4 * kMcSplitMax)
+        hipLaunchKernelGGL(k_mc_sum_kl<true>, dim3((unsigned)b + 1), dim3(kKlThreads), 0, (hipStream_t)stream, y, y_sample_stride, nsamples,
+                           n, scale, out, accumulate, advance_epoch, advance_inc, F, reinterpret_cast<const double *>(workspace), kl_out);
+    else
+        hipLaunchKernelGGL(k_mc_sum_kl<false>, dim3((unsigned)b + 1), dim3(kKlThreads), 0, (hipStream_t)stream, y, y_sample_stride, nsamples,
+                           n, scale, out, accumulate, advance_epoch, advance_inc, F, reinterpret_cast<const double *>(workspace), kl_out);
     return check_launch("bnn_mc_sum_kl");
 }
 

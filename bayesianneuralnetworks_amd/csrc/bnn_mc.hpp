@@ -32,27 +32,44 @@ __device__ __forceinline__ void mc_sum_body(const float *__restrict__ y, int64_t
 }
 
 // The same reduction for MANY addends per output (a fused head's ntn * NWN * S partial logits: 128 at the BASELINE layer): a
-// workgroup takes 64 outputs, its four waves a quarter of the addends each -- every load of a wave's quarter is requested before
-// the first add (one memory round trip instead of nsamples / 8) -- and the four sums are added in wave order through LDS:
-// fixed order, bitwise reproducible.  Launch with ceil(n / 64) workgroups of 256 threads.
+// workgroup takes 64 outputs, its four waves a quarter of ceil(nsamples / 4) addends each, summed from +0 in addend order, and
+// the four sums are added in wave order through LDS: fixed order, bitwise reproducible.  A wave requests kMcSplitMax loads before
+// its first add (one memory round trip instead of nsamples / 8); CHUNKED (quarters of more than kMcSplitMax addends) walks its
+// quarter in chunks of kMcSplitMax with the running sum carried over -- the same order; without it the body is one chunk.
+// Padding a chunk with +0 is exact (a sum that starts at +0 is never -0).  Launch with ceil(n / 64) workgroups of 256 threads.
 constexpr int kMcSplitAbove = 32;       // addends per output from which the launchers take this body
-constexpr int kMcSplitMax = 64;         // addends per wave held in registers: nsamples <= 4 * 64
+constexpr int kMcSplitMax = 64;         // addends per wave held in registers: one chunk up to nsamples <= 4 * 64
 
+template <bool CHUNKED>
 __device__ __forceinline__ void mc_sum_split_body(const float *__restrict__ y, int64_t y_sample_stride, int nsamples, int64_t n,
                                                   float scale, float *__restrict__ out, int accumulate, int block)
 {
     __shared__ float part[4][64];
     const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
     const int64_t i = (int64_t)block * 64 + lane;
-    const int per = (nsamples + 3) >> 2;
-    const int s0 = grp * per, s1 = s0 + per < nsamples ? s0 + per : nsamples;
     float a = 0.f;
-    if (i < n) {
-        float v[kMcSplitMax];
+    if constexpr (!CHUNKED) {
+        const int per = (nsamples + 3) >> 2;
+        const int s0 = grp * per, s1 = s0 + per < nsamples ? s0 + per : nsamples;
+        if (i < n) {
+            float v[kMcSplitMax];
 #pragma unroll
-        for (int j = 0; j < kMcSplitMax; ++j) v[j] = (s0 + j < s1) ? y[(int64_t)(s0 + j) * y_sample_stride + i] : 0.f;
+            for (int j = 0; j < kMcSplitMax; ++j) v[j] = (s0 + j < s1) ? y[(int64_t)(s0 + j) * y_sample_stride + i] : 0.f;
 #pragma unroll
-        for (int j = 0; j < kMcSplitMax; ++j) a += v[j];
+            for (int j = 0; j < kMcSplitMax; ++j) a += v[j];
+        }
+    } else {
+        const int64_t per = ((int64_t)nsamples + 3) >> 2;
+        const int64_t s1 = (grp + 1) * per < nsamples ? (grp + 1) * per : nsamples;
+        if (i < n) {
+            for (int64_t c = grp * per; c < s1; c += kMcSplitMax) {
+                float v[kMcSplitMax];
+#pragma unroll
+                for (int j = 0; j < kMcSplitMax; ++j) v[j] = (c + j < s1) ? y[(c + j) * y_sample_stride + i] : 0.f;
+#pragma unroll
+                for (int j = 0; j < kMcSplitMax; ++j) a += v[j];
+            }
+        }
     }
     part[grp][lane] = a;
     __syncthreads();

@@ -368,7 +368,6 @@ int bnn_mc_uncertainty(const float *y, int64_t addend_stride, int nparts, int ns
     if (nparts < 1 || nsamples < 1 || rows < 1 || classes < 1) { set_error("bnn_mc_uncertainty: bad extent"); return BNN_E_SHAPE; }
     if (nsamples > 65536) { set_error("bnn_mc_uncertainty: more than 65536 samples"); return BNN_E_RANGE; }
     if (classes > 4096) { set_error("bnn_mc_uncertainty: more than 4096 classes"); return BNN_E_RANGE; }
-    if (nparts > 4 * kMcSplitMax) { set_error("bnn_mc_uncertainty: more than %d parts", 4 * kMcSplitMax); return BNN_E_RANGE; }
     if (rows > 0x7FFFFFFF) { set_error("bnn_mc_uncertainty: more than 2^31 - 1 rows"); return BNN_E_RANGE; }
     if (kind != BNN_UNC_LOGITS && kind != BNN_UNC_PROBS) { set_error("bnn_mc_uncertainty: unknown kind %d", kind); return BNN_E_RANGE; }
     if ((int64_t)nparts * nsamples > 1 && addend_stride < rows * classes) {

@@ -314,9 +314,10 @@ int bnn_dense_forward_dropout(const void *x, int64_t x_sample_stride, int64_t ld
  *     partials[part][s][m][j],  part < bnn_dense_head_parts(M, N, nsamples),  fp32, M x n_head per (part, s);
  * partial 0 also carries the head's bias b_head (S x n_head fp32 or NULL).  The logits of sample s are the sum over `part`
  * (bnn_mc_sum with nsamples = parts, y_sample_stride = S * M * n_head, n = S * M * n_head), the predictive mean the sum over
- * (part, s) scaled by 1 / S (bnn_mc_sum / bnn_mc_sum_kl with nsamples = parts * S, y_sample_stride = M * n_head): one launch
- * (the head's own, >= 4 us) and the hidden activation's S * M * N * 2 bytes of stores fewer per forward.  Same bf16 products as
- * bnn_dense_forward twice; fp32 sums in another (fixed) order.
+ * (part, s) scaled by 1 / S (bnn_mc_sum / bnn_mc_sum_kl with nsamples = parts * S, y_sample_stride = M * n_head; parts * S
+ * is not bounded -- it passes 256 from S = 17 at the BASELINE widths): one launch (the head's own, >= 4 us) and the hidden
+ * activation's S * M * N * 2 bytes of stores fewer per forward.  Same bf16 products as bnn_dense_forward twice; fp32 sums in
+ * another (fixed) order.
  * replaces  two consecutive F.linear(x, *self.sampled)  pytorch_bayesian/nn/dense.py:60 (+ the ReLU between them) */
 int bnn_dense_head_parts(int64_t M, int64_t N, int nsamples);
 int bnn_dense_forward_head(const void *x, int64_t x_sample_stride, int64_t ldx,
@@ -624,8 +625,11 @@ int bnn_flipout_weight_backward(const float *g_w, int64_t g_w_sample_stride, con
 
 /* ---- MC reduction ----------------------------------------------------------
  * replaces  torch.stack(preds).mean(0)   examples/MNIST/uncertainty.py:50
- *   out[i] (+)= scale * sum_s y[s * y_sample_stride + i],  i < n   (nsamples <= 256; more than 32 addends per output -- the
- *   partial logits of bnn_dense_forward_head -- are summed by four waves per 64 outputs, fixed order).
+ *   out[i] (+)= scale * sum_s y[s * y_sample_stride + i],  i < n,  any nsamples >= 1, in a fixed order (bitwise reproducible):
+ *     nsamples <= 32: one fp32 sum from +0 in sample order;
+ *     nsamples > 32 (e.g. the partial logits of bnn_dense_forward_head): four quarters of ceil(nsamples / 4) consecutive
+ *     samples, each summed from +0 in sample order (a quarter may be empty: +0), then ((q0 + q1) + q2) + q3;
+ *   then times scale, and (accumulate) added to out[i] -- that add may be fused with the product (one rounding fewer).
  * advance_epoch (may be NULL): advance_epoch[0] += advance_inc in the same launch -- the
  * reduction is the tail of an MC step (every draw of the step has been consumed by the
  * kernels stream-ordered before it), so this saves the separate bnn_rng_advance launch. */
@@ -657,7 +661,7 @@ int bnn_mc_sum_kl(const float *y, int64_t y_sample_stride, int nsamples, int64_t
  *      BNN_UNC_LOGITS exact Shannon entropy: H(p_s) = lse(z_s) - sum_c p_s[c] z_s[c] (one log per sample and row), and
  *                     0 log 0 = 0 in total.  The two conventions differ by at most classes * 1e-10.
  *   The sums over samples are fp64, in a fixed sample order, without float atomics: bitwise reproducible run to run, and
- *   their error does not grow with S.  1 <= nsamples <= 65536, 1 <= classes <= 4096, 1 <= nparts <= 256,
+ *   their error does not grow with S.  1 <= nsamples <= 65536, 1 <= classes <= 4096, 1 <= nparts,
  *   1 <= rows <= 2^31 - 1 (BNN_E_SHAPE / BNN_E_RANGE otherwise).
  * Tails, as in bnn_mc_sum_kl: advance_epoch (may be NULL) += advance_inc in the same launch; kl_tensors != NULL: the second
  * pass of a KL begun by bnn_kl_forward_partial(kl_tensors, kl_ntensors, kl_workspace) runs as one extra workgroup, kl_out

@@ -221,7 +221,7 @@ def test_leading_row_dims_and_non_contiguous_input():
 
 @gpu
 @pytest.mark.parametrize("parts,S,M,C", [(3, 4, 37, 10), (16, 8, 512, 10), (33, 2, 9, 10), (100, 3, 5, 16), (5, 4, 6, 40),
-                                         (40, 2, 3, 1000)])
+                                         (40, 2, 3, 1000), (257, 2, 9, 10), (300, 3, 5, 16)])
 @pytest.mark.parametrize("inputs", ["logits", "probs"])
 def test_partial_logits_give_the_bits_of_logits_then_the_kernel(parts, S, M, C, inputs):
     """A fused head's partials (parts, S, M, C) summed in the launch: the same bits as HeadPartials.logits() (bnn_mc_sum over
