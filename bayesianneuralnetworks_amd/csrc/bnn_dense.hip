@@ -91,8 +91,22 @@ struct DrawLaunch {
 // kernel-argument segment by vector loads inside the sample loop -- the stores may alias it as far as the compiler
 // knows -- and every s_waitcnt vmcnt(0) on those loads also waited for the previous sample's store: PMC showed the
 // waves parked 47 % of the time.)
+// LEAN (kernel k_draw_lean): the body for launches whose draws are all Philox-7 / u16, with no conv taps, no Flipout and no
+// three-plane output (the host checks, bnn_draw_multi).  A kernel's VGPR budget is the maximum over ALL its paths: the
+// tap-group transpose, Flipout, three-plane stores and the Philox-10 branch of the sample loop put k_draw_multi<1> at 110
+// VGPRs = 4 waves per SIMD, against 56 for the lean body = 8.  The BASELINE launch is ~5000 waves: 1.2 rounds of 4096
+// slots at 4 waves per SIMD, one round of 8192 at 8.  Same code per element, same stream, same rounding -- only the paths
+// such a launch never takes are compiled out.
+template <int U, bool LEAN>
+__device__ __forceinline__ void draw_multi_body(const DrawLaunch &L);
+
 template <int U>
-__global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
+__global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L) { draw_multi_body<U, false>(L); }
+
+__global__ __launch_bounds__(256) void k_draw_lean(const DrawLaunch L) { draw_multi_body<1, true>(L); }
+
+template <int U, bool LEAN>
+__device__ __forceinline__ void draw_multi_body(const DrawLaunch &L)
 {
     // The KL's workgroups come FIRST in the grid: they are short (8 or 16 scalars per thread, no sample loop) and the dispatcher
     // hands workgroups out in index order -- at the end of the grid they waited for a draw workgroup to retire and became the
@@ -114,7 +128,7 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
     const int64_t t_stride = L.t[ti].out_sample_stride;
     const int t_rows = L.t[ti].rows, t_cols = L.t[ti].cols, t_ld = L.t[ti].ld;
     const bool t_bf16 = L.t[ti].bf16 != 0;
-    const bool t_x3 = L.t[ti].bf16 == 2;
+    const bool t_x3 = !LEAN && L.t[ti].bf16 == 2;
     const int t_taps = L.t[ti].perm_taps;
     const int t_kind = L.t[ti].kind;
     const RngDev rng = L.t[ti].rng;
@@ -137,6 +151,9 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
         }
         const int64_t e0 = (int64_t)local * 8;
         const bool live = e0 < (int64_t)t_rows * t_cols;
+        // the device epoch word is requested beside mu / rho, not behind sigma: a load issued there is a dependent round trip
+        // in front of the first Philox counter (tools/ubench_draw.hip (P): 17.97 -> 19.19 us with the word in memory)
+        const uint32_t edev = rng_epoch_dev(rng);
         float4 m0 = make_float4(0.f, 0.f, 0.f, 0.f), m1 = m0, r0 = m0, r1 = m0;
         if (live) {
             m0 = *reinterpret_cast<const float4 *>(t_mu + e0); m1 = *reinterpret_cast<const float4 *>(t_mu + e0 + 4);
@@ -161,10 +178,9 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
         const float m[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
         const float sg[8] = {sigma_draw(r0.x), sigma_draw(r0.y), sigma_draw(r0.z), sigma_draw(r0.w),
                              sigma_draw(r1.x), sigma_draw(r1.y), sigma_draw(r1.z), sigma_draw(r1.w)};
-        const uint32_t edev = rng_epoch_dev(rng);
         const PhiloxKeys keys = philox_keys(rng.key0, rng.key1);
         const uint32_t blk = (uint32_t)(e0 >> 2);
-        const bool gen16 = rng.gen == BNN_GEN_PHILOX7_U16;      // (wave-uniform)
+        const bool gen16 = LEAN || rng.gen == BNN_GEN_PHILOX7_U16;      // (wave-uniform)
         char *dst = t_out + ((int64_t)row * t_ld + c0) * esz2 + (int64_t)blockIdx.y * sbytes2;
         const int64_t step = sbytes2 * (int64_t)gridDim.y;
 #pragma unroll U
@@ -198,7 +214,7 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
         }
         return;
     }
-    if (L.t[ti].tapg) {
+    if (!LEAN && L.t[ti].tapg) {
         // ================= a conv weight (O, C, KH, KW), tap-major output =================
         // Element (o, c, t) sits at flat index (o C + c) taps + t and goes to column t C + c of row o.  A GROUP = the 8 taps
         // consecutive elements of 8 channels of one row = `taps` items of 8 consecutive elements (one 8-eps block each); its
@@ -308,7 +324,7 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
     char *const dst0 = t_out + orow * esz;
     const int64_t sbytes = t_stride * esz;
     const int64_t pbytes = sbytes * (t_kind == 3 ? 1 : L.nsamples);     // (three-plane output; kind 3: one copy, planes out_sample_stride apart)
-    if (t_kind == BNN_DRAW_FLIPOUT) {
+    if (!LEAN && t_kind == BNN_DRAW_FLIPOUT) {
         // Flipout (a linear weight, fp32 or bf16, no taps): w = mu + sigma R[row] S[c], the signs of the layer's ONE row of
         // rows + cols uniforms (sign contract).  A block of its own with a sample loop that is NOT unrolled: its sign blocks
         // stay out of the unrolled loop below, whose register budget every other draw of the launch pays for.
@@ -358,6 +374,7 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
     if (regular) {
         const bool pad = c0 >= t_cols;
         const int64_t e0 = pad ? 0 : (int64_t)row * t_cols + c0;
+        const uint32_t edev = rng_epoch_dev(rng);       // (beside mu / rho, as in the flat path)
         const float4 m0 = *reinterpret_cast<const float4 *>(t_mu + e0), m1 = *reinterpret_cast<const float4 *>(t_mu + e0 + 4);
         const float4 r0 = *reinterpret_cast<const float4 *>(t_rho + e0), r1 = *reinterpret_cast<const float4 *>(t_rho + e0 + 4);
         const float live = pad ? 0.f : 1.f;          // (0 * finite = 0; a NaN parameter would show in its own row anyway)
@@ -365,12 +382,11 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
                             pad ? 0.f : m1.x, pad ? 0.f : m1.y, pad ? 0.f : m1.z, pad ? 0.f : m1.w};
         const float sg[8] = {live * sigma_draw(r0.x), live * sigma_draw(r0.y), live * sigma_draw(r0.z), live * sigma_draw(r0.w),
                              live * sigma_draw(r1.x), live * sigma_draw(r1.y), live * sigma_draw(r1.z), live * sigma_draw(r1.w)};
-        const uint32_t edev = rng_epoch_dev(rng);
         const PhiloxKeys keys = philox_keys(rng.key0, rng.key1);
         const uint32_t blk = (uint32_t)(e0 >> 2);
         char *dst = dst0 + (int64_t)s_lo * sbytes;
         const int64_t step = sbytes * (int64_t)s_step;
-        const bool gen16 = rng.gen == BNN_GEN_PHILOX7_U16;      // (wave-uniform)
+        const bool gen16 = LEAN || rng.gen == BNN_GEN_PHILOX7_U16;      // (wave-uniform)
 #pragma unroll U
         for (int s = s_lo; s < s_hi; s += s_step, dst += step) {
             const uint32_t sample = rng.sample0 + (uint32_t)s;
@@ -398,6 +414,50 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
                 o.x = pack_bf16x2(w[0], w[1]); o.y = pack_bf16x2(w[2], w[3]);
                 o.z = pack_bf16x2(w[4], w[5]); o.w = pack_bf16x2(w[6], w[7]);
                 *reinterpret_cast<uint4 *>(dst) = o;
+            }
+        }
+        return;
+    }
+    if (LEAN) {
+        // the rest of a lean launch (biases, small or ragged tensors): the values of the general body below, with per-element
+        // loads and one store form per output dtype -- its branchier form alone would keep the lean kernel above 64 VGPRs.
+        // Padding groups (nval = 0) run the loop and store zeros.
+        const int64_t e0 = (int64_t)row * t_cols + c0;
+        const int nval = c0 >= t_cols ? 0 : t_cols - c0 < 8 ? t_cols - c0 : 8;
+        float m[8], sg[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const bool v = j < nval;
+            m[j] = v ? (t_kind != 2 ? t_mu[e0 + j] : sigma_accurate(t_rho[e0 + j])) : 0.f;
+            sg[j] = v && t_kind == 0 ? sigma_draw(t_rho[e0 + j]) : 0.f;
+        }
+        const uint32_t edev = rng_epoch_dev(rng);
+        const uint32_t blk = (uint32_t)(e0 >> 2);
+        for (int s = s_lo; s < s_hi; s += s_step) {
+            const uint32_t sample = rng.sample0 + (uint32_t)s;
+            float4 za = make_float4(0.f, 0.f, 0.f, 0.f), zb = za;
+            if (t_kind == 0) {
+                za = eps4_u16(rng, edev, blk, sample);          // (keys in SGPRs: a bias is a few draws per thread)
+                zb = eps4_u16(rng, edev, blk + 1u, sample);
+            }
+            float w[8];
+            w[0] = fmaf(sg[0], za.x, m[0]); w[1] = fmaf(sg[1], za.y, m[1]);
+            w[2] = fmaf(sg[2], za.z, m[2]); w[3] = fmaf(sg[3], za.w, m[3]);
+            w[4] = fmaf(sg[4], zb.x, m[4]); w[5] = fmaf(sg[5], zb.y, m[5]);
+            w[6] = fmaf(sg[6], zb.z, m[6]); w[7] = fmaf(sg[7], zb.w, m[7]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) w[j] = j < nval ? w[j] : 0.f;
+            char *dst = dst0 + s * sbytes;
+            if (t_bf16) {
+                // (bf16 rows are whole 16-B chunks: ld % 8 == 0, 16-B aligned output)
+                uint4 o;
+                o.x = pack_bf16x2(w[0], w[1]); o.y = pack_bf16x2(w[2], w[3]);
+                o.z = pack_bf16x2(w[4], w[5]); o.w = pack_bf16x2(w[6], w[7]);
+                *reinterpret_cast<uint4 *>(dst) = o;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (c0 + j < t_ld) reinterpret_cast<float *>(dst)[j] = w[j];
             }
         }
         return;
@@ -447,7 +507,10 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
     for (int s = s_lo; s < s_hi; s += s_step) {
         const uint32_t sample = rng.sample0 + (uint32_t)s;
         float4 za = make_float4(0.f, 0.f, 0.f, 0.f), zb = za;
-        if (t_kind == 0) {
+        if (LEAN && t_kind == 0) {
+            za = eps4_u16(rng, keys, edev, blk, sample);
+            zb = eps4_u16(rng, keys, edev, blk + 1u, sample);
+        } else if (t_kind == 0) {
             za = eps4(rng, keys, edev, blk, sample);
             zb = eps4(rng, keys, edev, blk + 1u, sample);
         }
@@ -469,7 +532,7 @@ __global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L)
             o.x = pack_bf16x2(w[0], w[1]); o.y = pack_bf16x2(w[2], w[3]);
             o.z = pack_bf16x2(w[4], w[5]); o.w = pack_bf16x2(w[6], w[7]);
             *reinterpret_cast<uint4 *>(dst) = o;
-        } else if (t_taps > 1) {
+        } else if (!LEAN && t_taps > 1) {
             // conv weight: element (o, c, tap) goes to column tap * C + c of row o (the implicit-GEMM kernel walks K
             // tap by tap, 64 channels at a time); the eps stream is addressed by the ORIGINAL flat index all the same
             const int Cn = t_cols / t_taps;
@@ -1955,7 +2018,15 @@ int bnn_draw_multi(const bnn_draw_tensor_t *tensors, int ntensors, int nsamples,
     static const int force_split = [] { const char *e = getenv("BNN_DRAW_SPLIT"); return e ? atoi(e) : 0; }();
     if (force_split >= 1 && force_split <= nsamples) split = force_split;
     static const int unroll = [] { const char *e = getenv("BNN_DRAW_UNROLL"); return e ? atoi(e) : 1; }();
-    if (unroll == 2) hipLaunchKernelGGL(k_draw_multi<2>, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
+    // the lean kernel when no tensor needs a path it compiles out (draw_multi_body: LEAN)
+    bool lean = true;
+    for (int i = 0; i < ntensors; ++i) {
+        const DrawTensorDev &d = L.t[i];
+        if (d.tapg || d.perm_taps > 1 || d.bf16 == 2 || d.kind == BNN_DRAW_FLIPOUT || (d.kind == 0 && d.rng.gen != BNN_GEN_PHILOX7_U16)) lean = false;
+    }
+    static const bool no_lean = [] { const char *e = getenv("BNN_DRAW_LEAN"); return e && e[0] == '0'; }();
+    if (lean && !no_lean && unroll <= 1) hipLaunchKernelGGL(k_draw_lean, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
+    else if (unroll == 2) hipLaunchKernelGGL(k_draw_multi<2>, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
     else if (unroll == 4) hipLaunchKernelGGL(k_draw_multi<4>, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
     else if (unroll == 8) hipLaunchKernelGGL(k_draw_multi<8>, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
     else

@@ -233,18 +233,35 @@ __device__ __forceinline__ float4 eps4(const RngDev &r, uint32_t epoch_dev, uint
     return z;
 }
 
+// BNN_GEN_PHILOX7_U16 only (a caller that knows the generator at compile time): quad `block`, keys in VGPRs
+__device__ __forceinline__ float4 eps4_u16(const RngDev &r, const PhiloxKeys &keys, uint32_t epoch_dev, uint32_t block,
+                                           uint32_t sample)
+{
+    float4 z;
+    const uint4 x = philox4x32_r<7>(make_uint4(block >> 1, r.stream_hi | (sample & 0xFFFFu), r.epoch_host, epoch_dev), keys);
+    const bool hi = (block & 1u) != 0;
+    box_muller16(hi ? x.z : x.x, z.x, z.y);
+    box_muller16(hi ? x.w : x.y, z.z, z.w);
+    return z;
+}
+
+// Same values with the keys in SGPRs (a few draws per thread: the 20 VGPRs of PhiloxKeys would cost more than they save)
+__device__ __forceinline__ float4 eps4_u16(const RngDev &r, uint32_t epoch_dev, uint32_t block, uint32_t sample)
+{
+    float4 z;
+    const uint4 x = philox4x32_r<7>(make_uint4(block >> 1, r.stream_hi | (sample & 0xFFFFu), r.epoch_host, epoch_dev), r.key0, r.key1);
+    const bool hi = (block & 1u) != 0;
+    box_muller16(hi ? x.z : x.x, z.x, z.y);
+    box_muller16(hi ? x.w : x.y, z.z, z.w);
+    return z;
+}
+
 // Same values with the round keys in VGPRs (keys = philox_keys(r.key0, r.key1), once per kernel).
 __device__ __forceinline__ float4 eps4(const RngDev &r, const PhiloxKeys &keys, uint32_t epoch_dev, uint32_t block,
                                        uint32_t sample)
 {
     float4 z;
-    if (r.gen == BNN_GEN_PHILOX7_U16) {
-        const uint4 x = philox4x32_r<7>(make_uint4(block >> 1, r.stream_hi | (sample & 0xFFFFu), r.epoch_host, epoch_dev), keys);
-        const bool hi = (block & 1u) != 0;
-        box_muller16(hi ? x.z : x.x, z.x, z.y);
-        box_muller16(hi ? x.w : x.y, z.z, z.w);
-        return z;
-    }
+    if (r.gen == BNN_GEN_PHILOX7_U16) return eps4_u16(r, keys, epoch_dev, block, sample);
     const uint4 x = philox4x32_10(make_uint4(block, r.stream_hi | (sample & 0xFFFFu),
                                              r.epoch_host, epoch_dev), keys);
     box_muller(x.x, x.y, z.x, z.y);
