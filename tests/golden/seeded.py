@@ -50,3 +50,19 @@ def mlp_posteriors(dims=(784, 1200, 1200, 10), seed=0):
 
 def mlp_input(batch=512, in_features=784, seed=1):
     return torch.randn(batch, in_features, generator=torch.Generator().manual_seed(seed))
+
+
+def pin_streams(module, base):
+    """Give every posterior tensor of `module` (a WeightNormal's `_stream`) and every layer's Flipout / MC-dropout stream
+    (`_flip_stream`, `_dropout_stream`) a fixed id base, base + 1, ... in module order, so that a test's draws depend on its own
+    seed and base only -- not on how many posterior tensors the tests before it created (`_rng.new_stream_id` counts per
+    process).  Returns the next free id.  Ids stay within 1 .. 65535 (the stream field of the Philox counter)."""
+    i = int(base)
+    for m in module.modules():
+        for attr in ("_stream", "_flip_stream", "_dropout_stream"):
+            if attr in m.__dict__:
+                if not 1 <= i <= 0xFFFF:
+                    raise ValueError("stream id %d outside 1 .. 65535" % i)
+                setattr(m, attr, i)
+                i += 1
+    return i

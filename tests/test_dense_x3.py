@@ -185,6 +185,7 @@ def test_fp32_mode_network_on_dense_path_equals_fused_kernels_and_oracle(env, di
             return self.layers(x)
 
     net = MLP().to(dev)
+    seeded.pin_streams(net, 1000)
     net.mc_batched = True
     fuse_activations(net, bf16_activations=True)
     x = torch.randn(B, dims[0], generator=gen).to(dev)

@@ -15,6 +15,7 @@ import tempfile
 
 import numpy as np
 import pytest
+import seeded
 import torch
 import torch.nn.functional as F
 
@@ -322,6 +323,7 @@ def test_fashion_batched_samples_differ_and_match_the_twin(dev, mode):
     S, B = 8, 32
     torch.manual_seed(1)
     net = FashionNet(samples=S).to(dev).eval()
+    seeded.pin_streams(net, 1000)
     net.mc_batched = True
     bnn.manual_seed(77)
     x = torch.randn(B, 1, 28, 28, device=dev)
@@ -350,6 +352,7 @@ def test_fashion_predictive_uncertainty_has_epistemic_part(dev, mode):
     S, B = 8, 48
     torch.manual_seed(2)
     net = FashionNet(samples=S).to(dev).eval()
+    seeded.pin_streams(net, 1010)
     net.mc_batched = True
     bnn.manual_seed(5)
     x = torch.randn(B, 1, 28, 28, device=dev)
@@ -472,6 +475,7 @@ def test_bf16_inference_pass_launches(dev):
     lib = _lib.load()
     torch.manual_seed(6)
     net = FashionNet(samples=8).to(dev).eval()
+    seeded.pin_streams(net, 1020)
     net.mc_batched = True
     x = torch.randn(64, 1, 28, 28, device=dev)
     with torch.no_grad():
@@ -490,6 +494,7 @@ def test_captured_graph_replays_fresh_signs(dev):
     bnn.set_compute("bf16")
     torch.manual_seed(7)
     net = FashionNet(samples=4).to(dev).eval()
+    seeded.pin_streams(net, 1030)
     net.mc_batched = True
     x = torch.randn(16, 1, 28, 28, device=dev)
     cell = _rng.default_generator.epoch_dev(dev)
@@ -520,6 +525,7 @@ def test_fashion_training_gradients(dev, mode):
     S, B = 4, 16
     torch.manual_seed(3)
     net = FashionNet(samples=S).to(dev).train()
+    seeded.pin_streams(net, 1040)
     net.mc_batched = True
     ref_net = FashionNet(samples=S).double().train()
     ref_net.load_state_dict({k: v.detach().cpu().double() if v.is_floating_point() else v.cpu() for k, v in net.state_dict().items()})

@@ -12,6 +12,7 @@ import re
 
 import numpy as np
 import pytest
+import seeded
 import torch
 import torch.nn.functional as F
 
@@ -272,6 +273,7 @@ def test_titanic_batched_samples_differ_and_match_the_twin(dev, mode, S):
     bnn.set_compute(mode)
     torch.manual_seed(1)
     net = Titanic(samples=S).to(dev)
+    seeded.pin_streams(net, 1000)
     net.mc_batched = True
     bnn.manual_seed(77)
     x = torch.randn(64, 9, device=dev)
@@ -293,6 +295,7 @@ def test_titanic_batched_samples_differ_and_match_the_twin(dev, mode, S):
 def test_titanic_predictive_uncertainty_has_epistemic_part(dev):
     torch.manual_seed(2)
     net = Titanic(samples=16).to(dev)
+    seeded.pin_streams(net, 1010)
     net.mc_batched = True
     bnn.manual_seed(5)
     x = torch.randn(128, 9, device=dev)
@@ -406,6 +409,7 @@ def test_titanic_training_gradients(dev, mode):
     S, B = 10, 96
     torch.manual_seed(3)
     net = Titanic(samples=S).to(dev)
+    seeded.pin_streams(net, 1020)
     net.mc_batched = True
     bnn.manual_seed(9)
     x = torch.randn(B, 9, device=dev)

@@ -11,6 +11,7 @@ import ctypes
 
 import numpy as np
 import pytest
+import seeded
 import torch
 import torch.nn.functional as F
 
@@ -189,9 +190,10 @@ class MLP(BayesianNetworkModule):
         return self.layers(x)
 
 
-def _net(seed):
+def _net(seed, base=1000):
     torch.manual_seed(seed)
     net = MLP([784, 1200, 1200, 10], 4).to(DEV)
+    seeded.pin_streams(net, base)
     net.mc_batched = True
     fuse_activations(net, bf16_activations=True, fuse_head=True)
     return net
@@ -233,10 +235,39 @@ def _net_ref64(net, x, S, bf16):
     return torch.stack(outs), wmax, hmax
 
 
-def _head_tol(want, wmax, hmax):
-    """test_fused_head_equals_two_dense_launches_and_double's tolerance: 1e-5 of the output scale, plus one bf16 ulp of one head
-    addend (a hidden value within fp32 rounding of a bf16 boundary may round the other way)."""
-    return 1e-5 + 2.0 ** -8 * wmax * hmax / max(1.0, float(want.pow(2).mean().sqrt()))
+def _device_chain_ref64(net, x, S, h1):
+    """The bf16 mode's chain checked layer by layer in float64 on the device's own operands (bf16ref): the weights drawn again on
+    the layers' recorded keys (the draw kernels are checked against their twins elsewhere), the hidden layer 1 the net stored (h1, captured) and the hidden layer 2
+    of a plain dense launch on it.  Each stored hidden value must be a bf16 rounding of a value within the accumulation bound of
+    its exact float64 value.  -> (want (S, M, 10) float64 logits on the stored hidden values, acc (S, M, 10) their accumulation
+    bound, a (S, M, 10) the head's sum |h| |w| + |b|)."""
+    from bf16ref import chain_layer, relu, rounding_interval
+    lins = [net.layers[0], net.layers[2], net.layers[4]]
+    pre = ops.draw_layers([(l.weight.mean, l.weight.scale, l.bias.mean, l.bias.scale, l.weight.draw_key, l.bias.draw_key)
+                           for l in lins], S)
+    M = x.shape[0]
+    assert h1.dtype == torch.bfloat16 and h1.numel() == S * M * 1200, (h1.dtype, tuple(h1.shape))
+    h1 = h1.reshape(S, M, 1200).contiguous()                # whatever the captured view's pitch: dense rows, samples M * K apart
+    h2 = ops._dense_raw(h1, M * 1200, M, pre[1], 1200, True, torch.bfloat16)
+    xb = x.bfloat16().double().cpu()
+    want, acc, a_head = [], [], []
+    for s in range(S):
+        ws = []
+        for li, lin in enumerate(lins):
+            K = lin.weight.mean.shape[1]
+            w = pre[li].w[s, :, :K].double().cpu()
+            b = pre[li].b[s].double().cpu()
+            ws.append((w, b))
+        h = xb
+        for li, dev_h in enumerate((h1[s], h2[s])):
+            t, bnd, _, _ = chain_layer(h, None, *ws[li])
+            lo, hi = rounding_interval(t, bnd, relu)
+            h = dev_h.double().cpu()
+            out = (h < lo) | (h > hi)
+            assert not bool(out.any()), ("stored hidden %d outside its rounding interval" % (li + 1), s, int(out.sum()))
+        t, bnd, _, a = chain_layer(h, None, *ws[2])
+        want.append(t); acc.append(bnd); a_head.append(a)
+    return torch.stack(want), torch.stack(acc), torch.stack(a_head)
 
 
 def _softmax_unc_tol(C, dz):
@@ -251,22 +282,39 @@ def _check_module(net, x, S, seed, bf16):
     assert parts >= 1
     with torch.no_grad():
         bnn.manual_seed(seed)
-        pm = net.predictive_mean(x, S)
+        box = []
+        hnd = net.layers[2].register_forward_pre_hook(lambda m, a: box.append(a[0]))
+        try:
+            pm = net.predictive_mean(x, S)
+        finally:
+            hnd.remove()
         keys = (net.layers[0].weight.draw_key, net.layers[4].weight.draw_key)
         assert keys[0].nsamples == S and keys[1].nsamples == S
-        want, wmax, hmax = _net_ref64(net, x, S, bf16)
-        wm = want.mean(0)
-        tol = _head_tol(wm, wmax, hmax) if bf16 else 1e-5
-        assert_close_scaled(pm.double().cpu().numpy(), wm.numpy(), tol, "predictive_mean S = %d (%d parts)" % (S, parts))
+        if bf16:
+            # derived bounds (bf16ref) on the device's own operands: the logits within their accumulation bound; the mean within
+            # the mean of those plus the reduction's own rounding (parts x S addends, the 1 / S scale)
+            assert len(box) == 1
+            want, acc, a_head = _device_chain_ref64(net, x, S, box[0])
+            wm = want.mean(0)
+            from bf16ref import gamma
+            bound_pm = acc.mean(0) + gamma(parts * S + 2) * (a_head + acc).mean(0)
+            err = (pm.double().cpu() - wm).abs()
+            assert bool((err <= bound_pm).all()), ("predictive_mean S = %d (%d parts)" % (S, parts), float((err / bound_pm).max()),
+                                                   int((err > bound_pm).sum()))
+        else:
+            want, _, _ = _net_ref64(net, x, S, False)
+            wm = want.mean(0)
+            assert_close_scaled(pm.double().cpu().numpy(), wm.numpy(), 1e-5, "predictive_mean S = %d (%d parts)" % (S, parts))
         # the same draws through the uncertainty launch; each sample's logits against float64
         bnn.manual_seed(seed)
         hp = net._forward_batched_stacked(x, S, 0, _lazy_head=True)
         assert isinstance(hp, ops.HeadPartials) and hp.p.shape == (parts, S, M, 10)
         lg = hp.logits()
-        # per sample, nothing averages the bf16 roundings out: both hidden layers round to bf16, and one row may meet a
-        # second hidden value on the other side of a boundary -- two head addends' ulps
-        tol_s = 1e-5 + 2 * (_head_tol(want, wmax, hmax) - 1e-5) if bf16 else 1e-5
-        assert_close_scaled(lg.double().cpu().numpy(), want.numpy(), tol_s, "logits S = %d" % S)
+        if bf16:
+            err = (lg.double().cpu() - want).abs()
+            assert bool((err <= acc).all()), ("logits S = %d" % S, float((err / acc).max()), int((err > acc).sum()))
+        else:
+            assert_close_scaled(lg.double().cpu().numpy(), want.numpy(), 1e-5, "logits S = %d" % S)
         dz = float((lg.double().cpu() - want).abs().max())
         bnn.manual_seed(seed)
         u = net.predictive_uncertainty(x, S, inputs="logits")
@@ -293,6 +341,57 @@ def test_fused_head_mlp_across_sample_counts_vs_float64(S):
         bnn.set_compute("f32")
     if S in (17, 20):
         assert parts * S > 256, (parts, S)
+
+
+SWEEP_BASES = [1, 411, 2000, 9001, 30011, 65000]          # pinned stream bases: six different draws of every posterior
+
+
+@gpu
+@pytest.mark.parametrize("S", [1, 8, 17, 300])
+@pytest.mark.parametrize("base", SWEEP_BASES)
+def test_fused_head_mlp_over_pinned_draws(base, S):
+    """The S-sweep's check on six pinned draws each: a kernel must pass on many draws, not on one."""
+    net = _net(5, base)
+    x = torch.randn(64, 784, generator=torch.Generator().manual_seed(S)).to(DEV)
+    bnn.set_compute("bf16")
+    try:
+        _check_module(net, x, S, 100 + S, True)
+    finally:
+        bnn.set_compute("f32")
+
+
+def _predictive_mean_s1():
+    """test_fused_head_mlp_across_sample_counts_vs_float64[1]'s predictive mean (its net, input, seed and pinned streams)."""
+    net = _net(5)
+    x = torch.randn(64, 784, generator=torch.Generator().manual_seed(1)).to(DEV)
+    bnn.set_compute("bf16")
+    try:
+        with torch.no_grad():
+            bnn.manual_seed(101)
+            return net.predictive_mean(x, 1).cpu()
+    finally:
+        bnn.set_compute("f32")
+
+
+@gpu
+def test_fused_head_draws_do_not_depend_on_what_ran_before(tmp_path):
+    """The S = 1 fused-head predictive mean in a fresh process, and here after 1000 unrelated posterior tensors took stream ids:
+    bit for bit the same (pinned streams: a test's draws are its own)."""
+    import os
+    import subprocess
+    import sys
+    from bayesianneuralnetworks_amd.nn.core import WeightNormal
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "pm.pt")
+    code = ("import sys, torch; sys.path[:0] = [%r, %r, %r]; import test_mc_sample_counts as t; "
+            "torch.save(t._predictive_mean_s1(), %r)" % (root, os.path.join(root, "tests"), os.path.join(root, "tests", "golden"), out))
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, timeout=300, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    fresh = torch.load(out)
+    unrelated = [WeightNormal(1) for _ in range(1000)]
+    assert unrelated[-1]._stream - unrelated[0]._stream == 999
+    here = _predictive_mean_s1()
+    assert here.dtype == fresh.dtype and torch.equal(here.view(torch.int32), fresh.view(torch.int32))
 
 
 @gpu

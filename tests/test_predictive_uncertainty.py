@@ -11,6 +11,7 @@ import re
 
 import numpy as np
 import pytest
+import seeded
 import torch
 
 import bayesianneuralnetworks_amd as bnn
@@ -260,6 +261,7 @@ def test_fused_head_mlp_costs_no_extra_launch():
     lib = _lib.load()
     torch.manual_seed(1)
     net = MLP([784, 1200, 1200, 10], samples=8).to(DEV)
+    seeded.pin_streams(net, 1000)
     net.mc_batched = True
     fuse_activations(net, bf16_activations=True, fuse_head=True)
     x = torch.randn(512, 784, device=DEV)
@@ -299,6 +301,7 @@ def test_fused_head_mlp_costs_no_extra_launch():
 def test_module_paths_equal_the_op_on_forward_stacked(mode, batched):
     torch.manual_seed(2)
     net = MLP([64, 96, 10], samples=6).to(DEV)
+    seeded.pin_streams(net, 1010)
     net.mc_batched = batched
     x = torch.randn(130, 64, device=DEV)
     bnn.set_compute(mode)
