@@ -77,6 +77,13 @@ class Conv2dShape(ctypes.Structure):
                  "dil_h", "dil_w", "groups")]
 
 
+class Conv3dShape(ctypes.Structure):
+    """bnn_conv3d_shape_t"""
+    _fields_ = [(n, ctypes.c_int64) for n in
+                ("B", "C", "D", "H", "W", "O", "KD", "KH", "KW", "stride_d", "stride_h", "stride_w",
+                 "pad_d", "pad_h", "pad_w", "dil_d", "dil_h", "dil_w", "groups")]
+
+
 _p = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
@@ -150,6 +157,10 @@ SIGNATURES = {
     "bnn_conv2d_col2im": (_int, [_p, ctypes.POINTER(Conv2dShape), _int, _int, _p, _p]),
     "bnn_nchw_to_rows": (_int, [_p, _i64, _int, _int, _p, _int, _p]),
     "bnn_conv2d_workspace_bytes": (_i64, [ctypes.POINTER(Conv2dShape), _int, _int]),
+    "bnn_conv3d_forward_drawn": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p]),
+    "bnn_conv3d_backward_input": (_int, [_p, _p, _i64, _p, _int, ctypes.POINTER(Conv3dShape), _int, _int, _p]),
+    "bnn_conv3d_backward_weight_workspace_bytes": (_i64, [ctypes.POINTER(Conv3dShape), _int]),
+    "bnn_conv3d_backward_weight": (_int, [_p, _i64, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p, _i64, _p]),
     "bnn_conv2d_forward_sampled": (_int, [_p, _i64, _p, _p, _p, _p, _p, _i64,
                                           ctypes.POINTER(Conv2dShape), _int, _rngp, _rngp, _int, _int, _p, _i64, _p]),
     "bnn_conv2d_forward": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, ctypes.POINTER(Conv2dShape),

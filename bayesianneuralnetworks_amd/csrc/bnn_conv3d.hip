@@ -1,0 +1,493 @@
+// bnn_conv3d.hip -- NormalConv3d (pytorch_bayesian/nn/conv.py:122-142) on drawn weights as implicit GEMMs, forward and backward.
+//
+// One tile skeleton serves the three contractions (C[m][n] = sum_r A(m, r) B(n, r), 128 x 64 x 32 tiles, 4 waves of 64 x 32):
+//   FWD   m = (b, od, oh, ow), n = o,        r = (c, kd, kh, kw): A gathered from x (im2col in the loader's address arithmetic,
+//         padding reads zero), B = the sample's drawn weight row.  Epilogue: + drawn bias, fp32 NCDHW store.
+//   DGRAD m = (b, id, ih, iw), n = c,        r = (o, kd, kh, kw): A gathered from gy (taps no stride step reaches read zero),
+//         B = the same weights read transposed.  A shared input sums its S samples inside the reduction loop, in sample order.
+//   WGRAD m = (c, kd, kh, kw), n = o,        r = (b, od, oh, ow): A = the forward's gather of x, B = gy.  The long reduction is
+//         split into slabs (gridDim.z); k_conv3d_slab_sum adds the slabs in slab order.
+// bf16 compute: operands rounded to bf16 as they are written to LDS, v_mfma_f32_16x16x32_bf16.  fp32: v_mfma_f32_16x16x4_f32, the
+// reduction a k-ordered fp32 fma chain per tile.  Every sum is in a fixed order and there are no atomics: two identical calls
+// give identical bits.  Indices inside one sample are 32-bit (the host refuses a per-sample tensor of 2^31 elements or more).
+#include "bnn_device.hpp"
+
+#include <algorithm>
+
+namespace bnn {
+
+constexpr int C3_BM = 128, C3_BN = 64, C3_BK = 32, C3_THREADS = 256;
+enum { C3_FWD = 0, C3_DGRAD = 1, C3_WGRAD = 2 };
+
+// n / d for n < 2^31 by multiply-high and shift (d >= 1)
+struct FastDiv { uint32_t d, mul, shift; };
+
+static FastDiv make_div(uint32_t d)
+{
+    FastDiv f;
+    f.d = d;
+    uint32_t s = 0;
+    while (s < 32 && (1ull << s) < d) ++s;
+    f.shift = s;
+    f.mul = (uint32_t)(((1ull << 32) * ((1ull << s) - d)) / d + 1);
+    return f;
+}
+
+__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv &f) { return (__umulhi(n, f.mul) + n) >> f.shift; }
+
+struct Conv3dGeo {
+    int32_t B, C, D, H, W, O, KD, KH, KW, OD, OH, OW;
+    int32_t sd, sh, sw, pd, ph, pw, dd, dh, dw, groups, Cg, Ng;
+    int32_t T, K, P, Pin;                    // taps, Cg * taps, OD OH OW, D H W
+    FastDiv fOW, fOH, fP, fW, fH, fPin, fKW, fKH, fT, fsd, fsh, fsw;
+};
+
+struct Conv3dArgs {
+    const float *x; int64_t x_ss;            // fp32 NCDHW, sample stride (0: shared)
+    const float *gy;                         // fp32 S x B x O x P
+    const void *w; int64_t w_ss;             // S x O x K (bf16 or fp32), sample stride
+    const float *bias; int64_t b_ss;         // FWD: S x O drawn bias or NULL
+    float *out;                              // FWD: y; DGRAD: gx; WGRAD: slab base (or gw when nslab == 1)
+    int32_t S, shared, nslab, chunk;         // WGRAD: slabs per (sample, group), reduction positions per slab (% C3_BK == 0)
+};
+
+template <typename T> struct Op;
+template <> struct Op<float> {
+    static constexpr int LDK = C3_BK + 4;
+    __device__ static float ld(const void *p, int64_t i) { return static_cast<const float *>(p)[i]; }
+};
+template <> struct Op<uint16_t> {
+    static constexpr int LDK = C3_BK + 8;    // 80-B rows: the 16-B fragment reads stay aligned
+    __device__ static float ld(const void *p, int64_t i)
+    {
+        return __uint_as_float((uint32_t)static_cast<const uint16_t *>(p)[i] << 16);
+    }
+};
+
+__device__ __forceinline__ void st_lds(float *p, float v) { *p = v; }
+__device__ __forceinline__ void st_lds(uint16_t *p, float v) { *p = f2bf(v); }
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(C3_THREADS) void k_conv3d(const Conv3dGeo g, const Conv3dArgs a)
+{
+    constexpr int LDK = Op<T>::LDK;
+    __shared__ __attribute__((aligned(16))) T As[C3_BM * LDK];
+    __shared__ __attribute__((aligned(16))) T Bs[C3_BN * LDK];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave & 1, wn = wave >> 1;
+
+    // the block's (sample, group, slab)
+    int z = blockIdx.z, slab = 0;
+    if (MODE == C3_WGRAD) { slab = z % a.nslab; z /= a.nslab; }
+    const int grp = z % g.groups;
+    const int s = z / g.groups;              // DGRAD with a shared input: 0 (the samples are summed below)
+
+    const int32_t M = MODE == C3_FWD ? g.B * g.P : MODE == C3_DGRAD ? g.B * g.Pin : g.K;
+    const int32_t N = MODE == C3_DGRAD ? g.Cg : g.Ng;
+    const int32_t m0 = blockIdx.x * C3_BM, n0 = blockIdx.y * C3_BN;
+    int32_t rbeg = 0, rend = MODE == C3_FWD ? g.K : MODE == C3_DGRAD ? g.Ng * g.T : g.B * g.P;
+    if (MODE == C3_WGRAD) {
+        rbeg = slab * a.chunk;
+        rend = min(rend, rbeg + a.chunk);
+    }
+    const int nsum = (MODE == C3_DGRAD && a.shared) ? a.S : 1;
+
+    // ---- A loader: row ar of the tile, reduction offsets ah * 16 .. + 15 of each k-tile
+    const int ar = tid & (C3_BM - 1);
+    const int ah = __builtin_amdgcn_readfirstlane(tid >> 7);
+    const int32_t am = m0 + ar;
+    const bool arow = am < M;
+    int32_t abase = 0, z0 = 0, z1 = 0, z2 = 0;   // FWD / DGRAD: gather origin of the row; WGRAD: its tap
+    if (MODE == C3_FWD && arow) {
+        const uint32_t b = fdiv(am, g.fP), p = am - b * g.P;
+        const uint32_t q = fdiv(p, g.fOW), ow = p - q * g.OW, od = fdiv(q, g.fOH), oh = q - od * g.OH;
+        z0 = od * g.sd - g.pd; z1 = oh * g.sh - g.ph; z2 = ow * g.sw - g.pw;
+        abase = (b * g.C + grp * g.Cg) * g.Pin;
+    } else if (MODE == C3_DGRAD && arow) {
+        const uint32_t b = fdiv(am, g.fPin), p = am - b * g.Pin;
+        const uint32_t q = fdiv(p, g.fW), iw = p - q * g.W, id = fdiv(q, g.fH), ih = q - id * g.H;
+        z0 = id + g.pd; z1 = ih + g.ph; z2 = iw + g.pw;
+        abase = (b * g.O + grp * g.Ng) * g.P;
+    } else if (MODE == C3_WGRAD && arow) {
+        const uint32_t c = fdiv(am, g.fT), t = am - c * g.T;
+        const uint32_t q = fdiv(t, g.fKW), kw = t - q * g.KW, kd = fdiv(q, g.fKH), kh = q - kd * g.KH;
+        z0 = kd * g.dd - g.pd; z1 = kh * g.dh - g.ph; z2 = kw * g.dw - g.pw;
+        abase = (grp * g.Cg + c) * g.Pin;
+    }
+
+    auto fetch_a = [&](int sm, int32_t r0, float (&v)[16]) {
+        int32_t r = r0 + ah * 16;
+        if (MODE == C3_WGRAD) {
+            // reduction index = output position (b, od, oh, ow), stepped with carries
+            const float *x = a.x + (int64_t)s * a.x_ss;
+            uint32_t b = 0, od = 0, oh = 0, ow = 0;
+            if (r < rend) {
+                b = fdiv(r, g.fP);
+                const uint32_t p = r - b * g.P, q = fdiv(p, g.fOW);
+                ow = p - q * g.OW; od = fdiv(q, g.fOH); oh = q - od * g.OH;
+            }
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int32_t id = (int32_t)(od * g.sd) + z0, ih = (int32_t)(oh * g.sh) + z1, iw = (int32_t)(ow * g.sw) + z2;
+                const bool ok = arow && r + j < rend && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H &&
+                                (uint32_t)iw < (uint32_t)g.W;
+                v[j] = ok ? x[(int64_t)b * g.C * g.Pin + abase + (id * g.H + ih) * g.W + iw] : 0.f;
+                if (++ow == (uint32_t)g.OW) { ow = 0; if (++oh == (uint32_t)g.OH) { oh = 0; if (++od == (uint32_t)g.OD) { od = 0; ++b; } } }
+            }
+            return;
+        }
+        // reduction index = (channel, kd, kh, kw), stepped with carries
+        const float *src = MODE == C3_FWD ? a.x + (int64_t)s * a.x_ss : a.gy + (int64_t)(s + sm) * g.B * g.O * g.P;
+        uint32_t c = 0, kd = 0, kh = 0, kw = 0;
+        if (r < rend) {
+            c = fdiv(r, g.fT);
+            const uint32_t t = r - c * g.T, q = fdiv(t, g.fKW);
+            kw = t - q * g.KW; kd = fdiv(q, g.fKH); kh = q - kd * g.KH;
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            bool ok = arow && r + j < rend;
+            int32_t off = 0;
+            if (MODE == C3_FWD) {
+                const int32_t id = z0 + (int32_t)kd * g.dd, ih = z1 + (int32_t)kh * g.dh, iw = z2 + (int32_t)kw * g.dw;
+                ok = ok && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H && (uint32_t)iw < (uint32_t)g.W;
+                off = (int32_t)c * g.Pin + (id * g.H + ih) * g.W + iw;
+            } else {
+                const int32_t nd = z0 - (int32_t)kd * g.dd, nh = z1 - (int32_t)kh * g.dh, nw = z2 - (int32_t)kw * g.dw;
+                ok = ok && nd >= 0 && nh >= 0 && nw >= 0;
+                const uint32_t od = fdiv(ok ? nd : 0, g.fsd), oh = fdiv(ok ? nh : 0, g.fsh), ow = fdiv(ok ? nw : 0, g.fsw);
+                ok = ok && (int32_t)(od * g.sd) == nd && (int32_t)(oh * g.sh) == nh && (int32_t)(ow * g.sw) == nw &&
+                     od < (uint32_t)g.OD && oh < (uint32_t)g.OH && ow < (uint32_t)g.OW;
+                off = (int32_t)c * g.P + (int32_t)((od * g.OH + oh) * g.OW + ow);
+            }
+            v[j] = ok ? src[abase + off] : 0.f;
+            if (++kw == (uint32_t)g.KW) { kw = 0; if (++kh == (uint32_t)g.KH) { kh = 0; if (++kd == (uint32_t)g.KD) { kd = 0; ++c; } } }
+        }
+    };
+
+    // ---- B loader: reduction offset bk of each k-tile, rows bn + 8 i of the tile
+    const int bk = tid & (C3_BK - 1), bn = tid >> 5;
+    auto fetch_b = [&](int sm, int32_t r0, float (&v)[8]) {
+        const int32_t r = r0 + bk;
+        const bool rok = r < rend;
+        if (MODE == C3_WGRAD) {
+            uint32_t b = 0, p = 0;
+            if (rok) { b = fdiv(r, g.fP); p = r - b * g.P; }
+            const float *gy = a.gy + ((int64_t)s * g.B + b) * g.O * g.P + (int64_t)grp * g.Ng * g.P + p;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int32_t n = n0 + bn + 8 * i;
+                v[i] = (rok && n < N) ? gy[(int64_t)n * g.P] : 0.f;
+            }
+            return;
+        }
+        const int64_t wb = (int64_t)(s + sm) * a.w_ss + (int64_t)grp * g.Ng * g.K;
+        int32_t roff = r;                               // FWD: w[o][r]
+        int32_t nstride = g.K;
+        if (MODE == C3_DGRAD) {                         // r = (o, tap): w[o][c][tap]
+            const uint32_t o = fdiv(rok ? r : 0, g.fT);
+            roff = (int32_t)(o * g.K + (r - o * g.T));
+            nstride = g.T;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int32_t n = n0 + bn + 8 * i;
+            v[i] = (rok && n < N) ? Op<T>::ld(a.w, wb + (int64_t)n * nstride + roff) : 0.f;
+        }
+    };
+
+    auto store_tiles = [&](const float (&va)[16], const float (&vb)[8]) {
+        T *pa = As + ar * LDK + ah * 16;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) st_lds(pa + j, va[j]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) st_lds(Bs + (bn + 8 * i) * LDK + bk, vb[i]);
+    };
+
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    f32x4 acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int ntile = rend > rbeg ? (rend - rbeg + C3_BK - 1) / C3_BK : 0;
+    const int nstep = nsum * ntile;
+    float va[16], vb[8];
+    if (nstep > 0) { fetch_a(0, rbeg, va); fetch_b(0, rbeg, vb); }
+    for (int step = 0; step < nstep; ++step) {
+        __syncthreads();                                // the previous tile's fragment reads are done
+        store_tiles(va, vb);
+        __syncthreads();
+        if (step + 1 < nstep) {                         // the next tile's loads fly under this tile's MFMAs
+            const int nx = step + 1, sm = nx / ntile;
+            const int32_t r0 = rbeg + (nx - sm * ntile) * C3_BK;
+            fetch_a(sm, r0, va);
+            fetch_b(sm, r0, vb);
+        }
+        if constexpr (sizeof(T) == 2) {
+            typedef short s16x8 __attribute__((ext_vector_type(8)));
+            s16x8 fa[4], fb[2];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                fa[i] = *reinterpret_cast<const s16x8 *>(As + (wm * 64 + i * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                fb[j] = *reinterpret_cast<const s16x8 *>(Bs + (wn * 32 + j * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < C3_BK / 4; ++kk) {
+                float fa[4], fb[2];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) fa[i] = As[(wm * 64 + i * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) fb[j] = Bs[(wn * 32 + j * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+            }
+        }
+    }
+
+    // ---- epilogue: lane holds C[(lane >> 4) * 4 + q][lane & 15] of each 16 x 16 block
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
+        if (n >= N) continue;
+        float bias = 0.f;
+        if (MODE == C3_FWD && a.bias) bias = a.bias[(int64_t)s * a.b_ss + grp * g.Ng + n];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int32_t m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + q;
+                if (m >= M) continue;
+                const float v = acc[i][j][q];
+                if (MODE == C3_FWD) {
+                    const uint32_t b = fdiv(m, g.fP), p = m - b * g.P;
+                    a.out[(int64_t)s * g.B * g.O * g.P + (b * g.O + grp * g.Ng + n) * g.P + p] = v + bias;
+                } else if (MODE == C3_DGRAD) {
+                    const uint32_t b = fdiv(m, g.fPin), p = m - b * g.Pin;
+                    a.out[(int64_t)s * g.B * g.C * g.Pin + (b * g.C + grp * g.Cg + n) * g.Pin + p] = v;
+                } else {
+                    // slab [slab][s][o][k] (gw itself when there is one slab)
+                    a.out[(((int64_t)slab * a.S + s) * g.O + grp * g.Ng + n) * g.K + m] = v;
+                }
+            }
+    }
+}
+
+// gw[e] = sum of the slabs in slab order
+__global__ __launch_bounds__(256) void k_conv3d_slab_sum(const float *__restrict__ slabs, int64_t slab_stride, int nslab,
+                                                        float *__restrict__ gw, int64_t n)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    float v = 0.f;
+    for (int k = 0; k < nslab; ++k) v += slabs[(int64_t)k * slab_stride + e];
+    gw[e] = v;
+}
+
+// gb[s][o] = sum over (b, position) of gy[s][b][o][.]: one workgroup per (s, o), fixed strided partials and a fixed tree
+__global__ __launch_bounds__(256) void k_conv3d_bias_grad(const float *__restrict__ gy, float *__restrict__ gb, int32_t B, int32_t O,
+                                                         int32_t P)
+{
+    __shared__ float red[256];
+    const int o = blockIdx.x, s = blockIdx.y;
+    float v = 0.f;
+    for (int32_t b = 0; b < B; ++b) {
+        const float *row = gy + (((int64_t)s * B + b) * O + o) * P;
+        for (int32_t p = threadIdx.x; p < P; p += 256) v += row[p];
+    }
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) gb[(int64_t)s * O + o] = red[0];
+}
+
+static int conv3d_geo(const char *who, const bnn_conv3d_shape_t *sh, int nsamples, int compute, Conv3dGeo &g)
+{
+    if (!sh) { set_error("%s: NULL shape", who); return BNN_E_NULL; }
+    if (sh->B < 1 || sh->C < 1 || sh->D < 1 || sh->H < 1 || sh->W < 1 || sh->O < 1 || sh->KD < 1 || sh->KH < 1 || sh->KW < 1 ||
+        sh->stride_d < 1 || sh->stride_h < 1 || sh->stride_w < 1 || sh->dil_d < 1 || sh->dil_h < 1 || sh->dil_w < 1 ||
+        sh->pad_d < 0 || sh->pad_h < 0 || sh->pad_w < 0 || sh->groups < 1 || sh->C % sh->groups || sh->O % sh->groups || nsamples < 1) {
+        set_error("%s: bad extent", who);
+        return BNN_E_SHAPE;
+    }
+    if (compute != BNN_COMPUTE_F32 && compute != BNN_COMPUTE_BF16) { set_error("%s: unknown compute mode", who); return BNN_E_DTYPE; }
+    const int64_t lim = 0x7FFFFFFF;
+    if (sh->D > lim || sh->H > lim || sh->W > lim || sh->KD > lim || sh->KH > lim || sh->KW > lim || sh->stride_d > lim ||
+        sh->stride_h > lim || sh->stride_w > lim || sh->dil_d > lim || sh->dil_h > lim || sh->dil_w > lim || sh->pad_d > lim ||
+        sh->pad_h > lim || sh->pad_w > lim) {
+        set_error("%s: an extent of 2^31 or more", who);
+        return BNN_E_RANGE;
+    }
+    const int64_t OD = (sh->D + 2 * sh->pad_d - sh->dil_d * (sh->KD - 1) - 1) / sh->stride_d + 1;
+    const int64_t OH = (sh->H + 2 * sh->pad_h - sh->dil_h * (sh->KH - 1) - 1) / sh->stride_h + 1;
+    const int64_t OW = (sh->W + 2 * sh->pad_w - sh->dil_w * (sh->KW - 1) - 1) / sh->stride_w + 1;
+    if (sh->D + 2 * sh->pad_d < sh->dil_d * (sh->KD - 1) + 1 || sh->H + 2 * sh->pad_h < sh->dil_h * (sh->KH - 1) + 1 ||
+        sh->W + 2 * sh->pad_w < sh->dil_w * (sh->KW - 1) + 1 || OD < 1 || OH < 1 || OW < 1) {
+        set_error("%s: kernel larger than the padded input", who);
+        return BNN_E_SHAPE;
+    }
+    // one sample's tensors and index arithmetic stay below 2^31 (padded origins and reach included)
+    const double B = (double)sh->B, T = (double)sh->KD * sh->KH * sh->KW;
+    const double Pin = (double)sh->D * sh->H * sh->W, P = (double)OD * OH * OW;
+    if (B * sh->C * Pin >= 2147483647.0 || B * sh->O * P >= 2147483647.0 || (double)sh->O * (sh->C / sh->groups) * T >= 2147483647.0 ||
+        (double)(sh->D + sh->pad_d) * sh->H * sh->W >= 2147483647.0 || (double)sh->pad_d + sh->dil_d * (double)sh->KD >= 2147483647.0 ||
+        (double)sh->pad_h + sh->dil_h * (double)sh->KH >= 2147483647.0 || (double)sh->pad_w + sh->dil_w * (double)sh->KW >= 2147483647.0 ||
+        (double)OD * sh->stride_d + sh->D >= 2147483647.0 || (double)OH * sh->stride_h + sh->H >= 2147483647.0 ||
+        (double)OW * sh->stride_w + sh->W >= 2147483647.0 || (double)sh->C * Pin + Pin >= 2147483647.0) {
+        set_error("%s: a per-sample tensor of 2^31 elements or more", who);
+        return BNN_E_RANGE;
+    }
+    if ((int64_t)nsamples * sh->groups > 65535) { set_error("%s: nsamples * groups > 65535", who); return BNN_E_RANGE; }
+    g.B = (int32_t)sh->B; g.C = (int32_t)sh->C; g.D = (int32_t)sh->D; g.H = (int32_t)sh->H; g.W = (int32_t)sh->W; g.O = (int32_t)sh->O;
+    g.KD = (int32_t)sh->KD; g.KH = (int32_t)sh->KH; g.KW = (int32_t)sh->KW;
+    g.OD = (int32_t)OD; g.OH = (int32_t)OH; g.OW = (int32_t)OW;
+    g.sd = (int32_t)sh->stride_d; g.sh = (int32_t)sh->stride_h; g.sw = (int32_t)sh->stride_w;
+    g.pd = (int32_t)sh->pad_d; g.ph = (int32_t)sh->pad_h; g.pw = (int32_t)sh->pad_w;
+    g.dd = (int32_t)sh->dil_d; g.dh = (int32_t)sh->dil_h; g.dw = (int32_t)sh->dil_w;
+    g.groups = (int32_t)sh->groups; g.Cg = g.C / g.groups; g.Ng = g.O / g.groups;
+    g.T = g.KD * g.KH * g.KW; g.K = g.Cg * g.T; g.P = g.OD * g.OH * g.OW; g.Pin = g.D * g.H * g.W;
+    g.fOW = make_div(g.OW); g.fOH = make_div(g.OH); g.fP = make_div(g.P);
+    g.fW = make_div(g.W); g.fH = make_div(g.H); g.fPin = make_div(g.Pin);
+    g.fKW = make_div(g.KW); g.fKH = make_div(g.KH); g.fT = make_div(g.T);
+    g.fsd = make_div(g.sd); g.fsh = make_div(g.sh); g.fsw = make_div(g.sw);
+    return BNN_OK;
+}
+
+static int check_w(const char *who, const void *w, int64_t w_ss, const Conv3dGeo &g, int nsamples, int compute)
+{
+    if (!w) { set_error("%s: NULL weights", who); return BNN_E_NULL; }
+    if (w_ss < 0 || (nsamples > 1 && w_ss > 0 && w_ss < (int64_t)g.O * g.K)) { set_error("%s: bad weight sample stride", who); return BNN_E_SHAPE; }
+    if (reinterpret_cast<uintptr_t>(w) & (compute == BNN_COMPUTE_BF16 ? 1u : 3u)) { set_error("%s: misaligned weights", who); return BNN_E_ALIGN; }
+    return BNN_OK;
+}
+
+static bool mis4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
+
+// slabs of the weight gradient's reduction: about 1024 workgroups in all, at most 16 slabs, whole k-tiles each
+static void wgrad_split(const Conv3dGeo &g, int nsamples, int &nslab, int &chunk)
+{
+    const int64_t R = (int64_t)g.B * g.P;
+    const int64_t tiles = (int64_t)((g.K + C3_BM - 1) / C3_BM) * ((g.Ng + C3_BN - 1) / C3_BN) * nsamples * g.groups;
+    int64_t want = (1024 + tiles - 1) / tiles;
+    const int64_t ktiles = (R + C3_BK - 1) / C3_BK;
+    want = std::min<int64_t>(std::min<int64_t>(want, 16), ktiles);
+    while (want > 1 && (int64_t)nsamples * g.groups * want > 65535) --want;
+    const int64_t per = (ktiles + want - 1) / want;
+    chunk = (int)(per * C3_BK);
+    nslab = (int)((R + chunk - 1) / chunk);
+}
+
+template <int MODE>
+static void launch(const Conv3dGeo &g, const Conv3dArgs &a, int compute, dim3 grid, hipStream_t st)
+{
+    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_conv3d<uint16_t, MODE>), grid, dim3(C3_THREADS), 0, st, g, a);
+    else hipLaunchKernelGGL((k_conv3d<float, MODE>), grid, dim3(C3_THREADS), 0, st, g, a);
+}
+
+}  // namespace bnn
+
+using namespace bnn;
+
+extern "C" {
+
+int bnn_conv3d_forward_drawn(const float *x, int64_t x_sample_stride, const void *w, int64_t w_sample_stride,
+                             const float *b, int64_t b_sample_stride, float *y, const bnn_conv3d_shape_t *shape,
+                             int nsamples, int compute, void *stream)
+{
+    const char *who = "bnn_conv3d_forward_drawn";
+    Conv3dGeo g;
+    int rc = conv3d_geo(who, shape, nsamples, compute, g);
+    if (rc) return rc;
+    if (!x || !y) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if ((rc = check_w(who, w, w_sample_stride, g, nsamples, compute))) return rc;
+    if (x_sample_stride < 0 || b_sample_stride < 0) { set_error("%s: negative sample stride", who); return BNN_E_SHAPE; }
+    if (mis4(x) || mis4(y) || mis4(b)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    Conv3dArgs a{};
+    a.x = x; a.x_ss = x_sample_stride; a.w = w; a.w_ss = w_sample_stride; a.bias = b; a.b_ss = b_sample_stride; a.out = y;
+    a.S = nsamples; a.shared = x_sample_stride == 0;
+    const dim3 grid((unsigned)(((int64_t)g.B * g.P + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN), (unsigned)(nsamples * g.groups));
+    launch<C3_FWD>(g, a, compute, grid, (hipStream_t)stream);
+    return check_launch(who);
+}
+
+int bnn_conv3d_backward_input(const float *gy, const void *w, int64_t w_sample_stride, float *gx, int shared_x,
+                              const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *stream)
+{
+    const char *who = "bnn_conv3d_backward_input";
+    Conv3dGeo g;
+    int rc = conv3d_geo(who, shape, nsamples, compute, g);
+    if (rc) return rc;
+    if (!gy || !gx) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if ((rc = check_w(who, w, w_sample_stride, g, nsamples, compute))) return rc;
+    if (mis4(gy) || mis4(gx)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    Conv3dArgs a{};
+    a.gy = gy; a.w = w; a.w_ss = w_sample_stride; a.out = gx; a.S = nsamples; a.shared = shared_x ? 1 : 0;
+    const dim3 grid((unsigned)(((int64_t)g.B * g.Pin + C3_BM - 1) / C3_BM), (unsigned)((g.Cg + C3_BN - 1) / C3_BN),
+                    (unsigned)((shared_x ? 1 : nsamples) * g.groups));
+    launch<C3_DGRAD>(g, a, compute, grid, (hipStream_t)stream);
+    return check_launch(who);
+}
+
+int64_t bnn_conv3d_backward_weight_workspace_bytes(const bnn_conv3d_shape_t *shape, int nsamples)
+{
+    Conv3dGeo g;
+    if (conv3d_geo("bnn_conv3d_backward_weight_workspace_bytes", shape, nsamples, BNN_COMPUTE_F32, g)) return -1;
+    int nslab, chunk;
+    wgrad_split(g, nsamples, nslab, chunk);
+    return nslab > 1 ? (int64_t)nslab * nsamples * g.O * g.K * (int64_t)sizeof(float) : 0;
+}
+
+int bnn_conv3d_backward_weight(const float *x, int64_t x_sample_stride, const float *gy, float *gw, float *gb,
+                               const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *workspace,
+                               int64_t workspace_bytes, void *stream)
+{
+    const char *who = "bnn_conv3d_backward_weight";
+    Conv3dGeo g;
+    int rc = conv3d_geo(who, shape, nsamples, compute, g);
+    if (rc) return rc;
+    if (!gy || (gw && !x) || (!gw && !gb)) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if (x_sample_stride < 0) { set_error("%s: negative sample stride", who); return BNN_E_SHAPE; }
+    if (mis4(x) || mis4(gy) || mis4(gw) || mis4(gb) || mis4(workspace)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    hipStream_t st = (hipStream_t)stream;
+    if (gw) {
+        int nslab, chunk;
+        wgrad_split(g, nsamples, nslab, chunk);
+        const int64_t n = (int64_t)nsamples * g.O * g.K;
+        if (nslab > 1 && (!workspace || workspace_bytes < nslab * n * (int64_t)sizeof(float))) {
+            set_error("%s: workspace of bnn_conv3d_backward_weight_workspace_bytes bytes needed", who);
+            return BNN_E_UNSUPPORTED;
+        }
+        Conv3dArgs a{};
+        a.x = x; a.x_ss = x_sample_stride; a.gy = gy; a.out = nslab > 1 ? static_cast<float *>(workspace) : gw;
+        a.S = nsamples; a.nslab = nslab; a.chunk = chunk;
+        const dim3 grid((unsigned)((g.K + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN), (unsigned)(nsamples * g.groups * nslab));
+        launch<C3_WGRAD>(g, a, compute, grid, st);
+        if ((rc = check_launch(who))) return rc;
+        if (nslab > 1) {
+            hipLaunchKernelGGL(k_conv3d_slab_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace), n,
+                               nslab, gw, n);
+            if ((rc = check_launch(who))) return rc;
+        }
+    }
+    if (gb) {
+        hipLaunchKernelGGL(k_conv3d_bias_grad, dim3((unsigned)g.O, (unsigned)nsamples), dim3(256), 0, st, gy, gb, g.B, g.O, g.P);
+        if ((rc = check_launch(who))) return rc;
+    }
+    return BNN_OK;
+}
+
+}  // extern "C"

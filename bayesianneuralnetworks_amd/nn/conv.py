@@ -1,9 +1,9 @@
 """Convolutional Bayesian layers (pytorch_bayesian/nn/conv.py).
 
 NormalConv2d is the hot path: an implicit-GEMM MFMA kernel whose B-operand loader draws the
-filter bank (bnn_conv2d_forward_sampled).  NormalConv1d/3d have no configuration in
-BASELINE.json: they take their weights from the fused HIP sampler (K1) and contract with the
-PyTorch-ROCm convNd op.  The FlipOut variants run on HIP on the device (2-d, and 1-d as 2-d at height 1); in a network's
+filter bank (bnn_conv2d_forward_sampled).  NormalConv1d runs on the same kernels (images of height 1).  NormalConv3d draws
+all S MC samples in one launch and contracts them in one implicit-GEMM launch, backward included (bnn_conv3d_forward_drawn,
+csrc/bnn_conv3d.hip).  The FlipOut variants run on HIP on the device (2-d, and 1-d as 2-d at height 1); in a network's
 MC-batched device pass their signs are keyed per MC sample (bnn_conv2d_flipout_forward_mc, bnn_flipout_signs).  The MC-dropout
 variants run their torch conv once and apply the keyed masks of a network's MC-batched device pass in HIP (bnn_mc_dropout).
 """
@@ -132,7 +132,24 @@ class NormalConv3d(NormalConvNd):
                          _triple(padding), _triple(dilation), False, groups, bias, prior)
 
     def forward(self, x, sample=True):
-        return self._torch_conv(torch.nn.functional.conv3d, x, sample)
+        if not x.is_cuda:
+            # CPU-resident module: the reference's own op sequence (conv.py:138-142)
+            return self._torch_conv(torch.nn.functional.conv3d, x, sample)
+        if x.dim() == 4:
+            return self.forward(x.unsqueeze(0), sample).squeeze(0)
+        # device: every MC sample of the context on its own keyed draw -- one draw launch, one implicit-GEMM launch
+        S, _, shared, per = self._mc_plan(x, sample)
+        x6 = x if shared else x.reshape(S, per, *x.shape[1:])
+        keys = self._keys(S)
+        geo = (self.stride, self.padding, self.dilation, self.groups)
+        if keys is not None:
+            y = ops.conv3d_sampled(x6, self.weight.mean, self.weight.scale,
+                                   self.bias.mean if self.bias is not None else None,
+                                   self.bias.scale if self.bias is not None else None,
+                                   keys[0], keys[1], shared, *geo, self._compute_mode())
+        else:
+            y = ops.conv3d_plain(x6, *self.sampled, S, shared, *geo, self._compute_mode())
+        return y.reshape(S * per, *y.shape[2:])
 
 
 def _flipout_conv2d_device(layer, x, R, S, view, stride, padding, dilation):

@@ -1622,6 +1622,140 @@ def conv2d_plain(x, w, b, shared_x, stride, padding, dilation, groups, compute="
                               _compute_code(compute))
 
 
+# --------------------------------------------------------------------------- conv3d (NormalConv3d on the device)
+def _conv3d_shape(x_shape, w_shape, stride, padding, dilation, groups):
+    """-> (bnn_conv3d_shape_t, (OD, OH, OW)) of conv3d(x (B, C, D, H, W), w (O, C/groups, KD, KH, KW)).  BnnHipError where torch's
+    conv3d refuses too: a channel count that does not match, a kernel larger than the padded input.  Host arithmetic only."""
+    B, C, D, H, W = (int(v) for v in x_shape)
+    O, Cg, KD, KH, KW = (int(v) for v in w_shape)
+    groups = int(groups)
+    if groups < 1 or C != Cg * groups or O % groups != 0:
+        raise BnnHipError("conv3d: input has %d channels, weight (%d, %d, ...) with groups=%d expects %d" % (C, O, Cg, groups, Cg * groups))
+    out = []
+    for n, k, s, p, d in zip((D, H, W), (KD, KH, KW), stride, padding, dilation):
+        span = int(d) * (k - 1) + 1
+        if n + 2 * int(p) < span:
+            raise BnnHipError("conv3d: kernel larger than padded input")
+        out.append((n + 2 * int(p) - span) // int(s) + 1)
+    sh = _lib.Conv3dShape(B, C, D, H, W, O, KD, KH, KW, *(int(v) for v in stride), *(int(v) for v in padding),
+                          *(int(v) for v in dilation), groups)
+    return sh, tuple(out)
+
+
+def _conv3d_operands(mu_w, rho_w, mu_b, rho_b, key_w, key_b, compute):
+    """The contraction's weight (and bias) operands -> (w, w_sample_stride, b, b_sample_stride).
+    Keyed: the S draws of the posterior in ONE bnn_draw_multi launch -- the weight as one flat row per sample (rows = 1: the eps
+    order is K1's and the draw's cols % 4 rule does not apply), bf16 with the row padded to a multiple of 8 or fp32, the bias fp32.
+    Explicit (key_w None): mu_w / mu_b are the weight and bias of every sample (sample stride 0); bf16 mode rounds the weight with
+    a kind-1 draw (the tensor as it is)."""
+    dev = mu_w.device
+    n = mu_w.numel()
+    bf = compute == _lib.COMPUTE_BF16
+    if key_w is None and not bf:
+        return mu_w, 0, mu_b, 0
+    ld = (n + 7) // 8 * 8 if bf else n
+    S = key_w.nsamples if key_w is not None else 1
+    w = torch.empty((S, ld), dtype=torch.bfloat16 if bf else torch.float32, device=dev)
+    arr = (_lib.DrawTensor * 2)()
+    t = arr[0]
+    t.mu, t.rho, t.rows, t.cols = mu_w.data_ptr(), (rho_w if key_w is not None else mu_w).data_ptr(), 1, n
+    t.out, t.ld, t.out_sample_stride, t.out_dtype = w.data_ptr(), ld, ld, (_lib.BF16 if bf else _lib.F32)
+    t.kind, t.taps = (0 if key_w is not None else 1), 0
+    if key_w is not None:
+        t.rng = _rng_struct(key_w, dev)
+    cnt, b = 1, (mu_b if key_w is None else None)
+    if key_w is not None and mu_b is not None:
+        b = torch.empty((S, mu_b.numel()), dtype=torch.float32, device=dev)
+        t = arr[1]
+        t.mu, t.rho, t.rows, t.cols = mu_b.data_ptr(), rho_b.data_ptr(), 1, mu_b.numel()
+        t.out, t.ld, t.out_sample_stride, t.out_dtype = b.data_ptr(), mu_b.numel(), mu_b.numel(), _lib.F32
+        t.kind, t.taps = 0, 0
+        t.rng = _rng_struct(key_b, dev)
+        cnt = 2
+    check(_lib.load().bnn_draw_multi(arr, cnt, S, None, 0, None, stream_ptr(dev)), "bnn_draw_multi")
+    return w, (ld if key_w is not None else 0), b, (0 if key_w is None or b is None else b.shape[1])
+
+
+class _Conv3d(torch.autograd.Function):
+    """y[s] = conv3d(x[s | 0], w_s, b_s, ...) for S samples on the implicit GEMMs of csrc/bnn_conv3d.hip (NormalConv3d.forward,
+    conv.py:138-142): one draw launch + one contraction launch.  Keyed (key_w given): w_s, b_s are the draws of the posterior on
+    the keys; the backward re-draws them from the keys (nothing drawn is saved) and takes g_mu / g_rho from bnn_sample_affine_bwd.
+    Explicit (key_w None): mu_w / mu_b are the weight and bias of every sample."""
+
+    @staticmethod
+    def forward(ctx, x, mu_w, rho_w, mu_b, rho_b, key_w, key_b, S, shared_x, conv_args, compute):
+        require_cuda_f32(x, "x")
+        require_cuda_f32(mu_w, "weight")
+        for t, name in ((rho_w, "weight.scale"), (mu_b, "bias"), (rho_b, "bias.scale")):
+            if t is not None:
+                require_cuda_f32(t, name)
+        stride, padding, dilation, groups = conv_args
+        if x.dim() != (5 if shared_x else 6) or (not shared_x and x.shape[0] != S):
+            raise BnnHipError("conv3d: x must be (B, C, D, H, W) shared by the samples or (S, B, C, D, H, W), got %s" % (tuple(x.shape),))
+        sh, (OD, OH, OW) = _conv3d_shape(x.shape[-5:], mu_w.shape, stride, padding, dilation, groups)
+        dev = x.device
+        w, w_ss, b, b_ss = _conv3d_operands(mu_w, rho_w, mu_b, rho_b, key_w, key_b, compute)
+        y = torch.empty((S, sh.B, sh.O, OD, OH, OW), dtype=torch.float32, device=dev)
+        check(_lib.load().bnn_conv3d_forward_drawn(ptr(x), 0 if shared_x else x[0].numel(), ptr(w), w_ss, ptr(b), b_ss, ptr(y),
+                                                   ctypes.byref(sh), S, compute, stream_ptr(dev)), "bnn_conv3d_forward_drawn")
+        ctx.save_for_backward(x, mu_w, rho_w, mu_b, rho_b)
+        ctx.key_w, ctx.key_b, ctx.S, ctx.shared_x, ctx.sh, ctx.compute = key_w, key_b, S, shared_x, sh, compute
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, mu_w, rho_w, mu_b, rho_b = ctx.saved_tensors
+        S, sh, compute, dev = ctx.S, ctx.sh, ctx.compute, gy.device
+        lib, st = _lib.load(), stream_ptr(dev)
+        keyed = ctx.key_w is not None
+        need_x = ctx.needs_input_grad[0]
+        need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        need_b = mu_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        gy = gy.contiguous()
+        gx = g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
+        if need_x:
+            w, w_ss, _, _ = _conv3d_operands(mu_w, rho_w, None, None, ctx.key_w, None, compute)
+            gx = torch.empty(x.shape, dtype=torch.float32, device=dev)
+            check(lib.bnn_conv3d_backward_input(ptr(gy), ptr(w), w_ss, ptr(gx), int(ctx.shared_x), ctypes.byref(sh), S, compute, st),
+                  "bnn_conv3d_backward_input")
+        if need_w or need_b:
+            O, K = sh.O, mu_w[0].numel()
+            gw = torch.empty((S, O, K), dtype=torch.float32, device=dev) if need_w else None
+            gb = torch.empty((S, O), dtype=torch.float32, device=dev) if need_b else None
+            nb = lib.bnn_conv3d_backward_weight_workspace_bytes(ctypes.byref(sh), S) if need_w else 0
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev) if nb > 0 else None     # this call's own slabs
+            check(lib.bnn_conv3d_backward_weight(ptr(x), 0 if ctx.shared_x else x[0].numel(), ptr(gy), ptr(gw), ptr(gb),
+                                                 ctypes.byref(sh), S, compute, ptr(ws), nb, st), "bnn_conv3d_backward_weight")
+            if need_w:
+                if keyed:
+                    g_mu_w, g_rho_w = _sample_affine_bwd_raw(gw, rho_w, rho_w.numel(), S, key=ctx.key_w)
+                else:
+                    g_mu_w = gw.sum(0).reshape(mu_w.shape)
+            if need_b:
+                if keyed:
+                    g_mu_b, g_rho_b = _sample_affine_bwd_raw(gb, rho_b, rho_b.numel(), S, key=ctx.key_b)
+                else:
+                    g_mu_b = gb.sum(0)
+        return gx, g_mu_w, g_rho_w, g_mu_b, g_rho_b, None, None, None, None, None, None
+
+
+def conv3d_sampled(x, mu_w, rho_w, mu_b, rho_b, key_w, key_b, shared_x, stride, padding, dilation, groups, compute="f32"):
+    """NormalConv3d on the device for the key's S MC samples: x (B, C, D, H, W) shared by them (shared_x) or (S, B, C, D, H, W)
+    -> (S, B, O, OD, OH, OW) fp32.  Draw + contraction: two launches; autograd to x and the four posterior tensors."""
+    return _Conv3d.apply(x.contiguous(), mu_w.contiguous(), rho_w.contiguous(),
+                         None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
+                         key_w, key_b, key_w.nsamples, bool(shared_x),
+                         (tuple(stride), tuple(padding), tuple(dilation), int(groups)), _compute_code(compute))
+
+
+def conv3d_plain(x, w, b, nsamples, shared_x, stride, padding, dilation, groups, compute="f32"):
+    """conv3d_sampled on ONE explicit weight (O, C/groups, KD, KH, KW) and bias (O,) or None for all `nsamples` samples (a layer
+    whose weights were set rather than keyed, e.g. WeightNormal.sample_with_eps); autograd to x, w and b."""
+    return _Conv3d.apply(x.contiguous(), w.contiguous(), None, None if b is None else b.contiguous(), None, None, None,
+                         int(nsamples), bool(shared_x), (tuple(stride), tuple(padding), tuple(dilation), int(groups)),
+                         _compute_code(compute))
+
+
 # --------------------------------------------------------------------------- K3
 _kl_ws = {}
 

@@ -550,6 +550,44 @@ int bnn_conv2d_col2im(const float *gpanel, const bnn_conv2d_shape_t *shape, int 
 int bnn_nchw_to_rows(const float *y, int64_t images, int channels, int pixels, void *rows,
                      int out_bf16, void *stream);
 
+/* ---- conv3d on drawn weights (NormalConv3d on the device) -------------------------------------------------------------
+ *   y[s] = conv3d(x[s | 0], w_s, b_s, stride, padding, dilation, groups), NCDHW activations, OIDHW weights.
+ * Implicit GEMMs per (sample, group) with the im2col gather in the loaders' address arithmetic (no panel in memory):
+ * forward M = B*OD*OH*OW, N = O/groups, K = (C/groups)*KD*KH*KW.  Every extent is accepted; the refusals are index ranges:
+ * a per-sample tensor (x, y, one sample's weights) of 2^31 elements or more, or nsamples * groups > 65535 (BNN_E_RANGE). */
+typedef struct bnn_conv3d_shape {
+    int64_t B, C, D, H, W;               /* input  (B, C, D, H, W) */
+    int64_t O, KD, KH, KW;               /* weight (O, C/groups, KD, KH, KW) */
+    int64_t stride_d, stride_h, stride_w, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, groups;
+} bnn_conv3d_shape_t;
+/* Forward on the S drawn weights: w sample s at w + s * w_sample_stride elements, O rows of K = (C/groups) KD KH KW
+ * (OIDHW order, row pitch K; w_sample_stride 0: one weight for every sample) -- bnn_draw_multi of the posterior as ONE flat row
+ * (rows = 1, cols = O K, kind 0, ld = out_sample_stride = roundup(O K, 8) for bf16), so the eps order and the values are
+ * K1's and the draw's cols % 4 rule does not apply.  compute BNN_COMPUTE_BF16: w bf16, x rounded to bf16 in the loader,
+ * v_mfma_f32_16x16x32_bf16; BNN_COMPUTE_F32: w fp32, v_mfma_f32_16x16x4_f32 (a k-ordered fp32 fma chain).  fp32
+ * accumulation.  x fp32 (x_sample_stride = 0: shared by the samples, the first Bayesian layer of a net), b S x O fp32
+ * (b_sample_stride) or NULL, y nsamples x B x O x OD x OH x OW fp32.  One launch.
+ * replaces  F.conv3d(x, *self.sampled, ...)  pytorch_bayesian/nn/conv.py:138-142 */
+int bnn_conv3d_forward_drawn(const float *x, int64_t x_sample_stride, const void *w, int64_t w_sample_stride,
+                             const float *b, int64_t b_sample_stride, float *y, const bnn_conv3d_shape_t *shape,
+                             int nsamples, int compute, void *stream);
+/* Input gradient: gx = the implicit GEMM of gy (nsamples x B x O x OD x OH x OW fp32) with the same weights over the input
+ * positions; taps that no stride step reaches contribute zero.  shared_x != 0: gx is B x C x D x H x W, the sum over the
+ * samples taken inside the reduction loop in sample order; else nsamples x B x C x D x H x W.  No atomics.  One launch.
+ * replaces  autograd through F.conv3d (input)  pytorch_bayesian/nn/conv.py:138-142 */
+int bnn_conv3d_backward_input(const float *gy, const void *w, int64_t w_sample_stride, float *gx, int shared_x,
+                              const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *stream);
+/* Weight and bias gradients: gw[s] = gy[s]^T . gathered x[s | 0], nsamples x O x K fp32 (NULL: bias only), gb[s][o] = the sum of
+ * gy[s][.][o] over the positions, nsamples x O fp32 (NULL: none).  The reduction over B*OD*OH*OW is split into slabs taken from
+ * the CALLER's workspace (bnn_conv3d_backward_weight_workspace_bytes(shape, nsamples) bytes, 4-B aligned; 0: none needed --
+ * a per-call buffer, never the registered one) and summed in slab order.  Bitwise reproducible.  One launch for gw (two with
+ * slabs), one for gb.  The posterior gradients follow from bnn_sample_affine_bwd on the recorded keys.
+ * replaces  autograd through F.conv3d (weight, bias)  pytorch_bayesian/nn/conv.py:138-142 */
+int64_t bnn_conv3d_backward_weight_workspace_bytes(const bnn_conv3d_shape_t *shape, int nsamples);
+int bnn_conv3d_backward_weight(const float *x, int64_t x_sample_stride, const float *gy, float *gw, float *gb,
+                               const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *workspace,
+                               int64_t workspace_bytes, void *stream);
+
 /* ---- diagnostics ------------------------------------------------------------
  * VALU cost of the draw, no memory traffic: `blocks` workgroups of 256 threads each run
  * `iters` Philox blocks (4 draws) of stage 0 (Philox4x32-10 only), 1 (+ Box-Muller),
