@@ -84,6 +84,19 @@ class Conv3dShape(ctypes.Structure):
                  "pad_d", "pad_h", "pad_w", "dil_d", "dil_h", "dil_w", "groups")]
 
 
+class MvnTensor(ctypes.Structure):
+    """bnn_mvn_tensor_t"""
+    _fields_ = [("mu", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("out", ctypes.c_void_p), ("g_w", ctypes.c_void_p),
+                ("g_mu", ctypes.c_void_p), ("g_scale", ctypes.c_void_p), ("sample_stride", ctypes.c_int64),
+                ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("rng", Rng)]
+
+
+class MvnKlTensor(ctypes.Structure):
+    """bnn_mvn_kl_tensor_t"""
+    _fields_ = [("mu", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("g_mu", ctypes.c_void_p), ("g_scale", ctypes.c_void_p),
+                ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("prior_mu", ctypes.c_float), ("prior_sigma", ctypes.c_float)]
+
+
 _p = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
@@ -161,6 +174,11 @@ SIGNATURES = {
     "bnn_conv3d_backward_input": (_int, [_p, _p, _i64, _p, _int, ctypes.POINTER(Conv3dShape), _int, _int, _p]),
     "bnn_conv3d_backward_weight_workspace_bytes": (_i64, [ctypes.POINTER(Conv3dShape), _int]),
     "bnn_conv3d_backward_weight": (_int, [_p, _i64, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p, _i64, _p]),
+    "bnn_mvn_draw": (_int, [ctypes.POINTER(MvnTensor), _int, _int, _p]),
+    "bnn_mvn_draw_backward": (_int, [ctypes.POINTER(MvnTensor), _int, _int, _p]),
+    "bnn_mvn_kl_workspace_bytes": (_i64, [ctypes.POINTER(MvnKlTensor), _int]),
+    "bnn_mvn_kl": (_int, [ctypes.POINTER(MvnKlTensor), _int, _p, _p, _i64, _p]),
+    "bnn_mvn_kl_backward": (_int, [ctypes.POINTER(MvnKlTensor), _int, _p, _p]),
     "bnn_conv2d_forward_sampled": (_int, [_p, _i64, _p, _p, _p, _p, _p, _i64,
                                           ctypes.POINTER(Conv2dShape), _int, _rngp, _rngp, _int, _int, _p, _i64, _p]),
     "bnn_conv2d_forward": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, ctypes.POINTER(Conv2dShape),

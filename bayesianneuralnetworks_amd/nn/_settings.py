@@ -29,6 +29,25 @@ def fuse_kl_gradient(enable=True):
     ops.FUSE_KL_GRADIENT = bool(enable)
 
 
+_keyed_mvn = False
+
+
+def keyed_mvn_draws(enable=True):
+    """Opt-in (default off) for the full-covariance posterior on the device: with it on, a MultivariateNormalLinear inside a
+    BayesianNetworkModule's MC-batched pass gives every MC sample a keyed draw of its own (layer.weight.draw_key /
+    layer.bias.draw_key; MVN-noise contract in include/bnn_hip.h) -- one bnn_mvn_draw launch for the weight and bias of all S
+    samples, one dense launch, a HIP backward -- and KLDivergence takes the closed-form HIP KL for a WeightMultivariateNormal on
+    the device with an isotropic prior (the default one).  With it off nothing about these layers changes: in a batched pass the
+    layer draws once for all S samples, as before.  Making it the default is a separate step: the CIFAR10 network's launch-count
+    test pins the draw-once head."""
+    global _keyed_mvn
+    _keyed_mvn = bool(enable)
+
+
+def keyed_mvn_enabled():
+    return _keyed_mvn
+
+
 def fuse_activations(module, bf16_activations=False, fuse_head=False):
     """Opt-in graph rewrite inside every torch.nn.Sequential:
 

@@ -112,16 +112,26 @@ class WeightNormal(Module):
 
 
 class WeightMultivariateNormal(Module):
-    """Per-row full-covariance posterior, core.py:48-92 (PyTorch ops; outside the HIP path).
+    """Per-row full-covariance posterior, core.py:48-92.
     Keeps the reference's quirks: uniform noise (core.py:91) and the element-wise sqrt of
-    the lower-triangular factor (core.py:69)."""
+    the lower-triangular factor (core.py:69).  sample() / sample_with_noise() are the reference's torch expressions; with
+    nn.keyed_mvn_draws() on, a MultivariateNormalLinear in an MC-batched device pass draws keyed (draw_key; MVN-noise contract,
+    include/bnn_hip.h) on a stream id taken at the first such draw, so that the ids of a model's other layers do not shift."""
 
     def __init__(self, *channels):
         super().__init__()
         self.mean = Parameter(torch.zeros(*channels))
         eye = torch.eye(channels[-1])
         self.scale = Parameter(eye.repeat(*channels[:-1], 1, 1))
+        self.draw_key = None            # DrawKey of the last keyed draw
+        self._mvn_stream = None
         self.sample()
+
+    def fresh_key(self, nsamples, sample0, epoch, gen):
+        """A DrawKey for a keyed draw of nsamples samples (not recorded)."""
+        if self._mvn_stream is None:
+            self._mvn_stream = new_stream_id()
+        return DrawKey(default_generator.seed, self._mvn_stream, sample0, nsamples, epoch, gen=gen)
 
     @property
     def device(self):

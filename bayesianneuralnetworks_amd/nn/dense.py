@@ -7,9 +7,10 @@ accumulate) or bnn_dense_forward_x3 (fp32 parity mode at inference: three bf16 p
 forwards, narrow fp32 layers and A/B runs take the round-1 fused kernel (bnn_linear_forward_sampled: the draw inside the
 B-operand loader of the GEMM).  MCDropoutLinear runs on HIP in a network's MC-batched device pass (keyed masks,
 bnn_dense_forward_dropout / bnn_mc_dropout) and keeps F.dropout elsewhere.  FlipoutNormalLinear draws mu + sigma R S^T
-with keyed signs per MC sample in that pass (bnn_draw_multi kind BNN_DRAW_FLIPOUT).  The other classes (multivariate,
-evidential) are outside the HIP scope and run as PyTorch-ROCm ops with the
-reference's semantics so that its examples keep working.
+with keyed signs per MC sample in that pass (bnn_draw_multi kind BNN_DRAW_FLIPOUT).  MultivariateNormalLinear keeps the
+reference's torch expression unless nn.keyed_mvn_draws() is on: then in that pass every MC sample gets a keyed draw of its own
+(bnn_mvn_draw, then the HIP linear).  The evidential head is outside the HIP scope and runs as PyTorch-ROCm
+ops with the reference's semantics so that its examples keep working.
 """
 import math
 
@@ -376,7 +377,9 @@ class FlipoutNormalLinear(NormalLinear):
 
 
 class MultivariateNormalLinear(BayesianLinear):
-    """dense.py:86-138 (PyTorch ops)."""
+    """dense.py:86-138.  PyTorch ops, unless nn.keyed_mvn_draws() is on and the layer runs on the device inside a
+    BayesianNetworkModule's MC-batched pass: then every MC sample gets a keyed draw of its own (weight.draw_key, bias.draw_key;
+    MVN-noise contract in include/bnn_hip.h), two launches per forward, and sample=False reuses the recorded keys."""
 
     def __init__(self, in_features, out_features, bias=True, weight_prior=None, bias_prior=None):
         if not weight_prior:
@@ -409,9 +412,49 @@ class MultivariateNormalLinear(BayesianLinear):
             self.sampled = (self.weight.sampled, None)
 
     def forward(self, x, sample=True):
+        if _settings.keyed_mvn_enabled() and isinstance(x, torch.Tensor) and x.is_cuda and _mc.current() is not None:
+            return self._forward_keyed(x, sample, _mc.current())
         if sample:
             self.sample()
         return torch.nn.functional.linear(x, *self.sampled)
+
+    def _mvn_keys(self, ctx, sample):
+        """sample: fresh keys for the pass's S samples, recorded as weight.draw_key / bias.draw_key.  sample=False: the recorded
+        keys, which must cover the pass's S samples."""
+        if sample:
+            epoch = default_generator.next_epoch()
+            gen = generator_for(_settings.get_compute())
+            self.weight.draw_key = self.weight.fresh_key(ctx.samples, ctx.sample0, epoch, gen)
+            if self.bias is not None:
+                self.bias.draw_key = self.bias.fresh_key(ctx.samples, ctx.sample0, epoch, gen)
+        kw = self.weight.draw_key
+        kb = self.bias.draw_key if self.bias is not None else None
+        if kw is None or kw.nsamples != ctx.samples or (self.bias is not None and (kb is None or kb.nsamples != ctx.samples)):
+            raise RuntimeError("sample=False: %s has %s keyed draws recorded, this MC-batched pass needs %d samples"
+                               % (type(self).__name__, "no" if kw is None else "%d samples of" % kw.nsamples, ctx.samples))
+        return kw, kb
+
+    def _forward_keyed(self, x, sample, ctx):
+        """Every MC sample of the pass on its own keyed draw: ONE bnn_mvn_draw launch for the weight and bias of all S samples,
+        ONE dense launch (ops.linear_plain) on the (S, O, K) weights -- shared B-row input or S * B rows.  layer.sampled keeps
+        the last torch-path draw."""
+        S = ctx.samples
+        if x.dim() >= 2 and x.shape[0] == ctx.base_batch:
+            shared, per = True, ctx.base_batch
+        elif x.dim() >= 2 and x.shape[0] == ctx.base_batch * S:
+            shared, per = False, ctx.base_batch
+        else:
+            raise RuntimeError("mc_batched: %s got an input of shape %s; expected (%d, ...) or (%d, ...) rows (batch %d x %d samples)"
+                               % (type(self).__name__, tuple(x.shape), ctx.base_batch, ctx.base_batch * S, ctx.base_batch, S))
+        kw, kb = self._mvn_keys(ctx, sample)
+        w, b = ops.mvn_draw_layer(self.weight.mean, self.weight.scale,
+                                  self.bias.mean if self.bias is not None else None,
+                                  self.bias.scale if self.bias is not None else None, kw, kb)
+        K = x.shape[-1]
+        lead = x.shape[1:-1]
+        x2 = x.reshape(-1, K) if shared else x.reshape(S, -1, K)
+        y = ops.linear_plain(x2.float(), w, b, shared, _settings.get_compute())
+        return y.reshape(S * per, *lead, y.shape[-1])
 
 
 class NormalInverseGaussianLinear(BayesianModule):

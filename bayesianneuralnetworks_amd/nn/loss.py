@@ -2,8 +2,9 @@
 
 KLDivergence is the hot path (K3): every mean-field Gaussian tensor of the model that lives
 on the GPU and has a scalar Normal prior goes through ONE multi-tensor HIP launch
-(bnn_kl_forward); other posteriors (multivariate, tensor-valued priors, CPU tensors) use
-torch.distributions and are averaged in.
+(bnn_kl_forward).  With nn.keyed_mvn_draws() on, a WeightMultivariateNormal on the GPU with an isotropic prior (the default
+one) takes the closed form in HIP (bnn_mvn_kl, every such tensor in one call).  Other posteriors (tensor-valued or
+non-isotropic priors, CPU tensors) use torch.distributions and are averaged in.
 """
 import math
 import warnings
@@ -15,7 +16,8 @@ from torch.distributions.kl import kl_divergence
 
 from .. import ops
 from ..utils import apply_wb
-from .core import WeightNormal
+from . import _settings
+from .core import WeightNormal, WeightMultivariateNormal
 from .dense import MultivariateNormalLinear
 
 
@@ -25,6 +27,19 @@ def _scalar_normal(prior):
     if prior.loc.numel() != 1 or prior.scale.numel() != 1:
         return None
     return float(prior.loc), float(prior.scale)
+
+
+def _hip_mvn_prior(param, prior):
+    """(m0, sigma0) when the HIP closed form takes this tensor: the switch on, a WeightMultivariateNormal on the device, an
+    isotropic MultivariateNormal prior of its event size (checked once per prior object); else None."""
+    if not (_settings.keyed_mvn_enabled() and isinstance(param, WeightMultivariateNormal) and param.mean.is_cuda
+            and isinstance(prior, MultivariateNormal) and prior.event_shape[-1:] == param.mean.shape[-1:]):
+        return None
+    try:
+        torch.broadcast_shapes(prior.batch_shape, param.mean.shape[:-1])
+    except RuntimeError:
+        return None
+    return ops.mvn_isotropic(prior)
 
 
 class KLDivergence(Module):
@@ -46,6 +61,9 @@ class KLDivergence(Module):
         if isinstance(param, WeightNormal) and param.mean.is_cuda and sn is not None:
             out = ops.kl_normal([param.mean], [param.scale], [sn], 1.0)
             return out[1]
+        iso = _hip_mvn_prior(param, prior)
+        if iso is not None:
+            return ops.mvn_kl([param.mean], [param.scale], [iso])[0]
         if isinstance(module, MultivariateNormalLinear):
             prior = MultivariateNormal(prior.mean.to(param.device),
                                        scale_tril=prior.scale_tril.to(param.device))
@@ -58,13 +76,23 @@ class KLDivergence(Module):
         if entries is None:
             # loss.py:34-36
             raise ValueError('KLDivergence was not able to find BayasianModules')
-        fused, other = [], []
+        fused, other, mvn = [], [], []
         for param, module, type in entries:
-            sn = _scalar_normal(self._prior_of(module, type))
+            prior = self._prior_of(module, type)
+            sn = _scalar_normal(prior)
+            iso = _hip_mvn_prior(param, prior)
             if isinstance(param, WeightNormal) and param.mean.is_cuda and sn is not None:
                 fused.append((param, sn))
+            elif iso is not None:
+                mvn.append((len(other), param, iso))
+                other.append(None)
             else:
                 other.append(self.compute_kl(param, module, type))
+        if mvn:
+            # every full-covariance tensor with an isotropic prior in ONE bnn_mvn_kl call, in its place in the list
+            kls = ops.mvn_kl([p.mean for _, p, _ in mvn], [p.scale for _, p, _ in mvn], [iso for _, _, iso in mvn])
+            for k, (i, _, _) in enumerate(mvn):
+                other[i] = kls[k]
         if fused and not other:
             return ops.kl_normal_scalar([p.mean for p, _ in fused], [p.scale for p, _ in fused],
                                         [sn for _, sn in fused], self.n_batches)

@@ -1756,6 +1756,156 @@ def conv3d_plain(x, w, b, nsamples, shared_x, stride, padding, dilation, groups,
                          _compute_code(compute))
 
 
+# --------------------------------------------------------------------------- MultivariateNormalLinear (MVN-noise contract)
+def _mvn_extent(mu, scale):
+    """(rows, cols) of a full-covariance posterior: mean (..., K), scale (..., K, K)."""
+    require_cuda_f32(mu, "mean")
+    require_cuda_f32(scale, "scale")
+    K = mu.shape[-1]
+    if tuple(scale.shape) != tuple(mu.shape) + (K,):
+        raise BnnHipError("mvn: scale has shape %s, the mean %s needs %s" % (tuple(scale.shape), tuple(mu.shape),
+                                                                             tuple(mu.shape) + (K,)))
+    return mu.numel() // K, K
+
+
+def _mvn_descs(mus, scales, keys, S, outs=None, gws=None, g_mus=None, g_scales=None):
+    arr = (_lib.MvnTensor * len(mus))()
+    for i, (m, sc, k) in enumerate(zip(mus, scales, keys)):
+        rows, K = _mvn_extent(m, sc)
+        t = arr[i]
+        t.mu, t.scale, t.rows, t.cols, t.sample_stride = m.data_ptr(), sc.data_ptr(), rows, K, rows * K
+        if outs is not None:
+            t.out = outs[i].data_ptr()
+        if gws is not None:
+            t.g_w, t.g_mu, t.g_scale = gws[i].data_ptr(), g_mus[i].data_ptr(), g_scales[i].data_ptr()
+        if k.nsamples != S:
+            raise BnnHipError("mvn: the keys of one draw must have the same number of samples")
+        t.rng = _rng_struct(k, m.device)
+    return arr
+
+
+def _mvn_draw_raw(mus, scales, keys):
+    S = keys[0].nsamples
+    outs = [torch.empty((S,) + tuple(m.shape), dtype=torch.float32, device=m.device) for m in mus]
+    arr = _mvn_descs(mus, scales, keys, S, outs=outs)
+    check(_lib.load().bnn_mvn_draw(arr, len(mus), S, stream_ptr(mus[0].device)), "bnn_mvn_draw")
+    return outs
+
+
+def mvn_draw(mu, scale, key):
+    """The keyed draws w_s = mu + L u_s of the key's nsamples MC samples (MVN-noise contract, include/bnn_hip.h): mu (O, K) with
+    scale (O, K, K), or a bias (O,) with (O, O) -> (S, *mu.shape) fp32.  One bnn_mvn_draw launch, no autograd."""
+    return _mvn_draw_raw([mu.detach().contiguous()], [scale.detach().contiguous()], [key])[0]
+
+
+class _MvnDraw(torch.autograd.Function):
+    """(w_s for each tensor) = mu + tril(sqrt(softplus(scale) + 1e-10 I)) u_s with keyed uniforms: bnn_mvn_draw forward (every
+    tensor in one launch), bnn_mvn_draw_backward backward (the uniforms re-created from the keys)."""
+
+    @staticmethod
+    def forward(ctx, keys, *params):
+        T = len(keys)
+        mus, scales = [p.detach() for p in params[:T]], [p.detach() for p in params[T:]]
+        outs = _mvn_draw_raw(mus, scales, keys)
+        ctx.save_for_backward(*params)
+        ctx.keys = keys
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        params = ctx.saved_tensors
+        T = len(ctx.keys)
+        mus, scales = params[:T], params[T:]
+        S = ctx.keys[0].nsamples
+        gws = [g.contiguous().float() if g is not None else torch.zeros((S,) + tuple(m.shape), device=m.device)
+               for g, m in zip(gs, mus)]
+        g_mus = [torch.empty_like(m) for m in mus]
+        g_scales = [torch.empty_like(sc) for sc in scales]
+        arr = _mvn_descs(mus, scales, ctx.keys, S, gws=gws, g_mus=g_mus, g_scales=g_scales)
+        check(_lib.load().bnn_mvn_draw_backward(arr, T, S, stream_ptr(mus[0].device)), "bnn_mvn_draw_backward")
+        return (None,) + tuple(g_mus) + tuple(g_scales)
+
+
+def mvn_draw_layer(mu_w, scale_w, mu_b, scale_b, key_w, key_b):
+    """A MultivariateNormalLinear's weight (S, O, K) and bias (S, O) (or None) for the keys' samples, in ONE launch, with autograd."""
+    if mu_b is None:
+        return _MvnDraw.apply((key_w,), mu_w.contiguous(), scale_w.contiguous())[0], None
+    w, b = _MvnDraw.apply((key_w, key_b), mu_w.contiguous(), mu_b.contiguous(), scale_w.contiguous(), scale_b.contiguous())
+    return w, b
+
+
+def mvn_isotropic(prior):
+    """(m0, sigma0) if `prior` is MultivariateNormal(loc = m0 everywhere, scale_tril = sigma0 I), else None.  Checked once per
+    prior object (its tensors are (O, K, K) on the host) and cached on it."""
+    cached = prior.__dict__.get("_bnn_isotropic", False)
+    if cached is not False:
+        return cached
+    from torch.distributions import MultivariateNormal
+    iso = None
+    if isinstance(prior, MultivariateNormal):
+        loc = prior.loc.detach().double().cpu()
+        tril = prior.scale_tril.detach().double().cpu()
+        K = loc.shape[-1]
+        m0, s0 = float(loc.reshape(-1)[0]), float(tril.reshape(-1, K, K)[0, 0, 0])
+        eye = torch.eye(K, dtype=torch.float64)
+        if s0 > 0 and bool((loc == m0).all()) and bool((tril == s0 * eye).all()):
+            iso = (m0, s0)
+    prior.__dict__["_bnn_isotropic"] = iso
+    return iso
+
+
+def _mvn_kl_descs(mus, scales, priors, g_mus=None, g_scales=None):
+    arr = (_lib.MvnKlTensor * len(mus))()
+    for i, (m, sc, pr) in enumerate(zip(mus, scales, priors)):
+        rows, K = _mvn_extent(m, sc)
+        t = arr[i]
+        t.mu, t.scale, t.rows, t.cols = m.data_ptr(), sc.data_ptr(), rows, K
+        t.prior_mu, t.prior_sigma = pr
+        if g_mus is not None:
+            t.g_mu, t.g_scale = g_mus[i].data_ptr(), g_scales[i].data_ptr()
+    return arr
+
+
+class _MvnKL(torch.autograd.Function):
+    """out[t] = mean over the rows of KL(MVN(mu_t, scale_tril = V_t) || isotropic prior t): bnn_mvn_kl (two launches) forward,
+    bnn_mvn_kl_backward backward.  The gradient is returned, never parked (FUSE_KL_GRADIENT covers WeightNormal only)."""
+
+    @staticmethod
+    def forward(ctx, priors, *params):
+        T = len(priors)
+        mus, scales = [p.detach() for p in params[:T]], [p.detach() for p in params[T:]]
+        dev = mus[0].device
+        arr = _mvn_kl_descs(mus, scales, priors)
+        nbytes = _lib.load().bnn_mvn_kl_workspace_bytes(arr, T)
+        if nbytes < 0:
+            raise BnnHipError("bnn_mvn_kl_workspace_bytes: bad tensors")
+        ws = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=dev)        # per call: concurrent KLs never share it
+        out = torch.empty(T, dtype=torch.float32, device=dev)
+        check(_lib.load().bnn_mvn_kl(arr, T, ptr(out), ptr(ws), ws.numel() * 8, stream_ptr(dev)), "bnn_mvn_kl")
+        ctx.save_for_backward(*params)
+        ctx.priors = priors
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        params = ctx.saved_tensors
+        T = len(ctx.priors)
+        mus, scales = params[:T], params[T:]
+        g_mus = [torch.empty_like(m) for m in mus]
+        g_scales = [torch.empty_like(sc) for sc in scales]
+        arr = _mvn_kl_descs(mus, scales, ctx.priors, g_mus, g_scales)
+        up = g.contiguous().float()
+        check(_lib.load().bnn_mvn_kl_backward(arr, T, ptr(up), stream_ptr(up.device)), "bnn_mvn_kl_backward")
+        return (None,) + tuple(g_mus) + tuple(g_scales)
+
+
+def mvn_kl(mus, scales, priors):
+    """priors: (m0, sigma0) per tensor (mvn_isotropic).  -> (T,) fp32: each tensor's mean KL over its rows, differentiable --
+    KLDivergence.compute_kl of a WeightMultivariateNormal against its isotropic prior."""
+    return _MvnKL.apply(tuple((float(a), float(b)) for a, b in priors), *[m.contiguous() for m in mus],
+                        *[sc.contiguous() for sc in scales])
+
+
 # --------------------------------------------------------------------------- K3
 _kl_ws = {}
 

@@ -64,6 +64,19 @@
  *     linear (O x K weight): one row of O + K elements, R = v[0 : O], S = v[O : O + K], eps[o][k] = R[o] S[k].
  *   rows (O + C) < 2^32 per sample.  Every kernel computes a sign with one device function (flip_sign on drop_u4).
  *   CPU twin: tests/test_flipout_mc.py (sign_twin), on the oracle's Philox.
+ *
+ * MVN-noise contract (the full-covariance posterior on the MC-batched path: bnn_mvn_draw, bnn_mvn_draw_backward)
+ *   The reference draws UNIFORM noise for WeightMultivariateNormal (torch.rand_like, pytorch_bayesian/nn/core.py:89-92), and so
+ *   does this contract: u_s[o][j] is the dropout mask's uniform above (same bnn_rng_t fields, both generators, before Box-Muller,
+ *   one device function: drop_u4) at element e = o K + j of the (O, K) mean, sample sample0 + s.  A bias (O,) with its (O, O)
+ *   scale is one row: K = O, e = j.  Under BNN_GEN_PHILOX10_U24 a uniform can round up to 1.0, as the mask's can.
+ *   The draw, all fp32:
+ *     L[o][i][j] = sqrt(softplus(scale[o][i][j]) + (i == j ? 1e-10 : 0))   for j <= i   (softplus: torch's, threshold 20)
+ *     w_s[o][i]  = mu[o][i] + sum_{j <= i} L[o][i][j] u_s[o][j]
+ *   (WeightMultivariateNormal.stddev / sample()).  Only the lower triangle of scale is read: the upper one has no effect.  The
+ *   summation order over j is fixed by K alone, so w_s is the same bit for bit for any nsamples, sample0 or grid, and where
+ *   the backward or a shard re-creates it.  O K < 2^32 per tensor.
+ *   CPU twin: tests/test_mvn_device.py (mvn_twin), on the oracle's Philox.
  */
 #ifndef BNN_HIP_H
 #define BNN_HIP_H
@@ -660,6 +673,57 @@ int bnn_flipout_signs(float *out, int64_t out_sample_stride, int64_t rows, int64
  * g_w: nsamples x O x K fp32 at g_w_sample_stride elements. */
 int bnn_flipout_weight_backward(const float *g_w, int64_t g_w_sample_stride, const float *rho, float *g_mu, float *g_rho,
                                 int64_t O, int64_t K, int nsamples, const bnn_rng_t *rng, void *stream);
+
+/* ---- MultivariateNormalLinear (MVN-noise contract above) --------------------------------
+ * One full-covariance posterior tensor: mean rows x cols (a weight O x K, or a bias as ONE row of O), scale rows x cols x cols
+ * (its lower triangle is read; the upper one never is).  Host struct. */
+typedef struct bnn_mvn_tensor {
+    const float *mu;            /* rows x cols */
+    const float *scale;         /* rows x cols x cols */
+    float *out;                 /* bnn_mvn_draw: nsamples x rows x cols at sample_stride elements (written) */
+    const float *g_w;           /* bnn_mvn_draw_backward: the gradient of out, same layout (read) */
+    float *g_mu;                /* bnn_mvn_draw_backward: rows x cols */
+    float *g_scale;             /* bnn_mvn_draw_backward: rows x cols x cols, every element (0 above the diagonal) */
+    int64_t sample_stride;
+    int64_t rows, cols;
+    bnn_rng_t rng;              /* the tensor's key: stream, sample0, epochs, generator */
+} bnn_mvn_tensor_t;
+/* w_s for s < nsamples of up to 8 tensors (a layer's weight and bias) in ONE launch.  A workgroup owns (tensor, row o, part of
+ * the triangle rows): it makes the row's cols x nsamples uniforms once into LDS and streams the lower triangle once, every L
+ * computed once and applied to all samples (beyond 16 samples, or cols x samples over 16 K floats, the triangle is streamed
+ * once per group of samples).  cols <= 16384.
+ * replaces  MultivariateNormalLinear.sample() -> WeightMultivariateNormal.sample()  pytorch_bayesian/nn/dense.py:123-130,
+ *           nn/core.py:89-92, once per MC sample */
+int bnn_mvn_draw(const bnn_mvn_tensor_t *tensors, int ntensors, int nsamples, void *stream);
+/* Backward of bnn_mvn_draw, the uniforms re-created from the keys (never stored):
+ *   g_mu = sum_s g_w[s];  g_scale[o][i][j] = (sum_s g_w[s][o][i] u_s[o][j]) sigmoid(scale[o][i][j]) / (2 L[o][i][j]) for j <= i,
+ *   exactly 0 for j > i (autograd of the reference expression, where tril masks the gradient).  Sums over s in sample order,
+ *   no atomics: bitwise reproducible.  Reads the lower triangle once.  ONE launch.  cols <= 8192. */
+int bnn_mvn_draw_backward(const bnn_mvn_tensor_t *tensors, int ntensors, int nsamples, void *stream);
+
+/* One full-covariance posterior against an ISOTROPIC prior MultivariateNormal(loc = prior_mu everywhere, scale_tril =
+ * prior_sigma I) -- the default prior of MultivariateNormalLinear is (0, 1).  Host struct. */
+typedef struct bnn_mvn_kl_tensor {
+    const float *mu;            /* rows x cols */
+    const float *scale;         /* rows x cols x cols, lower triangle read */
+    float *g_mu;                /* bnn_mvn_kl_backward: rows x cols */
+    float *g_scale;             /* bnn_mvn_kl_backward: rows x cols x cols, every element (0 above the diagonal) */
+    int64_t rows, cols;
+    float prior_mu, prior_sigma;
+} bnn_mvn_kl_tensor_t;
+/* KL(MVN(mu, scale_tril = V) || prior) in closed form, V = tril(softplus(scale)) + 1e-10 I (the reference's scale_tril is V
+ * itself, not its element-wise root), per row o with s0 = prior_sigma, m0 = prior_mu, K = cols:
+ *   KL_o = 0.5 (sum_{j <= i} V_ij^2 / s0^2 + sum_i (mu_i - m0)^2 / s0^2 - K) + K ln s0 - sum_i ln V_ii
+ * out[t] = the mean of KL_o over the rows of tensor t (what KLDivergence.compute_kl returns for it).  Partial sums per workgroup
+ * into the CALLER's workspace (bnn_mvn_kl_workspace_bytes, 8-B aligned; a per-call buffer), summed in fp64 in slot order: no
+ * atomics, bitwise reproducible.  Two launches whatever the shapes.
+ * replaces  kl_divergence(param.dist, MultivariateNormal(prior...)).mean()  pytorch_bayesian/nn/loss.py:16-28 */
+int64_t bnn_mvn_kl_workspace_bytes(const bnn_mvn_kl_tensor_t *tensors, int ntensors);
+int bnn_mvn_kl(const bnn_mvn_kl_tensor_t *tensors, int ntensors, float *out, void *workspace, int64_t workspace_bytes,
+               void *stream);
+/* Backward, g = upstream[t] / rows (upstream: ntensors device floats, NULL = 1):
+ *   g_mu = g (mu - m0) / s0^2;   g_scale = g (V_ij / s0^2 - [i == j] / V_ii) sigmoid(scale_ij) for j <= i, 0 above.  ONE launch. */
+int bnn_mvn_kl_backward(const bnn_mvn_kl_tensor_t *tensors, int ntensors, const float *upstream, void *stream);
 
 /* ---- MC reduction ----------------------------------------------------------
  * replaces  torch.stack(preds).mean(0)   examples/MNIST/uncertainty.py:50
