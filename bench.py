@@ -11,28 +11,34 @@ asynchronously so that it runs under the next step.
 (before the parent makes any GPU call) and relays rank 0's line.  N > 1 headline = STRONG scaling
 (SURVEY.md 8e / north_star "one sample per GPU"): the S = 8 global MC samples are sharded S / N per
 rank (`distributed.shard_samples`), value = 8 * steps / time; the weak-scaling number (8 samples on
-every rank, value = N * 8 * steps / time) rides along under "weak".
+every rank, value = N * 8 * steps / time) rides along under "weak" in a `--full` run.
 
 Timing: `--warmup` untimed steps, then ONE timed window of exactly `--steps` steps (barrier + synchronize on both sides);
 `ms_per_step` = the window / `--steps`.  The headline arrangement follows from the arguments alone: with graphs and
-`--inflight` > 1 (default 4, N = 1 forward) the pipelined steps (`PipelinedSteps`), else the single-stream step; next to a
-pipelined headline the single-stream step is timed too (the latency of one step, `config.pipeline`).
-A run whose oracle check fails, or that leaves the device error word set, prints its line with a `failed` list and exits
-non-zero.
+`--inflight` > 1 (default 4, N = 1 forward) the pipelined steps (`PipelinedSteps`), else the single-stream step.
+
+A plain run does what the headline needs and nothing else: it sets up, warms up, times the `--steps` steps, writes
+`--dump-outputs` and prints its line.  `--full` adds everything else this script measures or checks (below); a step that
+only `--full` builds ahead of the headline is stood in for by `skip_step`, so both runs draw the same noise for the
+headline and dump the same arrays.  Every run reads the device error word after timing; a run that leaves it set, or whose
+oracle check fails (`--full`), prints its line with a `failed` list and exits non-zero.
 
 `--dump-outputs DIR` (rank 0): after the timed window, what the headline path computed in its LAST timed step, as
 DIR/<name>.npy in float32 -- forward: `predictive_mean` (512 x 10), `kl_sums` (one per posterior tensor) and `kl` (the
 KLDivergence scalar); `--mode train`: `loss` and every parameter after the last Adam update.  Inputs, posteriors and seeds
 are fixed, so runs with the same arguments draw the same noise and two builds can be compared output for output.
 
-Prints ONE JSON line (rank 0).  Extra keys: `checked` / `checked_f32` (one more replay of the timed object compared
-with the CPU oracle on the replay's own draw keys -- a checker, never timed; N > 1: the all-reduced buffer against global
-sample ids, every rank replays, rank 0 compares), `device_error_word`, `roofline` (dominant
-kernel, measured live with events on the launch stream), `roofline_conv_lenet` / `roofline_conv_cifar`
-/ `roofline_wide_f32` (configs[2], [3], [4] layer launches), `roofline_lenet_net` / `roofline_wide_stack` (configs[2] and [4] as
-the whole networks they name), `cpu_baseline` (torch-CPU port of the
-reference, N = 1 only), `f32` (same step in the fp32 parity mode), `train` (N = 1: the reference's
-training-loop body, examples/MNIST/train.py:53-65, on the same model).
+Prints ONE JSON line (rank 0).  Extra keys: `device_error_word`, `full`, `config.pipeline` (pipelined headline); with `--full`
+also `checked` / `checked_f32` (one more replay of the timed object compared with the CPU oracle on the replay's own draw
+keys -- a checker, never timed; N > 1: the all-reduced buffer against global sample ids, every rank replays, rank 0
+compares), the single-stream step next to a pipelined headline (`config.pipeline.single_stream_*`: the latency of one
+step) and the oracle check of its in-flight results, `weak` (N > 1), `roofline` (dominant kernel, measured live with
+events on the launch stream), `roofline_draw`, `roofline_conv_lenet` / `roofline_conv_cifar` / `roofline_wide_f32`
+(configs[2], [3], [4] layer launches), `roofline_lenet_net` / `roofline_wide_stack` (configs[2] and [4] as the whole
+networks they name), `roofline_sampler` / `roofline_kl` (`--no-legs` skips these seven), `cpu_baseline` (torch-CPU port of
+the reference, N = 1 only; `--no-cpu-baseline` skips it), `f32` (same step in the fp32 parity mode, N = 1), `train` (N = 1:
+the body of the reference's MNIST training loop, on the same model) -- which is the headline of
+`--mode train`, with or without `--full`.
 """
 import argparse
 import json
@@ -536,6 +542,59 @@ class TrainStep:
             self._eager()
 
 
+def step_host_epochs(net, use_graph, runs=0):
+    """Host draw epochs a Step on `net` takes from the eps generator: one per Bayesian layer for every body it runs on the
+    host -- three to build a captured step (two warm-up bodies + the capture), one to build an eager one, and one more per
+    eager run (`runs`); a graph replay takes none."""
+    layers = sum(1 for m in net.layers if hasattr(m, "weight"))
+    return layers * (3 if use_graph else 1 + runs)
+
+
+def step_device_epochs(use_graph, runs=0):
+    """Bumps of the device-wide epoch word by a (not private) Step: one per body the device executes -- the two warm-up bodies
+    of a captured step (the capture itself executes nothing) or the one body that builds an eager step -- and one per run."""
+    return (2 if use_graph else 1) + runs
+
+
+def skip_step(net, dev, use_graph, runs=0):
+    """Stand-in for a Step that a plain run does not build (a leg that only --full measures), built and run `runs` times in a
+    --full run: advance the host epoch counter and the device epoch word as that Step would have, so that what runs next
+    draws the same keys -- and computes the same outputs -- as in a --full run."""
+    from bayesianneuralnetworks_amd._rng import default_generator
+    for _ in range(step_host_epochs(net, use_graph, runs)):
+        default_generator.next_epoch()
+    default_generator.epoch_dev(dev)[0] += step_device_epochs(use_graph, runs)
+
+
+def forward_modes(args, world):
+    """The compute modes main() runs the forward step in, in order: --dtype, then (N = 1) the fp32 parity mode."""
+    return [args.dtype] + (["f32"] if (args.dtype != "f32" and world == 1) else [])
+
+
+def leg_flags(args, world, mode):
+    """(use_pipe, headline, steps) of `mode`'s forward leg: whether the pipelined steps run (the headline then), whether the
+    single-stream step is the headline, and how many steps it times."""
+    use_pipe = args.inflight > 1 and not args.no_graph and args.mode == "forward" and mode == args.dtype
+    headline = args.mode == "forward" and mode == args.dtype and not use_pipe
+    steps = args.steps if mode == args.dtype else max(10, args.steps // 4)
+    return use_pipe, headline, steps
+
+
+def plain_stand_ins(args, world, strong, mode):
+    """The Steps on the shared epoch counters that a --full run builds in `mode`'s forward leg and a plain run does not, as
+    (leg, use_graph, runs) in the order a --full run builds them; a plain run calls skip_step for each in its place.
+    'single': the single-stream step unless it is the headline -- timed (warmup + steps runs), then replayed once by the
+    oracle check.  'weak': the weak-scaling step of a strong-scaling run -- timed only; when the headline is pipelined the
+    weak leg is pipelined too, on steps with private epoch words, after the headline and with nothing drawing after it."""
+    use_pipe, headline, steps = leg_flags(args, world, mode)
+    out = []
+    if not headline:
+        out.append(("single", not args.no_graph, args.warmup + steps + 1))
+    if mode == args.dtype and strong and not use_pipe:
+        out.append(("weak", not args.no_graph, args.warmup + steps))
+    return out
+
+
 def time_steps(step, steps, warmup, world, dev):
     """`warmup` untimed steps, then EXACTLY `steps` steps between barrier + synchronize on both sides; max over ranks."""
     for _ in range(warmup):
@@ -938,8 +997,11 @@ def main(argv=None):
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the headline path computed in its last timed step to DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the configs[2..4] / K1 / K3 roofline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle checks, the single-stream, fp32-mode, training and weak-scaling legs, "
+                         "the rooflines and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="--full: skip the configs[2..4] / K1 / K3 roofline legs")
     argv = sys.argv[1:] if argv is None else list(argv)
     args = ap.parse_args(argv)
 
@@ -976,6 +1038,7 @@ def main(argv=None):
     bnn.manual_seed(2)
 
     strong = world > 1 and args.scaling == "strong" and SAMPLES % world == 0
+    full = args.full
     results, checked, weak, pipeline = {}, {}, None, None
     failures = []
     dump = args.dump_outputs if rank == 0 else None
@@ -985,45 +1048,56 @@ def main(argv=None):
         dt = time_steps(step, steps, warmup, world, dev)
         return total * steps / dt, dt / steps * 1e3, steps
 
-    for mode in ([args.dtype] + (["f32"] if (args.dtype != "f32" and world == 1) else [])):
+    # A plain run builds and times the headline alone; --full adds the other legs.  A step that only --full builds ahead of
+    # the headline is stood in for by skip_step, so that the headline draws the same noise with and without --full.
+    for mode in forward_modes(args, world):
+        use_pipe, headline, steps = leg_flags(args, world, mode)
+        stand_ins = {} if full else {leg: (g, r) for leg, g, r in plain_stand_ins(args, world, strong, mode)}
+        if not (full or headline or use_pipe):
+            for g, r in stand_ins.values():         # nothing of this leg runs: the single-stream step, then the weak one
+                skip_step(net, dev, g, r)
+            continue
         bnn.set_compute(mode)
         # bf16 mode: the synthetic batch is resident in HBM as bf16 (the first layer would round its
         # A operand to bf16 anyway -- identical results, half the input stream); fp32 mode: fp32.
         x_in = resident_input(x, mode)
-        use_pipe = args.inflight > 1 and not args.no_graph and args.mode == "forward" and mode == args.dtype
         skw = {}
         if strong:
             s0, cnt = bd.shard_samples(SAMPLES, rank, world)
             skw = dict(samples=cnt, sample0=s0, total_samples=SAMPLES)
-        step = Step(net, x_in, rank, world, not args.no_graph, **skw)
-        steps = args.steps if mode == args.dtype else max(10, args.steps // 4)
         total = SAMPLES if strong else world * SAMPLES
-        results[mode] = timed(step, steps, args.warmup, total)
-        if dump and mode == args.dtype and args.mode == "forward" and not use_pipe:
-            dump_outputs(dump, step_outputs(step.result(), world))
-        # one more replay of the TIMED object against the oracle -- both modes, every N (N > 1: the all-reduced buffer, global
-        # sample ids; every rank replays, rank 0 compares)
-        chk = oracle_check(step, post, x_cpu, mode, evaluate=(rank == 0))
-        if rank == 0:
-            checked[mode] = chk
-            if not chk["ok"]:
-                failures.append("oracle check of the timed step failed (%s mode)" % mode)
+        step = None
+        if full or headline:
+            step = Step(net, x_in, rank, world, not args.no_graph, **skw)
+            results[mode] = timed(step, steps, args.warmup, total)
+            if dump and headline:
+                dump_outputs(dump, step_outputs(step.result(), world))
+            if full:
+                # one more replay of the TIMED object against the oracle -- both modes, every N (N > 1: the all-reduced
+                # buffer, global sample ids; every rank replays, rank 0 compares)
+                chk = oracle_check(step, post, x_cpu, mode, evaluate=(rank == 0))
+                if rank == 0:
+                    checked[mode] = chk
+                    if not chk["ok"]:
+                        failures.append("oracle check of the timed step failed (%s mode)" % mode)
+        else:
+            skip_step(net, dev, *stand_ins["single"])
         if use_pipe:
-            # throughput pipeline: `inflight` steps on as many streams -- the headline; the single-stream number above is the
-            # latency of one step
-            single = results[mode]
+            # throughput pipeline: `inflight` steps on as many streams -- the headline; the single-stream number above
+            # (--full) is the latency of one step
+            single = results.get(mode)
             pipe = PipelinedSteps(net, x_in, args.inflight, rank, world, **skw)
             results[mode] = piped = timed(pipe, steps, args.warmup, total)
             if dump:
                 dump_outputs(dump, step_outputs(pipe.result(), world))
             pipeline = {"steps_in_flight": args.inflight, "untimed_preroll_steps": int(os.environ.get("BNN_BENCH_PREROLL", "256")),
                         "reported": "pipelined",
-                        "pipelined_value": round(piped[0], 1), "pipelined_ms_per_step": round(piped[1], 4),
-                        "single_stream_value": round(single[0], 1),
-                        "single_stream_ms_per_step": round(single[1], 4),
-                        "note": "pipelined = `steps_in_flight` complete steps in flight on as many streams: THROUGHPUT (K complete "
-                                "steps / wall time); one step's LATENCY is single_stream_ms_per_step"}
-            if world == 1:
+                        "pipelined_value": round(piped[0], 1), "pipelined_ms_per_step": round(piped[1], 4)}
+            if single is not None:
+                pipeline.update({"single_stream_value": round(single[0], 1), "single_stream_ms_per_step": round(single[1], 4)})
+            pipeline["note"] = ("pipelined = `steps_in_flight` complete steps in flight on as many streams: THROUGHPUT (K complete "
+                                "steps / wall time); one step's LATENCY is single_stream_ms_per_step (--full)")
+            if full and world == 1:
                 # what the steps' LAST replays -- executed while the others were in flight -- left behind, against the oracle
                 pchks = [oracle_check(st, post, x_cpu, mode, replay=False) for st in pipe.steps]
                 pipeline.update({"checked_in_flight_results_ok": all(c["ok"] for c in pchks),
@@ -1032,13 +1106,15 @@ def main(argv=None):
                 if not pipeline["checked_in_flight_results_ok"]:
                     failures.append("oracle check of the in-flight results failed")
             del pipe
-        if mode == args.dtype and strong:
+        if full and mode == args.dtype and strong:
             if use_pipe:
                 wstep = PipelinedSteps(net, x_in, args.inflight, rank, world)
             else:
                 wstep = Step(net, x_in, rank, world, not args.no_graph)
             weak = timed(wstep, steps, args.warmup, world * SAMPLES)[:2]
             del wstep
+        elif "weak" in stand_ins:
+            skip_step(net, dev, *stand_ins["weak"])
         del step
     bnn.set_compute(args.dtype)
     # the device error word: a kernel whose bounded hand-off wait gave up has skipped its stores and said so there
@@ -1049,9 +1125,9 @@ def main(argv=None):
         device_word = "SET: %s" % e
         failures.append("device error word set after the timed runs")
 
-    # training step (own copy of the model: Adam moves the parameters)
+    # training step (own copy of the model: Adam moves the parameters) -- the headline of --mode train
     train = None
-    if args.mode == "train" or world == 1:
+    if args.mode == "train" or (full and world == 1):
         tnet = build_net(dev, post)
         tsteps = args.steps if args.mode == "train" else max(10, args.steps // 4)
         tstep = TrainStep(tnet, x.bfloat16() if args.dtype == "bf16" else x, rank, world, not args.no_graph)   # (dense rows: autograd saves x)
@@ -1064,7 +1140,8 @@ def main(argv=None):
         del tstep, tnet
 
     if rank == 0:
-        val, ms, steps = results[args.dtype]
+        fwd = results.get(args.dtype)
+        val, ms, steps = fwd if fwd is not None else train[:3]        # --mode train without --full times no forward leg
         per_gpu = SAMPLES // world if strong else SAMPLES
         line = {
             "metric": "MC-samples/sec (node), 784-1200-1200-10 BayesianLinear MLP, batch 512",
@@ -1088,6 +1165,7 @@ def main(argv=None):
         line["timing"] = {"note": "value / ms_per_step = ONE timed window of exactly `steps` steps after `warmup` untimed steps "
                                   "(barrier + synchronize on both sides)"}
         line["device_error_word"] = device_word
+        line["full"] = full
         if args.dtype in checked:
             line["checked"] = checked[args.dtype]
         if "f32" in checked and args.dtype != "f32":
@@ -1099,26 +1177,28 @@ def main(argv=None):
                              "steps": train[2], "loss": round(train[3], 4), "hip_graph": (not args.no_graph) and world == 1,
                              "note": "training-loop body of examples/MNIST/train.py:53-65 (fwd + KL + CE + HIP bwd + Adam)"}
             if args.mode == "train":
-                line["forward"] = {"value": line["value"], "ms_per_step": line["ms_per_step"]}
+                if fwd is not None:
+                    line["forward"] = {"value": round(fwd[0], 1), "ms_per_step": round(fwd[1], 4)}
                 line["metric"] = "MC-samples/sec (node), TRAINING step, 784-1200-1200-10 BayesianLinear MLP, batch 512"
                 line["value"], line["ms_per_step"], line["steps"] = line["train"]["value"], line["train"]["ms_per_step"], train[2]
                 line["scaling"] = "weak"
         if "f32" in results and args.dtype != "f32":
             line["f32"] = {"value": round(results["f32"][0], 1), "ms_per_step": round(results["f32"][1], 4),
                            "note": "same step in the 1e-5 parity mode: every operand as three bf16 planes on the dense kernel (six plane-pair k-steps per k-block), fp32 accumulate"}
-        line["roofline"] = kernel_roofline(net, x, args.dtype, dev)
-        if args.dtype == "bf16":
-            line["roofline_draw"] = draw_roofline(net, dev)
-        if world == 1 and not args.no_legs:
-            line["roofline_sampler"] = sampler_roofline(dev)
-            line["roofline_kl"] = kl_roofline(dev)
-            line["roofline_conv_lenet"] = conv_roofline("lenet", args.dtype, dev)
-            line["roofline_conv_cifar"] = conv_roofline("cifar", args.dtype, dev)
-            line["roofline_wide_f32"] = wide_roofline(dev)
-            line["roofline_lenet_net"] = lenet_net_roofline(args.dtype, dev)
-            line["roofline_wide_stack"] = wide_stack_roofline(dev)
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(post, x_cpu)
+        if full:
+            line["roofline"] = kernel_roofline(net, x, args.dtype, dev)
+            if args.dtype == "bf16":
+                line["roofline_draw"] = draw_roofline(net, dev)
+            if world == 1 and not args.no_legs:
+                line["roofline_sampler"] = sampler_roofline(dev)
+                line["roofline_kl"] = kl_roofline(dev)
+                line["roofline_conv_lenet"] = conv_roofline("lenet", args.dtype, dev)
+                line["roofline_conv_cifar"] = conv_roofline("cifar", args.dtype, dev)
+                line["roofline_wide_f32"] = wide_roofline(dev)
+                line["roofline_lenet_net"] = lenet_net_roofline(args.dtype, dev)
+                line["roofline_wide_stack"] = wide_stack_roofline(dev)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(post, x_cpu)
         if failures:
             line["failed"] = failures       # a wrong-result run publishes no headline: the process exits non-zero
         print(json.dumps(line), flush=True)

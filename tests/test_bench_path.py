@@ -121,6 +121,47 @@ def test_dump_outputs_unpack_the_packed_step_result(tmp_path):
     assert w.dtype == np.float32 and w.shape == (3, 2)
 
 
+def _parent_steps_before_headline(a, world, strong):
+    """What bench.py built on the shared epoch counters before its headline when every leg ran (the behaviour `--full` keeps),
+    as (use_graph, runs), written out from that arrangement: each forward mode's single-stream step (timed, then replayed
+    once by the oracle check), then -- strong scaling, --dtype -- the weak-scaling Step (timed only) unless it was pipelined.
+    The forward headline is the pipeline built after the single-stream step, or that step itself; the training headline
+    comes after every forward leg."""
+    graph = not a.no_graph
+    modes = [a.dtype] + (["f32"] if a.dtype != "f32" and world == 1 else [])
+    if a.mode == "forward":
+        return [(True, a.warmup + a.steps + 1)] if a.inflight > 1 and graph else []
+    out = []
+    for m in modes:
+        steps = a.steps if m == a.dtype else max(10, a.steps // 4)
+        out.append((graph, a.warmup + steps + 1))
+        if m == a.dtype and strong:
+            out.append((graph, a.warmup + steps))
+    return out
+
+
+def test_plain_run_stands_in_for_every_step_built_before_the_headline():
+    """A plain run replaces each Step that every-leg runs build before the headline with bench.skip_step, in the same order
+    and with the same (use_graph, runs): walked over the arrangements the arguments select (mode, N, scaling, graphs,
+    steps in flight, dtype)."""
+    import argparse
+    import itertools
+    sys.path.insert(0, ROOT)
+    import bench
+    for mode, world, scaling, no_graph, inflight, dtype in itertools.product(
+            ("forward", "train"), (1, 2, 4), ("strong", "weak"), (False, True), (1, 4), ("bf16", "f32")):
+        a = argparse.Namespace(mode=mode, scaling=scaling, no_graph=no_graph, inflight=inflight, dtype=dtype, steps=40, warmup=7)
+        strong = world > 1 and scaling == "strong" and bench.SAMPLES % world == 0
+        got = []
+        for m in bench.forward_modes(a, world):
+            use_pipe, headline, _ = bench.leg_flags(a, world, m)
+            for leg, g, r in bench.plain_stand_ins(a, world, strong, m):
+                # forward: only what precedes the headline of --dtype counts (the single-stream step ahead of the pipeline)
+                if mode == "train" or (m == a.dtype and use_pipe and leg == "single"):
+                    got.append((g, r))
+        assert got == _parent_steps_before_headline(a, world, strong), (mode, world, scaling, no_graph, inflight, dtype)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode,fuse_head", [("bf16", False), ("bf16", True), ("f32", False), ("f32", True)])
 def test_timed_graph_replays_match_oracle(mode, fuse_head):
@@ -259,3 +300,83 @@ def test_strong_scaling_shards_reproduce_the_single_gpu_step():
         bnn.set_compute("f32")
         from bayesianneuralnetworks_amd._rng import default_generator
         default_generator.epoch_dev(dev).zero_()
+
+
+@pytest.mark.gpu
+def test_skip_step_stands_in_for_the_single_stream_step():
+    """A `bench.py --full` run builds the single-stream step before the pipelined headline; a plain run does not and calls
+    bench.skip_step instead.  The pipelined steps built after either compute the same results bit for bit, so the two runs
+    dump the same arrays."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import bayesianneuralnetworks_amd as bnn
+    from bayesianneuralnetworks_amd._rng import default_generator
+    dev = torch.device("cuda:0")
+    net = bench.build_net(dev, bench.posteriors(0))
+    x = bench.resident_input(torch.randn(bench.BATCH, bench.DIMS[0], generator=torch.Generator().manual_seed(1)).to(dev), "bf16")
+    bnn.set_compute("bf16")
+    try:
+        outs = []
+        for real in (True, False):
+            bnn.manual_seed(2)
+            if real:
+                step = bench.Step(net, x, 0, 1, True)
+                step.run()
+                torch.cuda.synchronize()
+                del step
+            else:
+                bench.skip_step(net, dev, True, runs=1)
+            pipe = bench.PipelinedSteps(net, x, 2)
+            for _ in range(3):
+                pipe.run()
+            pipe.finish()
+            torch.cuda.synchronize()
+            outs.append([st.packed.detach().cpu().numpy().copy() for st in pipe.steps])
+            del pipe
+        for a, b in zip(*outs):
+            assert np.array_equal(a, b)
+    finally:
+        bnn.set_compute("f32")
+        default_generator.epoch_dev(dev).zero_()         # later tests address draws with epoch_dev = 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["bf16", "f32"])
+@pytest.mark.parametrize("use_graph", [True, False])
+def test_skip_step_leaves_the_counters_where_a_real_step_does(mode, use_graph):
+    """skip_step(net, dev, use_graph, runs) leaves the host epoch counter and the device epoch word where a real Step, built
+    and run `runs` times, leaves them -- captured or eager, in both compute modes: the single-stream, fp32-mode and
+    weak-scaling stand-ins of a plain run.  A step built after either draws the same noise: its result is the same bit for
+    bit."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import bayesianneuralnetworks_amd as bnn
+    from bayesianneuralnetworks_amd._rng import default_generator
+    dev = torch.device("cuda:0")
+    net = bench.build_net(dev, bench.posteriors(0))
+    x = bench.resident_input(torch.randn(bench.BATCH, bench.DIMS[0], generator=torch.Generator().manual_seed(1)).to(dev), mode)
+    word = default_generator.epoch_dev(dev)
+    bnn.set_compute(mode)
+    try:
+        counters, outs = [], []
+        for real in (True, False):
+            bnn.manual_seed(2)
+            if real:
+                step = bench.Step(net, x, 0, 1, use_graph)
+                for _ in range(3):
+                    step.run()
+                torch.cuda.synchronize()
+                del step
+            else:
+                bench.skip_step(net, dev, use_graph, runs=3)
+            counters.append((default_generator.epoch_host, int(word[0].item())))
+            nxt = bench.Step(net, x, 0, 1, False)        # eager: draws on the shared counters as it is built
+            torch.cuda.synchronize()
+            outs.append(nxt.packed.detach().cpu().numpy().copy())
+            del nxt
+        assert counters[0] == counters[1], counters
+        assert counters[1][0] > 0 and counters[1][1] > 0
+        assert np.array_equal(outs[0], outs[1])
+    finally:
+        bnn.set_compute("f32")
+        word.zero_()                                     # later tests address draws with epoch_dev = 0

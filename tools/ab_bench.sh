@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/ab_bench.sh : bench (no legs) with the current library, with tools/ab_old/libbnn_hip.so, and the current one again
 cd $GRAFT_REPO_ROOT
-run() { python3 bench.py --gpus 1 --steps 100 --warmup 20 --no-legs --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+run() { python3 bench.py --gpus 1 --steps 100 --warmup 20 --full --no-legs --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 l=json.loads(sys.stdin.read())
 p=l['config']['pipeline']

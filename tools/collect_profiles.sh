@@ -2,13 +2,15 @@
 # Round-3 profile collection on the GPU box (from the repo root): kernel stats of the bench command the driver runs, kernel
 # stats + PMC passes (separate runs, counters only: FETCH_SIZE alone; WRITE_SIZE + L2 hit / miss; two SQ groups, the second
 # with the MFMA-busy pair) of the step's kernels, the conv legs, the wide fp32 layer and the whole-network legs, the step and
-# pipeline timelines.  Summaries land in gpurun_out/ (copy the ones to keep into profiles/).
+# pipeline timelines.  The bench line (a --full run, every leg) is written straight to profiles/r03_bench_line.json, its
+# stderr left on this script's; the other summaries land in the output folder of tools/prof.sh and tools/pmc.sh (copy the
+# ones to keep into profiles/).
 set -e
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 cd $R
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r03_bench_line.json 2> gpurun_out/r03_bench_line.err
-bash tools/prof.sh r03_bench -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > profiles/r03_bench_line.json
+bash tools/prof.sh r03_bench -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline
 for w in step:run_step.py dense_l2:run_dense_l2.py conv_lenet:"run_conv.py lenet" conv_cifar:"run_conv.py cifar" wide:run_wide.py; do
   tag=${w%%:*}; cmd=${w#*:}
   bash tools/pmc.sh r03_${tag}_fetch "FETCH_SIZE" -- python3 tools/$cmd
