@@ -174,6 +174,11 @@ SIGNATURES = {
     "bnn_conv3d_backward_input": (_int, [_p, _p, _i64, _p, _int, ctypes.POINTER(Conv3dShape), _int, _int, _p]),
     "bnn_conv3d_backward_weight_workspace_bytes": (_i64, [ctypes.POINTER(Conv3dShape), _int]),
     "bnn_conv3d_backward_weight": (_int, [_p, _i64, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p, _i64, _p]),
+    "bnn_conv3d_flipout_forward": (_int, [_p, _i64, _p, _p, _i64, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p]),
+    "bnn_conv3d_flipout_backward_input": (_int, [_p, _p, _p, _i64, _p, _int, ctypes.POINTER(Conv3dShape), _int, _int, _p]),
+    "bnn_conv3d_flipout_backward_weight_workspace_bytes": (_i64, [ctypes.POINTER(Conv3dShape), _int]),
+    "bnn_conv3d_flipout_backward_weight": (_int, [_p, _i64, _p, _p, _i64, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p,
+                                                  _i64, _p]),
     "bnn_mvn_draw": (_int, [ctypes.POINTER(MvnTensor), _int, _int, _p]),
     "bnn_mvn_draw_backward": (_int, [ctypes.POINTER(MvnTensor), _int, _int, _p]),
     "bnn_mvn_kl_workspace_bytes": (_i64, [ctypes.POINTER(MvnKlTensor), _int]),

@@ -10,6 +10,15 @@
 // bf16 compute: operands rounded to bf16 as they are written to LDS, v_mfma_f32_16x16x32_bf16.  fp32: v_mfma_f32_16x16x4_f32, the
 // reduction a k-ordered fp32 fma chain per tile.  Every sum is in a fixed order and there are no atomics: two identical calls
 // give identical bits.  Indices inside one sample are 32-bit (the host refuses a per-sample tensor of 2^31 elements or more).
+//
+// FLIP (FlipOutNormalConv3d, pytorch_bayesian/nn/conv.py:237-251, groups == 1): every tile runs TWO contractions on one pass over
+// the gathers -- the mean weights, and the stddev weights with the per-example signs applied as the second copy of an operand is
+// written to LDS (x 1.0 / -1.0, exact in both modes).  Signs: sg[s][b][O + C] (R = [0, O), S = [O, O + C)), sample stride sg_ss.
+//   FWD   A2 = A (.) S_s[b][c]; epilogue acc + R_s[b][o] acc2.  One sample per workgroup (a shared input recomputes the mean
+//         contraction per sample: the kernel is gather-bound and the second MFMA set rides on the same LDS tiles).
+//   DGRAD A2 = gy (.) R_s[b][o]; at the end of each sample acc += S_s[b][c] acc2, acc2 = 0 (a shared input: in sample order).
+//   WGRAD A2 = x (.) S_s[b][c], B2 = gy (.) R_s[b][o]; both partials to slabs [slab][s][mean | stddev][O][K], then
+//         k_conv3d_flip_wsum adds slabs and samples in a fixed order and applies softplus'.
 #include "bnn_device.hpp"
 
 #include <algorithm>
@@ -49,6 +58,8 @@ struct Conv3dArgs {
     const float *bias; int64_t b_ss;         // FWD: S x O drawn bias or NULL
     float *out;                              // FWD: y; DGRAD: gx; WGRAD: slab base (or gw when nslab == 1)
     int32_t S, shared, nslab, chunk;         // WGRAD: slabs per (sample, group), reduction positions per slab (% C3_BK == 0)
+    const float *sg; int64_t sg_ss;          // FLIP: signs B x (O + C) per sample, sample stride (0: one set for all)
+    int64_t w_std;                           // FLIP: element offset of the stddev row in w
 };
 
 template <typename T> struct Op;
@@ -67,12 +78,14 @@ template <> struct Op<uint16_t> {
 __device__ __forceinline__ void st_lds(float *p, float v) { *p = v; }
 __device__ __forceinline__ void st_lds(uint16_t *p, float v) { *p = f2bf(v); }
 
-template <typename T, int MODE>
+template <typename T, int MODE, bool FLIP = false>
 __global__ __launch_bounds__(C3_THREADS) void k_conv3d(const Conv3dGeo g, const Conv3dArgs a)
 {
     constexpr int LDK = Op<T>::LDK;
-    __shared__ __attribute__((aligned(16))) T As[C3_BM * LDK];
-    __shared__ __attribute__((aligned(16))) T Bs[C3_BN * LDK];
+    constexpr int NT = FLIP ? 2 : 1;         // operand copies in LDS: plain, and (FLIP) signed / stddev
+    __shared__ __attribute__((aligned(16))) T As[NT * C3_BM * LDK];
+    __shared__ __attribute__((aligned(16))) T Bs[NT * C3_BN * LDK];
+    const int32_t OC = g.O + g.C;            // FLIP: one example's signs
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -100,25 +113,30 @@ __global__ __launch_bounds__(C3_THREADS) void k_conv3d(const Conv3dGeo g, const 
     const int32_t am = m0 + ar;
     const bool arow = am < M;
     int32_t abase = 0, z0 = 0, z1 = 0, z2 = 0;   // FWD / DGRAD: gather origin of the row; WGRAD: its tap
+    int32_t arow_sg = 0;                          // FLIP: FWD / DGRAD the row's example b (O + C); WGRAD O + the row's channel
     if (MODE == C3_FWD && arow) {
         const uint32_t b = fdiv(am, g.fP), p = am - b * g.P;
+        arow_sg = (int32_t)b * OC + g.O;
         const uint32_t q = fdiv(p, g.fOW), ow = p - q * g.OW, od = fdiv(q, g.fOH), oh = q - od * g.OH;
         z0 = od * g.sd - g.pd; z1 = oh * g.sh - g.ph; z2 = ow * g.sw - g.pw;
         abase = (b * g.C + grp * g.Cg) * g.Pin;
     } else if (MODE == C3_DGRAD && arow) {
         const uint32_t b = fdiv(am, g.fPin), p = am - b * g.Pin;
         const uint32_t q = fdiv(p, g.fW), iw = p - q * g.W, id = fdiv(q, g.fH), ih = q - id * g.H;
+        arow_sg = (int32_t)b * OC;
         z0 = id + g.pd; z1 = ih + g.ph; z2 = iw + g.pw;
         abase = (b * g.O + grp * g.Ng) * g.P;
     } else if (MODE == C3_WGRAD && arow) {
         const uint32_t c = fdiv(am, g.fT), t = am - c * g.T;
         const uint32_t q = fdiv(t, g.fKW), kw = t - q * g.KW, kd = fdiv(q, g.fKH), kh = q - kd * g.KH;
+        arow_sg = g.O + (int32_t)c;
         z0 = kd * g.dd - g.pd; z1 = kh * g.dh - g.ph; z2 = kw * g.dw - g.pw;
         abase = (grp * g.Cg + c) * g.Pin;
     }
 
-    auto fetch_a = [&](int sm, int32_t r0, float (&v)[16]) {
+    auto fetch_a = [&](int sm, int32_t r0, float (&v)[16], float (&sa)[16]) {
         int32_t r = r0 + ah * 16;
+        const float *sgs = FLIP ? a.sg + (int64_t)(s + sm) * a.sg_ss + arow_sg : nullptr;
         if (MODE == C3_WGRAD) {
             // reduction index = output position (b, od, oh, ow), stepped with carries
             const float *x = a.x + (int64_t)s * a.x_ss;
@@ -134,6 +152,7 @@ __global__ __launch_bounds__(C3_THREADS) void k_conv3d(const Conv3dGeo g, const 
                 const bool ok = arow && r + j < rend && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H &&
                                 (uint32_t)iw < (uint32_t)g.W;
                 v[j] = ok ? x[(int64_t)b * g.C * g.Pin + abase + (id * g.H + ih) * g.W + iw] : 0.f;
+                if constexpr (FLIP) sa[j] = ok ? sgs[(int32_t)b * OC] : 0.f;
                 if (++ow == (uint32_t)g.OW) { ow = 0; if (++oh == (uint32_t)g.OH) { oh = 0; if (++od == (uint32_t)g.OD) { od = 0; ++b; } } }
             }
             return;
@@ -163,23 +182,26 @@ __global__ __launch_bounds__(C3_THREADS) void k_conv3d(const Conv3dGeo g, const 
                 off = (int32_t)c * g.P + (int32_t)((od * g.OH + oh) * g.OW + ow);
             }
             v[j] = ok ? src[abase + off] : 0.f;
+            if constexpr (FLIP) sa[j] = ok ? sgs[c] : 0.f;
             if (++kw == (uint32_t)g.KW) { kw = 0; if (++kh == (uint32_t)g.KH) { kh = 0; if (++kd == (uint32_t)g.KD) { kd = 0; ++c; } } }
         }
     };
 
     // ---- B loader: reduction offset bk of each k-tile, rows bn + 8 i of the tile
     const int bk = tid & (C3_BK - 1), bn = tid >> 5;
-    auto fetch_b = [&](int sm, int32_t r0, float (&v)[8]) {
+    auto fetch_b = [&](int sm, int32_t r0, float (&v)[8], float (&v2)[8]) {
         const int32_t r = r0 + bk;
         const bool rok = r < rend;
         if (MODE == C3_WGRAD) {
             uint32_t b = 0, p = 0;
             if (rok) { b = fdiv(r, g.fP); p = r - b * g.P; }
             const float *gy = a.gy + ((int64_t)s * g.B + b) * g.O * g.P + (int64_t)grp * g.Ng * g.P + p;
+            const float *rs = FLIP ? a.sg + (int64_t)s * a.sg_ss + (int64_t)b * OC : nullptr;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int32_t n = n0 + bn + 8 * i;
                 v[i] = (rok && n < N) ? gy[(int64_t)n * g.P] : 0.f;
+                if constexpr (FLIP) v2[i] = (rok && n < N) ? v[i] * rs[n] : 0.f;
             }
             return;
         }
@@ -195,65 +217,106 @@ __global__ __launch_bounds__(C3_THREADS) void k_conv3d(const Conv3dGeo g, const 
         for (int i = 0; i < 8; ++i) {
             const int32_t n = n0 + bn + 8 * i;
             v[i] = (rok && n < N) ? Op<T>::ld(a.w, wb + (int64_t)n * nstride + roff) : 0.f;
+            if constexpr (FLIP) v2[i] = (rok && n < N) ? Op<T>::ld(a.w, a.w_std + wb + (int64_t)n * nstride + roff) : 0.f;
         }
     };
 
-    auto store_tiles = [&](const float (&va)[16], const float (&vb)[8]) {
+    auto store_tiles = [&](const float (&va)[16], const float (&sa)[16], const float (&vb)[8], const float (&vb2)[8]) {
         T *pa = As + ar * LDK + ah * 16;
 #pragma unroll
         for (int j = 0; j < 16; ++j) st_lds(pa + j, va[j]);
 #pragma unroll
         for (int i = 0; i < 8; ++i) st_lds(Bs + (bn + 8 * i) * LDK + bk, vb[i]);
+        if constexpr (FLIP) {
+            T *pa2 = pa + C3_BM * LDK;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) st_lds(pa2 + j, va[j] * sa[j]);          // x +-1: exact, then rounded as the plain copy
+#pragma unroll
+            for (int i = 0; i < 8; ++i) st_lds(Bs + (C3_BN + bn + 8 * i) * LDK + bk, vb2[i]);
+        }
     };
 
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    f32x4 acc[4][2];
+    f32x4 acc[NT][4][2];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int h = 0; h < NT; ++h)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // FLIP DGRAD: acc += S_smp[b][c] acc2 at the end of sample smp's reduction (lane rows m, columns n = c as in the epilogue)
+    auto fold = [&](int smp) {
+        const float *sgs = a.sg + (int64_t)smp * a.sg_ss + g.O;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int32_t m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + q;
+                    const bool ok = m < M && n < N;
+                    const float sgn = ok ? sgs[(int32_t)fdiv(ok ? m : 0, g.fPin) * OC + n] : 0.f;
+                    acc[0][i][j][q] = __builtin_fmaf(sgn, acc[NT - 1][i][j][q], acc[0][i][j][q]);
+                    acc[NT - 1][i][j][q] = 0.f;
+                }
+        }
+    };
 
     const int ntile = rend > rbeg ? (rend - rbeg + C3_BK - 1) / C3_BK : 0;
     const int nstep = nsum * ntile;
-    float va[16], vb[8];
-    if (nstep > 0) { fetch_a(0, rbeg, va); fetch_b(0, rbeg, vb); }
+    float va[16], sa[16], vb[8], vb2[8];          // sa, vb2: FLIP only (dead otherwise)
+    if (nstep > 0) { fetch_a(0, rbeg, va, sa); fetch_b(0, rbeg, vb, vb2); }
     for (int step = 0; step < nstep; ++step) {
         __syncthreads();                                // the previous tile's fragment reads are done
-        store_tiles(va, vb);
+        store_tiles(va, sa, vb, vb2);
         __syncthreads();
         if (step + 1 < nstep) {                         // the next tile's loads fly under this tile's MFMAs
             const int nx = step + 1, sm = nx / ntile;
             const int32_t r0 = rbeg + (nx - sm * ntile) * C3_BK;
-            fetch_a(sm, r0, va);
-            fetch_b(sm, r0, vb);
+            fetch_a(sm, r0, va, sa);
+            fetch_b(sm, r0, vb, vb2);
         }
         if constexpr (sizeof(T) == 2) {
             typedef short s16x8 __attribute__((ext_vector_type(8)));
-            s16x8 fa[4], fb[2];
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                fa[i] = *reinterpret_cast<const s16x8 *>(As + (wm * 64 + i * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
+            for (int h = 0; h < NT; ++h) {
+                const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
+                s16x8 fa[4], fb[2];
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-                fb[j] = *reinterpret_cast<const s16x8 *>(Bs + (wn * 32 + j * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
+                for (int i = 0; i < 4; ++i)
+                    fa[i] = *reinterpret_cast<const s16x8 *>(A + (wm * 64 + i * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < C3_BK / 4; ++kk) {
-                float fa[4], fb[2];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) fa[i] = As[(wm * 64 + i * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) fb[j] = Bs[(wn * 32 + j * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+                for (int j = 0; j < 2; ++j)
+                    fb[j] = *reinterpret_cast<const s16x8 *>(Bt + (wn * 32 + j * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+                    for (int j = 0; j < 2; ++j)
+                        acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[h][i][j], 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < C3_BK / 4; ++kk) {
+#pragma unroll
+                for (int h = 0; h < NT; ++h) {
+                    const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
+                    float fa[4], fb[2];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) fa[i] = A[(wm * 64 + i * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) fb[j] = Bt[(wn * 32 + j * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[h][i][j], 0, 0, 0);
+                }
             }
         }
+        if constexpr (FLIP && MODE == C3_DGRAD)
+            if ((step + 1) % ntile == 0) fold(s + step / ntile);
     }
 
     // ---- epilogue: lane holds C[(lane >> 4) * 4 + q][lane & 15] of each 16 x 16 block
@@ -269,8 +332,17 @@ __global__ __launch_bounds__(C3_THREADS) void k_conv3d(const Conv3dGeo g, const 
             for (int q = 0; q < 4; ++q) {
                 const int32_t m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + q;
                 if (m >= M) continue;
-                const float v = acc[i][j][q];
-                if (MODE == C3_FWD) {
+                const float v = acc[0][i][j][q];
+                if (MODE == C3_FWD && FLIP) {
+                    const uint32_t b = fdiv(m, g.fP), p = m - b * g.P;
+                    const float r = a.sg[(int64_t)s * a.sg_ss + (int32_t)b * OC + n];
+                    a.out[(int64_t)s * g.B * g.O * g.P + (b * g.O + n) * g.P + p] = __builtin_fmaf(r, acc[NT - 1][i][j][q], v);
+                } else if (MODE == C3_WGRAD && FLIP) {
+                    // slab [slab][s][mean | stddev][o][k]
+                    const int64_t e = (((int64_t)slab * a.S + s) * 2 * g.O + n) * g.K + m;
+                    a.out[e] = v;
+                    a.out[e + (int64_t)g.O * g.K] = acc[NT - 1][i][j][q];
+                } else if (MODE == C3_FWD) {
                     const uint32_t b = fdiv(m, g.fP), p = m - b * g.P;
                     a.out[(int64_t)s * g.B * g.O * g.P + (b * g.O + grp * g.Ng + n) * g.P + p] = v + bias;
                 } else if (MODE == C3_DGRAD) {
@@ -293,6 +365,28 @@ __global__ __launch_bounds__(256) void k_conv3d_slab_sum(const float *__restrict
     float v = 0.f;
     for (int k = 0; k < nslab; ++k) v += slabs[(int64_t)k * slab_stride + e];
     gw[e] = v;
+}
+
+// FLIP: g_mean[e] = sum_s sum_slab mean partials, g_scale[e] = (sum_s sum_slab stddev partials) softplus'(rho[e]); samples in
+// order, each sample's slabs in slab order
+__global__ __launch_bounds__(256) void k_conv3d_flip_wsum(const float *__restrict__ slabs, int nslab, int S, const float *__restrict__ rho,
+                                                         float *__restrict__ g_mean, float *__restrict__ g_scale, int64_t n)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    float gm = 0.f, gs = 0.f;
+    for (int s = 0; s < S; ++s) {
+        float vm = 0.f, vs = 0.f;
+        for (int k = 0; k < nslab; ++k) {
+            const float *p = slabs + (((int64_t)k * S + s) * 2) * n + e;
+            vm += p[0];
+            vs += p[n];
+        }
+        gm += vm;
+        gs += vs;
+    }
+    g_mean[e] = gm;
+    g_scale[e] = gs * dsoftplus(rho[e]);
 }
 
 // gb[s][o] = sum over (b, position) of gy[s][b][o][.]: one workgroup per (s, o), fixed strided partials and a fixed tree
@@ -391,11 +485,39 @@ static void wgrad_split(const Conv3dGeo &g, int nsamples, int &nslab, int &chunk
     nslab = (int)((R + chunk - 1) / chunk);
 }
 
-template <int MODE>
+template <int MODE, bool FLIP = false>
 static void launch(const Conv3dGeo &g, const Conv3dArgs &a, int compute, dim3 grid, hipStream_t st)
 {
-    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_conv3d<uint16_t, MODE>), grid, dim3(C3_THREADS), 0, st, g, a);
-    else hipLaunchKernelGGL((k_conv3d<float, MODE>), grid, dim3(C3_THREADS), 0, st, g, a);
+    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_conv3d<uint16_t, MODE, FLIP>), grid, dim3(C3_THREADS), 0, st, g, a);
+    else hipLaunchKernelGGL((k_conv3d<float, MODE, FLIP>), grid, dim3(C3_THREADS), 0, st, g, a);
+}
+
+// the Flipout entries' shared checks: K7's index ranges (conv3d_geo), groups == 1, the signs' layout
+static int flip_geo(const char *who, const bnn_conv3d_shape_t *sh, int nsamples, int compute, Conv3dGeo &g)
+{
+    int rc = conv3d_geo(who, sh, nsamples, compute, g);
+    if (rc) return rc;
+    if (g.groups != 1) { set_error("%s: groups != 1", who); return BNN_E_UNSUPPORTED; }
+    if ((double)g.B * (g.O + g.C) >= 2147483647.0) { set_error("%s: B (O + C) signs of 2^31 or more", who); return BNN_E_RANGE; }
+    return BNN_OK;
+}
+
+static int check_signs(const char *who, const float *sg, int64_t sg_ss, const Conv3dGeo &g, int nsamples)
+{
+    if (!sg) { set_error("%s: NULL signs", who); return BNN_E_NULL; }
+    if (sg_ss < 0 || (nsamples > 1 && sg_ss > 0 && sg_ss < (int64_t)g.B * (g.O + g.C))) {
+        set_error("%s: bad sign sample stride", who);
+        return BNN_E_SHAPE;
+    }
+    if (mis4(sg)) { set_error("%s: misaligned signs", who); return BNN_E_ALIGN; }
+    return BNN_OK;
+}
+
+// [mean | stddev] rows: the stddev row starts one padded row (bf16: a multiple of 8 elements) after the mean row
+static int64_t flip_w_std(const Conv3dGeo &g, int compute)
+{
+    const int64_t n = (int64_t)g.O * g.K;
+    return compute == BNN_COMPUTE_BF16 ? (n + 7) / 8 * 8 : n;
 }
 
 }  // namespace bnn
@@ -488,6 +610,90 @@ int bnn_conv3d_backward_weight(const float *x, int64_t x_sample_stride, const fl
         if ((rc = check_launch(who))) return rc;
     }
     return BNN_OK;
+}
+
+int bnn_conv3d_flipout_forward(const float *x, int64_t x_sample_stride, const void *w, const float *signs, int64_t sign_sample_stride,
+                               float *y, const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *stream)
+{
+    const char *who = "bnn_conv3d_flipout_forward";
+    Conv3dGeo g;
+    int rc = flip_geo(who, shape, nsamples, compute, g);
+    if (rc) return rc;
+    if (!x || !y) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if ((rc = check_w(who, w, 0, g, nsamples, compute))) return rc;
+    if ((rc = check_signs(who, signs, sign_sample_stride, g, nsamples))) return rc;
+    if (x_sample_stride < 0) { set_error("%s: negative sample stride", who); return BNN_E_SHAPE; }
+    if (mis4(x) || mis4(y)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    Conv3dArgs a{};
+    a.x = x; a.x_ss = x_sample_stride; a.w = w; a.w_std = flip_w_std(g, compute); a.out = y;
+    a.sg = signs; a.sg_ss = sign_sample_stride; a.S = nsamples; a.shared = x_sample_stride == 0;
+    const dim3 grid((unsigned)(((int64_t)g.B * g.P + C3_BM - 1) / C3_BM), (unsigned)((g.O + C3_BN - 1) / C3_BN), (unsigned)nsamples);
+    launch<C3_FWD, true>(g, a, compute, grid, (hipStream_t)stream);
+    return check_launch(who);
+}
+
+int bnn_conv3d_flipout_backward_input(const float *gy, const void *w, const float *signs, int64_t sign_sample_stride, float *gx,
+                                      int shared_x, const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *stream)
+{
+    const char *who = "bnn_conv3d_flipout_backward_input";
+    Conv3dGeo g;
+    int rc = flip_geo(who, shape, nsamples, compute, g);
+    if (rc) return rc;
+    if (!gy || !gx) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if ((rc = check_w(who, w, 0, g, nsamples, compute))) return rc;
+    if ((rc = check_signs(who, signs, sign_sample_stride, g, nsamples))) return rc;
+    if (mis4(gy) || mis4(gx)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    Conv3dArgs a{};
+    a.gy = gy; a.w = w; a.w_std = flip_w_std(g, compute); a.out = gx; a.S = nsamples; a.shared = shared_x ? 1 : 0;
+    a.sg = signs; a.sg_ss = sign_sample_stride;
+    const dim3 grid((unsigned)(((int64_t)g.B * g.Pin + C3_BM - 1) / C3_BM), (unsigned)((g.C + C3_BN - 1) / C3_BN),
+                    (unsigned)(shared_x ? 1 : nsamples));
+    launch<C3_DGRAD, true>(g, a, compute, grid, (hipStream_t)stream);
+    return check_launch(who);
+}
+
+int64_t bnn_conv3d_flipout_backward_weight_workspace_bytes(const bnn_conv3d_shape_t *shape, int nsamples)
+{
+    Conv3dGeo g;
+    if (flip_geo("bnn_conv3d_flipout_backward_weight_workspace_bytes", shape, nsamples, BNN_COMPUTE_F32, g)) return -1;
+    int nslab, chunk;
+    wgrad_split(g, nsamples, nslab, chunk);
+    return (int64_t)nslab * nsamples * 2 * g.O * g.K * (int64_t)sizeof(float);
+}
+
+int bnn_conv3d_flipout_backward_weight(const float *x, int64_t x_sample_stride, const float *gy, const float *signs,
+                                       int64_t sign_sample_stride, const float *rho, float *g_mean, float *g_scale,
+                                       const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *workspace,
+                                       int64_t workspace_bytes, void *stream)
+{
+    const char *who = "bnn_conv3d_flipout_backward_weight";
+    Conv3dGeo g;
+    int rc = flip_geo(who, shape, nsamples, compute, g);
+    if (rc) return rc;
+    if (!x || !gy || !rho || !g_mean || !g_scale) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if ((rc = check_signs(who, signs, sign_sample_stride, g, nsamples))) return rc;
+    if (x_sample_stride < 0) { set_error("%s: negative sample stride", who); return BNN_E_SHAPE; }
+    if (mis4(x) || mis4(gy) || mis4(rho) || mis4(g_mean) || mis4(g_scale) || mis4(workspace)) {
+        set_error("%s: misaligned pointer", who);
+        return BNN_E_ALIGN;
+    }
+    int nslab, chunk;
+    wgrad_split(g, nsamples, nslab, chunk);
+    const int64_t n = (int64_t)g.O * g.K;
+    if (!workspace || workspace_bytes < (int64_t)nslab * nsamples * 2 * n * (int64_t)sizeof(float)) {
+        set_error("%s: workspace of bnn_conv3d_flipout_backward_weight_workspace_bytes bytes needed", who);
+        return BNN_E_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    Conv3dArgs a{};
+    a.x = x; a.x_ss = x_sample_stride; a.gy = gy; a.out = static_cast<float *>(workspace);
+    a.S = nsamples; a.nslab = nslab; a.chunk = chunk; a.sg = signs; a.sg_ss = sign_sample_stride;
+    const dim3 grid((unsigned)((g.K + C3_BM - 1) / C3_BM), (unsigned)((g.O + C3_BN - 1) / C3_BN), (unsigned)(nsamples * nslab));
+    launch<C3_WGRAD, true>(g, a, compute, grid, st);
+    if ((rc = check_launch(who))) return rc;
+    hipLaunchKernelGGL(k_conv3d_flip_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
+                       nslab, nsamples, rho, g_mean, g_scale, n);
+    return check_launch(who);
 }
 
 }  // extern "C"

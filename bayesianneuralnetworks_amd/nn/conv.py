@@ -3,7 +3,8 @@
 NormalConv2d is the hot path: an implicit-GEMM MFMA kernel whose B-operand loader draws the
 filter bank (bnn_conv2d_forward_sampled).  NormalConv1d runs on the same kernels (images of height 1).  NormalConv3d draws
 all S MC samples in one launch and contracts them in one implicit-GEMM launch, backward included (bnn_conv3d_forward_drawn,
-csrc/bnn_conv3d.hip).  The FlipOut variants run on HIP on the device (2-d, and 1-d as 2-d at height 1); in a network's
+csrc/bnn_conv3d.hip).  The FlipOut variants run on HIP on the device (2-d, 1-d as 2-d at height 1, and 3-d with groups == 1 on
+the Flipout tiles of csrc/bnn_conv3d.hip); in a network's
 MC-batched device pass their signs are keyed per MC sample (bnn_conv2d_flipout_forward_mc, bnn_flipout_signs).  The MC-dropout
 variants run their torch conv once and apply the keyed masks of a network's MC-batched device pass in HIP (bnn_mc_dropout).
 """
@@ -183,7 +184,9 @@ class FlipOutNormalConvNd(NormalConvNd):
     like a posterior draw (layer.flip_key; sign contract in include/bnn_hip.h, conv layout).  2-d (and 1-d, as 2-d at height 1):
     in the bf16 mode at inference ONE keyed launch for all S samples (bnn_conv2d_flipout_forward_mc: the mean contraction of a
     shared input computed once, no sign tensor in memory); otherwise the signs are materialized (bnn_flipout_signs), a shared
-    input is fanned out to S * B rows and the launches above run on it.  3-d: materialized signs and torch conv3d.
+    input is fanned out to S * B rows and the launches above run on it.  3-d (groups == 1): one sign launch (bnn_flipout_signs)
+    and the Flipout implicit GEMM on the shared B rows or the S * B rows (bnn_conv3d_flipout_forward, HIP backward); the serial
+    device path runs the same kernels with one sample on layer.R / layer.S; other group counts keep the torch expression.
     sample=False in such a pass reuses flip_key.  layer.R / layer.S keep the values of the last serial-loop (torch.rand) call."""
 
     _op = None
@@ -214,6 +217,10 @@ class FlipOutNormalConvNd(NormalConvNd):
             self.sample(x.size(0), self._ones)
         if x.is_cuda and x.dim() == 4 and type(self)._op is torch.nn.functional.conv2d:
             return _flipout_conv2d_device(self, x, self.R, self.S, lambda t: t, self.stride, self.padding, self.dilation)
+        if x.is_cuda and x.dim() == 5 and len(self._ones) == 3:
+            y = self._serial3d(x)
+            if y is not None:
+                return y
         conv = type(self)._op
         out = conv(x, self.weight.mean, self.bias, self.stride, self.padding, self.dilation, self.groups)
         noise = conv(x * self.S.expand_as(x), self.weight.stddev, self.bias, self.stride, self.padding,
@@ -235,7 +242,16 @@ class FlipOutNormalConvNd(NormalConvNd):
             return self._mc2d(x.unsqueeze(2), key, shared, B, lambda t: t.unsqueeze(2), geo).squeeze(2)
         if nd == 2:
             return self._mc2d(x, key, shared, B, lambda t: t, (self.stride, self.padding, self.dilation))
-        # 3-d: the reference expression (conv.py:244-258) on materialized keyed signs and the fanned-out input
+        if ops.conv3d_flipout_eligible((B,) + tuple(x.shape[1:]), self.weight.mean.shape, S, self.stride, self.padding,
+                                       self.dilation, self.groups):
+            # 3-d: one sign launch, then the Flipout implicit GEMM on the shared B rows or the S * B rows (no fan-out)
+            sg = ops.flipout_signs(key, B, O + C, x.device)
+            x6 = x if shared else x.reshape(S, B, *x.shape[1:])
+            y = ops.conv3d_flipout(x6, self.weight.mean, self.weight.scale, sg, S, shared, self.stride, self.padding,
+                                   self.dilation, _settings.get_compute())
+            return y.reshape(S * B, *y.shape[2:])
+        # 3-d, a shape the HIP entries refuse (groups != 1, index range): the reference expression (conv.py:244-258) on
+        # materialized keyed signs and the fanned-out input
         sg = ops.flipout_signs(key, B, O + C, x.device).reshape(S * B, O + C)
         R, Sg = sg[:, :O].reshape(S * B, O, 1, 1, 1), sg[:, O:].reshape(S * B, C, 1, 1, 1)
         xf = x.unsqueeze(0).expand(S, *x.shape).reshape(S * B, *x.shape[1:]) if shared else x
@@ -243,6 +259,20 @@ class FlipOutNormalConvNd(NormalConvNd):
         out = conv(xf, self.weight.mean, None, self.stride, self.padding, self.dilation, self.groups)
         noise = conv(xf * Sg, self.weight.stddev, None, self.stride, self.padding, self.dilation, self.groups)
         return out + noise * R
+
+    def _serial3d(self, x):
+        """conv.py:244-258 on the device for a 5-d x and the recorded layer.R / layer.S: the Flipout implicit GEMM with ONE sample
+        (the B x (O + C) sign copy).  None: the HIP entries refuse the shape, or the recorded signs are not one per example."""
+        B, O, C = x.shape[0], self.weight.size(0), self.weight.size(1)
+        R, Sg = self.R, self.S
+        if (R.numel() != B * O or Sg.numel() != B * C or not R.is_cuda or not Sg.is_cuda or
+                not ops.conv3d_flipout_eligible(tuple(x.shape), self.weight.mean.shape, 1, self.stride, self.padding, self.dilation,
+                                                self.groups)):
+            return None
+        sg = torch.cat([R.reshape(B, O), Sg.reshape(B, C)], 1).float()
+        y = ops.conv3d_flipout(x, self.weight.mean, self.weight.scale, sg, 1, True, self.stride, self.padding, self.dilation,
+                               _settings.get_compute())
+        return y[0]
 
     def _mc2d(self, x, key, shared, B, view, geo):
         S = key.nsamples

@@ -1756,6 +1756,97 @@ def conv3d_plain(x, w, b, nsamples, shared_x, stride, padding, dilation, groups,
                          _compute_code(compute))
 
 
+# --------------------------------------------------------------------------- Flipout conv3d (FlipOutNormalConv3d on the device)
+def _flip3d_operands(mean, scale, compute):
+    """[O K mean | O K stddev] (OIDHW order, stddev = 1e-10 + softplus(scale)) in ONE bnn_draw_multi launch (kinds 1 / 2, one flat
+    row each): bf16 rows padded to a multiple of 8, or fp32 rows -> (2, ld)."""
+    dev = mean.device
+    n = mean.numel()
+    bf = compute == _lib.COMPUTE_BF16
+    ld = (n + 7) // 8 * 8 if bf else n
+    w = torch.empty((2, ld), dtype=torch.bfloat16 if bf else torch.float32, device=dev)
+    arr = (_lib.DrawTensor * 2)()
+    for i, kind in enumerate((1, 2)):
+        t = arr[i]
+        t.mu, t.rho, t.rows, t.cols = mean.data_ptr(), scale.data_ptr(), 1, n
+        t.out, t.ld, t.out_sample_stride = w.data_ptr() + i * ld * w.element_size(), ld, ld
+        t.out_dtype, t.kind, t.taps = (_lib.BF16 if bf else _lib.F32), kind, 0
+    check(_lib.load().bnn_draw_multi(arr, 2, 1, None, 0, None, stream_ptr(dev)), "bnn_draw_multi")
+    return w
+
+
+def conv3d_flipout_eligible(x_shape, mean_shape, nsamples, stride, padding, dilation, groups):
+    """The Flipout conv3d entries take this shape (groups == 1, K7's index ranges, B (O + C) < 2^31) -- host arithmetic only.
+    False: the caller keeps the torch expression."""
+    if int(groups) != 1 or len(x_shape) != 5 or len(mean_shape) != 5:
+        return False
+    try:
+        sh, _ = _conv3d_shape(x_shape, mean_shape, stride, padding, dilation, groups)
+    except BnnHipError:
+        return False
+    return _lib.load().bnn_conv3d_flipout_backward_weight_workspace_bytes(ctypes.byref(sh), int(nsamples)) >= 0
+
+
+class _FlipoutConv3d(torch.autograd.Function):
+    """y[s][b] = conv3d(x[s | 0][b], mean) + R_s[b] (.) conv3d(x[s | 0][b] (.) S_s[b], stddev) (FlipOutNormalConv3d.forward,
+    conv.py:237-251, groups == 1) for S samples on csrc/bnn_conv3d.hip's Flipout tiles: one operand draw + one contraction launch.
+    signs (S | 1, B, O + C): R then S per example (bnn_flipout_signs' conv layout), saved for the backward.  Backward: the operands
+    again (one draw), one input-gradient launch, one slab launch + one reduce for d/d mean and d/d scale."""
+
+    @staticmethod
+    def forward(ctx, x, mean, scale, signs, S, shared_x, conv_args, compute):
+        require_cuda_f32(x, "x")
+        require_cuda_f32(mean, "weight.mean")
+        require_cuda_f32(scale, "weight.scale")
+        require_cuda_f32(signs, "signs")
+        stride, padding, dilation = conv_args
+        if x.dim() != (5 if shared_x else 6) or (not shared_x and x.shape[0] != S):
+            raise BnnHipError("conv3d_flipout: x must be (B, C, D, H, W) shared by the samples or (S, B, C, D, H, W), got %s"
+                              % (tuple(x.shape),))
+        sh, (OD, OH, OW) = _conv3d_shape(x.shape[-5:], mean.shape, stride, padding, dilation, 1)
+        OC = sh.O + sh.C
+        if signs.numel() not in (sh.B * OC, S * sh.B * OC):
+            raise BnnHipError("conv3d_flipout: signs must hold (1 or %d) x %d x %d values, got %s" % (S, sh.B, OC, tuple(signs.shape)))
+        sg_ss = 0 if signs.numel() == sh.B * OC else sh.B * OC
+        dev = x.device
+        w = _flip3d_operands(mean, scale, compute)
+        y = torch.empty((S, sh.B, sh.O, OD, OH, OW), dtype=torch.float32, device=dev)
+        check(_lib.load().bnn_conv3d_flipout_forward(ptr(x), 0 if shared_x else x[0].numel(), ptr(w), ptr(signs), sg_ss, ptr(y),
+                                                     ctypes.byref(sh), S, compute, stream_ptr(dev)), "bnn_conv3d_flipout_forward")
+        ctx.save_for_backward(x, mean, scale, signs)
+        ctx.S, ctx.shared_x, ctx.sh, ctx.compute, ctx.sg_ss = S, shared_x, sh, compute, sg_ss
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, mean, scale, signs = ctx.saved_tensors
+        S, sh, compute, sg_ss, dev = ctx.S, ctx.sh, ctx.compute, ctx.sg_ss, gy.device
+        lib, st = _lib.load(), stream_ptr(dev)
+        gy = gy.contiguous()
+        gx = g_mean = g_scale = None
+        if ctx.needs_input_grad[0]:
+            w = _flip3d_operands(mean, scale, compute)
+            gx = torch.empty(x.shape, dtype=torch.float32, device=dev)
+            check(lib.bnn_conv3d_flipout_backward_input(ptr(gy), ptr(w), ptr(signs), sg_ss, ptr(gx), int(ctx.shared_x),
+                                                        ctypes.byref(sh), S, compute, st), "bnn_conv3d_flipout_backward_input")
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            g_mean, g_scale = torch.empty_like(mean), torch.empty_like(scale)
+            nb = lib.bnn_conv3d_flipout_backward_weight_workspace_bytes(ctypes.byref(sh), S)
+            ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)          # this call's own slabs
+            check(lib.bnn_conv3d_flipout_backward_weight(ptr(x), 0 if ctx.shared_x else x[0].numel(), ptr(gy), ptr(signs), sg_ss,
+                                                         ptr(scale), ptr(g_mean), ptr(g_scale), ctypes.byref(sh), S, compute,
+                                                         ptr(ws), nb, st), "bnn_conv3d_flipout_backward_weight")
+        return gx, g_mean, g_scale, None, None, None, None, None
+
+
+def conv3d_flipout(x, mean, scale, signs, nsamples, shared_x, stride, padding, dilation, compute="f32"):
+    """FlipOutNormalConv3d on the device for `nsamples` MC samples: x (B, C, D, H, W) shared by them (shared_x) or
+    (S, B, C, D, H, W), signs (S | 1, B, O + C) fp32 +-1 (R then S per example; one set is used by every sample) -> (S, B, O, OD,
+    OH, OW) fp32.  Draw + contraction: two launches; autograd to x, mean and scale.  groups == 1 (conv3d_flipout_eligible)."""
+    return _FlipoutConv3d.apply(x.contiguous(), mean.contiguous(), scale.contiguous(), signs.detach().contiguous(), int(nsamples),
+                                bool(shared_x), (tuple(stride), tuple(padding), tuple(dilation)), _compute_code(compute))
+
+
 # --------------------------------------------------------------------------- MultivariateNormalLinear (MVN-noise contract)
 def _mvn_extent(mu, scale):
     """(rows, cols) of a full-covariance posterior: mean (..., K), scale (..., K, K)."""

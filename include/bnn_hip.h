@@ -601,6 +601,36 @@ int bnn_conv3d_backward_weight(const float *x, int64_t x_sample_stride, const fl
                                const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *workspace,
                                int64_t workspace_bytes, void *stream);
 
+/* ---- Flipout conv3d (FlipOutNormalConv3d on the device), groups == 1 -------------------------------------------------------
+ *   y[s][b] = conv3d(x[s | 0][b], mean) + R_s[b] (.) conv3d(x[s | 0][b] (.) S_s[b], stddev),   stddev = 1e-10 + softplus(scale)
+ * The K7 tile skeleton with two contractions per tile on one pass over the gathers.  w = [O K mean | O K stddev], OIDHW order,
+ * K = C KD KH KW: bf16 rows padded to roundup(O K, 8) (BNN_COMPUTE_BF16) or fp32 rows of O K (BNN_COMPUTE_F32) -- ONE
+ * bnn_draw_multi with kinds 1 / 2, rows = 1, nsamples = 1.  signs: the conv layout of the Flipout-sign contract, per sample B rows
+ * of O + C fp32 +-1 (R first, then S) -- what bnn_flipout_signs writes -- at sign_sample_stride elements (0: one set for every
+ * sample).  Refusals (nothing launched): K7's index ranges and B (O + C) >= 2^31 (BNN_E_RANGE), groups != 1 (BNN_E_UNSUPPORTED).
+ * Fixed summation orders, no atomics: identical calls give identical bits.
+ * Forward, ONE launch for all samples: x fp32 (x_sample_stride 0: shared), y nsamples x B x O x OD x OH x OW fp32.
+ * replaces  FlipOutNormalConv3d.forward  pytorch_bayesian/nn/conv.py:237-251 */
+int bnn_conv3d_flipout_forward(const float *x, int64_t x_sample_stride, const void *w, const float *signs, int64_t sign_sample_stride,
+                               float *y, const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *stream);
+/* Input gradient, ONE launch: gx = dgrad(gy, mean) + S (.) dgrad(gy (.) R, stddev), gy nsamples x B x O x OD x OH x OW fp32.
+ * shared_x != 0: gx is B x C x D x H x W, the samples summed inside the kernel in sample order (each sample's S_s fold at its
+ * end); else nsamples x B x C x D x H x W.
+ * replaces  autograd through FlipOutNormalConv3d.forward (input)  pytorch_bayesian/nn/conv.py:237-251 */
+int bnn_conv3d_flipout_backward_input(const float *gy, const void *w, const float *signs, int64_t sign_sample_stride, float *gx,
+                                      int shared_x, const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *stream);
+/* Posterior gradients, TWO launches: one slab launch computes g_mean_s = wgrad(x, gy_s) and g_stddev_s = wgrad(x (.) S_s, gy_s (.) R_s)
+ * from one pass over the gathers into the CALLER's workspace (bnn_conv3d_flipout_backward_weight_workspace_bytes(shape, nsamples)
+ * bytes, 4-B aligned, always needed; -1 where the entries refuse the shape); one reduce launch writes
+ *   g_mean = sum_s g_mean_s,   g_scale = (sum_s g_stddev_s) (.) softplus'(rho)   (torch's softplus backward, threshold 20),
+ * samples in order, each sample's slabs in slab order.  rho, g_mean, g_scale: O x K fp32.
+ * replaces  autograd through FlipOutNormalConv3d.forward (weight.mean, weight.scale)  pytorch_bayesian/nn/conv.py:237-251 */
+int64_t bnn_conv3d_flipout_backward_weight_workspace_bytes(const bnn_conv3d_shape_t *shape, int nsamples);
+int bnn_conv3d_flipout_backward_weight(const float *x, int64_t x_sample_stride, const float *gy, const float *signs,
+                                       int64_t sign_sample_stride, const float *rho, float *g_mean, float *g_scale,
+                                       const bnn_conv3d_shape_t *shape, int nsamples, int compute, void *workspace,
+                                       int64_t workspace_bytes, void *stream);
+
 /* ---- diagnostics ------------------------------------------------------------
  * VALU cost of the draw, no memory traffic: `blocks` workgroups of 256 threads each run
  * `iters` Philox blocks (4 draws) of stage 0 (Philox4x32-10 only), 1 (+ Box-Muller),
