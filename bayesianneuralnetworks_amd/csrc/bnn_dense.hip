@@ -19,8 +19,9 @@
 //     MFMAs, epilogue), waves 4-7 load (LDS-DMA of both operands, 1-KiB pieces taken round-robin).  One raw s_barrier per
 //     64-k step, met by all eight waves, is the only hand-off; stages are requested ST - 1 steps ahead and waited for with
 //     counted s_waitcnt vmcnt.
-//   * tiles: 128 x 160 with a 4-stage ring (the BASELINE layers: 256 workgroups), 64 / 32 x 160 for launches over few
-//     samples, 256 x 128 with 3 stages (wide layers), 256 x 80.
+//   * tiles: 128 x 160 (the BASELINE layers: 256 workgroups) with a 2-stage ring, two workgroups per CU (plain bf16 operands)
+//     or a 4-stage ring, one per CU (fp32 parity mode, dropout epilogue), 64 / 32 x 160 for launches over few samples,
+//     256 x 128 with 3 stages (wide layers), 256 x 80.
 //   * LDS image of both operands: [row][8 x 16 B] with 16-B chunk c of row r at position c ^ (r & 7); the DMA writes
 //     linearly (lane l -> position l & 7 of row l >> 3 of its 8-row piece), so lane l FETCHES chunk (l & 7) ^ (l >> 3):
 //     eight lanes read one whole 128-B line.  ds_read_b128 fragment reads of this image are conflict-free.
@@ -633,11 +634,20 @@ __device__ __forceinline__ void dma_piece(const void *base, uint32_t voff, uint3
 //   <4, 8, 4, 1, 3>: 256 x 128 tile for wide layers
 // DIAG (BNN_DENSE_DIAG): timing-only builds whose outputs are wrong: 1 = consumers skip reads and MFMAs, 2 = loaders skip the
 // DMA, 5 = no DMA and no per-step barriers either (2 vs 5 = what the barriers cost: layer 2 13.85 vs 11.9 us, ~200 cycles per
-// step); correct builds for A/B runs of the read interleave: 3 = one MFMA per interleaved fragment read, 4 = two.
+// step); correct builds for A/B runs of the read interleave: 3 = one MFMA per interleaved fragment read, 4 = two.  Of these
+// the co-resident instantiation (ST = 2) is built with 6 (stamps) only: the launcher sends every other DIAG value of a tile-1
+// launch to the 4-stage kernel (tile 5), where the measurements above were taken.
+// ST = 2 is the CO-RESIDENT instantiation (<4, 5, 2, 2, 2>: the same 128 x 160 tile, 72 KiB of ring, <= 128 registers per
+// lane): two workgroups share a CU, so one workgroup's fill, epilogue and loop stalls run under the other's main loop (the
+// steps in flight of the pipelined MLP step).  Its consumers hold ONE set of fragment registers: [reads (t, h0)] [MFMAs
+// (t, h0)] [reads (t, h1) -> barrier t + 1] [MFMAs (t, h1)] -- the read latency a wave exposes is filled by the other
+// workgroup's consumer wave on the same SIMD.  Same MFMAs in the same k order per accumulator: bit-identical results.
+// (__launch_bounds__' second argument is waves per SIMD: two 8-wave workgroups per CU = 4.)
 template <int TM, int TN, int NWM, int NWN, int ST, int YM, bool RELU, int DIAG = 0, bool DROP = false>
-__global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
+__global__ __launch_bounds__(512, ST == 2 ? 4 : 1) void k_dense_bf16(const DenseParams p)
 {
     static_assert(!DROP || YM <= 1, "the dropout epilogue stores fp32 or bf16");
+    constexpr bool CO = ST == 2;                        // co-resident: single-buffered fragments, bias loaded in the epilogue
     constexpr int NWV = 4;                              // consumer waves = loader waves
     constexpr bool INTERLEAVE = true;
     constexpr int MPR = DIAG == 3 ? 1 : DIAG == 4 ? 2 : TN >= 8 ? 2 : 1;                // MFMAs per interleaved fragment read (measured: 64 x 80 wave tile 15.9 / 16.9 us with 1 / 2, 64 x 128 at 4096^3 171 / 140 us)
@@ -785,7 +795,7 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
     }
 
     // =============================== consumer ===============================
-    static_assert(ST == 3 || ST == 4, "ring depth");
+    static_assert(ST == 2 || ST == 3 || ST == 4, "ring depth");
     // DIAG 6 (BNN_DENSE_STAMPS=<device pointer>, a diagnostic build whose outputs stay correct): consumer wave 0 of every
     // workgroup leaves s_memrealtime stamps (100 MHz) -- entry, first stage landed, loop done, stores issued, stores retired --
     // in a buffer of its own (5 x uint64 per workgroup); no output value depends on them
@@ -881,7 +891,8 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
     const int mw = m0 + wm * WM, nw = n0 + wn * WN;
     // (the 64 x 128 wave tile has no registers for it -- 128 accumulators + 96 fragment registers: the prefetch spilled up to 102
     // registers there -- and loads the bias in the epilogue, where 2 us are 0.3 % of its launch)
-    constexpr bool BIAS_PRE = TM * TN <= 20;
+    // (nor has the co-resident instantiation: its 128-register budget holds the accumulators and ONE set of fragments)
+    constexpr bool BIAS_PRE = TM * TN <= 20 && !CO;
     float bv[TN][4];
     auto load_bias = [&]() {
 #pragma unroll
@@ -912,16 +923,39 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
     if constexpr (DIAG != 5 && DIAG != 9) __builtin_amdgcn_s_barrier();         // barrier 0
     asm volatile("" ::: "memory");
     if constexpr (DIAG >= 6) stamp[1] = __builtin_amdgcn_s_memrealtime();
-    rd(I0{}, 0u, I0{});
-    uint32_t stage = 0;
-    for (int kt = 0; kt + 1 < nk; ++kt) {
-        const uint32_t next = stage + 1 == (uint32_t)ST ? 0u : stage + 1;
-        first_half(stage);
-        second_half(next);
-        stage = next;
+    if constexpr (CO) {
+        // one fragment buffer: [reads (t, h0)] [MFMAs (t, h0)] [reads (t, h1) -> barrier t + 1] [MFMAs (t, h1)]; a wave reaches
+        // barrier t + 1 with its reads of stage t complete, as above (the last step peeled for the same reason)
+        uint32_t stage = 0;
+        for (int kt = 0; kt + 1 < nk; ++kt) {
+            rd(I0{}, stage, I0{});
+            mm(I0{});
+            __builtin_amdgcn_sched_barrier(0);
+            rd(I0{}, stage, I1{});
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if constexpr (DIAG != 5 && DIAG != 9) __builtin_amdgcn_s_barrier();  // barrier kt + 1
+            asm volatile("" ::: "memory");
+            mm(I0{});
+            __builtin_amdgcn_sched_barrier(0);
+            stage = stage + 1 == (uint32_t)ST ? 0u : stage + 1;
+        }
+        rd(I0{}, stage, I0{});
+        mm(I0{});
+        __builtin_amdgcn_sched_barrier(0);
+        rd(I0{}, stage, I1{});
+        mm(I0{});
+    } else {
+        rd(I0{}, 0u, I0{});
+        uint32_t stage = 0;
+        for (int kt = 0; kt + 1 < nk; ++kt) {
+            const uint32_t next = stage + 1 == (uint32_t)ST ? 0u : stage + 1;
+            first_half(stage);
+            second_half(next);
+            stage = next;
+        }
+        first_half(stage);                              // the last step: nothing left to read ahead
+        mm(I1{});
     }
-    first_half(stage);                                  // the last step: nothing left to read ahead
-    mm(I1{});
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -942,6 +976,18 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
 
     // ---- epilogue: bias, activation, store (accumulator lane (i, q), register r = output row i, column 4 q + r of a 16 x 16 block)
     if constexpr (!BIAS_PRE) load_bias();               // (the fragment registers are dead here: one exposed round trip)
+    // co-resident: the bias goes into the accumulators once, here -- the same fp32 additions vals() makes otherwise -- so that its
+    // 4 TN registers are dead before the staging temporaries live beside the 4 TM TN accumulators (128 registers: the stores
+    // spilled 4 of them without this)
+    constexpr bool BIAS_IN_ACC = CO && !DROP;
+    if constexpr (BIAS_IN_ACC) {
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int b = 0; b < TN; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[a][b][r] += bv[b][r];
+    }
     if constexpr (DROP) {
         // bias, activation and the 1 / (1 - p) scale once, IN PLACE (one rounding of the product, as the contract has it): what a
         // copy stores is then acc or 0, and no value of the tile stays live beside the accumulators across the copy loop (the
@@ -973,7 +1019,7 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
         } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                v[r] = acc[a][b][r] + bv[b][r];
+                v[r] = BIAS_IN_ACC ? acc[a][b][r] : acc[a][b][r] + bv[b][r];
                 if (RELU) v[r] = fmaxf(v[r], 0.f);
             }
         }
@@ -1048,6 +1094,7 @@ __global__ __launch_bounds__(512) void k_dense_bf16(const DenseParams p)
         // of a staging write -- hit 16 different bank groups), read it back as A fragments, one MFMA per (16-row block, 32
         // columns) against the head's weights for those hidden units (fragments straight from memory: Nh rows x 16 TN
         // columns, read once per wave)
+        // (the co-resident ring's quarter, 18 KiB, holds the 64 x 176-B tile too: the same single pass)
         constexpr int pitch = WN * 2 + 16;
         static_assert(WM * pitch <= EPI_BYTES, "the wave's quarter of the ring holds its bf16 tile");
         char *T = lds + wave * EPI_BYTES;
@@ -1763,13 +1810,14 @@ struct DropArgs {
     bool fan;
 };
 
-// tile of a dense launch: 0 (256 x 80), 1 (128 x 160), 2 (256 x 128), 3 (64 x 160), 4 (32 x 160) -- see dense_launch
+// tile of a dense launch: 0 (256 x 80), 1 (128 x 160), 2 (256 x 128), 3 (64 x 160), 4 (32 x 160), 5 (128 x 160 on the
+// one-workgroup-per-CU 4-stage ring that tile 1 ran before its co-resident ring: A/B runs only) -- see dense_launch
 static int dense_pick_tile(int64_t M, int64_t N, int nsamples)
 {
     static const int force_tile = [] { const char *e = getenv("BNN_DENSE_TILE"); return e ? atoi(e) : -1; }();
     int tile = (N % 80 == 0 || N < 128) ? 1 : 2;
     if (N <= 80) tile = 0;
-    if (force_tile >= 0 && force_tile <= 4) tile = force_tile;
+    if (force_tile >= 0 && force_tile <= 5) tile = force_tile;
     if (tile == 1 && force_tile < 0) {
         const int64_t cols = (N + 159) / 160;
         if (((M + 127) / 128) * cols * nsamples < 128 && M > 64) tile = 3;
@@ -1863,7 +1911,12 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
     if (lprio) p.flags |= kDenseLoaderPrio;
     // tile: the BASELINE-shaped layers (N % 80 == 0: 1200 = 7.5 x 160) take 128 x 160 with a 4-stage ring -- 36 KiB per
     // 64-k step instead of 256 x 80's 42 for the same MFMAs, 4 x 8 x 8 = 256 workgroups; wide layers 256 x 128.
-    // BNN_DENSE_TILE = 0 (256 x 80), 1 (128 x 160), 2 (256 x 128), 3 (64 x 160), 4 (32 x 160) forces one for A/B runs.
+    // BNN_DENSE_TILE = 0 (256 x 80), 1 (128 x 160), 2 (256 x 128), 3 (64 x 160), 4 (32 x 160), 5 (128 x 160, one workgroup per
+    // CU) forces one for A/B runs.
+    // Tile 1 on plain bf16 operands runs CO-RESIDENT (k_dense_bf16<4, 5, 2, 2, 2>: a 2-stage ring of 72 KiB, <= 128 registers,
+    // two workgroups per CU): with steps in flight the fill, epilogue and stalls of one workgroup run under another's main
+    // loop, and a dense workgroup no longer waits for a whole empty CU.  The fp32 parity mode (its fused head stages three
+    // planes) and the dropout epilogue keep the 4-stage ring (tile 5's kernel).
     int tile = dense_pick_tile(M, N, nsamples);
     // (the dropout epilogue runs on the 80- and 160-column tiles: the 256 x 128 tile's 128 accumulators per lane leave the mask
     // no registers, so its wide layers take 128 x 160)
@@ -1873,7 +1926,7 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
     // Measured at the BASELINE layers, one stream / three steps in flight, us per step: 4 samples 54.2 / 28.3 (128 rows),
     // 51.0 / 30.9 (64), 58.7 / 37.4 (32); 2 samples 48.8 / 22.3, 44.3 / 20.8, 41.9 / 24.0; 1 sample 46.2 / 19.3, 41.3 / 17.8,
     // 39.0 / 17.9: with the chip already full of other steps' work the bigger tile wins (fewer re-reads of the weights).
-    const int bm = tile == 1 ? 128 : tile == 3 ? 64 : tile == 4 ? 32 : 256;
+    const int bm = (tile == 1 || tile == 5) ? 128 : tile == 3 ? 64 : tile == 4 ? 32 : 256;
     const int bn = tile == 0 ? 80 : tile == 2 ? 128 : 160;
     p.ntm = (int32_t)((M + bm - 1) / bm);
     p.ntn = (int32_t)((N + bn - 1) / bn);
@@ -1908,11 +1961,21 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
     do { \
         if (relu) BNN_DENSE_LAUNCH(TM_, TN_, NWM_, NWN_, ST_, true, DROP_); else BNN_DENSE_LAUNCH(TM_, TN_, NWM_, NWN_, ST_, false, DROP_); \
     } while (0)
+#define BNN_DENSE_CO(RELU_) \
+    do { \
+        if (head) hipLaunchKernelGGL((k_dense_bf16<4, 5, 2, 2, 2, 3, RELU_>), g, blk, 0, st, p); \
+        else if (!ybf) hipLaunchKernelGGL((k_dense_bf16<4, 5, 2, 2, 2, 0, RELU_>), g, blk, 0, st, p); \
+        else if (diag == 6) hipLaunchKernelGGL((k_dense_bf16<4, 5, 2, 2, 2, 1, RELU_, 6>), g, blk, 0, st, p); \
+        else hipLaunchKernelGGL((k_dense_bf16<4, 5, 2, 2, 2, 1, RELU_>), g, blk, 0, st, p); \
+    } while (0)
     if (tile == 0) BNN_DENSE_PICK(4, 5, 4, 1, 3, true);
-    else if (tile == 1) BNN_DENSE_PICK(4, 5, 2, 2, 4, true);
+    else if (tile == 1 && !x3 && !fused_drop && (diag == 0 || diag == 6)) {
+        if (relu) BNN_DENSE_CO(true); else BNN_DENSE_CO(false);
+    } else if (tile == 1 || tile == 5) BNN_DENSE_PICK(4, 5, 2, 2, 4, true);
     else if (tile == 3) BNN_DENSE_PICK(2, 5, 2, 2, 4, true);
     else if (tile == 4) BNN_DENSE_PICK(1, 5, 2, 2, 4, true);
     else BNN_DENSE_PICK(4, 8, 4, 1, 3, false);     // (no dropout epilogue: fused_drop never picks this tile)
+#undef BNN_DENSE_CO
 #undef BNN_DENSE_PICK
 #undef BNN_DENSE_LAUNCH
     int rc = check_launch(who);

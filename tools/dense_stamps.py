@@ -26,7 +26,7 @@ for it in range(5):
     ops._dense_raw(h, B * ld, B, pre, K, True, torch.bfloat16, ldx=ld, pad_rows=True)
     torch.cuda.synchronize()
 tile = int(os.environ.get('BNN_DENSE_TILE', '1'))
-bm, bn = {0: (256, 80), 1: (128, 160), 2: (256, 128), 3: (64, 160), 4: (32, 160)}[tile]
+bm, bn = {0: (256, 80), 1: (128, 160), 2: (256, 128), 3: (64, 160), 4: (32, 160), 5: (128, 160)}[tile]
 NWG = S * ((B + bm - 1) // bm) * ((NN + bn - 1) // bn)
 st = buf.cpu().numpy().reshape(-1, 5)[:NWG].astype(np.float64) * 0.01    # us
 t0 = st[:, 0].min()
