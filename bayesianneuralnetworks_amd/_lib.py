@@ -195,6 +195,11 @@ SIGNATURES = {
                              _p, _p, _p]),
     "bnn_mc_uncertainty": (_int, [_p, _i64, _int, _int, _i64, _int, _int, _p, _p, _p, _p, _p, ctypes.c_uint32,
                                   ctypes.POINTER(KlTensor), _int, _f, _p, _p, _p]),
+    "bnn_lrt_prepare": (_int, [_p, _p, _i64, _p, _p, _i64, _p]),
+    "bnn_lrt_forward": (_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _rngp, _int, _int, _p]),
+    "bnn_lrt_backward_epilogue": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _rngp, _int, _p]),
+    "bnn_lrt_backward_input": (_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _int, _int, _p]),
+    "bnn_lrt_backward_weight": (_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
 }
 
 _lib = None

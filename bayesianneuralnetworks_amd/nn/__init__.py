@@ -1,7 +1,8 @@
 from .container import BayesianModule, BayesianNetworkModule
 from .core import WeightNormal, WeightMultivariateNormal
 from .dense import (BayesianLinear, NormalLinear, MultivariateNormalLinear, FlipoutNormalLinear,
-                    NormalInverseGaussianLinear, MCDropoutLinear)
+                    NormalInverseGaussianLinear, MCDropoutLinear,
+                    LocalReparamLinear)   # (not in __all__: that list is the reference's)
 from .conv import (BayesianConvNd, NormalConvNd, NormalConv1d, NormalConv2d, NormalConv3d,
                    FlipOutNormalConvNd, FlipOutNormalConv1d, FlipOutNormalConv2d, FlipOutNormalConv3d,
                    MCDropoutConvNd, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d)

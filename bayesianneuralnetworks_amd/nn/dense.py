@@ -268,6 +268,90 @@ class NormalLinear(_NormalSampling, BayesianLinear):
         return y.reshape(S * per, *lead, y.shape[-1])
 
 
+class LocalReparamLinear(_NormalSampling, BayesianLinear):
+    """The local-reparameterization estimator of NormalLinear's posterior (Kingma, Salimans, Welling 2015): with independent
+    Gaussian w and b the pre-activation is Gaussian per output element, so the layer samples IT instead of the weights:
+
+        m = x mu_w^T + mu_b,   v = x^2 (sigma_w^2)^T + sigma_b^2,   y_s = m + sqrt(v + 1e-16) eps_s,   eps_s ~ N(0, 1)
+
+    with one eps per output element and MC sample (S B N numbers, not S N K), independent across the rows of a batch.
+    Parameters, initialisation and state_dict keys are NormalLinear's (weight.mean, weight.scale, bias.mean, bias.scale; sigma =
+    1e-10 + softplus(rho)): a checkpoint of one loads into the other, and KLDivergence, .kl_divergence(), traverse, apply_wb and
+    PruneNormal see an ordinary Gaussian layer.
+
+    Device input: bnn_lrt_prepare + bnn_lrt_forward (csrc/bnn_lrt.hip), both compute modes.  In a BayesianNetworkModule's
+    MC-batched pass all S samples run in ONE contraction launch: a layer that sees the shared batch (B rows) contracts m and v once
+    and its S outputs differ in the epilogue only; one that sees S B rows contracts per sample.  Outside such a pass (or with
+    S = 1) it is one sample on the same kernels.  layer.noise_key is the DrawKey of the last device call: element b N + n of
+    sample s is eps[b N + n] of that key's sample sample0 + s (include/bnn_hip.h, LRT-noise contract), whatever the tile, the
+    input layout or the GPU of a sharded run.  sample=False reuses noise_key.  CPU tensors: the expression above in torch with
+    torch.randn_like.
+
+    Out of scope: nn.fuse_activations / fuse_head and the network draw plan (there is no tensor to pre-draw; both select
+    NormalLinear by exact type and pass this layer by), the three-plane (x3) hand-over, a conv variant."""
+
+    def __init__(self, in_features, out_features, bias=True, prior=Normal(0, .1)):
+        super().__init__(in_features, out_features, bias, WeightNormal, prior)
+        from .._rng import new_stream_id
+        self._noise_stream = new_stream_id()        # the layer's own eps stream, beside those of its two posterior tensors
+        self.noise_key = None                       # DrawKey of the last device call
+        self._noise_shape = None                    # (rows per sample, out_features) of that call
+        self._cpu_eps = None
+
+    def reset_parameters(self):
+        _init_normal_posterior(self)
+        self.sample()
+
+    def _noise_plan(self, x):
+        """-> (S, sample0, shared_x, rows of x per sample) for the current MC context (the row convention of _mc_plan)."""
+        ctx = _mc.current()
+        if ctx is None or ctx.samples == 1:
+            return 1, (ctx.sample0 if ctx else 0), True, x.shape[0]
+        if x.shape[0] == ctx.base_batch:
+            return ctx.samples, ctx.sample0, True, x.shape[0]
+        if x.shape[0] == ctx.base_batch * ctx.samples:
+            return ctx.samples, ctx.sample0, False, ctx.base_batch
+        raise RuntimeError("mc_batched: layer input has %d rows, expected %d or %d"
+                           % (x.shape[0], ctx.base_batch, ctx.base_batch * ctx.samples))
+
+    def forward(self, x, sample=True):
+        if not x.is_cuda:
+            m = torch.nn.functional.linear(x, self.weight.mean, self.bias.mean if self.bias is not None else None)
+            v = torch.nn.functional.linear(x * x, self.weight.variance, self.bias.variance if self.bias is not None else None)
+            if sample:
+                self._cpu_eps = torch.randn_like(m)
+            elif self._cpu_eps is None or self._cpu_eps.shape != m.shape:
+                raise RuntimeError("sample=False: no noise of shape %s was drawn by an earlier call" % (tuple(m.shape),))
+            return m + torch.sqrt(v + 1e-16) * self._cpu_eps
+        if x.dim() == 1:
+            return self.forward(x.unsqueeze(0), sample).squeeze(0)
+        from .._rng import DrawKey
+        S, s0, shared, per = self._noise_plan(x)
+        mode = self._compute_mode()
+        lead = x.shape[1:-1]
+        K = x.shape[-1]
+        N = self.weight.mean.shape[0]
+        x2 = x.reshape(-1, K) if shared else x.reshape(S, -1, K)
+        shape = (x2.shape[-2], N)
+        if sample:
+            self.noise_key = DrawKey(default_generator.seed, self._noise_stream, s0, S, default_generator.next_epoch(),
+                                     gen=generator_for(mode))
+            self._noise_shape = shape
+        key = self.noise_key
+        if key is None or self._noise_shape != shape:
+            raise RuntimeError("sample=False: %s noise recorded, this call needs %s per sample"
+                               % ("no" if key is None else "a %s" % (self._noise_shape,), shape))
+        if key.nsamples != S:
+            if S != 1:
+                raise RuntimeError("sample=False: the recorded noise has %d MC samples, this call needs %d" % (key.nsamples, S))
+            key = key.last_sample()
+        odt = torch.bfloat16 if (self.out_dtype == torch.bfloat16 and mode == "bf16") else torch.float32
+        y = ops.linear_lrt(x2, self.weight.mean, self.weight.scale,
+                           self.bias.mean if self.bias is not None else None,
+                           self.bias.scale if self.bias is not None else None, key, shared, mode, out_dtype=odt)
+        return y.reshape(S * per, *lead, N)
+
+
 def _flipout_plan(layer, x):
     """Inside a BayesianNetworkModule's MC-batched pass (an McContext) on a device tensor: -> (ctx, shared), shared = x holds the
     un-replicated batch (ctx.base_batch rows) rather than S * B rows (sample = row // B).  None: the reference's torch.rand signs

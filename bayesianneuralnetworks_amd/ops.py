@@ -821,6 +821,116 @@ def linear_sampled(x, mu_w, rho_w, mu_b, rho_b, key_w, key_b, shared_x, compute=
                                 torch.is_grad_enabled())
 
 
+# --------------------------------------------------------------------------- K10: local reparameterization
+def lrt_eligible(x, mu_w, rows, nsamples):
+    """None when bnn_lrt_forward takes the call, else the reason it refuses (index range, alignment, layout).  x: (rows, K) for a
+    shared input or (S, rows, K); there is no torch fallback on device tensors -- linear_lrt raises with this reason."""
+    N, K = mu_w.shape
+    if x.shape[-1] != K:
+        return "input has %d features, weight expects %d" % (x.shape[-1], K)
+    if nsamples < 1 or nsamples > 0xFFFF:
+        return "%d MC samples (1 .. 65535)" % nsamples
+    if rows * N >= 2 ** 32:
+        return "one sample has %d x %d output elements: the noise index b N + n is 32 bits wide" % (rows, N)
+    if rows > 64 * 65535 or nsamples * rows > 64 * 65535:
+        return "%d rows (at most %d)" % (nsamples * rows, 64 * 65535)
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        return "input dtype %s (float32 or bfloat16)" % x.dtype
+    if x.data_ptr() % x.element_size():
+        return "input pointer is not aligned to its element size"
+    return None
+
+
+def _lrt_prepare_raw(rho_w, rho_b):
+    """sigma^2 of weight and bias, fp32, one launch (bnn_lrt_prepare)."""
+    s2_w = torch.empty_like(rho_w)
+    s2_b = torch.empty_like(rho_b) if rho_b is not None else None
+    check(_lib.load().bnn_lrt_prepare(ptr(rho_w), ptr(s2_w), rho_w.numel(), ptr(rho_b), ptr(s2_b),
+                                      rho_b.numel() if rho_b is not None else 0, stream_ptr(rho_w.device)), "bnn_lrt_prepare")
+    return s2_w, s2_b
+
+
+class _LrtLinear(torch.autograd.Function):
+    """y_s = m + sqrt(v + 1e-16) eps_s, m = x mu_w^T + mu_b, v = x^2 (sigma_w^2)^T + sigma_b^2 (LocalReparamLinear): one
+    operand launch + one contraction launch for all S samples.  Backward: eps re-created from the key in one elementwise launch
+    (g_m, g_v from the saved v), then the paired input- and weight-gradient contractions (csrc/bnn_lrt.hip) -- no torch matmul."""
+
+    @staticmethod
+    def forward(ctx, x, mu_w, rho_w, mu_b, rho_b, key, shared_x, compute, out_dtype, track):
+        # x: (B, K) shared by all samples, or (S, B, K); fp32 or (bf16 compute mode) bf16
+        x = x.contiguous()
+        require_cuda_act(x, "x")
+        if (x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16) and compute != _lib.COMPUTE_BF16:
+            raise BnnHipError("bf16 activations need compute mode 'bf16'")
+        for t, n in ((mu_w, "weight.mean"), (rho_w, "weight.scale")):
+            require_cuda_f32(t, n)
+        if mu_b is not None:
+            require_cuda_f32(mu_b, "bias.mean")
+            require_cuda_f32(rho_b, "bias.scale")
+        S = key.nsamples
+        B, K = x.shape[-2], x.shape[-1]
+        N = mu_w.shape[0]
+        if not shared_x and (x.dim() != 3 or x.shape[0] != S):
+            raise BnnHipError("linear_lrt: a per-sample input must be (S, B, K) with S = %d, got %s" % (S, tuple(x.shape)))
+        why = lrt_eligible(x, mu_w, B, S)
+        if why is not None:
+            raise BnnHipError("linear_lrt: " + why)
+        dev = x.device
+        needs_grad = track and any(ctx.needs_input_grad[:5])
+        s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
+        y = torch.empty((S, B, N), dtype=out_dtype, device=dev)
+        v = torch.empty((B, N) if shared_x else (S, B, N), dtype=torch.float32, device=dev) if needs_grad else None
+        flags = (_lib.FLAG_X_BF16 if _bf(x) else 0) | (_lib.FLAG_Y_BF16 if out_dtype == torch.bfloat16 else 0)
+        r = _rng_struct(key, dev)
+        check(_lib.load().bnn_lrt_forward(ptr(x), K, ptr(mu_w), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(y), ptr(v), B, N, K, S,
+                                          1 if shared_x else 0, ctypes.byref(r), compute, flags, stream_ptr(dev)), "bnn_lrt_forward")
+        if needs_grad:
+            ctx.save_for_backward(x, mu_w, rho_w, rho_b if mu_b is not None else None, s2_w, v)
+        ctx.key, ctx.shared_x, ctx.compute = key, shared_x, compute
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, mu_w, rho_w, rho_b, s2_w, v = ctx.saved_tensors
+        S, compute, shared = ctx.key.nsamples, ctx.compute, ctx.shared_x
+        N, K = mu_w.shape
+        B = x.shape[-2]
+        M = B if shared else S * B
+        dev = gy.device
+        lib = _lib.load()
+        gy = gy.contiguous()
+        if compute != _lib.COMPUTE_BF16 and gy.dtype != torch.float32:
+            gy = gy.float()
+        g_m = torch.empty((M, N), dtype=torch.float32, device=dev)
+        g_v = torch.empty((M, N), dtype=torch.float32, device=dev)
+        r = _rng_struct(ctx.key, dev)
+        check(lib.bnn_lrt_backward_epilogue(ptr(gy), ptr(v), ptr(g_m), ptr(g_v), B, N, S, 1 if shared else 0, ctypes.byref(r),
+                                            _lib.FLAG_X_BF16 if _bf(gy) else 0, stream_ptr(dev)), "bnn_lrt_backward_epilogue")
+        xflag = _lib.FLAG_X_BF16 if _bf(x) else 0
+        gx = g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            check(lib.bnn_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(mu_w), ptr(s2_w), ptr(x), K, ptr(gx), M, N, K, compute,
+                                             xflag | (_lib.FLAG_Y_BF16 if _bf(x) else 0), stream_ptr(dev)), "bnn_lrt_backward_input")
+        need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or need_b:
+            g_mu_w, g_rho_w = torch.empty_like(mu_w), torch.empty_like(rho_w)
+            if need_b:
+                g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
+            check(lib.bnn_lrt_backward_weight(ptr(x), K, ptr(g_m), ptr(g_v), ptr(rho_w), ptr(g_mu_w), ptr(g_rho_w),
+                                              ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), M, N, K, compute, xflag,
+                                              stream_ptr(dev)), "bnn_lrt_backward_weight")
+        return gx, g_mu_w, g_rho_w, g_mu_b, g_rho_b, None, None, None, None, None
+
+
+def linear_lrt(x, mu_w, rho_w, mu_b, rho_b, key, shared_x, compute="f32", out_dtype=torch.float32):
+    """LocalReparamLinear on the device: -> (S, B, N), S = key.nsamples; sample s uses eps[b N + n] of the key's sample
+    sample0 + s.  Raises BnnHipError (with lrt_eligible's reason) for a call the kernel refuses: no torch fallback."""
+    return _LrtLinear.apply(x, mu_w.contiguous(), rho_w.contiguous(),
+                            None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
+                            key, shared_x, _compute_code(compute), out_dtype, torch.is_grad_enabled())
+
+
 class _PlainLinear(torch.autograd.Function):
     """y[s] = x[s] @ w[s]^T + b[s] with given weights (F.linear, dense.py:60)."""
 

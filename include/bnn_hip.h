@@ -77,6 +77,14 @@
  *   summation order over j is fixed by K alone, so w_s is the same bit for bit for any nsamples, sample0 or grid, and where
  *   the backward or a shard re-creates it.  O K < 2^32 per tensor.
  *   CPU twin: tests/test_mvn_device.py (mvn_twin), on the oracle's Philox.
+ *
+ * LRT-noise contract (the local-reparameterization dense layer: bnn_lrt_forward, bnn_lrt_backward_epilogue)
+ *   The noise of LocalReparamLinear is one eps per OUTPUT element and MC sample, on the eps stream above (same bnn_rng_t fields,
+ *   both generators, one device function: eps4), one stream per layer: element e = b N + n of a sample's (B, N) output -- row b
+ *   within the sample, N outputs per row -- uses eps[e] of sample sample0 + s.  The value depends only on the key and
+ *   (s, b, n): not on the tile shape, not on whether the input is shared by the samples or given per sample, not on which GPU
+ *   of a sharded run computes the sample.  The backward re-creates it from the key; it is never stored.  B N < 2^32 per sample.
+ *   CPU twin: oracle.eps_fill on the key (tests/test_lrt_device.py).
  */
 #ifndef BNN_HIP_H
 #define BNN_HIP_H
@@ -805,6 +813,51 @@ int bnn_mc_uncertainty(const float *y, int64_t addend_stride, int nparts, int ns
                        uint32_t *advance_epoch, uint32_t advance_inc,
                        const bnn_kl_tensor_t *kl_tensors, int kl_ntensors, float kl_n_batches,
                        float *kl_out, const void *kl_workspace, void *stream);
+
+/* ---- K10: local reparameterization (LocalReparamLinear, bayesianneuralnetworks_amd/nn/dense.py; Kingma, Salimans, Welling 2015,
+ * "Variational Dropout and the Local Reparameterization Trick").  The layer has no call site in the reference: it is the other
+ * estimator of NormalLinear's posterior (pytorch_bayesian/nn/dense.py:27-60).  With w ~ N(mu_w, sigma_w^2), b ~ N(mu_b, sigma_b^2)
+ * independent, y = x w^T + b is Gaussian per output element:
+ *     m = x mu_w^T + mu_b                      (mean contraction)
+ *     v = x^2 (sigma_w^2)^T + sigma_b^2        (variance contraction, x^2 element-wise)
+ *     y_s = m + sqrt(v + 1e-16) eps_s          eps_s ~ N(0, 1): the LRT-noise contract above
+ * Both contractions of a pair run in one tile from one pass over the shared operand (x is squared in fp32 before any rounding).
+ * compute: BNN_COMPUTE_F32 = fp32 operands on v_mfma_f32_16x16x4_f32, an ordered fp32 fma chain per output element;
+ * BNN_COMPUTE_BF16 = every operand rounded to bf16 (RNE) as it is staged, v_mfma_f32_16x16x32_bf16, fp32 accumulate.  No
+ * atomics and no split contraction: identical calls give identical bits.  Errors (nothing launched): BNN_E_NULL, BNN_E_SHAPE
+ * (extent < 1, ldx < K), BNN_E_RANGE (more than 65535 samples, B N >= 2^32, rows > 64 * 65535, bad rng), BNN_E_DTYPE (compute),
+ * BNN_E_UNSUPPORTED (bf16 activations in the fp32 mode), BNN_E_ALIGN (element alignment; 16 bytes for every output).
+ *
+ * bnn_lrt_prepare: s2_w[i] = sigma(rho_w[i])^2 for i < n_w and s2_b likewise (n_b may be 0), sigma = 1e-10 + softplus(rho):
+ * the variance operands of one forward and its backward, one launch. */
+int bnn_lrt_prepare(const float *rho_w, float *s2_w, int64_t n_w, const float *rho_b, float *s2_b, int64_t n_b, void *stream);
+/* y_s = m + sqrt(v + 1e-16) eps_s for s = 0 .. nsamples - 1, ONE launch.  mu_w, s2_w: (N, K) fp32; mu_b, s2_b: (N) fp32, both
+ * or neither.  shared_x != 0: x is (B, K) (row pitch ldx) and serves every sample -- m and v are contracted once and the
+ * workgroup loops over the samples in its epilogue only; otherwise x is (nsamples B, K), rows [s B, (s + 1) B) belong to
+ * sample s, and the sample is a grid dimension.  y: (nsamples B, N), rows [s B, (s + 1) B) sample s.  v_out (may be NULL):
+ * v, (B, N) for a shared x, (nsamples B, N) otherwise -- what bnn_lrt_backward_epilogue reads.
+ * flags: BNN_FLAG_X_BF16 = x is bf16, BNN_FLAG_Y_BF16 = y is written as bf16 (bf16 compute only). */
+int bnn_lrt_forward(const void *x, int64_t ldx, const float *mu_w, const float *s2_w, const float *mu_b, const float *s2_b,
+                    void *y, float *v_out, int64_t B, int64_t N, int64_t K, int nsamples, int shared_x,
+                    const bnn_rng_t *rng, int compute, int flags, void *stream);
+/* The elementwise part of the backward, eps re-created from the key:
+ *     g_m = sum_s gy_s,   g_v = sum_s gy_s eps_s / (2 sqrt(v + 1e-16))     shared_x: (B, N), the sum in sample order
+ *     g_m[s] = gy_s,      g_v[s] = gy_s eps_s / (2 sqrt(v_s + 1e-16))      otherwise: (nsamples B, N)
+ * gy: (nsamples B, N), fp32 or (BNN_FLAG_X_BF16) bf16; v as bnn_lrt_forward stored it; g_m, g_v fp32. */
+int bnn_lrt_backward_epilogue(const void *gy, const float *v, float *g_m, float *g_v, int64_t B, int64_t N, int nsamples,
+                              int shared_x, const bnn_rng_t *rng, int flags, void *stream);
+/* g_x = g_m mu_w + 2 x (.) (g_v sigma_w^2): both contractions (over n) in one tile, the product with 2 x in the epilogue.
+ * g_m, g_v: (M, N) fp32; x: (M, K) fp32 or (BNN_FLAG_X_BF16) bf16, row pitch ldx; gx: (M, K) fp32 or (BNN_FLAG_Y_BF16) bf16.
+ * M = B for a shared input (one sample's size), nsamples B otherwise (per row). */
+int bnn_lrt_backward_input(const float *g_m, const float *g_v, const float *mu_w, const float *s2_w, const void *x, int64_t ldx,
+                           void *gx, int64_t M, int64_t N, int64_t K, int compute, int flags, void *stream);
+/* g_mu_w = g_m^T x and g(sigma_w^2) = g_v^T x^2 in one tile (the contraction runs over all M rows in row order), then
+ * g_rho_w = g(sigma_w^2) 2 sigma_w sigmoid(rho_w) in the epilogue.  Bias (rho_b, g_mu_b, g_rho_b all given, or all NULL), a second
+ * launch: g_mu_b = sum_rows g_m, g_rho_b = (sum_rows g_v) 2 sigma_b sigmoid(rho_b), rows added in a fixed order.
+ * flags: BNN_FLAG_X_BF16 = x is bf16. */
+int bnn_lrt_backward_weight(const void *x, int64_t ldx, const float *g_m, const float *g_v, const float *rho_w, float *g_mu_w,
+                            float *g_rho_w, const float *rho_b, float *g_mu_b, float *g_rho_b, int64_t M, int64_t N, int64_t K,
+                            int compute, int flags, void *stream);
 
 #ifdef __cplusplus
 }
