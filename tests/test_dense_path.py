@@ -29,6 +29,11 @@ def N(t):
     return t.detach().float().cpu().numpy()
 
 
+def _pair(v):
+    """A scalar geometry argument or an (h, w) pair -> the pair (the reference's _pair): the conv bodies below take either."""
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
 def _post(shape, seed, dev, bias=True):
     gen = torch.Generator().manual_seed(seed)
     mw, rw, mb, rb = seeded.posterior(gen, shape, bias)
@@ -66,21 +71,25 @@ def test_draw_multi_equals_standalone_sampler_and_oracle(env, shape, S, gen):
 
 
 @pytest.mark.parametrize("O,C,k,S,gen,x3", [(64, 64, 3, 8, 1, False), (128, 128, 3, 3, 0, True), (16, 8, 5, 2, 1, False), (5, 16, 7, 2, 0, False),
-                                               (24, 40, 2, 3, 1, True), (3, 8, 1, 2, 0, False), (10, 12, 3, 2, 1, False)])
+                                               (24, 40, 2, 3, 1, True), (3, 8, 1, 2, 0, False), (10, 12, 3, 2, 1, False),
+                                               # KH != KW (taps = KH KW of a non-square window), both bodies, both output kinds
+                                               (64, 64, (3, 2), 3, 1, False), (128, 128, (1, 3), 2, 0, True), (16, 8, (5, 1), 2, 1, False),
+                                               (10, 12, (2, 3), 2, 0, False), (24, 40, (1, 4), 3, 1, True)])
 def test_conv_weight_draw_tap_major(env, O, C, k, S, gen, x3):
-    """A conv weight (O, C, k, k) drawn tap-major (element (o, c, t) -> column t C + c; C % 8 == 0: groups of 8 channels x taps through
+    """A conv weight (O, C, KH, KW) drawn tap-major (element (o, c, t) -> column t C + c; C % 8 == 0: groups of 8 channels x taps through
     LDS, 16-B chunks; C = 12: the general body): the values of K1 on the same key, permuted -- bit for bit --, zero padding, for
-    bf16 and three-plane outputs and both eps streams."""
+    bf16 and three-plane outputs and both eps streams.  k: one window size or a (KH, KW) pair."""
     from bayesianneuralnetworks_amd._rng import DrawKey
     ops, dev = env["ops"], env["dev"]
-    g = torch.Generator().manual_seed(O + C + k)
-    mw = (torch.randn(O, C, k, k, generator=g) * 0.1).to(dev)
-    rw = (torch.randn(O, C, k, k, generator=g) * 0.2 - 2.0).to(dev)
+    kh, kw_ = _pair(k)
+    g = torch.Generator().manual_seed(O + C + (k if isinstance(k, int) else 16 * kh + kw_))
+    mw = (torch.randn(O, C, kh, kw_, generator=g) * 0.1).to(dev)
+    rw = (torch.randn(O, C, kh, kw_, generator=g) * 0.2 - 2.0).to(dev)
     kw = DrawKey(31, 7, 1, S, 4, gen=gen)
-    K, taps = C * k * k, k * k
+    K, taps = C * kh * kw_, kh * kw_
     pre = ops.draw_layers([(mw.reshape(O, K), rw.reshape(O, K), None, None, kw, None, taps)], S, x3=x3)[0]
     kp = (K + 63) // 64 * 64
-    w = ops._sample_affine_philox_raw(mw, rw, kw)                                  # (S, O, C, k, k) fp32, the same key
+    w = ops._sample_affine_philox_raw(mw, rw, kw)                                  # (S, O, C, KH, KW) fp32, the same key
     want = w.reshape(S, O, C, taps).transpose(2, 3).reshape(S, O, K)              # tap-major
     if x3:
         assert pre.w.shape == (3, S, O, kp)
@@ -318,6 +327,43 @@ def test_draw_plan_is_consumed_once_and_matches_per_layer_draws(env):
 
 
 # ------------------------------------------------------------------ conv2d as implicit GEMM on drawn weights
+def _swapped_axis_note(got, x64, w64, b64, st, pad, dil, groups=1, tol=1e-2):
+    """For the message of a failed conv comparison: which ONE (h, w) pair, swapped in the float64 reference, reproduces the device's
+    output -- the axis the kernel mixed up.  x64 (B, C, H, W), w64 (O, C / groups, KH, KW), b64 or None: float64 CPU tensors."""
+    got = np.asarray(got, dtype=np.float64)
+    found = []
+    for name in ("window", "stride", "padding", "dilation"):
+        w_, st_, pad_, dil_ = w64, tuple(st), tuple(pad), tuple(dil)
+        if name == "window":
+            if w64.shape[2] == w64.shape[3]:
+                continue
+            w_ = w64.reshape(w64.shape[0], w64.shape[1], w64.shape[3], w64.shape[2])         # the same numbers read as (KW, KH)
+        elif name == "stride":
+            st_ = st_[::-1]
+        elif name == "padding":
+            pad_ = pad_[::-1]
+        else:
+            dil_ = dil_[::-1]
+        if (st_, pad_, dil_) == (tuple(st), tuple(pad), tuple(dil)) and w_ is w64:
+            continue
+        try:
+            alt = torch.nn.functional.conv2d(x64, w_, b64, st_, pad_, dil_, groups).numpy()
+        except RuntimeError:
+            continue
+        if alt.shape == got.shape and allclose_scaled(got, alt, tol):
+            found.append(name)
+    return "; the device output equals the reference with this pair swapped: %s" % ", ".join(found) if found else \
+        "; no single swapped (h, w) pair reproduces the device output"
+
+
+def _assert_conv_close(got, want, tol, what, x64, w64, b64, st, pad, dil, groups=1):
+    """assert_close_scaled; a failure names the swapped axis (the extra float64 convolutions run only then)."""
+    try:
+        return assert_close_scaled(got, want, tol, what)
+    except AssertionError as e:
+        raise AssertionError(str(e) + _swapped_axis_note(got, x64, w64, b64, st, pad, dil, groups)) from None
+
+
 CONV_CASES = [  # B, C, O, H, W, k, stride, pad, dil, shared_x
     (5, 64, 64, 6, 6, 3, 2, 1, 1, False),          # the MNIST / FashionMNIST layer (configs[2] shape), ragged last tile
     (1024, 64, 64, 6, 6, 3, 2, 1, 1, False),       # configs[2] at full size (checked on a slice)
@@ -329,17 +375,26 @@ CONV_CASES = [  # B, C, O, H, W, k, stride, pad, dil, shared_x
 ]
 
 
-def _random_conv_cases(n, seed):
+def _random_conv_cases(n, seed, per_axis=False, accept=None):
+    """n seeded cases (B, C, O, H, W, k, st, pad, dil, shared).  per_axis: every geometry entry is an (h, w) pair drawn per axis
+    (the scalar draw, twice); accept(case) -> bool: draw by rejection until n cases pass, so that no drawn case is left out later.
+    The default arguments draw the same numbers in the same order as ever."""
     rng = np.random.RandomState(seed)
     out = []
     while len(out) < n:
         C, O = int(rng.choice([64, 128, 256])), int(rng.choice([64, 128]))
         H, W = int(rng.randint(2, 9)), int(rng.randint(2, 9))
-        k, st, pad, dil = int(rng.choice([1, 2, 3])), int(rng.choice([1, 2])), int(rng.choice([0, 1, 2])), int(rng.choice([1, 2]))
-        OH, OW = (H + 2 * pad - dil * (k - 1) - 1) // st + 1, (W + 2 * pad - dil * (k - 1) - 1) // st + 1
-        if OH < 1 or OW < 1 or OH * OW > 128 or pad >= k * dil:
+        if per_axis:
+            k, st, pad, dil = (tuple(int(v) for v in rng.choice(vals, 2)) for vals in ([1, 2, 3], [1, 2], [0, 1, 2], [1, 2]))
+        else:
+            k, st, pad, dil = int(rng.choice([1, 2, 3])), int(rng.choice([1, 2])), int(rng.choice([0, 1, 2])), int(rng.choice([1, 2]))
+        (kh, kw), (sh, sw), (ph, pw), (dh, dw) = _pair(k), _pair(st), _pair(pad), _pair(dil)
+        OH, OW = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+        if OH < 1 or OW < 1 or OH * OW > 128 or ph >= kh * dh or pw >= kw * dw:
             continue
-        out.append((int(rng.choice([1, 3, 9, 17])), C, O, H, W, k, st, pad, dil, bool(rng.randint(2))))
+        case = (int(rng.choice([1, 3, 9, 17])), C, O, H, W, k, st, pad, dil, bool(rng.randint(2)))
+        if accept is None or accept(case):
+            out.append(case)
     return out
 
 
@@ -358,11 +413,12 @@ def test_conv_dense_path_random_shapes(env, B, C, O, H, W, k, st, pad, dil, shar
 def test_conv_dense_path_vs_oracle(env, B, C, O, H, W, k, st, pad, dil, shared):
     """NormalConv2d in bf16 mode (draw once, tap-major + k_conv_bf16) against the oracle's F.conv2d on the same Philox
     draws with bf16-rounded inputs / weights (double accumulate) -- 1e-5 of the output scale; and the launch count: one
-    draw + one contraction, no im2col panel."""
+    draw + one contraction, no im2col panel.  k, st, pad, dil: one number for both axes or an (h, w) pair."""
     import bayesianneuralnetworks_amd as bnn
     from bayesianneuralnetworks_amd.nn import NormalConv2d
     from bayesianneuralnetworks_amd import _mc
     orc, dev = env["orc"], env["dev"]
+    (kh, kw_), st2, pad2, dil2 = _pair(k), _pair(st), _pair(pad), _pair(dil)
     S = 8 if B >= 256 else 3
     torch.manual_seed(B + C + O)
     layer = NormalConv2d(C, O, k, stride=st, padding=pad, dilation=dil).to(dev)
@@ -381,10 +437,10 @@ def test_conv_dense_path_vs_oracle(env, B, C, O, H, W, k, st, pad, dil, shared):
     y = N(y).reshape(S, B, O, OH, OW)
     kw, kb = layer.weight.draw_key, layer.bias.draw_key
     # the weights the launch drew (same keys -> same launch), back from tap-major to (O, C, KH, KW): bit-identical to K1 ...
-    K = C * k * k
+    K = C * kh * kw_
     pre = env["ops"].draw_layers([(layer.weight.mean.detach().reshape(O, K), layer.weight.scale.detach().reshape(O, K),
-                                   layer.bias.mean.detach(), layer.bias.scale.detach(), kw, kb, k * k)], S)[0]
-    wt = pre.w[:, :, :K].reshape(S, O, k * k, C).permute(0, 1, 3, 2).reshape(S, O, C, k, k)
+                                   layer.bias.mean.detach(), layer.bias.scale.detach(), kw, kb, kh * kw_)], S)[0]
+    wt = pre.w[:, :, :K].reshape(S, O, kh * kw_, C).permute(0, 1, 3, 2).reshape(S, O, C, kh, kw_)
     w1 = env["ops"]._sample_affine_philox_raw(layer.weight.mean.detach(), layer.weight.scale.detach(), kw, out_dtype=torch.bfloat16)
     assert torch.equal(wt, w1) and (pre.w[:, :, K:] == 0).all()
     # ... and within one bf16 ulp of the oracle's draw (a weight within the eps twin's 1e-6 of a rounding boundary rounds the
@@ -397,7 +453,7 @@ def test_conv_dense_path_vs_oracle(env, B, C, O, H, W, k, st, pad, dil, shared):
     xr = orc.bf16_round(x.numpy())
     for s in range(S):
         xs = xr[sel] if shared else xr[s * B:(s + 1) * B][sel]
-        want = orc.conv2d(xs, N(wt[s]), N(pre.b[s]), stride=(st, st), padding=(pad, pad), dilation=(dil, dil))
+        want = orc.conv2d(xs, N(wt[s]), N(pre.b[s]), stride=st2, padding=pad2, dilation=dil2)
         assert allclose_scaled(y[s][sel], want), np.abs(y[s][sel] - want).max()
     # EVERY image of EVERY workgroup tile (the slice above leaves most tiles of configs[2] / [3] unseen): the whole
     # batch against torch's conv2d in float64 on the CPU, fed the device's own bf16 weights and the bf16-rounded inputs --
@@ -406,10 +462,11 @@ def test_conv_dense_path_vs_oracle(env, B, C, O, H, W, k, st, pad, dil, shared):
     worst = 0.0
     for s in range(S):
         xs = xr64 if shared else xr64[s * B:(s + 1) * B]
-        full = torch.nn.functional.conv2d(xs, wt[s].double().cpu(), pre.b[s].double().cpu(), stride=st, padding=pad, dilation=dil).numpy()
-        assert np.abs(full[sel] - orc.conv2d(xs[sel].float().numpy(), N(wt[s]), N(pre.b[s]), stride=(st, st), padding=(pad, pad),
-                                             dilation=(dil, dil))).max() < 1e-4
-        assert_close_scaled(y[s], full, 1e-5, "conv %s sample %d, all %d images" % ((B, C, O, H, W, k, st, pad, dil), s, B))
+        full = torch.nn.functional.conv2d(xs, wt[s].double().cpu(), pre.b[s].double().cpu(), stride=st2, padding=pad2, dilation=dil2).numpy()
+        assert np.abs(full[sel] - orc.conv2d(xs[sel].float().numpy(), N(wt[s]), N(pre.b[s]), stride=st2, padding=pad2,
+                                             dilation=dil2)).max() < 1e-4
+        _assert_conv_close(y[s], full, 1e-5, "conv %s sample %d, all %d images" % ((B, C, O, H, W, k, st, pad, dil), s, B),
+                           xs, wt[s].double().cpu(), pre.b[s].double().cpu(), st2, pad2, dil2)
         worst = max(worst, float(np.abs(y[s] - full).max()))
     assert np.isfinite(worst)
 
@@ -447,16 +504,18 @@ def test_conv_dense_path_equals_panel_path_and_trains(env):
 
 
 @pytest.mark.parametrize("B,C,O,HW,k,st,pad", [(37, 64, 64, 6, 3, 2, 1), (5, 128, 32, 5, 3, 1, 1), (1024, 64, 64, 6, 3, 2, 1)])
-def test_flipout_conv_fused_kernel_vs_oracle(env, B, C, O, HW, k, st, pad):
+def test_flipout_conv_fused_kernel_vs_oracle(env, B, C, O, HW, k, st, pad, dil=1):
     """FlipOutNormalConv2d in bf16 mode without grad = ONE contraction launch (both operands share the A tile; S in the
     fragment's sign bits, R in the epilogue) against the reference's expression (conv.py:207-221) evaluated by the oracle
-    on bf16-rounded x / mean / stddev -- and against this package's two-convolution fp32 path on the same signs."""
+    on bf16-rounded x / mean / stddev -- and against this package's two-convolution fp32 path on the same signs.
+    HW, k, st, pad, dil: one number for both axes or an (h, w) pair."""
     import bayesianneuralnetworks_amd as bnn
     from bayesianneuralnetworks_amd.nn import FlipOutNormalConv2d
     orc, dev = env["orc"], env["dev"]
+    (H, W), (kh, kw_), st2, pad2, dil2 = _pair(HW), _pair(k), _pair(st), _pair(pad), _pair(dil)
     torch.manual_seed(B + C)
-    layer = FlipOutNormalConv2d(C, O, k, stride=st, padding=pad).to(dev)
-    x = torch.randn(B, C, HW, HW, generator=torch.Generator().manual_seed(2)).to(dev)
+    layer = FlipOutNormalConv2d(C, O, k, stride=st, padding=pad, dilation=dil).to(dev)
+    x = torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(2)).to(dev)
     bnn.set_compute("bf16")
     try:
         n0 = env["lib"].bnn_launch_count()
@@ -472,19 +531,20 @@ def test_flipout_conv_fused_kernel_vs_oracle(env, B, C, O, HW, k, st, pad):
     sel = sorted(set([0, 1, B // 2, B - 1]))
     # the weight operand the launch contracts on: bf16 mean / stddev, tap-major -- within one bf16 ulp of the rounded reference
     # values (a stddev within ~1e-6 of a rounding boundary rounds the other way), and the contraction is checked on THEM
-    K = C * k * k
+    K = C * kh * kw_
     w2 = env["ops"].flipout_conv_weights(layer.weight.mean, layer.weight.scale)
     assert (w2[:, K:] == 0).all()
-    w2 = N(w2[:, :K]).reshape(2 * O, k * k, C).transpose(0, 2, 1).reshape(2 * O, C, k, k)
+    w2 = N(w2[:, :K]).reshape(2 * O, kh * kw_, C).transpose(0, 2, 1).reshape(2 * O, C, kh, kw_)
     mean, std = w2[:O], w2[O:]
     assert (np.abs(mean - N(layer.weight.mean)) <= np.abs(N(layer.weight.mean)) * 2.0 ** -8 + 1e-30).all()
     assert (np.abs(std - N(layer.weight.stddev)) <= N(layer.weight.stddev) * 2.0 ** -8).all()
     xs = orc.bf16_round(N(x)[sel])
     Sn, Rn = N(S).reshape(B, C, 1, 1)[sel], N(R).reshape(B, O, 1, 1)[sel]
-    want = (orc.conv2d(xs, mean, None, stride=(st, st), padding=(pad, pad)) +
-            orc.conv2d(xs * Sn, std, None, stride=(st, st), padding=(pad, pad)) * Rn)
+    want = (orc.conv2d(xs, mean, None, stride=st2, padding=pad2, dilation=dil2) +
+            orc.conv2d(xs * Sn, std, None, stride=st2, padding=pad2, dilation=dil2) * Rn)
     got = N(y)[sel]
     assert allclose_scaled(got, want), np.abs(got - want).max()
+    assert np.isfinite(N(y)).all()
     rms = float(np.sqrt((N(y32) ** 2).mean()))
     assert np.abs(N(y) - N(y32)).max() <= 2e-2 * max(1.0, rms)     # bf16 operands against fp32 operands
 
@@ -711,16 +771,18 @@ def test_predictive_mean_fuses_the_head_and_matches_forward_stacked(env):
 
 @pytest.mark.parametrize("B,C,O,HW,k,st,pad", [(37, 64, 64, 6, 3, 2, 1), (9, 128, 128, 4, 3, 1, 1), (1024, 64, 64, 6, 3, 2, 1), (5, 128, 32, 5, 3, 1, 1),
                                                (3, 64, 32, 7, 2, 1, 0), (11, 256, 64, 3, 1, 1, 0)])
-def test_flipout_conv_f32_mode_without_the_panel_vs_double(env, B, C, O, HW, k, st, pad):
+def test_flipout_conv_f32_mode_without_the_panel_vs_double(env, B, C, O, HW, k, st, pad, dil=1):
     """FlipOutNormalConv2d in the fp32 PARITY mode at inference: mean and stddev as three bf16 planes (one launch), two
     implicit-GEMM contractions on three-plane operands, no im2col panel -- conv.py:207-221 evaluated by torch in float64 on the
-    layer's own mean / stddev / signs, EVERY image, 1e-5 of the output scale; with gradients wanted the panel path, same values."""
+    layer's own mean / stddev / signs, EVERY image, 1e-5 of the output scale; with gradients wanted the panel path, same values.
+    HW, k, st, pad, dil: one number for both axes or an (h, w) pair."""
     import bayesianneuralnetworks_amd as bnn
     from bayesianneuralnetworks_amd.nn import FlipOutNormalConv2d
     dev, lib = env["dev"], env["lib"]
+    (H, W), st, pad, dil = _pair(HW), _pair(st), _pair(pad), _pair(dil)
     torch.manual_seed(B + C + 3)
-    layer = FlipOutNormalConv2d(C, O, k, stride=st, padding=pad).to(dev)
-    x = torch.randn(B, C, HW, HW, generator=torch.Generator().manual_seed(4)).to(dev)
+    layer = FlipOutNormalConv2d(C, O, k, stride=st, padding=pad, dilation=dil).to(dev)
+    x = torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(4)).to(dev)
     bnn.set_compute("f32")
     n0 = lib.bnn_launch_count()
     with torch.no_grad():
@@ -729,7 +791,7 @@ def test_flipout_conv_f32_mode_without_the_panel_vs_double(env, B, C, O, HW, k, 
     R, S = layer.sampled
     F = torch.nn.functional
     x64, m64, s64 = x.double().cpu(), layer.weight.mean.detach().double().cpu(), layer.weight.stddev.detach().double().cpu()
-    want = (F.conv2d(x64, m64, None, st, pad) + F.conv2d(x64 * S.double().cpu().expand_as(x64), s64, None, st, pad) * R.double().cpu())
+    want = (F.conv2d(x64, m64, None, st, pad, dil) + F.conv2d(x64 * S.double().cpu().expand_as(x64), s64, None, st, pad, dil) * R.double().cpu())
     assert_close_scaled(N(y), want.numpy(), 1e-5, "fp32-mode Flipout conv vs float64")
     xg = x.clone().requires_grad_(True)
     yg = layer(xg, sample=False)                          # gradients wanted: the two-convolution panel path on the same signs
@@ -828,12 +890,14 @@ def test_conv_f32_mode_without_the_panel_vs_double(env, B, C, O, H, W, k, st, pa
     """NormalConv2d in the fp32 PARITY mode at inference (bnn_conv2d_dense_forward_x3: weights drawn as three bf16 planes,
     images split into planes in LDS, six plane pairs per 64-k block, no im2col panel): 1e-5 of the output scale against
     torch's conv2d in float64 on the K1 draw of the recorded keys -- EVERY image -- and pinned to the scalar oracle on a slice;
-    two launches (draw + contraction); with gradients wanted the layer stays on the panel kernels and agrees."""
+    two launches (draw + contraction); with gradients wanted the layer stays on the panel kernels and agrees.  k, st, pad, dil: one
+    number for both axes or an (h, w) pair."""
     import bayesianneuralnetworks_amd as bnn
     from bayesianneuralnetworks_amd.nn import NormalConv2d
     from bayesianneuralnetworks_amd import _mc
     ops, orc, dev, lib = env["ops"], env["orc"], env["dev"], env["lib"]
     assert ops.CONV_X3_F32
+    st2, pad2, dil2 = _pair(st), _pair(pad), _pair(dil)
     S = 8 if B >= 256 else 3
     torch.manual_seed(B + C + O + 1)
     layer = NormalConv2d(C, O, k, stride=st, padding=pad, dilation=dil).to(dev)
@@ -854,10 +918,11 @@ def test_conv_f32_mode_without_the_panel_vs_double(env, B, C, O, H, W, k, st, pa
     x64 = x.double()
     for s in range(S):
         xs = x64 if shared else x64[s * B:(s + 1) * B]
-        full = torch.nn.functional.conv2d(xs, w[s], b[s], stride=st, padding=pad, dilation=dil).numpy()
-        assert_close_scaled(y[s], full, 1e-5, "fp32-mode conv %s sample %d" % ((B, C, O, H, W, k, st, pad, dil), s))
+        full = torch.nn.functional.conv2d(xs, w[s], b[s], stride=st2, padding=pad2, dilation=dil2).numpy()
+        _assert_conv_close(y[s], full, 1e-5, "fp32-mode conv %s sample %d" % ((B, C, O, H, W, k, st, pad, dil), s),
+                           xs, w[s], b[s], st2, pad2, dil2)
     sel = [0, B - 1]
-    want = orc.conv2d((x if shared else x[:B])[sel].numpy(), w[0].float().numpy(), b[0].float().numpy(), stride=(st, st), padding=(pad, pad), dilation=(dil, dil))
+    want = orc.conv2d((x if shared else x[:B])[sel].numpy(), w[0].float().numpy(), b[0].float().numpy(), stride=st2, padding=pad2, dilation=dil2)
     assert_close_scaled(y[0][sel], want, 1e-5, "fp32-mode conv vs scalar oracle")
     # training-time forward (gradients wanted): the panel kernels, same keys -> same values to 1e-5
     with _mc.McContext(S, B, 0):

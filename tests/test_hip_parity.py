@@ -45,6 +45,11 @@ def N(t):
     return t.detach().cpu().numpy()
 
 
+def _pair(v):
+    """A scalar geometry argument or an (h, w) pair -> the pair: the conv bodies below take either."""
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
 LINEAR = ["linear_4x3", "linear_7x11", "linear_7x11_nobias", "linear_64x48", "linear_1x1",
           "linear_mnist_pretrained"]
 CONV = ["conv_1_1_k1", "conv_3_4_k3_p1", "conv_4_6_k3_s2_d2_g2", "conv_mnist_pretrained"]
@@ -577,25 +582,40 @@ def test_conv_forward_and_backward_golden(env, name):
     (16, 64, 6, 6, 64, 3, 2, 1, 1, 1, True),         # MNIST/FMNIST implicit-GEMM shape
     (8, 128, 4, 4, 128, 3, 1, 1, 1, 1, True),        # CIFAR10 shape
 ])
-def test_conv_fused_philox_vs_oracle(env, cfg):
+def test_conv_fused_philox_vs_oracle(env, cfg, mode="f32"):
+    """(k, stride, pad, dil of a cfg: one number for both axes or an (h, w) pair.  mode "bf16": the oracle is fed what the kernel
+    multiplies -- the bf16-rounded input and the device's own draw of the recorded key, rounded to bf16 -- and accumulates in double.)"""
     from bayesianneuralnetworks_amd.nn import NormalConv2d
     B, C, H, W, O, k, s, p, d, groups, bias = cfg
     dev = env["dev"]
+    kh, kw = _pair(k)
     torch.manual_seed(B + C)
     layer = NormalConv2d(C, O, k, s, p, d, groups, bias).to(dev)
     seeded.pin_streams(layer, 2020)
     env["bnn"].manual_seed(31)
     x = torch.randn(B, C, H, W, device=dev)
-    n0 = env["lib"].bnn_launch_count()
-    y = layer(x)
-    # generic implicit-GEMM kernel: 1 launch; fast path (groups 1, K % 8 == 0, O >= 16): im2col + fused GEMM
-    fast = groups == 1 and (C * k * k) % 8 == 0 and C * k * k >= 32 and O >= 16
-    assert env["lib"].bnn_launch_count() == n0 + (2 if fast else 1)
-    w, b = _oracle_layer_draw(env["orc"], layer, 0)
-    want = env["orc"].conv2d(N(x), w, b, (s, s), (p, p), (d, d), groups)
-    assert y.shape == want.shape
-    assert allclose(N(y), want)
-    assert torch.equal(layer(x, sample=False), y)
+    env["bnn"].set_compute(mode)
+    try:
+        n0 = env["lib"].bnn_launch_count()
+        y = layer(x)
+        # generic implicit-GEMM kernel: 1 launch; fast path (groups 1, K % 8 == 0, O >= 16): im2col + fused GEMM
+        fast = groups == 1 and (C * kh * kw) % 8 == 0 and C * kh * kw >= 32 and O >= 16
+        assert env["lib"].bnn_launch_count() == n0 + (2 if fast else 1)
+        w, b = _oracle_layer_draw(env["orc"], layer, 0)
+        xin = N(x)
+        if mode == "bf16":
+            # (the oracle's draw is within ~1e-6 of the device's, which can round to the neighbouring bf16 value: contract on the
+            # device's own weights, pinned to the oracle's to one bf16 ulp)
+            wd = N(env["ops"]._sample_affine_philox_raw(layer.weight.mean.detach(), layer.weight.scale.detach(), layer.weight.draw_key,
+                                                        out_dtype=torch.bfloat16)[0].float())
+            assert (np.abs(wd - w) <= np.abs(w) * 2.0 ** -8 + 1e-6).all()
+            xin, w = env["orc"].bf16_round(xin), wd
+        want = env["orc"].conv2d(xin, w, b, _pair(s), _pair(p), _pair(d), groups)
+        assert y.shape == want.shape
+        assert allclose(N(y), want), np.abs(N(y) - want).max()
+        assert torch.equal(layer(x, sample=False), y)
+    finally:
+        env["bnn"].set_compute("f32")
 
 
 def test_conv_reference_kat_and_errors(env):
@@ -1132,11 +1152,13 @@ def test_sampled_conv2d_backward_vs_float64_autograd(env, cfg, mode):
     """Sampled conv2d backward, all HIP (NCHW -> rows, im2col panel, fused weight / input gradient kernels,
     col2im): against float64 autograd through F.conv2d (conv.py:116) on the oracle's draws."""
     from bayesianneuralnetworks_amd._rng import DrawKey
-    S, B, C, H, W, O, k, st, pd, dl, bias, shared = cfg
+    S, B, C, H, W, O, k, st, pd, dl, bias, shared = cfg[:12]
+    groups = cfg[12] if len(cfg) > 12 else 1                 # (k, st, pd, dl: one number for both axes or an (h, w) pair)
+    (kh, kw_), st, pd, dl = _pair(k), _pair(st), _pair(pd), _pair(dl)
     orc, dev = env["orc"], env["dev"]
     gen = torch.Generator().manual_seed(17)
-    mu = torch.randn(O, C, k, k, generator=gen) * 0.1
-    rho = torch.randn(O, C, k, k, generator=gen) * 0.15 - 2.0
+    mu = torch.randn(O, C // groups, kh, kw_, generator=gen) * 0.1
+    rho = torch.randn(O, C // groups, kh, kw_, generator=gen) * 0.15 - 2.0
     mub = torch.randn(O, generator=gen) * 0.1
     rhob = torch.randn(O, generator=gen) * 0.15 - 2.0
     x = torch.randn((B, C, H, W) if shared else (S, B, C, H, W), generator=gen)
@@ -1145,10 +1167,11 @@ def test_sampled_conv2d_backward_vs_float64_autograd(env, cfg, mode):
     md, rd = mu.to(dev).requires_grad_(True), rho.to(dev).requires_grad_(True)
     mbd, rbd = (mub.to(dev).requires_grad_(True), rhob.to(dev).requires_grad_(True)) if bias else (None, None)
     n0 = env["lib"].bnn_launch_count()
-    y = env["ops"].conv2d_sampled(xd, md, rd, mbd, rbd, kw, kb if bias else None, shared, (st, st), (pd, pd), (dl, dl), 1, mode)
+    y = env["ops"].conv2d_sampled(xd, md, rd, mbd, rbd, kw, kb if bias else None, shared, st, pd, dl, groups, mode)
     gy = torch.randn(y.shape, generator=gen)
     grads = torch.autograd.grad(y, [xd, md, rd] + ([mbd, rbd] if bias else []), gy.to(dev))
-    if (C * k * k) % 8 == 0 and C * k * k >= 32 and O >= 16 and O % 8 == 0:
+    Kc = C * kh * kw_
+    if groups == 1 and Kc % 8 == 0 and Kc >= 32 and O >= 16 and O % 8 == 0:
         assert env["lib"].bnn_launch_count() >= n0 + 7       # fwd 2 + rows, im2col, wgrad, dgrad, col2im
     # float64 restatement
     x64 = x.double().requires_grad_(True)
@@ -1162,39 +1185,43 @@ def test_sampled_conv2d_backward_vs_float64_autograd(env, cfg, mode):
         if bias:
             eb = torch.from_numpy(orc.eps_fill(kb.seed, kb.stream, s_, kb.epoch_host, 0, (O,), kb.gen)).double()
             b_ = mb64 + (1e-10 + torch.nn.functional.softplus(rb64)) * eb
-        ys.append(torch.nn.functional.conv2d(x64 if shared else x64[s_], w, b_, st, pd, dl))
+        ys.append(torch.nn.functional.conv2d(x64 if shared else x64[s_], w, b_, st, pd, dl, groups))
     y64 = torch.stack(ys)
     tol_y = 1e-5 if mode == "f32" else 2e-2
-    assert allclose_scaled(N(y), y64.detach().numpy(), tol_y)
+    assert_close_scaled(N(y), y64.detach().numpy(), tol_y, "y %s %s" % (cfg, mode))
     want = torch.autograd.grad(y64, [x64, m64, r64] + ([mb64, rb64] if bias else []), gy.double())
     tol = 2e-5 if mode == "f32" else 3e-2
-    for got, w_ in zip(grads, want):
+    for name, got, w_ in zip(("g_x", "g_mu", "g_rho", "g_mu_b", "g_rho_b"), grads, want):
         assert got.shape == w_.shape
-        assert allclose_scaled(N(got), w_.numpy(), tol)
+        assert torch.isfinite(got).all()
+        assert_close_scaled(N(got), w_.numpy(), tol, "%s %s %s" % (name, cfg, mode))
 
 
 @pytest.mark.parametrize("shared", [False, True])
-def test_plain_conv2d_backward_panel_vs_float64_autograd(env, shared):
+def test_plain_conv2d_backward_panel_vs_float64_autograd(env, shared, cfg=(2, 3, 8, 7, 6, 12, 3, 2, 1, 1)):
     """Explicit-weight conv2d (parity mode, Flipout): backward through the panel -- rows, im2col, per-sample
-    weight gradient, plain input gradient, col2im, column sums -- against float64 autograd of F.conv2d."""
+    weight gradient, plain input gradient, col2im, column sums -- against float64 autograd of F.conv2d.
+    cfg = (S, B, C, H, W, O, k, stride, pad, dil); the last four: one number for both axes or an (h, w) pair."""
     dev = env["dev"]
     gen = torch.Generator().manual_seed(23)
-    S, B, C, H, W, O, k, st, pd = 2, 3, 8, 7, 6, 12, 3, 2, 1
-    w = torch.randn(S, O, C, k, k, generator=gen) * 0.2
+    S, B, C, H, W, O, k, st, pd, dl = cfg
+    (kh, kw_), st, pd, dl = _pair(k), _pair(st), _pair(pd), _pair(dl)
+    w = torch.randn(S, O, C, kh, kw_, generator=gen) * 0.2
     b = torch.randn(S, O, generator=gen) * 0.1
     x = torch.randn((B, C, H, W) if shared else (S, B, C, H, W), generator=gen)
     xd, wd, bd = x.to(dev).requires_grad_(True), w.to(dev).requires_grad_(True), b.to(dev).requires_grad_(True)
     n0 = env["lib"].bnn_launch_count()
-    y = env["ops"].conv2d_plain(xd, wd, bd, shared, (st, st), (pd, pd), (1, 1), 1, "f32")
+    y = env["ops"].conv2d_plain(xd, wd, bd, shared, st, pd, dl, 1, "f32")
     gy = torch.randn(y.shape, generator=gen)
     gx, gw, gb = torch.autograd.grad(y, (xd, wd, bd), gy.to(dev))
     assert env["lib"].bnn_launch_count() >= n0 + 6
     x64, w64, b64 = x.double().requires_grad_(True), w.double().requires_grad_(True), b.double().requires_grad_(True)
-    y64 = torch.stack([torch.nn.functional.conv2d(x64 if shared else x64[s_], w64[s_], b64[s_], st, pd) for s_ in range(S)])
-    assert allclose_scaled(N(y), y64.detach().numpy())
+    y64 = torch.stack([torch.nn.functional.conv2d(x64 if shared else x64[s_], w64[s_], b64[s_], st, pd, dl) for s_ in range(S)])
+    assert_close_scaled(N(y), y64.detach().numpy(), 1e-5, "y %s" % (cfg,))
     want = torch.autograd.grad(y64, (x64, w64, b64), gy.double())
-    for got, w_ in zip((gx, gw, gb), want):
-        assert got.shape == w_.shape and allclose_scaled(N(got), w_.numpy(), 2e-5)
+    for name, got, w_ in zip(("g_x", "g_w", "g_b"), (gx, gw, gb), want):
+        assert got.shape == w_.shape and torch.isfinite(got).all()
+        assert_close_scaled(N(got), w_.numpy(), 2e-5, "%s %s" % (name, cfg))
 
 
 def _random_linear_shapes():

@@ -142,6 +142,26 @@ def test_conv2d_forward_and_kl(name):
     assert abs(orc.kl_divergence(tensors, 1.0) - float(g["kl"])) <= 1e-5 * (1 + abs(float(g["kl"])))
 
 
+def _geometry_cases():
+    from test_conv2d_geometry import CASES, _cid
+    return [pytest.param(c, id=_cid(c)) for c in CASES]
+
+
+@pytest.mark.parametrize("c", _geometry_cases())
+def test_conv2d_per_axis_geometry_vs_float64_torch(c):
+    """orc.conv2d is the reference of the GPU tests in test_conv2d_geometry.py: pin it on that table -- every (h, w) pair unequal,
+    groups, border outputs that see only padding -- against torch's conv2d in float64, 1e-5 of the output scale."""
+    from conftest import assert_close_scaled
+    gen = torch.Generator().manual_seed(c.B + c.C + c.H)
+    x = torch.randn(min(c.B, 3), c.C, c.H, c.W, generator=gen)
+    w = torch.randn(c.O, c.C // c.groups, *c.k, generator=gen) * 0.1
+    b = torch.randn(c.O, generator=gen)
+    want = torch.nn.functional.conv2d(x.double(), w.double(), b.double(), c.st, c.pad, c.dil, c.groups).numpy()
+    for bias, ref in ((b.numpy(), want), (None, want - b.double().numpy().reshape(1, -1, 1, 1))):
+        y = orc.conv2d(x.numpy(), w.numpy(), bias, c.st, c.pad, c.dil, c.groups)
+        assert_close_scaled(y, ref, 1e-5, "orc.conv2d %s" % (c,))
+
+
 def test_conv_128_regenerated_from_seed():
     g = load_golden("conv_128_128_k3_p1")
     cin, cout, k, batch, hw = [int(v) for v in g["shape"]]
