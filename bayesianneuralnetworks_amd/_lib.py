@@ -200,6 +200,11 @@ SIGNATURES = {
     "bnn_lrt_backward_epilogue": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _rngp, _int, _p]),
     "bnn_lrt_backward_input": (_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _int, _int, _p]),
     "bnn_lrt_backward_weight": (_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
+    "bnn_conv3d_lrt_forward": (_int, [_p, _i64, _p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _rngp, _int, _p]),
+    "bnn_conv3d_lrt_backward_input": (_int, [_p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p]),
+    "bnn_conv3d_lrt_backward_weight_workspace_bytes": (_i64, [ctypes.POINTER(Conv3dShape), _int]),
+    "bnn_conv3d_lrt_backward_weight": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p,
+                                              _i64, _p]),
 }
 
 _lib = None

@@ -409,6 +409,368 @@ __global__ __launch_bounds__(256) void k_conv3d_bias_grad(const float *__restric
     if (threadIdx.x == 0) gb[(int64_t)s * O + o] = red[0];
 }
 
+// ---- K11: the local-reparameterization conv tile (LocalReparamConv1d / 2d / 3d, nn/conv.py) -------------------------------
+// m = conv(x, mu_w) + mu_b, v = conv(x^2, sigma_w^2) + sigma_b^2, y_s = m + sqrt(v + 1e-16) eps_s with one eps per output element
+// and MC sample (LRT-conv noise contract, include/bnn_hip.h).  The tile is k_conv3d's with TWO contractions on one pass over the
+// gathers, like its Flipout instantiation; the second copy of an operand is its square (taken in fp32, then rounded as the plain
+// copy) or a second tensor:
+//   FWD   A = gather(x), A2 = A^2; B = mu_w, B2 = sigma_w^2.  Epilogue: v (stored for the backward) and the S samples -- a shared
+//         input is contracted ONCE and the workgroup stores S tiles; a per-sample input has the sample in the grid.
+//   DGRAD A = gather(g_m), A2 = gather(g_v); B, B2 = the same weights read transposed.  Epilogue: acc + 2 x acc2.
+//   WGRAD A = gather(x), A2 = A^2; B = g_m, B2 = g_v.  Every slab adds its share of the positions of every image set in set order;
+//         both partials to slabs [slab][mean | variance][O][K], k_lrt_conv_wsum adds the slabs and applies d sigma^2 / d rho.
+// The weights (mu_w, sigma_w^2) are fp32 in memory in both modes; the bf16 mode rounds them, like every operand, as they are
+// written to LDS.
+struct LrtConvArgs {
+    const float *x;                          // FWD: the input; DGRAD: the input (2 x in the epilogue); WGRAD: the input
+    int64_t x_ss;                            // FWD: sample stride (0: shared); DGRAD / WGRAD: B C Pin (one image set)
+    const float *g1, *g2;                    // DGRAD / WGRAD: g_m, g_v, (sets, B, O, P)
+    const float *w1, *w2;                    // FWD / DGRAD: mu_w, sigma_w^2, O x K
+    const float *b1, *b2;                    // FWD: mu_b, sigma_b^2 (both or neither)
+    float *out, *out2;                       // FWD: y, v (may be NULL); DGRAD: gx; WGRAD: slab base
+    int32_t S, shared, nslab, chunk;         // FWD: samples; DGRAD / WGRAD: image sets
+    RngDev rng;
+};
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(C3_THREADS) void k_lrt_conv3d(const Conv3dGeo g, const LrtConvArgs a)
+{
+    constexpr int LDK = Op<T>::LDK;
+    __shared__ __attribute__((aligned(16))) T As[2 * C3_BM * LDK];
+    __shared__ __attribute__((aligned(16))) T Bs[2 * C3_BN * LDK];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave & 1, wn = wave >> 1;
+
+    // the block's (sample or set, group, slab)
+    int z = blockIdx.z, slab = 0;
+    if (MODE == C3_WGRAD) { slab = z % a.nslab; z /= a.nslab; }
+    const int grp = z % g.groups;
+    const int s = z / g.groups;              // FWD with a shared input, WGRAD: 0
+
+    const int32_t M = MODE == C3_FWD ? g.B * g.P : MODE == C3_DGRAD ? g.B * g.Pin : g.K;
+    const int32_t N = MODE == C3_DGRAD ? g.Cg : g.Ng;
+    const int32_t m0 = blockIdx.x * C3_BM, n0 = blockIdx.y * C3_BN;
+    int32_t rbeg = 0, rend = MODE == C3_FWD ? g.K : MODE == C3_DGRAD ? g.Ng * g.T : g.B * g.P;
+    if (MODE == C3_WGRAD) {
+        rbeg = slab * a.chunk;
+        rend = min(rend, rbeg + a.chunk);
+    }
+    const int nsum = MODE == C3_WGRAD ? a.S : 1;
+    const int64_t gset = (int64_t)g.B * g.O * g.P;       // one image set of g_m / g_v / y
+
+    // ---- A loader: row ar of the tile, reduction offsets ah * 16 .. + 15 of each k-tile
+    const int ar = tid & (C3_BM - 1);
+    const int ah = __builtin_amdgcn_readfirstlane(tid >> 7);
+    const int32_t am = m0 + ar;
+    const bool arow = am < M;
+    int32_t abase = 0, z0 = 0, z1 = 0, z2 = 0;   // FWD / DGRAD: gather origin of the row; WGRAD: its tap
+    if (MODE == C3_FWD && arow) {
+        const uint32_t b = fdiv(am, g.fP), p = am - b * g.P;
+        const uint32_t q = fdiv(p, g.fOW), ow = p - q * g.OW, od = fdiv(q, g.fOH), oh = q - od * g.OH;
+        z0 = od * g.sd - g.pd; z1 = oh * g.sh - g.ph; z2 = ow * g.sw - g.pw;
+        abase = (b * g.C + grp * g.Cg) * g.Pin;
+    } else if (MODE == C3_DGRAD && arow) {
+        const uint32_t b = fdiv(am, g.fPin), p = am - b * g.Pin;
+        const uint32_t q = fdiv(p, g.fW), iw = p - q * g.W, id = fdiv(q, g.fH), ih = q - id * g.H;
+        z0 = id + g.pd; z1 = ih + g.ph; z2 = iw + g.pw;
+        abase = (b * g.O + grp * g.Ng) * g.P;
+    } else if (MODE == C3_WGRAD && arow) {
+        const uint32_t c = fdiv(am, g.fT), t = am - c * g.T;
+        const uint32_t q = fdiv(t, g.fKW), kw = t - q * g.KW, kd = fdiv(q, g.fKH), kh = q - kd * g.KH;
+        z0 = kd * g.dd - g.pd; z1 = kh * g.dh - g.ph; z2 = kw * g.dw - g.pw;
+        abase = (grp * g.Cg + c) * g.Pin;
+    }
+
+    // v: the plain copy; v2: DGRAD only, the second tensor (FWD / WGRAD square v as they store it)
+    auto fetch_a = [&](int sm, int32_t r0, float (&v)[16], float (&v2)[16]) {
+        int32_t r = r0 + ah * 16;
+        if (MODE == C3_WGRAD) {
+            // reduction index = output position (b, od, oh, ow) of image set sm, stepped with carries
+            const float *x = a.x + (int64_t)sm * a.x_ss;
+            uint32_t b = 0, od = 0, oh = 0, ow = 0;
+            if (r < rend) {
+                b = fdiv(r, g.fP);
+                const uint32_t p = r - b * g.P, q = fdiv(p, g.fOW);
+                ow = p - q * g.OW; od = fdiv(q, g.fOH); oh = q - od * g.OH;
+            }
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int32_t id = (int32_t)(od * g.sd) + z0, ih = (int32_t)(oh * g.sh) + z1, iw = (int32_t)(ow * g.sw) + z2;
+                const bool ok = arow && r + j < rend && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H &&
+                                (uint32_t)iw < (uint32_t)g.W;
+                v[j] = ok ? x[(int64_t)b * g.C * g.Pin + abase + (id * g.H + ih) * g.W + iw] : 0.f;
+                if (++ow == (uint32_t)g.OW) { ow = 0; if (++oh == (uint32_t)g.OH) { oh = 0; if (++od == (uint32_t)g.OD) { od = 0; ++b; } } }
+            }
+            return;
+        }
+        // reduction index = (channel, kd, kh, kw), stepped with carries
+        const float *src = MODE == C3_FWD ? a.x + (int64_t)s * a.x_ss : a.g1 + (int64_t)s * gset;
+        const float *src2 = MODE == C3_FWD ? nullptr : a.g2 + (int64_t)s * gset;
+        uint32_t c = 0, kd = 0, kh = 0, kw = 0;
+        if (r < rend) {
+            c = fdiv(r, g.fT);
+            const uint32_t t = r - c * g.T, q = fdiv(t, g.fKW);
+            kw = t - q * g.KW; kd = fdiv(q, g.fKH); kh = q - kd * g.KH;
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            bool ok = arow && r + j < rend;
+            int32_t off = 0;
+            if (MODE == C3_FWD) {
+                const int32_t id = z0 + (int32_t)kd * g.dd, ih = z1 + (int32_t)kh * g.dh, iw = z2 + (int32_t)kw * g.dw;
+                ok = ok && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H && (uint32_t)iw < (uint32_t)g.W;
+                off = (int32_t)c * g.Pin + (id * g.H + ih) * g.W + iw;
+            } else {
+                const int32_t nd = z0 - (int32_t)kd * g.dd, nh = z1 - (int32_t)kh * g.dh, nw = z2 - (int32_t)kw * g.dw;
+                ok = ok && nd >= 0 && nh >= 0 && nw >= 0;
+                const uint32_t od = fdiv(ok ? nd : 0, g.fsd), oh = fdiv(ok ? nh : 0, g.fsh), ow = fdiv(ok ? nw : 0, g.fsw);
+                ok = ok && (int32_t)(od * g.sd) == nd && (int32_t)(oh * g.sh) == nh && (int32_t)(ow * g.sw) == nw &&
+                     od < (uint32_t)g.OD && oh < (uint32_t)g.OH && ow < (uint32_t)g.OW;
+                off = (int32_t)c * g.P + (int32_t)((od * g.OH + oh) * g.OW + ow);
+            }
+            v[j] = ok ? src[abase + off] : 0.f;
+            if constexpr (MODE == C3_DGRAD) v2[j] = ok ? src2[abase + off] : 0.f;
+            if (++kw == (uint32_t)g.KW) { kw = 0; if (++kh == (uint32_t)g.KH) { kh = 0; if (++kd == (uint32_t)g.KD) { kd = 0; ++c; } } }
+        }
+    };
+
+    // ---- B loader: reduction offset bk of each k-tile, rows bn + 8 i of the tile
+    const int bk = tid & (C3_BK - 1), bn = tid >> 5;
+    auto fetch_b = [&](int sm, int32_t r0, float (&v)[8], float (&v2)[8]) {
+        const int32_t r = r0 + bk;
+        const bool rok = r < rend;
+        if (MODE == C3_WGRAD) {
+            uint32_t b = 0, p = 0;
+            if (rok) { b = fdiv(r, g.fP); p = r - b * g.P; }
+            const int64_t o0 = (int64_t)sm * gset + ((int64_t)b * g.O + (int64_t)grp * g.Ng) * g.P + p;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int32_t n = n0 + bn + 8 * i;
+                const bool ok = rok && n < N;
+                v[i] = ok ? a.g1[o0 + (int64_t)n * g.P] : 0.f;
+                v2[i] = ok ? a.g2[o0 + (int64_t)n * g.P] : 0.f;
+            }
+            return;
+        }
+        const int64_t wb = (int64_t)grp * g.Ng * g.K;
+        int32_t roff = r;                               // FWD: w[o][r]
+        int32_t nstride = g.K;
+        if (MODE == C3_DGRAD) {                         // r = (o, tap): w[o][c][tap]
+            const uint32_t o = fdiv(rok ? r : 0, g.fT);
+            roff = (int32_t)(o * g.K + (r - o * g.T));
+            nstride = g.T;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int32_t n = n0 + bn + 8 * i;
+            const bool ok = rok && n < N;
+            v[i] = ok ? a.w1[wb + (int64_t)n * nstride + roff] : 0.f;
+            v2[i] = ok ? a.w2[wb + (int64_t)n * nstride + roff] : 0.f;
+        }
+    };
+
+    auto store_tiles = [&](const float (&va)[16], const float (&va2)[16], const float (&vb)[8], const float (&vb2)[8]) {
+        T *pa = As + ar * LDK + ah * 16, *pa2 = pa + C3_BM * LDK;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            st_lds(pa + j, va[j]);
+            st_lds(pa2 + j, MODE == C3_DGRAD ? va2[j] : va[j] * va[j]);      // the square in fp32, then rounded as the plain copy
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            st_lds(Bs + (bn + 8 * i) * LDK + bk, vb[i]);
+            st_lds(Bs + (C3_BN + bn + 8 * i) * LDK + bk, vb2[i]);
+        }
+    };
+
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    f32x4 acc[2][4][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int ntile = rend > rbeg ? (rend - rbeg + C3_BK - 1) / C3_BK : 0;
+    const int nstep = nsum * ntile;
+    float va[16], va2[16], vb[8], vb2[8];          // va2: DGRAD only (dead otherwise)
+    if (nstep > 0) { fetch_a(0, rbeg, va, va2); fetch_b(0, rbeg, vb, vb2); }
+    for (int step = 0; step < nstep; ++step) {
+        __syncthreads();                                // the previous tile's fragment reads are done
+        store_tiles(va, va2, vb, vb2);
+        __syncthreads();
+        if (step + 1 < nstep) {                         // the next tile's loads fly under this tile's MFMAs
+            const int nx = step + 1, sm = nx / ntile;
+            const int32_t r0 = rbeg + (nx - sm * ntile) * C3_BK;
+            fetch_a(sm, r0, va, va2);
+            fetch_b(sm, r0, vb, vb2);
+        }
+        if constexpr (sizeof(T) == 2) {
+            typedef short s16x8 __attribute__((ext_vector_type(8)));
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
+                s16x8 fa[4], fb[2];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    fa[i] = *reinterpret_cast<const s16x8 *>(A + (wm * 64 + i * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    fb[j] = *reinterpret_cast<const s16x8 *>(Bt + (wn * 32 + j * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[h][i][j], 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < C3_BK / 4; ++kk) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
+                    float fa[4], fb[2];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) fa[i] = A[(wm * 64 + i * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) fb[j] = Bt[(wn * 32 + j * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[h][i][j], 0, 0, 0);
+                }
+            }
+        }
+    }
+
+    // ---- epilogue: lane holds C[(lane >> 4) * 4 + q][lane & 15] of each 16 x 16 block
+    if constexpr (MODE == C3_FWD) {
+        // a lane's quad runs along the output position p: with P % 4 == 0 it is one aligned eps quad of one image and channel
+        const bool vec = (g.P & 3) == 0;
+        const uint32_t ed = rng_epoch_dev(a.rng);
+        const int ns = a.shared ? a.S : 1;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
+            if (n >= N) continue;
+            const int32_t o = grp * g.Ng + n;
+            const float mb = a.b1 ? a.b1[o] : 0.f, sb = a.b1 ? a.b2[o] : 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int32_t mq = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
+                if (mq >= M) continue;
+                float r1[4], r2[4], sd[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    r1[q] = acc[0][i][j][q] + mb;
+                    r2[q] = acc[1][i][j][q] + sb;
+                    sd[q] = sqrtf(r2[q] + 1e-16f);
+                }
+                // element (b O + o) P + p of output row m = b P + p
+                auto elem = [&](uint32_t m) {
+                    const uint32_t b = fdiv(m, g.fP);
+                    return (b * (uint32_t)g.O + (uint32_t)o) * (uint32_t)g.P + (m - b * (uint32_t)g.P);
+                };
+                if (vec) {
+                    const uint32_t e0 = elem(mq);          // the quad stays inside one image and channel
+                    if (a.out2) *reinterpret_cast<float4 *>(a.out2 + (int64_t)s * gset + e0) = make_float4(r2[0], r2[1], r2[2], r2[3]);
+                    for (int t = 0; t < ns; ++t) {
+                        const int smp = a.shared ? t : s;
+                        const float4 e4 = eps4(a.rng, ed, e0 >> 2, a.rng.sample0 + (uint32_t)smp);
+                        *reinterpret_cast<float4 *>(a.out + (int64_t)smp * gset + e0) =
+                            make_float4(__builtin_fmaf(sd[0], e4.x, r1[0]), __builtin_fmaf(sd[1], e4.y, r1[1]),
+                                        __builtin_fmaf(sd[2], e4.z, r1[2]), __builtin_fmaf(sd[3], e4.w, r1[3]));
+                    }
+                } else {
+                    uint32_t e[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) e[q] = elem(min(mq + q, M - 1));
+                    const int nq = M - mq < 4 ? M - mq : 4;
+                    if (a.out2)
+                        for (int q = 0; q < nq; ++q) a.out2[(int64_t)s * gset + e[q]] = r2[q];
+                    for (int t = 0; t < ns; ++t) {
+                        const int smp = a.shared ? t : s;
+                        for (int q = 0; q < nq; ++q)
+                            a.out[(int64_t)smp * gset + e[q]] =
+                                __builtin_fmaf(sd[q], eps1(a.rng, ed, (uint64_t)e[q], a.rng.sample0 + (uint32_t)smp), r1[q]);
+                    }
+                }
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
+        if (n >= N) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int32_t m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + q;
+                if (m >= M) continue;
+                if (MODE == C3_DGRAD) {
+                    const uint32_t b = fdiv(m, g.fPin), p = m - b * g.Pin;
+                    const int64_t idx = (int64_t)s * a.x_ss + (b * g.C + grp * g.Cg + n) * g.Pin + p;
+                    a.out[idx] = __builtin_fmaf(2.0f * a.x[idx], acc[1][i][j][q], acc[0][i][j][q]);
+                } else {
+                    // slab [slab][mean | variance][o][k]
+                    const int64_t e = (((int64_t)slab * 2) * g.O + grp * g.Ng + n) * g.K + m;
+                    a.out[e] = acc[0][i][j][q];
+                    a.out[e + (int64_t)g.O * g.K] = acc[1][i][j][q];
+                }
+            }
+    }
+}
+
+// g_mu_w[e] = sum of the mean slabs in slab order, g_rho_w[e] = (sum of the variance slabs) 2 sigma sigmoid(rho_w[e])
+__global__ __launch_bounds__(256) void k_lrt_conv_wsum(const float *__restrict__ slabs, int nslab, const float *__restrict__ rho,
+                                                      float *__restrict__ g_mu, float *__restrict__ g_rho, int64_t n)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    float gm = 0.f, gv = 0.f;
+    for (int k = 0; k < nslab; ++k) {
+        const float *p = slabs + (int64_t)k * 2 * n + e;
+        gm += p[0];
+        gv += p[n];
+    }
+    const float r = rho[e];
+    g_mu[e] = gm;
+    g_rho[e] = gv * (2.0f * sigma_lrt(r) * dsigma_lrt(r));
+}
+
+// g_mu_b[o] = sum over (image, position) of g_m, g_rho_b[o] = (the same sum of g_v) 2 sigma_b sigmoid(rho_b): one workgroup per
+// o, fixed strided partials (images in order) and a fixed tree.  rows = every image of every set.
+__global__ __launch_bounds__(256) void k_lrt_conv_bias_grad(const float *__restrict__ g_m, const float *__restrict__ g_v, int64_t rows,
+                                                           int32_t O, int32_t P, const float *__restrict__ rho_b,
+                                                           float *__restrict__ g_mu_b, float *__restrict__ g_rho_b)
+{
+    __shared__ float rm[256], rv[256];
+    const int o = blockIdx.x;
+    float sm = 0.f, sv = 0.f;
+    for (int64_t b = 0; b < rows; ++b) {
+        const int64_t row = (b * O + o) * P;
+        for (int32_t p = threadIdx.x; p < P; p += 256) { sm += g_m[row + p]; sv += g_v[row + p]; }
+    }
+    rm[threadIdx.x] = sm;
+    rv[threadIdx.x] = sv;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) { rm[threadIdx.x] += rm[threadIdx.x + w]; rv[threadIdx.x] += rv[threadIdx.x + w]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float r = rho_b[o];
+        g_mu_b[o] = rm[0];
+        g_rho_b[o] = rv[0] * (2.0f * sigma_lrt(r) * dsigma_lrt(r));
+    }
+}
+
 static int conv3d_geo(const char *who, const bnn_conv3d_shape_t *sh, int nsamples, int compute, Conv3dGeo &g)
 {
     if (!sh) { set_error("%s: NULL shape", who); return BNN_E_NULL; }
@@ -518,6 +880,16 @@ static int64_t flip_w_std(const Conv3dGeo &g, int compute)
 {
     const int64_t n = (int64_t)g.O * g.K;
     return compute == BNN_COMPUTE_BF16 ? (n + 7) / 8 * 8 : n;
+}
+
+// K11 (LocalReparamConv1d / 2d / 3d): the entries' shared pieces
+static bool mis16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+template <int MODE>
+static void lrt_conv_launch(const Conv3dGeo &g, const LrtConvArgs &a, int compute, dim3 grid, hipStream_t st)
+{
+    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_lrt_conv3d<uint16_t, MODE>), grid, dim3(C3_THREADS), 0, st, g, a);
+    else hipLaunchKernelGGL((k_lrt_conv3d<float, MODE>), grid, dim3(C3_THREADS), 0, st, g, a);
 }
 
 }  // namespace bnn
@@ -693,6 +1065,100 @@ int bnn_conv3d_flipout_backward_weight(const float *x, int64_t x_sample_stride, 
     if ((rc = check_launch(who))) return rc;
     hipLaunchKernelGGL(k_conv3d_flip_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
                        nslab, nsamples, rho, g_mean, g_scale, n);
+    return check_launch(who);
+}
+
+// ---- K11 entries (LocalReparamConv1d / 2d / 3d) ----------------------------------------------------------------------------
+int bnn_conv3d_lrt_forward(const float *x, int64_t x_sample_stride, const float *mu_w, const float *s2_w, const float *mu_b,
+                           const float *s2_b, float *y, float *v_out, const bnn_conv3d_shape_t *shape, int nsamples,
+                           const bnn_rng_t *rng, int compute, void *stream)
+{
+    const char *who = "bnn_conv3d_lrt_forward";
+    Conv3dGeo g;
+    int rc = conv3d_geo(who, shape, nsamples, compute, g);
+    if (rc) return rc;
+    if (!x || !mu_w || !s2_w || !y || (mu_b == nullptr) != (s2_b == nullptr)) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if (!rng) { set_error("%s: NULL rng", who); return BNN_E_NULL; }
+    if (x_sample_stride < 0) { set_error("%s: negative sample stride", who); return BNN_E_SHAPE; }
+    if ((rc = check_rng(rng, nsamples))) { set_error("%s: bad rng", who); return rc; }
+    if (mis4(x) || mis4(mu_w) || mis4(s2_w) || mis4(mu_b) || mis4(s2_b) || mis16(y) || mis16(v_out)) {
+        set_error("%s: misaligned pointer (y and v: 16 bytes)", who);
+        return BNN_E_ALIGN;
+    }
+    LrtConvArgs a{};
+    a.x = x; a.x_ss = x_sample_stride; a.w1 = mu_w; a.w2 = s2_w; a.b1 = mu_b; a.b2 = s2_b; a.out = y; a.out2 = v_out;
+    a.S = nsamples; a.shared = x_sample_stride == 0;
+    a.rng = make_rng(rng);
+    const dim3 grid((unsigned)(((int64_t)g.B * g.P + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN),
+                    (unsigned)((a.shared ? 1 : nsamples) * g.groups));
+    lrt_conv_launch<C3_FWD>(g, a, compute, grid, (hipStream_t)stream);
+    return check_launch(who);
+}
+
+int bnn_conv3d_lrt_backward_input(const float *g_m, const float *g_v, const float *mu_w, const float *s2_w, const float *x,
+                                  float *gx, const bnn_conv3d_shape_t *shape, int nsets, int compute, void *stream)
+{
+    const char *who = "bnn_conv3d_lrt_backward_input";
+    Conv3dGeo g;
+    int rc = conv3d_geo(who, shape, nsets, compute, g);
+    if (rc) return rc;
+    if (!g_m || !g_v || !mu_w || !s2_w || !x || !gx) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if (mis4(g_m) || mis4(g_v) || mis4(mu_w) || mis4(s2_w) || mis4(x) || mis4(gx)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    LrtConvArgs a{};
+    a.g1 = g_m; a.g2 = g_v; a.w1 = mu_w; a.w2 = s2_w; a.x = x; a.x_ss = (int64_t)g.B * g.C * g.Pin; a.out = gx; a.S = nsets;
+    const dim3 grid((unsigned)(((int64_t)g.B * g.Pin + C3_BM - 1) / C3_BM), (unsigned)((g.Cg + C3_BN - 1) / C3_BN),
+                    (unsigned)(nsets * g.groups));
+    lrt_conv_launch<C3_DGRAD>(g, a, compute, grid, (hipStream_t)stream);
+    return check_launch(who);
+}
+
+int64_t bnn_conv3d_lrt_backward_weight_workspace_bytes(const bnn_conv3d_shape_t *shape, int nsets)
+{
+    Conv3dGeo g;
+    if (conv3d_geo("bnn_conv3d_lrt_backward_weight_workspace_bytes", shape, nsets, BNN_COMPUTE_F32, g)) return -1;
+    int nslab, chunk;
+    wgrad_split(g, 1, nslab, chunk);           // one image set: every slab walks all of them
+    return (int64_t)nslab * 2 * g.O * g.K * (int64_t)sizeof(float);
+}
+
+int bnn_conv3d_lrt_backward_weight(const float *x, const float *g_m, const float *g_v, const float *rho_w, float *g_mu_w,
+                                   float *g_rho_w, const float *rho_b, float *g_mu_b, float *g_rho_b,
+                                   const bnn_conv3d_shape_t *shape, int nsets, int compute, void *workspace,
+                                   int64_t workspace_bytes, void *stream)
+{
+    const char *who = "bnn_conv3d_lrt_backward_weight";
+    Conv3dGeo g;
+    int rc = conv3d_geo(who, shape, nsets, compute, g);
+    if (rc) return rc;
+    const bool bias = rho_b || g_mu_b || g_rho_b;
+    if (!x || !g_m || !g_v || !rho_w || !g_mu_w || !g_rho_w || (bias && (!rho_b || !g_mu_b || !g_rho_b))) {
+        set_error("%s: NULL pointer", who);
+        return BNN_E_NULL;
+    }
+    if (mis4(x) || mis4(g_m) || mis4(g_v) || mis4(rho_w) || mis4(g_mu_w) || mis4(g_rho_w) || mis4(rho_b) || mis4(g_mu_b) ||
+        mis4(g_rho_b) || mis4(workspace)) {
+        set_error("%s: misaligned pointer", who);
+        return BNN_E_ALIGN;
+    }
+    int nslab, chunk;
+    wgrad_split(g, 1, nslab, chunk);           // one image set: every slab walks all of them
+    const int64_t n = (int64_t)g.O * g.K;
+    if (!workspace || workspace_bytes < (int64_t)nslab * 2 * n * (int64_t)sizeof(float)) {
+        set_error("%s: workspace of bnn_conv3d_lrt_backward_weight_workspace_bytes bytes needed", who);
+        return BNN_E_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    LrtConvArgs a{};
+    a.x = x; a.x_ss = (int64_t)g.B * g.C * g.Pin; a.g1 = g_m; a.g2 = g_v; a.out = static_cast<float *>(workspace);
+    a.S = nsets; a.nslab = nslab; a.chunk = chunk;
+    const dim3 grid((unsigned)((g.K + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN), (unsigned)(g.groups * nslab));
+    lrt_conv_launch<C3_WGRAD>(g, a, compute, grid, st);
+    if ((rc = check_launch(who))) return rc;
+    hipLaunchKernelGGL(k_lrt_conv_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
+                       nslab, rho_w, g_mu_w, g_rho_w, n);
+    if ((rc = check_launch(who)) || !bias) return rc;
+    hipLaunchKernelGGL(k_lrt_conv_bias_grad, dim3((unsigned)g.O), dim3(256), 0, st, g_m, g_v, (int64_t)nsets * g.B, g.O, g.P, rho_b,
+                       g_mu_b, g_rho_b);
     return check_launch(who);
 }
 

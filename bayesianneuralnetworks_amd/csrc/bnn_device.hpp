@@ -354,6 +354,18 @@ __device__ __forceinline__ float dsoftplus(float rho)
     return rho > 20.0f ? 1.0f : __fdividef(1.0f, 1.0f + __expf(-rho));
 }
 
+// K10 / K11 (local reparameterization): sigma = 1e-10 + softplus(rho) (torch: beta 1, threshold 20) on the accurate log1p / exp
+// -- v = ... sigma^2 is compared at 1e-5 -- and d sigma / d rho
+__device__ __forceinline__ float sigma_lrt(float rho)
+{
+    return 1e-10f + (rho > 20.0f ? rho : log1pf(expf(rho)));
+}
+
+__device__ __forceinline__ float dsigma_lrt(float rho)
+{
+    return rho > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-rho));
+}
+
 // fp32 -> bf16 bits, round-to-nearest-even, NaN kept NaN (v_cvt_pk_bf16_f32).
 __device__ __forceinline__ uint16_t f2bf(float v)
 {

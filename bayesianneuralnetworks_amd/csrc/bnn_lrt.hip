@@ -30,17 +30,6 @@ constexpr int kLrtTile = 64;
 constexpr int kLrtThreads = 256;
 enum { LRT_FWD = 0, LRT_DGRAD = 1, LRT_WGRAD = 2 };
 
-// sigma = 1e-10 + softplus(rho) (torch: beta 1, threshold 20) on the accurate log1p / exp: v = ... sigma^2 is compared at 1e-5
-__device__ __forceinline__ float sigma_lrt(float rho)
-{
-    return 1e-10f + (rho > 20.0f ? rho : log1pf(expf(rho)));
-}
-
-__device__ __forceinline__ float dsigma_lrt(float rho)
-{
-    return rho > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-rho));
-}
-
 struct LrtArgs {
     const void *p1, *p2;        // P planes (p2 NULL: the square of p1); rows index i
     const void *q1, *q2;        // Q planes; rows index j

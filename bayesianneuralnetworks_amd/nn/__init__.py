@@ -5,7 +5,8 @@ from .dense import (BayesianLinear, NormalLinear, MultivariateNormalLinear, Flip
                     LocalReparamLinear)   # (not in __all__: that list is the reference's)
 from .conv import (BayesianConvNd, NormalConvNd, NormalConv1d, NormalConv2d, NormalConv3d,
                    FlipOutNormalConvNd, FlipOutNormalConv1d, FlipOutNormalConv2d, FlipOutNormalConv3d,
-                   MCDropoutConvNd, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d)
+                   MCDropoutConvNd, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d,
+                   LocalReparamConvNd, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)   # (not in __all__ either)
 from .loss import KLDivergence, Entropy, NormalInverseGaussianLoss, NormalInverseGaussianUncertainty
 from ._settings import set_compute, get_compute, fuse_activations, fuse_kl_gradient, keyed_mvn_draws
 

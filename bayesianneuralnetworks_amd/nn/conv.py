@@ -7,6 +7,8 @@ csrc/bnn_conv3d.hip).  The FlipOut variants run on HIP on the device (2-d, 1-d a
 the Flipout tiles of csrc/bnn_conv3d.hip); in a network's
 MC-batched device pass their signs are keyed per MC sample (bnn_conv2d_flipout_forward_mc, bnn_flipout_signs).  The MC-dropout
 variants run their torch conv once and apply the keyed masks of a network's MC-batched device pass in HIP (bnn_mc_dropout).
+LocalReparamConv1d / 2d / 3d (not reference names) sample the Gaussian pre-activation instead of the weights: one operand launch
+and ONE paired-contraction launch for all S samples (bnn_conv3d_lrt_forward; 1-d and 2-d as unit depth / height), HIP backward.
 """
 import torch
 from torch.distributions import Normal
@@ -16,7 +18,8 @@ from . import _settings
 from ..utils import _single, _pair, _triple
 from .container import BayesianModule
 from .core import WeightNormal
-from .dense import _NormalSampling, _init_normal_posterior, _mc_dropout_plan, _mc_dropout_key, _flipout_plan, _flipout_mc_key
+from .dense import (_NormalSampling, _init_normal_posterior, _mc_dropout_plan, _mc_dropout_key, _flipout_plan, _flipout_mc_key,
+                    _lrt_noise_plan)
 
 
 class BayesianConvNd(BayesianModule):
@@ -151,6 +154,101 @@ class NormalConv3d(NormalConvNd):
         else:
             y = ops.conv3d_plain(x6, *self.sampled, S, shared, *geo, self._compute_mode())
         return y.reshape(S * per, *y.shape[2:])
+
+
+class LocalReparamConvNd(_NormalSampling, BayesianConvNd):
+    """The local-reparameterization estimator of NormalConvNd's posterior (Kingma, Salimans, Welling 2015; the conv variant of
+    LocalReparamLinear).  With independent Gaussian w and b every output element of the convolution is Gaussian, so the layer
+    samples IT instead of the weights:
+
+        m   = convNd(x,   mu_w,      mu_b,      stride, padding, dilation, groups)
+        v   = convNd(x^2, sigma_w^2, sigma_b^2, stride, padding, dilation, groups)        sigma = 1e-10 + softplus(rho)
+        y_s = m + sqrt(v + 1e-16) eps_s,        eps_s ~ N(0, 1), one per output element and MC sample
+
+    What the estimator is and is not: per output element y_s has EXACTLY the marginal mean and variance of weight sampling.  The
+    weights of a convolution are shared by the positions of one image, so weight sampling correlates the positions of an output
+    map and this layer does not -- the usual LRT-for-conv approximation.  It is a different estimator from Flipout too, which
+    perturbs the weights per example.
+
+    Parameters, initialisation and state_dict keys are NormalConvNd's (weight.mean, weight.scale, bias.mean, bias.scale): a
+    checkpoint of one loads into the other, and KLDivergence, .kl_divergence(), traverse, apply_wb and PruneNormal see an ordinary
+    Gaussian conv layer.  The network draw plan and nn.fuse_activations select by exact type and pass this layer by.
+
+    Device input: bnn_lrt_prepare + bnn_conv3d_lrt_forward (csrc/bnn_conv3d.hip, k_lrt_conv3d; both compute modes; 1-d and 2-d
+    layers on unit depth / height), fp32 output, HIP backward, no torch fallback (BnnHipError with the kernel's reason).  In a
+    BayesianNetworkModule's MC-batched pass a layer that sees the shared batch (B rows) contracts m and v ONCE and returns S B
+    rows; one that sees S B rows contracts per sample.  layer.noise_key is the DrawKey of the last device call, on a stream of
+    the layer's own: element (b O + o) P + p of sample s is that eps of the key's sample sample0 + s (include/bnn_hip.h, LRT-conv
+    noise contract).  sample=False reuses it.  CPU tensors: the expression above in torch with torch.randn_like."""
+
+    _op = None
+    _nd = 0
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, prior):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, False, groups, bias, WeightNormal, prior)
+        from .._rng import new_stream_id
+        self._noise_stream = new_stream_id()        # the layer's own eps stream, beside those of its two posterior tensors
+        self.noise_key = None                       # DrawKey of the last device call
+        self._noise_shape = None                    # one sample's INPUT shape (B, C, *spatial) of that call (it fixes the output's)
+        self._cpu_eps = None
+
+    def reset_parameters(self):
+        _init_normal_posterior(self)
+        self.sample()
+
+    def forward(self, x, sample=True):
+        conv = type(self)._op
+        geo = (self.stride, self.padding, self.dilation, self.groups)
+        if not x.is_cuda:
+            has_b = self.bias is not None
+            m = conv(x, self.weight.mean, self.bias.mean if has_b else None, *geo)
+            v = conv(x * x, self.weight.variance, self.bias.variance if has_b else None, *geo)
+            if sample:
+                self._cpu_eps = torch.randn_like(m)
+            elif self._cpu_eps is None or self._cpu_eps.shape != m.shape:
+                raise RuntimeError("sample=False: no noise of shape %s was drawn by an earlier call" % (tuple(m.shape),))
+            return m + torch.sqrt(v + 1e-16) * self._cpu_eps
+        if x.dim() == self._nd + 1:
+            return self.forward(x.unsqueeze(0), sample).squeeze(0)
+        from .._rng import DrawKey, default_generator, generator_for
+        S, s0, shared, per = _lrt_noise_plan(x)
+        mode = self._compute_mode()
+        xs = x if shared else x.reshape(S, per, *x.shape[1:])
+        if sample:
+            self.noise_key = DrawKey(default_generator.seed, self._noise_stream, s0, S, default_generator.next_epoch(),
+                                     gen=generator_for(mode))
+            self._noise_shape = (per,) + tuple(x.shape[1:])
+        key = self.noise_key
+        shape = (per,) + tuple(x.shape[1:])
+        if key is None or self._noise_shape != shape:
+            raise RuntimeError("sample=False: %s noise recorded, this call has %s per sample"
+                               % ("no" if key is None else "an input of %s gave the" % (self._noise_shape,), shape))
+        if key.nsamples != S:
+            if S != 1:
+                raise RuntimeError("sample=False: the recorded noise has %d MC samples, this call needs %d" % (key.nsamples, S))
+            key = key.last_sample()
+        y = ops.convNd_lrt(xs, self.weight.mean, self.weight.scale,
+                           self.bias.mean if self.bias is not None else None,
+                           self.bias.scale if self.bias is not None else None, key, shared, *geo, mode)
+        return y.reshape(S * per, *y.shape[2:])
+
+
+def _local_reparam(name, ntuple, op, nd):
+    class _LocalReparam(LocalReparamConvNd):
+        _op = staticmethod(op)
+        _nd = nd
+
+        def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
+                     groups=1, bias=True, prior=Normal(0, .1)):
+            super().__init__(in_channels, out_channels, ntuple(kernel_size), ntuple(stride), ntuple(padding),
+                             ntuple(dilation), groups, bias, prior)
+    _LocalReparam.__name__ = _LocalReparam.__qualname__ = name
+    return _LocalReparam
+
+
+LocalReparamConv1d = _local_reparam('LocalReparamConv1d', _single, torch.nn.functional.conv1d, 1)
+LocalReparamConv2d = _local_reparam('LocalReparamConv2d', _pair, torch.nn.functional.conv2d, 2)
+LocalReparamConv3d = _local_reparam('LocalReparamConv3d', _triple, torch.nn.functional.conv3d, 3)
 
 
 def _flipout_conv2d_device(layer, x, R, S, view, stride, padding, dilation):

@@ -268,6 +268,20 @@ class NormalLinear(_NormalSampling, BayesianLinear):
         return y.reshape(S * per, *lead, y.shape[-1])
 
 
+def _lrt_noise_plan(x):
+    """-> (S, sample0, shared_x, rows of x per sample) for the current MC context (the row convention of _mc_plan): what the
+    local-reparameterization layers (LocalReparamLinear, LocalReparamConvNd) key their noise on."""
+    ctx = _mc.current()
+    if ctx is None or ctx.samples == 1:
+        return 1, (ctx.sample0 if ctx else 0), True, x.shape[0]
+    if x.shape[0] == ctx.base_batch:
+        return ctx.samples, ctx.sample0, True, x.shape[0]
+    if x.shape[0] == ctx.base_batch * ctx.samples:
+        return ctx.samples, ctx.sample0, False, ctx.base_batch
+    raise RuntimeError("mc_batched: layer input has %d rows, expected %d or %d"
+                       % (x.shape[0], ctx.base_batch, ctx.base_batch * ctx.samples))
+
+
 class LocalReparamLinear(_NormalSampling, BayesianLinear):
     """The local-reparameterization estimator of NormalLinear's posterior (Kingma, Salimans, Welling 2015): with independent
     Gaussian w and b the pre-activation is Gaussian per output element, so the layer samples IT instead of the weights:
@@ -288,7 +302,8 @@ class LocalReparamLinear(_NormalSampling, BayesianLinear):
     torch.randn_like.
 
     Out of scope: nn.fuse_activations / fuse_head and the network draw plan (there is no tensor to pre-draw; both select
-    NormalLinear by exact type and pass this layer by), the three-plane (x3) hand-over, a conv variant."""
+    NormalLinear by exact type and pass this layer by), the three-plane (x3) hand-over.  The conv variant is
+    nn.LocalReparamConv1d / 2d / 3d (nn/conv.py)."""
 
     def __init__(self, in_features, out_features, bias=True, prior=Normal(0, .1)):
         super().__init__(in_features, out_features, bias, WeightNormal, prior)
@@ -303,16 +318,7 @@ class LocalReparamLinear(_NormalSampling, BayesianLinear):
         self.sample()
 
     def _noise_plan(self, x):
-        """-> (S, sample0, shared_x, rows of x per sample) for the current MC context (the row convention of _mc_plan)."""
-        ctx = _mc.current()
-        if ctx is None or ctx.samples == 1:
-            return 1, (ctx.sample0 if ctx else 0), True, x.shape[0]
-        if x.shape[0] == ctx.base_batch:
-            return ctx.samples, ctx.sample0, True, x.shape[0]
-        if x.shape[0] == ctx.base_batch * ctx.samples:
-            return ctx.samples, ctx.sample0, False, ctx.base_batch
-        raise RuntimeError("mc_batched: layer input has %d rows, expected %d or %d"
-                           % (x.shape[0], ctx.base_batch, ctx.base_batch * ctx.samples))
+        return _lrt_noise_plan(x)
 
     def forward(self, x, sample=True):
         if not x.is_cuda:

@@ -1866,6 +1866,125 @@ def conv3d_plain(x, w, b, nsamples, shared_x, stride, padding, dilation, groups,
                          _compute_code(compute))
 
 
+# --------------------------------------------------------------------------- K11: local reparameterization, convolutions
+def _lrt_conv_views(x_shape, w_shape, stride, padding, dilation):
+    """A 1-d / 2-d / 3-d conv as the 3-d one on unit depth / height: -> (image shape (C, D, H, W), weight shape
+    (O, C / groups, KD, KH, KW), stride, padding, dilation) with x_shape = (..., C, *spatial)."""
+    nd = len(w_shape) - 2
+    if nd not in (1, 2, 3):
+        raise BnnHipError("conv_lrt: weight must be (O, C / groups, *kernel) with 1, 2 or 3 kernel axes, got %s" % (tuple(w_shape),))
+    if len(stride) != nd or len(padding) != nd or len(dilation) != nd:
+        raise BnnHipError("conv_lrt: stride, padding and dilation must have %d entries" % nd)
+    one = (1,) * (3 - nd)
+    img = (int(x_shape[-nd - 1]),) + one + tuple(int(v) for v in x_shape[-nd:])
+    w5 = tuple(int(v) for v in w_shape[:2]) + one + tuple(int(v) for v in w_shape[2:])
+    return (img, w5, one + tuple(int(v) for v in stride), (0,) * (3 - nd) + tuple(int(v) for v in padding),
+            one + tuple(int(v) for v in dilation))
+
+
+def conv_lrt_eligible(x, mu_w, nsamples, shared_x, stride, padding, dilation, groups):
+    """None when the K11 entries take the call, else the reason they refuse (layout, K7's index ranges).  x: (B, C, *spatial) for
+    a shared input or (S, B, C, *spatial); there is no torch fallback on device tensors -- convNd_lrt raises with this reason."""
+    nd = mu_w.dim() - 2
+    if nd not in (1, 2, 3):
+        return "weight has %d kernel axes (1, 2 or 3)" % nd
+    if x.dim() != nd + (2 if shared_x else 3) or (not shared_x and x.shape[0] != nsamples):
+        return "input must be (B, C, ...) shared by the samples or (S = %d, B, C, ...) with %d spatial axes, got %s" % (
+            nsamples, nd, tuple(x.shape))
+    if x.dtype != torch.float32:
+        return "input dtype %s (float32)" % x.dtype
+    if x.data_ptr() % 4:
+        return "input pointer is not aligned to its element size"
+    if nsamples < 1 or nsamples > 0xFFFF:
+        return "%d MC samples (1 .. 65535)" % nsamples
+    try:
+        img, w5, st, pd, dl = _lrt_conv_views(x.shape, mu_w.shape, stride, padding, dilation)
+        sh, _ = _conv3d_shape((int(x.shape[-nd - 2]),) + img, w5, st, pd, dl, groups)
+    except BnnHipError as e:
+        return str(e)
+    lib = _lib.load()
+    if lib.bnn_conv3d_lrt_backward_weight_workspace_bytes(ctypes.byref(sh), int(nsamples)) < 0:
+        return lib.bnn_last_error().decode()
+    return None
+
+
+class _LrtConv(torch.autograd.Function):
+    """y_s = m + sqrt(v + 1e-16) eps_s, m = convNd(x, mu_w, mu_b), v = convNd(x^2, sigma_w^2, sigma_b^2) (LocalReparamConvNd): one
+    operand launch + one paired-contraction launch for all S samples (csrc/bnn_conv3d.hip, k_lrt_conv3d).  Backward: eps re-created
+    from the key in one elementwise launch (g_m, g_v from the saved v; K10's, with N = O P), the paired input-gradient launch, the
+    paired weight-gradient slabs + their reduce, the bias sums -- 5 launches with a bias, 4 without, no torch conv."""
+
+    @staticmethod
+    def forward(ctx, x, mu_w, rho_w, mu_b, rho_b, key, shared_x, conv_args, compute, track):
+        for t, n in ((x, "x"), (mu_w, "weight.mean"), (rho_w, "weight.scale")):
+            require_cuda_f32(t, n)
+        if mu_b is not None:
+            require_cuda_f32(mu_b, "bias.mean")
+            require_cuda_f32(rho_b, "bias.scale")
+        stride, padding, dilation, groups = conv_args
+        S = key.nsamples
+        why = conv_lrt_eligible(x, mu_w, S, shared_x, stride, padding, dilation, groups)
+        if why is not None:
+            raise BnnHipError("conv_lrt: " + why)
+        nd = mu_w.dim() - 2
+        img, w5, st, pd, dl = _lrt_conv_views(x.shape, mu_w.shape, stride, padding, dilation)
+        B = int(x.shape[-nd - 2])
+        sh, out3 = _conv3d_shape((B,) + img, w5, st, pd, dl, groups)
+        out_sp = out3[3 - nd:]
+        dev = x.device
+        needs_grad = track and any(ctx.needs_input_grad[:5])
+        s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
+        y = torch.empty((S, B, sh.O) + out_sp, dtype=torch.float32, device=dev)
+        v = torch.empty(((B, sh.O) if shared_x else (S, B, sh.O)) + out_sp, dtype=torch.float32, device=dev) if needs_grad else None
+        r = _rng_struct(key, dev)
+        check(_lib.load().bnn_conv3d_lrt_forward(ptr(x), 0 if shared_x else x[0].numel(), ptr(mu_w), ptr(s2_w), ptr(mu_b), ptr(s2_b),
+                                                 ptr(y), ptr(v), ctypes.byref(sh), S, ctypes.byref(r), compute, stream_ptr(dev)),
+              "bnn_conv3d_lrt_forward")
+        if needs_grad:
+            ctx.save_for_backward(x, mu_w, rho_w, rho_b if mu_b is not None else None, s2_w, v)
+        ctx.key, ctx.shared_x, ctx.compute, ctx.sh = key, shared_x, compute, sh
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, mu_w, rho_w, rho_b, s2_w, v = ctx.saved_tensors
+        S, compute, shared, sh = ctx.key.nsamples, ctx.compute, ctx.shared_x, ctx.sh
+        dev = gy.device
+        lib, st = _lib.load(), stream_ptr(dev)
+        gy = gy.contiguous().float()
+        nsets = 1 if shared else S
+        g_m, g_v = torch.empty_like(v), torch.empty_like(v)
+        r = _rng_struct(ctx.key, dev)
+        check(lib.bnn_lrt_backward_epilogue(ptr(gy), ptr(v), ptr(g_m), ptr(g_v), sh.B, v[0].numel() if shared else v[0][0].numel(),
+                                            S, 1 if shared else 0, ctypes.byref(r), 0, st), "bnn_lrt_backward_epilogue")
+        gx = g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            check(lib.bnn_conv3d_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(mu_w), ptr(s2_w), ptr(x), ptr(gx), ctypes.byref(sh),
+                                                    nsets, compute, st), "bnn_conv3d_lrt_backward_input")
+        need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or need_b:
+            g_mu_w, g_rho_w = torch.empty_like(mu_w), torch.empty_like(rho_w)
+            if need_b:
+                g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
+            nb = lib.bnn_conv3d_lrt_backward_weight_workspace_bytes(ctypes.byref(sh), nsets)
+            ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)          # this call's own slabs
+            check(lib.bnn_conv3d_lrt_backward_weight(ptr(x), ptr(g_m), ptr(g_v), ptr(rho_w), ptr(g_mu_w), ptr(g_rho_w),
+                                                     ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), ctypes.byref(sh),
+                                                     nsets, compute, ptr(ws), nb, st), "bnn_conv3d_lrt_backward_weight")
+        return gx, g_mu_w, g_rho_w, g_mu_b, g_rho_b, None, None, None, None, None
+
+
+def convNd_lrt(x, mu_w, rho_w, mu_b, rho_b, key, shared_x, stride, padding, dilation, groups=1, compute="f32"):
+    """LocalReparamConv{1,2,3}d on the device (the dimension is the weight's): x (B, C, *spatial) shared by the key's S samples
+    (shared_x) or (S, B, C, *spatial) -> (S, B, O, *out_spatial) fp32; sample s uses eps[(b O + o) P + p] of the key's sample
+    sample0 + s.  Raises BnnHipError (with conv_lrt_eligible's reason) for a call the kernel refuses: no torch fallback."""
+    return _LrtConv.apply(x.contiguous(), mu_w.contiguous(), rho_w.contiguous(),
+                          None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
+                          key, bool(shared_x), (tuple(stride), tuple(padding), tuple(dilation), int(groups)),
+                          _compute_code(compute), torch.is_grad_enabled())
+
+
 # --------------------------------------------------------------------------- Flipout conv3d (FlipOutNormalConv3d on the device)
 def _flip3d_operands(mean, scale, compute):
     """[O K mean | O K stddev] (OIDHW order, stddev = 1e-10 + softplus(scale)) in ONE bnn_draw_multi launch (kinds 1 / 2, one flat

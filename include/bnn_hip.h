@@ -85,6 +85,18 @@
  *   (s, b, n): not on the tile shape, not on whether the input is shared by the samples or given per sample, not on which GPU
  *   of a sharded run computes the sample.  The backward re-creates it from the key; it is never stored.  B N < 2^32 per sample.
  *   CPU twin: oracle.eps_fill on the key (tests/test_lrt_device.py).
+ *
+ * LRT-conv noise contract (the local-reparameterization conv layers, K11: the forward entry of the bnn_conv3d_lrt_ family and
+ * the backward epilogue of K10, which re-creates the noise)
+ *   The noise of LocalReparamConv{1,2,3}d is one eps per OUTPUT element and MC sample, on the same eps stream and the same
+ *   device function (eps4 / eps1) as the LRT-noise contract above, one stream per layer.  Element e of ONE sample's
+ *   (B, O, *out_spatial) output, in that contiguous order -- e = (b O + o) P + p, P = the number of output positions, p the flat
+ *   position -- takes eps[e] of sample sample0 + s of the key.  The value depends only on the key and (s, b, o, p): not on the
+ *   tile, not on whether the input is shared by the samples or given per sample, not on groups, not on which GPU of a sharded
+ *   run computes the sample.  It is never stored: the backward re-creates it from the key.  B O P < 2^32 per sample (the conv
+ *   entries refuse a per-sample tensor of 2^31 elements already).  A lane's four accumulator registers run along p; when P is a
+ *   multiple of 4 they are one aligned eps quad (one Philox block per four outputs), otherwise every output takes its own block.
+ *   CPU twin: oracle.eps_fill on the key (tests/test_lrt_conv_device.py).
  */
 #ifndef BNN_HIP_H
 #define BNN_HIP_H
@@ -858,6 +870,48 @@ int bnn_lrt_backward_input(const float *g_m, const float *g_v, const float *mu_w
 int bnn_lrt_backward_weight(const void *x, int64_t ldx, const float *g_m, const float *g_v, const float *rho_w, float *g_mu_w,
                             float *g_rho_w, const float *rho_b, float *g_mu_b, float *g_rho_b, int64_t M, int64_t N, int64_t K,
                             int compute, int flags, void *stream);
+
+/* ---- K11: local reparameterization for convolutions (LocalReparamConv1d / 2d / 3d, bayesianneuralnetworks_amd/nn/conv.py).
+ * Like K10 the layer has no call site in the reference: it is the other estimator of NormalConvNd's posterior
+ * (pytorch_bayesian/nn/conv.py:43-142).  Per output element the pre-activation of a conv with independent Gaussian weights is
+ * Gaussian with
+ *     m = convNd(x,   mu_w,      mu_b)
+ *     v = convNd(x^2, sigma_w^2, sigma_b^2)
+ *     y_s = m + sqrt(v + 1e-16) eps_s          eps_s ~ N(0, 1): the LRT-conv noise contract above
+ * (the noise of different output positions is independent, which weight sampling's is not: the usual LRT-for-conv
+ * approximation).  One paired-contraction implicit-GEMM tile on K7's skeleton (128 x 64 x 32, im2col in the loader's address
+ * arithmetic, no panel): both contractions from one pass over the gathers, the second operand copy squared in fp32 before any
+ * rounding.  sigma_w^2 / sigma_b^2 are bnn_lrt_prepare's fp32 values.  compute: BNN_COMPUTE_F32 = v_mfma_f32_16x16x4_f32;
+ * BNN_COMPUTE_BF16 = every operand (x, x^2, g_m, g_v, mu_w, the fp32 sigma_w^2) rounded to bf16 (RNE) as it is written to LDS,
+ * v_mfma_f32_16x16x32_bf16, fp32 accumulate.  Fixed summation orders, no atomics: identical calls give identical bits, and a
+ * shared input gives the bits of the same images given per sample.  1-d and 2-d layers: unit depth / height.
+ * Errors (nothing launched): K7's -- BNN_E_NULL, BNN_E_SHAPE (extents, groups not dividing the channels), BNN_E_DTYPE (compute),
+ * BNN_E_RANGE (a per-sample tensor of 2^31 elements or more, so B O P < 2^32; nsamples * groups > 65535; bad rng), BNN_E_ALIGN
+ * (4 bytes; 16 bytes for y and v_out), BNN_E_UNSUPPORTED (workspace too small).
+ *
+ * Forward, ONE launch for all nsamples samples.  x: fp32 NCDHW, x_sample_stride == 0: (B, C, D, H, W) serves every sample -- m
+ * and v are contracted ONCE and the workgroup loops over the samples in its epilogue only; otherwise sample s starts at
+ * x + s * x_sample_stride and the sample is a grid dimension.  mu_w, s2_w: (O, C / groups, KD, KH, KW) fp32; mu_b, s2_b: (O) fp32,
+ * both or neither.  y: (nsamples, B, O, OD, OH, OW) fp32.  v_out (may be NULL): v, (B, O, OD, OH, OW) for a shared x, one per
+ * sample otherwise -- what the backward epilogue of K10 reads with N = O P. */
+int bnn_conv3d_lrt_forward(const float *x, int64_t x_sample_stride, const float *mu_w, const float *s2_w, const float *mu_b,
+                           const float *s2_b, float *y, float *v_out, const bnn_conv3d_shape_t *shape, int nsamples,
+                           const bnn_rng_t *rng, int compute, void *stream);
+/* g_x = convNd^T(g_m, mu_w) + 2 x (.) convNd^T(g_v, sigma_w^2): both transposed contractions in one tile, the product with 2 x
+ * in the epilogue.  nsets image sets, each of the shape's B images: 1 for a shared input (g_m, g_v are sums over the samples),
+ * the sample count for a per-sample input.  g_m, g_v: (nsets, B, O, OD, OH, OW); x, gx: (nsets, B, C, D, H, W), contiguous. */
+int bnn_conv3d_lrt_backward_input(const float *g_m, const float *g_v, const float *mu_w, const float *s2_w, const float *x,
+                                  float *gx, const bnn_conv3d_shape_t *shape, int nsets, int compute, void *stream);
+/* g_mu_w = sum over (set, b, position) of gather(x) g_m and g(sigma_w^2) likewise of gather(x)^2 g_v, in one tile; the
+ * reduction over the B P positions of a set is split into slabs (caller's workspace, a per-call buffer), every slab adds its
+ * share of every set in set order, and a second launch adds the slabs in slab order and writes g_mu_w and
+ * g_rho_w = g(sigma_w^2) 2 sigma_w sigmoid(rho_w).  Bias (rho_b, g_mu_b, g_rho_b all given, or all NULL), a third launch:
+ * g_mu_b[o] = sum g_m, g_rho_b[o] = (sum g_v) 2 sigma_b sigmoid(rho_b), in a fixed order. */
+int64_t bnn_conv3d_lrt_backward_weight_workspace_bytes(const bnn_conv3d_shape_t *shape, int nsets);
+int bnn_conv3d_lrt_backward_weight(const float *x, const float *g_m, const float *g_v, const float *rho_w, float *g_mu_w,
+                                   float *g_rho_w, const float *rho_b, float *g_mu_b, float *g_rho_b,
+                                   const bnn_conv3d_shape_t *shape, int nsets, int compute, void *workspace,
+                                   int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
