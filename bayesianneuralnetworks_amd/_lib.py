@@ -20,6 +20,7 @@ FLAG_X_BF16 = 2
 E_ALIGN, E_UNSUPPORTED, E_DEVICE = -4, -6, -7     # BNN_E_ALIGN, BNN_E_UNSUPPORTED, BNN_E_DEVICE (include/bnn_hip.h)
 FLAG_Y_BF16 = 4
 UNC_LOGITS, UNC_PROBS = 0, 1                     # BNN_UNC_* (bnn_mc_uncertainty)
+REG_VALUES, REG_MEAN_LOGVAR, REG_MEAN_VAR = 0, 1, 2     # BNN_REG_* (bnn_mc_regression)
 
 
 class BnnHipError(RuntimeError):
@@ -195,6 +196,10 @@ SIGNATURES = {
                              _p, _p, _p]),
     "bnn_mc_uncertainty": (_int, [_p, _i64, _int, _int, _i64, _int, _int, _p, _p, _p, _p, _p, ctypes.c_uint32,
                                   ctypes.POINTER(KlTensor), _int, _f, _p, _p, _p]),
+    "bnn_mc_regression": (_int, [_p, _i64, _int, _int, _i64, _int, _int, _p, _p, _p, _p, _p, ctypes.c_uint32,
+                                 ctypes.POINTER(KlTensor), _int, _f, _p, _p, _p]),
+    "bnn_gaussian_nll_workspace_bytes": (_i64, [_i64, _i64, _int]),
+    "bnn_gaussian_nll": (_int, [_p, _int, _i64, _int, _p, _p, _p, _p, _p]),
     "bnn_lrt_prepare": (_int, [_p, _p, _i64, _p, _p, _i64, _p]),
     "bnn_lrt_forward": (_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _rngp, _int, _int, _p]),
     "bnn_lrt_backward_epilogue": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _rngp, _int, _p]),

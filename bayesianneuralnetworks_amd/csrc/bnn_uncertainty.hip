@@ -15,77 +15,11 @@
 //           4 (lane + k TPR) (16-B loads); per sample one max and one (sum e, sum e t) reduction (__shfl_xor, + LDS across
 //           the four waves), the next sample's loads in flight meanwhile.
 // The optional tails are those of k_mc_sum_kl: block 0 bumps the device epoch, one extra workgroup runs KL's second pass.
-#include "bnn_device.hpp"
-#include "bnn_kl_body.hpp"
-#include "bnn_mc.hpp"
+#include "bnn_mc_parts.hpp"
 
 namespace bnn {
 
-constexpr int kUncThreads = 256;
-constexpr int kUncNarrow = 16;              // classes a lane of the narrow split holds
-constexpr int kUncMaxBlocks = 1 << 20;      // work workgroups per launch (grid-stride above)
-constexpr float kLog2e = 1.44269504088896341f;
 constexpr double kLn2 = 0.693147180559945309417;
-static_assert(kUncThreads == kKlThreads, "the KL tail runs as one workgroup of this launch");
-
-struct UncArgs {
-    const float *y;
-    int64_t stride;         // elements between addends
-    int64_t part_stride;    // nsamples * stride: between the parts of one sample
-    int64_t rows;
-    int nparts, nsamples, classes;
-    int vec;                // wide split: 16-B loads / stores are aligned (classes % 4 == 0, y / stride / mean aligned)
-    float *mean, *total, *aleatoric, *epistemic;
-};
-
-// Class of value slot i of a lane: 4-class chunks, chunk k at 4 * (lead + k * STEP).  Narrow: lead 0, STEP 1 -> slot i = class i.
-template <int STEP>
-__device__ __forceinline__ int unc_col(int lead, int i) { return 4 * (lead + (i >> 2) * STEP) + (i & 3); }
-
-// a[i] = 0.f + q[p0 ps + c_i] + ... + q[(p1 - 1) ps + c_i] in part order, PB parts' loads in flight.  Padding with 0.f is exact
-// (a sum that starts at +0 is never -0), as in mc_sum_split_body.
-template <int NV, int STEP, int PB>
-__device__ __forceinline__ void seq_parts(const float *__restrict__ q, int64_t ps, int p0, int p1, int lead, int C, float (&a)[NV])
-{
-#pragma unroll
-    for (int i = 0; i < NV; ++i) a[i] = 0.f;
-    for (int p = p0; p < p1; p += PB) {
-        float v[PB][NV];
-#pragma unroll
-        for (int j = 0; j < PB; ++j)
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int c = unc_col<STEP>(lead, i);
-                v[j][i] = (p + j < p1 && c < C) ? q[(int64_t)(p + j) * ps + c] : 0.f;
-            }
-#pragma unroll
-        for (int j = 0; j < PB; ++j)
-#pragma unroll
-            for (int i = 0; i < NV; ++i) a[i] += v[j][i];
-    }
-}
-
-// The logits of one sample from a fused head's partials (q = y + s * stride + row * classes): bnn_mc_sum's order over `parts`
-// addends -- sequential up to kMcSplitAbove, else four sequential quarters added left to right -- so the values are the bits
-// HeadPartials.logits() stores.
-template <int NV, int STEP, int PB>
-__device__ __forceinline__ void parts_sum(const UncArgs &A, const float *__restrict__ q, int lead, float (&z)[NV])
-{
-    if (A.nparts <= kMcSplitAbove) {
-        seq_parts<NV, STEP, PB>(q, A.part_stride, 0, A.nparts, lead, A.classes, z);
-        return;
-    }
-    const int per = (A.nparts + 3) >> 2;
-#pragma unroll 1
-    for (int w = 0; w < 4; ++w) {
-        const int s0 = w * per < A.nparts ? w * per : A.nparts;
-        const int s1 = s0 + per < A.nparts ? s0 + per : A.nparts;
-        float g[NV];
-        seq_parts<NV, STEP, PB>(q, A.part_stride, s0, s1, lead, A.classes, g);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) z[i] = w == 0 ? g[i] : z[i] + g[i];
-    }
-}
 
 // Entropy of the per-row mean in bits, one class: -m log2 m (LOGITS, 0 log 0 = 0) / -m log2(m + 1e-10) (PROBS, the
 // reference's Entropy convention).  The log is v_log_f32 on the fp32-rounded mean; a term below 2^-100 is dropped (<= 1e-28).
@@ -95,18 +29,6 @@ __device__ __forceinline__ double total_term_bits(double m)
     const float mf = (float)m;
     if constexpr (KIND == BNN_UNC_LOGITS) return mf > 0x1p-100f ? -m * (double)__builtin_amdgcn_logf(mf) : 0.0;
     return -m * (double)__builtin_amdgcn_logf(mf + 1e-10f);
-}
-
-// The kernel's two tails; true = this workgroup ran the KL pass and is done.
-__device__ __forceinline__ bool unc_tails(int nwork, uint32_t *advance_epoch, uint32_t advance_inc, const KlFinal &F,
-                                          const double *__restrict__ partials, float *__restrict__ kl_out)
-{
-    if ((int)blockIdx.x == nwork) {
-        kl_final_body(F, partials, kl_out);
-        return true;
-    }
-    if (advance_epoch && blockIdx.x == 0 && threadIdx.x == 0) advance_epoch[0] += advance_inc;
-    return false;
 }
 
 // ---------------------------------------------------------------------------------------------- narrow: classes <= 16
@@ -135,7 +57,7 @@ __global__ __launch_bounds__(kUncThreads) void k_unc_narrow(UncArgs A, int glog,
             float z[NV], zn[NV];
             auto load = [&](int s, float (&v)[NV]) {
                 if constexpr (FUSED) {
-                    parts_sum<NV, 1, 8>(A, row + (int64_t)s * A.stride, 0, v);
+                    parts_sum<NV, 1, 8>(A.nparts, A.part_stride, A.classes, row + (int64_t)s * A.stride, 0, v);
                 } else {
 #pragma unroll
                     for (int i = 0; i < NV; ++i) v[i] = i < C ? row[(int64_t)s * A.stride + i] : 0.f;
@@ -263,7 +185,7 @@ __global__ __launch_bounds__(kUncThreads) void k_unc_wide(UncArgs A, int has_kl,
         auto load = [&](int s, float (&v)[NV]) {
             const float *q = row + (int64_t)s * A.stride;
             if constexpr (FUSED) {
-                parts_sum<NV, TPR, (NV >= 16 ? 2 : 32 / NV)>(A, q, t, v);
+                parts_sum<NV, TPR, (NV >= 16 ? 2 : 32 / NV)>(A.nparts, A.part_stride, A.classes, q, t, v);
             } else if (A.vec) {
 #pragma unroll
                 for (int k = 0; k < NCH; ++k) {

@@ -8,6 +8,7 @@ from .conv import (BayesianConvNd, NormalConvNd, NormalConv1d, NormalConv2d, Nor
                    MCDropoutConvNd, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d,
                    LocalReparamConvNd, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)   # (not in __all__ either)
 from .loss import KLDivergence, Entropy, NormalInverseGaussianLoss, NormalInverseGaussianUncertainty
+from .loss import GaussianNLL   # (not in __all__ either)
 from ._settings import set_compute, get_compute, fuse_activations, fuse_kl_gradient, keyed_mvn_draws
 
 # the names pytorch_bayesian/nn/__init__.py:7-35 exports

@@ -118,6 +118,31 @@ class BayesianNetworkModule(Module):
             y = self.forward_stacked(x, samples, sample0, **kwargs)
         return ops.mc_uncertainty(y, inputs, advance=advance, kl=kl)
 
+    def predictive_regression(self, x, samples=None, sample0=0, *, outputs, advance=None, kl=None, **kwargs):
+        """Predictive mean and variance decomposition of `samples` MC draws of a real-valued `_forward(x)` ->
+        ops.PredictiveRegression(mean, total, aleatoric, epistemic), each (*rows, D): the moments of the equal-weight mixture of
+        the per-sample predictives -- aleatoric = mean of the per-sample variances, epistemic = variance of the per-sample means,
+        total = their sum.  outputs: 'values' (point predictions: aleatoric is 0), 'mean_logvar' (D means then D log-variances,
+        what nn.GaussianNLL trains) or 'mean_var' (D means then D variances) -- required.  Draws are consumed as by
+        predictive_mean with the same arguments.
+          mc_batched on CUDA: one batched pass (a hidden layer fused with its <= 16-wide head hands on partials) + ONE
+                              bnn_mc_regression launch, which also runs the `advance` / `kl` tails (as ops.mc_mean);
+          other CUDA:         forward_stacked (the serial loop), then the same launch;
+          CPU:                forward_stacked, then ops.regression_f64 (the same formulas in float64)."""
+        from .. import ops
+        ops._reg_kind(outputs, "predictive_regression", kl)         # before a draw is consumed
+        if samples is None:
+            samples = self.samples
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            if advance is not None or kl is not None:
+                raise ops.BnnHipError("predictive_regression: advance / kl are tails of the device launch; x is not on the device")
+            return ops.regression_f64(self.forward_stacked(x, samples, sample0, **kwargs), outputs)
+        if self.mc_batched:
+            y = self._forward_batched_stacked(x, samples, sample0, _lazy_head=True, **kwargs)
+        else:
+            y = self.forward_stacked(x, samples, sample0, **kwargs)
+        return ops.mc_regression(y, outputs, advance=advance, kl=kl)
+
     def _forward_batched_stacked(self, x, samples, sample0, *args, _lazy_head=False, **kwargs):
         B = x.shape[0]
         with _mc.McContext(samples, B, sample0) as ctx:

@@ -117,6 +117,20 @@ class Entropy(Module):
         return (-x * torch.log(x + 1e-10)).sum(dim=self.dim).mean()
 
 
+class GaussianNLL(Module):
+    """The heteroscedastic Gaussian likelihood that trains a regression head in 'mean_logvar' layout (D means then D
+    log-variances), averaged over the MC samples: forward(ys, target) with ys the stacked (S, B, 2 D) tensor
+    (`model.forward_stacked(x)`), the list of S per-sample (B, 2 D) outputs `model(x)` returns, or one (B, 2 D) output; target
+    (B, D).  = torch.nn.functional.gaussian_nll_loss(m, target, exp(s)) over the stacked samples, without the constant term.
+    On the device the loss and its gradient come out of one HIP pass (ops.gaussian_nll).  Not in the reference (its
+    examples/Simple regression trains an evidential head); the companion of BayesianNetworkModule.predictive_regression."""
+
+    def forward(self, ys, target):
+        if isinstance(ys, (list, tuple)):
+            ys = torch.stack(list(ys))
+        return ops.gaussian_nll(ys, target)
+
+
 class NormalInverseGaussianLoss(Module):
     """loss.py:54-69: evidential-regression NLL + reg_lambda * |y - gamma| (2 upsilon + alpha)."""
 

@@ -2500,6 +2500,153 @@ def mc_uncertainty(y, inputs=None, advance=None, kl=None):
     return PredictiveUncertainty(mean, total, ale, epi)
 
 
+# --------------------------------------------------------------------------- predictive regression
+PredictiveRegression = collections.namedtuple("PredictiveRegression", ("mean", "total", "aleatoric", "epistemic"))
+PredictiveRegression.__doc__ = """What mc_regression returns, all (*rows, D): mean, the mean of the per-sample means; aleatoric, the
+mean of the per-sample variances; epistemic, the (population) variance of the per-sample means; total = aleatoric + epistemic, the
+variance of the equal-weight mixture of the per-sample predictives (law of total variance)."""
+
+_REG_OUTPUTS = {"values": _lib.REG_VALUES, "mean_logvar": _lib.REG_MEAN_LOGVAR, "mean_var": _lib.REG_MEAN_VAR}
+
+
+def _reg_kind(outputs, who, kl=None):
+    """BNN_REG_* of `outputs`.  Raises ValueError for anything but 'values' / 'mean_logvar' / 'mean_var' (what the last axis
+    holds cannot be told from its values) -- and then leaves no KL pending for a later launch to carry."""
+    if isinstance(outputs, str) and outputs in _REG_OUTPUTS:
+        return _REG_OUTPUTS[outputs]
+    if kl is not None and _tls.kl_carry is kl:
+        _tls.kl_carry = None
+    raise ValueError("%s: outputs must be 'values', 'mean_logvar' or 'mean_var', got %r" % (who, outputs))
+
+
+def _reg_split(y, kind, who):
+    """(means, variances or None) of stacked outputs y (..., width) in float64."""
+    if kind == _lib.REG_VALUES:
+        return y, None
+    if y.shape[-1] % 2:
+        raise ValueError("%s: a (mean, variance) layout needs an even last axis, got %d" % (who, y.shape[-1]))
+    D = y.shape[-1] // 2
+    m, v = y[..., :D], y[..., D:]
+    return m, (torch.exp(v) if kind == _lib.REG_MEAN_LOGVAR else v)
+
+
+def regression_f64(ys, outputs):
+    """The formulas of mc_regression in float64 torch, rounded to float32 at the end (the CPU path of
+    BayesianNetworkModule.predictive_regression): ys (S, *rows, width), the stacked MC outputs.  The variance of the means is
+    the two-pass population variance."""
+    kind = _reg_kind(outputs, "regression_f64")
+    m, v = _reg_split(ys.detach().to(torch.float64), kind, "regression_f64")
+    mean = m.mean(0)
+    epi = ((m - mean) ** 2).mean(0)
+    ale = torch.zeros_like(mean) if v is None else v.mean(0)
+    f32 = lambda t: t.to(torch.float32)         # noqa: E731
+    return PredictiveRegression(f32(mean), f32(ale + epi), f32(ale), f32(epi))
+
+
+def mc_regression(y, outputs=None, advance=None, kl=None):
+    """Predictive mean and variance decomposition over the leading MC axis in ONE launch (bnn_mc_regression) ->
+    PredictiveRegression.
+    y: CUDA fp32 (S, *rows, width) (made contiguous if it is not), or a HeadPartials (a hidden layer fused with its <= 16-wide
+    head: the launch adds the partials itself, bit for bit as y.logits() would).
+    outputs: 'values' (point predictions, D = width), 'mean_logvar' (D means then D log-variances) or 'mean_var' (D means then
+    D variances as given) -- required.
+    advance / kl: as mc_mean (the device epoch bumped, a KlDeferred's second pass run, in the same launch).
+    The sums over samples are fp64 in a fixed order: bitwise reproducible."""
+    kind = _reg_kind(outputs, "mc_regression", kl)
+    try:
+        if isinstance(y, HeadPartials):
+            yy = y.p
+            require_cuda_f32(yy, "y")
+            nparts, S, M, W = yy.shape
+            rows_shape = (M,)
+        else:
+            if not y.is_cuda:
+                raise BnnHipError("y must be a CUDA/HIP tensor")
+            if y.dtype != torch.float32:
+                raise BnnHipError("y must be float32, got %s" % y.dtype)
+            if y.dim() < 2:
+                raise BnnHipError("mc_regression: y must be (S, *rows, width), got %s" % (tuple(y.shape),))
+            yy = y.detach().contiguous()
+            nparts, S, W = 1, yy.shape[0], yy.shape[-1]
+            rows_shape = tuple(yy.shape[1:-1])
+        if kind != _lib.REG_VALUES and W % 2:
+            raise BnnHipError("mc_regression: outputs=%r needs an even last axis, got %d" % (outputs, W))
+        D = W if kind == _lib.REG_VALUES else W // 2
+        rows = 1
+        for d in rows_shape:
+            rows *= d
+        dev = yy.device
+        mean, total, ale, epi = (torch.empty(rows_shape + (D,), dtype=torch.float32, device=dev) for _ in range(4))
+        adv = ptr(advance) if advance is not None else None
+        karr, kT, kn, kout, kws = None, 0, 1.0, None, None
+        if kl is not None:
+            # second pass of a KL begun by kl_normal_begin, as one extra workgroup of this launch (as in mc_mean)
+            if kl.done:
+                raise BnnHipError("mc_regression: this KlDeferred has already been finished")
+            if not kl.launched:                     # no narrow layer took it along
+                if _tls.kl_carry is kl:
+                    _tls.kl_carry = None
+                check(_lib.load().bnn_kl_forward_partial(kl.arr, kl.T, ptr(kl.ws), stream_ptr(dev)), "bnn_kl_forward_partial")
+                kl.launched = True
+            karr, kT, kn, kout, kws = kl.arr, kl.T, kl.n_batches, ptr(kl.out), ptr(kl.ws)
+        check(_lib.load().bnn_mc_regression(ptr(yy), rows * W, nparts, S, rows, W, kind, ptr(mean), ptr(total), ptr(ale),
+                                            ptr(epi), adv, 1, karr, kT, kn, kout, kws, stream_ptr(dev)), "bnn_mc_regression")
+        if kl is not None:
+            kl.done = True
+    except BnnHipError:
+        if kl is not None and _tls.kl_carry is kl:
+            _tls.kl_carry = None                    # the launch that was to finish it failed: nothing may carry it later
+        raise
+    return PredictiveRegression(mean, total, ale, epi)
+
+
+class _GaussianNLL(torch.autograd.Function):
+    """gaussian_nll_loss(m, t, exp(s), full=False, reduction='mean') over the stacked samples: the loss and d loss / d ys in
+    one HIP pass (bnn_gaussian_nll).  ys (S, rows, 2 D), target (rows, D); the target carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, ys, target):
+        require_cuda_f32(ys, "ys")
+        require_cuda_f32(target, "target")
+        S, R, W = ys.shape
+        lib = _lib.load()
+        loss = torch.empty((), dtype=torch.float32, device=ys.device)
+        g = torch.empty_like(ys) if ys.requires_grad else None
+        ws = torch.empty(max(1, lib.bnn_gaussian_nll_workspace_bytes(S, R, W) // 8), dtype=torch.float64, device=ys.device)
+        check(lib.bnn_gaussian_nll(ptr(ys), S, R, W, ptr(target), ptr(loss), ptr(g), ptr(ws), stream_ptr(ys.device)),
+              "bnn_gaussian_nll")
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, up):
+        (g,) = ctx.saved_tensors
+        return (g * up if g is not None else None), None
+
+
+def gaussian_nll(ys, target):
+    """Mean heteroscedastic Gaussian negative log-likelihood (no constant term) of MC outputs in 'mean_logvar' layout:
+    ys (S, *rows, 2 D) -- or (*rows, 2 D), one sample -- holding D means then D log-variances s; target (*rows, D), shared by
+    the samples (never expanded).  mean over samples, rows and D of 0.5 (s + (target - m)^2 exp(-s)) =
+    torch.nn.functional.gaussian_nll_loss(m, target, exp(s)).  Differentiable in ys (the gradient comes out of the same launch);
+    the target carries no gradient.  CPU tensors: the same expression in torch (float64 inside)."""
+    if ys.dim() == target.dim():
+        ys = ys.unsqueeze(0)
+    if ys.dim() != target.dim() + 1 or ys.dim() < 3 or ys.shape[-1] != 2 * target.shape[-1] or ys.shape[1:-1] != target.shape[:-1]:
+        raise ValueError("gaussian_nll: ys must be (S, *rows, 2 D) or (*rows, 2 D) for a target (*rows, D), got %s and %s"
+                         % (tuple(ys.shape), tuple(target.shape)))
+    if not ys.is_cuda:
+        D = target.shape[-1]
+        y64 = ys.to(torch.float64)
+        m, s = y64[..., :D], y64[..., D:]
+        r = target.to(torch.float64) - m
+        return (0.5 * (s + r * r * torch.exp(-s))).mean().to(ys.dtype)
+    if target.requires_grad:
+        raise BnnHipError("gaussian_nll: the target carries no gradient on the device path")
+    S, W = ys.shape[0], ys.shape[-1]
+    return _GaussianNLL.apply(ys.contiguous().view(S, -1, W), target.contiguous().view(-1, W // 2))
+
+
 # --------------------------------------------------------------------------- training-loop callers
 class _SoftmaxXent(torch.autograd.Function):
     """CrossEntropyLoss()(logits, target), reduction 'mean' (examples/MNIST/train.py:39,59-61): the loss

@@ -826,6 +826,42 @@ int bnn_mc_uncertainty(const float *y, int64_t addend_stride, int nparts, int ns
                        const bnn_kl_tensor_t *kl_tensors, int kl_ntensors, float kl_n_batches,
                        float *kl_out, const void *kl_workspace, void *stream);
 
+/* ---- K12: the regression tail of an MC forward -------------------------------------
+ * Predictive mean and variance decomposition of S stacked regression outputs in ONE launch: the moments of the equal-weight
+ * mixture of the S per-sample predictives (law of total variance).
+ * replaces  the mean / aleatoric / epistemic bands of examples/Simple/uncertainty.py over torch.stack(preds)
+ *   y, addend_stride, nparts, nsamples, rows: as bnn_mc_uncertainty (a fused head's partials are first summed over the parts in
+ *   bnn_mc_sum's order, bit-identical to bnn_mc_sum over the parts followed by this call); width: floats per row.
+ *   kind BNN_REG_VALUES       D = width      m_s = y_s                    v_s = 0
+ *        BNN_REG_MEAN_LOGVAR  D = width / 2  m_s = y_s[:D]                v_s = exp(y_s[D:])   (one v_exp_f32 per element)
+ *        BNN_REG_MEAN_VAR     D = width / 2  m_s = y_s[:D]                v_s = y_s[D:] as given
+ *   mean      = (1/S) sum_s m_s                  aleatoric = (1/S) sum_s v_s
+ *   epistemic = (1/S) sum_s (m_s - mean)^2  (population variance: exactly 0 for S = 1; never negative)
+ *   total     = aleatoric + epistemic, added before the outputs are rounded to fp32.       All four: rows x D fp32.
+ *   The sums over samples are fp64 in a fixed order, without float atomics: bitwise reproducible.  The variance of the means is
+ *   taken on m_s - m_0 (sample 0's value), so it keeps its relative accuracy when |mean| is large against the spread.
+ *   1 <= nsamples <= 65536, 1 <= width <= 4096 (even for the two (mean, variance) kinds), 1 <= nparts, 1 <= rows <= 2^31 - 1
+ *   (BNN_E_SHAPE / BNN_E_RANGE otherwise, nothing launched).  Tails: as bnn_mc_uncertainty. */
+enum { BNN_REG_VALUES = 0, BNN_REG_MEAN_LOGVAR = 1, BNN_REG_MEAN_VAR = 2 };
+int bnn_mc_regression(const float *y, int64_t addend_stride, int nparts, int nsamples, int64_t rows, int width,
+                      int kind /* BNN_REG_VALUES 0 | BNN_REG_MEAN_LOGVAR 1 | BNN_REG_MEAN_VAR 2 */,
+                      float *mean, float *total, float *aleatoric, float *epistemic,
+                      uint32_t *advance_epoch, uint32_t advance_inc,
+                      const bnn_kl_tensor_t *kl_tensors, int kl_ntensors, float kl_n_batches,
+                      float *kl_out, const void *kl_workspace, void *stream);
+
+/* The heteroscedastic Gaussian likelihood of a (mean, log-variance) head over the stacked MC samples, loss and gradient in one
+ * pass (no constant term).
+ * replaces  torch.nn.functional.gaussian_nll_loss(m, t, exp(s), full=False, reduction='mean') and its autograd
+ *   y (nsamples, rows, width = 2 D) fp32 contiguous: D means then D log-variances s; target (rows, D) fp32, read once per
+ *   sample, never expanded.  With r = target - m and N = nsamples rows D:
+ *   loss[0] = (1/N) sum 0.5 (s + r^2 exp(-s));   g_y (may be NULL; y's layout): -r exp(-s) / N | 0.5 (1 - r^2 exp(-s)) / N.
+ * Terms in fp32; the sum as per-workgroup fp64 partials into `workspace` (the workspace-bytes query below, 8-B aligned), added
+ * in index order by a second one-workgroup launch: no float atomics, bitwise reproducible.  Errors as above (odd width: BNN_E_SHAPE). */
+int64_t bnn_gaussian_nll_workspace_bytes(int64_t nsamples, int64_t rows, int width);
+int bnn_gaussian_nll(const float *y, int nsamples, int64_t rows, int width, const float *target,
+                     float *loss, float *g_y /* may be NULL */, void *workspace, void *stream);
+
 /* ---- K10: local reparameterization (LocalReparamLinear, bayesianneuralnetworks_amd/nn/dense.py; Kingma, Salimans, Welling 2015,
  * "Variational Dropout and the Local Reparameterization Trick").  The layer has no call site in the reference: it is the other
  * estimator of NormalLinear's posterior (pytorch_bayesian/nn/dense.py:27-60).  With w ~ N(mu_w, sigma_w^2), b ~ N(mu_b, sigma_b^2)
