@@ -200,6 +200,11 @@ SIGNATURES = {
                                  ctypes.POINTER(KlTensor), _int, _f, _p, _p, _p]),
     "bnn_gaussian_nll_workspace_bytes": (_i64, [_i64, _i64, _int]),
     "bnn_gaussian_nll": (_int, [_p, _int, _i64, _int, _p, _p, _p, _p, _p]),
+    "bnn_nig_head_forward": (_int, [_p, _i64, _int, _p, _p, _p, _p, _p]),
+    "bnn_nig_head_backward": (_int, [_p, _p, _p, _p, _p, _i64, _int, _p, _p]),
+    "bnn_nig_loss_workspace_bytes": (_i64, [_i64]),
+    "bnn_nig_loss": (_int, [_p, _p, _p, _p, _p, _i64, ctypes.c_double, _p, _p, _p, _p, _p, _p, _p]),
+    "bnn_mc_evidential": (_int, [_p, _p, _p, _p, _i64, _int, _i64, _int, _p, _p, _p, _p, _p]),
     "bnn_lrt_prepare": (_int, [_p, _p, _i64, _p, _p, _i64, _p]),
     "bnn_lrt_forward": (_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _rngp, _int, _int, _p]),
     "bnn_lrt_backward_epilogue": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _rngp, _int, _p]),

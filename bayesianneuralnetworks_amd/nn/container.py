@@ -75,7 +75,11 @@ class BayesianNetworkModule(Module):
     def _forward_batched(self, x, samples, sample0, *args, **kwargs):
         """One pass, all samples per layer launch.  Returns the list of per-sample outputs
         (views of one (S*B, ...) tensor)."""
-        return list(self._forward_batched_stacked(x, samples, sample0, *args, **kwargs).unbind(0))
+        ys = self._forward_batched_stacked(x, samples, sample0, *args, **kwargs)
+        if isinstance(ys, tuple):
+            # a tuple-valued head (NormalInverseGaussianLinear): S tuples, as the serial loop returns
+            return list(zip(*[t.unbind(0) for t in ys]))
+        return list(ys.unbind(0))
 
     def predictive_mean(self, x, samples=None, sample0=0, out=None, scale=None, advance=None, kl=None, *args, **kwargs):
         """scale (default 1 / samples) * sum over the MC samples of `_forward(x)` -- torch.stack(preds).mean(0) of
@@ -143,6 +147,27 @@ class BayesianNetworkModule(Module):
             y = self.forward_stacked(x, samples, sample0, **kwargs)
         return ops.mc_regression(y, outputs, advance=advance, kl=kl)
 
+    def predictive_evidential(self, x, samples=None, sample0=0, **kwargs):
+        """Predictive mean and variance decomposition of `samples` MC draws of a network whose `_forward(x)` ends in an
+        evidential head and returns its (gamma, upsilon, alpha, beta) -> ops.PredictiveRegression(mean, total, aleatoric,
+        epistemic), each (*rows, D): the moments of the equal-weight mixture of the S heads -- aleatoric = mean of the heads'
+        beta / (alpha - 1), epistemic = mean of the heads' beta / (upsilon (alpha - 1)) plus the variance of gamma over the
+        draws of the trunk, total = their sum.  samples = 1 gives gamma and NormalInverseGaussianUncertainty's two outputs.
+        Draws are consumed as by predictive_regression with the same arguments.
+          mc_batched on CUDA: one batched pass + ONE bnn_mc_evidential launch;
+          other CUDA:         forward_stacked (the serial loop), then the same launch;
+          CPU:                forward_stacked, then ops.evidential_f64 (the same formulas in float64)."""
+        from .. import ops
+        if samples is None:
+            samples = self.samples
+        ys = self.forward_stacked(x, samples, sample0, **kwargs)
+        if not (isinstance(ys, tuple) and len(ys) == 4):
+            raise ValueError("predictive_evidential: _forward must return (gamma, upsilon, alpha, beta), got %s"
+                             % type(ys).__name__)
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            return ops.evidential_f64(*ys)
+        return ops.mc_evidential(*ys)
+
     def _forward_batched_stacked(self, x, samples, sample0, *args, _lazy_head=False, **kwargs):
         B = x.shape[0]
         with _mc.McContext(samples, B, sample0) as ctx:
@@ -159,6 +184,12 @@ class BayesianNetworkModule(Module):
         from .. import ops
         if isinstance(y, ops.HeadPartials):
             return y if _lazy_head else y.logits()
+        if isinstance(y, tuple) and y and all(isinstance(t, torch.Tensor) for t in y):
+            return tuple(self._stack_samples(t, samples, B) for t in y)
+        return self._stack_samples(y, samples, B)
+
+    @staticmethod
+    def _stack_samples(y, samples, B):
         if y.shape[0] == B * samples:
             return y.view(samples, B, *y.shape[1:])
         if y.shape[0] == B:
@@ -244,10 +275,13 @@ class BayesianNetworkModule(Module):
         return todo
 
     def forward_stacked(self, x, samples=None, sample0=0, *args, **kwargs):
-        """(S, B, ...) tensor of all MC outputs (batched path when enabled)."""
+        """(S, B, ...) tensor of all MC outputs (batched path when enabled).  A tuple-valued `_forward` (an evidential head) gives
+        a tuple of (S, B, ...) tensors; the serial loop stacks each component with one `torch.stack` copy (four for that head)."""
         if samples is None:
             samples = self.samples
-        if self.mc_batched and x.is_cuda:
+        if self.mc_batched and isinstance(x, torch.Tensor) and x.is_cuda:
             return self._forward_batched_stacked(x, samples, sample0, *args, **kwargs)
         out = [self._forward(x, *args, **kwargs) for _ in range(samples)]
+        if out and isinstance(out[0], tuple):
+            return tuple(torch.stack(ts) for ts in zip(*out))       # a tuple-valued head: each component stacked
         return torch.stack(out)

@@ -548,18 +548,24 @@ class MultivariateNormalLinear(BayesianLinear):
 
 
 class NormalInverseGaussianLinear(BayesianModule):
-    """dense.py:141-162: evidential head, deterministic Linear(in, 4*out) + softplus splits."""
+    """dense.py:141-162: evidential head, deterministic Linear(in, 4*out) + softplus splits.  On a CUDA fp32 input the splits,
+    softplus and offsets are one HIP launch (ops.nig_head; the Linear stays torch's); CPU and other dtypes: torch ops."""
 
     def __init__(self, in_features, out_features, bias=True):
         super().__init__(in_features, out_features, None)
         self.linear = torch.nn.Linear(in_features, 4 * out_features, bias)
 
     def forward(self, x, sample=False):
-        sp = torch.nn.functional.softplus
-        gamma, upsilon, alpha, beta = torch.split(self.linear(x), self.out_channels, dim=-1)
-        upsilon = 1e-10 + sp(upsilon)
-        alpha = 1 + 1e-10 + sp(alpha)
-        beta = 1e-10 + sp(beta)
+        z = self.linear(x)
+        if ops.EVIDENTIAL_HIP and z.is_cuda and z.dtype == torch.float32 and z.numel() > 0:
+            # K13: the split, the three softplus and the offsets in one launch (and one backward)
+            gamma, upsilon, alpha, beta = ops.nig_head(z, self.out_channels)
+        else:
+            sp = torch.nn.functional.softplus
+            gamma, upsilon, alpha, beta = torch.split(z, self.out_channels, dim=-1)
+            upsilon = 1e-10 + sp(upsilon)
+            alpha = 1 + 1e-10 + sp(alpha)
+            beta = 1e-10 + sp(beta)
         if not sample:
             return (gamma, upsilon, alpha, beta)
         return Normal(gamma.clone(), torch.sqrt(beta / (upsilon * (alpha - 1))))

@@ -132,7 +132,8 @@ class GaussianNLL(Module):
 
 
 class NormalInverseGaussianLoss(Module):
-    """loss.py:54-69: evidential-regression NLL + reg_lambda * |y - gamma| (2 upsilon + alpha)."""
+    """loss.py:54-69: evidential-regression NLL + reg_lambda * |y - gamma| (2 upsilon + alpha).  Five CUDA fp32 tensors of one
+    shape: ops.nig_loss (one HIP pass; y then carries no gradient); anything else: the torch expression below."""
 
     def __init__(self, reg_lambda=1e-2):
         super().__init__()
@@ -146,6 +147,12 @@ class NormalInverseGaussianLoss(Module):
                 + torch.lgamma(alpha) - torch.lgamma(alpha + 0.5))
 
     def forward(self, gamma, upsilon, alpha, beta, y):
+        ts = (gamma, upsilon, alpha, beta, y)
+        if ops.EVIDENTIAL_HIP and ops._is_dev_f32(*ts) and all(t.shape == gamma.shape for t in ts) and gamma.numel() > 0 and \
+                not (y.requires_grad and torch.is_grad_enabled()):
+            # K13: the loss and the gradients of the inputs that require one in one HIP pass (a y that wants a gradient keeps
+            # the torch expression below; only the explicit ops.nig_loss refuses it)
+            return ops.nig_loss(gamma, upsilon, alpha, beta, y, self.reg_lambda)
         penalty = torch.mean(torch.abs(y - gamma) * (2 * upsilon + alpha))
         return self.nll(y, gamma, upsilon, alpha, beta).mean() + self.reg_lambda * penalty
 

@@ -2647,6 +2647,139 @@ def gaussian_nll(ys, target):
     return _GaussianNLL.apply(ys.contiguous().view(S, -1, W), target.contiguous().view(-1, W // 2))
 
 
+# --------------------------------------------------------------------------- K13: evidential regression
+# The device path of NormalInverseGaussianLinear / NormalInverseGaussianLoss (A/B switch: off = the torch-op chain of the
+# reference on the device, what the layers did before K13).
+EVIDENTIAL_HIP = True
+
+
+def _is_dev_f32(*ts):
+    return all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in ts)
+
+
+class _NigHead(torch.autograd.Function):
+    """z (rows, 4 D) -> gamma, upsilon, alpha, beta (rows, D) in one launch (bnn_nig_head_forward); the backward is one launch
+    too (bnn_nig_head_backward), an absent incoming gradient is passed as NULL."""
+
+    @staticmethod
+    def forward(ctx, z, D):
+        require_cuda_f32(z, "z")
+        rows = z.shape[0]
+        outs = tuple(torch.empty((rows, D), dtype=torch.float32, device=z.device) for _ in range(4))
+        check(_lib.load().bnn_nig_head_forward(ptr(z), rows, D, *[ptr(t) for t in outs], stream_ptr(z.device)),
+              "bnn_nig_head_forward")
+        ctx.save_for_backward(z)
+        ctx.D = D
+        ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    def backward(ctx, *gs):
+        (z,) = ctx.saved_tensors
+        gs = [None if g is None else g.contiguous() for g in gs]
+        for g in gs:
+            if g is not None:
+                require_cuda_f32(g, "gradient")
+        gz = torch.empty_like(z)
+        check(_lib.load().bnn_nig_head_backward(ptr(z), *[ptr(g) for g in gs], z.shape[0], ctx.D, ptr(gz), stream_ptr(z.device)),
+              "bnn_nig_head_backward")
+        return gz, None
+
+
+def nig_head(z, D):
+    """The evidential head's activation on the output z (*rows, 4 D) of its Linear (CUDA fp32) -> (gamma, upsilon, alpha, beta),
+    each (*rows, D) and contiguous: gamma = z[..., :D], upsilon = 1e-10 + softplus(z[..., D:2D]), alpha = 1 + 1e-10 +
+    softplus(z[..., 2D:3D]), beta = 1e-10 + softplus(z[..., 3D:]) (NormalInverseGaussianLinear, dense.py:141-162).
+    Differentiable in z; one launch forward, one backward."""
+    if not _is_dev_f32(z):
+        raise BnnHipError("nig_head: z must be a CUDA/HIP float32 tensor")
+    if z.dim() < 1 or D < 1 or z.shape[-1] != 4 * D:
+        raise BnnHipError("nig_head: z must be (*rows, 4 D) with D = %d, got %s" % (D, tuple(z.shape)))
+    lead = tuple(z.shape[:-1])
+    outs = _NigHead.apply(z.contiguous().view(-1, 4 * D), D)
+    return tuple(t.view(lead + (D,)) for t in outs)
+
+
+class _NigLoss(torch.autograd.Function):
+    """NormalInverseGaussianLoss.forward (loss.py:54-69) and the gradients of the inputs that require one, in one HIP pass
+    (bnn_nig_loss: two launches).  Flat contiguous fp32 inputs of one length; y carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, gamma, upsilon, alpha, beta, y, reg_lambda):
+        for t, name in ((gamma, "gamma"), (upsilon, "upsilon"), (alpha, "alpha"), (beta, "beta"), (y, "y")):
+            require_cuda_f32(t, name)
+        n = gamma.numel()
+        lib = _lib.load()
+        dev = gamma.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        gs = [torch.empty_like(t) if need else None for t, need in zip((gamma, upsilon, alpha, beta), ctx.needs_input_grad[:4])]
+        ws = torch.empty(max(1, lib.bnn_nig_loss_workspace_bytes(n) // 8), dtype=torch.float64, device=dev)
+        check(lib.bnn_nig_loss(ptr(gamma), ptr(upsilon), ptr(alpha), ptr(beta), ptr(y), n, float(reg_lambda), ptr(loss),
+                               *[ptr(g) for g in gs], ptr(ws), stream_ptr(dev)), "bnn_nig_loss")
+        ctx.save_for_backward(*gs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, up):
+        return tuple(None if g is None else g * up for g in ctx.saved_tensors) + (None, None)
+
+
+def nig_loss(gamma, upsilon, alpha, beta, y, reg_lambda=1e-2):
+    """mean(nll) + reg_lambda * mean(|y - gamma| (2 upsilon + alpha)) of an evidential head's outputs against y
+    (NormalInverseGaussianLoss, loss.py:54-69): five CUDA fp32 tensors of one shape (strided views are made contiguous).  The
+    gradients of the inputs that require one come out of the same pass; y carries no gradient.  Every element is evaluated in
+    float64 on the device and the sum is taken in a fixed order: bitwise reproducible."""
+    ts = (gamma, upsilon, alpha, beta, y)
+    if not _is_dev_f32(*ts):
+        raise BnnHipError("nig_loss: gamma, upsilon, alpha, beta and y must be CUDA/HIP float32 tensors")
+    if any(t.shape != gamma.shape for t in ts) or gamma.numel() < 1:
+        raise BnnHipError("nig_loss: the five tensors must have one non-empty shape, got %s" % ([tuple(t.shape) for t in ts],))
+    if y.requires_grad and torch.is_grad_enabled():
+        raise BnnHipError("nig_loss: y carries no gradient on the device path")
+    return _NigLoss.apply(*[t.contiguous().view(-1) for t in ts], float(reg_lambda))
+
+
+def _evidential_shapes(ts, who):
+    if any(not isinstance(t, torch.Tensor) or t.shape != ts[0].shape for t in ts) or ts[0].dim() < 2 or ts[0].numel() < 1:
+        raise ValueError("%s: gamma, upsilon, alpha, beta must be four (S, *rows, D) tensors of one shape" % who)
+
+
+def evidential_f64(gamma, upsilon, alpha, beta):
+    """The formulas of mc_evidential in float64 torch, rounded to float32 at the end (the CPU path of
+    BayesianNetworkModule.predictive_evidential): four (S, *rows, D) tensors, the stacked per-sample head outputs.  The variance
+    of gamma is the two-pass population variance."""
+    _evidential_shapes((gamma, upsilon, alpha, beta), "evidential_f64")
+    g, u, a, b = (t.detach().to(torch.float64) for t in (gamma, upsilon, alpha, beta))
+    ale_s = b / (a - 1)
+    mean = g.mean(0)
+    ale = ale_s.mean(0)
+    epi = (ale_s / u).mean(0) + ((g - mean) ** 2).mean(0)
+    f32 = lambda t: t.to(torch.float32)         # noqa: E731
+    return PredictiveRegression(f32(mean), f32(ale + epi), f32(ale), f32(epi))
+
+
+def mc_evidential(gamma, upsilon, alpha, beta):
+    """Predictive moments of the equal-weight mixture of S evidential heads over the leading MC axis in ONE launch
+    (bnn_mc_evidential) -> PredictiveRegression: mean = mean_s gamma_s, aleatoric = mean_s beta / (alpha - 1), epistemic =
+    mean_s beta / (upsilon (alpha - 1)) + Var_s(gamma_s), total = aleatoric + epistemic.  Four CUDA fp32 (S, *rows, D) tensors
+    (made contiguous if they are not).  S = 1: gamma and NormalInverseGaussianUncertainty's two outputs, bit for bit.  The
+    sums over samples are fp64 in a fixed order: bitwise reproducible."""
+    ts = (gamma, upsilon, alpha, beta)
+    _evidential_shapes(ts, "mc_evidential")
+    if not _is_dev_f32(*ts):
+        raise BnnHipError("mc_evidential: gamma, upsilon, alpha, beta must be CUDA/HIP float32 tensors")
+    g, u, a, b = (t.detach().contiguous() for t in ts)
+    S, D = g.shape[0], g.shape[-1]
+    rows_shape = tuple(g.shape[1:-1])
+    rows = 1
+    for d in rows_shape:
+        rows *= d
+    mean, total, ale, epi = (torch.empty(rows_shape + (D,), dtype=torch.float32, device=g.device) for _ in range(4))
+    check(_lib.load().bnn_mc_evidential(ptr(g), ptr(u), ptr(a), ptr(b), rows * D, S, rows, D, ptr(mean), ptr(total), ptr(ale),
+                                        ptr(epi), stream_ptr(g.device)), "bnn_mc_evidential")
+    return PredictiveRegression(mean, total, ale, epi)
+
+
 # --------------------------------------------------------------------------- training-loop callers
 class _SoftmaxXent(torch.autograd.Function):
     """CrossEntropyLoss()(logits, target), reduction 'mean' (examples/MNIST/train.py:39,59-61): the loss

@@ -862,6 +862,46 @@ int64_t bnn_gaussian_nll_workspace_bytes(int64_t nsamples, int64_t rows, int wid
 int bnn_gaussian_nll(const float *y, int nsamples, int64_t rows, int width, const float *target,
                      float *loss, float *g_y /* may be NULL */, void *workspace, void *stream);
 
+/* ---- K13: evidential regression (the Normal-Inverse-Gamma head of examples/Simple) ----------------------------------
+ * The head's activation.  replaces  the split / softplus / offsets of NormalInverseGaussianLinear.forward (nn/dense.py:141-162)
+ *   z (rows, 4 D) fp32 contiguous, the output of the head's Linear.  One launch writes four contiguous (rows, D) tensors:
+ *   gamma = z[:, 0:D];  upsilon = 1e-10 + softplus(z[:, D:2D]);  alpha = 1 + 1e-10 + softplus(z[:, 2D:3D]);
+ *   beta = 1e-10 + softplus(z[:, 3D:4D]).  Softplus: torch's (beta 1, threshold 20: z > 20 gives z), log1pf(expf(z)) below.
+ *   1 <= rows <= 2^31 - 1, 1 <= D <= 4096 (BNN_E_SHAPE / BNN_E_RANGE otherwise, nothing launched). */
+int bnn_nig_head_forward(const float *z, int64_t rows, int D, float *gamma, float *upsilon, float *alpha, float *beta,
+                         void *stream);
+/* g_z (rows, 4 D) = [g_gamma | g_upsilon sigmoid(z_u) | g_alpha sigmoid(z_a) | g_beta sigmoid(z_b)] in one launch; the derivative
+ * of the softplus is 1 above the threshold.  Each incoming gradient ((rows, D) contiguous) may be NULL = zero. */
+int bnn_nig_head_backward(const float *z, const float *g_gamma, const float *g_upsilon, const float *g_alpha,
+                          const float *g_beta, int64_t rows, int D, float *g_z, void *stream);
+
+/* The evidential loss and its four gradients in one pass.
+ * replaces  NormalInverseGaussianLoss.forward (nn/loss.py:54-69) and its autograd
+ *   loss[0] = mean(nll) + reg_lambda mean(|y - gamma| (2 upsilon + alpha)) over n elements (five fp32 arrays of n), with
+ *   nll = 0.5 ln(pi / upsilon) - alpha ln omega + (alpha + 0.5) ln(upsilon (y - gamma)^2 + omega) + lgamma(alpha) - lgamma(alpha + 0.5),
+ *   omega = 2 beta (1 + upsilon).  g_gamma, g_upsilon, g_alpha, g_beta (n fp32 each): d loss / d input; each may be NULL and is
+ *   then neither computed nor written.  y carries no gradient; d|y - gamma| at 0 is 0 (torch.abs).
+ * Every element is evaluated in fp64 (the differences of lgamma and of digamma cancel for large alpha); the sum as
+ * per-workgroup fp64 partials into `workspace` (bnn_nig_loss_workspace_bytes(n) bytes, 8-B aligned), added in a fixed order by a
+ * second one-workgroup launch: no float atomics, bitwise reproducible.  n >= 1 (BNN_E_SHAPE otherwise; the query returns 0). */
+int64_t bnn_nig_loss_workspace_bytes(int64_t n);
+int bnn_nig_loss(const float *gamma, const float *upsilon, const float *alpha, const float *beta, const float *y, int64_t n,
+                 double reg_lambda /* a double: the reference multiplies by the Python float */, float *loss,
+                 float *g_gamma /* may be NULL */, float *g_upsilon /* may be NULL */,
+                 float *g_alpha /* may be NULL */, float *g_beta /* may be NULL */, void *workspace, void *stream);
+
+/* The moments of the equal-weight mixture of S NIG heads over a leading MC axis in ONE launch (law of total variance).
+ *   gamma, upsilon, alpha, beta: (nsamples, rows, D) fp32, sample s at + s * sample_stride elements (>= rows * D).
+ *   a_s = beta / (alpha - 1), e_s = a_s / upsilon: NormalInverseGaussianUncertainty (nn/loss.py:72-79) per sample, in fp32.
+ *   mean = (1/S) sum gamma_s;  aleatoric = (1/S) sum a_s;  epistemic = (1/S) sum e_s + Var_s(gamma_s);  total = aleatoric +
+ *   epistemic, added before the outputs are rounded to fp32.  All four: rows x D fp32.  Var_s as in bnn_mc_regression: on
+ *   gamma_s - gamma_0, fp64, clamped at 0.  nsamples = 1 gives gamma and that module's two outputs exactly.
+ *   Sums over samples fp64 in a fixed order, no float atomics: bitwise reproducible.
+ *   1 <= nsamples <= 65536, 1 <= D <= 4096, 1 <= rows <= 2^31 - 1 (BNN_E_SHAPE / BNN_E_RANGE otherwise, nothing launched). */
+int bnn_mc_evidential(const float *gamma, const float *upsilon, const float *alpha, const float *beta, int64_t sample_stride,
+                      int nsamples, int64_t rows, int D, float *mean, float *total, float *aleatoric, float *epistemic,
+                      void *stream);
+
 /* ---- K10: local reparameterization (LocalReparamLinear, bayesianneuralnetworks_amd/nn/dense.py; Kingma, Salimans, Welling 2015,
  * "Variational Dropout and the Local Reparameterization Trick").  The layer has no call site in the reference: it is the other
  * estimator of NormalLinear's posterior (pytorch_bayesian/nn/dense.py:27-60).  With w ~ N(mu_w, sigma_w^2), b ~ N(mu_b, sigma_b^2)
