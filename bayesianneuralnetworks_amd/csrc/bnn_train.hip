@@ -82,6 +82,7 @@ __global__ void k_adam_step_bump(float *step, uint32_t *epoch_dev, uint32_t inc)
 
 // Mean cross-entropy over R rows of C <= 64 logits each (CrossEntropyLoss, reduction = 'mean'):
 //   loss = mean_r (logsumexp(x_r) - x_r[y_r]);   gx_r = (softmax(x_r) - onehot(y_r)) / R
+// (a target outside [0, C): NaN loss and NaN gradient row)
 // One thread per row (rows are short: C = 10 for the north-star head); per-workgroup partial sums in
 // double, fixed-order final sum by a second 1-workgroup kernel (bitwise reproducible).
 __global__ __launch_bounds__(256) void k_xent_rows(const float *__restrict__ x, const int64_t *__restrict__ y,
@@ -97,12 +98,19 @@ __global__ __launch_bounds__(256) void k_xent_rows(const float *__restrict__ x, 
         for (int c = 1; c < C; ++c) mx = fmaxf(mx, xr[c]);
         float se = 0.f;
         for (int c = 0; c < C; ++c) se += __expf(xr[c] - mx);
-        const float lse = mx + __logf(se);
-        const int yc = (int)y[r];
-        li = (double)(lse - xr[yc]);
+        // The target is compared as the int64 it is (2^32 + 1 is not class 1).  Outside [0, C): the row's loss and its
+        // gradient row are NaN -- so is the mean -- and nothing outside the row is read; no host round trip.
+        const int64_t y64 = y[r];
+        const bool ok = y64 >= 0 && y64 < (int64_t)C;
+        const int yc = ok ? (int)y64 : 0;
+        const float nan = __builtin_nanf("");
+        // ln(se) - (x[y] - mx), not (mx + ln(se)) - x[y]: every rounding is at the magnitude of the loss and of the gap to the
+        // largest logit (0 for a correct, confident row), none at the magnitude of the logits themselves.
+        li = ok ? (double)(__logf(se) - (xr[yc] - mx)) : (double)nan;
         if (gx) {
             const float inv = inv_R / se;
-            for (int c = 0; c < C; ++c) gx[r * C + c] = __expf(xr[c] - mx) * inv - (c == yc ? inv_R : 0.f);
+            for (int c = 0; c < C; ++c)
+                gx[r * C + c] = ok ? __expf(xr[c] - mx) * inv - (c == yc ? inv_R : 0.f) : nan;
         }
     }
     li = wave_sum(li);

@@ -2809,7 +2809,11 @@ class _SoftmaxXent(torch.autograd.Function):
 
 
 def cross_entropy(logits, target):
-    """Mean cross-entropy of (rows, classes) fp32 logits against int64 class indices."""
+    """Mean cross-entropy of (rows, classes) fp32 logits against int64 class indices.
+
+    A target outside [0, classes) (compared as int64; there is no ignore_index) makes the loss NaN and that row of the
+    gradient NaN; the other gradient rows are unaffected and nothing outside the row is read.  The check runs on the device:
+    no host synchronisation, the call stays graph-capturable."""
     return _SoftmaxXent.apply(logits.contiguous(), target.contiguous())
 
 

@@ -4,11 +4,19 @@ tensor of the model updated by ONE HIP launch (csrc/bnn_train.hip) -- graph-capt
 counter lives on the device.
 
 Deviations from torch.optim.Adam (pinned by tests/test_hip_parity.py::test_fused_adam_matches_torch_adam at
-rtol 1e-5 over the first steps, where they are largest): ONE step counter per parameter group (torch: one per
-parameter -- the same value whenever every parameter of the group has a gradient, as in the reference's loop)
-and the bias corrections 1 - beta^t evaluated in fp32 on the device (torch: Python doubles), about 6e-5 relative
-on the very first updates.  The state_dict therefore holds `step` in the group, not per parameter: it is not
-interchangeable with torch.optim.Adam's."""
+rtol 1e-5 against torch, and held to float64 in tests/test_train_tail.py): ONE step counter per parameter group
+(torch: one per parameter -- the same value whenever every parameter of the group has a gradient, as in the
+reference's loop), and hyper-parameters and bias corrections in fp32 (torch: Python doubles).  Two effects, both
+relative to the update:
+  * lr, betas, eps and weight_decay are passed to the device as floats.  1 - beta then carries the beta's rounding
+    amplified by beta / (1 - beta): at most 2^-24 (2 + 2 b1 / (1 - b1) + b2 / (1 - b2)) = 6e-5 for the default
+    betas.  Measured from arbitrary (m, v) states: 6.7e-6 for (0.9, 0.999), 7e-7 for (0.9, 0.99), about constant
+    over the first 1 / (1 - b2) steps and below 1e-6 after them; 8.3e-5 for b2 = 0.9999, NOT largest at the first
+    steps.  From a zero state the first steps deviate least (5e-8: the factor 1 - b2 of v and of 1 - b2^t cancels).
+  * 1 - powf(beta, t) in fp32 is within 4 * 2^-24 * beta^t / (1 - beta^t) relative (halved for b2 by the square
+    root): largest on the first updates -- at most 6e-5 at t = 2 for b2 = 0.999 (t = 1 is exact) -- and gone once
+    beta^t is small.
+The state_dict holds `step` in the group, not per parameter: it is not interchangeable with torch.optim.Adam's."""
 import ctypes
 
 import torch

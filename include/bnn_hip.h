@@ -686,7 +686,11 @@ int bnn_adam_step_advance(const bnn_adam_tensor_t *tensors, int ntensors, float 
                           uint32_t advance_inc, void *stream);
 /* replaces  torch.nn.CrossEntropyLoss()(pred, y)   examples/MNIST/train.py:39,59-61  (reduction 'mean'):
  *   loss[0] = mean_r (logsumexp(x_r) - x_r[y_r]);  g_logits (may be NULL) = (softmax(x_r) - onehot(y_r)) / rows.
- * logits (rows, classes) fp32 row-major, target int64; workspace: bnn_xent_workspace_bytes(rows). */
+ * logits (rows, classes) fp32 row-major, target int64; workspace: bnn_xent_workspace_bytes(rows).
+ * The row loss is formed as ln(sum_c exp(x_c - max)) - (x_y - max): it rounds at the magnitude of the loss, not of the logits.
+ * A target outside [0, classes) -- compared as int64, before any narrowing; ignore_index is NOT supported -- makes that
+ * row's loss NaN, hence loss[0], and its row of g_logits NaN; nothing outside the row is read, every other gradient row is
+ * what it would be without it.  Checked on the device: no host synchronisation, the call stays graph-capturable. */
 int64_t bnn_xent_workspace_bytes(int64_t rows);
 int bnn_softmax_xent(const float *logits, const int64_t *target, int64_t rows, int classes,
                      float *loss, float *g_logits, void *workspace, void *stream);
