@@ -196,6 +196,10 @@ SIGNATURES = {
                              _p, _p, _p]),
     "bnn_mc_uncertainty": (_int, [_p, _i64, _int, _int, _i64, _int, _int, _p, _p, _p, _p, _p, ctypes.c_uint32,
                                   ctypes.POINTER(KlTensor), _int, _f, _p, _p, _p]),
+    "bnn_mc_score_state_doubles": (_i64, [_int, _int]),
+    "bnn_mc_score_workspace_bytes": (_i64, [_i64]),
+    "bnn_mc_score": (_int, [_p, _i64, _int, _int, _i64, _int, _int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _int, _int, _p, _p,
+                            ctypes.c_uint32, _p]),
     "bnn_mc_regression": (_int, [_p, _i64, _int, _int, _i64, _int, _int, _p, _p, _p, _p, _p, ctypes.c_uint32,
                                  ctypes.POINTER(KlTensor), _int, _f, _p, _p, _p]),
     "bnn_gaussian_nll_workspace_bytes": (_i64, [_i64, _i64, _int]),

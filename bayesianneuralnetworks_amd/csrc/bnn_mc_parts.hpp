@@ -1,6 +1,6 @@
 // bnn_mc_parts.hpp -- what the one-launch MC tails over (S, rows, width) outputs share (bnn_uncertainty.hip: classification,
-// bnn_regression.hip: regression): the launch arguments, a fused head's partials added in bnn_mc_sum's order, and the epoch / KL
-// tails of the launch.
+// bnn_score.hip: classification against labels, bnn_regression.hip: regression): the launch arguments, a fused head's partials
+// added in bnn_mc_sum's order, the epoch / KL tails of the launch, and the classification tails' row reductions.
 #pragma once
 #include "bnn_device.hpp"
 #include "bnn_kl_body.hpp"
@@ -83,6 +83,50 @@ __device__ __forceinline__ bool unc_tails(int nwork, uint32_t *advance_epoch, ui
     }
     if (advance_epoch && blockIdx.x == 0 && threadIdx.x == 0) advance_epoch[0] += advance_inc;
     return false;
+}
+
+// ---- shared by the classification tails (bnn_uncertainty.hip, bnn_score.hip)
+constexpr double kLn2 = 0.693147180559945309417;
+
+// Entropy of the per-row mean in bits, one class: -m log2 m (LOGITS, 0 log 0 = 0) / -m log2(m + 1e-10) (PROBS, the
+// reference's Entropy convention).  The log is v_log_f32 on the fp32-rounded mean; a term below 2^-100 is dropped (<= 1e-28).
+template <int KIND>
+__device__ __forceinline__ double total_term_bits(double m)
+{
+    const float mf = (float)m;
+    if constexpr (KIND == BNN_UNC_LOGITS) return mf > 0x1p-100f ? -m * (double)__builtin_amdgcn_logf(mf) : 0.0;
+    return -m * (double)__builtin_amdgcn_logf(mf + 1e-10f);
+}
+
+// Row reductions over TPR threads: the wave's xor tree, then (TPR 256) the four waves' values in a fixed order through LDS.
+// Every thread returns the same bits.  `slot`: LDS of this reduction (alternating per sample, so one barrier suffices).
+template <int TPR>
+__device__ __forceinline__ float row_max(float v, float *slot)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    if constexpr (TPR == 256) {
+        if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
+        __syncthreads();
+        v = fmaxf(fmaxf(slot[0], slot[1]), fmaxf(slot[2], slot[3]));
+    }
+    return v;
+}
+
+template <int TPR, typename T>
+__device__ __forceinline__ void row_sum2(T &a, T &b, T *slot)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+    }
+    if constexpr (TPR == 256) {
+        if ((threadIdx.x & 63) == 0) { slot[threadIdx.x >> 6] = a; slot[4 + (threadIdx.x >> 6)] = b; }
+        __syncthreads();
+        a = (slot[0] + slot[1]) + (slot[2] + slot[3]);
+        b = (slot[4] + slot[5]) + (slot[6] + slot[7]);
+    }
 }
 
 }  // namespace bnn

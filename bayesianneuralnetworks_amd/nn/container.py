@@ -122,6 +122,37 @@ class BayesianNetworkModule(Module):
             y = self.forward_stacked(x, samples, sample0, **kwargs)
         return ops.mc_uncertainty(y, inputs, advance=advance, kl=kl)
 
+    def predictive_score(self, x, target, samples=None, sample0=0, *, inputs, state=None, advance=None, **kwargs):
+        """`samples` MC draws of `_forward(x)` scored against the labels `target` (int64, one per row) -> ops.PredictiveScore(mean,
+        nll, expected_nll, brier, confidence, prediction, entropy): nll = -ln mean[y] of the MC predictive, expected_nll the mean
+        per-sample NLL (the ELBO's data term), brier, the confidence max_c mean[c] with its class, and H(mean).  inputs: 'logits'
+        or 'probs' as predictive_uncertainty -- required.  state: an ops.ScoreState on x's device that this batch is added to, so
+        that one state carries a test set (accuracy, NLL, Brier, ECE / MCE with the reliability diagram, the accuracy-rejection
+        curve: ScoreState.result(), the only host copy).  Draws are consumed as by predictive_mean with the same arguments.
+          mc_batched on CUDA: one batched pass (a hidden layer fused with its head hands on partial logits) + ONE bnn_mc_score
+                              launch (two with a state), which also runs the `advance` tail (as ops.mc_mean);
+          other CUDA:         forward_stacked (the serial loop), then the same launch;
+          CPU:                forward_stacked, then ops.score_f64 (the same formulas in float64), added to a CPU state."""
+        from .. import ops
+        ops._unc_kind(inputs, "predictive_score")                   # before a draw is consumed
+        if samples is None:
+            samples = self.samples
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            if advance is not None:
+                raise ops.BnnHipError("predictive_score: advance is a tail of the device launch; x is not on the device")
+            if state is not None and not (isinstance(state, ops.ScoreState) and state.device.type == "cpu"):
+                raise ops.BnnHipError("predictive_score: x is not on the device, so state must be a ScoreState on the CPU")
+            cb, eb = (state.conf_bins, state.ent_bins) if state is not None else (15, 20)
+            out, vec = ops.score_f64(self.forward_stacked(x, samples, sample0, **kwargs), target, inputs, cb, eb)
+            if state is not None:
+                state.add_(vec)
+            return out
+        if self.mc_batched:
+            y = self._forward_batched_stacked(x, samples, sample0, _lazy_head=True, **kwargs)
+        else:
+            y = self.forward_stacked(x, samples, sample0, **kwargs)
+        return ops.mc_score(y, target, inputs, state=state, advance=advance)
+
     def predictive_regression(self, x, samples=None, sample0=0, *, outputs, advance=None, kl=None, **kwargs):
         """Predictive mean and variance decomposition of `samples` MC draws of a real-valued `_forward(x)` ->
         ops.PredictiveRegression(mean, total, aleatoric, epistemic), each (*rows, D): the moments of the equal-weight mixture of

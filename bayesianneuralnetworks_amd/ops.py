@@ -9,6 +9,7 @@ Every function here requires CUDA (HIP) tensors and raises BnnHipError otherwise
 """
 import collections
 import ctypes
+import math
 import os
 import threading
 
@@ -2500,8 +2501,199 @@ def mc_uncertainty(y, inputs=None, advance=None, kl=None):
     return PredictiveUncertainty(mean, total, ale, epi)
 
 
+# --------------------------------------------------------------------------- predictive score (against labels)
+PredictiveScore = collections.namedtuple("PredictiveScore", ("mean", "nll", "expected_nll", "brier", "confidence", "prediction",
+                                                             "entropy"))
+PredictiveScore.__doc__ = """What mc_score returns: mean (*rows, C), the predictive mean of the per-sample probabilities; and per row
+(*rows) nll = -ln mean[y], expected_nll = -(1/S) sum_s ln p_s[y] (the ELBO's data term), brier = sum_c (mean[c] - [c = y])^2,
+confidence = max_c mean[c], prediction (int64) = the lowest class attaining it, entropy = H(mean).  A target outside [0, C) makes
+the row's nll, expected_nll and brier NaN."""
+
+ScoreResult = collections.namedtuple("ScoreResult", ("n", "accuracy", "nll", "expected_nll", "brier", "ece", "mce", "reliability",
+                                                     "rejection"))
+ScoreResult.__doc__ = """What ScoreState.result() returns (Python floats): n rows; accuracy, nll, expected_nll, brier: their means;
+ece = sum_b (n_b / n) |acc_b - conf_b| and mce = max_b |acc_b - conf_b| over the non-empty confidence bins; reliability: per
+confidence bin (count, mean confidence, accuracy), NaN in an empty bin; rejection: per upper entropy-bin edge (coverage, accuracy)
+of the rows kept when only those up to that edge are answered -- cumulative from the least uncertain bin upward."""
+
+
+def score_state_size(conf_bins, ent_bins):
+    """Doubles of a score state: [n, sum nll, sum expected_nll, sum brier, sum correct] + (count, sum confidence, sum correct) per
+    confidence bin + (count, sum correct) per entropy bin (bnn_mc_score_state_doubles)."""
+    if not (1 <= int(conf_bins) <= 128 and 1 <= int(ent_bins) <= 128):
+        raise ValueError("score state: conf_bins and ent_bins must be in 1 .. 128, got %r, %r" % (conf_bins, ent_bins))
+    return 5 + 3 * int(conf_bins) + 2 * int(ent_bins)
+
+
+class ScoreState:
+    """The accumulator of mc_score / BayesianNetworkModule.predictive_score over the batches of a test set: a zeroed float64
+    buffer on `device` (layout: score_state_size) that every scored batch is added to on the device, and the launch's workspace.
+    Nothing is copied to the host until result().  On a CPU device it accumulates what score_f64 returns."""
+
+    def __init__(self, device, conf_bins=15, ent_bins=20):
+        self.conf_bins, self.ent_bins = int(conf_bins), int(ent_bins)
+        self.device = torch.device(device)
+        self.state = torch.zeros(score_state_size(conf_bins, ent_bins), dtype=torch.float64, device=self.device)
+        self._ws = None
+
+    def workspace(self, rows):
+        """The launch's per-row words (bnn_mc_score_workspace_bytes), grown when a larger batch comes."""
+        need = _lib.load().bnn_mc_score_workspace_bytes(rows) // 4
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._ws
+
+    def reset(self):
+        self.state.zero_()
+        return self
+
+    def add_(self, vec):
+        """Adds a state vector (what score_f64 returns) -- the CPU path."""
+        self.state += vec.to(self.state.device, torch.float64)
+        return self
+
+    def result(self):
+        """ScoreResult of everything added so far: ONE device-to-host copy, finished in Python float64.  n = 0: NaN ratios."""
+        v = self.state.detach().cpu().tolist()
+        nan = float("nan")
+        div = lambda a, b: a / b if b > 0 else nan         # noqa: E731
+        n = v[0]
+        cb, eb = self.conf_bins, self.ent_bins
+        rel, ece, gaps = [], 0.0, []
+        for b in range(cb):
+            cnt, sc, sk = v[5 + 3 * b:8 + 3 * b]
+            conf, acc = div(sc, cnt), div(sk, cnt)
+            rel.append((cnt, conf, acc))
+            if cnt > 0:
+                gaps.append(abs(acc - conf))
+                ece += cnt / n * gaps[-1]
+        ece, mce = (ece, max(gaps)) if gaps else (nan, nan)
+        rej, cum_n, cum_k = [], 0.0, 0.0
+        for b in range(eb):
+            cnt, sk = v[5 + 3 * cb + 2 * b:7 + 3 * cb + 2 * b]
+            cum_n += cnt
+            cum_k += sk
+            rej.append((div(cum_n, n), div(cum_k, cum_n)))
+        return ScoreResult(n, div(v[4], n), div(v[1], n), div(v[2], n), div(v[3], n), ece, mce, rel, rej)
+
+
+def _score_bins(conf, ent, C, conf_bins, ent_bins):
+    """The launch's bins of fp32 confidences / entropies, in float64: min(conf_bins - 1, floor(confidence conf_bins)),
+    clamp(floor(entropy / ln C ent_bins), 0, ent_bins - 1)."""
+    cbin = torch.floor(conf.to(torch.float64) * conf_bins).clamp_(0, conf_bins - 1).to(torch.int64)
+    ebin = torch.floor(ent.to(torch.float64) * (ent_bins / math.log(C))).clamp_(0, ent_bins - 1).to(torch.int64)
+    return cbin, ebin
+
+
+def score_f64(ys, target, inputs, conf_bins=15, ent_bins=20):
+    """The formulas of mc_score in float64 torch (the CPU path of BayesianNetworkModule.predictive_score): ys (S, *rows, C), the
+    stacked MC outputs; target (*rows) int64.  Returns (PredictiveScore, state vector): the per-row values rounded to float32 at
+    the end, and the float64 vector a ScoreState adds (score_state_size), whose bins and sums are those of the rounded values.
+    logits: log p_s = log_softmax(z_s), nll = -(logsumexp_s log p_s[y] - ln S);  probs: p_s = ys[s] as given, logs of p + 1e-10."""
+    kind = _unc_kind(inputs, "score_f64")
+    nstate = score_state_size(conf_bins, ent_bins)
+    y = ys.detach().to(torch.float64)
+    if y.dim() < 2 or y.shape[-1] < 2:
+        raise ValueError("score_f64: ys must be (S, *rows, classes >= 2), got %s" % (tuple(ys.shape),))
+    S, C = y.shape[0], y.shape[-1]
+    if target.dtype != torch.int64 or tuple(target.shape) != tuple(y.shape[1:-1]):
+        raise ValueError("score_f64: target must be int64 of shape %s, got %s %s" % (tuple(y.shape[1:-1]), target.dtype, tuple(target.shape)))
+    y = y.reshape(S, -1, C)
+    t = target.detach().reshape(-1).to(y.device)
+    ok = (t >= 0) & (t < C)
+    idx = torch.where(ok, t, torch.zeros_like(t)).view(1, -1, 1).expand(S, -1, 1)
+    if kind == _lib.UNC_LOGITS:
+        lp = torch.log_softmax(y, -1)
+        mean = lp.exp().mean(0)
+        lpy = lp.gather(-1, idx).squeeze(-1)                        # (S, rows)
+        nll = -(torch.logsumexp(lpy, 0) - math.log(S))
+        enll = -lpy.mean(0)
+        ent = -torch.xlogy(mean, mean).sum(-1)
+    else:
+        mean = y.mean(0)
+        py = y.gather(-1, idx).squeeze(-1)
+        nll = -torch.log(mean.gather(-1, idx[0]).squeeze(-1) + 1e-10)
+        enll = -torch.log(py + 1e-10).mean(0)
+        ent = -(mean * torch.log(mean + 1e-10)).sum(-1)
+    onehot = torch.zeros_like(mean).scatter_(-1, idx[0], 1.0)
+    brier = ((mean - onehot) ** 2).sum(-1)
+    nan = torch.full_like(nll, float("nan"))
+    nll, enll, brier = (torch.where(ok, v, nan) for v in (nll, enll, brier))
+    mean32 = mean.to(torch.float32)
+    conf = mean32.max(-1).values
+    pred = (mean32 == conf.unsqueeze(-1)).to(torch.int64).argmax(-1)      # the lowest class attaining the maximum
+    f32 = lambda v: v.to(torch.float32)         # noqa: E731
+    rows_shape = tuple(ys.shape[1:-1])
+    out = PredictiveScore(mean32.reshape(rows_shape + (C,)), *(v.reshape(rows_shape) for v in
+                          (f32(nll), f32(enll), f32(brier), conf, pred, f32(ent))))
+    correct = (ok & (pred == t)).to(torch.float64)
+    cbin, ebin = _score_bins(conf, f32(ent), C, conf_bins, ent_bins)
+    vec = torch.zeros(nstate, dtype=torch.float64, device=y.device)
+    vec[0] = t.numel()
+    vec[1], vec[2], vec[3] = (f32(v).to(torch.float64).sum() for v in (nll, enll, brier))
+    vec[4] = correct.sum()
+    one = torch.ones_like(correct)
+    cpart = vec[5:5 + 3 * conf_bins].view(conf_bins, 3)
+    cpart[:, 0].index_add_(0, cbin, one)
+    cpart[:, 1].index_add_(0, cbin, conf.to(torch.float64))
+    cpart[:, 2].index_add_(0, cbin, correct)
+    epart = vec[5 + 3 * conf_bins:].view(ent_bins, 2)
+    epart[:, 0].index_add_(0, ebin, one)
+    epart[:, 1].index_add_(0, ebin, correct)
+    return out, vec
+
+
+def mc_score(y, target, inputs=None, state=None, advance=None):
+    """An MC forward scored against its labels over the leading MC axis in ONE launch (bnn_mc_score) -> PredictiveScore.
+    y: CUDA fp32 (S, *rows, C >= 2), class axis last (made contiguous if it is not), or a HeadPartials (the launch adds the partial
+    logits itself, bit for bit as y.logits() would).  target: CUDA int64 (*rows); a value outside [0, C) makes its row's nll,
+    expected_nll and brier NaN (checked on the device: no host synchronisation, no ignore_index).
+    inputs: 'logits' (p_s = softmax) or 'probs' (p_s as given) -- required.
+    state: a ScoreState on y's device; a second one-workgroup launch adds this batch to it (sums, reliability and rejection
+    histograms), so one state carries a whole test set and ScoreState.result() is the only host copy.
+    advance: as mc_mean (the device epoch bumped in the same launch).  Bitwise reproducible; graph-capturable."""
+    kind = _unc_kind(inputs, "mc_score")
+    if isinstance(y, HeadPartials):
+        yy = y.p
+        require_cuda_f32(yy, "y")
+        nparts, S, M, C = yy.shape
+        rows_shape = (M,)
+    else:
+        if not y.is_cuda:
+            raise BnnHipError("y must be a CUDA/HIP tensor")
+        if y.dtype != torch.float32:
+            raise BnnHipError("y must be float32, got %s" % y.dtype)
+        if y.dim() < 2:
+            raise BnnHipError("mc_score: y must be (S, *rows, classes), got %s" % (tuple(y.shape),))
+        yy = y.detach().contiguous()
+        nparts, S, C = 1, yy.shape[0], yy.shape[-1]
+        rows_shape = tuple(yy.shape[1:-1])
+    dev = yy.device
+    if not isinstance(target, torch.Tensor) or not target.is_cuda or target.device != dev:
+        raise BnnHipError("mc_score: target must be a CUDA/HIP tensor on y's device")
+    if target.dtype != torch.int64 or tuple(target.shape) != rows_shape:
+        raise BnnHipError("mc_score: target must be int64 of shape %s, got %s %s" % (rows_shape, target.dtype, tuple(target.shape)))
+    tt = target.detach().contiguous()
+    rows = 1
+    for d in rows_shape:
+        rows *= d
+    sp, cb, eb, ws = None, 0, 0, None
+    if state is not None:
+        if not isinstance(state, ScoreState) or state.device.type != "cuda" or state.state.device != dev:
+            raise BnnHipError("mc_score: state must be a ScoreState on y's device")
+        if rows > 0:
+            sp, cb, eb, ws = ptr(state.state), state.conf_bins, state.ent_bins, ptr(state.workspace(rows))
+    mean = torch.empty(rows_shape + (C,), dtype=torch.float32, device=dev)
+    nll, enll, brier, conf, ent = (torch.empty(rows_shape, dtype=torch.float32, device=dev) for _ in range(5))
+    pred = torch.empty(rows_shape, dtype=torch.int64, device=dev)
+    adv = ptr(advance) if advance is not None else None
+    check(_lib.load().bnn_mc_score(ptr(yy), rows * C, nparts, S, rows, C, kind, ptr(tt), ptr(mean), ptr(nll), ptr(enll), ptr(brier),
+                                   ptr(conf), ptr(pred), ptr(ent), sp, cb, eb, ws, adv, 1, stream_ptr(dev)), "bnn_mc_score")
+    return PredictiveScore(mean, nll, enll, brier, conf, pred, ent)
+
+
 # --------------------------------------------------------------------------- predictive regression
-PredictiveRegression = collections.namedtuple("PredictiveRegression", ("mean", "total", "aleatoric", "epistemic"))
+PredictiveRegression =collections.namedtuple("PredictiveRegression", ("mean", "total", "aleatoric", "epistemic"))
 PredictiveRegression.__doc__ = """What mc_regression returns, all (*rows, D): mean, the mean of the per-sample means; aleatoric, the
 mean of the per-sample variances; epistemic, the (population) variance of the per-sample means; total = aleatoric + epistemic, the
 variance of the equal-weight mixture of the per-sample predictives (law of total variance)."""

@@ -830,6 +830,49 @@ int bnn_mc_uncertainty(const float *y, int64_t addend_stride, int nparts, int ns
                        const bnn_kl_tensor_t *kl_tensors, int kl_ntensors, float kl_n_batches,
                        float *kl_out, const void *kl_workspace, void *stream);
 
+/* ---- K14: an MC forward scored against its labels ----------------------------------
+ * Per row, in ONE launch: the predictive mean, the negative log-likelihood of the MC predictive, the expected per-sample NLL,
+ * the Brier score, the confidence, the prediction and the entropy; with a `state`, a second one-workgroup launch adds the
+ * batch to a device accumulator that carries a whole test set (sums, reliability and rejection histograms).
+ * replaces  the per-batch stack / mean / argmax / compare / host sum of examples/MNIST/prune.py:52-65
+ *   y, addend_stride, nparts, nsamples, rows, classes, kind: as bnn_mc_uncertainty (a fused head's partials are first summed
+ *   over the parts in bnn_mc_sum's order), but classes >= 2.  target: rows int64 labels.  With p_s the per-sample
+ *   probabilities and m = (1/S) sum_s p_s, every output may be NULL and is then not written; fp32 except `prediction`:
+ *   mean (rows x classes)  m: the bits bnn_mc_uncertainty writes as `mean`
+ *   nll[r]           -ln m[y_r].  LOGITS: -(logsumexp_s(z_s[y] - lse(z_s)) - ln S), formed in the log domain: finite and
+ *                    accurate where p_s[y] underflows fp32 (+inf only where no sample gives the label any mass).
+ *                    PROBS: -ln(m[y] + 1e-10), the convention of Entropy (nn/loss.py).
+ *   expected_nll[r]  -(1/S) sum_s ln p_s[y_r], the data term of the ELBO.  LOGITS: exact, each term ln(sum e) - (z[y] - max) as
+ *                    bnn_softmax_xent forms its row loss.  PROBS: ln(p + 1e-10).
+ *   brier[r]         sum_c (m[c] - [c = y_r])^2
+ *   confidence[r]    max_c mean[r, c] (of the fp32 values written);  prediction[r] (int64): the lowest c attaining it.  The
+ *                    row is correct where prediction == target.
+ *   entropy[r]       H(m): the bits bnn_mc_uncertainty writes as `total` for the same kind.
+ *   A target outside [0, classes) -- compared as int64 before any narrowing; there is no ignore_index -- makes that row's
+ *   nll, expected_nll and brier NaN and the row not correct; nothing outside the row is read or changed, every other row keeps
+ *   its bits, and no host synchronisation is involved.
+ *   Per-sample terms fp32, sums over samples fp64 in a fixed order, no float atomics: bitwise reproducible.
+ * state (may be NULL; bnn_mc_score_state_doubles(conf_bins, ent_bins) = 5 + 3 conf_bins + 2 ent_bins doubles, zeroed by the
+ * caller once): the launch ADDS this batch --
+ *   [n, sum nll, sum expected_nll, sum brier, sum correct], then per confidence bin (count, sum confidence, sum correct), then
+ *   per entropy bin (count, sum correct).  Equal-width bins of the fp32 values written: confidence bin = min(conf_bins - 1,
+ *   floor(confidence conf_bins)), entropy bin = clamp(floor(entropy / ln(classes) ent_bins), 0, ent_bins - 1);
+ *   1 <= conf_bins, ent_bins <= 128.  An invalid target makes the three sums NaN; the row still counts in n and in its bins.
+ *   The main launch leaves five words per row in `workspace` (bnn_mc_score_workspace_bytes(rows) = 20 rows bytes, 4-B aligned;
+ *   required with a state) and one workgroup adds them in a fixed order: the counts are integers, the confidence sums 2^-31
+ *   fixed point (confidences clamped to [0, 2] for the sum; within 2^-32 per row), the three other sums fp64.  Bitwise
+ *   reproducible.  That pass reads 20 bytes per row through one workgroup: sized for evaluation batches.
+ * advance_epoch (may be NULL) += advance_inc in the main launch, as in bnn_mc_uncertainty; there is no KL tail.
+ * Launches: one without a state, two with it.  Errors (nothing launched): BNN_E_NULL (y, target; workspace with a state),
+ * BNN_E_SHAPE / BNN_E_RANGE (extents as bnn_mc_uncertainty, classes < 2, bins outside 1 .. 128), BNN_E_ALIGN. */
+int64_t bnn_mc_score_state_doubles(int conf_bins, int ent_bins);       /* 0 for bins outside 1 .. 128 */
+int64_t bnn_mc_score_workspace_bytes(int64_t rows);                    /* 0 for rows outside 1 .. 2^31 - 1 */
+int bnn_mc_score(const float *y, int64_t addend_stride, int nparts, int nsamples, int64_t rows, int classes,
+                 int kind /* BNN_UNC_LOGITS 0 | BNN_UNC_PROBS 1 */, const int64_t *target,
+                 float *mean, float *nll, float *expected_nll, float *brier, float *confidence, int64_t *prediction,
+                 float *entropy, double *state /* may be NULL */, int conf_bins, int ent_bins, void *workspace,
+                 uint32_t *advance_epoch, uint32_t advance_inc, void *stream);
+
 /* ---- K12: the regression tail of an MC forward -------------------------------------
  * Predictive mean and variance decomposition of S stacked regression outputs in ONE launch: the moments of the equal-weight
  * mixture of the S per-sample predictives (law of total variance).
