@@ -25,8 +25,9 @@
 // bnn_mc_evidential: the moments of the equal-weight mixture of S NIG heads over a leading MC axis (law of total variance), with
 // a_s = beta / (alpha - 1), e_s = a_s / upsilon in fp32 exactly as the module computes them:
 //   mean = (1/S) sum gamma_s,  aleatoric = (1/S) sum a_s,  epistemic = (1/S) sum e_s + Var_s(gamma_s),  total = their sum.
-// Var_s(gamma_s) as in bnn_mc_regression: on gamma_s - gamma_0, fp64, clamped at 0; and its two work splits (narrow: lane =
-// (row, sample), G lanes a row, a fixed xor tree; wide: a lane owns 4-quantity chunks over all samples in order).
+// Var_s(gamma_s) as in bnn_mc_regression: on gamma_s - gamma_0, fp64, clamped at 0; the two work splits and their launch shapes
+// are bnn_mc_parts.hpp's (narrow: lane = (row, sample), G lanes a row, a fixed xor tree; wide: a lane owns 4-quantity chunks
+// over all samples in order).
 #include "bnn_mc_parts.hpp"
 
 namespace bnn {
@@ -123,8 +124,6 @@ static int nig_head_check(const char *who, int64_t rows, int D)
     if (rows > 0x7FFFFFFF) { set_error("%s: more than 2^31 - 1 rows", who); return BNN_E_RANGE; }
     return BNN_OK;
 }
-
-static bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ---------------------------------------------------------------------------------------------- the loss
 constexpr int kNigLossMaxBlocks = 1024;     // workgroups per launch = fp64 partials in the workspace (grid-stride above)
@@ -229,16 +228,14 @@ __device__ __forceinline__ void evi_acc(float g, float ref, float u, float a, fl
     s.se += (double)ep;
 }
 
-struct EviOut { float mean, total, ale, epi; };
-
-__device__ __forceinline__ EviOut evi_finish(float ref, const EviSums &s, double inv_S)
+__device__ __forceinline__ Moments evi_finish(float ref, const EviSums &s, double inv_S)
 {
     const double md = s.sd * inv_S;
     double var = __builtin_fma(-md, md, s.sd2 * inv_S);
     var = var > 0.0 ? var : 0.0;
     const double ale = s.sa * inv_S;
     const double epi = s.se * inv_S + var;
-    EviOut o;
+    Moments o;
     o.mean = (float)((double)ref + md);
     o.total = (float)(ale + epi);
     o.ale = (float)ale;
@@ -250,21 +247,20 @@ __device__ __forceinline__ EviOut evi_finish(float ref, const EviSums &s, double
 template <int NV>
 __global__ __launch_bounds__(kUncThreads) void k_evi_narrow(EviArgs A, int glog, int rpb)
 {
-    const int G = 1 << glog, sl = (int)threadIdx.x & (G - 1);
-    const int lr = (int)threadIdx.x >> glog;
+    const NarrowLane L(glog, rpb);
+    const int G = L.G, sl = L.sl;
     const int D = A.D, S = A.nsamples;
     const double inv_S = 1.0 / (double)S;
     for (int64_t rb = blockIdx.x; rb * rpb < A.rows; rb += gridDim.x) {
-        const int64_t r = rb * rpb + lr;
-        const bool live = lr < rpb && r < A.rows;
+        const int64_t r = rb * rpb + L.lr;
+        const bool live = L.live(r, A.rows);
         const bool work = live && sl < S;
         // sample 0's gamma: lane sl == 0 of the group loads it; every lane of the wave takes part in the shuffle
         float ref[NV];
-        const int lead = ((int)threadIdx.x & 63) & ~(G - 1);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const float g0 = (live && sl == 0 && i < D) ? A.gamma[r * D + i] : 0.f;
-            ref[i] = __shfl(g0, lead, 64);
+            ref[i] = __shfl(g0, L.lead, 64);
         }
         EviSums sum[NV];
 #pragma unroll
@@ -295,13 +291,7 @@ __global__ __launch_bounds__(kUncThreads) void k_evi_narrow(EviArgs A, int glog,
         if (live && sl == 0) {
 #pragma unroll
             for (int i = 0; i < NV; ++i)
-                if (i < D) {
-                    const EviOut o = evi_finish(ref[i], sum[i], inv_S);
-                    A.mean[r * D + i] = o.mean;
-                    A.total[r * D + i] = o.total;
-                    A.aleatoric[r * D + i] = o.ale;
-                    A.epistemic[r * D + i] = o.epi;
-                }
+                if (i < D) store_moments(A, r * D + i, evi_finish(ref[i], sum[i], inv_S));
         }
     }
 }
@@ -320,23 +310,8 @@ __global__ __launch_bounds__(kUncThreads) void k_evi_wide(EviArgs A)
         const int64_t r = rb * RPB + (int)threadIdx.x / TPR;
         if (r >= A.rows) continue;
         const int64_t o0 = r * D;
-        // PAD: what a slot outside the row holds (a finite head: aleatoric 0)
-        auto load4 = [&](const float *q, float pad, float (&v)[NV]) {
-            if (A.vec) {
-#pragma unroll
-                for (int k = 0; k < NCH; ++k) {
-                    const int c = 4 * (t + k * TPR);
-                    const float4 f = c < D ? *reinterpret_cast<const float4 *>(q + c) : make_float4(pad, pad, pad, pad);
-                    v[4 * k] = f.x; v[4 * k + 1] = f.y; v[4 * k + 2] = f.z; v[4 * k + 3] = f.w;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < NV; ++i) {
-                    const int c = unc_col<TPR>(t, i);
-                    v[i] = c < D ? q[c] : pad;
-                }
-            }
-        };
+        // pad: what a slot outside the row holds (a finite head: aleatoric 0)
+        auto load4 = [&](const float *q, float pad, float (&v)[NV]) { row_load<NV, TPR>(q, D, A.vec, t, pad, v); };
         float ref[NV];
         load4(A.gamma + o0, 0.f, ref);
         EviSums sum[NV];
@@ -354,27 +329,10 @@ __global__ __launch_bounds__(kUncThreads) void k_evi_wide(EviArgs A)
         }
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {
-            const int c = 4 * (t + k * TPR);
-            EviOut o[4];
+            Moments o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = evi_finish(ref[4 * k + j], sum[4 * k + j], inv_S);
-            if (A.vec) {
-                if (c < D) {
-                    *reinterpret_cast<float4 *>(A.mean + o0 + c) = make_float4(o[0].mean, o[1].mean, o[2].mean, o[3].mean);
-                    *reinterpret_cast<float4 *>(A.total + o0 + c) = make_float4(o[0].total, o[1].total, o[2].total, o[3].total);
-                    *reinterpret_cast<float4 *>(A.aleatoric + o0 + c) = make_float4(o[0].ale, o[1].ale, o[2].ale, o[3].ale);
-                    *reinterpret_cast<float4 *>(A.epistemic + o0 + c) = make_float4(o[0].epi, o[1].epi, o[2].epi, o[3].epi);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (c + j < D) {
-                        A.mean[o0 + c + j] = o[j].mean;
-                        A.total[o0 + c + j] = o[j].total;
-                        A.aleatoric[o0 + c + j] = o[j].ale;
-                        A.epistemic[o0 + c + j] = o[j].epi;
-                    }
-            }
+            store_moments4(A, o0, 4 * (t + k * TPR), D, o);
         }
     }
 }
@@ -453,54 +411,35 @@ int bnn_mc_evidential(const float *gamma, const float *upsilon, const float *alp
                       int nsamples, int64_t rows, int D, float *mean, float *total, float *aleatoric, float *epistemic,
                       void *stream)
 {
-    const char *who = "bnn_mc_evidential";
+    const TailNames N{"bnn_mc_evidential", "D above 4096", "sample_stride below rows * D"};
     if (!gamma || !upsilon || !alpha || !beta || !mean || !total || !aleatoric || !epistemic) {
-        set_error("%s: NULL pointer", who);
+        set_error("%s: NULL pointer", N.who);
         return BNN_E_NULL;
     }
-    if (nsamples < 1 || rows < 1 || D < 1) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
-    if (nsamples > 65536) { set_error("%s: more than 65536 samples", who); return BNN_E_RANGE; }
-    if (D > 4096) { set_error("%s: D above 4096", who); return BNN_E_RANGE; }
-    if (rows > 0x7FFFFFFF) { set_error("%s: more than 2^31 - 1 rows", who); return BNN_E_RANGE; }
-    if (nsamples > 1 && sample_stride < rows * D) { set_error("%s: sample_stride below rows * D", who); return BNN_E_SHAPE; }
+    int rc = tail_check_extents(N, 1, nsamples, rows, D);
+    if (!rc) rc = tail_check_stride(N, nsamples, sample_stride, rows, D);
+    if (rc) return rc;
     EviArgs A{};
     A.gamma = gamma; A.upsilon = upsilon; A.alpha = alpha; A.beta = beta;
     A.stride = sample_stride;
     A.rows = rows;
     A.nsamples = nsamples;
     A.D = D;
-    A.vec = D % 4 == 0 && al16(gamma) && al16(upsilon) && al16(alpha) && al16(beta) && al16(mean) && al16(total) &&
-            al16(aleatoric) && al16(epistemic) && (sample_stride % 4 == 0 || nsamples == 1);
+    A.vec = tail_vec(D, nsamples, sample_stride, {gamma, upsilon, alpha, beta, mean, total, aleatoric, epistemic});
     A.mean = mean; A.total = total; A.aleatoric = aleatoric; A.epistemic = epistemic;
     hipStream_t st = (hipStream_t)stream;
-    auto grid = [](int64_t work) { return dim3((unsigned)(work < kUncMaxBlocks ? work : kUncMaxBlocks)); };
     if (D <= kUncNarrow) {
-        int glog = 0;
-        while ((1 << glog) < nsamples && glog < 6) ++glog;
-        // as bnn_mc_regression: below 256 workgroups, fewer rows per workgroup, so that the scattered loads spread over more CUs
-        int rpb = kUncThreads >> glog;
-        while (rpb > 1 && (rows + rpb - 1) / rpb < 256) rpb >>= 1;
-        const dim3 g = grid((rows + rpb - 1) / rpb);
-        if (D == 1) hipLaunchKernelGGL(k_evi_narrow<1>, g, dim3(kUncThreads), 0, st, A, glog, rpb);
-        else if (D <= 4) hipLaunchKernelGGL(k_evi_narrow<4>, g, dim3(kUncThreads), 0, st, A, glog, rpb);
-        else hipLaunchKernelGGL(k_evi_narrow<kUncNarrow>, g, dim3(kUncThreads), 0, st, A, glog, rpb);
-        return check_launch(who);
+        const NarrowPlan P = narrow_plan(nsamples, rows, 0);
+        if (D == 1) hipLaunchKernelGGL(k_evi_narrow<1>, P.grid, dim3(kUncThreads), 0, st, A, P.glog, P.rpb);
+        else if (D <= 4) hipLaunchKernelGGL(k_evi_narrow<4>, P.grid, dim3(kUncThreads), 0, st, A, P.glog, P.rpb);
+        else hipLaunchKernelGGL(k_evi_narrow<kUncNarrow>, P.grid, dim3(kUncThreads), 0, st, A, P.glog, P.rpb);
+        return check_launch(N.who);
     }
-    // wide: a wave per row up to D = 1024, the workgroup per row above; <= 16 quantities per lane either way
-    const int tpr = D <= 1024 ? 64 : 256;
-    const int nch = (D + 4 * tpr - 1) / (4 * tpr);
-    const dim3 g = grid((rows + kUncThreads / tpr - 1) / (kUncThreads / tpr));
-#define EVI_WIDE(T, N) hipLaunchKernelGGL((k_evi_wide<T, N>), g, dim3(kUncThreads), 0, st, A)
-    if (tpr == 64) {
-        if (nch == 1) EVI_WIDE(64, 1);
-        else if (nch == 2) EVI_WIDE(64, 2);
-        else EVI_WIDE(64, 4);
-    } else {
-        if (nch <= 2) EVI_WIDE(256, 2);
-        else EVI_WIDE(256, 4);
-    }
-#undef EVI_WIDE
-    return check_launch(who);
+    const WidePlan P = wide_plan(D, D, rows, 0);
+    wide_dispatch(P, [&](auto T, auto NC) {
+        hipLaunchKernelGGL((k_evi_wide<T.value, NC.value>), P.grid, dim3(kUncThreads), 0, st, A);
+    });
+    return check_launch(N.who);
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@
 // 1e-2: wrong in the 4th - 5th digit even in fp64); shifted, it cancels only (m_0 - mean)^2 / var, a few units for any sample
 // drawn from the same distribution as the rest.  S = 1 gives d = 0: exactly 0.  A negative rounding residue is clamped to 0.
 // All sums over samples are fp64 in a fixed order (lane-strided, then a fixed shuffle tree): no float atomics, bitwise
-// reproducible.  Two work splits, those of bnn_mc_uncertainty:
+// reproducible.  Two work splits, with the launch shapes of bnn_mc_parts.hpp:
 //   narrow (width <= 16: every regression head here): a lane holds one (row, sample)'s values in registers; G lanes share a row
 //           (G = the next power of two >= S, <= 64); sample 0's means reach the group by one shuffle per quantity, the G lanes'
 //           fp64 sums meet in a shuffle tree at the end.
@@ -41,15 +41,13 @@ __device__ __forceinline__ void reg_acc(float m, float ref, float v, double &sd,
     if constexpr (KIND != BNN_REG_VALUES) sv += (double)reg_var<KIND>(v);
 }
 
-struct RegOut { float mean, total, ale, epi; };
-
-__device__ __forceinline__ RegOut reg_finish(float ref, double sd, double sd2, double sv, double inv_S)
+__device__ __forceinline__ Moments reg_finish(float ref, double sd, double sd2, double sv, double inv_S)
 {
     const double md = sd * inv_S;
     double epi = __builtin_fma(-md, md, sd2 * inv_S);
     epi = epi > 0.0 ? epi : 0.0;
     const double ale = sv * inv_S;
-    RegOut o;
+    Moments o;
     o.mean = (float)((double)ref + md);
     o.total = (float)(ale + epi);
     o.ale = (float)ale;
@@ -69,13 +67,13 @@ __global__ __launch_bounds__(kUncThreads) void k_reg_narrow(UncArgs A, int D, in
     constexpr int NV = VAR ? kUncNarrow / 2 : kUncNarrow;
     const int nwork = (int)gridDim.x - has_kl;
     if (unc_tails(nwork, advance_epoch, advance_inc, F, partials, kl_out)) return;
-    const int G = 1 << glog, sl = (int)threadIdx.x & (G - 1);
+    const NarrowLane L(glog, rpb);
+    const int G = L.G, sl = L.sl;
     const int W = A.classes, S = A.nsamples;
-    const int lr = (int)threadIdx.x >> glog;
     const double inv_S = 1.0 / (double)S;
     for (int64_t rb = blockIdx.x; rb * rpb < A.rows; rb += nwork) {
-        const int64_t r = rb * rpb + lr;
-        const bool live = lr < rpb && r < A.rows;
+        const int64_t r = rb * rpb + L.lr;
+        const bool live = L.live(r, A.rows);
         const bool work = live && sl < S;
         const float *row = A.y + r * W;
         float m[NV], v[NV], mn[NV], vn[NV];
@@ -87,19 +85,15 @@ __global__ __launch_bounds__(kUncThreads) void k_reg_narrow(UncArgs A, int D, in
                 parts_sum<NV, 1, 8>(A.nparts, A.part_stride, D, q, 0, a);
                 if constexpr (VAR) parts_sum<NV, 1, 8>(A.nparts, A.part_stride, D, q + D, 0, b);
             } else {
-#pragma unroll
-                for (int i = 0; i < NV; ++i) {
-                    a[i] = i < D ? q[i] : 0.f;
-                    if constexpr (VAR) b[i] = i < D ? q[D + i] : 0.f;
-                }
+                row_load<NV, 1>(q, D, 0, 0, 0.f, a);
+                if constexpr (VAR) row_load<NV, 1>(q + D, D, 0, 0, 0.f, b);
             }
         };
         if (work) load(sl, m, v);
         // sample 0's means: lane sl == 0 of the group holds them (S >= 1); every lane of the wave takes part in the shuffle
         float ref[NV];
-        const int lead = ((int)threadIdx.x & 63) & ~(G - 1);
 #pragma unroll
-        for (int i = 0; i < NV; ++i) ref[i] = __shfl(m[i], lead, 64);
+        for (int i = 0; i < NV; ++i) ref[i] = __shfl(m[i], L.lead, 64);
         double sd[NV], sd2[NV], sv[NV];
 #pragma unroll
         for (int i = 0; i < NV; ++i) sd[i] = sd2[i] = sv[i] = 0.0;
@@ -130,13 +124,7 @@ __global__ __launch_bounds__(kUncThreads) void k_reg_narrow(UncArgs A, int D, in
         if (live && sl == 0) {
 #pragma unroll
             for (int i = 0; i < NV; ++i)
-                if (i < D) {
-                    const RegOut o = reg_finish(ref[i], sd[i], sd2[i], sv[i], inv_S);
-                    A.mean[r * D + i] = o.mean;
-                    A.total[r * D + i] = o.total;
-                    A.aleatoric[r * D + i] = o.ale;
-                    A.epistemic[r * D + i] = o.epi;
-                }
+                if (i < D) store_moments(A, r * D + i, reg_finish(ref[i], sd[i], sd2[i], sv[i], inv_S));
         }
     }
 }
@@ -163,30 +151,14 @@ __global__ __launch_bounds__(kUncThreads) void k_reg_wide(UncArgs A, int D, int 
         float m[NV], v[NV], mn[NV], vn[NV], ref[NV];
 #pragma unroll
         for (int i = 0; i < NV; ++i) v[i] = vn[i] = 0.f;
-        auto load4 = [&](const float *q, float (&a)[NV]) {
-            if (A.vec) {
-#pragma unroll
-                for (int k = 0; k < NCH; ++k) {
-                    const int c = 4 * (t + k * TPR);
-                    const float4 f = c < D ? *reinterpret_cast<const float4 *>(q + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    a[4 * k] = f.x; a[4 * k + 1] = f.y; a[4 * k + 2] = f.z; a[4 * k + 3] = f.w;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < NV; ++i) {
-                    const int c = unc_col<TPR>(t, i);
-                    a[i] = c < D ? q[c] : 0.f;
-                }
-            }
-        };
         auto load = [&](int s, float (&a)[NV], float (&b)[NV]) {
             const float *q = row + (int64_t)s * A.stride;
             if constexpr (FUSED) {
                 parts_sum<NV, TPR, (NV >= 16 ? 2 : 32 / NV)>(A.nparts, A.part_stride, D, q, t, a);
                 if constexpr (VAR) parts_sum<NV, TPR, (NV >= 16 ? 2 : 32 / NV)>(A.nparts, A.part_stride, D, q + D, t, b);
             } else {
-                load4(q, a);
-                if constexpr (VAR) load4(q + D, b);
+                row_load<NV, TPR>(q, D, A.vec, t, 0.f, a);
+                if constexpr (VAR) row_load<NV, TPR>(q + D, D, A.vec, t, 0.f, b);
             }
         };
         double sd[NV], sd2[NV], sv[NV];
@@ -209,27 +181,10 @@ __global__ __launch_bounds__(kUncThreads) void k_reg_wide(UncArgs A, int D, int 
         const int64_t o0 = r * D;
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {
-            const int c = 4 * (t + k * TPR);
-            RegOut o[4];
+            Moments o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = reg_finish(ref[4 * k + j], sd[4 * k + j], sd2[4 * k + j], sv[4 * k + j], inv_S);
-            if (A.vec) {
-                if (c < D) {
-                    *reinterpret_cast<float4 *>(A.mean + o0 + c) = make_float4(o[0].mean, o[1].mean, o[2].mean, o[3].mean);
-                    *reinterpret_cast<float4 *>(A.total + o0 + c) = make_float4(o[0].total, o[1].total, o[2].total, o[3].total);
-                    *reinterpret_cast<float4 *>(A.aleatoric + o0 + c) = make_float4(o[0].ale, o[1].ale, o[2].ale, o[3].ale);
-                    *reinterpret_cast<float4 *>(A.epistemic + o0 + c) = make_float4(o[0].epi, o[1].epi, o[2].epi, o[3].epi);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (c + j < D) {
-                        A.mean[o0 + c + j] = o[j].mean;
-                        A.total[o0 + c + j] = o[j].total;
-                        A.aleatoric[o0 + c + j] = o[j].ale;
-                        A.epistemic[o0 + c + j] = o[j].epi;
-                    }
-            }
+            store_moments4(A, o0, 4 * (t + k * TPR), D, o);
         }
     }
 }
@@ -325,96 +280,47 @@ int bnn_mc_regression(const float *y, int64_t addend_stride, int nparts, int nsa
                       uint32_t advance_inc, const bnn_kl_tensor_t *kl_tensors, int kl_ntensors, float kl_n_batches,
                       float *kl_out, const void *kl_workspace, void *stream)
 {
-    const char *who = "bnn_mc_regression";
-    if (!y || !mean || !total || !aleatoric || !epistemic) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
-    if (nparts < 1 || nsamples < 1 || rows < 1 || width < 1) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
-    if (nsamples > 65536) { set_error("%s: more than 65536 samples", who); return BNN_E_RANGE; }
-    if (width > 4096) { set_error("%s: width above 4096", who); return BNN_E_RANGE; }
-    if (rows > 0x7FFFFFFF) { set_error("%s: more than 2^31 - 1 rows", who); return BNN_E_RANGE; }
+    const TailNames N{"bnn_mc_regression", "width above 4096", "addend_stride below rows * width"};
+    if (!y || !mean || !total || !aleatoric || !epistemic) { set_error("%s: NULL pointer", N.who); return BNN_E_NULL; }
+    int rc = tail_check_extents(N, nparts, nsamples, rows, width);
+    if (rc) return rc;
     if (kind != BNN_REG_VALUES && kind != BNN_REG_MEAN_LOGVAR && kind != BNN_REG_MEAN_VAR) {
-        set_error("%s: unknown kind %d", who, kind);
+        set_error("%s: unknown kind %d", N.who, kind);
         return BNN_E_RANGE;
     }
-    if (kind != BNN_REG_VALUES && width % 2) { set_error("%s: odd width %d for a (mean, variance) layout", who, width); return BNN_E_SHAPE; }
-    if ((int64_t)nparts * nsamples > 1 && addend_stride < rows * width) {
-        set_error("%s: addend_stride below rows * width", who);
-        return BNN_E_SHAPE;
-    }
+    if (kind != BNN_REG_VALUES && width % 2) { set_error("%s: odd width %d for a (mean, variance) layout", N.who, width); return BNN_E_SHAPE; }
+    const int64_t naddends = (int64_t)nparts * nsamples;
+    rc = tail_check_stride(N, naddends, addend_stride, rows, width);
+    if (rc) return rc;
     KlFinal F{};
     const int has_kl = kl_tensors != nullptr;
     if (has_kl) {
-        const int rc = kl_final_plan(kl_tensors, kl_ntensors, kl_n_batches, kl_out, kl_workspace, F, who);
+        rc = kl_final_plan(kl_tensors, kl_ntensors, kl_n_batches, kl_out, kl_workspace, F, N.who);
         if (rc) return rc;
     }
     const int D = kind == BNN_REG_VALUES ? width : width / 2;
-    auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    UncArgs A{};
-    A.y = y;
-    A.stride = addend_stride;
-    A.part_stride = (int64_t)nsamples * addend_stride;
-    A.rows = rows;
-    A.nparts = nparts;
-    A.nsamples = nsamples;
-    A.classes = width;
     // 16-B loads of both halves and 16-B stores of every output: D % 4 == 0 (then width % 4 == 0 as well)
-    A.vec = D % 4 == 0 && al16(y) && al16(mean) && al16(total) && al16(aleatoric) && al16(epistemic) &&
-            (addend_stride % 4 == 0 || (int64_t)nparts * nsamples == 1);
-    A.mean = mean; A.total = total; A.aleatoric = aleatoric; A.epistemic = epistemic;
-    const bool fused = nparts > 1;
+    const int vec = tail_vec(D, naddends, addend_stride, {y, mean, total, aleatoric, epistemic});
+    const UncArgs A = unc_args(y, addend_stride, nparts, nsamples, rows, width, vec, mean, total, aleatoric, epistemic);
     const double *ws = reinterpret_cast<const double *>(kl_workspace);
     hipStream_t st = (hipStream_t)stream;
-    auto grid = [&](int64_t work) { return dim3((unsigned)((work < kUncMaxBlocks ? work : kUncMaxBlocks) + has_kl)); };
-#define REG_KINDS(LAUNCH)                                                                                  \
-    do {                                                                                                   \
-        if (kind == BNN_REG_VALUES) { if (fused) LAUNCH(BNN_REG_VALUES, true); else LAUNCH(BNN_REG_VALUES, false); } \
-        else if (kind == BNN_REG_MEAN_LOGVAR) { if (fused) LAUNCH(BNN_REG_MEAN_LOGVAR, true); else LAUNCH(BNN_REG_MEAN_LOGVAR, false); } \
-        else { if (fused) LAUNCH(BNN_REG_MEAN_VAR, true); else LAUNCH(BNN_REG_MEAN_VAR, false); }          \
-    } while (0)
     if (width <= kUncNarrow) {
-        int glog = 0;
-        while ((1 << glog) < nsamples && glog < 6) ++glog;
-        // as bnn_mc_uncertainty: below 256 workgroups, fewer rows per workgroup, so that the scattered loads spread over more CUs
-        int rpb = kUncThreads >> glog;
-        while (rpb > 1 && (rows + rpb - 1) / rpb < 256) rpb >>= 1;
-        const dim3 g = grid((rows + rpb - 1) / rpb);
-#define REG_NARROW(K, FU) hipLaunchKernelGGL((k_reg_narrow<K, FU>), g, dim3(kUncThreads), 0, st, A, D, glog, rpb, has_kl, advance_epoch, \
-                                             advance_inc, F, ws, kl_out)
-        REG_KINDS(REG_NARROW);
-#undef REG_NARROW
-        return check_launch(who);
+        const NarrowPlan P = narrow_plan(nsamples, rows, has_kl);
+        kind_dispatch<BNN_REG_VALUES, BNN_REG_MEAN_LOGVAR, BNN_REG_MEAN_VAR>(kind, nparts > 1, [&](auto K, auto FU) {
+            hipLaunchKernelGGL((k_reg_narrow<K.value, FU.value>), P.grid, dim3(kUncThreads), 0, st, A, D, P.glog, P.rpb, has_kl,
+                               advance_epoch, advance_inc, F, ws, kl_out);
+        });
+        return check_launch(N.who);
     }
-    // wide: a wave per row up to width 1024, the workgroup per row above; <= 16 quantities per lane either way
-    const int tpr = width <= 1024 ? 64 : 256;
-    const int nch = (D + 4 * tpr - 1) / (4 * tpr);
-    const dim3 g = grid((rows + kUncThreads / tpr - 1) / (kUncThreads / tpr));
-#define REG_WIDE(K, FU, T, N) hipLaunchKernelGGL((k_reg_wide<K, FU, T, N>), g, dim3(kUncThreads), 0, st, A, D, has_kl, advance_epoch, \
-                                                 advance_inc, F, ws, kl_out)
-// (VALUES: D = width, up to 4 chunks per thread; the (mean, variance) layouts: D = width / 2, at most 2)
-#define REG_WIDE_V(K, FU)                                                            \
-    do {                                                                             \
-        if (tpr == 64) {                                                             \
-            if (nch == 1) REG_WIDE(K, FU, 64, 1);                                    \
-            else if (nch == 2) REG_WIDE(K, FU, 64, 2);                               \
-            else REG_WIDE(K, FU, 64, 4);                                             \
-        } else {                                                                     \
-            if (nch <= 2) REG_WIDE(K, FU, 256, 2);                                   \
-            else REG_WIDE(K, FU, 256, 4);                                            \
-        }                                                                            \
-    } while (0)
-#define REG_WIDE_P(K, FU)                                                            \
-    do {                                                                             \
-        if (tpr == 256) REG_WIDE(K, FU, 256, 2);                                     \
-        else if (nch == 1) REG_WIDE(K, FU, 64, 1);                                   \
-        else REG_WIDE(K, FU, 64, 2);                                                 \
-    } while (0)
-    if (kind == BNN_REG_VALUES) { if (fused) REG_WIDE_V(BNN_REG_VALUES, true); else REG_WIDE_V(BNN_REG_VALUES, false); }
-    else if (kind == BNN_REG_MEAN_LOGVAR) { if (fused) REG_WIDE_P(BNN_REG_MEAN_LOGVAR, true); else REG_WIDE_P(BNN_REG_MEAN_LOGVAR, false); }
-    else { if (fused) REG_WIDE_P(BNN_REG_MEAN_VAR, true); else REG_WIDE_P(BNN_REG_MEAN_VAR, false); }
-#undef REG_WIDE_V
-#undef REG_WIDE_P
-#undef REG_WIDE
-#undef REG_KINDS
-    return check_launch(who);
+    const WidePlan P = wide_plan(width, D, rows, has_kl);
+    kind_dispatch<BNN_REG_VALUES, BNN_REG_MEAN_LOGVAR, BNN_REG_MEAN_VAR>(kind, nparts > 1, [&](auto K, auto FU) {
+        // VALUES: D = width, up to 4 chunks per thread; the (mean, variance) layouts: D = width / 2, at most 2
+        wide_dispatch<(K.value == BNN_REG_VALUES ? 4 : 2)>(P, [&](auto T, auto NC) {
+            hipLaunchKernelGGL((k_reg_wide<K.value, FU.value, T.value, NC.value>), P.grid, dim3(kUncThreads), 0, st, A, D, has_kl,
+                               advance_epoch, advance_inc, F, ws, kl_out);
+        });
+    });
+    return check_launch(N.who);
 }
 
 int64_t bnn_gaussian_nll_workspace_bytes(int64_t nsamples, int64_t rows, int width)

@@ -114,14 +114,14 @@ __global__ __launch_bounds__(kUncThreads) void k_score_narrow(ScoreArgs A, int g
                                                               uint32_t advance_inc)
 {
     constexpr int NV = kUncNarrow;
-    if (advance_epoch && blockIdx.x == 0 && threadIdx.x == 0) advance_epoch[0] += advance_inc;
+    unc_advance(advance_epoch, advance_inc);
     const int nwork = (int)gridDim.x;
-    const int G = 1 << glog, sl = (int)threadIdx.x & (G - 1);
+    const NarrowLane lane(glog, rpb);
+    const int G = lane.G, sl = lane.sl;
     const int C = A.u.classes, S = A.u.nsamples;
-    const int lr = (int)threadIdx.x >> glog;
     for (int64_t rb = blockIdx.x; rb * rpb < A.u.rows; rb += nwork) {
-        const int64_t r = rb * rpb + lr;
-        const bool live = lr < rpb && r < A.u.rows;
+        const int64_t r = rb * rpb + lane.lr;
+        const bool live = lane.live(r, A.u.rows);
         double acc[NV];
 #pragma unroll
         for (int i = 0; i < NV; ++i) acc[i] = 0.0;
@@ -137,8 +137,7 @@ __global__ __launch_bounds__(kUncThreads) void k_score_narrow(ScoreArgs A, int g
                 if constexpr (FUSED) {
                     parts_sum<NV, 1, 8>(A.u.nparts, A.u.part_stride, A.u.classes, row + (int64_t)s * A.u.stride, 0, v);
                 } else {
-#pragma unroll
-                    for (int i = 0; i < NV; ++i) v[i] = i < C ? row[(int64_t)s * A.u.stride + i] : 0.f;
+                    row_load<NV, 1>(row + (int64_t)s * A.u.stride, C, 0, 0, 0.f, v);
                 }
             };
             load(sl, z);
@@ -254,7 +253,7 @@ __global__ __launch_bounds__(kUncThreads, FUSED ? 1 : 4) void k_score_wide(Score
     __shared__ double red_y[8];
     __shared__ float red_av[4];
     __shared__ int red_ac[4];
-    if (advance_epoch && blockIdx.x == 0 && threadIdx.x == 0) advance_epoch[0] += advance_inc;
+    unc_advance(advance_epoch, advance_inc);
     const int nwork = (int)gridDim.x;
     const int t = (int)threadIdx.x % TPR;
     const int C = A.u.classes, S = A.u.nsamples;
@@ -280,6 +279,8 @@ __global__ __launch_bounds__(kUncThreads, FUSED ? 1 : 4) void k_score_wide(Score
                 vy = one[0];
             } else {
                 vy = q[yc];
+                // row_load's body, written out: through the helper <LOGITS, false, 64, 2> and <PROBS, false, 64, 2> come out with
+                // other register counts (88 -> 87, 77 -> 76), and this launch's timings were taken on the code as it is
                 if (A.u.vec) {
 #pragma unroll
                     for (int k = 0; k < NCH; ++k) {
@@ -486,18 +487,16 @@ int bnn_mc_score(const float *y, int64_t addend_stride, int nparts, int nsamples
                  int64_t *prediction, float *entropy, double *state, int conf_bins, int ent_bins, void *workspace,
                  uint32_t *advance_epoch, uint32_t advance_inc, void *stream)
 {
-    const char *who = "bnn_mc_score";
+    const TailNames N{"bnn_mc_score", "more than 4096 classes", "addend_stride below rows * classes"};
+    const char *who = N.who;
     if (!y || !target) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
-    if (nparts < 1 || nsamples < 1 || rows < 1 || classes < 1) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
+    int rc = tail_check_extents(N, nparts, nsamples, rows, classes);
+    if (rc) return rc;
     if (classes < 2) { set_error("%s: fewer than 2 classes (the entropy is normalised by ln C)", who); return BNN_E_RANGE; }
-    if (nsamples > 65536) { set_error("%s: more than 65536 samples", who); return BNN_E_RANGE; }
-    if (classes > 4096) { set_error("%s: more than 4096 classes", who); return BNN_E_RANGE; }
-    if (rows > 0x7FFFFFFF) { set_error("%s: more than 2^31 - 1 rows", who); return BNN_E_RANGE; }
     if (kind != BNN_UNC_LOGITS && kind != BNN_UNC_PROBS) { set_error("%s: unknown kind %d", who, kind); return BNN_E_RANGE; }
-    if ((int64_t)nparts * nsamples > 1 && addend_stride < rows * classes) {
-        set_error("%s: addend_stride below rows * classes", who);
-        return BNN_E_SHAPE;
-    }
+    const int64_t naddends = (int64_t)nparts * nsamples;
+    rc = tail_check_stride(N, naddends, addend_stride, rows, classes);
+    if (rc) return rc;
     if (state) {
         if (conf_bins < 1 || ent_bins < 1) { set_error("%s: fewer than 1 bin", who); return BNN_E_SHAPE; }
         if (conf_bins > kScoreMaxBins || ent_bins > kScoreMaxBins) { set_error("%s: more than %d bins", who, kScoreMaxBins); return BNN_E_RANGE; }
@@ -508,16 +507,8 @@ int bnn_mc_score(const float *y, int64_t addend_stride, int nparts, int nsamples
         }
     }
     ScoreArgs A{};
-    A.u.y = y;
-    A.u.stride = addend_stride;
-    A.u.part_stride = (int64_t)nsamples * addend_stride;
-    A.u.rows = rows;
-    A.u.nparts = nparts;
-    A.u.nsamples = nsamples;
-    A.u.classes = classes;
-    A.u.vec = classes % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15u) == 0 && (reinterpret_cast<uintptr_t>(mean) & 15u) == 0 &&
-              (addend_stride % 4 == 0 || (int64_t)nparts * nsamples == 1);
-    A.u.mean = mean;
+    A.u = unc_args(y, addend_stride, nparts, nsamples, rows, classes, tail_vec(classes, naddends, addend_stride, {y, mean}),
+                   mean, nullptr, nullptr, nullptr);
     A.target = target;
     A.nll = nll; A.expected_nll = expected_nll; A.brier = brier; A.confidence = confidence; A.entropy = entropy;
     A.prediction = prediction;
@@ -525,42 +516,23 @@ int bnn_mc_score(const float *y, int64_t addend_stride, int nparts, int nsamples
     A.conf_bins = conf_bins;
     A.ent_bins = ent_bins;
     A.ent_scale = state ? (double)ent_bins / log((double)classes) : 0.0;
-    const bool fused = nparts > 1;
     hipStream_t st = (hipStream_t)stream;
-    auto grid = [&](int64_t work) { return dim3((unsigned)(work < kUncMaxBlocks ? work : kUncMaxBlocks)); };
     if (classes <= kUncNarrow) {
-        // bnn_mc_uncertainty's launch shape
-        int glog = 0;
-        while ((1 << glog) < nsamples && glog < 6) ++glog;
-        int rpb = kUncThreads >> glog;
-        while (rpb > 1 && (rows + rpb - 1) / rpb < 256) rpb >>= 1;
-        const dim3 g = grid((rows + rpb - 1) / rpb);
-#define SCORE_NARROW(K, FU) hipLaunchKernelGGL((k_score_narrow<K, FU>), g, dim3(kUncThreads), 0, st, A, glog, rpb, advance_epoch, advance_inc)
-        if (kind == BNN_UNC_LOGITS) { if (fused) SCORE_NARROW(BNN_UNC_LOGITS, true); else SCORE_NARROW(BNN_UNC_LOGITS, false); }
-        else { if (fused) SCORE_NARROW(BNN_UNC_PROBS, true); else SCORE_NARROW(BNN_UNC_PROBS, false); }
-#undef SCORE_NARROW
+        const NarrowPlan P = narrow_plan(nsamples, rows, 0);
+        kind_dispatch<BNN_UNC_LOGITS, BNN_UNC_PROBS>(kind, nparts > 1, [&](auto K, auto FU) {
+            hipLaunchKernelGGL((k_score_narrow<K.value, FU.value>), P.grid, dim3(kUncThreads), 0, st, A, P.glog, P.rpb, advance_epoch,
+                               advance_inc);
+        });
     } else {
-        const int tpr = classes <= 1024 ? 64 : 256;
-        const int nch = (classes + 4 * tpr - 1) / (4 * tpr);
-        const dim3 g = grid((rows + kUncThreads / tpr - 1) / (kUncThreads / tpr));
-#define SCORE_WIDE(K, FU, T, N) hipLaunchKernelGGL((k_score_wide<K, FU, T, N>), g, dim3(kUncThreads), 0, st, A, advance_epoch, advance_inc)
-#define SCORE_WIDE_K(K, FU)                                                          \
-    do {                                                                             \
-        if (tpr == 64) {                                                             \
-            if (nch == 1) SCORE_WIDE(K, FU, 64, 1);                                  \
-            else if (nch == 2) SCORE_WIDE(K, FU, 64, 2);                             \
-            else SCORE_WIDE(K, FU, 64, 4);                                           \
-        } else {                                                                     \
-            if (nch <= 2) SCORE_WIDE(K, FU, 256, 2);                                 \
-            else SCORE_WIDE(K, FU, 256, 4);                                          \
-        }                                                                            \
-    } while (0)
-        if (kind == BNN_UNC_LOGITS) { if (fused) SCORE_WIDE_K(BNN_UNC_LOGITS, true); else SCORE_WIDE_K(BNN_UNC_LOGITS, false); }
-        else { if (fused) SCORE_WIDE_K(BNN_UNC_PROBS, true); else SCORE_WIDE_K(BNN_UNC_PROBS, false); }
-#undef SCORE_WIDE_K
-#undef SCORE_WIDE
+        const WidePlan P = wide_plan(classes, classes, rows, 0);
+        kind_dispatch<BNN_UNC_LOGITS, BNN_UNC_PROBS>(kind, nparts > 1, [&](auto K, auto FU) {
+            wide_dispatch(P, [&](auto T, auto NC) {
+                hipLaunchKernelGGL((k_score_wide<K.value, FU.value, T.value, NC.value>), P.grid, dim3(kUncThreads), 0, st, A,
+                                   advance_epoch, advance_inc);
+            });
+        });
     }
-    const int rc = check_launch(who);
+    rc = check_launch(who);
     if (rc || !state) return rc;
     hipLaunchKernelGGL(k_score_accumulate, dim3(1), dim3(kAccThreads), 0, st, reinterpret_cast<const float *>(workspace), rows,
                        conf_bins, ent_bins, state);

@@ -30,12 +30,12 @@ __global__ __launch_bounds__(kUncThreads) void k_unc_narrow(UncArgs A, int glog,
     constexpr int NV = kUncNarrow;
     const int nwork = (int)gridDim.x - has_kl;
     if (unc_tails(nwork, advance_epoch, advance_inc, F, partials, kl_out)) return;
-    const int G = 1 << glog, sl = (int)threadIdx.x & (G - 1);
+    const NarrowLane L(glog, rpb);
+    const int G = L.G, sl = L.sl;
     const int C = A.classes, S = A.nsamples;
-    const int lr = (int)threadIdx.x >> glog;
     for (int64_t rb = blockIdx.x; rb * rpb < A.rows; rb += nwork) {
-        const int64_t r = rb * rpb + lr;
-        const bool live = lr < rpb && r < A.rows;
+        const int64_t r = rb * rpb + L.lr;
+        const bool live = L.live(r, A.rows);
         double acc[NV];
 #pragma unroll
         for (int i = 0; i < NV; ++i) acc[i] = 0.0;
@@ -47,8 +47,7 @@ __global__ __launch_bounds__(kUncThreads) void k_unc_narrow(UncArgs A, int glog,
                 if constexpr (FUSED) {
                     parts_sum<NV, 1, 8>(A.nparts, A.part_stride, A.classes, row + (int64_t)s * A.stride, 0, v);
                 } else {
-#pragma unroll
-                    for (int i = 0; i < NV; ++i) v[i] = i < C ? row[(int64_t)s * A.stride + i] : 0.f;
+                    row_load<NV, 1>(row + (int64_t)s * A.stride, C, 0, 0, 0.f, v);
                 }
             };
             load(sl, z);
@@ -144,6 +143,8 @@ __global__ __launch_bounds__(kUncThreads) void k_unc_wide(UncArgs A, int has_kl,
             if constexpr (FUSED) {
                 parts_sum<NV, TPR, (NV >= 16 ? 2 : 32 / NV)>(A.nparts, A.part_stride, A.classes, q, t, v);
             } else if (A.vec) {
+                // row_load's body, written out: through the helper <LOGITS, false, 256, 2> and <PROBS, false, 64, 2> come out with
+                // other register counts (74 -> 70, 60 -> 59), and this launch's timings were taken on the code as it is
 #pragma unroll
                 for (int k = 0; k < NCH; ++k) {
                     const int c = 4 * (t + k * TPR);
@@ -243,74 +244,40 @@ int bnn_mc_uncertainty(const float *y, int64_t addend_stride, int nparts, int ns
                        uint32_t advance_inc, const bnn_kl_tensor_t *kl_tensors, int kl_ntensors, float kl_n_batches,
                        float *kl_out, const void *kl_workspace, void *stream)
 {
-    if (!y || !mean || !total || !aleatoric || !epistemic) { set_error("bnn_mc_uncertainty: NULL pointer"); return BNN_E_NULL; }
-    if (nparts < 1 || nsamples < 1 || rows < 1 || classes < 1) { set_error("bnn_mc_uncertainty: bad extent"); return BNN_E_SHAPE; }
-    if (nsamples > 65536) { set_error("bnn_mc_uncertainty: more than 65536 samples"); return BNN_E_RANGE; }
-    if (classes > 4096) { set_error("bnn_mc_uncertainty: more than 4096 classes"); return BNN_E_RANGE; }
-    if (rows > 0x7FFFFFFF) { set_error("bnn_mc_uncertainty: more than 2^31 - 1 rows"); return BNN_E_RANGE; }
-    if (kind != BNN_UNC_LOGITS && kind != BNN_UNC_PROBS) { set_error("bnn_mc_uncertainty: unknown kind %d", kind); return BNN_E_RANGE; }
-    if ((int64_t)nparts * nsamples > 1 && addend_stride < rows * classes) {
-        set_error("bnn_mc_uncertainty: addend_stride below rows * classes");
-        return BNN_E_SHAPE;
-    }
+    const TailNames N{"bnn_mc_uncertainty", "more than 4096 classes", "addend_stride below rows * classes"};
+    if (!y || !mean || !total || !aleatoric || !epistemic) { set_error("%s: NULL pointer", N.who); return BNN_E_NULL; }
+    int rc = tail_check_extents(N, nparts, nsamples, rows, classes);
+    if (rc) return rc;
+    if (kind != BNN_UNC_LOGITS && kind != BNN_UNC_PROBS) { set_error("%s: unknown kind %d", N.who, kind); return BNN_E_RANGE; }
+    const int64_t naddends = (int64_t)nparts * nsamples;
+    rc = tail_check_stride(N, naddends, addend_stride, rows, classes);
+    if (rc) return rc;
     KlFinal F{};
     const int has_kl = kl_tensors != nullptr;
     if (has_kl) {
-        const int rc = kl_final_plan(kl_tensors, kl_ntensors, kl_n_batches, kl_out, kl_workspace, F, "bnn_mc_uncertainty");
+        rc = kl_final_plan(kl_tensors, kl_ntensors, kl_n_batches, kl_out, kl_workspace, F, N.who);
         if (rc) return rc;
     }
-    UncArgs A{};
-    A.y = y;
-    A.stride = addend_stride;
-    A.part_stride = (int64_t)nsamples * addend_stride;
-    A.rows = rows;
-    A.nparts = nparts;
-    A.nsamples = nsamples;
-    A.classes = classes;
-    A.vec = classes % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15u) == 0 && (reinterpret_cast<uintptr_t>(mean) & 15u) == 0 &&
-            (addend_stride % 4 == 0 || (int64_t)nparts * nsamples == 1);
-    A.mean = mean; A.total = total; A.aleatoric = aleatoric; A.epistemic = epistemic;
-    const bool fused = nparts > 1;
+    const UncArgs A = unc_args(y, addend_stride, nparts, nsamples, rows, classes, tail_vec(classes, naddends, addend_stride, {y, mean}),
+                               mean, total, aleatoric, epistemic);
     const double *ws = reinterpret_cast<const double *>(kl_workspace);
     hipStream_t st = (hipStream_t)stream;
-    auto grid = [&](int64_t work) { return dim3((unsigned)((work < kUncMaxBlocks ? work : kUncMaxBlocks) + has_kl)); };
     if (classes <= kUncNarrow) {
-        int glog = 0;
-        while ((1 << glog) < nsamples && glog < 6) ++glog;
-        // a workgroup's four waves issue their scattered loads through one CU: below 256 workgroups, fewer rows per workgroup
-        // (the step's tail, 512 rows x 8 samples: 16 workgroups of 32 rows -> 256 of 2)
-        int rpb = kUncThreads >> glog;
-        while (rpb > 1 && (rows + rpb - 1) / rpb < 256) rpb >>= 1;
-        const dim3 g = grid((rows + rpb - 1) / rpb);
-#define UNC_NARROW(K, FU) hipLaunchKernelGGL((k_unc_narrow<K, FU>), g, dim3(kUncThreads), 0, st, A, glog, rpb, has_kl, advance_epoch, \
-                                             advance_inc, F, ws, kl_out)
-        if (kind == BNN_UNC_LOGITS) { if (fused) UNC_NARROW(BNN_UNC_LOGITS, true); else UNC_NARROW(BNN_UNC_LOGITS, false); }
-        else { if (fused) UNC_NARROW(BNN_UNC_PROBS, true); else UNC_NARROW(BNN_UNC_PROBS, false); }
-#undef UNC_NARROW
-        return check_launch("bnn_mc_uncertainty");
+        const NarrowPlan P = narrow_plan(nsamples, rows, has_kl);
+        kind_dispatch<BNN_UNC_LOGITS, BNN_UNC_PROBS>(kind, nparts > 1, [&](auto K, auto FU) {
+            hipLaunchKernelGGL((k_unc_narrow<K.value, FU.value>), P.grid, dim3(kUncThreads), 0, st, A, P.glog, P.rpb, has_kl,
+                               advance_epoch, advance_inc, F, ws, kl_out);
+        });
+        return check_launch(N.who);
     }
-    // wide: a wave per row up to 1024 classes (<= 16 per lane), the workgroup per row above
-    const int tpr = classes <= 1024 ? 64 : 256;
-    const int nch = (classes + 4 * tpr - 1) / (4 * tpr);
-    const dim3 g = grid((rows + kUncThreads / tpr - 1) / (kUncThreads / tpr));
-#define UNC_WIDE(K, FU, T, N) hipLaunchKernelGGL((k_unc_wide<K, FU, T, N>), g, dim3(kUncThreads), 0, st, A, has_kl, advance_epoch, \
-                                                 advance_inc, F, ws, kl_out)
-#define UNC_WIDE_K(K, FU)                                                            \
-    do {                                                                             \
-        if (tpr == 64) {                                                             \
-            if (nch == 1) UNC_WIDE(K, FU, 64, 1);                                    \
-            else if (nch == 2) UNC_WIDE(K, FU, 64, 2);                               \
-            else UNC_WIDE(K, FU, 64, 4);                                             \
-        } else {                                                                     \
-            if (nch <= 2) UNC_WIDE(K, FU, 256, 2);                                   \
-            else UNC_WIDE(K, FU, 256, 4);                                            \
-        }                                                                            \
-    } while (0)
-    if (kind == BNN_UNC_LOGITS) { if (fused) UNC_WIDE_K(BNN_UNC_LOGITS, true); else UNC_WIDE_K(BNN_UNC_LOGITS, false); }
-    else { if (fused) UNC_WIDE_K(BNN_UNC_PROBS, true); else UNC_WIDE_K(BNN_UNC_PROBS, false); }
-#undef UNC_WIDE_K
-#undef UNC_WIDE
-    return check_launch("bnn_mc_uncertainty");
+    const WidePlan P = wide_plan(classes, classes, rows, has_kl);
+    kind_dispatch<BNN_UNC_LOGITS, BNN_UNC_PROBS>(kind, nparts > 1, [&](auto K, auto FU) {
+        wide_dispatch(P, [&](auto T, auto NC) {
+            hipLaunchKernelGGL((k_unc_wide<K.value, FU.value, T.value, NC.value>), P.grid, dim3(kUncThreads), 0, st, A, has_kl,
+                               advance_epoch, advance_inc, F, ws, kl_out);
+        });
+    });
+    return check_launch(N.who);
 }
 
 }  // extern "C"

@@ -116,10 +116,7 @@ class BayesianNetworkModule(Module):
             if advance is not None or kl is not None:
                 raise ops.BnnHipError("predictive_uncertainty: advance / kl are tails of the device launch; x is not on the device")
             return ops.uncertainty_f64(self.forward_stacked(x, samples, sample0, **kwargs), inputs)
-        if self.mc_batched:
-            y = self._forward_batched_stacked(x, samples, sample0, _lazy_head=True, **kwargs)
-        else:
-            y = self.forward_stacked(x, samples, sample0, **kwargs)
+        y = self._mc_outputs(x, samples, sample0, kwargs)
         return ops.mc_uncertainty(y, inputs, advance=advance, kl=kl)
 
     def predictive_score(self, x, target, samples=None, sample0=0, *, inputs, state=None, advance=None, **kwargs):
@@ -147,10 +144,7 @@ class BayesianNetworkModule(Module):
             if state is not None:
                 state.add_(vec)
             return out
-        if self.mc_batched:
-            y = self._forward_batched_stacked(x, samples, sample0, _lazy_head=True, **kwargs)
-        else:
-            y = self.forward_stacked(x, samples, sample0, **kwargs)
+        y = self._mc_outputs(x, samples, sample0, kwargs)
         return ops.mc_score(y, target, inputs, state=state, advance=advance)
 
     def predictive_regression(self, x, samples=None, sample0=0, *, outputs, advance=None, kl=None, **kwargs):
@@ -172,10 +166,7 @@ class BayesianNetworkModule(Module):
             if advance is not None or kl is not None:
                 raise ops.BnnHipError("predictive_regression: advance / kl are tails of the device launch; x is not on the device")
             return ops.regression_f64(self.forward_stacked(x, samples, sample0, **kwargs), outputs)
-        if self.mc_batched:
-            y = self._forward_batched_stacked(x, samples, sample0, _lazy_head=True, **kwargs)
-        else:
-            y = self.forward_stacked(x, samples, sample0, **kwargs)
+        y = self._mc_outputs(x, samples, sample0, kwargs)
         return ops.mc_regression(y, outputs, advance=advance, kl=kl)
 
     def predictive_evidential(self, x, samples=None, sample0=0, **kwargs):
@@ -198,6 +189,13 @@ class BayesianNetworkModule(Module):
         if not (isinstance(x, torch.Tensor) and x.is_cuda):
             return ops.evidential_f64(*ys)
         return ops.mc_evidential(*ys)
+
+    def _mc_outputs(self, x, samples, sample0, kwargs):
+        """What a predictive_* tail launch reads for x on the device: with mc_batched one batched pass whose fused head, if any,
+        hands on its partials (ops.HeadPartials); else the stacked outputs of the serial loop."""
+        if self.mc_batched:
+            return self._forward_batched_stacked(x, samples, sample0, _lazy_head=True, **kwargs)
+        return self.forward_stacked(x, samples, sample0, **kwargs)
 
     def _forward_batched_stacked(self, x, samples, sample0, *args, _lazy_head=False, **kwargs):
         B = x.shape[0]

@@ -8,6 +8,7 @@ torch.bmm / torch's conv backward on the GPU (library GEMMs on already-drawn wei
 Every function here requires CUDA (HIP) tensors and raises BnnHipError otherwise.
 """
 import collections
+import contextlib
 import ctypes
 import math
 import os
@@ -2365,6 +2366,63 @@ def kl_normal_begin(mus, rhos, priors, n_batches=1.0, out=None, carry=False):
     return h
 
 
+def _kl_uncarry(kl):
+    """No later launch may carry `kl`'s first pass (a KlDeferred or None)."""
+    if kl is not None and _tls.kl_carry is kl:
+        _tls.kl_carry = None
+
+
+def _kl_tail_args(kl, who, dev):
+    """The five KL arguments of a launch whose extra workgroup runs the second pass of `kl` (a KlDeferred from kl_normal_begin;
+    None: no such tail).  Refuses a finished one; launches the first pass now if no narrow layer took it along."""
+    if kl is None:
+        return None, 0, 1.0, None, None
+    if kl.done:
+        raise BnnHipError("%s: this KlDeferred has already been finished" % who)
+    if not kl.launched:
+        _kl_uncarry(kl)
+        check(_lib.load().bnn_kl_forward_partial(kl.arr, kl.T, ptr(kl.ws), stream_ptr(dev)), "bnn_kl_forward_partial")
+        kl.launched = True
+    return kl.arr, kl.T, kl.n_batches, ptr(kl.out), ptr(kl.ws)
+
+
+@contextlib.contextmanager
+def _kl_finishing(kl):
+    """Around the checks and the launch that finish `kl` (a KlDeferred or None): done once they succeeded; after a BnnHipError the
+    launch that was to finish it has failed, and nothing may carry it later."""
+    try:
+        yield
+    except BnnHipError:
+        _kl_uncarry(kl)
+        raise
+    if kl is not None:
+        kl.done = True
+
+
+def _mc_input(y, who, noun):
+    """The stacked MC outputs of a tail -> (yy, nparts, S, rows_shape, rows, width): y a CUDA fp32 (S, *rows, width) tensor (made
+    contiguous if it is not), or a HeadPartials, whose (parts, S, M, width) partials the launch adds itself."""
+    if isinstance(y, HeadPartials):
+        yy = y.p
+        require_cuda_f32(yy, "y")
+        nparts, S, M, width = yy.shape
+        rows_shape = (M,)
+    else:
+        if not y.is_cuda:
+            raise BnnHipError("y must be a CUDA/HIP tensor")
+        if y.dtype != torch.float32:
+            raise BnnHipError("y must be float32, got %s" % y.dtype)
+        if y.dim() < 2:
+            raise BnnHipError("%s: y must be (S, *rows, %s), got %s" % (who, noun, tuple(y.shape)))
+        yy = y.detach().contiguous()
+        nparts, S, width = 1, yy.shape[0], yy.shape[-1]
+        rows_shape = tuple(yy.shape[1:-1])
+    rows = 1
+    for d in rows_shape:
+        rows *= d
+    return yy, nparts, S, rows_shape, rows, width
+
+
 # --------------------------------------------------------------------------- MC reduction
 def mc_mean(y, out=None, scale=None, advance=None, kl=None):
     """scale * sum over the leading MC axis (default scale 1/S = torch.stack(preds).mean(0),
@@ -2392,16 +2450,10 @@ def mc_mean(y, out=None, scale=None, advance=None, kl=None):
     sc = (1.0 / S) if scale is None else float(scale)
     adv = ptr(advance) if advance is not None else None
     if kl is not None:
-        # second pass of a KL begun by kl_normal_begin, as one extra workgroup of this launch
-        if kl.done:
-            raise BnnHipError("mc_mean: this KlDeferred has already been finished")
-        if not kl.launched:                         # no narrow layer took it along
-            if _tls.kl_carry is kl:
-                _tls.kl_carry = None
-            check(_lib.load().bnn_kl_forward_partial(kl.arr, kl.T, ptr(kl.ws), stream_ptr(y.device)), "bnn_kl_forward_partial")
-            kl.launched = True
-        check(_lib.load().bnn_mc_sum_kl(ptr(y), n, nadd, n, sc, ptr(out), 0, adv, 1, kl.arr, kl.T, kl.n_batches,
-                                        ptr(kl.out), ptr(kl.ws), stream_ptr(y.device)), "bnn_mc_sum_kl")
+        # second pass of a KL begun by kl_normal_begin, as one extra workgroup of this launch (a failed launch leaves a
+        # carried handle where it is: no _kl_finishing here)
+        check(_lib.load().bnn_mc_sum_kl(ptr(y), n, nadd, n, sc, ptr(out), 0, adv, 1, *_kl_tail_args(kl, "mc_mean", y.device),
+                                        stream_ptr(y.device)), "bnn_mc_sum_kl")
         kl.done = True
         return out
     check(_lib.load().bnn_mc_sum(ptr(y), n, nadd, n, sc, ptr(out), 0, adv, 1, stream_ptr(y.device)), "bnn_mc_sum")
@@ -2422,8 +2474,7 @@ def _unc_kind(inputs, who, kl=None):
     probabilities cannot be told safely from their values) -- and then leaves no KL pending for a later launch to carry."""
     if isinstance(inputs, str) and inputs in _UNC_INPUTS:
         return _UNC_INPUTS[inputs]
-    if kl is not None and _tls.kl_carry is kl:
-        _tls.kl_carry = None
+    _kl_uncarry(kl)
     raise ValueError("%s: inputs must be 'logits' or 'probs', got %r" % (who, inputs))
 
 
@@ -2456,48 +2507,15 @@ def mc_uncertainty(y, inputs=None, advance=None, kl=None):
     advance / kl: as mc_mean (the device epoch bumped, a KlDeferred's second pass run, in the same launch).
     The sums over samples are fp64 in a fixed order: bitwise reproducible."""
     kind = _unc_kind(inputs, "mc_uncertainty", kl)
-    try:
-        if isinstance(y, HeadPartials):
-            yy = y.p
-            require_cuda_f32(yy, "y")
-            nparts, S, M, C = yy.shape
-            rows_shape = (M,)
-        else:
-            if not y.is_cuda:
-                raise BnnHipError("y must be a CUDA/HIP tensor")
-            if y.dtype != torch.float32:
-                raise BnnHipError("y must be float32, got %s" % y.dtype)
-            if y.dim() < 2:
-                raise BnnHipError("mc_uncertainty: y must be (S, *rows, classes), got %s" % (tuple(y.shape),))
-            yy = y.detach().contiguous()
-            nparts, S, C = 1, yy.shape[0], yy.shape[-1]
-            rows_shape = tuple(yy.shape[1:-1])
-        rows = 1
-        for d in rows_shape:
-            rows *= d
+    with _kl_finishing(kl):
+        yy, nparts, S, rows_shape, rows, C = _mc_input(y, "mc_uncertainty", "classes")
         dev = yy.device
         mean = torch.empty(rows_shape + (C,), dtype=torch.float32, device=dev)
         total, ale, epi = (torch.empty(rows_shape, dtype=torch.float32, device=dev) for _ in range(3))
         adv = ptr(advance) if advance is not None else None
-        karr, kT, kn, kout, kws = None, 0, 1.0, None, None
-        if kl is not None:
-            # second pass of a KL begun by kl_normal_begin, as one extra workgroup of this launch (as in mc_mean)
-            if kl.done:
-                raise BnnHipError("mc_uncertainty: this KlDeferred has already been finished")
-            if not kl.launched:                     # no narrow layer took it along
-                if _tls.kl_carry is kl:
-                    _tls.kl_carry = None
-                check(_lib.load().bnn_kl_forward_partial(kl.arr, kl.T, ptr(kl.ws), stream_ptr(dev)), "bnn_kl_forward_partial")
-                kl.launched = True
-            karr, kT, kn, kout, kws = kl.arr, kl.T, kl.n_batches, ptr(kl.out), ptr(kl.ws)
         check(_lib.load().bnn_mc_uncertainty(ptr(yy), rows * C, nparts, S, rows, C, kind, ptr(mean), ptr(total), ptr(ale),
-                                             ptr(epi), adv, 1, karr, kT, kn, kout, kws, stream_ptr(dev)), "bnn_mc_uncertainty")
-        if kl is not None:
-            kl.done = True
-    except BnnHipError:
-        if kl is not None and _tls.kl_carry is kl:
-            _tls.kl_carry = None                    # the launch that was to finish it failed: nothing may carry it later
-        raise
+                                             ptr(epi), adv, 1, *_kl_tail_args(kl, "mc_uncertainty", dev), stream_ptr(dev)),
+              "bnn_mc_uncertainty")
     return PredictiveUncertainty(mean, total, ale, epi)
 
 
@@ -2653,30 +2671,13 @@ def mc_score(y, target, inputs=None, state=None, advance=None):
     histograms), so one state carries a whole test set and ScoreState.result() is the only host copy.
     advance: as mc_mean (the device epoch bumped in the same launch).  Bitwise reproducible; graph-capturable."""
     kind = _unc_kind(inputs, "mc_score")
-    if isinstance(y, HeadPartials):
-        yy = y.p
-        require_cuda_f32(yy, "y")
-        nparts, S, M, C = yy.shape
-        rows_shape = (M,)
-    else:
-        if not y.is_cuda:
-            raise BnnHipError("y must be a CUDA/HIP tensor")
-        if y.dtype != torch.float32:
-            raise BnnHipError("y must be float32, got %s" % y.dtype)
-        if y.dim() < 2:
-            raise BnnHipError("mc_score: y must be (S, *rows, classes), got %s" % (tuple(y.shape),))
-        yy = y.detach().contiguous()
-        nparts, S, C = 1, yy.shape[0], yy.shape[-1]
-        rows_shape = tuple(yy.shape[1:-1])
+    yy, nparts, S, rows_shape, rows, C = _mc_input(y, "mc_score", "classes")
     dev = yy.device
     if not isinstance(target, torch.Tensor) or not target.is_cuda or target.device != dev:
         raise BnnHipError("mc_score: target must be a CUDA/HIP tensor on y's device")
     if target.dtype != torch.int64 or tuple(target.shape) != rows_shape:
         raise BnnHipError("mc_score: target must be int64 of shape %s, got %s %s" % (rows_shape, target.dtype, tuple(target.shape)))
     tt = target.detach().contiguous()
-    rows = 1
-    for d in rows_shape:
-        rows *= d
     sp, cb, eb, ws = None, 0, 0, None
     if state is not None:
         if not isinstance(state, ScoreState) or state.device.type != "cuda" or state.state.device != dev:
@@ -2706,8 +2707,7 @@ def _reg_kind(outputs, who, kl=None):
     holds cannot be told from its values) -- and then leaves no KL pending for a later launch to carry."""
     if isinstance(outputs, str) and outputs in _REG_OUTPUTS:
         return _REG_OUTPUTS[outputs]
-    if kl is not None and _tls.kl_carry is kl:
-        _tls.kl_carry = None
+    _kl_uncarry(kl)
     raise ValueError("%s: outputs must be 'values', 'mean_logvar' or 'mean_var', got %r" % (who, outputs))
 
 
@@ -2745,50 +2745,17 @@ def mc_regression(y, outputs=None, advance=None, kl=None):
     advance / kl: as mc_mean (the device epoch bumped, a KlDeferred's second pass run, in the same launch).
     The sums over samples are fp64 in a fixed order: bitwise reproducible."""
     kind = _reg_kind(outputs, "mc_regression", kl)
-    try:
-        if isinstance(y, HeadPartials):
-            yy = y.p
-            require_cuda_f32(yy, "y")
-            nparts, S, M, W = yy.shape
-            rows_shape = (M,)
-        else:
-            if not y.is_cuda:
-                raise BnnHipError("y must be a CUDA/HIP tensor")
-            if y.dtype != torch.float32:
-                raise BnnHipError("y must be float32, got %s" % y.dtype)
-            if y.dim() < 2:
-                raise BnnHipError("mc_regression: y must be (S, *rows, width), got %s" % (tuple(y.shape),))
-            yy = y.detach().contiguous()
-            nparts, S, W = 1, yy.shape[0], yy.shape[-1]
-            rows_shape = tuple(yy.shape[1:-1])
+    with _kl_finishing(kl):
+        yy, nparts, S, rows_shape, rows, W = _mc_input(y, "mc_regression", "width")
         if kind != _lib.REG_VALUES and W % 2:
             raise BnnHipError("mc_regression: outputs=%r needs an even last axis, got %d" % (outputs, W))
         D = W if kind == _lib.REG_VALUES else W // 2
-        rows = 1
-        for d in rows_shape:
-            rows *= d
         dev = yy.device
         mean, total, ale, epi = (torch.empty(rows_shape + (D,), dtype=torch.float32, device=dev) for _ in range(4))
         adv = ptr(advance) if advance is not None else None
-        karr, kT, kn, kout, kws = None, 0, 1.0, None, None
-        if kl is not None:
-            # second pass of a KL begun by kl_normal_begin, as one extra workgroup of this launch (as in mc_mean)
-            if kl.done:
-                raise BnnHipError("mc_regression: this KlDeferred has already been finished")
-            if not kl.launched:                     # no narrow layer took it along
-                if _tls.kl_carry is kl:
-                    _tls.kl_carry = None
-                check(_lib.load().bnn_kl_forward_partial(kl.arr, kl.T, ptr(kl.ws), stream_ptr(dev)), "bnn_kl_forward_partial")
-                kl.launched = True
-            karr, kT, kn, kout, kws = kl.arr, kl.T, kl.n_batches, ptr(kl.out), ptr(kl.ws)
         check(_lib.load().bnn_mc_regression(ptr(yy), rows * W, nparts, S, rows, W, kind, ptr(mean), ptr(total), ptr(ale),
-                                            ptr(epi), adv, 1, karr, kT, kn, kout, kws, stream_ptr(dev)), "bnn_mc_regression")
-        if kl is not None:
-            kl.done = True
-    except BnnHipError:
-        if kl is not None and _tls.kl_carry is kl:
-            _tls.kl_carry = None                    # the launch that was to finish it failed: nothing may carry it later
-        raise
+                                            ptr(epi), adv, 1, *_kl_tail_args(kl, "mc_regression", dev), stream_ptr(dev)),
+              "bnn_mc_regression")
     return PredictiveRegression(mean, total, ale, epi)
 
 

@@ -555,7 +555,7 @@ def _mc_ref(ts):
 
 
 @gpu
-@pytest.mark.parametrize("D", [1, 3, 16, 17, 1028])
+@pytest.mark.parametrize("D", [1, 3, 16, 17, 300, 1000, 1028, 4096])     # wide: <64,1>, <64,2>, <64,4>, <256,2>, <256,4>
 @pytest.mark.parametrize("rows", [1, 37, 257])
 @pytest.mark.parametrize("S", [1, 3, 8, 65, 130])
 def test_mc_evidential_against_float64(S, rows, D):
