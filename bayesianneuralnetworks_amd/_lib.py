@@ -202,6 +202,10 @@ SIGNATURES = {
                             ctypes.c_uint32, _p]),
     "bnn_mc_regression": (_int, [_p, _i64, _int, _int, _i64, _int, _int, _p, _p, _p, _p, _p, ctypes.c_uint32,
                                  ctypes.POINTER(KlTensor), _int, _f, _p, _p, _p]),
+    "bnn_mc_regression_score_state_doubles": (_i64, [_int, _int]),
+    "bnn_mc_regression_score_workspace_bytes": (_i64, [_int, _int, _i64, _int, _int, _int]),
+    "bnn_mc_regression_score": (_int, [_p, _i64, _int, _int, _i64, _int, _int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _int, _p, _p,
+                                       ctypes.c_uint32, _p]),
     "bnn_gaussian_nll_workspace_bytes": (_i64, [_i64, _i64, _int]),
     "bnn_gaussian_nll": (_int, [_p, _int, _i64, _int, _p, _p, _p, _p, _p]),
     "bnn_nig_head_forward": (_int, [_p, _i64, _int, _p, _p, _p, _p, _p]),

@@ -1,9 +1,10 @@
 // bnn_mc_parts.hpp -- the skeleton the one-launch MC tails over (S, rows, width) outputs share (bnn_uncertainty.hip:
-// classification, bnn_score.hip: classification against labels, bnn_regression.hip: regression, bnn_evidential.hip: the NIG
-// mixture).  Host: the argument checks, the launch arguments with their `vec` rule, the narrow and wide launch plans and the
+// classification, bnn_score.hip: classification against labels, bnn_regression.hip: regression, bnn_regression_score.hip:
+// regression against targets, bnn_evidential.hip: the NIG mixture).  Host: the argument checks, the launch arguments with their `vec` rule, the narrow and wide launch plans and the
 // dispatch of a plan / a (kind, fused) pair to a kernel instantiation.  Device: the narrow split's lane geometry, the row
 // loader, a fused head's partials added in bnn_mc_sum's order, the four-moment stores, the epoch / KL tails of the launch, and
-// the classification tails' row reductions.  What a sample contributes -- the arithmetic -- stays in each tail's own file.
+// the classification tails' row reductions, the log-sum-exp over samples the two scoring tails share and the moments the two
+// regression tails share.  What else a sample contributes -- the arithmetic -- stays in each tail's own file.
 #pragma once
 #include <initializer_list>
 #include <type_traits>
@@ -310,6 +311,83 @@ __device__ __forceinline__ void row_sum2(T &a, T &b, T *slot)
         a = (slot[0] + slot[1]) + (slot[2] + slot[3]);
         b = (slot[4] + slot[5]) + (slot[6] + slot[7]);
     }
+}
+
+
+// ---- shared by the tails that take a log-sum-exp over the samples (bnn_score.hip, bnn_regression_score.hip)
+constexpr int kLseEmpty = -(1 << 28);       // exponent of an empty log-sum-exp (A = 0)
+constexpr int kLseShift = -2000;            // a rescale below 2^-2000 is 0 in fp64 anyway
+
+// running log-sum-exp in base 2 over a row's samples
+struct Lse { int M; double A; };
+
+__device__ __forceinline__ void lse_add(Lse &L, float lp)
+{
+    if (lp != lp) { L.A = (double)lp; return; }                     // NaN in, NaN out
+    if (!(lp >= -1.0e6f)) return;                                   // no mass
+    const int c = (int)ceilf(lp);
+    if (c > L.M) {
+        const int d = L.M - c;
+        L.A = ldexp(L.A, d > kLseShift ? d : kLseShift);
+        L.M = c;
+    }
+    L.A += (double)__builtin_amdgcn_exp2f(lp - (float)L.M);
+}
+
+// the two operands' exact rescales, one commutative add: both lanes of an xor pair end with the same bits
+__device__ __forceinline__ void lse_merge(Lse &L, int M2, double A2)
+{
+    const int M = L.M > M2 ? L.M : M2;
+    const int d1 = L.M - M, d2 = M2 - M;
+    L.A = ldexp(L.A, d1 > kLseShift ? d1 : kLseShift) + ldexp(A2, d2 > kLseShift ? d2 : kLseShift);
+    L.M = M;
+}
+
+// -ln of the MC predictive at the label, LOGITS: -ln 2 (M + log2(A / S)), the log as total_term_bits takes it (v_log_f32 on the
+// fp32-rounded A / S in (2^-17, 1]: M carries the range); +inf where no sample gave the label any mass
+__device__ __forceinline__ double lse_nll(const Lse &L, int S)
+{
+    return -kLn2 * ((double)L.M + (double)__builtin_amdgcn_logf((float)(L.A / (double)S)));
+}
+
+// ---- shared by the regression tails (bnn_regression.hip, bnn_regression_score.hip)
+template <int KIND>
+__device__ __forceinline__ float reg_var(float v)
+{
+    if constexpr (KIND == BNN_REG_MEAN_LOGVAR) return __builtin_amdgcn_exp2f(v * kLog2e);
+    return v;
+}
+
+// one sample's contribution of one quantity: d = m - m_0 in fp64 (exact for fp32 operands less than 2^29 apart in exponent)
+template <int KIND>
+__device__ __forceinline__ void reg_acc(float m, float ref, float v, double &sd, double &sd2, double &sv)
+{
+    const double d = (double)m - (double)ref;
+    sd += d;
+    sd2 = __builtin_fma(d, d, sd2);
+    if constexpr (KIND != BNN_REG_VALUES) sv += (double)reg_var<KIND>(v);
+}
+
+// the fp64 moments of one quantity before they are rounded: mean, aleatoric, epistemic (total = ale + epi)
+struct Moments64 { double mean, ale, epi; };
+
+__device__ __forceinline__ Moments64 reg_moments(float ref, double sd, double sd2, double sv, double inv_S)
+{
+    const double md = sd * inv_S;
+    double epi = __builtin_fma(-md, md, sd2 * inv_S);
+    epi = epi > 0.0 ? epi : 0.0;
+    return Moments64{(double)ref + md, sv * inv_S, epi};
+}
+
+__device__ __forceinline__ Moments reg_finish(float ref, double sd, double sd2, double sv, double inv_S)
+{
+    const Moments64 q = reg_moments(ref, sd, sd2, sv, inv_S);
+    Moments o;
+    o.mean = (float)q.mean;
+    o.total = (float)(q.ale + q.epi);
+    o.ale = (float)q.ale;
+    o.epi = (float)q.epi;
+    return o;
 }
 
 }  // namespace bnn

@@ -24,37 +24,6 @@
 
 namespace bnn {
 
-template <int KIND>
-__device__ __forceinline__ float reg_var(float v)
-{
-    if constexpr (KIND == BNN_REG_MEAN_LOGVAR) return __builtin_amdgcn_exp2f(v * kLog2e);
-    return v;
-}
-
-// one sample's contribution of one quantity: d = m - m_0 in fp64 (exact for fp32 operands less than 2^29 apart in exponent)
-template <int KIND>
-__device__ __forceinline__ void reg_acc(float m, float ref, float v, double &sd, double &sd2, double &sv)
-{
-    const double d = (double)m - (double)ref;
-    sd += d;
-    sd2 = __builtin_fma(d, d, sd2);
-    if constexpr (KIND != BNN_REG_VALUES) sv += (double)reg_var<KIND>(v);
-}
-
-__device__ __forceinline__ Moments reg_finish(float ref, double sd, double sd2, double sv, double inv_S)
-{
-    const double md = sd * inv_S;
-    double epi = __builtin_fma(-md, md, sd2 * inv_S);
-    epi = epi > 0.0 ? epi : 0.0;
-    const double ale = sv * inv_S;
-    Moments o;
-    o.mean = (float)((double)ref + md);
-    o.total = (float)(ale + epi);
-    o.ale = (float)ale;
-    o.epi = (float)epi;
-    return o;
-}
-
 // ---------------------------------------------------------------------------------------------- narrow: width <= 16
 // Lane = (row, sl): sl = lane & (G - 1) takes samples sl, sl + G, ...  A.classes is the row width, D the predicted quantities
 // (width, or width / 2 with the variances' half D columns behind the means').  FUSED: y is a fused head's partials.

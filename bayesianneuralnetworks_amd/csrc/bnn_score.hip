@@ -27,9 +27,6 @@
 namespace bnn {
 
 constexpr int kScoreMaxBins = 128;
-constexpr int kLseEmpty = -(1 << 28);       // exponent of an empty log-sum-exp (A = 0)
-constexpr int kLseShift = -2000;            // a rescale below 2^-2000 is 0 in fp64 anyway
-
 struct ScoreArgs {
     UncArgs u;                              // u.mean may be NULL; u.total / aleatoric / epistemic unused
     const int64_t *target;
@@ -39,38 +36,6 @@ struct ScoreArgs {
     int conf_bins, ent_bins;
     double ent_scale;                       // ent_bins / ln(classes)
 };
-
-// running log-sum-exp in base 2 over a row's samples
-struct Lse { int M; double A; };
-
-__device__ __forceinline__ void lse_add(Lse &L, float lp)
-{
-    if (lp != lp) { L.A = (double)lp; return; }                     // NaN in, NaN out
-    if (!(lp >= -1.0e6f)) return;                                   // no mass
-    const int c = (int)ceilf(lp);
-    if (c > L.M) {
-        const int d = L.M - c;
-        L.A = ldexp(L.A, d > kLseShift ? d : kLseShift);
-        L.M = c;
-    }
-    L.A += (double)__builtin_amdgcn_exp2f(lp - (float)L.M);
-}
-
-// the two operands' exact rescales, one commutative add: both lanes of an xor pair end with the same bits
-__device__ __forceinline__ void lse_merge(Lse &L, int M2, double A2)
-{
-    const int M = L.M > M2 ? L.M : M2;
-    const int d1 = L.M - M, d2 = M2 - M;
-    L.A = ldexp(L.A, d1 > kLseShift ? d1 : kLseShift) + ldexp(A2, d2 > kLseShift ? d2 : kLseShift);
-    L.M = M;
-}
-
-// -ln of the MC predictive at the label, LOGITS: -ln 2 (M + log2(A / S)), the log as total_term_bits takes it (v_log_f32 on the
-// fp32-rounded A / S in (2^-17, 1]: M carries the range); +inf where no sample gave the label any mass
-__device__ __forceinline__ double lse_nll(const Lse &L, int S)
-{
-    return -kLn2 * ((double)L.M + (double)__builtin_amdgcn_logf((float)(L.A / (double)S)));
-}
 
 // What the row's last lane writes once the row's sums are known.  m_y: the fp64 mean at the label (PROBS).
 template <int KIND>

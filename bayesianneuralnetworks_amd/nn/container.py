@@ -169,6 +169,37 @@ class BayesianNetworkModule(Module):
         y = self._mc_outputs(x, samples, sample0, kwargs)
         return ops.mc_regression(y, outputs, advance=advance, kl=kl)
 
+    def predictive_regression_score(self, x, target, samples=None, sample0=0, *, outputs, state=None, advance=None, **kwargs):
+        """`samples` MC draws of a real-valued `_forward(x)` scored against the targets `target` (*rows, D) ->
+        ops.RegressionScore(mean, variance, sq_err, nll, gaussian_nll, crps, pit), each (*rows, D): the proper scores of the MC
+        predictive -- the equal-weight mixture of the per-sample Gaussians -- and its probability integral transform.  outputs:
+        'values', 'mean_logvar' or 'mean_var' as predictive_regression -- required.  state: an ops.RegressionScoreState on x's
+        device that this batch is added to, so that one state carries a test set (RMSE, NLL, CRPS, sharpness, the PIT histogram
+        with the calibration curve and interval coverage: RegressionScoreState.result(), the only host copy).  Draws are consumed
+        as by predictive_mean with the same arguments.  Not covered: the evidential head's Student-t predictive, a KL tail,
+        more than 1024 samples.
+          mc_batched on CUDA: one batched pass (a hidden layer fused with its <= 16-wide head hands on partials) + ONE
+                              bnn_mc_regression_score launch (two with a state), which also runs the `advance` tail;
+          other CUDA:         forward_stacked (the serial loop), then the same launch;
+          CPU:                forward_stacked, then ops.regression_score_f64 (the same formulas in float64), added to a CPU state."""
+        from .. import ops
+        ops._reg_kind(outputs, "predictive_regression_score")       # before a draw is consumed
+        if samples is None:
+            samples = self.samples
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            if advance is not None:
+                raise ops.BnnHipError("predictive_regression_score: advance is a tail of the device launch; x is not on the device")
+            if state is not None and not (isinstance(state, ops.RegressionScoreState) and state.device.type == "cpu"):
+                raise ops.BnnHipError("predictive_regression_score: x is not on the device, so state must be a "
+                                      "RegressionScoreState on the CPU")
+            bins = state.pit_bins if state is not None else 20
+            out, mat = ops.regression_score_f64(self.forward_stacked(x, samples, sample0, **kwargs), target, outputs, bins)
+            if state is not None:
+                state.add_(mat)
+            return out
+        y = self._mc_outputs(x, samples, sample0, kwargs)
+        return ops.mc_regression_score(y, target, outputs, state=state, advance=advance)
+
     def predictive_evidential(self, x, samples=None, sample0=0, **kwargs):
         """Predictive mean and variance decomposition of `samples` MC draws of a network whose `_forward(x)` ends in an
         evidential head and returns its (gamma, upsilon, alpha, beta) -> ops.PredictiveRegression(mean, total, aleatoric,

@@ -2759,6 +2759,223 @@ def mc_regression(y, outputs=None, advance=None, kl=None):
     return PredictiveRegression(mean, total, ale, epi)
 
 
+# --------------------------------------------------------------------------- predictive regression score (against targets)
+RegressionScore = collections.namedtuple("RegressionScore", ("mean", "variance", "sq_err", "nll", "gaussian_nll", "crps", "pit"))
+RegressionScore.__doc__ = """What mc_regression_score returns, all (*rows, D): mean and variance, mc_regression's mean and total;
+sq_err = (mean - t)^2; nll, the negative log-density of the MC predictive -- the equal-weight mixture of the S per-sample Gaussians
+-- at the target t ('values' has no density: gaussian_nll's bits); gaussian_nll, that of the moment-matched Gaussian
+N(mean, variance) (NaN where variance == 0); crps, the mixture's continuous ranked probability score (the ensemble CRPS for
+'values'); pit, the mixture's cdf at t.  A NaN target makes its element's last five NaN; a negative or NaN per-sample variance
+('mean_var') makes its element's nll, crps and pit NaN."""
+
+REG_SCORE_MAX_SAMPLES = 1024            # the CRPS's pair sum is quadratic in S
+
+
+def regression_score_state_size(D, pit_bins):
+    """Doubles of a regression score state: per predicted quantity [n, sum sq_err, sum nll, sum gaussian_nll, sum crps,
+    sum variance] + pit_bins counts (bnn_mc_regression_score_state_doubles)."""
+    if not (1 <= int(D) <= 4096 and 1 <= int(pit_bins) <= 128):
+        raise ValueError("regression score state: D must be in 1 .. 4096 and pit_bins in 1 .. 128, got %r, %r" % (D, pit_bins))
+    return int(D) * (6 + int(pit_bins))
+
+
+class RegressionScoreResult(collections.namedtuple("RegressionScoreResult", ("n", "rmse", "nll", "gaussian_nll", "crps", "sharpness",
+                                                                             "pit_hist", "calibration", "calibration_error"))):
+    """What RegressionScoreState.result() returns: per predicted quantity d (lists of length D, Python floats) n targets; rmse;
+    the means of nll, gaussian_nll and crps; sharpness = sqrt(mean predictive variance); pit_hist, the counts of the PIT in
+    equal-width bins (a NaN pit is in none); calibration, the list of (k / bins, observed share of the binned pit below that
+    edge) for k = 1 .. bins -- a calibrated predictive lies on the diagonal --; calibration_error = mean_k |observed - k / bins|.
+    n = 0 (or nothing binned): NaN ratios."""
+    __slots__ = ()
+
+    def coverage(self, level):
+        """Per d, the share of the binned targets inside the central `level` interval of the predictive: pit in
+        [(1 - level) / 2, (1 + level) / 2].  The interval must end on bin edges: ValueError unless (1 - level) / 2 * bins is an
+        integer to 1e-9."""
+        out = []
+        for hist in self.pit_hist:
+            bins = len(hist)
+            lo = (1.0 - float(level)) / 2.0 * bins
+            k = int(round(lo))
+            if not (0.0 < float(level) <= 1.0) or abs(lo - k) > 1e-9:
+                raise ValueError("coverage: the central %r interval does not end on the edges of %d bins" % (level, bins))
+            tot = sum(hist)
+            out.append(sum(hist[k:bins - k]) / tot if tot > 0 else float("nan"))
+        return out
+
+
+class RegressionScoreState:
+    """The accumulator of mc_regression_score / BayesianNetworkModule.predictive_regression_score over the batches of a test set:
+    a zeroed float64 (D, 6 + pit_bins) buffer on `device` (layout: regression_score_state_size) that every scored batch is added
+    to on the device, and the launch's workspace.  Nothing is copied to the host until result().  On a CPU device it accumulates
+    what regression_score_f64 returns."""
+
+    def __init__(self, device, D, pit_bins=20):
+        self.D, self.pit_bins = int(D), int(pit_bins)
+        self.device = torch.device(device)
+        regression_score_state_size(D, pit_bins)
+        self.state = torch.zeros(self.D, 6 + self.pit_bins, dtype=torch.float64, device=self.device)
+        self._ws = None
+
+    def workspace(self, nparts, nsamples, rows, width, kind):
+        """The launch's workspace with this state (bnn_mc_regression_score_workspace_bytes), grown when a larger batch comes."""
+        need = _lib.load().bnn_mc_regression_score_workspace_bytes(nparts, nsamples, rows, width, kind, 1) // 4
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._ws
+
+    def reset(self):
+        self.state.zero_()
+        return self
+
+    def add_(self, mat):
+        """Adds a state matrix (what regression_score_f64 returns) -- the CPU path."""
+        self.state += mat.to(self.state.device, torch.float64).reshape(self.state.shape)
+        return self
+
+    def result(self):
+        """RegressionScoreResult of everything added so far: ONE device-to-host copy, finished in Python float64."""
+        rows = self.state.detach().cpu().tolist()
+        nan = float("nan")
+        div = lambda a, b: a / b if b > 0 else nan         # noqa: E731
+        root = lambda a: math.sqrt(a) if a >= 0 else nan   # noqa: E731      (NaN: NaN)
+        bins = self.pit_bins
+        out = [[] for _ in range(9)]
+        for v in rows:
+            n = v[0]
+            hist = v[6:6 + bins]
+            tot, cum, cal = sum(hist), 0.0, []
+            for k in range(1, bins + 1):
+                cum += hist[k - 1]
+                cal.append((k / bins, div(cum, tot)))
+            err = sum(abs(obs - edge) for edge, obs in cal) / bins if tot > 0 else nan
+            for o, x in zip(out, (n, root(div(v[1], n)), div(v[2], n), div(v[3], n), div(v[4], n), root(div(v[5], n)), hist, cal, err)):
+                o.append(x)
+        return RegressionScoreResult(*out)
+
+
+def _crps_a(mu, var):
+    """A(mu, sigma^2) = mu (2 Phi(mu / sigma) - 1) + 2 sigma phi(mu / sigma), A(mu, 0) = |mu|; a negative or NaN variance: NaN."""
+    sg = torch.sqrt(var.clamp_min(0.0))
+    safe = torch.where(sg > 0, sg, torch.ones_like(sg))
+    z = mu / safe
+    a = mu * torch.erf(z / math.sqrt(2.0)) + safe * math.sqrt(2.0 / math.pi) * torch.exp(-0.5 * z * z)
+    a = torch.where(var == 0, mu.abs(), a)
+    return torch.where(var >= 0, a, torch.full_like(a, float("nan")))
+
+
+def regression_score_f64(ys, target, outputs, pit_bins=20):
+    """The formulas of mc_regression_score in float64 torch (the CPU path of BayesianNetworkModule.predictive_regression_score):
+    ys (S, *rows, width), the stacked MC outputs; target (*rows, D).  Returns (RegressionScore, state matrix): the per-element
+    values rounded to float32 at the end, and the float64 (D, 6 + pit_bins) matrix a RegressionScoreState adds, whose bins and
+    sums are those of the rounded values.  The pair term of the CRPS is summed one sample at a time: O(S) memory."""
+    kind = _reg_kind(outputs, "regression_score_f64")
+    y = ys.detach().to(torch.float64)
+    if y.dim() < 2:
+        raise ValueError("regression_score_f64: ys must be (S, *rows, width), got %s" % (tuple(ys.shape),))
+    raw = None if kind == _lib.REG_VALUES else y[..., y.shape[-1] // 2:]
+    m, v = _reg_split(y, kind, "regression_score_f64")
+    S, D = m.shape[0], m.shape[-1]
+    regression_score_state_size(D, pit_bins)
+    rows_shape = tuple(m.shape[1:-1])
+    if not isinstance(target, torch.Tensor) or tuple(target.shape) != rows_shape + (D,):
+        raise ValueError("regression_score_f64: target must be a tensor of shape %s" % (rows_shape + (D,),))
+    m = m.reshape(S, -1, D)
+    v = torch.zeros_like(m) if v is None else v.reshape(S, -1, D)
+    t = target.detach().to(y.device, torch.float64).reshape(-1, D)
+    nan = torch.full_like(t, float("nan"))
+    mean = m.mean(0)
+    V = v.mean(0) + ((m - mean) ** 2).mean(0)
+    e = mean - t
+    Vs = torch.where(V == 0, torch.ones_like(V), V)
+    gnll = torch.where(V == 0, nan, 0.5 * (torch.log(2.0 * math.pi * Vs) + e * e / Vs))
+    r = t - m                                                       # (S, rows, D)
+    if kind == _lib.REG_VALUES:
+        nll = gnll
+    else:
+        raw = raw.reshape(S, -1, D)
+        if kind == _lib.REG_MEAN_LOGVAR:
+            lnv, inv = raw, torch.exp(-raw)
+        else:
+            pos = v > 0
+            vs = torch.where(pos, v, torch.ones_like(v))
+            lnv, inv = torch.where(pos, torch.log(vs), torch.full_like(v, float("nan"))), 1.0 / vs
+        ell = -0.5 * (math.log(2.0 * math.pi) + lnv + r * r * inv)
+        nll = -(torch.logsumexp(ell, 0) - math.log(S))
+    sg = torch.sqrt(v.clamp_min(0.0))
+    safe = torch.where(sg > 0, sg, torch.ones_like(sg))
+    step = (r > 0).to(torch.float64) + 0.5 * (r == 0).to(torch.float64)
+    cdf = torch.where(sg > 0, 0.5 * torch.erfc(-(r / safe) / math.sqrt(2.0)), step)
+    cdf = torch.where(v >= 0, cdf, torch.full_like(cdf, float("nan")))
+    pit = cdf.mean(0)
+    pair = torch.zeros_like(mean)
+    for i in range(S):
+        pair += _crps_a(m[i] - m, v[i] + v).sum(0)
+    bad = (v >= 0).logical_not().any(0)                             # a pair's variances may add up to a valid one
+    crps = _crps_a(r, v).mean(0) - pair / (2.0 * S * S)
+    crps = torch.where(bad, nan, crps)
+    tnan = torch.isnan(t)
+    sq, nll, gnll, crps, pit = (torch.where(tnan, nan, x) for x in (e * e, nll, gnll, crps, pit))
+    f32 = lambda x: x.to(torch.float32)         # noqa: E731
+    vals = [f32(x) for x in (mean, V, sq, nll, gnll, crps, pit)]
+    out = RegressionScore(*(x.reshape(rows_shape + (D,)) for x in vals))
+    mat = torch.zeros(D, 6 + pit_bins, dtype=torch.float64, device=y.device)
+    mat[:, 0] = t.shape[0]
+    for k, x in enumerate((vals[2], vals[3], vals[4], vals[5], vals[1])):
+        mat[:, 1 + k] = x.to(torch.float64).sum(0)
+    p64 = vals[6].to(torch.float64)
+    bins = torch.floor(p64 * pit_bins).clamp(0, pit_bins - 1)
+    for d in range(D):
+        ok = ~torch.isnan(p64[:, d])
+        mat[d, 6:] = torch.bincount(bins[ok, d].to(torch.int64), minlength=pit_bins).to(torch.float64)
+    return out, mat
+
+
+def mc_regression_score(y, target, outputs=None, state=None, advance=None):
+    """A regression MC forward scored against its targets over the leading MC axis in ONE launch (bnn_mc_regression_score) ->
+    RegressionScore.
+    y: CUDA fp32 (S, *rows, width) (made contiguous if it is not), S <= 1024, or a HeadPartials (the launch adds the partials
+    itself, once, bit for bit as y.logits() would).  target: CUDA fp32 (*rows, D); a NaN target makes its element's scores NaN
+    (on the device: no host synchronisation).
+    outputs: 'values', 'mean_logvar' or 'mean_var' as mc_regression -- required.
+    state: a RegressionScoreState on y's device with the same D; a second launch adds this batch to it (sums and the PIT
+    histogram per predicted quantity), so one state carries a whole test set and RegressionScoreState.result() is the only host
+    copy.  advance: as mc_mean (the device epoch bumped in the same launch).  Bitwise reproducible; graph-capturable.
+    Not covered: the evidential head's Student-t predictive, a KL tail, S above 1024 (the pair sum is O(S^2 rows D))."""
+    kind = _reg_kind(outputs, "mc_regression_score")
+    yy, nparts, S, rows_shape, rows, W = _mc_input(y, "mc_regression_score", "width")
+    if kind != _lib.REG_VALUES and W % 2:
+        raise BnnHipError("mc_regression_score: outputs=%r needs an even last axis, got %d" % (outputs, W))
+    if S > REG_SCORE_MAX_SAMPLES:
+        raise BnnHipError("mc_regression_score: %d samples; the pair sum of the CRPS takes at most %d" % (S, REG_SCORE_MAX_SAMPLES))
+    D = W if kind == _lib.REG_VALUES else W // 2
+    dev = yy.device
+    if not isinstance(target, torch.Tensor) or not target.is_cuda or target.device != dev:
+        raise BnnHipError("mc_regression_score: target must be a CUDA/HIP tensor on y's device")
+    if target.dtype != torch.float32 or tuple(target.shape) != rows_shape + (D,):
+        raise BnnHipError("mc_regression_score: target must be float32 of shape %s, got %s %s"
+                          % (rows_shape + (D,), target.dtype, tuple(target.shape)))
+    tt = target.detach().contiguous()
+    lib = _lib.load()
+    sp, bins, ws = None, 0, None
+    if state is not None:
+        if not isinstance(state, RegressionScoreState) or state.device.type != "cuda" or state.state.device != dev:
+            raise BnnHipError("mc_regression_score: state must be a RegressionScoreState on y's device")
+        if state.D != D:
+            raise BnnHipError("mc_regression_score: the state holds %d predicted quantities, y has %d" % (state.D, D))
+        sp, bins, ws = ptr(state.state), state.pit_bins, state.workspace(nparts, S, rows, W, kind)
+    else:
+        need = lib.bnn_mc_regression_score_workspace_bytes(nparts, S, rows, W, kind, 0) // 4
+        if need:
+            ws = torch.empty(need, dtype=torch.float32, device=dev)         # a fused head's rows, the parts added once
+    outs = [torch.empty(rows_shape + (D,), dtype=torch.float32, device=dev) for _ in range(7)]
+    adv = ptr(advance) if advance is not None else None
+    check(lib.bnn_mc_regression_score(ptr(yy), rows * W, nparts, S, rows, W, kind, ptr(tt), *(ptr(o) for o in outs), sp, bins,
+                                      ptr(ws) if ws is not None and ws.numel() else None, adv, 1, stream_ptr(dev)),
+          "bnn_mc_regression_score")
+    return RegressionScore(*outs)
+
+
 class _GaussianNLL(torch.autograd.Function):
     """gaussian_nll_loss(m, t, exp(s), full=False, reduction='mean') over the stacked samples: the loss and d loss / d ys in
     one HIP pass (bnn_gaussian_nll).  ys (S, rows, 2 D), target (rows, D); the target carries no gradient."""

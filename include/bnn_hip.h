@@ -909,6 +909,55 @@ int64_t bnn_gaussian_nll_workspace_bytes(int64_t nsamples, int64_t rows, int wid
 int bnn_gaussian_nll(const float *y, int nsamples, int64_t rows, int width, const float *target,
                      float *loss, float *g_y /* may be NULL */, void *workspace, void *stream);
 
+/* ---- K15: a regression MC forward scored against its targets -------------------------
+ * Per row and predicted quantity, in ONE launch: the predictive mean and variance, the squared error, the negative
+ * log-likelihood of the MC predictive -- the equal-weight mixture of the S per-sample Gaussians --, that of the moment-matched
+ * Gaussian, the mixture's CRPS and its probability integral transform (PIT); with a `state`, a second launch adds the batch to
+ * a device accumulator that carries a whole test set (sums and the PIT histogram per predicted quantity).
+ * replaces  pulling the stacked outputs back and a dozen small torch launches per batch, the O(S^2) pair term among them
+ *   y, addend_stride, nparts, nsamples, rows, width, kind, D and the per-sample (m_s, v_s): as bnn_mc_regression (a fused head's
+ *   partials are first summed over the parts in bnn_mc_sum's order), but 1 <= nsamples <= 1024 (BNN_E_RANGE above: the pair sum
+ *   is quadratic in S).  target: rows x D fp32.  Every output is rows x D fp32, may be NULL and is then not written.  With
+ *   t = target[r, d], Phi / phi the standard normal cdf / pdf, sg_s = sqrt(v_s):
+ *   mean, variance   the bits bnn_mc_regression writes as `mean` and `total`
+ *   sq_err           (mean - t)^2, of the fp64 mean before it is rounded
+ *   gaussian_nll     (ln(2 pi V) + (t - mean)^2 / V) / 2 with V the fp64 total variance; NaN where V == 0
+ *   nll              -(logsumexp_s l_s - ln S), l_s = -(ln 2 pi + ln v_s + (t - m_s)^2 / v_s) / 2, formed in the log domain.
+ *                    MEAN_LOGVAR: ln v_s is the input s itself and (t - m_s)^2 / v_s = ((t - m_s) e^(-s / 2))^2, finite for a
+ *                    log-variance far below fp32's exp range (down to -176).  MEAN_VAR: v_s <= 0 or NaN gives NaN.  VALUES has
+ *                    no mixture density: written with gaussian_nll's bits.
+ *   crps             (1/S) sum_s A(t - m_s, v_s) - (1 / 2 S^2) sum_i sum_j A(m_i - m_j, v_i + v_j)   (Grimit et al. 2006) with
+ *                    A(mu, sg^2) = mu (2 Phi(mu / sg) - 1) + 2 sg phi(mu / sg), A(mu, 0) = |mu|: the ensemble CRPS for VALUES.
+ *                    A negative or NaN v_s gives NaN.
+ *   pit              (1/S) sum_s Phi((t - m_s) / sg_s); a zero-variance sample adds [t > m_s] + [t == m_s] / 2 (VALUES: the
+ *                    ensemble's empirical cdf with mid-point ties).  A negative or NaN v_s gives NaN.
+ *   A NaN target makes that element's sq_err, nll, gaussian_nll, crps and pit NaN; nothing outside the element changes, every
+ *   other element keeps its bits, and no host synchronisation is involved.  Infinite targets follow IEEE.
+ *   Per-term arithmetic fp32 (erf, exp, log, sqrt); every sum over samples and over pairs fp64 in a fixed order, no float
+ *   atomics: bitwise reproducible.  The pair sum takes every unordered pair once and costs O(S^2 rows D).
+ * state (may be NULL; bnn_mc_regression_score_state_doubles(D, pit_bins) = D (6 + pit_bins) doubles, zeroed by the caller
+ * once): per predicted quantity d the launch ADDS [n, sum sq_err, sum nll, sum gaussian_nll, sum crps, sum variance], then
+ *   pit_bins counts: bin = min(pit_bins - 1, floor(pit pit_bins)) of the fp32 pit written, 1 <= pit_bins <= 128.  The sums are
+ *   of the fp32 values written; a NaN pit counts in n and in no bin; a NaN element makes its d's affected sums NaN.  Counts are
+ *   exact integers, the sums fp64 in a fixed order.
+ * workspace: bnn_mc_regression_score_workspace_bytes(...) bytes, 4-B aligned (16-B for 16-B loads), required whenever that
+ *   query is non-zero (BNN_E_NULL otherwise): nsamples rows width floats where nparts > 1 -- the parts are added once, not once
+ *   per pair --, then 6 rows D floats with a state, which a second launch of D workgroups adds to `state`.
+ * advance_epoch (may be NULL) += advance_inc in the main launch, as in bnn_mc_score; there is no KL tail.
+ * Launches: one without a state, two with it.  Errors (nothing launched): BNN_E_NULL (y, target, a needed workspace),
+ * BNN_E_SHAPE / BNN_E_RANGE (extents as bnn_mc_regression, nsamples > 1024, unknown kind, odd width for a (mean, variance) kind,
+ * bins outside 1 .. 128 with a state), BNN_E_ALIGN (state 8 B, workspace 4 B).
+ * Not covered: the evidential head's Student-t predictive, a KL tail, S above 1024. */
+int64_t bnn_mc_regression_score_state_doubles(int D, int pit_bins);    /* D * (6 + pit_bins); 0 for D outside 1 .. 4096 or bins outside 1 .. 128 */
+int64_t bnn_mc_regression_score_workspace_bytes(int nparts, int nsamples, int64_t rows, int width, int kind, int with_state);
+                                                                       /* may be 0 without a state; 0 for bad extents */
+int bnn_mc_regression_score(const float *y, int64_t addend_stride, int nparts, int nsamples, int64_t rows, int width,
+                            int kind /* BNN_REG_VALUES 0 | BNN_REG_MEAN_LOGVAR 1 | BNN_REG_MEAN_VAR 2 */,
+                            const float *target /* rows x D */,
+                            float *mean, float *variance, float *sq_err, float *nll, float *gaussian_nll, float *crps, float *pit,
+                            double *state /* may be NULL */, int pit_bins, void *workspace,
+                            uint32_t *advance_epoch, uint32_t advance_inc, void *stream);
+
 /* ---- K13: evidential regression (the Normal-Inverse-Gamma head of examples/Simple) ----------------------------------
  * The head's activation.  replaces  the split / softplus / offsets of NormalInverseGaussianLinear.forward (nn/dense.py:141-162)
  *   z (rows, 4 D) fp32 contiguous, the output of the head's Linear.  One launch writes four contiguous (rows, D) tensors:
