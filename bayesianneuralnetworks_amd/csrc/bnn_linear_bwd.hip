@@ -1463,12 +1463,14 @@ int bnn_linear_backward_narrow_sampled(const void *x, int64_t x_sample_stride, i
     const bool xh = (flags & BNN_FLAG_X_BF16) != 0, gxh = (flags & BNN_FLAG_Y_BF16) != 0;
     const int xe = xh ? 2 : 4, ge = gxh ? 2 : 4;
     if (!al16(mu_w) || !al16(rho_w) || !al16(g_mu) || !al16(g_rho) || (reinterpret_cast<uintptr_t>(x) & (4 * xe - 1)) || (ldx * xe) % (4 * xe) != 0 ||
-        (x_sample_stride * xe) % (4 * xe) != 0 || (gx && ((reinterpret_cast<uintptr_t>(gx) & (4 * ge - 1)) || (gx_sample_stride * ge) % (4 * ge) != 0))) {
+        (x_sample_stride * xe) % (4 * xe) != 0 ||
+        (gx && ((reinterpret_cast<uintptr_t>(gx) & (4 * ge - 1)) || (gx_sample_stride * ge) % (4 * ge) != 0 || ldgx % 4 != 0))) {   // gx rows are stored as float4 / uint2
         set_error("%s: misaligned operand", who);
         return BNN_E_ALIGN;
     }
     int rc = check_rng(rng_w, nsamples);
     if (rc) { set_error("%s: bad rng_w", who); return rc; }
+    if (want_bias) { rc = check_rng(rng_b, nsamples); if (rc) { set_error("%s: bad rng_b", who); return rc; } }
     GemmParams ws{};
     fill_workspace(ws);
     const int64_t Z = (M + H_ROWS - 1) / H_ROWS, nslab = (int64_t)nsamples * Z;
@@ -1498,11 +1500,7 @@ int bnn_linear_backward_narrow_sampled(const void *x, int64_t x_sample_stride, i
     const int64_t n = N * K;
     (void)cs_sum;
     RngDev rb{};
-    if (want_bias) {
-        rc = check_rng(rng_b, nsamples);
-        if (rc) { set_error("%s: bad rng_b", who); return rc; }
-        rb = make_rng(rng_b);
-    }
+    if (want_bias) rb = make_rng(rng_b);
     const bool klb = want_bias && kl && kl->mu_b;
     hipLaunchKernelGGL(k_head_tail, dim3((unsigned)((n + 255) / 256 + (want_bias ? 1 : 0))), dim3(256), 0, st, ws.ws_slabs, p.slab_stride,
                        (int)nslab, rho_w, g_mu, g_rho, n, accumulate, kl ? kl->upstream : nullptr, kl ? kl->mu_w : nullptr,

@@ -457,7 +457,9 @@ int bnn_linear_backward_weight_sampled(const void *x, int64_t x_sample_stride, i
  * activations: gx (may be NULL), g_mu / g_rho of the weight, and the bias gradients -- same definitions
  * as the three entry points above.  gy fp32; flags: BNN_FLAG_X_BF16 = x is bf16, BNN_FLAG_Y_BF16 = gx
  * is written as bf16.  Needs the registered workspace (S * (2 N K + N) floats); BNN_E_UNSUPPORTED
- * otherwise (callers then use the general entry points). */
+ * otherwise (callers then use the general entry points).  Rows of x and gx are read / written four
+ * elements at a time: bases, sample strides and the pitches ldx, ldgx must be multiples of 4 elements,
+ * BNN_E_ALIGN otherwise.  Every argument check, both keys included, comes before the first launch. */
 int bnn_linear_backward_narrow_sampled(const void *x, int64_t x_sample_stride, int64_t ldx,
                                        const float *gy, int64_t gy_sample_stride, int64_t ldgy,
                                        const float *mu_w, const float *rho_w,

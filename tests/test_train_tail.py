@@ -72,6 +72,7 @@ import pytest
 import torch
 
 from bayesianneuralnetworks_amd import _lib, ops, optim
+from klref import softplus64, dsoftplus64, kl_grad64              # noqa: F401  (tests/golden, shared with test_train_step.py)
 
 gpu = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -284,33 +285,6 @@ def assert_xent_rows(got, x, y, what=""):
     print(what, "rows: max err %.3e, max bound %.3e, max ratio %.3f" % (e.max(), bnd.max(), ratio))
     assert (e <= bnd).all(), (what, "max err %.3e" % e.max(), "ratio %.2f" % ratio, "%d of %d rows out" % ((e > bnd).sum(), e.size))
     return ratio
-
-
-def softplus64(r):
-    r = np.asarray(r, np.float64)
-    return np.where(r > 20.0, r, np.log1p(np.exp(np.minimum(r, 20.0))))
-
-
-def dsoftplus64(r):
-    r = np.asarray(r, np.float64)
-    return np.where(r > 20.0, 1.0, 1.0 / (1.0 + np.exp(-r)))
-
-
-def kl_grad64(mu, rho, prior, n_tensors, n_batches, upstream):
-    """float64 closed form -> g_mu, g_rho, and the bounds on both.  The prior goes through np.float32 (bnn_kl_tensor_t)."""
-    mu, rho = np.asarray(mu, np.float64), np.asarray(rho, np.float64)
-    pm, ps = float(np.float32(prior[0])), float(np.float32(prior[1]))
-    sg = 1e-10 + softplus64(rho)
-    ds = dsoftplus64(rho)
-    sc = float(upstream) / (mu.size * n_tensors * float(n_batches))
-    g_mu = sc * (mu - pm) / ps ** 2
-    g_rho = sc * (sg / ps ** 2 - 1.0 / sg) * ds
-    rc = np.minimum(rho, 20.0)
-    e = np.exp(rc)
-    w = np.where(rho > 20.0, 0.0, e / ((1.0 + e) * np.log1p(e)))
-    w2 = np.where(rho > 20.0, 0.0, 1.0 - dsoftplus64(rc))
-    c = 28.0 + 2.0 * np.abs(rho) * (w + w2)
-    return g_mu, g_rho, 8.0 * U * np.abs(g_mu), c * U * abs(sc) * (sg / ps ** 2 + 1.0 / sg) * ds
 
 
 # =================================================================================================== CPU section
