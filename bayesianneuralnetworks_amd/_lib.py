@@ -13,7 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BNN_HIP_LIB") or os.path.join(_HERE, "libbnn_hip.so")
 
 F32, BF16, BF16X3 = 0, 1, 2
-DRAW_FLIPOUT = 16         # bnn_draw_tensor_t.kind of a Flipout draw (BNN_DRAW_FLIPOUT)
+DRAW_SAMPLE, DRAW_MEAN, DRAW_SIGMA, DRAW_COPY, DRAW_FLIPOUT = 0, 1, 2, 3, 16     # bnn_draw_tensor_t.kind (BNN_DRAW_*)
+CONV_DENSE, CONV_DENSE_X3, CONV_FLIPOUT, CONV_FLIPOUT_X3, CONV_FLIPOUT_MC = range(5)    # bnn_conv2d_dense_images variant (BNN_CONV_*)
 COMPUTE_F32, COMPUTE_BF16 = 0, 1
 FLAG_RELU = 1
 FLAG_X_BF16 = 2
@@ -149,6 +150,7 @@ SIGNATURES = {
     "bnn_conv2d_dense_forward": (_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, ctypes.POINTER(Conv2dShape), _int, _int, _p]),
     "bnn_conv2d_flipout_forward": (_int, [_p, _p, _i64, _p, _p, _p, ctypes.POINTER(Conv2dShape), _int, _p]),
     "bnn_conv2d_flipout_forward_mc": (_int, [_p, _i64, _p, _i64, _p, _i64, ctypes.POINTER(Conv2dShape), _int, _rngp, _int, _p]),
+    "bnn_conv2d_dense_images": (_int, [ctypes.POINTER(Conv2dShape), _int, _int, _int]),
     "bnn_conv2d_flipout_forward_x3": (_int, [_p, _p, _i64, _i64, _p, _p, _p, ctypes.POINTER(Conv2dShape), _int, _p]),
     "bnn_linear_forward": (_int, [_p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64,
                                   _int, _int, _int, _p]),

@@ -2206,6 +2206,47 @@ int bnn_transpose_bf16(const void *in, int64_t in_batch_stride, int64_t ld_in, v
 
 }  // extern "C"
 
+// What the LDS-resident conv (k_conv_bf16) decides from the shape alone -- the ONE place that knows the ring depths and LDS blocks of
+// its instantiations; conv_dense_launch launches by it and bnn_conv2d_dense_images answers the Python predicates with it.
+struct ConvFit {
+    int OH, OW;
+    bool family;        // groups = 1, C = 64 or a multiple of 128, 64 or 128 weight rows in the tile
+    int ns;             // keyed: samples per workgroup (else 0)
+    int img;            // images per workgroup; < 1: an image + the weight ring do not fit the LDS block (or > 128 output pixels)
+    int64_t img_bytes;  // an image's bf16 bytes + its sign masks
+};
+
+static int conv_dense_fit(const char *who, const bnn_conv2d_shape_t *sh, int nsamples, int flags, bool flip, bool x3, bool keyed,
+                          bool shared_x, int64_t ldw, ConvFit *f)
+{
+    if (sh->B < 1 || sh->C < 1 || sh->H < 1 || sh->W < 1 || sh->O < 1 || sh->KH < 1 || sh->KW < 1 || sh->stride_h < 1 ||
+        sh->stride_w < 1 || sh->pad_h < 0 || sh->pad_w < 0 || sh->dil_h < 1 || sh->dil_w < 1 || nsamples < 1) { set_error("%s: bad shape", who); return BNN_E_SHAPE; }
+    if (flags != 0) { set_error("%s: unknown flags", who); return BNN_E_UNSUPPORTED; }
+    const int OH = (sh->H + 2 * sh->pad_h - sh->dil_h * (sh->KH - 1) - 1) / sh->stride_h + 1;
+    const int OW = (sh->W + 2 * sh->pad_w - sh->dil_w * (sh->KW - 1) - 1) / sh->stride_w + 1;
+    if (OH < 1 || OW < 1) { set_error("%s: kernel larger than the padded input", who); return BNN_E_SHAPE; }
+    // what the kernel is built for (everything else: bnn_conv2d_forward_sampled / bnn_conv2d_forward)
+    const int64_t bn = flip ? 2 * (int64_t)sh->O : sh->O;       // weight rows of the tile
+    f->OH = OH; f->OW = OW;
+    f->family = sh->groups == 1 && (sh->C == 64 || sh->C % 128 == 0) && (bn == 64 || bn == 128);
+    // keyed: samples per workgroup (the mean contraction is shared by them; a per-sample input takes one)
+    // (2 O = 128 keeps two: with four its 40 accumulator blocks + the samples' masks spill, 192 VGPRs per lane)
+    const int ns = !keyed ? 0 : (!shared_x || nsamples == 1) ? 1 : (nsamples == 2 || bn == 128) ? 2 : 4;
+    const int64_t img_bytes = (int64_t)sh->H * sh->W * sh->C * 2 + (flip ? (int64_t)(sh->C / 8) * 16 * (keyed ? ns : 1) : 0);   // + sign masks
+    const int64_t rsign = keyed ? (int64_t)ns * sh->O * 4 : 0;      // keyed: an image's R_s of the workgroup's samples, fp32
+    const int64_t P = (int64_t)OH * OW;                 // (the query is asked about any conv shape: no 32-bit products here)
+    // ring stages (8 KB / 16 KB each); three-plane operands: the big block for both widths (three image planes), 4 / 3 stages
+    const int st = bn == 64 ? 4 : (x3 ? 3 : flip ? 4 : 6);
+    const int64_t lds_block = (bn == 64 && !x3 && !keyed) ? kConvLds : kConvLdsBig;
+    const int64_t ring = st * bn * 128;
+    int img = P > 128 ? 0 : (int)(128 / P);             // rows per workgroup <= 128
+    while (img > 0 && (img * (img_bytes * (x3 ? 3 : 1) + rsign) + ring > lds_block || img * (sh->O * P * 4 + rsign) > lds_block)) --img;
+    if (img > sh->B) img = sh->B;
+    if (bn * ldw * 2 >= ((int64_t)1 << 32)) img = 0;
+    f->ns = ns; f->img = img; f->img_bytes = img_bytes;
+    return BNN_OK;
+}
+
 static int conv_dense_launch(const float *x, int64_t x_sample_stride, const void *w, int64_t w_sample_stride, int64_t ldw,
                              const float *b, int64_t b_sample_stride, const float *sgn_in, const float *sgn_out,
                              float *y, int64_t y_sample_stride, const bnn_conv2d_shape_t *sh, int nsamples, int flags,
@@ -2215,39 +2256,22 @@ static int conv_dense_launch(const float *x, int64_t x_sample_stride, const void
     const bool flip = sgn_in != nullptr || keyed;
     const bool x3 = w_plane_stride != 0;
     if (!x || !w || !y || !sh || (flip && !keyed && !sgn_out)) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
-    if (sh->B < 1 || sh->C < 1 || sh->H < 1 || sh->W < 1 || sh->O < 1 || sh->KH < 1 || sh->KW < 1 || sh->stride_h < 1 ||
-        sh->stride_w < 1 || sh->pad_h < 0 || sh->pad_w < 0 || sh->dil_h < 1 || sh->dil_w < 1 || nsamples < 1) { set_error("%s: bad shape", who); return BNN_E_SHAPE; }
-    if (flags != 0) { set_error("%s: unknown flags", who); return BNN_E_UNSUPPORTED; }
-    const int OH = (sh->H + 2 * sh->pad_h - sh->dil_h * (sh->KH - 1) - 1) / sh->stride_h + 1;
-    const int OW = (sh->W + 2 * sh->pad_w - sh->dil_w * (sh->KW - 1) - 1) / sh->stride_w + 1;
-    if (OH < 1 || OW < 1) { set_error("%s: kernel larger than the padded input", who); return BNN_E_SHAPE; }
-    // what the kernel is built for (everything else: bnn_conv2d_forward_sampled / bnn_conv2d_forward)
+    ConvFit fit;
+    const int rc_fit = conv_dense_fit(who, sh, nsamples, flags, flip, x3, keyed, x_sample_stride == 0, ldw, &fit);
+    if (rc_fit) return rc_fit;
+    const int OH = fit.OH, OW = fit.OW, ns = fit.ns, img = fit.img;
     const int K = sh->C * sh->KH * sh->KW;
-    const int bn = flip ? 2 * sh->O : sh->O;            // weight rows of the tile
-    const bool ok = sh->groups == 1 && (sh->C == 64 || sh->C % 128 == 0) && (bn == 64 || bn == 128) &&
-                    ldw >= K && ldw % 8 == 0 && w_sample_stride % 8 == 0 && al16(w) &&
+    const int bn = flip ? 2 * sh->O : sh->O;
+    const bool ok = fit.family && ldw >= K && ldw % 8 == 0 && w_sample_stride % 8 == 0 && al16(w) &&
                     (reinterpret_cast<uintptr_t>(x) & 3u) == 0 && (reinterpret_cast<uintptr_t>(y) & 3u) == 0;
     if (!ok) { set_error("%s: needs groups = 1, C = 64 or a multiple of 128, O = 64 or 128 (Flipout: 32 or 64), tap-major bf16 weights with 16-B aligned rows", who); return BNN_E_UNSUPPORTED; }
-    // keyed: samples per workgroup (the mean contraction is shared by them; a per-sample input takes one)
-    // (2 O = 128 keeps two: with four its 40 accumulator blocks + the samples' masks spill, 192 VGPRs per lane)
-    const int ns = !keyed ? 0 : (x_sample_stride != 0 || nsamples == 1) ? 1 : (nsamples == 2 || bn == 128) ? 2 : 4;
     if (keyed) {
         const int rc = check_flip_args(who, sh->B, (int64_t)sh->O + sh->C, nsamples, rng);
         if (rc) return rc;
     }
     ConvParams p{};
-    const int64_t img_bytes = (int64_t)sh->H * sh->W * sh->C * 2 + (flip ? (sh->C / 8) * 16 * (keyed ? ns : 1) : 0);   // + sign masks
-    const int64_t rsign = keyed ? (int64_t)ns * sh->O * 4 : 0;      // keyed: an image's R_s of the workgroup's samples, fp32
-    const int P = OH * OW;
     if (x3 && (w_plane_stride % 8 != 0 || w_plane_stride < (int64_t)bn * ldw)) { set_error("%s: bad plane stride", who); return BNN_E_SHAPE; }
-    // ring stages (8 KB / 16 KB each); three-plane operands: the big block for both widths (three image planes), 4 / 3 stages
-    const int st = bn == 64 ? 4 : (x3 ? 3 : flip ? 4 : 6);
-    const int64_t lds_block = (bn == 64 && !x3 && !keyed) ? kConvLds : kConvLdsBig;
-    const int64_t ring = (int64_t)st * bn * 128;
-    int img = 128 / P;                                  // rows per workgroup <= 128
-    while (img > 0 && (img * (img_bytes * (x3 ? 3 : 1) + rsign) + ring > lds_block || (int64_t)img * (sh->O * P * 4 + rsign) > lds_block)) --img;
-    if (img > sh->B) img = sh->B;
-    if (img < 1 || (int64_t)bn * ldw * 2 >= ((int64_t)1 << 32)) { set_error("%s: one image (%lld B bf16) + the weight ring do not fit the LDS block, or more than 128 output pixels per image", who, (long long)img_bytes); return BNN_E_UNSUPPORTED; }
+    if (img < 1) { set_error("%s: one image (%lld B bf16) + the weight ring do not fit the LDS block, or more than 128 output pixels per image", who, (long long)fit.img_bytes); return BNN_E_UNSUPPORTED; }
     p.X = x; p.x_sample_stride = x_sample_stride;
     p.W = reinterpret_cast<const uint16_t *>(w); p.w_sample_stride = w_sample_stride; p.ldw = ldw;
     p.bias = b; p.bias_sample_stride = b_sample_stride;
@@ -2343,6 +2367,20 @@ int bnn_conv2d_flipout_forward_x3(const float *x, const void *w, int64_t w_plane
     if (w_plane_stride <= 0) { set_error("bnn_conv2d_flipout_forward_x3: plane stride of the weights"); return BNN_E_SHAPE; }
     return conv_dense_launch(x, 0, w, 0, ldw, nullptr, 0, sign_in, sign_out, y, 0, sh, 1, flags, stream, "bnn_conv2d_flipout_forward_x3",
                              w_plane_stride);
+}
+
+int bnn_conv2d_dense_images(const bnn_conv2d_shape_t *sh, int variant, int nsamples, int shared_x)
+{
+    const char *who = "bnn_conv2d_dense_images";
+    if (!sh) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if (variant < BNN_CONV_DENSE || variant > BNN_CONV_FLIPOUT_MC) { set_error("%s: unknown variant", who); return BNN_E_RANGE; }
+    const bool keyed = variant == BNN_CONV_FLIPOUT_MC, x3 = variant == BNN_CONV_DENSE_X3 || variant == BNN_CONV_FLIPOUT_X3;
+    const bool flip = variant >= BNN_CONV_FLIPOUT;
+    const int64_t ldw = ((int64_t)sh->C * sh->KH * sh->KW + 63) / 64 * 64;
+    ConvFit fit;
+    const int rc = conv_dense_fit(who, sh, keyed ? nsamples : 1, 0, flip, x3, keyed, shared_x != 0, ldw, &fit);
+    if (rc) return rc;
+    return fit.family && fit.img > 0 ? fit.img : 0;
 }
 
 }  // extern "C"

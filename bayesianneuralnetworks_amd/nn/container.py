@@ -237,9 +237,6 @@ class BayesianNetworkModule(Module):
                 y = self._forward(x, *args, **kwargs)
             finally:
                 for m in drawn:
-                    left = getattr(m, "_predrawn", None)
-                    if left is not None:
-                        left[1].wait()          # a layer `_forward` never reached: join its side-stream draw anyway
                     m._predrawn = None
         from .. import ops
         if isinstance(y, ops.HeadPartials):
@@ -308,14 +305,7 @@ class BayesianNetworkModule(Module):
             specs = specs_of(todo) + [(m.weight.mean.detach(), m.weight.scale.detach(), None, None, _flipout_fresh_key(m, ctx), None, 0, _lib.DRAW_FLIPOUT)
                                       for m in flips]
             todo = todo + flips
-            if ops.DRAW_SIDE_STREAM and len(specs) > 1:
-                # the first layer's weights on the main stream; the rest (and the KL's first pass) on a side stream, where the
-                # VALU-bound draw runs beside the first layer's draw and DMA / MFMA-bound contraction
-                dev = specs[0][0].device
-                pre = ops.draw_layers(specs[:1], ctx.samples)
-                pre += ops.draw_layers(specs[1:], ctx.samples, kl=kl, stream=ops.side_stream(dev))
-            else:
-                pre = ops.draw_layers(specs, ctx.samples, kl=kl)
+            pre = ops.draw_layers(specs, ctx.samples, kl=kl)
         if todo3:
             # fp32 parity mode: the network input's three bf16 planes (what the first dense layer would launch bnn_split_bf16x3
             # for) ride in the same launch; the layer that is called with this very tensor takes them (ctx.x_planes)

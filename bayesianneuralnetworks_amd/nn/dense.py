@@ -157,8 +157,6 @@ class _NormalSampling:
             xb, ldx, xs = x2.contiguous().to(torch.bfloat16), K, per * K
         head._predrawn = None                                   # the head's drawn weights are consumed here ...
         head._adopt_keys(hd[1].key_w, hd[1].key_b)              # ... and this is its sample() for this forward
-        predrawn.wait()
-        hd[1].wait()
         hp = ops._dense_head_raw(xb, 0 if shared else xs, per, predrawn, K, self.activation == 'relu', hd[1], ldx=ldx)
         hp.head = head
         return hp

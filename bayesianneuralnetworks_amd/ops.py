@@ -148,54 +148,40 @@ def dense_eligible(mu_w):
 class Predrawn:
     """The drawn weights of one layer for one forward: w (S, N, Kp) bf16 zero-padded to Kp = roundup(K, 64) -- or, drawn
     for the fp32 parity mode, (3, S, N, Kp): the three bf16 planes of the fp32 draw -- b (S, N) fp32 or None, and the
-    DrawKeys they were drawn with.  `ready`: the side stream the draw was launched on
-    (the consumer's stream waits for it before the contraction), or None."""
-    __slots__ = ("w", "b", "key_w", "key_b", "ready")
+    DrawKeys they were drawn with."""
+    __slots__ = ("w", "b", "key_w", "key_b")
 
-    def __init__(self, w, b, key_w, key_b, ready=None):
-        self.w, self.b, self.key_w, self.key_b, self.ready = w, b, key_w, key_b, ready
-
-    def wait(self):
-        """Make the current stream wait for the draw (once: later consumers of the same side-stream launch are ordered
-        behind this one on the same stream)."""
-        if self.ready is not None:
-            torch.cuda.current_stream(self.w.device).wait_stream(self.ready)
-            self.ready = None
+    def __init__(self, w, b, key_w, key_b):
+        self.w, self.b, self.key_w, self.key_b = w, b, key_w, key_b
 
 
-_side_streams = {}
+def _draw_slot(t, mu, rho, rows, cols, out, ld, sample_stride, dtype, kind=_lib.DRAW_SAMPLE, taps=0, key=None):
+    """Fills one bnn_draw_tensor_t (include/bnn_hip.h): the (rows, cols) source tensors mu / rho (rho None: a kind that reads mu
+    alone), `out` the address of draw 0 -- rows of ld elements of `dtype`, the draws sample_stride elements apart -- the kind
+    (_lib.DRAW_*), taps = KH * KW of a conv weight written tap-major, and the DrawKey of a kind that draws."""
+    t.mu, t.rho, t.rows, t.cols = mu.data_ptr(), (mu if rho is None else rho).data_ptr(), rows, cols
+    t.out, t.ld, t.out_sample_stride, t.out_dtype = out, ld, sample_stride, dtype
+    t.kind, t.taps = kind, taps
+    if key is not None:
+        t.rng = _rng_struct(key, mu.device)
 
 
-def side_stream(device):
-    """One extra stream per device for work that runs BESIDE the main stream's launches (draw of the later layers under the
-    first layers' contractions: the draw is VALU-bound, the dense GEMM DMA / MFMA-bound, and their workgroups fit a CU
-    together)."""
-    key = (device.type, device.index)
-    st = _side_streams.get(key)
-    if st is None:
-        st = torch.cuda.Stream(device)
-        _side_streams[key] = st
-    return st
+def _draw_launch(arr, n, nsamples, device):
+    """ONE bnn_draw_multi launch of the first n slots of arr (no KL riding along)."""
+    check(_lib.load().bnn_draw_multi(arr, n, nsamples, None, 0, None, stream_ptr(device)), "bnn_draw_multi")
 
 
-def draw_layers(layers, nsamples, kl=None, stream=None, x3=False, split=None):
+def draw_layers(layers, nsamples, kl=None, x3=False, split=None):
     """ONE launch (bnn_draw_multi) draws the weights and biases of every (mu_w, rho_w, mu_b, rho_b, key_w, key_b) in
     `layers` for `nsamples` MC samples -> list of Predrawn.  kl (a KlDeferred from kl_normal_begin(carry=True)): the
     launch also carries that KL's first pass.  At most 4 layers (8 tensors) per launch; more are split.
-    stream: launch on that side stream (forked from the current one here; consumers join through Predrawn.wait()).
     x3: weights as three bf16 planes of the fp32 draw (BNN_BF16X3; the fp32 parity mode's dense path).
     split (x3 only): an fp32 (M, K) activation whose three-plane split (what split_x3 returns) rides in the FIRST launch as one more
-    tensor (kind 3) instead of a launch of its own; the planes come back as `_tls.last_split`."""
+    tensor (kind BNN_DRAW_COPY) instead of a launch of its own; the planes come back as `_tls.last_split`."""
     _tls.last_split = None
     out = []
     lib = _lib.load()
     dev = layers[0][0].device
-    cur = torch.cuda.current_stream(dev)
-    if stream is not None:
-        stream.wait_stream(cur)                     # fork: the draw is ordered behind everything already on the main stream
-    launch_stream = stream if stream is not None else cur
-    sp = _lib.stream_ptr(dev)
-    sp.value = launch_stream.cuda_stream
     step = 4 if split is None else 3                # (8 tensors per launch: the split takes one)
     for i0 in range(0, len(layers), step):
         group = layers[i0:i0 + step]
@@ -207,50 +193,39 @@ def draw_layers(layers, nsamples, kl=None, stream=None, x3=False, split=None):
             Ms, Ks = split.shape
             lds_ = _pad64(Ks)
             planes = torch.empty((3, 1, Ms, lds_), dtype=torch.bfloat16, device=dev)
-            t = arr[n]
-            t.mu, t.rho, t.rows, t.cols = split.data_ptr(), split.data_ptr(), Ms, Ks
-            t.out, t.ld, t.out_sample_stride, t.out_dtype = planes.data_ptr(), lds_, Ms * lds_, _lib.BF16X3
-            t.kind, t.taps = 3, 0
+            _draw_slot(arr[n], split, None, Ms, Ks, planes.data_ptr(), lds_, Ms * lds_, _lib.BF16X3, _lib.DRAW_COPY)
             n += 1
             _tls.last_split = planes
             keep.append(split)
         for spec in group:
             mu_w, rho_w, mu_b, rho_b, key_w, key_b = spec[:6]
             taps = spec[6] if len(spec) > 6 else 0      # KH * KW: a conv weight, written tap-major
-            kind = spec[7] if len(spec) > 7 else 0      # _lib.DRAW_FLIPOUT (16): a Flipout draw (eps = the key's sign outer product)
+            kind = spec[7] if len(spec) > 7 else _lib.DRAW_SAMPLE      # _lib.DRAW_FLIPOUT: a Flipout draw (eps = the key's sign outer product)
             require_cuda_f32(mu_w, "weight.mean")
             require_cuda_f32(rho_w, "weight.scale")
             N, K = mu_w.shape
             kp = _pad64(K)
             w = torch.empty(((3, nsamples, N, kp) if x3 else (nsamples, N, kp)), dtype=torch.bfloat16, device=dev)
-            t = arr[n]
-            t.mu, t.rho, t.rows, t.cols = mu_w.data_ptr(), rho_w.data_ptr(), N, K
-            t.out, t.ld, t.out_sample_stride, t.out_dtype = w.data_ptr(), kp, N * kp, (_lib.BF16X3 if x3 else _lib.BF16)
-            t.taps, t.kind = taps, kind
-            t.rng = _rng_struct(key_w, dev)
+            _draw_slot(arr[n], mu_w, rho_w, N, K, w.data_ptr(), kp, N * kp, _lib.BF16X3 if x3 else _lib.BF16, kind, taps, key_w)
             n += 1
             b = None
             if mu_b is not None:
                 require_cuda_f32(mu_b, "bias.mean")
                 require_cuda_f32(rho_b, "bias.scale")
                 b = torch.empty((nsamples, N), dtype=torch.float32, device=dev)
-                t = arr[n]
-                t.mu, t.rho, t.rows, t.cols = mu_b.data_ptr(), rho_b.data_ptr(), 1, N
-                t.out, t.ld, t.out_sample_stride, t.out_dtype = b.data_ptr(), N, N, _lib.F32
-                t.taps = 0
-                t.rng = _rng_struct(key_b, dev)
+                _draw_slot(arr[n], mu_b, rho_b, 1, N, b.data_ptr(), N, N, _lib.F32, key=key_b)
                 n += 1
             keep.append((mu_w, rho_w, mu_b, rho_b))
-            out.append(Predrawn(w, b, key_w, key_b, ready=stream))
+            out.append(Predrawn(w, b, key_w, key_b))
         carried = False
         if kl is not None and not kl.launched and i0 == 0 and kl.out.device == dev:
-            rc = lib.bnn_draw_multi(arr, n, nsamples, kl.arr, kl.T, ptr(kl.ws), sp)
+            rc = lib.bnn_draw_multi(arr, n, nsamples, kl.arr, kl.T, ptr(kl.ws), stream_ptr(dev))
             if rc == 0:
                 kl.launched = carried = True
             elif rc != _lib.E_UNSUPPORTED:
                 check(rc, "bnn_draw_multi")
         if not carried:
-            check(lib.bnn_draw_multi(arr, n, nsamples, None, 0, None, sp), "bnn_draw_multi")
+            _draw_launch(arr, n, nsamples, dev)
     return out
 
 
@@ -455,7 +430,6 @@ def linear_sampled_x3(x2, shared, M, mu_w, rho_w, mu_b, rho_b, key_w, key_b, rel
         pre = draw_layers([(mu_w, rho_w, mu_b, rho_b, key_w, key_b)], S, kl=_tls.kl_carry, x3=True)[0]
         if _tls.kl_carry is not None and _tls.kl_carry.launched:
             _tls.kl_carry = None
-    pre.wait()
     if isinstance(x2, X3Activation):
         xp = x2.planes
         if xp.shape[1] not in (1, S) or xp.shape[2] != M or x2.cols != K:
@@ -466,7 +440,6 @@ def linear_sampled_x3(x2, shared, M, mu_w, rho_w, mu_b, rho_b, key_w, key_b, rel
         if not shared:
             xp = xp.view(3, S, M, xp.shape[3])
     if head_pre is not None:
-        head_pre.wait()
         return _dense_head_raw_x3(xp, shared, M, pre, K, relu, head_pre)
     return _dense_raw_x3(xp, shared, M, pre, K, relu, planes_out)
 
@@ -486,7 +459,6 @@ def _linear_sampled_raw(x2, x_sample_stride, M, mu_w, rho_w, mu_b, rho_b, key_w,
             pre = draw_layers([(mu_w, rho_w, mu_b, rho_b, key_w, key_b)], S, kl=_tls.kl_carry)[0]
             if _tls.kl_carry is not None and _tls.kl_carry.launched:
                 _tls.kl_carry = None
-        pre.wait()
         pitch = rows_pitch(x2, K) if x2.dtype == torch.bfloat16 else None
         if pitch is not None:
             ldx, xs = pitch
@@ -545,9 +517,6 @@ DRAW_ONCE_MIN_ROWS = 2048
 # bf16 compute mode: draw once + dense GEMM at every batch size (False: the round-1 fused kernel, kept for A/B runs)
 DRAW_ONCE_BF16 = True
 DENSE_X3_F32 = os.environ.get("BNN_DENSE_X3", "1") != "0"    # fp32 parity mode of wide inference layers on the dense kernel
-# BNN_DRAW_SIDE=1: a network draw plan launches the layers after the first on a side stream, beside the first layer draw + contraction
-# (measured on the BASELINE step: SLOWER, 0.0832 vs 0.0749 ms -- the cross-queue dependency costs more than the overlap hides; off)
-DRAW_SIDE_STREAM = os.environ.get("BNN_DRAW_SIDE", "0") == "1"
 
 
 def _bf(t):
@@ -679,6 +648,52 @@ def _sum_samples(t):
     return out
 
 
+def _wgrad_sampled_raw(x, x_sample_stride, gy, mu_w, rho_w, mu_b, rho_b, rw, key_b, M, N, K, S, need_b, compute, flags, *,
+                       kl_weight, kl_bias, narrow_gx=None):
+    """The sampled layer's weight-gradient launch (bnn_linear_backward_weight_sampled: x (., M, K), gy (S, M, N)) with the bias
+    gradient (need_b) and the KL gradient KLDivergence's backward parked for this layer riding along -> (g_mu_w, g_rho_w,
+    g_mu_b, g_rho_b).  What differs between its three callers is spelled out by them:
+      kl_weight  take the weight's parked KL entry (the general linear site: M > 0 -- an empty batch zero-fills, the flush adds KL);
+      kl_bias    ... and with it the bias's (False at the conv site: a conv bias entry is left to the flush);
+      narrow_gx  (gx,), gx (S, M, K) or None: the narrow layer's one-pass kernel (bnn_linear_backward_narrow_sampled), which
+                 writes the input gradient too.  Where it does not apply (workspace, alignment) the KL entries go back to
+                 _tls.kl_pending and the answer is None: the caller falls through to the general kernels."""
+    dev = gy.device
+    g_mu_w, g_rho_w = torch.empty_like(mu_w), torch.empty_like(rho_w)
+    g_mu_b = g_rho_b = rb = None
+    if need_b:                                                         # bias gradient rides in the same launch
+        g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
+        rb = _rng_struct(key_b, dev)
+    ent_w = _kl_take(mu_w) if kl_weight else None
+    ent_b = _kl_take(mu_b) if (kl_bias and ent_w is not None and need_b and mu_b is not None) else None
+    kl = _kl_fuse_struct(ent_w, ent_b) if ent_w is not None else None
+    grads = (ptr(g_mu_w), ptr(g_rho_w), ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), M, N, K, S, ctypes.byref(rw),
+             ctypes.byref(rb) if rb is not None else None, ctypes.byref(kl) if kl is not None else None)
+    lib = _lib.load()
+    if narrow_gx is None:
+        check(lib.bnn_linear_backward_weight_sampled(ptr(x), x_sample_stride, K, ptr(gy), M * N, N, ptr(rho_w), *grads,
+                                                     compute, flags, 0, stream_ptr(dev)), "bnn_linear_backward_weight_sampled")
+        return g_mu_w, g_rho_w, g_mu_b, g_rho_b
+    rc = lib.bnn_linear_backward_narrow_sampled(ptr(x), x_sample_stride, K, ptr(gy), M * N, N, ptr(mu_w), ptr(rho_w),
+                                                ptr(narrow_gx[0]), M * K, K, *grads, flags, 0, stream_ptr(dev))
+    if rc == 0:
+        return g_mu_w, g_rho_w, g_mu_b, g_rho_b
+    if rc not in (_lib.E_UNSUPPORTED, _lib.E_ALIGN):
+        check(rc, "bnn_linear_backward_narrow_sampled")
+    for e in (ent_w, ent_b):
+        if e is not None:
+            _tls.kl_pending[(e.mu.device.index, e.mu.data_ptr())] = e
+    return None
+
+
+def _wgrad_plain_raw(x, x_sample_stride, gy, M, N, K, S, compute=_lib.COMPUTE_F32):
+    """gw[s] = gy[s]^T x[s] for explicit weights (bnn_linear_backward_weight): x (., M, K), gy (S, M, N) fp32 -> (S, N, K) fp32."""
+    gw = torch.empty((S, N, K), dtype=torch.float32, device=gy.device)
+    check(_lib.load().bnn_linear_backward_weight(ptr(x), x_sample_stride, K, ptr(gy), M * N, N, ptr(gw), N * K, M, N, K, S,
+                                                 compute, 0, 0, stream_ptr(gy.device)), "bnn_linear_backward_weight")
+    return gw
+
+
 class _SampledLinear(torch.autograd.Function):
     """y[s] = x[s] @ w_s^T + b_s, w_s / b_s drawn in-kernel (NormalLinear.forward, dense.py:56-60).
     Backward (what autograd derives in the reference, train.py:63-65) is HIP as well: the input
@@ -743,31 +758,14 @@ class _SampledLinear(torch.autograd.Function):
         if N <= 16 and K % 4 == 0 and M > 0 and need_w and not _bf(gy) and not (ctx.shared_x and ctx.needs_input_grad[0]):
             # narrow layer (classifier head): the whole backward in one pass over the activations
             need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
-            g_mu_w, g_rho_w = torch.empty_like(mu_w), torch.empty_like(rho_w)
-            rb = None
-            if need_b:
-                g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
-                rb = _rng_struct(ctx.key_b, dev)
             if ctx.needs_input_grad[0]:
                 gx = torch.empty((S, M, K), dtype=x.dtype, device=dev)
-            ent_w = _kl_take(mu_w)
-            ent_b = _kl_take(mu_b) if (ent_w is not None and need_b and mu_b is not None) else None
-            kl = _kl_fuse_struct(ent_w, ent_b) if ent_w is not None else None
             flags = (_lib.FLAG_X_BF16 if _bf(x) else 0) | (_lib.FLAG_Y_BF16 if (gx is not None and _bf(gx)) else 0)
-            rc = lib.bnn_linear_backward_narrow_sampled(
-                ptr(x), 0 if ctx.shared_x else M * K, K, ptr(gy), M * N, N, ptr(mu_w), ptr(rho_w), ptr(gx), M * K, K,
-                ptr(g_mu_w), ptr(g_rho_w), ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), M, N, K, S,
-                ctypes.byref(rw), ctypes.byref(rb) if rb is not None else None,
-                ctypes.byref(kl) if kl is not None else None, flags, 0, stream_ptr(dev))
-            if rc == 0:
-                return gx, g_mu_w, g_rho_w, g_mu_b, g_rho_b, None, None, None, None, None, None, None, None
-            if rc not in (_lib.E_UNSUPPORTED, _lib.E_ALIGN):
-                check(rc, "bnn_linear_backward_narrow_sampled")
-            # not applicable here (workspace, alignment): the general kernels below; hand the KL entries back
-            for e in (ent_w, ent_b):
-                if e is not None:
-                    _tls.kl_pending[(e.mu.device.index, e.mu.data_ptr())] = e
-            gx = g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
+            grads = _wgrad_sampled_raw(x, 0 if ctx.shared_x else M * K, gy, mu_w, rho_w, mu_b, rho_b, rw, ctx.key_b, M, N, K, S, need_b,
+                                       compute, flags, kl_weight=True, kl_bias=True, narrow_gx=(gx,))
+            if grads is not None:
+                return (gx,) + grads + (None,) * 8
+            gx = None               # not applicable here (workspace, alignment): the general kernels below
         if ctx.needs_input_grad[0]:
             # a shared input sums its gradient over the samples: fp32 partials, then one reduction
             gx_dtype = torch.float32 if ctx.shared_x else x.dtype
@@ -788,26 +786,10 @@ class _SampledLinear(torch.autograd.Function):
                 gx = _sum_samples(gx).to(x.dtype)
         need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            g_mu_w = torch.empty_like(mu_w)
-            g_rho_w = torch.empty_like(rho_w)
             flags = (_lib.FLAG_X_BF16 if _bf(x) else 0) | (_lib.FLAG_Y_BF16 if _bf(gy) else 0)
-            rb = None
-            if need_b:                                                     # bias gradient rides in the same launch
-                g_mu_b = torch.empty_like(rho_b)
-                g_rho_b = torch.empty_like(rho_b)
-                rb = _rng_struct(ctx.key_b, dev)
-            # ... and so does the KL gradient, when KLDivergence's backward parked it for this layer
-            ent_w = _kl_take(mu_w) if M > 0 else None                     # (an empty batch zero-fills; the flush adds KL)
-            ent_b = _kl_take(mu_b) if (ent_w is not None and need_b and mu_b is not None) else None
-            kl = _kl_fuse_struct(ent_w, ent_b) if ent_w is not None else None
-            check(lib.bnn_linear_backward_weight_sampled(ptr(x), 0 if ctx.shared_x else M * K, K, ptr(gy), M * N, N,
-                                                         ptr(rho_w), ptr(g_mu_w), ptr(g_rho_w),
-                                                         ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b),
-                                                         M, N, K, S, ctypes.byref(rw),
-                                                         ctypes.byref(rb) if rb is not None else None,
-                                                         ctypes.byref(kl) if kl is not None else None,
-                                                         compute, flags, 0, stream_ptr(dev)),
-                  "bnn_linear_backward_weight_sampled")
+            g_mu_w, g_rho_w, g_mu_b, g_rho_b = _wgrad_sampled_raw(
+                x, 0 if ctx.shared_x else M * K, gy, mu_w, rho_w, mu_b, rho_b, rw, ctx.key_b, M, N, K, S, need_b, compute, flags,
+                kl_weight=M > 0, kl_bias=True)
         elif need_b:
             gb = _colsum_raw(gy)                                           # (S, N)
             g_mu_b, g_rho_b = _sample_affine_bwd_raw(gb, rho_b, rho_b.numel(), S, key=ctx.key_b)
@@ -966,10 +948,7 @@ class _PlainLinear(torch.autograd.Function):
             if ctx.shared_x:
                 gx = _sum_samples(gx)
         if ctx.needs_input_grad[1]:
-            gw = torch.empty_like(w)
-            check(_lib.load().bnn_linear_backward_weight(ptr(x), 0 if ctx.shared_x else M * K, K, ptr(gy), M * N, N,
-                                                         ptr(gw), N * K, M, N, K, S, ctx.compute, 0, 0,
-                                                         stream_ptr(gy.device)), "bnn_linear_backward_weight")
+            gw = _wgrad_plain_raw(x, 0 if ctx.shared_x else M * K, gy, M, N, K, S, ctx.compute)
         if ctx.has_b and ctx.needs_input_grad[2]:
             gb = _colsum_raw(gy)
         return gx, gw, gb, None, None
@@ -1043,17 +1022,14 @@ def mc_dropout(y, p, key, shared):
 
 
 def mean_bf16(w):
-    """The fp32 weight (N, K) as the dense kernel's operand: (1, N, roundup(K, 64)) bf16 zero-padded (bnn_draw_multi kind 1)."""
+    """The fp32 weight (N, K) as the dense kernel's operand: (1, N, roundup(K, 64)) bf16 zero-padded (bnn_draw_multi kind BNN_DRAW_MEAN)."""
     require_cuda_f32(w, "weight")
     N, K = w.shape
     kp = _pad64(K)
     out = torch.empty((1, N, kp), dtype=torch.bfloat16, device=w.device)
     arr = (_lib.DrawTensor * 1)()
-    t = arr[0]
-    t.mu, t.rho, t.rows, t.cols = w.data_ptr(), w.data_ptr(), N, K
-    t.out, t.ld, t.out_sample_stride, t.out_dtype = out.data_ptr(), kp, N * kp, _lib.BF16
-    t.kind, t.taps = 1, 0
-    check(_lib.load().bnn_draw_multi(arr, 1, 1, None, 0, None, stream_ptr(w.device)), "bnn_draw_multi")
+    _draw_slot(arr[0], w, None, N, K, out.data_ptr(), kp, N * kp, _lib.BF16, _lib.DRAW_MEAN)
+    _draw_launch(arr, 1, 1, w.device)
     return out
 
 
@@ -1105,15 +1081,12 @@ def _plain_linear_bwd(ctx, x, w, g):
     """(gx, gw, gb) of y = x w^T + b for ONE weight over all rows of x (M, K) / g (M, N), fp32."""
     N, K = w.shape
     M = x.shape[0]
-    lib = _lib.load()
     gx = gw = gb = None
     g3 = g.view(1, M, N)
     if ctx.needs_input_grad[0]:
         gx = _dgrad_plain_raw(g3, w.view(1, N, K), torch.float32).view(M, K)
     if ctx.needs_input_grad[1]:
-        gw = torch.empty_like(w)
-        check(lib.bnn_linear_backward_weight(ptr(x), M * K, K, ptr(g), M * N, N, ptr(gw), N * K, M, N, K, 1,
-                                             _lib.COMPUTE_F32, 0, 0, stream_ptr(g.device)), "bnn_linear_backward_weight")
+        gw = _wgrad_plain_raw(x, M * K, g, M, N, K, 1).view(N, K)
     if ctx.has_b and ctx.needs_input_grad[2]:
         gb = _colsum_raw(g3).view(N)
     return gx, gw, gb
@@ -1160,13 +1133,9 @@ def flipout_draw(mu, rho, key, out_dtype=torch.float32, pad=False):
     S = key.nsamples
     w = torch.empty((S, O, ld), dtype=out_dtype, device=mu.device)
     arr = (_lib.DrawTensor * 1)()
-    t = arr[0]
-    t.mu, t.rho, t.rows, t.cols = mu.data_ptr(), rho.data_ptr(), O, K
-    t.out, t.ld, t.out_sample_stride = w.data_ptr(), ld, O * ld
-    t.out_dtype = _lib.F32 if out_dtype == torch.float32 else _lib.BF16
-    t.kind, t.taps = _lib.DRAW_FLIPOUT, 0
-    t.rng = _rng_struct(key, mu.device)
-    check(_lib.load().bnn_draw_multi(arr, 1, S, None, 0, None, stream_ptr(mu.device)), "bnn_draw_multi")
+    _draw_slot(arr[0], mu, rho, O, K, w.data_ptr(), ld, O * ld, _lib.F32 if out_dtype == torch.float32 else _lib.BF16,
+               _lib.DRAW_FLIPOUT, key=key)
+    _draw_launch(arr, 1, S, mu.device)
     return w
 
 
@@ -1193,7 +1162,6 @@ class _FlipoutLinear(torch.autograd.Function):
             pre = predrawn
             if pre is None:
                 pre = Predrawn(flipout_draw(mu, rho, key, torch.bfloat16, pad=True), None, key, None)
-            pre.wait()
             xb = x.to(torch.bfloat16).contiguous()
             y = _dense_raw(xb, 0 if shared else B * K, B, pre, K, False, torch.float32)
         else:
@@ -1219,9 +1187,7 @@ class _FlipoutLinear(torch.autograd.Function):
             gx = _dgrad_plain_raw(gy, flipout_draw(mu, rho, key), torch.float32)       # (S, B, K)
             gx = _sum_samples(gx) if ctx.shared else gx.reshape(S * B, K)
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            gw = torch.empty((S, O, K), dtype=torch.float32, device=dev)
-            check(lib.bnn_linear_backward_weight(ptr(x), 0 if ctx.shared else B * K, K, ptr(gy), B * O, O, ptr(gw), O * K, B, O, K,
-                                                 S, _lib.COMPUTE_F32, 0, 0, stream_ptr(dev)), "bnn_linear_backward_weight")
+            gw = _wgrad_plain_raw(x, 0 if ctx.shared else B * K, gy, B, O, K, S)
             g_mu, g_rho = torch.empty_like(mu), torch.empty_like(rho)
             r = _rng_struct(key, dev)
             check(lib.bnn_flipout_weight_backward(ptr(gw), O * K, ptr(rho), ptr(g_mu), ptr(g_rho), O, K, S, ctypes.byref(r),
@@ -1239,19 +1205,14 @@ def linear_flipout_mc(x, mu, rho, key, shared, compute="f32", predrawn=None):
 def conv2d_flipout_mc_eligible(x, mean, stride, padding, dilation, groups, S, shared):
     """bf16 compute, inference: the keyed one-launch Flipout conv (bnn_conv2d_flipout_forward_mc) takes this layer -- the shapes
     of bnn_conv2d_flipout_forward, with the samples' masks and R signs in the LDS block too."""
-    if not (DRAW_ONCE_BF16 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and groups == 1):
+    if not (DRAW_ONCE_BF16 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and mean.data_ptr() % 16 == 0):
         return False
     O, C, KH, KW = mean.shape
-    if not ((C == 64 or C % 128 == 0) and O in (32, 64) and mean.data_ptr() % 16 == 0):
-        return False
     B = x.shape[0] if shared else x.shape[0] // S
-    sh, OH, OW = _conv_shape((B,) + tuple(x.shape[1:]), mean.shape, stride, padding, dilation, groups)
-    if OH < 1 or OW < 1 or OH * OW > 128 or B * (O + C) >= 2 ** 32 or S > 0xFFFF:
+    if B * (O + C) >= 2 ** 32 or S > 0xFFFF:
         return False
-    ns = 1 if (not shared or S == 1) else 2 if (S == 2 or O == 64) else 4          # (as bnn_dense.hip chooses)
-    block = 136 * 1024
-    rsign = ns * O * 4
-    return sh.H * sh.W * C * 2 + ns * (C // 8) * 16 + rsign + 4 * 2 * O * 128 <= block and O * OH * OW * 4 + rsign <= block
+    sh = _conv_shape((B,) + tuple(x.shape[1:]), mean.shape, stride, padding, dilation, groups)[0]
+    return _conv_lds_images(sh, _lib.CONV_FLIPOUT_MC, S, shared) > 0
 
 
 def conv2d_flipout_mc(x, mean, scale, key, shared, stride, padding, dilation):
@@ -1298,34 +1259,62 @@ def _conv_workspace(sh, x_samples, compute, device):
     return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
 
 
-_CONV_LDS = {64: (78 * 1024, 4), 128: (136 * 1024, 6)}       # O -> (LDS block, ring stages) of k_conv_bf16
+def _conv_lds_images(sh, variant, nsamples=1, shared_x=True):
+    """Images a workgroup of the LDS-resident conv launch `variant` (_lib.CONV_*) keeps, 0 where that launch does not take the
+    shape: the library's own fit computation (bnn_conv2d_dense_images, a host query), so the predicates below cannot drift from
+    the kernel's ring depths and LDS blocks.  (A kernel larger than the padded input is a negative code: not taken either.)"""
+    return _lib.load().bnn_conv2d_dense_images(ctypes.byref(sh), variant, nsamples, int(shared_x))
 
 
 def conv_dense_eligible(sh, OH, OW):
     """Shapes bnn_conv2d_dense_forward is built for (include/bnn_hip.h): both BASELINE conv layers."""
-    if sh.groups != 1 or not (sh.C == 64 or sh.C % 128 == 0) or sh.O not in (64, 128):
-        return False
-    P = OH * OW
-    if P > 128:
-        return False
-    img_bytes = sh.H * sh.W * sh.C * 2
-    block, st = _CONV_LDS[sh.O]
-    return img_bytes + st * sh.O * 128 <= block and sh.O * P * 4 <= block
+    return _conv_lds_images(sh, _lib.CONV_DENSE) > 0
 
 
-_CONV_LDS_X3 = {64: (136 * 1024, 4), 128: (136 * 1024, 3)}   # fp32 parity mode: three image planes, the big block for both widths
 CONV_X3_F32 = os.environ.get("BNN_CONV_X3", "1") != "0"      # fp32 parity mode of eligible inference convolutions without the im2col panel
 
 
 def conv_dense_x3_eligible(sh, OH, OW):
     """Shapes bnn_conv2d_dense_forward_x3 takes: as conv_dense_eligible with three bf16 planes of an image resident."""
-    if sh.groups != 1 or not (sh.C == 64 or sh.C % 128 == 0) or sh.O not in (64, 128):
-        return False
-    P = OH * OW
-    if P > 128:
-        return False
-    block, st = _CONV_LDS_X3[sh.O]
-    return 3 * sh.H * sh.W * sh.C * 2 + st * sh.O * 128 <= block and sh.O * P * 4 <= block
+    return _conv_lds_images(sh, _lib.CONV_DENSE_X3) > 0
+
+
+def _conv_rows_raw(gy, sh, P, S, bf):
+    """gy (S, B, O, OH, OW) fp32 -> the rows (S, B P, O) of the conv seen as a linear layer, fp32 or bf16 (bnn_nchw_to_rows)."""
+    rows = torch.empty((S, sh.B * P, sh.O), dtype=torch.bfloat16 if bf else torch.float32, device=gy.device)
+    check(_lib.load().bnn_nchw_to_rows(ptr(gy), S * sh.B, sh.O, P, ptr(rows), int(bf), stream_ptr(gy.device)), "bnn_nchw_to_rows")
+    return rows
+
+
+def _conv_panel_raw(x, sh, M, K, S, shared_x, bf):
+    """x -> its im2col panel (1 or S, M, K), fp32 or bf16 (bnn_conv2d_im2col) -> (panel, its sample stride)."""
+    nsx = 1 if shared_x else S
+    panel = torch.empty((nsx, M, K), dtype=torch.bfloat16 if bf else torch.float32, device=x.device)
+    per = sh.B * sh.C * sh.H * sh.W
+    check(_lib.load().bnn_conv2d_im2col(ptr(x), 0 if shared_x else per, ctypes.byref(sh), nsx, ptr(panel), int(bf), stream_ptr(x.device)),
+          "bnn_conv2d_im2col")
+    return panel, 0 if shared_x else M * K
+
+
+def _conv_col2im_raw(gpanel, sh, S, shared_x):
+    """The panel's gradient (S, M, K) fp32 -> gx (B, C, H, W) summed over the samples (shared x) or (S, B, C, H, W) (bnn_conv2d_col2im)."""
+    gx = torch.empty((sh.B, sh.C, sh.H, sh.W) if shared_x else (S, sh.B, sh.C, sh.H, sh.W), dtype=torch.float32, device=gpanel.device)
+    check(_lib.load().bnn_conv2d_col2im(ptr(gpanel), ctypes.byref(sh), S, int(shared_x), ptr(gx), stream_ptr(gpanel.device)), "bnn_conv2d_col2im")
+    return gx
+
+
+def _conv2d_torch_bwd(x, w, gy, shared_x, conv_args, need_x, need_w):
+    """Where the panel does not apply (groups > 1, K % 8 != 0): torch's conv gradients per sample on explicit weights w (S, O, Cg,
+    KH, KW) -> (gx, gw), None where not wanted; gx summed over the samples for a shared x."""
+    gxs, gws = [], []
+    for s in range(w.shape[0]):
+        xs_ = x if shared_x else x[s]
+        if need_x:
+            gxs.append(torch.nn.grad.conv2d_input(xs_.shape, w[s], gy[s], *conv_args))
+        if need_w:
+            gws.append(torch.nn.grad.conv2d_weight(xs_, w[s].shape, gy[s], *conv_args))
+    gx = (torch.stack(gxs).sum(0) if shared_x else torch.stack(gxs)) if need_x else None
+    return gx, (torch.stack(gws) if need_w else None)
 
 
 class _SampledConv2d(torch.autograd.Function):
@@ -1402,17 +1391,8 @@ class _SampledConv2d(torch.autograd.Function):
         gx = g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
         if need_x or need_w:
             w = _sample_affine_philox_raw(mu_w, rho_w, ctx.key_w)          # (S, O, Cg, KH, KW)
-            gxs, gws = [], []
-            for s in range(S):
-                xs_ = x if ctx.shared_x else x[s]
-                if need_x:
-                    gxs.append(torch.nn.grad.conv2d_input(xs_.shape, w[s], gy[s], stride, padding, dilation, groups))
-                if need_w:
-                    gws.append(torch.nn.grad.conv2d_weight(xs_, w[s].shape, gy[s], stride, padding, dilation, groups))
-            if need_x:
-                gx = torch.stack(gxs).sum(0) if ctx.shared_x else torch.stack(gxs)
+            gx, gw = _conv2d_torch_bwd(x, w, gy, ctx.shared_x, ctx.conv_args, need_x, need_w)
             if need_w:
-                gw = torch.stack(gws)
                 g_mu_w, g_rho_w = _sample_affine_bwd_raw(gw, rho_w, rho_w.numel(), S, key=ctx.key_w)
         if need_b:
             gb = gy.sum((1, 3, 4))
@@ -1426,50 +1406,26 @@ class _SampledConv2d(torch.autograd.Function):
         draw-backward) do the work; only the layout changes (NCHW -> rows, col2im) are conv-specific."""
         x, mu_w, rho_w, rho_b = ctx.saved_tensors
         S, compute, dev = ctx.key_w.nsamples, ctx.compute, gy.device
-        lib = _lib.load()
         _lib.ensure_workspace(dev)
-        st = stream_ptr(dev)
         P, O = OH * OW, sh.O
         M, K = sh.B * P, mu_w[0].numel()
         bf = compute == _lib.COMPUTE_BF16
-        adt = torch.bfloat16 if bf else torch.float32
-        rows = torch.empty((S, M, O), dtype=adt, device=dev)
-        check(lib.bnn_nchw_to_rows(ptr(gy), S * sh.B, O, P, ptr(rows), int(bf), st), "bnn_nchw_to_rows")
+        rows = _conv_rows_raw(gy, sh, P, S, bf)
         rw = _rng_struct(ctx.key_w, dev)
         gx = g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
         aflag = _lib.FLAG_X_BF16 if bf else 0
         if need_w:
-            nsx = 1 if ctx.shared_x else S
-            panel = torch.empty((nsx, M, K), dtype=adt, device=dev)
-            per = sh.B * sh.C * sh.H * sh.W
-            check(lib.bnn_conv2d_im2col(ptr(x), 0 if ctx.shared_x else per, ctypes.byref(sh), nsx, ptr(panel), int(bf), st),
-                  "bnn_conv2d_im2col")
-            g_mu_w = torch.empty_like(mu_w)
-            g_rho_w = torch.empty_like(rho_w)
-            rb = None
-            if need_b:
-                g_mu_b = torch.empty_like(rho_b)
-                g_rho_b = torch.empty_like(rho_b)
-                rb = _rng_struct(ctx.key_b, dev)
-            ent_w = _kl_take(mu_w)
-            kl = _kl_fuse_struct(ent_w, None) if ent_w is not None else None    # (a conv bias entry is left to the flush)
-            check(lib.bnn_linear_backward_weight_sampled(ptr(panel), 0 if ctx.shared_x else M * K, K, ptr(rows), M * O, O,
-                                                         ptr(rho_w), ptr(g_mu_w), ptr(g_rho_w),
-                                                         ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b),
-                                                         M, O, K, S, ctypes.byref(rw),
-                                                         ctypes.byref(rb) if rb is not None else None,
-                                                         ctypes.byref(kl) if kl is not None else None,
-                                                         compute, aflag | (_lib.FLAG_Y_BF16 if bf else 0), 0, st),
-                  "bnn_linear_backward_weight_sampled")
+            panel, pstride = _conv_panel_raw(x, sh, M, K, S, ctx.shared_x, bf)
+            g_mu_w, g_rho_w, g_mu_b, g_rho_b = _wgrad_sampled_raw(
+                panel, pstride, rows, mu_w, rho_w, None, rho_b, rw, ctx.key_b, M, O, K, S, need_b, compute,
+                aflag | (_lib.FLAG_Y_BF16 if bf else 0), kl_weight=True, kl_bias=False)
             need_b = False
         if need_x:
             gpanel = torch.empty((S, M, K), dtype=torch.float32, device=dev)
-            check(lib.bnn_linear_backward_input_sampled(ptr(rows), M * O, O, ptr(mu_w), ptr(rho_w), ptr(gpanel), M * K, K,
-                                                        M, O, K, S, ctypes.byref(rw), compute, aflag, st),
+            check(_lib.load().bnn_linear_backward_input_sampled(ptr(rows), M * O, O, ptr(mu_w), ptr(rho_w), ptr(gpanel), M * K, K,
+                                                                M, O, K, S, ctypes.byref(rw), compute, aflag, stream_ptr(dev)),
                   "bnn_linear_backward_input_sampled")
-            gx = torch.empty((sh.B, sh.C, sh.H, sh.W) if ctx.shared_x else (S, sh.B, sh.C, sh.H, sh.W),
-                             dtype=torch.float32, device=dev)
-            check(lib.bnn_conv2d_col2im(ptr(gpanel), ctypes.byref(sh), S, int(ctx.shared_x), ptr(gx), st), "bnn_conv2d_col2im")
+            gx = _conv_col2im_raw(gpanel, sh, S, ctx.shared_x)
         if need_b:
             gb = _colsum_raw(rows)                                          # (S, O)
             g_mu_b, g_rho_b = _sample_affine_bwd_raw(gb, rho_b, rho_b.numel(), S, key=ctx.key_b)
@@ -1478,16 +1434,10 @@ class _SampledConv2d(torch.autograd.Function):
 
 def conv2d_flipout_eligible(x, mean, stride, padding, dilation, groups):
     """bf16 compute, inference: the one-launch Flipout conv (bnn_conv2d_flipout_forward) takes this layer."""
-    if not (DRAW_ONCE_BF16 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and groups == 1):
+    if not (DRAW_ONCE_BF16 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and mean.data_ptr() % 16 == 0):
         return False
-    O, C, KH, KW = mean.shape
-    if not ((C == 64 or C % 128 == 0) and O in (32, 64) and mean.data_ptr() % 16 == 0):
-        return False
-    sh, OH, OW = _conv_shape(x.shape, mean.shape, stride, padding, dilation, groups)
-    if OH < 1 or OW < 1 or OH * OW > 128:
-        return False
-    block = _CONV_LDS[2 * O][0]
-    return sh.H * sh.W * C * 2 + (C // 8) * 16 + 4 * 2 * O * 128 <= block and O * OH * OW * 4 <= block
+    sh = _conv_shape(x.shape, mean.shape, stride, padding, dilation, groups)[0]
+    return _conv_lds_images(sh, _lib.CONV_FLIPOUT) > 0
 
 
 def conv2d_flipout(x, mean, scale, R, S, stride, padding, dilation):
@@ -1515,15 +1465,10 @@ def conv2d_flipout(x, mean, scale, R, S, stride, padding, dilation):
 def conv2d_flipout_x3_fused_eligible(x, mean, stride, padding, dilation):
     """ONE contraction launch for both of Flipout's convolutions in the fp32 parity mode (bnn_conv2d_flipout_forward_x3): the tile's
     columns are [O means | O stddevs], so 2 O = 64 or 128, and three planes of an image + the ring fit the LDS block."""
-    O, C, KH, KW = mean.shape
-    if not (CONV_X3_F32 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and O in (32, 64) and (C == 64 or C % 128 == 0)
-            and mean.data_ptr() % 16 == 0):
+    if not (CONV_X3_F32 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and mean.data_ptr() % 16 == 0):
         return False
-    sh, OH, OW = _conv_shape(x.shape, mean.shape, stride, padding, dilation, 1)
-    if OH < 1 or OW < 1 or OH * OW > 128:
-        return False
-    block, st = _CONV_LDS_X3[2 * O]
-    return 3 * (sh.H * sh.W * C * 2 + (C // 8) * 16) + st * 2 * O * 128 <= block and O * OH * OW * 4 <= block
+    sh = _conv_shape(x.shape, mean.shape, stride, padding, dilation, 1)[0]
+    return _conv_lds_images(sh, _lib.CONV_FLIPOUT_X3) > 0
 
 
 def conv2d_flipout_x3_fused(x, mean, stddev, R, S, stride, padding, dilation):
@@ -1541,11 +1486,8 @@ def conv2d_flipout_x3_fused(x, mean, stddev, R, S, stride, padding, dilation):
     srcs = (mean.detach().contiguous(), stddev.detach().contiguous())
     for i, src in enumerate(srcs):
         require_cuda_f32(src, "weight")
-        t = arr[i]
-        t.mu, t.rho, t.rows, t.cols = src.data_ptr(), src.data_ptr(), O, K
-        t.out, t.ld, t.out_sample_stride, t.out_dtype = w2.data_ptr() + i * O * kp * 2, kp, 2 * O * kp, _lib.BF16X3
-        t.kind, t.taps = 1, KH * KW
-    check(lib.bnn_draw_multi(arr, 2, 1, None, 0, None, stream_ptr(dev)), "bnn_draw_multi")
+        _draw_slot(arr[i], src, None, O, K, w2.data_ptr() + i * O * kp * 2, kp, 2 * O * kp, _lib.BF16X3, _lib.DRAW_MEAN, KH * KW)
+    _draw_launch(arr, 2, 1, dev)
     sh, OH, OW = _conv_shape(x.shape, mean.shape, stride, padding, dilation, 1)
     y = torch.empty((sh.B, O, OH, OW), dtype=torch.float32, device=dev)
     Sf = S.to(torch.float32).expand(sh.B, C, 1, 1).reshape(sh.B, C).contiguous()
@@ -1578,15 +1520,11 @@ def flipout_conv_weights(mean, scale):
     K = C * KH * KW
     kp = _pad64(K)
     dev = mean.device
-    lib = _lib.load()
     w2 = torch.empty((2 * O, kp), dtype=torch.bfloat16, device=dev)
     arr = (_lib.DrawTensor * 2)()
-    for i, kind in enumerate((1, 2)):
-        t = arr[i]
-        t.mu, t.rho, t.rows, t.cols = mean.data_ptr(), scale.data_ptr(), O, K
-        t.out, t.ld, t.out_sample_stride, t.out_dtype = w2.data_ptr() + i * O * kp * 2, kp, O * kp, _lib.BF16
-        t.kind, t.taps = kind, KH * KW
-    check(lib.bnn_draw_multi(arr, 2, 1, None, 0, None, stream_ptr(dev)), "bnn_draw_multi")
+    for i, kind in enumerate((_lib.DRAW_MEAN, _lib.DRAW_SIGMA)):
+        _draw_slot(arr[i], mean, scale, O, K, w2.data_ptr() + i * O * kp * 2, kp, O * kp, _lib.BF16, kind, KH * KW)
+    _draw_launch(arr, 2, 1, dev)
     return w2
 
 
@@ -1637,41 +1575,20 @@ class _PlainConv2d(torch.autograd.Function):
         if groups == 1 and K % 8 == 0:
             # all-HIP backward through the im2col panel (exact fp32 here: parity mode / Flipout): the conv is
             # F.linear on rows = (image, pixel), see include/bnn_hip.h 'backward of K2 conv2d'
-            lib, dev, st = _lib.load(), gy.device, stream_ptr(gy.device)
-            _lib.ensure_workspace(dev)
+            _lib.ensure_workspace(gy.device)
             P, O = OH * OW, sh.O
             M = sh.B * P
-            rows = torch.empty((S, M, O), dtype=torch.float32, device=dev)
-            check(lib.bnn_nchw_to_rows(ptr(gy), S * sh.B, O, P, ptr(rows), 0, st), "bnn_nchw_to_rows")
+            rows = _conv_rows_raw(gy, sh, P, S, False)
             if ctx.needs_input_grad[1]:
-                nsx = 1 if ctx.shared_x else S
-                panel = torch.empty((nsx, M, K), dtype=torch.float32, device=dev)
-                per = sh.B * sh.C * sh.H * sh.W
-                check(lib.bnn_conv2d_im2col(ptr(x), 0 if ctx.shared_x else per, ctypes.byref(sh), nsx, ptr(panel), 0, st),
-                      "bnn_conv2d_im2col")
-                gw = torch.empty_like(w)
-                check(lib.bnn_linear_backward_weight(ptr(panel), 0 if ctx.shared_x else M * K, K, ptr(rows), M * O, O,
-                                                     ptr(gw), O * K, M, O, K, S, _lib.COMPUTE_F32, 0, 0, st),
-                      "bnn_linear_backward_weight")
+                panel, pstride = _conv_panel_raw(x, sh, M, K, S, ctx.shared_x, False)
+                gw = _wgrad_plain_raw(panel, pstride, rows, M, O, K, S).view_as(w)
             if ctx.needs_input_grad[0]:
                 gpanel = _dgrad_plain_raw(rows, w.reshape(S, O, K), torch.float32)          # (S, M, K)
-                gx = torch.empty((sh.B, sh.C, sh.H, sh.W) if ctx.shared_x else (S, sh.B, sh.C, sh.H, sh.W),
-                                 dtype=torch.float32, device=dev)
-                check(lib.bnn_conv2d_col2im(ptr(gpanel), ctypes.byref(sh), S, int(ctx.shared_x), ptr(gx), st), "bnn_conv2d_col2im")
+                gx = _conv_col2im_raw(gpanel, sh, S, ctx.shared_x)
             if ctx.has_b and ctx.needs_input_grad[2]:
                 gb = _colsum_raw(rows)
             return gx, gw, gb, None, None, None
-        gxs, gws = [], []
-        for s in range(S):
-            xs_ = x if ctx.shared_x else x[s]
-            if ctx.needs_input_grad[0]:
-                gxs.append(torch.nn.grad.conv2d_input(xs_.shape, w[s], gy[s], stride, padding, dilation, groups))
-            if ctx.needs_input_grad[1]:
-                gws.append(torch.nn.grad.conv2d_weight(xs_, w[s].shape, gy[s], stride, padding, dilation, groups))
-        if gxs:
-            gx = torch.stack(gxs).sum(0) if ctx.shared_x else torch.stack(gxs)
-        if gws:
-            gw = torch.stack(gws)
+        gx, gw = _conv2d_torch_bwd(x, w, gy, ctx.shared_x, ctx.conv_args, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         if ctx.has_b and ctx.needs_input_grad[2]:
             gb = gy.sum((1, 3, 4))
         return gx, gw, gb, None, None, None
@@ -1689,12 +1606,9 @@ def plain_conv_planes(ws):
         K = C * KH * KW
         kp = _pad64(K)
         out = torch.empty((3, 1, O, kp), dtype=torch.bfloat16, device=dev)
-        t = arr[i]
-        t.mu, t.rho, t.rows, t.cols = w.data_ptr(), w.data_ptr(), O, K
-        t.out, t.ld, t.out_sample_stride, t.out_dtype = out.data_ptr(), kp, O * kp, _lib.BF16X3
-        t.kind, t.taps = 1, KH * KW
+        _draw_slot(arr[i], w, None, O, K, out.data_ptr(), kp, O * kp, _lib.BF16X3, _lib.DRAW_MEAN, KH * KW)
         outs.append(out)
-    check(_lib.load().bnn_draw_multi(arr, len(ws), 1, None, 0, None, stream_ptr(dev)), "bnn_draw_multi")
+    _draw_launch(arr, len(ws), 1, dev)
     return outs
 
 
@@ -1769,22 +1683,17 @@ def _conv3d_operands(mu_w, rho_w, mu_b, rho_b, key_w, key_b, compute):
     S = key_w.nsamples if key_w is not None else 1
     w = torch.empty((S, ld), dtype=torch.bfloat16 if bf else torch.float32, device=dev)
     arr = (_lib.DrawTensor * 2)()
-    t = arr[0]
-    t.mu, t.rho, t.rows, t.cols = mu_w.data_ptr(), (rho_w if key_w is not None else mu_w).data_ptr(), 1, n
-    t.out, t.ld, t.out_sample_stride, t.out_dtype = w.data_ptr(), ld, ld, (_lib.BF16 if bf else _lib.F32)
-    t.kind, t.taps = (0 if key_w is not None else 1), 0
     if key_w is not None:
-        t.rng = _rng_struct(key_w, dev)
+        _draw_slot(arr[0], mu_w, rho_w, 1, n, w.data_ptr(), ld, ld, _lib.BF16 if bf else _lib.F32, key=key_w)
+    else:
+        _draw_slot(arr[0], mu_w, None, 1, n, w.data_ptr(), ld, ld, _lib.BF16, _lib.DRAW_MEAN)
     cnt, b = 1, (mu_b if key_w is None else None)
     if key_w is not None and mu_b is not None:
-        b = torch.empty((S, mu_b.numel()), dtype=torch.float32, device=dev)
-        t = arr[1]
-        t.mu, t.rho, t.rows, t.cols = mu_b.data_ptr(), rho_b.data_ptr(), 1, mu_b.numel()
-        t.out, t.ld, t.out_sample_stride, t.out_dtype = b.data_ptr(), mu_b.numel(), mu_b.numel(), _lib.F32
-        t.kind, t.taps = 0, 0
-        t.rng = _rng_struct(key_b, dev)
+        nb = mu_b.numel()
+        b = torch.empty((S, nb), dtype=torch.float32, device=dev)
+        _draw_slot(arr[1], mu_b, rho_b, 1, nb, b.data_ptr(), nb, nb, _lib.F32, key=key_b)
         cnt = 2
-    check(_lib.load().bnn_draw_multi(arr, cnt, S, None, 0, None, stream_ptr(dev)), "bnn_draw_multi")
+    _draw_launch(arr, cnt, S, dev)
     return w, (ld if key_w is not None else 0), b, (0 if key_w is None or b is None else b.shape[1])
 
 
@@ -1997,12 +1906,9 @@ def _flip3d_operands(mean, scale, compute):
     ld = (n + 7) // 8 * 8 if bf else n
     w = torch.empty((2, ld), dtype=torch.bfloat16 if bf else torch.float32, device=dev)
     arr = (_lib.DrawTensor * 2)()
-    for i, kind in enumerate((1, 2)):
-        t = arr[i]
-        t.mu, t.rho, t.rows, t.cols = mean.data_ptr(), scale.data_ptr(), 1, n
-        t.out, t.ld, t.out_sample_stride = w.data_ptr() + i * ld * w.element_size(), ld, ld
-        t.out_dtype, t.kind, t.taps = (_lib.BF16 if bf else _lib.F32), kind, 0
-    check(_lib.load().bnn_draw_multi(arr, 2, 1, None, 0, None, stream_ptr(dev)), "bnn_draw_multi")
+    for i, kind in enumerate((_lib.DRAW_MEAN, _lib.DRAW_SIGMA)):
+        _draw_slot(arr[i], mean, scale, 1, n, w.data_ptr() + i * ld * w.element_size(), ld, ld, _lib.BF16 if bf else _lib.F32, kind)
+    _draw_launch(arr, 2, 1, dev)
     return w
 
 

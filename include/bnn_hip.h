@@ -288,7 +288,8 @@ int bnn_linear_forward_sampled_kl(const void *x, int64_t x_sample_stride, int64_
  * replaces  WeightNormal.sample  pytorch_bayesian/nn/core.py:44-45, called weight-then-bias by
  *           NormalLinear.sample  pytorch_bayesian/nn/dense.py:46-54, once per MC sample by the loop at
  *           pytorch_bayesian/nn/container.py:36-37 */
-enum { BNN_DRAW_FLIPOUT = 16 };  /* bnn_draw_tensor_t.kind of a Flipout draw (sign contract below) */
+enum { BNN_DRAW_SAMPLE = 0, BNN_DRAW_MEAN = 1, BNN_DRAW_SIGMA = 2, BNN_DRAW_COPY = 3,   /* bnn_draw_tensor_t.kind (below) */
+       BNN_DRAW_FLIPOUT = 16 };  /* ... of a Flipout draw (sign contract below) */
 typedef struct bnn_draw_tensor {
     const float *mu;
     const float *rho;
@@ -298,10 +299,10 @@ typedef struct bnn_draw_tensor {
     int64_t out_sample_stride;  /* elements */
     int out_dtype;              /* BNN_F32, BNN_BF16, or BNN_BF16X3: three planes, plane p of draw s at
                                  * out + (p * nsamples + s) * out_sample_stride (kinds 0, 1, 2) */
-    int kind;                   /* 0: draw mu + sigma(rho) eps (rng used); BNN_DRAW_FLIPOUT: the same with eps[r][c] = R[r] S[c], the
+    int kind;                   /* BNN_DRAW_SAMPLE 0: draw mu + sigma(rho) eps (rng used); BNN_DRAW_FLIPOUT: the same with eps[r][c] = R[r] S[c], the
                                  * Flipout signs of rng (sign contract above, linear layout with O = rows, K = cols; no taps);
-                                 * 1: mu itself; 2: sigma(rho) itself (no eps: Flipout's
-                                 * two operands, nsamples = 1); 3: `mu` as it is, written ONCE whatever nsamples is (rho ignored,
+                                 * BNN_DRAW_MEAN 1: mu itself; BNN_DRAW_SIGMA 2: sigma(rho) itself (no eps: Flipout's
+                                 * two operands, nsamples = 1); BNN_DRAW_COPY 3: `mu` as it is, written ONCE whatever nsamples is (rho ignored,
                                  * pass mu) -- with BNN_BF16X3 (planes out_sample_stride apart) this is bnn_split_bf16x3 of an
                                  * activation riding in the draw launch: the fp32 parity mode's input planes */
     int taps;                   /* 0 / 1: rows are written as they are.  KH * KW of a conv weight (O, C, KH, KW) viewed as
@@ -568,6 +569,17 @@ int bnn_conv2d_flipout_forward_x3(const float *x, const void *w, int64_t w_plane
 int bnn_conv2d_flipout_forward_mc(const float *x, int64_t x_sample_stride, const void *w, int64_t ldw, float *y,
                                   int64_t y_sample_stride, const bnn_conv2d_shape_t *shape, int nsamples, const bnn_rng_t *rng,
                                   int flags, void *stream);
+/* Does the LDS-resident kernel behind the five launches above take this shape?  A pure host query (no GPU call), the launches'
+ * own fit computation: -> the images one workgroup keeps resident (>= 1, at most shape->B), 0 where the launch would answer
+ * BNN_E_UNSUPPORTED for the shape (groups, C, O, > 128 output pixels per image, an image + the weight ring past the LDS block),
+ * BNN_E_NULL / BNN_E_SHAPE / BNN_E_RANGE for a bad argument.  It assumes tap-major weights with ldw = roundup(C KH KW, 64) and
+ * aligned pointers (what bnn_draw_multi writes); nsamples and shared_x (x_sample_stride = 0) matter to BNN_CONV_FLIPOUT_MC only. */
+enum { BNN_CONV_DENSE = 0,        /* bnn_conv2d_dense_forward */
+       BNN_CONV_DENSE_X3 = 1,     /* bnn_conv2d_dense_forward_x3 */
+       BNN_CONV_FLIPOUT = 2,      /* bnn_conv2d_flipout_forward */
+       BNN_CONV_FLIPOUT_X3 = 3,   /* bnn_conv2d_flipout_forward_x3 */
+       BNN_CONV_FLIPOUT_MC = 4 }; /* bnn_conv2d_flipout_forward_mc */
+int bnn_conv2d_dense_images(const bnn_conv2d_shape_t *shape, int variant, int nsamples, int shared_x);
 
 /* ---- backward of K2 conv2d through the panel ------------------
  * replaces  autograd through F.conv2d (conv.py:116) for groups == 1, C*KH*KW % 8 == 0.  With

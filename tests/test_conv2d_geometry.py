@@ -6,18 +6,19 @@ that read one member of a pair where it meant the other is invisible to cases wr
 is one table of fully anisotropic shapes, each tagged with the paths it is meant for.
 
 CPU (-m "not gpu"): the table can tell the axes apart (float64 F.conv2d with one pair swapped is another output), holds the
-edges by name, and every case routes where its tags say (the pure-Python predicates of ops.py and the rules of
-bnn_conv2d_workspace_bytes / launch_im2col).  The oracle pin (orc.conv2d on these cases) is in test_oracle_golden.py.
+edges by name, and every case routes where its tags say (the predicates of ops.py, which ask the built library's host query
+bnn_conv2d_dense_images, and the rules of bnn_conv2d_workspace_bytes / launch_im2col).  The oracle pin (orc.conv2d on these cases) is in test_oracle_golden.py.
 GPU: every path against float64 F.conv2d fed what the kernel is fed, at the tolerance its square-shaped sibling test holds --
 the sibling's own body, called with pairs (test_dense_path.py, test_hip_parity.py, test_flipout_mc.py).  No case is skipped:
 a case that does not route where its tag says fails."""
 import collections
+import json
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import allclose_scaled, assert_close_scaled
+from conftest import GOLDEN, allclose_scaled, assert_close_scaled
 import test_dense_path as tdp
 import test_flipout_mc as tfm
 import test_hip_parity as thp
@@ -106,14 +107,8 @@ def _image_kernel(c):
 
 
 def _images_per_workgroup(c):
-    """conv_dense_launch's tile of the bf16 launch (csrc/bnn_dense.hip): images whose 128 rows and bytes fit one workgroup."""
-    OH, OW = _out_hw(c)
-    P = OH * OW
-    block, st = ops._CONV_LDS[c.O]
-    img = 128 // P
-    while img > 0 and (img * c.H * c.W * c.C * 2 + st * c.O * 128 > block or img * c.O * P * 4 > block):
-        img -= 1
-    return img
+    """conv_dense_launch's tile of the bf16 launch (bnn_conv2d_dense_images): images whose 128 rows and bytes fit one workgroup."""
+    return ops._conv_lds_images(_shape(c, B=128)[0], _lib.CONV_DENSE)
 
 
 class _Stub:
@@ -200,7 +195,7 @@ def test_table_holds_the_edges():
 
 @pytest.mark.parametrize("c", [pytest.param(c, id=_cid(c)) for c in CASES])
 def test_table_routes_where_its_tags_say(c):
-    """The pure-Python predicates of ops.py and the rules of bnn_conv2d_workspace_bytes / launch_im2col, on the CPU."""
+    """The predicates of ops.py and the rules of bnn_conv2d_workspace_bytes / launch_im2col, on the CPU."""
     sh, OH, OW = _shape(c)
     assert (OH, OW) == _out_hw(c) and OH >= 1 and OW >= 1
     dense = ops.conv_dense_eligible(sh, OH, OW) and ops.conv_dense_x3_eligible(sh, OH, OW)
@@ -241,6 +236,23 @@ MC_SAMPLES = (1, 2, 3, 8)                                # keyed Flipout: 1, 2 a
 
 def test_sweep_is_complete():
     assert len(SWEEP) == 8 and all(_sweep_accept(c) for c in SWEEP)
+
+
+def test_predicates_answer_as_recorded():
+    """golden/conv2d_lds_fit.json: the five predicates' answers from when ops.py did the LDS arithmetic by hand (a strided sweep and,
+    per (launch, C, O), the largest image that fits with the next one up) and the bf16 launch's images per workgroup: all unchanged."""
+    with open(GOLDEN + "/conv2d_lds_fit.json") as f:
+        doc = json.load(f)
+    B = doc["B"]
+    assert len(doc["cases"]) > 3000
+    for C, O, H, W, k, st, pad, dil, g, S, shared, *want in doc["cases"]:
+        geo = ((st, st), (pad, pad), (dil, dil))
+        x, xs, mean = _Stub(B, C, H, W), _Stub(B if shared else S * B, C, H, W), _Stub(O, C // g, k, k)
+        sh, OH, OW = ops._conv_shape(x.shape, mean.shape, *geo, g)
+        got = [ops.conv_dense_eligible(sh, OH, OW), ops.conv_dense_x3_eligible(sh, OH, OW), ops.conv2d_flipout_eligible(x, mean, *geo, g),
+               ops.conv2d_flipout_x3_fused_eligible(x, mean, *geo) if g == 1 else None,      # (no groups argument: recorded for 1)
+               ops.conv2d_flipout_mc_eligible(xs, mean, *geo, g, S, bool(shared)), ops._conv_lds_images(sh, _lib.CONV_DENSE)]
+        assert got == want, (C, O, H, W, k, st, pad, dil, g, S, shared)
 
 
 # ================================================================================================== GPU

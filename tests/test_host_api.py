@@ -177,6 +177,14 @@ def test_draw_once_entry_points_reject_bad_arguments_without_launching():
     assert lib.bnn_conv2d_flipout_forward(one, one, 576, None, one, one, ctypes.byref(sh), 0, None) == -1
     sh.O = 128                                                                           # Flipout: 2 O must be 64 or 128
     assert lib.bnn_conv2d_flipout_forward(one, one, 576, one, one, one, ctypes.byref(sh), 0, None) == _lib.E_UNSUPPORTED
+    # the launches' fit as a host query: 0 where they answer BNN_E_UNSUPPORTED for the shape, the images per workgroup where they launch
+    assert lib.bnn_conv2d_dense_images(ctypes.byref(sh), _lib.CONV_FLIPOUT, 1, 1) == 0
+    assert lib.bnn_conv2d_dense_images(ctypes.byref(sh), _lib.CONV_DENSE, 1, 1) == 2     # 128 // 36 = 3 images, B = 2 of them
+    assert lib.bnn_conv2d_dense_images(None, _lib.CONV_DENSE, 1, 1) == -1
+    assert lib.bnn_conv2d_dense_images(ctypes.byref(sh), 5, 1, 1) == -5 and b"variant" in lib.bnn_last_error()
+    assert lib.bnn_conv2d_dense_images(ctypes.byref(sh), _lib.CONV_FLIPOUT_MC, 0, 1) == -2      # BNN_E_SHAPE: no samples
+    sh.KH = 9                                                                            # kernel larger than the padded input
+    assert lib.bnn_conv2d_dense_images(ctypes.byref(sh), _lib.CONV_DENSE, 1, 1) == -2
     assert lib.bnn_launch_count() == n0
 
 
