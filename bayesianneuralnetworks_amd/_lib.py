@@ -225,6 +225,9 @@ SIGNATURES = {
     "bnn_conv3d_lrt_backward_weight_workspace_bytes": (_i64, [ctypes.POINTER(Conv3dShape), _int]),
     "bnn_conv3d_lrt_backward_weight": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p,
                                               _i64, _p]),
+    "bnn_moments_forward": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
+    "bnn_moments_relu": (_int, [_p, _p, _p, _p, _i64, _p]),
+    "bnn_moments_sample": (_int, [_p, _p, _p, _i64, _i64, _int, _rngp, _int, _p]),
 }
 
 _lib = None

@@ -36,3 +36,23 @@ class McContext:
 
 def current():
     return getattr(_state, "ctx", None)
+
+
+class MomentContext:
+    """Set by BayesianNetworkModule.predictive_moments for ONE pass of `_forward`: inside it NormalLinear and LocalReparamLinear
+    take a tensor (a deterministic input) or an ops.Moments and hand on the mean and variance of their output
+    (ops.moments_linear) instead of samples.  They draw nothing and record no key.  Thread-local, like McContext, and kept apart
+    from it: an MC-batched pass and a moment pass do not see each other."""
+
+    def __enter__(self):
+        self.prev = getattr(_state, "moments", None)
+        _state.moments = self
+        return self
+
+    def __exit__(self, *exc):
+        _state.moments = self.prev
+        return False
+
+
+def moments_current():
+    return getattr(_state, "moments", None)

@@ -40,6 +40,21 @@ class _Single:
         return traverse(self.layer, fn, *args, **kwargs)
 
 
+_MOMENTS_SUPPORTED = ("moment propagation supports NormalLinear / LocalReparamLinear, ReLU folded into them by "
+                      "nn.fuse_activations, and torch.nn.Identity")
+
+
+def _moments_asked(propagation, who, kl=None):
+    """propagation == 'moments'?  ValueError for anything but 'samples' / 'moments' (and then no KL is left pending)."""
+    if propagation == 'samples':
+        return False
+    if propagation == 'moments':
+        return True
+    from .. import ops
+    ops._kl_uncarry(kl)
+    raise ValueError("%s: propagation must be 'samples' or 'moments', got %r" % (who, propagation))
+
+
 class BayesianNetworkModule(Module):
     """container.py:17-37.  Subclasses implement `_forward`."""
 
@@ -81,14 +96,27 @@ class BayesianNetworkModule(Module):
             return list(zip(*[t.unbind(0) for t in ys]))
         return list(ys.unbind(0))
 
-    def predictive_mean(self, x, samples=None, sample0=0, out=None, scale=None, advance=None, kl=None, *args, **kwargs):
+    def predictive_mean(self, x, samples=None, sample0=0, out=None, scale=None, advance=None, kl=None, *args,
+                        propagation='samples', **kwargs):
         """scale (default 1 / samples) * sum over the MC samples of `_forward(x)` -- torch.stack(preds).mean(0) of
         examples/MNIST/uncertainty.py:50 -- as the tail of ONE batched pass: the caller wants the mean, not the samples, so a
         hidden layer may run fused with the classifier head behind it (nn.fuse_activations; bnn_dense_forward_head) and the
-        reduction adds that pair's partial logits in the same launch.  out / advance / kl: as ops.mc_mean."""
+        reduction adds that pair's partial logits in the same launch.  out / advance / kl: as ops.mc_mean.
+        propagation='moments': the samples are drawn from ONE sampling-free pass (predictive_moments; _moment_outputs)."""
         from .. import ops
         if samples is None:
             samples = self.samples
+        if _moments_asked(propagation, "predictive_mean"):
+            ys = self._moment_outputs("predictive_mean", x, samples, sample0, kl, args, kwargs)
+            if ys.is_cuda:
+                return ops.mc_mean(ys, out=out, scale=(1.0 / samples) if scale is None else scale, advance=advance)
+            if advance is not None:
+                raise ops.BnnHipError("predictive_mean: advance is a tail of the device launch; x is not on the device")
+            m = ys.sum(0) * ((1.0 / samples) if scale is None else scale)
+            if out is not None:
+                out.copy_(m.reshape(out.shape))
+                return out
+            return m
         if not (self.mc_batched and isinstance(x, torch.Tensor) and x.is_cuda):
             ys = self.forward_stacked(x, samples, sample0, *args, **kwargs)
             m = ys.sum(0) * ((1.0 / samples) if scale is None else scale)
@@ -99,7 +127,7 @@ class BayesianNetworkModule(Module):
         y = self._forward_batched_stacked(x, samples, sample0, *args, _lazy_head=True, **kwargs)
         return ops.mc_mean(y, out=out, scale=(1.0 / samples) if scale is None else scale, advance=advance, kl=kl)
 
-    def predictive_uncertainty(self, x, samples=None, sample0=0, *, inputs, advance=None, kl=None, **kwargs):
+    def predictive_uncertainty(self, x, samples=None, sample0=0, *, inputs, advance=None, kl=None, propagation='samples', **kwargs):
         """Predictive mean and uncertainty of `samples` MC draws of `_forward(x)` -> ops.PredictiveUncertainty(mean, total,
         aleatoric, epistemic): total = H(mean), aleatoric = mean over samples of H(p_s), epistemic = total - aleatoric (the
         mutual information, BALD).  inputs: 'logits' (p_s = softmax of the outputs) or 'probs' (outputs used as given, e.g. a
@@ -107,19 +135,26 @@ class BayesianNetworkModule(Module):
           mc_batched on CUDA: one batched pass (a hidden layer fused with its head hands on partial logits) + ONE
                               bnn_mc_uncertainty launch, which also runs the `advance` / `kl` tails (as ops.mc_mean);
           other CUDA:         forward_stacked (the serial loop), then the same launch;
-          CPU:                forward_stacked, then ops.uncertainty_f64 (the same formulas in float64)."""
+          CPU:                forward_stacked, then ops.uncertainty_f64 (the same formulas in float64).
+        propagation='moments': the `samples` logits are drawn from ONE sampling-free pass (predictive_moments; _moment_outputs)
+        instead of `samples` stochastic forwards; the tail is the same."""
         from .. import ops
         ops._unc_kind(inputs, "predictive_uncertainty", kl)         # before a draw is consumed
         if samples is None:
             samples = self.samples
+        moments = _moments_asked(propagation, "predictive_uncertainty", kl)
         if not (isinstance(x, torch.Tensor) and x.is_cuda):
             if advance is not None or kl is not None:
                 raise ops.BnnHipError("predictive_uncertainty: advance / kl are tails of the device launch; x is not on the device")
-            return ops.uncertainty_f64(self.forward_stacked(x, samples, sample0, **kwargs), inputs)
-        y = self._mc_outputs(x, samples, sample0, kwargs)
+            ys = self._moment_outputs("predictive_uncertainty", x, samples, sample0, kl, (), kwargs) if moments else \
+                self.forward_stacked(x, samples, sample0, **kwargs)
+            return ops.uncertainty_f64(ys, inputs)
+        y = self._moment_outputs("predictive_uncertainty", x, samples, sample0, kl, (), kwargs) if moments else \
+            self._mc_outputs(x, samples, sample0, kwargs)
         return ops.mc_uncertainty(y, inputs, advance=advance, kl=kl)
 
-    def predictive_score(self, x, target, samples=None, sample0=0, *, inputs, state=None, advance=None, **kwargs):
+    def predictive_score(self, x, target, samples=None, sample0=0, *, inputs, state=None, advance=None, propagation='samples',
+                         **kwargs):
         """`samples` MC draws of `_forward(x)` scored against the labels `target` (int64, one per row) -> ops.PredictiveScore(mean,
         nll, expected_nll, brier, confidence, prediction, entropy): nll = -ln mean[y] of the MC predictive, expected_nll the mean
         per-sample NLL (the ELBO's data term), brier, the confidence max_c mean[c] with its class, and H(mean).  inputs: 'logits'
@@ -129,25 +164,30 @@ class BayesianNetworkModule(Module):
           mc_batched on CUDA: one batched pass (a hidden layer fused with its head hands on partial logits) + ONE bnn_mc_score
                               launch (two with a state), which also runs the `advance` tail (as ops.mc_mean);
           other CUDA:         forward_stacked (the serial loop), then the same launch;
-          CPU:                forward_stacked, then ops.score_f64 (the same formulas in float64), added to a CPU state."""
+          CPU:                forward_stacked, then ops.score_f64 (the same formulas in float64), added to a CPU state.
+        propagation='moments': as predictive_uncertainty."""
         from .. import ops
         ops._unc_kind(inputs, "predictive_score")                   # before a draw is consumed
         if samples is None:
             samples = self.samples
+        moments = _moments_asked(propagation, "predictive_score")
         if not (isinstance(x, torch.Tensor) and x.is_cuda):
             if advance is not None:
                 raise ops.BnnHipError("predictive_score: advance is a tail of the device launch; x is not on the device")
             if state is not None and not (isinstance(state, ops.ScoreState) and state.device.type == "cpu"):
                 raise ops.BnnHipError("predictive_score: x is not on the device, so state must be a ScoreState on the CPU")
             cb, eb = (state.conf_bins, state.ent_bins) if state is not None else (15, 20)
-            out, vec = ops.score_f64(self.forward_stacked(x, samples, sample0, **kwargs), target, inputs, cb, eb)
+            ys = self._moment_outputs("predictive_score", x, samples, sample0, None, (), kwargs) if moments else \
+                self.forward_stacked(x, samples, sample0, **kwargs)
+            out, vec = ops.score_f64(ys, target, inputs, cb, eb)
             if state is not None:
                 state.add_(vec)
             return out
-        y = self._mc_outputs(x, samples, sample0, kwargs)
+        y = self._moment_outputs("predictive_score", x, samples, sample0, None, (), kwargs) if moments else \
+            self._mc_outputs(x, samples, sample0, kwargs)
         return ops.mc_score(y, target, inputs, state=state, advance=advance)
 
-    def predictive_regression(self, x, samples=None, sample0=0, *, outputs, advance=None, kl=None, **kwargs):
+    def predictive_regression(self, x, samples=None, sample0=0, *, outputs, advance=None, kl=None, propagation='samples', **kwargs):
         """Predictive mean and variance decomposition of `samples` MC draws of a real-valued `_forward(x)` ->
         ops.PredictiveRegression(mean, total, aleatoric, epistemic), each (*rows, D): the moments of the equal-weight mixture of
         the per-sample predictives -- aleatoric = mean of the per-sample variances, epistemic = variance of the per-sample means,
@@ -157,19 +197,34 @@ class BayesianNetworkModule(Module):
           mc_batched on CUDA: one batched pass (a hidden layer fused with its <= 16-wide head hands on partials) + ONE
                               bnn_mc_regression launch, which also runs the `advance` / `kl` tails (as ops.mc_mean);
           other CUDA:         forward_stacked (the serial loop), then the same launch;
-          CPU:                forward_stacked, then ops.regression_f64 (the same formulas in float64)."""
+          CPU:                forward_stacked, then ops.regression_f64 (the same formulas in float64).
+        propagation='moments': as predictive_uncertainty -- except outputs='values', which needs no sampling: the propagated
+        moments ARE the answer (mean, total = epistemic = var, aleatoric = 0), `samples` is not used and nothing is drawn."""
         from .. import ops
         ops._reg_kind(outputs, "predictive_regression", kl)         # before a draw is consumed
         if samples is None:
             samples = self.samples
+        moments = _moments_asked(propagation, "predictive_regression", kl)
+        if moments and outputs == 'values':
+            if advance is not None:
+                raise ops.BnnHipError("predictive_regression: outputs='values' with propagation='moments' has no tail launch "
+                                      "to run `advance` in")
+            self._moment_refusals("predictive_regression", kl)
+            mom = self.predictive_moments(x, **kwargs)
+            var = torch.zeros_like(mom.mean) if mom.var is None else mom.var
+            return ops.PredictiveRegression(mom.mean, var, torch.zeros_like(mom.mean), var.clone())
         if not (isinstance(x, torch.Tensor) and x.is_cuda):
             if advance is not None or kl is not None:
                 raise ops.BnnHipError("predictive_regression: advance / kl are tails of the device launch; x is not on the device")
-            return ops.regression_f64(self.forward_stacked(x, samples, sample0, **kwargs), outputs)
-        y = self._mc_outputs(x, samples, sample0, kwargs)
+            ys = self._moment_outputs("predictive_regression", x, samples, sample0, kl, (), kwargs) if moments else \
+                self.forward_stacked(x, samples, sample0, **kwargs)
+            return ops.regression_f64(ys, outputs)
+        y = self._moment_outputs("predictive_regression", x, samples, sample0, kl, (), kwargs) if moments else \
+            self._mc_outputs(x, samples, sample0, kwargs)
         return ops.mc_regression(y, outputs, advance=advance, kl=kl)
 
-    def predictive_regression_score(self, x, target, samples=None, sample0=0, *, outputs, state=None, advance=None, **kwargs):
+    def predictive_regression_score(self, x, target, samples=None, sample0=0, *, outputs, state=None, advance=None,
+                                    propagation='samples', **kwargs):
         """`samples` MC draws of a real-valued `_forward(x)` scored against the targets `target` (*rows, D) ->
         ops.RegressionScore(mean, variance, sq_err, nll, gaussian_nll, crps, pit), each (*rows, D): the proper scores of the MC
         predictive -- the equal-weight mixture of the per-sample Gaussians -- and its probability integral transform.  outputs:
@@ -181,11 +236,13 @@ class BayesianNetworkModule(Module):
           mc_batched on CUDA: one batched pass (a hidden layer fused with its <= 16-wide head hands on partials) + ONE
                               bnn_mc_regression_score launch (two with a state), which also runs the `advance` tail;
           other CUDA:         forward_stacked (the serial loop), then the same launch;
-          CPU:                forward_stacked, then ops.regression_score_f64 (the same formulas in float64), added to a CPU state."""
+          CPU:                forward_stacked, then ops.regression_score_f64 (the same formulas in float64), added to a CPU state.
+        propagation='moments': as predictive_uncertainty."""
         from .. import ops
         ops._reg_kind(outputs, "predictive_regression_score")       # before a draw is consumed
         if samples is None:
             samples = self.samples
+        moments = _moments_asked(propagation, "predictive_regression_score")
         if not (isinstance(x, torch.Tensor) and x.is_cuda):
             if advance is not None:
                 raise ops.BnnHipError("predictive_regression_score: advance is a tail of the device launch; x is not on the device")
@@ -193,11 +250,14 @@ class BayesianNetworkModule(Module):
                 raise ops.BnnHipError("predictive_regression_score: x is not on the device, so state must be a "
                                       "RegressionScoreState on the CPU")
             bins = state.pit_bins if state is not None else 20
-            out, mat = ops.regression_score_f64(self.forward_stacked(x, samples, sample0, **kwargs), target, outputs, bins)
+            ys = self._moment_outputs("predictive_regression_score", x, samples, sample0, None, (), kwargs) if moments else \
+                self.forward_stacked(x, samples, sample0, **kwargs)
+            out, mat = ops.regression_score_f64(ys, target, outputs, bins)
             if state is not None:
                 state.add_(mat)
             return out
-        y = self._mc_outputs(x, samples, sample0, kwargs)
+        y = self._moment_outputs("predictive_regression_score", x, samples, sample0, None, (), kwargs) if moments else \
+            self._mc_outputs(x, samples, sample0, kwargs)
         return ops.mc_regression_score(y, target, outputs, state=state, advance=advance)
 
     def predictive_evidential(self, x, samples=None, sample0=0, **kwargs):
@@ -220,6 +280,65 @@ class BayesianNetworkModule(Module):
         if not (isinstance(x, torch.Tensor) and x.is_cuda):
             return ops.evidential_f64(*ys)
         return ops.mc_evidential(*ys)
+
+    def predictive_moments(self, x, *args, **kwargs):
+        """Sampling-free inference: ONE pass of `_forward(x)` that carries a mean and a variance per activation through the
+        network (moment propagation: Frey & Hinton 1999; Hernandez-Lobato & Adams 2015; Wu et al. 2019) -> ops.Moments(mean, var)
+        of the output, fp32.  Every NormalLinear / LocalReparamLinear runs as ops.moments_linear (one bnn_moments_forward launch
+        beside its operand launch, both compute modes; ReLU folded by nn.fuse_activations is moment-matched in that launch); the
+        cost does not depend on a sample count and no mc_batched is needed.  With ONE hidden ReLU layer every output's marginal
+        mean and variance are exact; from the second hidden layer on the recursion treats a layer's inputs as independent
+        Gaussians (the usual diagonal-covariance approximation), and the outputs' covariances are not carried at all.
+        Supported: NormalLinear and LocalReparamLinear, ReLU folded into them by nn.fuse_activations, torch.nn.Identity, and any
+        deterministic module in FRONT of the first Bayesian layer; anything else raises ops.BnnHipError.  A `_forward` that
+        returns a plain tensor gives it back with var None.  CPU tensors: the same recursion in float64 (ops.moments_f64),
+        rounded to fp32 at the end.  Inference only: nothing is drawn, no draw epoch is consumed, no key is recorded, and the
+        result is detached whatever the grad mode."""
+        from .. import ops
+        from .dense import NormalLinear, LocalReparamLinear
+        for m in self.modules():
+            if isinstance(m, BayesianModule) and type(m) not in (NormalLinear, LocalReparamLinear):
+                raise ops.BnnHipError("predictive_moments: %s is not supported; %s" % (type(m).__name__, _MOMENTS_SUPPORTED))
+        with torch.no_grad(), _mc.MomentContext():
+            try:
+                y = self._forward(x, *args, **kwargs)
+            except (TypeError, AttributeError) as e:
+                raise ops.BnnHipError("predictive_moments: a module of this network cannot take a mean and a variance (%s); %s"
+                                      % (e, _MOMENTS_SUPPORTED)) from e
+        if torch.is_tensor(y):
+            y = ops.Moments(y.detach(), None)
+        if not isinstance(y, ops.Moments):
+            raise ops.BnnHipError("predictive_moments: _forward returned %s; %s" % (type(y).__name__, _MOMENTS_SUPPORTED))
+        if not y.mean.is_cuda:
+            return ops.Moments(y.mean.to(torch.float32), None if y.var is None else y.var.to(torch.float32))
+        return y
+
+    def _moment_refusals(self, who, kl):
+        from .. import ops
+        if kl is not None:
+            ops._kl_uncarry(kl)
+            raise ops.BnnHipError("%s: propagation='moments' draws no weights and has no KL tail (kl=)" % who)
+        if any(m.__dict__.get("_fuse_head") is not None for m in self.modules()):
+            raise ops.BnnHipError("%s: propagation='moments' has no fused head: this network was rewritten with "
+                                  "nn.fuse_activations(fuse_head=True), whose hidden layer hands on partial logits" % who)
+
+    def _moment_outputs(self, who, x, samples, sample0, kl, args, kwargs):
+        """propagation='moments': what a predictive_* tail reads -- the (S, *rows, C) outputs drawn from the propagated moments
+        by ONE bnn_moments_sample launch, independent across outputs, on a model-level noise stream (its id is taken at first
+        use, so that a model's layers keep theirs; the key is recorded as model.moment_key).  CPU: torch.randn."""
+        from .. import ops
+        from .._rng import DrawKey, default_generator, generator_for, new_stream_id
+        from . import _settings
+        self._moment_refusals(who, kl)
+        mom = self.predictive_moments(x, *args, **kwargs)
+        if not mom.mean.is_cuda:
+            return ops.moments_sample(mom, None, samples)
+        if self.__dict__.get("_moment_stream") is None:
+            self.__dict__["_moment_stream"] = new_stream_id()
+        key = DrawKey(default_generator.seed, self.__dict__["_moment_stream"], sample0, samples, default_generator.next_epoch(),
+                      gen=generator_for(_settings.get_compute()))
+        self.__dict__["moment_key"] = key
+        return ops.moments_sample(mom, key, samples)
 
     def _mc_outputs(self, x, samples, sample0, kwargs):
         """What a predictive_* tail launch reads for x on the device: with mc_batched one batched pass whose fused head, if any,

@@ -9,7 +9,8 @@ B-operand loader of the GEMM).  MCDropoutLinear runs on HIP in a network's MC-ba
 bnn_dense_forward_dropout / bnn_mc_dropout) and keeps F.dropout elsewhere.  FlipoutNormalLinear draws mu + sigma R S^T
 with keyed signs per MC sample in that pass (bnn_draw_multi kind BNN_DRAW_FLIPOUT).  MultivariateNormalLinear keeps the
 reference's torch expression unless nn.keyed_mvn_draws() is on: then in that pass every MC sample gets a keyed draw of its own
-(bnn_mvn_draw, then the HIP linear).  The evidential head is outside the HIP scope and runs as PyTorch-ROCm
+(bnn_mvn_draw, then the HIP linear).  Inside BayesianNetworkModule.predictive_moments (a _mc.MomentContext) NormalLinear and
+LocalReparamLinear draw nothing: they take and return a mean and a variance per activation (ops.moments_linear, K16).  The evidential head is outside the HIP scope and runs as PyTorch-ROCm
 ops with the reference's semantics so that its examples keep working.
 """
 import math
@@ -105,6 +106,21 @@ class _NormalSampling:
             ps += [self.bias.mean, self.bias.scale]
         return any(p.requires_grad for p in ps)
 
+    def _forward_moments(self, x):
+        """The layer inside a moment pass (_mc.MomentContext; BayesianNetworkModule.predictive_moments): x a tensor (a
+        deterministic input) or an ops.Moments -> the ops.Moments of the output, with the moment-matched ReLU when
+        nn.fuse_activations folded one into the layer (activation == 'relu').  Device: ops.moments_linear (bnn_moments_forward,
+        hidden moments fp32 in both compute modes); CPU: the same recursion in float64 (ops.moments_linear_f64).  Nothing is
+        drawn, no draw epoch is consumed, draw_key / noise_key stay as they are; the result is detached (inference only)."""
+        mom = x if isinstance(x, ops.Moments) else ops.Moments(x, None)
+        if not torch.is_tensor(mom.mean):
+            raise TypeError("%s takes a tensor or ops.Moments in a moment pass, got %s" % (type(self).__name__, type(x).__name__))
+        b = self.bias is not None
+        args = (self.weight.mean, self.weight.scale, self.bias.mean if b else None, self.bias.scale if b else None)
+        if not mom.mean.is_cuda:
+            return ops.moments_linear_f64(mom, *args, relu=self.activation == 'relu')
+        return ops.moments_linear(mom, *args, relu=self.activation == 'relu', compute=self._compute_mode())
+
     def _mc_plan(self, x, sample):
         """-> (S, sample0, shared_x, rows_per_sample) for the current MC context."""
         ctx = _mc.current()
@@ -185,6 +201,8 @@ class NormalLinear(_NormalSampling, BayesianLinear):
         self.sample()                                                   # dense.py:44
 
     def forward(self, x, sample=True):
+        if _mc.moments_current() is not None:
+            return self._forward_moments(x)                              # predictive_moments: moments in, moments out, no draw
         if not x.is_cuda:
             # CPU-resident module: the reference's own op sequence (dense.py:56-60)
             if sample:
@@ -299,6 +317,9 @@ class LocalReparamLinear(_NormalSampling, BayesianLinear):
     input layout or the GPU of a sharded run.  sample=False reuses noise_key.  CPU tensors: the expression above in torch with
     torch.randn_like.
 
+    Inside BayesianNetworkModule.predictive_moments the layer is NormalLinear's moment layer (same parameters, same bits) and
+    honours activation == 'relu' there.
+
     Out of scope: nn.fuse_activations / fuse_head and the network draw plan (there is no tensor to pre-draw; both select
     NormalLinear by exact type and pass this layer by), the three-plane (x3) hand-over.  The conv variant is
     nn.LocalReparamConv1d / 2d / 3d (nn/conv.py)."""
@@ -319,6 +340,8 @@ class LocalReparamLinear(_NormalSampling, BayesianLinear):
         return _lrt_noise_plan(x)
 
     def forward(self, x, sample=True):
+        if _mc.moments_current() is not None:
+            return self._forward_moments(x)                              # predictive_moments: moments in, moments out, no noise
         if not x.is_cuda:
             m = torch.nn.functional.linear(x, self.weight.mean, self.bias.mean if self.bias is not None else None)
             v = torch.nn.functional.linear(x * x, self.weight.variance, self.bias.variance if self.bias is not None else None)

@@ -915,6 +915,161 @@ def linear_lrt(x, mu_w, rho_w, mu_b, rho_b, key, shared_x, compute="f32", out_dt
                             key, shared_x, _compute_code(compute), out_dtype, torch.is_grad_enabled())
 
 
+# --------------------------------------------------------------------------- K16: moment propagation (sampling-free inference)
+class Moments:
+    """A mean and a variance per activation, independent across elements (the mean-field assumption): what a dense layer takes
+    and hands on inside a BayesianNetworkModule.predictive_moments pass.  A plain holder, not a Tensor; var None = a
+    deterministic input (every variance zero), as the first Bayesian layer of a network sees."""
+    __slots__ = ("mean", "var")
+
+    def __init__(self, mean, var=None):
+        if var is not None and var.shape != mean.shape:
+            raise ValueError("Moments: mean %s and var %s differ in shape" % (tuple(mean.shape), tuple(var.shape)))
+        self.mean, self.var = mean, var
+
+    def __repr__(self):
+        return "Moments(mean=%r, var=%r)" % (self.mean, self.var)
+
+
+def _as_moments(a, who):
+    if isinstance(a, Moments):
+        return a
+    if torch.is_tensor(a):
+        return Moments(a, None)
+    raise TypeError("%s: expected a tensor or ops.Moments, got %s" % (who, type(a).__name__))
+
+
+def moments_linear(a, mu_w, rho_w, mu_b, rho_b, relu=False, compute="f32"):
+    """Mean and variance of a dense layer's pre-activation for independent Gaussian weights, from the mean and variance of its
+    input (bnn_lrt_prepare + bnn_moments_forward, csrc/bnn_moments.hip) -> Moments, fp32 (*rows, N):
+
+        m = a_m mu_w^T + mu_b,    v = a_m^2 (sigma_w^2)^T + a_v (mu_w^2 + sigma_w^2)^T + sigma_b^2
+
+    a: a device tensor (a deterministic input: the second term is absent) or a Moments.  relu: the moment-matched ReLU of
+    moments_relu in the launch's epilogue (the same bits).  A bf16 `a` is read as it is in the 'bf16' mode (deterministic input
+    only).  Inference only: nothing is drawn, no key is touched, the result is detached whatever the grad mode."""
+    mom = _as_moments(a, "moments_linear")
+    code = _compute_code(compute)
+    am = mom.mean.detach()
+    av = None if mom.var is None else mom.var.detach()
+    mu_w, rho_w = mu_w.detach().contiguous(), rho_w.detach().contiguous()
+    require_cuda_f32(mu_w, "weight.mean")
+    require_cuda_f32(rho_w, "weight.scale")
+    if mu_b is not None:
+        mu_b, rho_b = mu_b.detach().contiguous(), rho_b.detach().contiguous()
+        require_cuda_f32(mu_b, "bias.mean")
+        require_cuda_f32(rho_b, "bias.scale")
+    N, K = mu_w.shape
+    if am.dim() < 1 or am.shape[-1] != K:
+        raise BnnHipError("moments_linear: input has %s features, weight expects %d" % (am.shape[-1] if am.dim() else "no", K))
+    lead = tuple(am.shape[:-1])
+    am = am.reshape(-1, K).contiguous()
+    require_cuda_act(am, "a.mean")
+    if am.dtype == torch.bfloat16 and (code != _lib.COMPUTE_BF16 or av is not None):
+        raise BnnHipError("moments_linear: a bf16 input needs compute mode 'bf16' and no variance (hidden moments are fp32)")
+    if av is not None:
+        av = av.reshape(-1, K).contiguous()
+        require_cuda_f32(av, "a.var")
+    B = am.shape[0]
+    if B > 64 * 65535:
+        raise BnnHipError("moments_linear: %d rows (at most %d)" % (B, 64 * 65535))
+    dev = am.device
+    s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
+    out_m = torch.empty((B, N), dtype=torch.float32, device=dev)
+    out_v = torch.empty((B, N), dtype=torch.float32, device=dev)
+    flags = (_lib.FLAG_RELU if relu else 0) | (_lib.FLAG_X_BF16 if _bf(am) else 0)
+    check(_lib.load().bnn_moments_forward(ptr(am), ptr(av), K, ptr(mu_w), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(out_m), ptr(out_v),
+                                          B, N, K, code, flags, stream_ptr(dev)), "bnn_moments_forward")
+    return Moments(out_m.reshape(lead + (N,)), out_v.reshape(lead + (N,)))
+
+
+def moments_relu(mom):
+    """ReLU of Gaussian activations by moment matching (bnn_moments_relu) -> Moments: with s = sqrt(v), alpha = m / s,
+    mean' = s (alpha Phi + phi), var' = v (Phi + alpha^2 Phi Phi(-alpha) + alpha phi (Phi(-alpha) - Phi) - phi^2) clamped at 0;
+    v == 0 gives (max(m, 0), 0).  A deterministic input (var None) stays one."""
+    mom = _as_moments(mom, "moments_relu")
+    if mom.var is None:
+        return Moments(torch.relu(mom.mean.detach()), None)
+    m, v = mom.mean.detach().contiguous(), mom.var.detach().contiguous()
+    require_cuda_f32(m, "mean")
+    require_cuda_f32(v, "var")
+    om, ov = torch.empty_like(m), torch.empty_like(v)
+    check(_lib.load().bnn_moments_relu(ptr(m), ptr(v), ptr(om), ptr(ov), m.numel(), stream_ptr(m.device)), "bnn_moments_relu")
+    return Moments(om, ov)
+
+
+def moments_sample(mom, key, nsamples):
+    """nsamples draws of independent Gaussians with the given moments in ONE launch (bnn_moments_sample) -> (S, *shape) fp32:
+    y_s[e] = m[e] + sqrt(v[e] + 1e-16) eps_s[e], e the flat index within one sample, eps_s[e] element e of the key's sample
+    sample0 + s (the LRT-noise contract).  The result is what the mc_* tails read.  CPU moments: torch.randn (the key is not
+    used and may be None)."""
+    mom = _as_moments(mom, "moments_sample")
+    S = int(nsamples)
+    m = mom.mean.detach()
+    v = torch.zeros_like(m) if mom.var is None else mom.var.detach()
+    if not m.is_cuda:
+        m64, v64 = m.double(), v.double()
+        return (m64 + torch.sqrt(v64 + 1e-16) * torch.randn((S,) + tuple(m.shape), dtype=torch.float64)).to(torch.float32)
+    m, v = m.contiguous(), v.contiguous()
+    require_cuda_f32(m, "mean")
+    require_cuda_f32(v, "var")
+    if m.dim() < 1:
+        raise BnnHipError("moments_sample: the moments must have at least one axis")
+    N = m.shape[-1]
+    rows = m.numel() // N if N else 0
+    if S < 1 or S > 0xFFFF:
+        raise BnnHipError("moments_sample: %d MC samples (1 .. 65535)" % S)
+    if m.numel() >= 2 ** 32:
+        raise BnnHipError("moments_sample: one sample has %d elements: the noise index is 32 bits wide" % m.numel())
+    y = torch.empty((S,) + tuple(m.shape), dtype=torch.float32, device=m.device)
+    r = _rng_struct(key, m.device)
+    check(_lib.load().bnn_moments_sample(ptr(m), ptr(v), ptr(y), rows, N, S, ctypes.byref(r), 0, stream_ptr(m.device)),
+          "bnn_moments_sample")
+    return y
+
+
+def moments_relu_f64(mom):
+    """moments_relu in float64 torch."""
+    mom = _as_moments(mom, "moments_relu_f64")
+    m = mom.mean.detach().to(torch.float64)
+    if mom.var is None:
+        return Moments(m.clamp_min(0), None)
+    v = mom.var.detach().to(torch.float64)
+    pos = v > 0
+    s = torch.sqrt(torch.where(pos, v, torch.ones_like(v)))
+    al = m / s
+    cdf, cdc = 0.5 * torch.special.erfc(-al / math.sqrt(2.0)), 0.5 * torch.special.erfc(al / math.sqrt(2.0))
+    pdf = torch.exp(-0.5 * al * al) / math.sqrt(2.0 * math.pi)
+    mean = s * (al * cdf + pdf)
+    var = (v * (cdf + al * al * cdf * cdc + al * pdf * (cdc - cdf) - pdf * pdf)).clamp_min(0)
+    return Moments(torch.where(pos, mean, m.clamp_min(0)), torch.where(pos, var, torch.zeros_like(v)))
+
+
+def moments_linear_f64(a, mu_w, rho_w, mu_b, rho_b, relu=False):
+    """moments_linear in float64 torch (sigma = 1e-10 + softplus(rho)) -> Moments of float64 tensors."""
+    mom = _as_moments(a, "moments_linear_f64")
+    f64 = lambda t: t.detach().to(torch.float64)         # noqa: E731
+    sig2 = lambda rho: (1e-10 + torch.nn.functional.softplus(f64(rho))) ** 2         # noqa: E731
+    am, mu, s2 = f64(mom.mean), f64(mu_w), sig2(rho_w)
+    m = am @ mu.t()
+    v = (am * am) @ s2.t()
+    if mom.var is not None:
+        v = v + f64(mom.var) @ (mu * mu + s2).t()
+    if mu_b is not None:
+        m, v = m + f64(mu_b), v + sig2(rho_b)
+    out = Moments(m, v)
+    return moments_relu_f64(out) if relu else out
+
+
+def moments_f64(a, layers):
+    """The moment recursion of a chain of dense layers in float64 torch -- the CPU path of predictive_moments and the tests'
+    reference: a, a tensor or Moments; layers, a sequence of (mu_w, rho_w, mu_b, rho_b, relu).  -> Moments of float64 tensors."""
+    mom = _as_moments(a, "moments_f64")
+    for mu_w, rho_w, mu_b, rho_b, relu in layers:
+        mom = moments_linear_f64(mom, mu_w, rho_w, mu_b, rho_b, relu)
+    return mom
+
+
 class _PlainLinear(torch.autograd.Function):
     """y[s] = x[s] @ w[s]^T + b[s] with given weights (F.linear, dense.py:60)."""
 

@@ -1099,6 +1099,37 @@ int bnn_conv3d_lrt_backward_weight(const float *x, const float *g_m, const float
                                    const bnn_conv3d_shape_t *shape, int nsets, int compute, void *workspace,
                                    int64_t workspace_bytes, void *stream);
 
+/* ---- K16: sampling-free inference, moment propagation through dense layers (csrc/bnn_moments.hip; ops.moments_linear,
+ * BayesianNetworkModule.predictive_moments).  No call site in the reference: one pass carries a mean and a variance per
+ * activation (independent across elements) through NormalLinear / LocalReparamLinear's posterior, w ~ N(mu_w, sigma_w^2),
+ * b ~ N(mu_b, sigma_b^2), sigma^2 = bnn_lrt_prepare's fp32 values:
+ *     m = a_m mu_w^T + mu_b
+ *     v = a_m^2 (sigma_w^2)^T + a_v (mu_w^2 + sigma_w^2)^T + sigma_b^2      (second term absent when a_v is NULL)
+ * Three contractions in one 64 x 64 tile from one pass over the operands; a_m^2 and mu_w^2 + sigma_w^2 (one fma) are formed in fp32
+ * by the loader before any rounding; both variance contractions add into one accumulator set; every addend of v is >= 0.
+ * compute: BNN_COMPUTE_F32 = v_mfma_f32_16x16x4_f32 (an ordered fp32 fma chain per output element); BNN_COMPUTE_BF16 = all six
+ * planes rounded to bf16 (RNE) as they are staged, v_mfma_f32_16x16x32_bf16, fp32 accumulate.  No atomics and no split
+ * contraction: identical calls give identical bits.  Every entry is graph-capturable and returns its errors before launching.
+ *
+ * a_m: (B, K) fp32, or bf16 with BNN_FLAG_X_BF16 (bf16 compute and a_v == NULL only); a_v: (B, K) fp32 or NULL (a deterministic
+ * input); both with row pitch lda.  mu_w, s2_w: (N, K) fp32; mu_b, s2_b: (N) fp32, both or neither.  out_m, out_v: (B, N) fp32.
+ * BNN_FLAG_RELU: the moment-matched ReLU below in the epilogue.
+ * Errors: BNN_E_NULL, BNN_E_SHAPE (extent < 1, lda < K), BNN_E_RANGE (rows > 64 * 65535), BNN_E_DTYPE (compute),
+ * BNN_E_UNSUPPORTED (unknown flag; a bf16 a_m in the fp32 mode or beside a_v), BNN_E_ALIGN (element; 16 bytes for the outputs). */
+int bnn_moments_forward(const void *a_m, const float *a_v, int64_t lda, const float *mu_w, const float *s2_w, const float *mu_b,
+                        const float *s2_b, float *out_m, float *out_v, int64_t B, int64_t N, int64_t K, int compute, int flags,
+                        void *stream);
+/* ReLU of a Gaussian N(m, v) by moment matching, s = sqrt(v), alpha = m / s, Phi / phi the standard normal cdf / pdf:
+ *     mean' = s (alpha Phi + phi)      var' = v (Phi + alpha^2 Phi Phi(-alpha) + alpha phi (Phi(-alpha) - Phi) - phi^2), clamped at 0
+ * v == 0 gives (max(m, 0), 0).  n elements, in place allowed.  The device function is the forward's epilogue's: same bits. */
+int bnn_moments_relu(const float *m, const float *v, float *out_m, float *out_v, int64_t n, void *stream);
+/* y_s[e] = m[e] + sqrt(v[e] + 1e-16) eps_s[e], e = b N + n, s = 0 .. nsamples - 1, ONE launch: the LRT-noise contract above
+ * (eps4 / eps1 on the key, sample sample0 + s).  m, v: (rows, N) fp32; y: (nsamples, rows, N) fp32; all 16-byte aligned.
+ * flags: 0.  Errors: BNN_E_NULL, BNN_E_SHAPE, BNN_E_RANGE (more than 65535 samples, rows N >= 2^32, bad rng),
+ * BNN_E_UNSUPPORTED (flags), BNN_E_ALIGN. */
+int bnn_moments_sample(const float *m, const float *v, float *y, int64_t rows, int64_t N, int nsamples, const bnn_rng_t *rng,
+                       int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
