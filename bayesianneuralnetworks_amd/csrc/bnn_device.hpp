@@ -13,6 +13,7 @@ namespace bnn {
 void set_error(const char *fmt, ...);
 void count_launch();
 int check_launch(const char *what);
+static inline bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 // bnn_dropout.hip: the mask entries' shared argument checks, and the mask launch with row pitches (no checks)
 int check_dropout_args(const char *who, int64_t rows, int64_t F, int nsamples, float p, const bnn_rng_t *rng);
 int mc_dropout_launch(const char *who, const void *x, int64_t x_sample_stride, int64_t ldx, void *y, int64_t y_sample_stride,

@@ -6,15 +6,11 @@
 //     v = a_m^2 (sigma_w^2)^T + a_v (mu_w^2 + sigma_w^2)^T + sigma_b^2          (second term absent for a deterministic input)
 // Every addend of v is non-negative: no difference of second moments is formed.
 //
-// One tile on K10's skeleton (bnn_lrt.hip): 64 x 64 outputs, 4 waves of 32 x 32, operands through registers, one LDS stage with
-// the next tile's global loads issued before the MFMAs of the current one.  Three contractions from one pass over the operands:
-//     P planes (MFMA A)   mu_w,  sigma_w^2,  mu_w^2 + sigma_w^2        Q planes (MFMA B)   a_m,  a_m^2,  a_v
-// The derived planes (fma(mu_w, mu_w, sigma_w^2) and a_m a_m) are formed in fp32 by the loader as it stages them, before any bf16
-// rounding.  The two variance contractions add into ONE accumulator set, so a lane holds K10's 32 accumulator registers.
-// bf16 compute: all planes rounded to bf16 (RNE) as they are written to LDS, v_mfma_f32_16x16x32_bf16.  fp32: v_mfma_f32_16x16x4_f32.
+// The contraction tile of bnn_lrt_tile.hpp with BK = 32 and, for an input that carries a variance, three planes per operand:
+//     P planes (MFMA A)   mu_w,  sigma_w^2,  [mu_w^2 + sigma_w^2]      Q planes (MFMA B)   a_m,  a_m^2,  [a_v]
+// The two variance contractions add into ONE accumulator set, so a lane holds K10's 32 accumulator registers.
 // Epilogue: + mu_b / + sigma_b^2, then (BNN_FLAG_RELU) the moment-matched ReLU moments_relu_dev -- the function the standalone
-// launch calls, so fused and standalone agree bit for bit.  Outputs fp32 (B, N), 16-byte stores (scalar when N % 4 != 0).
-// No atomics, no split of the contraction: identical calls give identical bits.
+// launch calls, so fused and standalone agree bit for bit.  Outputs fp32 (B, N).
 #include "bnn_lrt_tile.hpp"
 
 namespace bnn {
@@ -61,21 +57,14 @@ __global__ __launch_bounds__(kLrtThreads) void k_moments(const MomArgs A)
     constexpr int LDK = BF ? BK + 8 : BK + 1;       // bf16: rows stay 16-byte aligned for the 8-element fragment read
     constexpr int EPT = BK / 4;
     constexpr int NPL = VAR ? 3 : 2;                // planes per operand
-    constexpr int PL = kLrtTile * LDK;
-    __shared__ __attribute__((aligned(16))) T lds[2 * NPL * PL];
-    T *lp = lds, *lq = lds + NPL * PL;              // P planes: mu_w, s2_w, [mu_w^2 + s2_w]; Q planes: a_m, a_m^2, [a_v]
+    __shared__ __attribute__((aligned(16))) T lds[2 * NPL * kLrtTile * LDK];
+    T *lp = lds, *lq = lds + NPL * kLrtTile * LDK;
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wi = wave >> 1, wj = wave & 1;
     const int i0 = blockIdx.x * kLrtTile, j0 = blockIdx.y * kLrtTile;
     const bool a_bf = !VAR && A.a_bf16;
 
     f32x4 accm[2][2], accv[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) { accm[a][b] = f32x4{0.f, 0.f, 0.f, 0.f}; accv[a][b] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-
+    lrt_zero(accm, accv);
     float rmu[EPT], rs2[EPT], ram[EPT], rav[EPT] = {};
     auto fetch = [&](int c0) {
         lrt_fetch<false, BK>(rmu, A.mu_w, false, A.K, i0, A.N, c0, A.K);
@@ -85,107 +74,29 @@ __global__ __launch_bounds__(kLrtThreads) void k_moments(const MomArgs A)
     };
     fetch(0);
     for (int c0 = 0; c0 < A.K; c0 += BK) {
-#pragma unroll
-        for (int it = 0; it < EPT; ++it) {
-            const int idx = it * kLrtThreads + (int)threadIdx.x;
-            const int o = (idx / BK) * LDK + idx % BK;
-            lp[o] = lrt_cvt<T>(rmu[it]);
-            lp[PL + o] = lrt_cvt<T>(rs2[it]);
-            lq[o] = lrt_cvt<T>(ram[it]);
-            lq[PL + o] = lrt_cvt<T>(ram[it] * ram[it]);
-            if constexpr (VAR) {
-                lp[2 * PL + o] = lrt_cvt<T>(__builtin_fmaf(rmu[it], rmu[it], rs2[it]));
-                lq[2 * PL + o] = lrt_cvt<T>(rav[it]);
-            }
-        }
+        lrt_stage2<T, false, false, false, true, NPL, BK, LDK>(lp, lq, rmu, rs2, ram, rav);
         __syncthreads();
         if (c0 + BK < A.K) fetch(c0 + BK);
-        const int pr = (wi * 32 + (lane & 15)) * LDK, qr = (wj * 32 + (lane & 15)) * LDK;
-        if constexpr (BF) {
-#pragma unroll
-            for (int kk = 0; kk < BK / 32; ++kk) {
-                const int ko = kk * 32 + 8 * (lane >> 4);
-                s16x8 fp[NPL][2], fq[NPL][2];
-#pragma unroll
-                for (int pl = 0; pl < NPL; ++pl)
-#pragma unroll
-                    for (int a = 0; a < 2; ++a) {
-                        fp[pl][a] = *reinterpret_cast<const s16x8 *>(lp + pl * PL + pr + a * 16 * LDK + ko);
-                        fq[pl][a] = *reinterpret_cast<const s16x8 *>(lq + pl * PL + qr + a * 16 * LDK + ko);
-                    }
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        accm[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fp[0][a]),
-                                                                             __builtin_bit_cast(bf16x8, fq[0][b]), accm[a][b], 0, 0, 0);
-                        accv[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fp[1][a]),
-                                                                             __builtin_bit_cast(bf16x8, fq[1][b]), accv[a][b], 0, 0, 0);
-                    }
-                if constexpr (VAR) {
-#pragma unroll
-                    for (int a = 0; a < 2; ++a)
-#pragma unroll
-                        for (int b = 0; b < 2; ++b)
-                            accv[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fp[2][a]),
-                                                                                 __builtin_bit_cast(bf16x8, fq[2][b]), accv[a][b], 0, 0, 0);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < BK / 4; ++kk) {
-                const int ko = kk * 4 + (lane >> 4);
-                float fp[NPL][2], fq[NPL][2];
-#pragma unroll
-                for (int pl = 0; pl < NPL; ++pl)
-#pragma unroll
-                    for (int a = 0; a < 2; ++a) {
-                        fp[pl][a] = lp[pl * PL + pr + a * 16 * LDK + ko];
-                        fq[pl][a] = lq[pl * PL + qr + a * 16 * LDK + ko];
-                    }
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        accm[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fp[0][a], fq[0][b], accm[a][b], 0, 0, 0);
-                        accv[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fp[1][a], fq[1][b], accv[a][b], 0, 0, 0);
-                    }
-                if constexpr (VAR) {
-#pragma unroll
-                    for (int a = 0; a < 2; ++a)
-#pragma unroll
-                        for (int b = 0; b < 2; ++b)
-                            accv[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fp[2][a], fq[2][b], accv[a][b], 0, 0, 0);
-                }
-            }
-        }
+        lrt_mfma_block<T, NPL, BK, LDK>(accm, accv, lp, lq);
         __syncthreads();
     }
 
-    // ----- epilogue: lane holds out[j][i .. i + 3], i = i0 + 32 wi + 16 a + 4 (lane >> 4), j = j0 + 32 wj + 16 b + (lane & 15)
     const bool vec = (A.N & 3) == 0;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const int i = i0 + wi * 32 + a * 16 + 4 * (lane >> 4);
-            const int j = j0 + wj * 32 + b * 16 + (lane & 15);
-            if (i >= A.N || j >= A.B) continue;
-            const int ni = A.N - i < 4 ? A.N - i : 4;
+            LrtQuad q;
+            if (!lrt_quad(q, a, b, A.N, A.B)) continue;
             float rm[4] = {accm[a][b][0], accm[a][b][1], accm[a][b][2], accm[a][b][3]};
             float rv[4] = {accv[a][b][0], accv[a][b][1], accv[a][b][2], accv[a][b][3]};
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (A.mu_b && r < ni) { rm[r] += A.mu_b[i + r]; rv[r] += A.s2_b[i + r]; }
+                if (A.mu_b && r < q.ni) { rm[r] += A.mu_b[q.i + r]; rv[r] += A.s2_b[q.i + r]; }
                 if (A.relu) moments_relu_dev(rm[r], rv[r], rm[r], rv[r]);
             }
-            float *mo = A.out_m + (int64_t)j * A.N + i, *vo = A.out_v + (int64_t)j * A.N + i;
-            if (vec) {
-                *reinterpret_cast<float4 *>(mo) = make_float4(rm[0], rm[1], rm[2], rm[3]);
-                *reinterpret_cast<float4 *>(vo) = make_float4(rv[0], rv[1], rv[2], rv[3]);
-            } else {
-                for (int r = 0; r < ni; ++r) { mo[r] = rm[r]; vo[r] = rv[r]; }
-            }
+            const int64_t o = (int64_t)q.j * A.N + q.i;
+            lrt_store4x2(A.out_m + o, rm, A.out_v + o, rv, vec, q.ni);
         }
 }
 
@@ -200,8 +111,8 @@ __global__ __launch_bounds__(256) void k_moments_relu(const float *m, const floa
     }
 }
 
-// y_s[e] = m[e] + sqrt(v[e] + 1e-16) eps_s[e]: one thread per quad of the flat index e = b N + n, all S samples (K10's epilogue
-// as a launch of its own: the same fma, the same eps quad).  VEC: n % 4 == 0, 16-byte loads and stores.
+// y_s[e] = m[e] + sqrt(v[e] + 1e-16) eps_s[e]: one thread per quad of the flat index e = b N + n, all S samples (lrt_noise4: the
+// fma and the eps quad of K10's epilogue).  VEC: n % 4 == 0, 16-byte loads and stores.
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_moments_sample(const float *__restrict__ m, const float *__restrict__ v, float *__restrict__ y,
                                                         uint32_t n, int S, RngDev rng)
@@ -222,17 +133,12 @@ __global__ __launch_bounds__(256) void k_moments_sample(const float *__restrict_
 #pragma unroll
         for (int r = 0; r < 4; ++r) sd[r] = sqrtf(sd[r] + 1e-16f);
         for (int s = 0; s < S; ++s) {
-            const float4 z = eps4(rng, ed, q, rng.sample0 + (uint32_t)s);
-            const float yy[4] = {__builtin_fmaf(sd[0], z.x, mm[0]), __builtin_fmaf(sd[1], z.y, mm[1]),
-                                 __builtin_fmaf(sd[2], z.z, mm[2]), __builtin_fmaf(sd[3], z.w, mm[3])};
-            float *yo = y + (int64_t)s * n + e0;
-            if (VEC) *reinterpret_cast<float4 *>(yo) = make_float4(yy[0], yy[1], yy[2], yy[3]);
-            else for (int r = 0; r < ne; ++r) yo[r] = yy[r];
+            float yy[4];
+            lrt_noise4(yy, mm, sd, rng, ed, e0, rng.sample0 + (uint32_t)s, true, 4);
+            lrt_store4(y + (int64_t)s * n + e0, yy, VEC, ne);
         }
     }
 }
-
-static inline bool mom_misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 }  // namespace bnn
 
@@ -249,20 +155,18 @@ int bnn_moments_forward(const void *a_m, const float *a_v, int64_t lda, const fl
         set_error("%s: NULL pointer", who);
         return BNN_E_NULL;
     }
-    if (B < 0 || N < 1 || K < 1 || lda < K) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
-    if (B > 0x7FFFFFFF || N > 0x7FFFFFFF || K > 0x7FFFFFFF || (B + kLrtTile - 1) / kLrtTile > 65535) {
-        set_error("%s: extent outside the supported range (rows <= 64 * 65535, N, K < 2^31)", who);
-        return BNN_E_RANGE;
-    }
+    if (lda < K) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
+    const int rc = lrt_check_extents(who, B, N, K);
+    if (rc) return rc;
     if (compute != BNN_COMPUTE_F32 && compute != BNN_COMPUTE_BF16) { set_error("%s: unknown compute mode", who); return BNN_E_DTYPE; }
     if (flags & ~(BNN_FLAG_RELU | BNN_FLAG_X_BF16)) { set_error("%s: unknown flag", who); return BNN_E_UNSUPPORTED; }
     if ((flags & BNN_FLAG_X_BF16) && (compute != BNN_COMPUTE_BF16 || a_v)) {
         set_error("%s: a bf16 a_m needs the bf16 compute mode and a deterministic input (hidden moments are fp32)", who);
         return BNN_E_UNSUPPORTED;
     }
-    if (mom_misaligned(a_m, (flags & BNN_FLAG_X_BF16) ? 1 : 3) || mom_misaligned(a_v, 3) || mom_misaligned(mu_w, 3) ||
-        mom_misaligned(s2_w, 3) || mom_misaligned(mu_b, 3) || mom_misaligned(s2_b, 3) || mom_misaligned(out_m, 15) ||
-        mom_misaligned(out_v, 15)) {
+    if (misaligned(a_m, (flags & BNN_FLAG_X_BF16) ? 1 : 3) || misaligned(a_v, 3) || misaligned(mu_w, 3) ||
+        misaligned(s2_w, 3) || misaligned(mu_b, 3) || misaligned(s2_b, 3) || misaligned(out_m, 15) ||
+        misaligned(out_v, 15)) {
         set_error("%s: misaligned pointer (out_m and out_v: 16 bytes)", who);
         return BNN_E_ALIGN;
     }
@@ -291,7 +195,7 @@ int bnn_moments_relu(const float *m, const float *v, float *out_m, float *out_v,
     const char *who = "bnn_moments_relu";
     if (!m || !v || !out_m || !out_v) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
     if (n < 0) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
-    if (mom_misaligned(m, 3) || mom_misaligned(v, 3) || mom_misaligned(out_m, 3) || mom_misaligned(out_v, 3)) {
+    if (misaligned(m, 3) || misaligned(v, 3) || misaligned(out_m, 3) || misaligned(out_v, 3)) {
         set_error("%s: misaligned pointer", who);
         return BNN_E_ALIGN;
     }
@@ -317,7 +221,7 @@ int bnn_moments_sample(const float *m, const float *v, float *y, int64_t rows, i
     const int rc = check_rng(rng, nsamples);
     if (rc) { set_error("%s: bad rng", who); return rc; }
     if (flags) { set_error("%s: unknown flag (the samples are fp32)", who); return BNN_E_UNSUPPORTED; }
-    if (mom_misaligned(m, 15) || mom_misaligned(v, 15) || mom_misaligned(y, 15)) {
+    if (misaligned(m, 15) || misaligned(v, 15) || misaligned(y, 15)) {
         set_error("%s: misaligned pointer (m, v, y: 16 bytes)", who);
         return BNN_E_ALIGN;
     }

@@ -55,6 +55,32 @@ def _moments_asked(propagation, who, kl=None):
     raise ValueError("%s: propagation must be 'samples' or 'moments', got %r" % (who, propagation))
 
 
+def _on_device(x):
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
+def _refuse_cpu_tails(who, tails, *given):
+    """x is not on the device, so `tails` ("advance is a tail" / "advance / kl are tails") of the device launch cannot run."""
+    if any(t is not None for t in given):
+        from .. import ops
+        raise ops.BnnHipError("%s: %s of the device launch; x is not on the device" % (who, tails))
+
+
+def _refuse_device_state(who, state, state_type):
+    if state is not None and not (isinstance(state, state_type) and state.device.type == "cpu"):
+        from .. import ops
+        raise ops.BnnHipError("%s: x is not on the device, so state must be a %s on the CPU" % (who, state_type.__name__))
+
+
+def _scaled_sum(ys, scale, out):
+    """predictive_mean without the device tail: scale * sum over the samples, into `out` when given."""
+    m = ys.sum(0) * scale
+    if out is not None:
+        out.copy_(m.reshape(out.shape))
+        return out
+    return m
+
+
 class BayesianNetworkModule(Module):
     """container.py:17-37.  Subclasses implement `_forward`."""
 
@@ -106,26 +132,18 @@ class BayesianNetworkModule(Module):
         from .. import ops
         if samples is None:
             samples = self.samples
+        tail = self.mc_batched and _on_device(x)                    # the device launch reduces; else the sum below
         if _moments_asked(propagation, "predictive_mean"):
             ys = self._moment_outputs("predictive_mean", x, samples, sample0, kl, args, kwargs)
-            if ys.is_cuda:
-                return ops.mc_mean(ys, out=out, scale=(1.0 / samples) if scale is None else scale, advance=advance)
-            if advance is not None:
-                raise ops.BnnHipError("predictive_mean: advance is a tail of the device launch; x is not on the device")
-            m = ys.sum(0) * ((1.0 / samples) if scale is None else scale)
-            if out is not None:
-                out.copy_(m.reshape(out.shape))
-                return out
-            return m
-        if not (self.mc_batched and isinstance(x, torch.Tensor) and x.is_cuda):
+            tail, kl = ys.is_cuda, None                             # _moment_outputs has taken kl
+            if not tail:
+                _refuse_cpu_tails("predictive_mean", "advance is a tail", advance)
+        elif tail:
+            ys = self._forward_batched_stacked(x, samples, sample0, *args, _lazy_head=True, **kwargs)
+        else:
             ys = self.forward_stacked(x, samples, sample0, *args, **kwargs)
-            m = ys.sum(0) * ((1.0 / samples) if scale is None else scale)
-            if out is not None:
-                out.copy_(m.reshape(out.shape))
-                return out
-            return m
-        y = self._forward_batched_stacked(x, samples, sample0, *args, _lazy_head=True, **kwargs)
-        return ops.mc_mean(y, out=out, scale=(1.0 / samples) if scale is None else scale, advance=advance, kl=kl)
+        scale = (1.0 / samples) if scale is None else scale
+        return ops.mc_mean(ys, out=out, scale=scale, advance=advance, kl=kl) if tail else _scaled_sum(ys, scale, out)
 
     def predictive_uncertainty(self, x, samples=None, sample0=0, *, inputs, advance=None, kl=None, propagation='samples', **kwargs):
         """Predictive mean and uncertainty of `samples` MC draws of `_forward(x)` -> ops.PredictiveUncertainty(mean, total,
@@ -140,17 +158,11 @@ class BayesianNetworkModule(Module):
         instead of `samples` stochastic forwards; the tail is the same."""
         from .. import ops
         ops._unc_kind(inputs, "predictive_uncertainty", kl)         # before a draw is consumed
-        if samples is None:
-            samples = self.samples
         moments = _moments_asked(propagation, "predictive_uncertainty", kl)
-        if not (isinstance(x, torch.Tensor) and x.is_cuda):
-            if advance is not None or kl is not None:
-                raise ops.BnnHipError("predictive_uncertainty: advance / kl are tails of the device launch; x is not on the device")
-            ys = self._moment_outputs("predictive_uncertainty", x, samples, sample0, kl, (), kwargs) if moments else \
-                self.forward_stacked(x, samples, sample0, **kwargs)
-            return ops.uncertainty_f64(ys, inputs)
-        y = self._moment_outputs("predictive_uncertainty", x, samples, sample0, kl, (), kwargs) if moments else \
-            self._mc_outputs(x, samples, sample0, kwargs)
+        if not _on_device(x):
+            _refuse_cpu_tails("predictive_uncertainty", "advance / kl are tails", advance, kl)
+            return ops.uncertainty_f64(self._tail_inputs("predictive_uncertainty", x, samples, sample0, moments, kl, kwargs), inputs)
+        y = self._tail_inputs("predictive_uncertainty", x, samples, sample0, moments, kl, kwargs)
         return ops.mc_uncertainty(y, inputs, advance=advance, kl=kl)
 
     def predictive_score(self, x, target, samples=None, sample0=0, *, inputs, state=None, advance=None, propagation='samples',
@@ -168,23 +180,17 @@ class BayesianNetworkModule(Module):
         propagation='moments': as predictive_uncertainty."""
         from .. import ops
         ops._unc_kind(inputs, "predictive_score")                   # before a draw is consumed
-        if samples is None:
-            samples = self.samples
         moments = _moments_asked(propagation, "predictive_score")
-        if not (isinstance(x, torch.Tensor) and x.is_cuda):
-            if advance is not None:
-                raise ops.BnnHipError("predictive_score: advance is a tail of the device launch; x is not on the device")
-            if state is not None and not (isinstance(state, ops.ScoreState) and state.device.type == "cpu"):
-                raise ops.BnnHipError("predictive_score: x is not on the device, so state must be a ScoreState on the CPU")
+        if not _on_device(x):
+            _refuse_cpu_tails("predictive_score", "advance is a tail", advance)
+            _refuse_device_state("predictive_score", state, ops.ScoreState)
             cb, eb = (state.conf_bins, state.ent_bins) if state is not None else (15, 20)
-            ys = self._moment_outputs("predictive_score", x, samples, sample0, None, (), kwargs) if moments else \
-                self.forward_stacked(x, samples, sample0, **kwargs)
+            ys = self._tail_inputs("predictive_score", x, samples, sample0, moments, None, kwargs)
             out, vec = ops.score_f64(ys, target, inputs, cb, eb)
             if state is not None:
                 state.add_(vec)
             return out
-        y = self._moment_outputs("predictive_score", x, samples, sample0, None, (), kwargs) if moments else \
-            self._mc_outputs(x, samples, sample0, kwargs)
+        y = self._tail_inputs("predictive_score", x, samples, sample0, moments, None, kwargs)
         return ops.mc_score(y, target, inputs, state=state, advance=advance)
 
     def predictive_regression(self, x, samples=None, sample0=0, *, outputs, advance=None, kl=None, propagation='samples', **kwargs):
@@ -202,8 +208,6 @@ class BayesianNetworkModule(Module):
         moments ARE the answer (mean, total = epistemic = var, aleatoric = 0), `samples` is not used and nothing is drawn."""
         from .. import ops
         ops._reg_kind(outputs, "predictive_regression", kl)         # before a draw is consumed
-        if samples is None:
-            samples = self.samples
         moments = _moments_asked(propagation, "predictive_regression", kl)
         if moments and outputs == 'values':
             if advance is not None:
@@ -213,14 +217,10 @@ class BayesianNetworkModule(Module):
             mom = self.predictive_moments(x, **kwargs)
             var = torch.zeros_like(mom.mean) if mom.var is None else mom.var
             return ops.PredictiveRegression(mom.mean, var, torch.zeros_like(mom.mean), var.clone())
-        if not (isinstance(x, torch.Tensor) and x.is_cuda):
-            if advance is not None or kl is not None:
-                raise ops.BnnHipError("predictive_regression: advance / kl are tails of the device launch; x is not on the device")
-            ys = self._moment_outputs("predictive_regression", x, samples, sample0, kl, (), kwargs) if moments else \
-                self.forward_stacked(x, samples, sample0, **kwargs)
-            return ops.regression_f64(ys, outputs)
-        y = self._moment_outputs("predictive_regression", x, samples, sample0, kl, (), kwargs) if moments else \
-            self._mc_outputs(x, samples, sample0, kwargs)
+        if not _on_device(x):
+            _refuse_cpu_tails("predictive_regression", "advance / kl are tails", advance, kl)
+            return ops.regression_f64(self._tail_inputs("predictive_regression", x, samples, sample0, moments, kl, kwargs), outputs)
+        y = self._tail_inputs("predictive_regression", x, samples, sample0, moments, kl, kwargs)
         return ops.mc_regression(y, outputs, advance=advance, kl=kl)
 
     def predictive_regression_score(self, x, target, samples=None, sample0=0, *, outputs, state=None, advance=None,
@@ -240,24 +240,17 @@ class BayesianNetworkModule(Module):
         propagation='moments': as predictive_uncertainty."""
         from .. import ops
         ops._reg_kind(outputs, "predictive_regression_score")       # before a draw is consumed
-        if samples is None:
-            samples = self.samples
         moments = _moments_asked(propagation, "predictive_regression_score")
-        if not (isinstance(x, torch.Tensor) and x.is_cuda):
-            if advance is not None:
-                raise ops.BnnHipError("predictive_regression_score: advance is a tail of the device launch; x is not on the device")
-            if state is not None and not (isinstance(state, ops.RegressionScoreState) and state.device.type == "cpu"):
-                raise ops.BnnHipError("predictive_regression_score: x is not on the device, so state must be a "
-                                      "RegressionScoreState on the CPU")
+        if not _on_device(x):
+            _refuse_cpu_tails("predictive_regression_score", "advance is a tail", advance)
+            _refuse_device_state("predictive_regression_score", state, ops.RegressionScoreState)
             bins = state.pit_bins if state is not None else 20
-            ys = self._moment_outputs("predictive_regression_score", x, samples, sample0, None, (), kwargs) if moments else \
-                self.forward_stacked(x, samples, sample0, **kwargs)
+            ys = self._tail_inputs("predictive_regression_score", x, samples, sample0, moments, None, kwargs)
             out, mat = ops.regression_score_f64(ys, target, outputs, bins)
             if state is not None:
                 state.add_(mat)
             return out
-        y = self._moment_outputs("predictive_regression_score", x, samples, sample0, None, (), kwargs) if moments else \
-            self._mc_outputs(x, samples, sample0, kwargs)
+        y = self._tail_inputs("predictive_regression_score", x, samples, sample0, moments, None, kwargs)
         return ops.mc_regression_score(y, target, outputs, state=state, advance=advance)
 
     def predictive_evidential(self, x, samples=None, sample0=0, **kwargs):
@@ -277,7 +270,7 @@ class BayesianNetworkModule(Module):
         if not (isinstance(ys, tuple) and len(ys) == 4):
             raise ValueError("predictive_evidential: _forward must return (gamma, upsilon, alpha, beta), got %s"
                              % type(ys).__name__)
-        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        if not _on_device(x):
             return ops.evidential_f64(*ys)
         return ops.mc_evidential(*ys)
 
@@ -340,10 +333,15 @@ class BayesianNetworkModule(Module):
         self.__dict__["moment_key"] = key
         return ops.moments_sample(mom, key, samples)
 
-    def _mc_outputs(self, x, samples, sample0, kwargs):
-        """What a predictive_* tail launch reads for x on the device: with mc_batched one batched pass whose fused head, if any,
-        hands on its partials (ops.HeadPartials); else the stacked outputs of the serial loop."""
-        if self.mc_batched:
+    def _tail_inputs(self, who, x, samples, sample0, moments, kl, kwargs):
+        """The (S, *rows, C) outputs a predictive_* tail reads.  `moments`: drawn from the propagated moments (_moment_outputs).
+        Else `samples` stochastic forwards: for x on the device with mc_batched one batched pass whose fused head, if any, hands
+        on its partials (ops.HeadPartials); otherwise the stacked outputs of the serial loop."""
+        if samples is None:
+            samples = self.samples
+        if moments:
+            return self._moment_outputs(who, x, samples, sample0, kl, (), kwargs)
+        if self.mc_batched and _on_device(x):
             return self._forward_batched_stacked(x, samples, sample0, _lazy_head=True, **kwargs)
         return self.forward_stacked(x, samples, sample0, **kwargs)
 

@@ -834,6 +834,15 @@ def _lrt_prepare_raw(rho_w, rho_b):
     return s2_w, s2_b
 
 
+def _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b):
+    """The four posterior tensors of a K10 / K16 dense call: fp32, contiguous, on the device."""
+    require_cuda_f32(mu_w, "weight.mean")
+    require_cuda_f32(rho_w, "weight.scale")
+    if mu_b is not None:
+        require_cuda_f32(mu_b, "bias.mean")
+        require_cuda_f32(rho_b, "bias.scale")
+
+
 class _LrtLinear(torch.autograd.Function):
     """y_s = m + sqrt(v + 1e-16) eps_s, m = x mu_w^T + mu_b, v = x^2 (sigma_w^2)^T + sigma_b^2 (LocalReparamLinear): one
     operand launch + one contraction launch for all S samples.  Backward: eps re-created from the key in one elementwise launch
@@ -846,11 +855,7 @@ class _LrtLinear(torch.autograd.Function):
         require_cuda_act(x, "x")
         if (x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16) and compute != _lib.COMPUTE_BF16:
             raise BnnHipError("bf16 activations need compute mode 'bf16'")
-        for t, n in ((mu_w, "weight.mean"), (rho_w, "weight.scale")):
-            require_cuda_f32(t, n)
-        if mu_b is not None:
-            require_cuda_f32(mu_b, "bias.mean")
-            require_cuda_f32(rho_b, "bias.scale")
+        _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b)
         S = key.nsamples
         B, K = x.shape[-2], x.shape[-1]
         N = mu_w.shape[0]
@@ -953,12 +958,9 @@ def moments_linear(a, mu_w, rho_w, mu_b, rho_b, relu=False, compute="f32"):
     am = mom.mean.detach()
     av = None if mom.var is None else mom.var.detach()
     mu_w, rho_w = mu_w.detach().contiguous(), rho_w.detach().contiguous()
-    require_cuda_f32(mu_w, "weight.mean")
-    require_cuda_f32(rho_w, "weight.scale")
     if mu_b is not None:
         mu_b, rho_b = mu_b.detach().contiguous(), rho_b.detach().contiguous()
-        require_cuda_f32(mu_b, "bias.mean")
-        require_cuda_f32(rho_b, "bias.scale")
+    _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b)
     N, K = mu_w.shape
     if am.dim() < 1 or am.shape[-1] != K:
         raise BnnHipError("moments_linear: input has %s features, weight expects %d" % (am.shape[-1] if am.dim() else "no", K))
