@@ -464,6 +464,8 @@ def _linear_sampled_raw(x2, x_sample_stride, M, mu_w, rho_w, mu_b, rho_b, key_w,
             ldx, xs = pitch
             return _dense_raw(x2, 0 if x_sample_stride == 0 else xs, M, pre, K, relu, out_dtype, ldx=ldx, pad_rows=pad_rows)
         xb = x2.contiguous().to(torch.bfloat16)        # (the fused kernel rounds its A operand the same way)
+        if not _aligned16(xb):                         # (already bf16 and contiguous, at an odd offset: nothing above copied it)
+            xb = xb.clone()
         return _dense_raw(xb, x_sample_stride, M, pre, K, relu, out_dtype, pad_rows=pad_rows)
     x2 = x2.contiguous()
     y = torch.empty((S, M, N), dtype=out_dtype, device=x2.device)
@@ -471,6 +473,10 @@ def _linear_sampled_raw(x2, x_sample_stride, M, mu_w, rho_w, mu_b, rho_b, key_w,
     rb = _rng_struct(key_b, x2.device) if mu_b is not None else None
     flags = (_lib.FLAG_RELU if relu else 0) | (_lib.FLAG_X_BF16 if x2.dtype == torch.bfloat16 else 0) | \
             (_lib.FLAG_Y_BF16 if out_dtype == torch.bfloat16 else 0)
+    if flags & (_lib.FLAG_X_BF16 | _lib.FLAG_Y_BF16) and not _aligned16(x2, mu_w, rho_w):
+        # bf16 activations exist only on the kernels' 16-B path, which refuses an operand at an odd offset (a view into a flat
+        # parameter buffer, a row slice): such an operand is copied -- the draw is addressed by position, so the bits are the same
+        x2, mu_w, rho_w = (t if _aligned16(t) else t.clone() for t in (x2, mu_w, rho_w))
     if (M >= DRAW_ONCE_MIN_ROWS and N > 16 and K % 8 == 0 and mu_w.data_ptr() % 16 == 0 and rho_w.data_ptr() % 16 == 0):
         # Large batch: the fused kernel's 256- / 512-row tiles would re-draw every weight M / 256 (M / 512) times, and at
         # that size the draw is what the launch is made of -- so the weights of the S samples are drawn ONCE by K1 (same
@@ -521,6 +527,11 @@ DENSE_X3_F32 = os.environ.get("BNN_DENSE_X3", "1") != "0"    # fp32 parity mode 
 
 def _bf(t):
     return t.dtype == torch.bfloat16
+
+
+def _aligned16(*ts):
+    """Every tensor starts on a 16-byte boundary (what the kernels' 16-B loads and the LDS-DMA ask of an operand)."""
+    return all(t.data_ptr() % 16 == 0 for t in ts)
 
 
 # --- KL gradient fused into the weight-gradient launch ------------------------------------------------
@@ -769,8 +780,10 @@ class _SampledLinear(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # a shared input sums its gradient over the samples: fp32 partials, then one reduction
             gx_dtype = torch.float32 if ctx.shared_x else x.dtype
+            # (bnn_linear_backward_input_sampled reads mu_w, rho_w and gy in 16-B pieces and refuses them elsewhere: a posterior that
+            # is a view into a flat buffer, a gy that is a slice of a larger gradient -> the explicit-weight kernel below)
             fused = K % 4 == 0 and N % (8 if _bf(gy) else 4) == 0 and \
-                (compute == _lib.COMPUTE_BF16 or (not _bf(gy) and gx_dtype == torch.float32))
+                (compute == _lib.COMPUTE_BF16 or (not _bf(gy) and gx_dtype == torch.float32)) and _aligned16(mu_w, rho_w, gy)
             if ctx.drawn_w is not None and _bf(gy) and gx_dtype == torch.bfloat16:
                 gx = _dgrad_drawn_raw(gy, ctx.drawn_w, K)
             elif fused:
@@ -1023,6 +1036,7 @@ def moments_sample(mom, key, nsamples):
         raise BnnHipError("moments_sample: %d MC samples (1 .. 65535)" % S)
     if m.numel() >= 2 ** 32:
         raise BnnHipError("moments_sample: one sample has %d elements: the noise index is 32 bits wide" % m.numel())
+    m, v = (t if _aligned16(t) else t.clone() for t in (m, v))     # (bnn_moments_sample refuses moments off a 16-B boundary)
     y = torch.empty((S,) + tuple(m.shape), dtype=torch.float32, device=m.device)
     r = _rng_struct(key, m.device)
     check(_lib.load().bnn_moments_sample(ptr(m), ptr(v), ptr(y), rows, N, S, ctypes.byref(r), 0, stream_ptr(m.device)),
@@ -1579,6 +1593,8 @@ class _SampledConv2d(torch.autograd.Function):
             need_b = False
         if need_x:
             gpanel = torch.empty((S, M, K), dtype=torch.float32, device=dev)
+            if not _aligned16(mu_w, rho_w):     # the re-draw reads the posterior in 16-B pieces: a view at an odd offset is copied
+                mu_w, rho_w = mu_w.clone(), rho_w.clone()
             check(_lib.load().bnn_linear_backward_input_sampled(ptr(rows), M * O, O, ptr(mu_w), ptr(rho_w), ptr(gpanel), M * K, K,
                                                                 M, O, K, S, ctypes.byref(rw), compute, aflag, stream_ptr(dev)),
                   "bnn_linear_backward_input_sampled")

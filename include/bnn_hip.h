@@ -114,7 +114,7 @@ enum {
     BNN_E_NULL = -1,      /* required pointer is NULL */
     BNN_E_SHAPE = -2,     /* negative / zero / inconsistent extent */
     BNN_E_DTYPE = -3,     /* unknown dtype code */
-    BNN_E_ALIGN = -4,     /* pointer not aligned to the element size */
+    BNN_E_ALIGN = -4,     /* pointer not aligned: to its element, or to the 16 bytes the entry documents for it */
     BNN_E_RANGE = -5,     /* value outside the supported range (e.g. >65535 samples) */
     BNN_E_UNSUPPORTED = -6,
     BNN_E_DEVICE = -7     /* a kernel reported an internal error through the device error word (bnn_check_device) */
@@ -253,7 +253,9 @@ enum {
     BNN_FLAG_RELU = 1,
     /* bf16 compute mode only: x is bf16 in memory (ldx, strides in elements; K % 8 == 0,
      * 16-B aligned) / y is written as bf16.  Lets a chain of layers keep its hidden
-     * activations in bf16: half the activation stream of the next layer. */
+     * activations in bf16: half the activation stream of the next layer.  With either flag x AND the weights (mu_w and
+     * rho_w, or w) must be 16-B aligned: BNN_E_UNSUPPORTED otherwise.  Without them every operand may lie on its element
+     * (BNN_E_ALIGN below that); 16-B aligned x, weights and K % 4 == 0 buy the sampler-paced kernel. */
     BNN_FLAG_X_BF16 = 2,
     BNN_FLAG_Y_BF16 = 4
 };
@@ -438,7 +440,9 @@ int bnn_linear_backward_input(const void *gy, int64_t gy_sample_stride, int64_t 
  * KL (kl != NULL): the gradient of the layer's share of KLDivergence (loss.py:16-38) is added in the
  * same final store -- g_mu += c (mu - mu_p) / sigma_p^2, g_rho += c (sigma / sigma_p^2 - 1 / sigma)
  * sigmoid(rho), c = *upstream * scale -- instead of a separate bnn_kl_backward pass plus autograd's
- * accumulation adds.  scale_x = 1 / (n_x * ntensors * n_batches), n_x = elements of that tensor. */
+ * accumulation adds.  scale_x = 1 / (n_x * ntensors * n_batches), n_x = elements of that tensor.
+ * Alignment: x, gy, rho_w and the bias tensors on their element (16 bytes buy the 16-B loads and the LDS-DMA kernel); with
+ * K % 4 == 0 g_mu and g_rho are stored four columns at a time and must be 16-B aligned, BNN_E_ALIGN otherwise. */
 typedef struct bnn_kl_fuse {
     const float *upstream;      /* device scalar: d loss / d KL */
     const float *mu_w;          /* (N, K) */
@@ -459,8 +463,10 @@ int bnn_linear_backward_weight_sampled(const void *x, int64_t x_sample_stride, i
  * as the three entry points above.  gy fp32; flags: BNN_FLAG_X_BF16 = x is bf16, BNN_FLAG_Y_BF16 = gx
  * is written as bf16.  Needs the registered workspace (S * (2 N K + N) floats); BNN_E_UNSUPPORTED
  * otherwise (callers then use the general entry points).  Rows of x and gx are read / written four
- * elements at a time: bases, sample strides and the pitches ldx, ldgx must be multiples of 4 elements,
- * BNN_E_ALIGN otherwise.  Every argument check, both keys included, comes before the first launch. */
+ * elements at a time: bases, sample strides and the pitches ldx, ldgx must be multiples of 4 elements;
+ * mu_w, rho_w, g_mu and g_rho are read / written 16 bytes at a time and must be 16-B aligned: BNN_E_ALIGN
+ * otherwise (callers use the general entry points then, too).  gy: element alignment.  Every argument check, both
+ * keys included, comes before the first launch. */
 int bnn_linear_backward_narrow_sampled(const void *x, int64_t x_sample_stride, int64_t ldx,
                                        const float *gy, int64_t gy_sample_stride, int64_t ldgy,
                                        const float *mu_w, const float *rho_w,
@@ -471,7 +477,8 @@ int bnn_linear_backward_narrow_sampled(const void *x, int64_t x_sample_stride, i
                                        const bnn_rng_t *rng_w, const bnn_rng_t *rng_b,
                                        const bnn_kl_fuse_t *kl, int flags, int accumulate, void *stream);
 /* F.linear's own weight gradient, per sample: gw[s][n][k] (+)= sum_m gy[s][m][n] * x[s][m][k],
- * gw[s] = gw + s * gw_sample_stride (parity mode, where the draw is a separate op). */
+ * gw[s] = gw + s * gw_sample_stride (parity mode, where the draw is a separate op).  With K % 4 == 0 gw must be 16-B aligned
+ * and gw_sample_stride a multiple of 4 (BNN_E_ALIGN otherwise); x and gy: element alignment. */
 int bnn_linear_backward_weight(const void *x, int64_t x_sample_stride, int64_t ldx,
                                const void *gy, int64_t gy_sample_stride, int64_t ldgy,
                                float *gw, int64_t gw_sample_stride,
@@ -589,7 +596,9 @@ int bnn_conv2d_dense_images(const bnn_conv2d_shape_t *shape, int variant, int ns
  *   bnn_linear_backward_weight_sampled(panel, rows, ...)   -> g_mu, g_rho of the (O, K) weight
  *   bnn_linear_backward_input_sampled(rows, ...) -> gpanel (S*M, K) fp32
  *   bnn_conv2d_col2im(gpanel)                    -> gx (S | 1, B, C, H, W), gather (no atomics);
- *                                                   shared_x != 0 also sums over the samples. */
+ *                                                   shared_x != 0 also sums over the samples.
+ * bnn_conv2d_im2col: the panel must be 16-B aligned (BNN_E_UNSUPPORTED otherwise); x on its element (16 bytes and
+ * C H W % 4 == 0 buy 16-B image loads). */
 int bnn_conv2d_im2col(const float *x, int64_t x_sample_stride, const bnn_conv2d_shape_t *shape,
                       int x_samples, void *panel, int out_bf16, void *stream);
 int bnn_conv2d_col2im(const float *gpanel, const bnn_conv2d_shape_t *shape, int nsamples,

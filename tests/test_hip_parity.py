@@ -1151,6 +1151,18 @@ def test_full_size_backward_properties(env):
 def test_sampled_conv2d_backward_vs_float64_autograd(env, cfg, mode):
     """Sampled conv2d backward, all HIP (NCHW -> rows, im2col panel, fused weight / input gradient kernels,
     col2im): against float64 autograd through F.conv2d (conv.py:116) on the oracle's draws."""
+    sampled_conv2d_backward_check(env, cfg, mode)
+
+
+# tolerances of the sampled / plain conv2d checks against float64, relative to the output scale (assert_close_scaled):
+# (forward, gradients) per compute mode
+CONV2D_TOL = {"f32": (1e-5, 2e-5), "bf16": (2e-2, 3e-2)}
+
+
+def sampled_conv2d_backward_check(env, cfg, mode, place=None):
+    """The body of test_sampled_conv2d_backward_vs_float64_autograd -> (y, gradients).  place(name, tensor) (optional) returns the
+    device tensor to use for the operand `name` -- the same values somewhere else in memory (test_operand_alignment.py)."""
+    put = place if place is not None else (lambda name, t: t)
     from bayesianneuralnetworks_amd._rng import DrawKey
     S, B, C, H, W, O, k, st, pd, dl, bias, shared = cfg[:12]
     groups = cfg[12] if len(cfg) > 12 else 1                 # (k, st, pd, dl: one number for both axes or an (h, w) pair)
@@ -1163,13 +1175,13 @@ def test_sampled_conv2d_backward_vs_float64_autograd(env, cfg, mode):
     rhob = torch.randn(O, generator=gen) * 0.15 - 2.0
     x = torch.randn((B, C, H, W) if shared else (S, B, C, H, W), generator=gen)
     kw, kb = DrawKey(5, 40, 0, S, 3), DrawKey(5, 41, 0, S, 3)
-    xd = x.to(dev).requires_grad_(True)
-    md, rd = mu.to(dev).requires_grad_(True), rho.to(dev).requires_grad_(True)
-    mbd, rbd = (mub.to(dev).requires_grad_(True), rhob.to(dev).requires_grad_(True)) if bias else (None, None)
+    xd = put("x", x.to(dev)).requires_grad_(True)
+    md, rd = put("mu_w", mu.to(dev)).requires_grad_(True), put("rho_w", rho.to(dev)).requires_grad_(True)
+    mbd, rbd = (put("mu_b", mub.to(dev)).requires_grad_(True), put("rho_b", rhob.to(dev)).requires_grad_(True)) if bias else (None, None)
     n0 = env["lib"].bnn_launch_count()
     y = env["ops"].conv2d_sampled(xd, md, rd, mbd, rbd, kw, kb if bias else None, shared, st, pd, dl, groups, mode)
     gy = torch.randn(y.shape, generator=gen)
-    grads = torch.autograd.grad(y, [xd, md, rd] + ([mbd, rbd] if bias else []), gy.to(dev))
+    grads = torch.autograd.grad(y, [xd, md, rd] + ([mbd, rbd] if bias else []), put("gy", gy.to(dev)))
     Kc = C * kh * kw_
     if groups == 1 and Kc % 8 == 0 and Kc >= 32 and O >= 16 and O % 8 == 0:
         assert env["lib"].bnn_launch_count() >= n0 + 7       # fwd 2 + rows, im2col, wgrad, dgrad, col2im
@@ -1187,14 +1199,14 @@ def test_sampled_conv2d_backward_vs_float64_autograd(env, cfg, mode):
             b_ = mb64 + (1e-10 + torch.nn.functional.softplus(rb64)) * eb
         ys.append(torch.nn.functional.conv2d(x64 if shared else x64[s_], w, b_, st, pd, dl, groups))
     y64 = torch.stack(ys)
-    tol_y = 1e-5 if mode == "f32" else 2e-2
+    tol_y, tol = CONV2D_TOL[mode]
     assert_close_scaled(N(y), y64.detach().numpy(), tol_y, "y %s %s" % (cfg, mode))
     want = torch.autograd.grad(y64, [x64, m64, r64] + ([mb64, rb64] if bias else []), gy.double())
-    tol = 2e-5 if mode == "f32" else 3e-2
     for name, got, w_ in zip(("g_x", "g_mu", "g_rho", "g_mu_b", "g_rho_b"), grads, want):
         assert got.shape == w_.shape
         assert torch.isfinite(got).all()
         assert_close_scaled(N(got), w_.numpy(), tol, "%s %s %s" % (name, cfg, mode))
+    return y.detach(), [g.detach() for g in grads]
 
 
 @pytest.mark.parametrize("shared", [False, True])
