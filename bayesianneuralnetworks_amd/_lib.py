@@ -20,6 +20,7 @@ FLAG_RELU = 1
 FLAG_X_BF16 = 2
 E_ALIGN, E_UNSUPPORTED, E_DEVICE = -4, -6, -7     # BNN_E_ALIGN, BNN_E_UNSUPPORTED, BNN_E_DEVICE (include/bnn_hip.h)
 FLAG_Y_BF16 = 4
+FLAG_ELU = 8                                     # BNN_FLAG_ELU (bnn_conv3d_moments_forward)
 UNC_LOGITS, UNC_PROBS = 0, 1                     # BNN_UNC_* (bnn_mc_uncertainty)
 REG_VALUES, REG_MEAN_LOGVAR, REG_MEAN_VAR = 0, 1, 2     # BNN_REG_* (bnn_mc_regression)
 
@@ -228,6 +229,8 @@ SIGNATURES = {
     "bnn_moments_forward": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
     "bnn_moments_relu": (_int, [_p, _p, _p, _p, _i64, _p]),
     "bnn_moments_sample": (_int, [_p, _p, _p, _i64, _i64, _int, _rngp, _int, _p]),
+    "bnn_conv3d_moments_forward": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, ctypes.c_float, _p]),
+    "bnn_moments_elu": (_int, [_p, _p, _p, _p, _i64, ctypes.c_float, _p]),
 }
 
 _lib = None

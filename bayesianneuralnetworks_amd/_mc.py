@@ -39,9 +39,9 @@ def current():
 
 
 class MomentContext:
-    """Set by BayesianNetworkModule.predictive_moments for ONE pass of `_forward`: inside it NormalLinear and LocalReparamLinear
-    take a tensor (a deterministic input) or an ops.Moments and hand on the mean and variance of their output
-    (ops.moments_linear) instead of samples.  They draw nothing and record no key.  Thread-local, like McContext, and kept apart
+    """Set by BayesianNetworkModule.predictive_moments for ONE pass of `_forward`: inside it NormalLinear, LocalReparamLinear,
+    NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d take a tensor (a deterministic input) or an ops.Moments and hand on
+    the mean and variance of their output (ops.moments_linear, ops.moments_convNd) instead of samples.  They draw nothing and record no key.  Thread-local, like McContext, and kept apart
     from it: an MC-batched pass and a moment pass do not see each other."""
 
     def __enter__(self):

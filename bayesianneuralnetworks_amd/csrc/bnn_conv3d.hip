@@ -20,6 +20,7 @@
 //   WGRAD A2 = x (.) S_s[b][c], B2 = gy (.) R_s[b][o]; both partials to slabs [slab][s][mean | stddev][O][K], then
 //         k_conv3d_flip_wsum adds slabs and samples in a fixed order and applies softplus'.
 #include "bnn_device.hpp"
+#include "bnn_moments_act.hpp"
 
 #include <algorithm>
 
@@ -771,6 +772,216 @@ __global__ __launch_bounds__(256) void k_lrt_conv_bias_grad(const float *__restr
     }
 }
 
+// ---- K17: moment propagation through a convolution (sampling-free inference; NormalConv / LocalReparamConv 1d / 2d / 3d inside
+// BayesianNetworkModule.predictive_moments).  Input and output hold a mean and a variance per element, independent across elements:
+//     m = conv(a_m, mu_w) + mu_b
+//     v = conv(a_m^2, sigma_w^2) + conv(a_v, mu_w^2 + sigma_w^2) + sigma_b^2          (second term absent for a deterministic input)
+// Every addend of v is non-negative.  K11's forward tile (128 x 64 x 32, im2col in the loader, padding reads zero, groups in the
+// grid) with K16's planes: A planes a_m, a_m^2, [a_v]; B planes mu_w, sigma_w^2, [fma(mu_w, mu_w, sigma_w^2)], the derived planes
+// formed in fp32 as they are staged (before any bf16 rounding).  Both variance contractions add into ONE accumulator set: a lane
+// holds K11's 64 accumulator registers.  Epilogue: + mu_b / + sigma_b^2, then moments_relu_dev or moments_elu_dev
+// (bnn_moments_act.hpp: the standalone launches' functions, so fused and standalone agree bit for bit); fp32 (B, O, P) stores.
+// No sample axis, no rng, no atomics, no split reduction: identical calls give identical bits.
+struct MomConvArgs {
+    const float *a_m, *a_v;                  // (B, C, D, H, W); a_v NULL in the deterministic instantiation
+    const float *w1, *w2;                    // mu_w, sigma_w^2, O x K
+    const float *b1, *b2;                    // mu_b, sigma_b^2 (both or neither)
+    float *out_m, *out_v;                    // (B, O, OD, OH, OW)
+    int32_t act;                             // 0, BNN_FLAG_RELU or BNN_FLAG_ELU
+    float elu_alpha;
+};
+
+template <typename T, bool VAR>
+__global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d(const Conv3dGeo g, const MomConvArgs a)
+{
+    constexpr int LDK = Op<T>::LDK;
+    constexpr int NPL = VAR ? 3 : 2;                 // planes per operand
+    __shared__ __attribute__((aligned(16))) T As[NPL * C3_BM * LDK];
+    __shared__ __attribute__((aligned(16))) T Bs[NPL * C3_BN * LDK];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave & 1, wn = wave >> 1;
+    const int grp = blockIdx.z;
+
+    const int32_t M = g.B * g.P, N = g.Ng;
+    const int32_t m0 = blockIdx.x * C3_BM, n0 = blockIdx.y * C3_BN;
+    const int32_t rend = g.K;
+
+    // ---- A loader: row ar of the tile, reduction offsets ah * 16 .. + 15 of each k-tile
+    const int ar = tid & (C3_BM - 1);
+    const int ah = __builtin_amdgcn_readfirstlane(tid >> 7);
+    const int32_t am = m0 + ar;
+    const bool arow = am < M;
+    int32_t abase = 0, z0 = 0, z1 = 0, z2 = 0;       // gather origin of the row
+    if (arow) {
+        const uint32_t b = fdiv(am, g.fP), p = am - b * g.P;
+        const uint32_t q = fdiv(p, g.fOW), ow = p - q * g.OW, od = fdiv(q, g.fOH), oh = q - od * g.OH;
+        z0 = od * g.sd - g.pd; z1 = oh * g.sh - g.ph; z2 = ow * g.sw - g.pw;
+        abase = (b * g.C + grp * g.Cg) * g.Pin;
+    }
+
+    // v: a_m; v2: a_v (VAR only; dead otherwise).  Reduction index = (channel, kd, kh, kw), stepped with carries
+    auto fetch_a = [&](int32_t r0, float (&v)[16], float (&v2)[16]) {
+        const int32_t r = r0 + ah * 16;
+        uint32_t c = 0, kd = 0, kh = 0, kw = 0;
+        if (r < rend) {
+            c = fdiv(r, g.fT);
+            const uint32_t t = r - c * g.T, q = fdiv(t, g.fKW);
+            kw = t - q * g.KW; kd = fdiv(q, g.fKH); kh = q - kd * g.KH;
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int32_t id = z0 + (int32_t)kd * g.dd, ih = z1 + (int32_t)kh * g.dh, iw = z2 + (int32_t)kw * g.dw;
+            const bool ok = arow && r + j < rend && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H &&
+                            (uint32_t)iw < (uint32_t)g.W;
+            const int32_t off = abase + (int32_t)c * g.Pin + (id * g.H + ih) * g.W + iw;
+            v[j] = ok ? a.a_m[off] : 0.f;
+            if constexpr (VAR) v2[j] = ok ? a.a_v[off] : 0.f;
+            if (++kw == (uint32_t)g.KW) { kw = 0; if (++kh == (uint32_t)g.KH) { kh = 0; if (++kd == (uint32_t)g.KD) { kd = 0; ++c; } } }
+        }
+    };
+
+    // ---- B loader: reduction offset bk of each k-tile, rows bn + 8 i of the tile (w[o][r])
+    const int bk = tid & (C3_BK - 1), bn = tid >> 5;
+    const int64_t wb = (int64_t)grp * g.Ng * g.K;
+    auto fetch_b = [&](int32_t r0, float (&v)[8], float (&v2)[8]) {
+        const int32_t r = r0 + bk;
+        const bool rok = r < rend;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int32_t n = n0 + bn + 8 * i;
+            const bool ok = rok && n < N;
+            v[i] = ok ? a.w1[wb + (int64_t)n * g.K + r] : 0.f;
+            v2[i] = ok ? a.w2[wb + (int64_t)n * g.K + r] : 0.f;
+        }
+    };
+
+    // the derived planes in fp32, then rounded as the plain copies
+    auto store_tiles = [&](const float (&va)[16], const float (&va2)[16], const float (&vb)[8], const float (&vb2)[8]) {
+        T *pa = As + ar * LDK + ah * 16;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            st_lds(pa + j, va[j]);
+            st_lds(pa + C3_BM * LDK + j, va[j] * va[j]);
+            if constexpr (VAR) st_lds(pa + 2 * C3_BM * LDK + j, va2[j]);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            T *pb = Bs + (bn + 8 * i) * LDK + bk;
+            st_lds(pb, vb[i]);
+            st_lds(pb + C3_BN * LDK, vb2[i]);
+            if constexpr (VAR) st_lds(pb + 2 * C3_BN * LDK, __builtin_fmaf(vb[i], vb[i], vb2[i]));
+        }
+    };
+
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    f32x4 acc[2][4][2];                              // [mean | variance]: planes 1 and 2 both add into acc[1]
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int ntile = (rend + C3_BK - 1) / C3_BK;
+    float va[16], va2[16], vb[8], vb2[8];
+    fetch_a(0, va, va2);
+    fetch_b(0, vb, vb2);
+    for (int step = 0; step < ntile; ++step) {
+        __syncthreads();                                // the previous tile's fragment reads are done
+        store_tiles(va, va2, vb, vb2);
+        __syncthreads();
+        if (step + 1 < ntile) {                         // the next tile's loads fly under this tile's MFMAs
+            fetch_a((step + 1) * C3_BK, va, va2);
+            fetch_b((step + 1) * C3_BK, vb, vb2);
+        }
+        if constexpr (sizeof(T) == 2) {
+            typedef short s16x8 __attribute__((ext_vector_type(8)));
+#pragma unroll
+            for (int h = 0; h < NPL; ++h) {
+                const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
+                s16x8 fa[4], fb[2];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    fa[i] = *reinterpret_cast<const s16x8 *>(A + (wm * 64 + i * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    fb[j] = *reinterpret_cast<const s16x8 *>(Bt + (wn * 32 + j * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[h ? 1 : 0][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[h ? 1 : 0][i][j], 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < C3_BK / 4; ++kk) {
+#pragma unroll
+                for (int h = 0; h < NPL; ++h) {
+                    const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
+                    float fa[4], fb[2];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) fa[i] = A[(wm * 64 + i * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) fb[j] = Bt[(wn * 32 + j * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[h ? 1 : 0][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[h ? 1 : 0][i][j], 0, 0, 0);
+                }
+            }
+        }
+    }
+
+    // ---- epilogue: lane holds C[(lane >> 4) * 4 + q][lane & 15] of each 16 x 16 block; a lane's quad runs along the output
+    // position p: with P % 4 == 0 it is four consecutive elements of one image and channel
+    const bool vec = (g.P & 3) == 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
+        if (n >= N) continue;
+        const int32_t o = grp * g.Ng + n;
+        const float mb = a.b1 ? a.b1[o] : 0.f, sb = a.b1 ? a.b2[o] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int32_t mq = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
+            if (mq >= M) continue;
+            float r1[4], r2[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                r1[q] = acc[0][i][j][q] + mb;
+                r2[q] = acc[1][i][j][q] + sb;
+            }
+            if (a.act == BNN_FLAG_RELU) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) moments_relu_dev(r1[q], r2[q], r1[q], r2[q]);
+            } else if (a.act == BNN_FLAG_ELU) {
+#pragma unroll 1
+                for (int q = 0; q < 4; ++q) moments_elu_dev(r1[q], r2[q], a.elu_alpha, r1[q], r2[q]);
+            }
+            // element (b O + o) P + p of output row m = b P + p
+            auto elem = [&](uint32_t m) {
+                const uint32_t b = fdiv(m, g.fP);
+                return (b * (uint32_t)g.O + (uint32_t)o) * (uint32_t)g.P + (m - b * (uint32_t)g.P);
+            };
+            if (vec) {
+                const uint32_t e0 = elem(mq);              // the quad stays inside one image and channel
+                *reinterpret_cast<float4 *>(a.out_m + e0) = make_float4(r1[0], r1[1], r1[2], r1[3]);
+                *reinterpret_cast<float4 *>(a.out_v + e0) = make_float4(r2[0], r2[1], r2[2], r2[3]);
+            } else {
+                const int nq = M - mq < 4 ? M - mq : 4;
+                for (int q = 0; q < nq; ++q) {
+                    const uint32_t e = elem(mq + q);
+                    a.out_m[e] = r1[q];
+                    a.out_v[e] = r2[q];
+                }
+            }
+        }
+    }
+}
+
 static int conv3d_geo(const char *who, const bnn_conv3d_shape_t *sh, int nsamples, int compute, Conv3dGeo &g)
 {
     if (!sh) { set_error("%s: NULL shape", who); return BNN_E_NULL; }
@@ -1159,6 +1370,55 @@ int bnn_conv3d_lrt_backward_weight(const float *x, const float *g_m, const float
     if ((rc = check_launch(who)) || !bias) return rc;
     hipLaunchKernelGGL(k_lrt_conv_bias_grad, dim3((unsigned)g.O), dim3(256), 0, st, g_m, g_v, (int64_t)nsets * g.B, g.O, g.P, rho_b,
                        g_mu_b, g_rho_b);
+    return check_launch(who);
+}
+
+// ---- K17 entry (moment propagation through NormalConv / LocalReparamConv 1d / 2d / 3d) ---------------------------------------
+int bnn_conv3d_moments_forward(const float *a_m, const float *a_v, const float *mu_w, const float *s2_w, const float *mu_b,
+                               const float *s2_b, float *out_m, float *out_v, const bnn_conv3d_shape_t *shape, int compute,
+                               int flags, float elu_alpha, void *stream)
+{
+    const char *who = "bnn_conv3d_moments_forward";
+    if (!shape) { set_error("%s: NULL shape", who); return BNN_E_NULL; }
+    bnn_conv3d_shape_t sh = *shape;
+    const bool empty = sh.B == 0;               // no images: every other check still runs, nothing is launched
+    if (empty) sh.B = 1;
+    Conv3dGeo g;
+    const int rc = conv3d_geo(who, &sh, 1, compute, g);
+    if (rc) return rc;
+    if (!a_m || !mu_w || !s2_w || !out_m || !out_v || (mu_b == nullptr) != (s2_b == nullptr)) {
+        set_error("%s: NULL pointer (mu_b and s2_b: both or neither)", who);
+        return BNN_E_NULL;
+    }
+    if (flags & ~(BNN_FLAG_RELU | BNN_FLAG_ELU)) { set_error("%s: unknown flag", who); return BNN_E_UNSUPPORTED; }
+    if ((flags & BNN_FLAG_RELU) && (flags & BNN_FLAG_ELU)) {
+        set_error("%s: BNN_FLAG_RELU and BNN_FLAG_ELU together", who);
+        return BNN_E_UNSUPPORTED;
+    }
+    if ((flags & BNN_FLAG_ELU) && (!(elu_alpha >= 0.0f) || elu_alpha > 3.0e38f)) {
+        set_error("%s: elu_alpha must be finite and >= 0", who);
+        return BNN_E_RANGE;
+    }
+    if (mis4(a_m) || mis4(a_v) || mis4(mu_w) || mis4(s2_w) || mis4(mu_b) || mis4(s2_b) || mis16(out_m) || mis16(out_v)) {
+        set_error("%s: misaligned pointer (out_m and out_v: 16 bytes)", who);
+        return BNN_E_ALIGN;
+    }
+    if ((g.Ng + C3_BN - 1) / C3_BN > 65535) { set_error("%s: more than 64 * 65535 output channels per group", who); return BNN_E_RANGE; }
+    if (empty) return BNN_OK;
+    MomConvArgs a{};
+    a.a_m = a_m; a.a_v = a_v; a.w1 = mu_w; a.w2 = s2_w; a.b1 = mu_b; a.b2 = s2_b; a.out_m = out_m; a.out_v = out_v;
+    a.act = flags & (BNN_FLAG_RELU | BNN_FLAG_ELU);
+    a.elu_alpha = elu_alpha;
+    const dim3 grid((unsigned)(((int64_t)g.B * g.P + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN), (unsigned)g.groups);
+    const dim3 block(C3_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (compute == BNN_COMPUTE_BF16) {
+        if (a_v) hipLaunchKernelGGL((k_moments_conv3d<uint16_t, true>), grid, block, 0, st, g, a);
+        else hipLaunchKernelGGL((k_moments_conv3d<uint16_t, false>), grid, block, 0, st, g, a);
+    } else {
+        if (a_v) hipLaunchKernelGGL((k_moments_conv3d<float, true>), grid, block, 0, st, g, a);
+        else hipLaunchKernelGGL((k_moments_conv3d<float, false>), grid, block, 0, st, g, a);
+    }
     return check_launch(who);
 }
 

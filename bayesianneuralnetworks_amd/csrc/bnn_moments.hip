@@ -9,33 +9,13 @@
 // The contraction tile of bnn_lrt_tile.hpp with BK = 32 and, for an input that carries a variance, three planes per operand:
 //     P planes (MFMA A)   mu_w,  sigma_w^2,  [mu_w^2 + sigma_w^2]      Q planes (MFMA B)   a_m,  a_m^2,  [a_v]
 // The two variance contractions add into ONE accumulator set, so a lane holds K10's 32 accumulator registers.
-// Epilogue: + mu_b / + sigma_b^2, then (BNN_FLAG_RELU) the moment-matched ReLU moments_relu_dev -- the function the standalone
-// launch calls, so fused and standalone agree bit for bit.  Outputs fp32 (B, N).
+// Epilogue: + mu_b / + sigma_b^2, then (BNN_FLAG_RELU) the moment-matched ReLU moments_relu_dev (bnn_moments_act.hpp) -- the
+// function the standalone launch calls, so fused and standalone agree bit for bit.  Outputs fp32 (B, N).
+// The elementwise launches k_moments_relu / k_moments_elu (K17: the conv tile's epilogue functions, bnn_conv3d.hip) live here too.
 #include "bnn_lrt_tile.hpp"
+#include "bnn_moments_act.hpp"
 
 namespace bnn {
-
-// ReLU of a Gaussian pre-activation N(m, v) by moment matching, s = sqrt(v), alpha = m / s, Phi / phi the standard normal cdf / pdf:
-//     mean' = s (alpha Phi + phi)
-//     var'  = v (Phi + alpha^2 Phi Phi_c + alpha phi (Phi_c - Phi) - phi^2),   Phi_c = Phi(-alpha),   clamped at 0
-// (E[y^2] - mean'^2 with m^2 never subtracted from m^2 + v).  Beyond |alpha| = 40 Phi_c and phi are zero in fp32 and the form is
-// its own limit: the input passes (alpha > 0) or (0, 0) comes out; v == 0 (alpha infinite or 0 / 0) takes that branch too.
-__device__ __forceinline__ void moments_relu_dev(float m, float v, float &om, float &ov)
-{
-    const float s = sqrtf(v);
-    const float alpha = m / s;
-    if (!(fabsf(alpha) < 40.0f)) {
-        om = fmaxf(m, 0.0f);
-        ov = m > 0.0f ? v : 0.0f;
-        return;
-    }
-    const float cdf = 0.5f * erfcf(-0.70710678118654752f * alpha);
-    const float cdc = 0.5f * erfcf(0.70710678118654752f * alpha);
-    const float pdf = 0.39894228040143268f * expf(-0.5f * alpha * alpha);
-    om = s * (alpha * cdf + pdf);
-    const float r = cdf + alpha * alpha * cdf * cdc + alpha * pdf * (cdc - cdf) - pdf * pdf;
-    ov = fmaxf(v * r, 0.0f);
-}
 
 struct MomArgs {
     const void *a_m;            // (B, K) fp32 or (deterministic input, bf16 compute) bf16, row pitch lda
@@ -106,6 +86,17 @@ __global__ __launch_bounds__(256) void k_moments_relu(const float *m, const floa
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
         float a, b;
         moments_relu_dev(m[t], v[t], a, b);
+        om[t] = a;
+        ov[t] = b;
+    }
+}
+
+// the moment-matched ELU (moments_elu_dev, bnn_moments_act.hpp) as an elementwise launch; in place allowed, as above
+__global__ __launch_bounds__(256) void k_moments_elu(const float *m, const float *v, float *om, float *ov, int64_t n, float alpha)
+{
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
+        float a, b;
+        moments_elu_dev(m[t], v[t], alpha, a, b);
         om[t] = a;
         ov[t] = b;
     }
@@ -203,6 +194,23 @@ int bnn_moments_relu(const float *m, const float *v, float *out_m, float *out_v,
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_moments_relu, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m, v, out_m, out_v, n);
+    return check_launch(who);
+}
+
+int bnn_moments_elu(const float *m, const float *v, float *out_m, float *out_v, int64_t n, float alpha, void *stream)
+{
+    const char *who = "bnn_moments_elu";
+    if (!m || !v || !out_m || !out_v) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if (n < 0) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
+    if (!(alpha >= 0.0f) || alpha > 3.0e38f) { set_error("%s: alpha must be finite and >= 0", who); return BNN_E_RANGE; }
+    if (misaligned(m, 3) || misaligned(v, 3) || misaligned(out_m, 3) || misaligned(out_v, 3)) {
+        set_error("%s: misaligned pointer", who);
+        return BNN_E_ALIGN;
+    }
+    if (n == 0) return BNN_OK;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_moments_elu, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m, v, out_m, out_v, n, alpha);
     return check_launch(who);
 }
 

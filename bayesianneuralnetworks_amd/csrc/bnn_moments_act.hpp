@@ -1,0 +1,75 @@
+// bnn_moments_act.hpp -- moment-matched activations of a Gaussian pre-activation N(m, v): the device functions that the fused
+// epilogues (k_moments, bnn_moments.hip; k_moments_conv3d, bnn_conv3d.hip) and the standalone elementwise launches
+// (k_moments_relu, k_moments_elu) both call, so that fused and standalone agree bit for bit.
+#pragma once
+#include "bnn_device.hpp"
+
+namespace bnn {
+
+// ReLU of a Gaussian pre-activation N(m, v) by moment matching, s = sqrt(v), alpha = m / s, Phi / phi the standard normal cdf / pdf:
+//     mean' = s (alpha Phi + phi)
+//     var'  = v (Phi + alpha^2 Phi Phi_c + alpha phi (Phi_c - Phi) - phi^2),   Phi_c = Phi(-alpha),   clamped at 0
+// (E[y^2] - mean'^2 with m^2 never subtracted from m^2 + v).  Beyond |alpha| = 40 Phi_c and phi are zero in fp32 and the form is
+// its own limit: the input passes (alpha > 0) or (0, 0) comes out; v == 0 (alpha infinite or 0 / 0) takes that branch too.
+__device__ __forceinline__ void moments_relu_dev(float m, float v, float &om, float &ov)
+{
+    const float s = sqrtf(v);
+    const float alpha = m / s;
+    if (!(fabsf(alpha) < 40.0f)) {
+        om = fmaxf(m, 0.0f);
+        ov = m > 0.0f ? v : 0.0f;
+        return;
+    }
+    const float cdf = 0.5f * erfcf(-0.70710678118654752f * alpha);
+    const float cdc = 0.5f * erfcf(0.70710678118654752f * alpha);
+    const float pdf = 0.39894228040143268f * expf(-0.5f * alpha * alpha);
+    om = s * (alpha * cdf + pdf);
+    const float r = cdf + alpha * alpha * cdf * cdc + alpha * pdf * (cdc - cdf) - pdf * pdf;
+    ov = fmaxf(v * r, 0.0f);
+}
+
+// ELU (x > 0: x; else a (exp(x) - 1)) of a Gaussian pre-activation N(m, v) by moment matching.  The positive part is the ReLU's;
+// the negative part g = (exp(x) - 1) [x <= 0] has N1 = E[g] = E_1 - Phi_c and N2 = E[g^2] = E_2 - 2 E_1 + Phi_c with
+// E_k = E[exp(k x); x <= 0] = exp(k m + k^2 v / 2) Phi(-alpha - k s):
+//     mean' = P1 + a N1,                                  P1 = s (alpha Phi + phi)
+//     var'  = v r(alpha) + a^2 (N2 - N1^2) - 2 a P1 N1,   r the ReLU's bracket above,   clamped at 0
+// -- the variance as the sum of the two parts' own variances and their (non-negative) cross term, so m^2 is never subtracted from
+// m^2 + v.  What is left cancels in N2 and in N2 - N1^2, absolutely to a few ulp of a^2: in fp32 that is 1e-7 a^2 / v in units of
+// v and useless for small v, so the function works in fp64 (the inputs and the two results are fp32) and the cancellation costs
+// 1e-16 a^2 / v -- below fp32's own rounding of the result for every v >= 1e-9 a^2.
+// Every Gaussian tail comes from ONE function, X_k = erfcx(|t_k| / sqrt 2) at t_k = alpha + k s, k = 0, 1, 2 (a rolled loop: one
+// copy of its code), and g = exp(-alpha^2 / 2):  Phi(-t_k) exp(k m + k^2 v / 2) = g X_k / 2 for t_k >= 0, which neither overflows
+// nor underflows before the answer does, and exp(k m + k^2 v / 2) - g X_k / 2 for t_k < 0, where the exponent
+// k s (alpha + k s / 2) is below -k^2 v / 2 <= 0 and the difference loses at most one bit.
+// v == 0 (and a NaN v) gives (elu(m), 0); large alpha passes the input; large negative alpha tends to
+// (a (exp(m + v / 2) - 1), a^2 exp(2 m + v) (exp(v) - 1)), finite and non-negative.
+__device__ __forceinline__ void moments_elu_dev(float mf, float vf, float a_elu, float &om, float &ov)
+{
+    const double m = (double)mf, v = (double)vf, a = (double)a_elu;
+    if (!(vf > 0.0f)) {
+        om = mf > 0.0f ? mf : (float)(a * expm1(m));
+        ov = 0.0f;
+        return;
+    }
+    const double s = sqrt(v), alpha = m / s;
+    double x0 = 0.0, x1 = 0.0, x2 = 0.0;            // X_0, X_1, X_2 after the loop
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k) {
+        x0 = x1;
+        x1 = x2;
+        x2 = erfcx(0.70710678118654752 * fabs(alpha + (double)k * s));
+    }
+    const double g = exp(-0.5 * alpha * alpha);
+    const double h0 = 0.5 * g * x0, h1 = 0.5 * g * x1, h2 = 0.5 * g * x2;
+    const double cdc = alpha >= 0.0 ? h0 : 1.0 - h0, cdf = alpha >= 0.0 ? 1.0 - h0 : h0;
+    const double pdf = 0.39894228040143268 * g;
+    const double e1 = alpha + s >= 0.0 ? h1 : exp(m + 0.5 * v) - h1;
+    const double e2 = alpha + 2.0 * s >= 0.0 ? h2 : exp(2.0 * (m + v)) - h2;
+    const double p1 = s * (alpha * cdf + pdf);
+    const double r = cdf + alpha * alpha * cdf * cdc + alpha * pdf * (cdc - cdf) - pdf * pdf;
+    const double n1 = e1 - cdc, n2 = e2 - 2.0 * e1 + cdc;
+    om = (float)(p1 + a * n1);
+    ov = (float)fmax(v * r + a * a * (n2 - n1 * n1) - 2.0 * a * p1 * n1, 0.0);
+}
+
+}  // namespace bnn

@@ -1,4 +1,5 @@
 from .container import BayesianModule, BayesianNetworkModule
+from .container import MomentReLU, MomentELU, MomentLinear, MomentSoftmax   # (not in __all__: that list is the reference's)
 from .core import WeightNormal, WeightMultivariateNormal
 from .dense import (BayesianLinear, NormalLinear, MultivariateNormalLinear, FlipoutNormalLinear,
                     NormalInverseGaussianLinear, MCDropoutLinear,
@@ -9,7 +10,7 @@ from .conv import (BayesianConvNd, NormalConvNd, NormalConv1d, NormalConv2d, Nor
                    LocalReparamConvNd, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)   # (not in __all__ either)
 from .loss import KLDivergence, Entropy, NormalInverseGaussianLoss, NormalInverseGaussianUncertainty
 from .loss import GaussianNLL   # (not in __all__ either)
-from ._settings import set_compute, get_compute, fuse_activations, fuse_kl_gradient, keyed_mvn_draws
+from ._settings import set_compute, get_compute, fuse_activations, fuse_kl_gradient, keyed_mvn_draws, moment_activations
 
 # the names pytorch_bayesian/nn/__init__.py:7-35 exports
 __all__ = [

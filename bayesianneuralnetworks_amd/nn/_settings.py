@@ -98,3 +98,55 @@ def fuse_activations(module, bf16_activations=False, fuse_head=False):
                             # bf16 planes they read (ops.X3Activation): same values, no split pass
                             la.out_x3 = mods[j].weight.mean.shape[0] > 16 or mods[j].in_channels <= 2048
     return fused
+
+
+def moment_activations(module):
+    """Opt-in rewrite for sampling-free inference (BayesianNetworkModule.predictive_moments, propagation='moments'), in the style
+    of fuse_activations.  Inside every torch.nn.Sequential:
+
+    * `torch.nn.ReLU`, `torch.nn.ELU` and a `torch.nn.Softmax(dim=-1)` become `nn.MomentReLU`, `nn.MomentELU` and
+      `nn.MomentSoftmax`: subclasses that return the parent's bits on tensors, so every sampling path is unchanged, and that
+      take and return an ops.Moments in a moment pass (MomentSoftmax does not transform: it sets link='softmax', which the
+      predictive_* tails apply to the sampled logits -- it must end the network).
+    * a `torch.nn.Linear` that lies behind a Bayesian layer of the same Sequential (the CIFAR10 example has one) becomes an
+      `nn.MomentLinear` IN PLACE (the module is re-classed: its parameters and hooks are its own): a deterministic dense layer
+      that hands moments on, m = a_m w^T + b, v = a_v (w^2)^T.
+    * a twin directly behind a NormalConv1d / 2d / 3d or LocalReparamConv1d / 2d / 3d is made known to that layer
+      (`_moment_act`, a __dict__ entry, not a submodule): in a moment pass the activation runs in the conv launch's epilogue
+      (the standalone launch's bits) and the twin passes the result through.  Behind a dense layer the twins use the
+      standalone launches.
+
+    Idempotent; state_dict keys are unchanged (the activations have no state).  Returns the number of modules replaced."""
+    import torch
+    from .container import BayesianModule, MomentReLU, MomentELU, MomentLinear, MomentSoftmax
+    from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
+    convs = (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
+    replaced = 0
+    for m in module.modules():
+        if not isinstance(m, torch.nn.Sequential):
+            continue
+        behind = False                                        # a Bayesian layer of this Sequential lies in front
+        for name, child in list(m._modules.items()):
+            twin = None
+            if type(child) is torch.nn.Linear and behind:
+                child.__class__ = MomentLinear
+                replaced += 1
+            behind = behind or isinstance(child, BayesianModule)
+            if type(child) is torch.nn.ReLU:
+                twin = MomentReLU(inplace=child.inplace)
+            elif type(child) is torch.nn.ELU:
+                twin = MomentELU(alpha=child.alpha, inplace=child.inplace)
+            elif type(child) is torch.nn.Softmax and child.dim == -1:
+                twin = MomentSoftmax(dim=-1)
+            if twin is not None:
+                twin.train(child.training)
+                m._modules[name] = twin
+                replaced += 1
+        mods = list(m._modules.values())
+        for la, lb in zip(mods[:-1], mods[1:]):
+            if type(la) in convs:
+                if isinstance(lb, (MomentReLU, MomentELU)):
+                    la.__dict__["_moment_act"] = lb._moment_spec()
+                else:
+                    la.__dict__.pop("_moment_act", None)
+    return replaced

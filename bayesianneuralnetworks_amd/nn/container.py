@@ -41,7 +41,83 @@ class _Single:
 
 
 _MOMENTS_SUPPORTED = ("moment propagation supports NormalLinear / LocalReparamLinear, ReLU folded into them by "
-                      "nn.fuse_activations, and torch.nn.Identity")
+                      "nn.fuse_activations, NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d, the activations "
+                      "nn.moment_activations rewrites (ReLU, ELU, a torch.nn.Linear behind a Bayesian layer, and a Softmax over the last "
+                      "axis that ends the network), "
+                      "reshaping modules such as torch.nn.Flatten, and torch.nn.Identity")
+
+
+def _moment_twin_forward(self, parent, x, apply):
+    """forward of nn.MomentReLU / MomentELU: a tensor takes the parent's forward (its bits, on every sampling path); an
+    ops.Moments is moment-matched by `apply` -- unless the conv launch that produced it already ran this activation in its
+    epilogue (nn.moment_activations told that layer; the Moments says which activation it carries)."""
+    from .. import ops
+    if not isinstance(x, ops.Moments):
+        return parent.forward(self, x)
+    ops._refuse_link(x, type(self).__name__)
+    if x._act is not None:
+        if x._act != self._moment_spec():
+            raise ops.BnnHipError("%s: the layer in front fused %r into its launch, this module is %r: call "
+                                  "nn.moment_activations again after changing a Sequential" % (type(self).__name__, x._act, self._moment_spec()))
+        return ops.Moments(x.mean, x.var)
+    return apply(x)
+
+
+class MomentReLU(torch.nn.ReLU):
+    """torch.nn.ReLU that also takes an ops.Moments inside a moment pass (ops.moments_relu / moments_relu_f64); on tensors it
+    is its parent.  Put in place by nn.moment_activations."""
+
+    def _moment_spec(self):
+        return 'relu'
+
+    def forward(self, x):
+        from .. import ops
+        return _moment_twin_forward(self, torch.nn.ReLU, x,
+                                    lambda mom: ops.moments_relu(mom) if mom.mean.is_cuda else ops.moments_relu_f64(mom))
+
+
+class MomentELU(torch.nn.ELU):
+    """torch.nn.ELU that also takes an ops.Moments inside a moment pass (ops.moments_elu / moments_elu_f64); on tensors it is
+    its parent.  Put in place by nn.moment_activations."""
+
+    def _moment_spec(self):
+        return ('elu', float(self.alpha))
+
+    def forward(self, x):
+        from .. import ops
+        return _moment_twin_forward(self, torch.nn.ELU, x,
+                                    lambda mom: ops.moments_elu(mom, self.alpha) if mom.mean.is_cuda else ops.moments_elu_f64(mom, self.alpha))
+
+
+class MomentLinear(torch.nn.Linear):
+    """torch.nn.Linear that also takes an ops.Moments inside a moment pass -- a deterministic dense layer BEHIND a Bayesian one,
+    as in the CIFAR10 example: m = a_m w^T + b, v = a_v (w^2)^T (ops.moments_affine: K16's launch with sigma^2 = 0; CPU:
+    ops.moments_affine_f64).  On tensors it is its parent.  nn.moment_activations re-classes a Linear in place: its parameters,
+    hooks and state_dict are the module's own."""
+
+    def forward(self, x):
+        from .. import ops
+        from . import _settings
+        if not isinstance(x, ops.Moments):
+            return torch.nn.Linear.forward(self, x)
+        if not x.mean.is_cuda:
+            return ops.moments_affine_f64(x, self.weight, self.bias)
+        return ops.moments_affine(x, self.weight, self.bias, compute=_settings.get_compute())
+
+
+class MomentSoftmax(torch.nn.Softmax):
+    """torch.nn.Softmax over the last axis that, inside a moment pass, does NOT transform: it hands on the logit moments with
+    link='softmax', which the predictive_* tails apply to the sampled logits.  It must end the network: every layer refuses
+    moments that carry a link.  On tensors it is its parent."""
+
+    def forward(self, x):
+        from .. import ops
+        if not isinstance(x, ops.Moments):
+            return torch.nn.Softmax.forward(self, x)
+        ops._refuse_link(x, "MomentSoftmax")
+        if self.dim not in (-1, x.dim() - 1):
+            raise ops.BnnHipError("MomentSoftmax: softmax over axis %r of %d; only the last axis is supported" % (self.dim, x.dim()))
+        return ops.Moments(x.mean, x.var, link='softmax')
 
 
 def _moments_asked(propagation, who, kl=None):
@@ -215,6 +291,9 @@ class BayesianNetworkModule(Module):
                                       "to run `advance` in")
             self._moment_refusals("predictive_regression", kl)
             mom = self.predictive_moments(x, **kwargs)
+            if mom.link is not None:
+                raise ops.BnnHipError("predictive_regression: outputs='values' with propagation='moments' reads the propagated "
+                                      "moments as they are; this network ends in a %s link" % mom.link)
             var = torch.zeros_like(mom.mean) if mom.var is None else mom.var
             return ops.PredictiveRegression(mom.mean, var, torch.zeros_like(mom.mean), var.clone())
         if not _on_device(x):
@@ -282,15 +361,23 @@ class BayesianNetworkModule(Module):
         cost does not depend on a sample count and no mc_batched is needed.  With ONE hidden ReLU layer every output's marginal
         mean and variance are exact; from the second hidden layer on the recursion treats a layer's inputs as independent
         Gaussians (the usual diagonal-covariance approximation), and the outputs' covariances are not carried at all.
-        Supported: NormalLinear and LocalReparamLinear, ReLU folded into them by nn.fuse_activations, torch.nn.Identity, and any
-        deterministic module in FRONT of the first Bayesian layer; anything else raises ops.BnnHipError.  A `_forward` that
+        NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d run as ops.moments_convNd (K17: per output element the marginal
+        moments are exact for a deterministic input; the correlation between the positions of an output map is dropped).
+        Supported: those layers, ReLU folded into the dense ones by nn.fuse_activations, what nn.moment_activations rewrites
+        (ReLU, ELU, a torch.nn.Linear behind a Bayesian layer, a Softmax over the last axis that ends the network: the result
+        then carries link='softmax' and holds the LOGIT moments), modules that only reshape (torch.nn.Flatten, x.view),
+        torch.nn.Identity, and any deterministic module in FRONT of the first Bayesian layer; anything else raises
+        ops.BnnHipError.  A `_forward` that
         returns a plain tensor gives it back with var None.  CPU tensors: the same recursion in float64 (ops.moments_f64),
         rounded to fp32 at the end.  Inference only: nothing is drawn, no draw epoch is consumed, no key is recorded, and the
         result is detached whatever the grad mode."""
         from .. import ops
         from .dense import NormalLinear, LocalReparamLinear
+        from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
+        admitted = (NormalLinear, LocalReparamLinear, NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d,
+                    LocalReparamConv2d, LocalReparamConv3d)
         for m in self.modules():
-            if isinstance(m, BayesianModule) and type(m) not in (NormalLinear, LocalReparamLinear):
+            if isinstance(m, BayesianModule) and type(m) not in admitted:
                 raise ops.BnnHipError("predictive_moments: %s is not supported; %s" % (type(m).__name__, _MOMENTS_SUPPORTED))
         with torch.no_grad(), _mc.MomentContext():
             try:
@@ -303,7 +390,7 @@ class BayesianNetworkModule(Module):
         if not isinstance(y, ops.Moments):
             raise ops.BnnHipError("predictive_moments: _forward returned %s; %s" % (type(y).__name__, _MOMENTS_SUPPORTED))
         if not y.mean.is_cuda:
-            return ops.Moments(y.mean.to(torch.float32), None if y.var is None else y.var.to(torch.float32))
+            return ops.Moments(y.mean.to(torch.float32), None if y.var is None else y.var.to(torch.float32), y.link)
         return y
 
     def _moment_refusals(self, who, kl):
@@ -324,14 +411,15 @@ class BayesianNetworkModule(Module):
         from . import _settings
         self._moment_refusals(who, kl)
         mom = self.predictive_moments(x, *args, **kwargs)
+        link = (lambda ys: torch.softmax(ys, -1)) if mom.link == 'softmax' else (lambda ys: ys)
         if not mom.mean.is_cuda:
-            return ops.moments_sample(mom, None, samples)
+            return link(ops.moments_sample(mom, None, samples))
         if self.__dict__.get("_moment_stream") is None:
             self.__dict__["_moment_stream"] = new_stream_id()
         key = DrawKey(default_generator.seed, self.__dict__["_moment_stream"], sample0, samples, default_generator.next_epoch(),
                       gen=generator_for(_settings.get_compute()))
         self.__dict__["moment_key"] = key
-        return ops.moments_sample(mom, key, samples)
+        return link(ops.moments_sample(mom, key, samples))
 
     def _tail_inputs(self, who, x, samples, sample0, moments, kl, kwargs):
         """The (S, *rows, C) outputs a predictive_* tail reads.  `moments`: drawn from the propagated moments (_moment_outputs).

@@ -13,7 +13,7 @@ and ONE paired-contraction launch for all S samples (bnn_conv3d_lrt_forward; 1-d
 import torch
 from torch.distributions import Normal
 
-from .. import ops
+from .. import _mc, ops
 from . import _settings
 from ..utils import _single, _pair, _triple
 from .container import BayesianModule
@@ -53,8 +53,39 @@ class BayesianConvNd(BayesianModule):
         pass
 
 
+def _conv_forward_moments(layer, x):
+    """A Gaussian conv layer inside a moment pass (_mc.MomentContext; BayesianNetworkModule.predictive_moments): x a tensor (a
+    deterministic input) or an ops.Moments, (B, C, *spatial) or one image (C, *spatial) -> the ops.Moments of the output, with
+    the moment-matched activation in the launch's epilogue when nn.moment_activations found one directly behind the layer
+    (layer._moment_act; the twin module then passes the result through).  Device: ops.moments_convNd
+    (bnn_conv3d_moments_forward, fp32 moments in both compute modes); CPU: the same recursion in float64
+    (ops.moments_convNd_f64).  Nothing is drawn, no draw epoch is consumed, draw_key / noise_key stay as they are; the result
+    is detached (inference only)."""
+    mom = x if isinstance(x, ops.Moments) else ops.Moments(x, None)
+    if not torch.is_tensor(mom.mean):
+        raise TypeError("%s takes a tensor or ops.Moments in a moment pass, got %s" % (type(layer).__name__, type(x).__name__))
+    ops._refuse_link(mom, type(layer).__name__)
+    nd = layer.weight.mean.dim() - 2
+    if mom.mean.dim() == nd + 1:
+        out = _conv_forward_moments(layer, ops.Moments(mom.mean.unsqueeze(0), None if mom.var is None else mom.var.unsqueeze(0)))
+        res = ops.Moments(out.mean.squeeze(0), out.var.squeeze(0))
+        res._act = out._act
+        return res
+    act = layer.__dict__.get("_moment_act")
+    b = layer.bias is not None
+    args = (layer.weight.mean, layer.weight.scale, layer.bias.mean if b else None, layer.bias.scale if b else None,
+            layer.stride, layer.padding, layer.dilation, layer.groups)
+    if not mom.mean.is_cuda:
+        out = ops.moments_convNd_f64(mom, *args, activation=act)
+    else:
+        out = ops.moments_convNd(mom, *args, activation=act, compute=layer._compute_mode())
+    out._act = act
+    return out
+
+
 class NormalConvNd(_NormalSampling, BayesianConvNd):
-    """conv.py:43-73."""
+    """conv.py:43-73.  Inside BayesianNetworkModule.predictive_moments NormalConv1d / 2d / 3d draw nothing: they take and
+    return a mean and a variance per element (_conv_forward_moments, K17)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation,
                  transposed, groups, bias, prior):
@@ -64,6 +95,9 @@ class NormalConvNd(_NormalSampling, BayesianConvNd):
     def reset_parameters(self):
         _init_normal_posterior(self)
         self.sample()
+
+    def _forward_moments(self, x):
+        return _conv_forward_moments(self, x)
 
     def _torch_conv(self, op, x, sample):
         if sample:
@@ -80,6 +114,8 @@ class NormalConv1d(NormalConvNd):
                          _single(padding), _single(dilation), False, groups, bias, prior)
 
     def forward(self, x, sample=True):
+        if _mc.moments_current() is not None:
+            return self._forward_moments(x)                              # predictive_moments: moments in, moments out, no draw
         if not x.is_cuda or x.dim() not in (2, 3):
             return self._torch_conv(torch.nn.functional.conv1d, x, sample)
         # device: a 1-d convolution is the 2-d one on images of height 1 -- the same HIP kernels (implicit GEMM where the shape
@@ -119,6 +155,8 @@ class NormalConv2d(NormalConvNd):
                          _pair(padding), _pair(dilation), False, groups, bias, prior)
 
     def forward(self, x, sample=True):
+        if _mc.moments_current() is not None:
+            return self._forward_moments(x)                              # predictive_moments: moments in, moments out, no draw
         if not x.is_cuda:
             # CPU-resident module: the reference's own op sequence (conv.py:112-119)
             return self._torch_conv(torch.nn.functional.conv2d, x, sample)
@@ -136,6 +174,8 @@ class NormalConv3d(NormalConvNd):
                          _triple(padding), _triple(dilation), False, groups, bias, prior)
 
     def forward(self, x, sample=True):
+        if _mc.moments_current() is not None:
+            return self._forward_moments(x)                              # predictive_moments: moments in, moments out, no draw
         if not x.is_cuda:
             # CPU-resident module: the reference's own op sequence (conv.py:138-142)
             return self._torch_conv(torch.nn.functional.conv3d, x, sample)
@@ -179,7 +219,9 @@ class LocalReparamConvNd(_NormalSampling, BayesianConvNd):
     BayesianNetworkModule's MC-batched pass a layer that sees the shared batch (B rows) contracts m and v ONCE and returns S B
     rows; one that sees S B rows contracts per sample.  layer.noise_key is the DrawKey of the last device call, on a stream of
     the layer's own: element (b O + o) P + p of sample s is that eps of the key's sample sample0 + s (include/bnn_hip.h, LRT-conv
-    noise contract).  sample=False reuses it.  CPU tensors: the expression above in torch with torch.randn_like."""
+    noise contract).  sample=False reuses it.  CPU tensors: the expression above in torch with torch.randn_like.
+
+    Inside BayesianNetworkModule.predictive_moments the layer is NormalConvNd's moment layer (same parameters, same bits)."""
 
     _op = None
     _nd = 0
@@ -196,7 +238,12 @@ class LocalReparamConvNd(_NormalSampling, BayesianConvNd):
         _init_normal_posterior(self)
         self.sample()
 
+    def _forward_moments(self, x):
+        return _conv_forward_moments(self, x)
+
     def forward(self, x, sample=True):
+        if _mc.moments_current() is not None:
+            return self._forward_moments(x)                              # predictive_moments: NormalConvNd's moment layer, no noise
         conv = type(self)._op
         geo = (self.stride, self.padding, self.dilation, self.groups)
         if not x.is_cuda:

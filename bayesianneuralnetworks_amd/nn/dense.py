@@ -115,6 +115,7 @@ class _NormalSampling:
         mom = x if isinstance(x, ops.Moments) else ops.Moments(x, None)
         if not torch.is_tensor(mom.mean):
             raise TypeError("%s takes a tensor or ops.Moments in a moment pass, got %s" % (type(self).__name__, type(x).__name__))
+        ops._refuse_link(mom, type(self).__name__)
         b = self.bias is not None
         args = (self.weight.mean, self.weight.scale, self.bias.mean if b else None, self.bias.scale if b else None)
         if not mom.mean.is_cuda:

@@ -937,16 +937,43 @@ def linear_lrt(x, mu_w, rho_w, mu_b, rho_b, key, shared_x, compute="f32", out_dt
 class Moments:
     """A mean and a variance per activation, independent across elements (the mean-field assumption): what a dense layer takes
     and hands on inside a BayesianNetworkModule.predictive_moments pass.  A plain holder, not a Tensor; var None = a
-    deterministic input (every variance zero), as the first Bayesian layer of a network sees."""
-    __slots__ = ("mean", "var")
+    deterministic input (every variance zero), as the first Bayesian layer of a network sees.  It reshapes like a tensor (shape,
+    size, dim, view, reshape, flatten -- each applied to mean and var alike), so torch.nn.Flatten and `x.view(x.size(0), -1)`
+    work on it unchanged.  link: None, or 'softmax' when the moments are those of logits whose softmax ends the network
+    (nn.MomentSoftmax): the predictive_* tails apply it to the sampled logits, and no layer takes such moments."""
+    __slots__ = ("mean", "var", "link", "_act")     # _act: the activation the producing conv launch fused (the twin behind it passes)
 
-    def __init__(self, mean, var=None):
+    def __init__(self, mean, var=None, link=None):
         if var is not None and var.shape != mean.shape:
             raise ValueError("Moments: mean %s and var %s differ in shape" % (tuple(mean.shape), tuple(var.shape)))
-        self.mean, self.var = mean, var
+        if link not in (None, 'softmax'):
+            raise ValueError("Moments: link must be None or 'softmax', got %r" % (link,))
+        self.mean, self.var, self.link, self._act = mean, var, link, None
 
     def __repr__(self):
-        return "Moments(mean=%r, var=%r)" % (self.mean, self.var)
+        return "Moments(mean=%r, var=%r%s)" % (self.mean, self.var, "" if self.link is None else ", link=%r" % self.link)
+
+    def _both(self, fn):
+        return Moments(fn(self.mean), None if self.var is None else fn(self.var), self.link)
+
+    @property
+    def shape(self):
+        return self.mean.shape
+
+    def size(self, dim=None):
+        return self.mean.size() if dim is None else self.mean.size(dim)
+
+    def dim(self):
+        return self.mean.dim()
+
+    def view(self, *shape):
+        return self._both(lambda t: t.view(*shape))
+
+    def reshape(self, *shape):
+        return self._both(lambda t: t.reshape(*shape))
+
+    def flatten(self, start_dim=0, end_dim=-1):
+        return self._both(lambda t: t.flatten(start_dim, end_dim))
 
 
 def _as_moments(a, who):
@@ -1084,6 +1111,186 @@ def moments_f64(a, layers):
     for mu_w, rho_w, mu_b, rho_b, relu in layers:
         mom = moments_linear_f64(mom, mu_w, rho_w, mu_b, rho_b, relu)
     return mom
+
+
+# --------------------------------------------------------------------------- K17: moment propagation through convolutions and ELU
+def _refuse_link(mom, who):
+    """Moments that carry a link are the network's output: a softmax must end the network."""
+    if mom.link is not None:
+        raise BnnHipError("%s: the input carries link=%r: nn.MomentSoftmax must end the network (nothing propagates moments "
+                          "through a softmax)" % (who, mom.link))
+
+
+def _moment_activation(activation, who):
+    """None | 'relu' | ('elu', alpha) -> (name or None, alpha)."""
+    if activation is None:
+        return None, 0.0
+    if activation == 'relu':
+        return 'relu', 0.0
+    if isinstance(activation, (tuple, list)) and len(activation) == 2 and activation[0] == 'elu':
+        alpha = float(activation[1])
+        if not (0.0 <= alpha < float("inf")):
+            raise BnnHipError("%s: ELU alpha must be finite and >= 0, got %r" % (who, alpha))
+        return 'elu', alpha
+    raise ValueError("%s: activation must be None, 'relu' or ('elu', alpha), got %r" % (who, activation))
+
+
+def moments_convNd(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, groups=1, activation=None, compute="f32"):
+    """Mean and variance of a convolution's pre-activation for independent Gaussian weights, from the mean and variance of its
+    input, elements independent (bnn_lrt_prepare + bnn_conv3d_moments_forward, csrc/bnn_conv3d.hip; the dimension is the
+    weight's, 1-d and 2-d as unit depth / height) -> Moments, fp32 (B, O, *out_spatial):
+
+        m = convNd(a_m, mu_w) + mu_b,    v = convNd(a_m^2, sigma_w^2) + convNd(a_v, mu_w^2 + sigma_w^2) + sigma_b^2
+
+    a: a device tensor (B, C, *spatial) (a deterministic input: the second term is absent) or a Moments.  activation: None,
+    'relu' or ('elu', alpha) -- moments_relu / moments_elu in the launch's epilogue (the same bits).  Inference only: nothing is
+    drawn, no key is touched, the result is detached.  Raises BnnHipError for a call the kernel refuses: no torch fallback."""
+    who = "moments_convNd"
+    mom = _as_moments(a, who)
+    _refuse_link(mom, who)
+    act, alpha = _moment_activation(activation, who)
+    code = _compute_code(compute)
+    am = mom.mean.detach().contiguous()
+    av = None if mom.var is None else mom.var.detach().contiguous()
+    mu_w, rho_w = mu_w.detach().contiguous(), rho_w.detach().contiguous()
+    if mu_b is not None:
+        mu_b, rho_b = mu_b.detach().contiguous(), rho_b.detach().contiguous()
+    _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b)
+    require_cuda_f32(am, "a.mean")
+    if av is not None:
+        require_cuda_f32(av, "a.var")
+    nd = mu_w.dim() - 2
+    if nd not in (1, 2, 3) or am.dim() != nd + 2:
+        raise BnnHipError("%s: input must be (B, C, ...) with %d spatial axes for a weight of shape %s, got %s"
+                          % (who, nd, tuple(mu_w.shape), tuple(am.shape)))
+    img, w5, st, pd, dl = _lrt_conv_views(am.shape, mu_w.shape, stride, padding, dilation)
+    B = int(am.shape[0])
+    sh, out3 = _conv3d_shape((B,) + img, w5, st, pd, dl, groups)
+    out_sp = out3[3 - nd:]
+    dev = am.device
+    s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
+    out_m = torch.empty((B, sh.O) + out_sp, dtype=torch.float32, device=dev)
+    out_v = torch.empty_like(out_m)
+    flags = {None: 0, 'relu': _lib.FLAG_RELU, 'elu': _lib.FLAG_ELU}[act]
+    check(_lib.load().bnn_conv3d_moments_forward(ptr(am), ptr(av), ptr(mu_w), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(out_m),
+                                                 ptr(out_v), ctypes.byref(sh), code, flags, alpha, stream_ptr(dev)),
+          "bnn_conv3d_moments_forward")
+    return Moments(out_m, out_v)
+
+
+def moments_affine(a, w, b, compute="f32"):
+    """A DETERMINISTIC dense layer (torch.nn.Linear behind a Bayesian layer, as in the CIFAR10 example) in a moment pass:
+    m = a_m w^T + b, v = a_v (w^2)^T -- exact for independent inputs.  It is bnn_moments_forward with sigma_w^2 = 0 (the planes
+    w, 0, fma(w, w, 0)), so K16's tile, bounds and both compute modes apply; no operand launch.  a: a tensor or a Moments
+    (*rows, K); w (N, K); b (N) or None -> Moments, fp32 (*rows, N); a deterministic input stays one (var None).  Detached."""
+    who = "moments_affine"
+    mom = _as_moments(a, who)
+    _refuse_link(mom, who)
+    w = w.detach().contiguous()
+    b = None if b is None else b.detach().contiguous()
+    if mom.var is None:
+        return Moments(torch.nn.functional.linear(mom.mean.detach(), w, b), None)
+    code = _compute_code(compute)
+    N, K = w.shape
+    am, av = mom.mean.detach(), mom.var.detach()
+    if am.dim() < 1 or am.shape[-1] != K:
+        raise BnnHipError("%s: input has %s features, weight expects %d" % (who, am.shape[-1] if am.dim() else "no", K))
+    lead = tuple(am.shape[:-1])
+    am, av = am.reshape(-1, K).contiguous(), av.reshape(-1, K).contiguous()
+    for t, n in ((am, "a.mean"), (av, "a.var"), (w, "weight")) + (((b, "bias"),) if b is not None else ()):
+        require_cuda_f32(t, n)
+    B = am.shape[0]
+    if B > 64 * 65535:
+        raise BnnHipError("%s: %d rows (at most %d)" % (who, B, 64 * 65535))
+    dev = am.device
+    z_w = torch.zeros_like(w)
+    z_b = None if b is None else torch.zeros_like(b)
+    out_m = torch.empty((B, N), dtype=torch.float32, device=dev)
+    out_v = torch.empty((B, N), dtype=torch.float32, device=dev)
+    check(_lib.load().bnn_moments_forward(ptr(am), ptr(av), K, ptr(w), ptr(z_w), ptr(b), ptr(z_b), ptr(out_m), ptr(out_v),
+                                          B, N, K, code, 0, stream_ptr(dev)), "bnn_moments_forward")
+    return Moments(out_m.reshape(lead + (N,)), out_v.reshape(lead + (N,)))
+
+
+def moments_affine_f64(a, w, b):
+    """moments_affine in float64 torch."""
+    mom = _as_moments(a, "moments_affine_f64")
+    _refuse_link(mom, "moments_affine_f64")
+    f64 = lambda t: t.detach().to(torch.float64)         # noqa: E731
+    m = torch.nn.functional.linear(f64(mom.mean), f64(w), None if b is None else f64(b))
+    return Moments(m, None if mom.var is None else f64(mom.var) @ (f64(w) * f64(w)).t())
+
+
+def moments_elu(mom, alpha=1.0):
+    """ELU of Gaussian activations by moment matching (bnn_moments_elu; the formulas are include/bnn_hip.h's, evaluated in fp64
+    on the device and rounded to fp32) -> Moments.  v == 0 gives (elu(m), 0).  A deterministic input (var None) stays one."""
+    mom = _as_moments(mom, "moments_elu")
+    _refuse_link(mom, "moments_elu")
+    _, alpha = _moment_activation(('elu', alpha), "moments_elu")
+    if mom.var is None:
+        return Moments(torch.nn.functional.elu(mom.mean.detach(), alpha), None)
+    m, v = mom.mean.detach().contiguous(), mom.var.detach().contiguous()
+    require_cuda_f32(m, "mean")
+    require_cuda_f32(v, "var")
+    om, ov = torch.empty_like(m), torch.empty_like(v)
+    check(_lib.load().bnn_moments_elu(ptr(m), ptr(v), ptr(om), ptr(ov), m.numel(), alpha, stream_ptr(m.device)), "bnn_moments_elu")
+    return Moments(om, ov)
+
+
+def moments_elu_f64(mom, alpha=1.0):
+    """moments_elu in float64 torch: the closed form of include/bnn_hip.h (the variance as the ReLU part's, the negative part's
+    and their cross term; E_k through erfcx where alpha + k s >= 0, so that nothing overflows)."""
+    mom = _as_moments(mom, "moments_elu_f64")
+    a = float(alpha)
+    m = mom.mean.detach().to(torch.float64)
+    if mom.var is None:
+        return Moments(torch.nn.functional.elu(m, a), None)
+    v = mom.var.detach().to(torch.float64)
+    pos = v > 0
+    vs = torch.where(pos, v, torch.ones_like(v))
+    s = torch.sqrt(vs)
+    al = m / s
+    r2 = math.sqrt(2.0)
+    cdf, cdc = 0.5 * torch.special.erfc(-al / r2), 0.5 * torch.special.erfc(al / r2)
+    pdf = torch.exp(-0.5 * al * al) / math.sqrt(2.0 * math.pi)
+
+    def e_k(k):
+        t = al + k * s
+        up = 0.5 * torch.exp(-0.5 * al * al) * torch.special.erfcx(t.clamp_min(0) / r2)
+        lo = torch.exp((k * m + 0.5 * k * k * vs).clamp_max(0)) * 0.5 * torch.special.erfc(t.clamp_max(0) / r2)
+        return torch.where(t >= 0, up, lo)
+
+    e1, e2 = e_k(1.0), e_k(2.0)
+    p1 = s * (al * cdf + pdf)
+    n1, n2 = e1 - cdc, e2 - 2.0 * e1 + cdc
+    mean = p1 + a * n1
+    var = (vs * (cdf + al * al * cdf * cdc + al * pdf * (cdc - cdf) - pdf * pdf) + a * a * (n2 - n1 * n1) - 2.0 * a * p1 * n1).clamp_min(0)
+    return Moments(torch.where(pos, mean, torch.nn.functional.elu(m, a)), torch.where(pos, var, torch.zeros_like(v)))
+
+
+def moments_convNd_f64(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, groups=1, activation=None):
+    """moments_convNd in float64 torch (two / three torch.nn.functional.convNd calls on the CPU; sigma = 1e-10 + softplus(rho))
+    -> Moments of float64 tensors."""
+    who = "moments_convNd_f64"
+    mom = _as_moments(a, who)
+    _refuse_link(mom, who)
+    act, alpha = _moment_activation(activation, who)
+    f64 = lambda t: t.detach().to(torch.float64)         # noqa: E731
+    sig2 = lambda rho: (1e-10 + torch.nn.functional.softplus(f64(rho))) ** 2         # noqa: E731
+    nd = mu_w.dim() - 2
+    if nd not in (1, 2, 3):
+        raise BnnHipError("%s: weight must be (O, C / groups, *kernel) with 1, 2 or 3 kernel axes, got %s" % (who, tuple(mu_w.shape)))
+    conv = (torch.nn.functional.conv1d, torch.nn.functional.conv2d, torch.nn.functional.conv3d)[nd - 1]
+    geo = (tuple(stride), tuple(padding), tuple(dilation), int(groups))
+    am, mu, s2 = f64(mom.mean), f64(mu_w), sig2(rho_w)
+    m = conv(am, mu, None if mu_b is None else f64(mu_b), *geo)
+    v = conv(am * am, s2, None if mu_b is None else sig2(rho_b), *geo)
+    if mom.var is not None:
+        v = v + conv(f64(mom.var), mu * mu + s2, None, *geo)
+    out = Moments(m, v)
+    if act == 'relu':
+        return moments_relu_f64(out)
+    return moments_elu_f64(out, alpha) if act == 'elu' else out
 
 
 class _PlainLinear(torch.autograd.Function):

@@ -257,7 +257,9 @@ enum {
      * rho_w, or w) must be 16-B aligned: BNN_E_UNSUPPORTED otherwise.  Without them every operand may lie on its element
      * (BNN_E_ALIGN below that); 16-B aligned x, weights and K % 4 == 0 buy the sampler-paced kernel. */
     BNN_FLAG_X_BF16 = 2,
-    BNN_FLAG_Y_BF16 = 4
+    BNN_FLAG_Y_BF16 = 4,
+    /* bnn_conv3d_moments_forward only: the moment-matched ELU (bnn_moments_elu's function, its alpha an argument) in the epilogue */
+    BNN_FLAG_ELU = 8
 };
 int bnn_linear_forward_sampled(const void *x, int64_t x_sample_stride, int64_t ldx,
                                const float *mu_w, const float *rho_w,
@@ -1138,6 +1140,39 @@ int bnn_moments_relu(const float *m, const float *v, float *out_m, float *out_v,
  * BNN_E_UNSUPPORTED (flags), BNN_E_ALIGN. */
 int bnn_moments_sample(const float *m, const float *v, float *y, int64_t rows, int64_t N, int nsamples, const bnn_rng_t *rng,
                        int flags, void *stream);
+
+/* ---- K17: moment propagation through convolutions and ELU (csrc/bnn_conv3d.hip, csrc/bnn_moments_act.hpp; ops.moments_convNd,
+ * ops.moments_elu).  K16's recursion for NormalConv / LocalReparamConv 1d / 2d / 3d, elements independent:
+ *     m = convNd(a_m, mu_w) + mu_b
+ *     v = convNd(a_m^2, sigma_w^2) + convNd(a_v, mu_w^2 + sigma_w^2) + sigma_b^2      (second term absent when a_v is NULL)
+ * One implicit-GEMM tile on K7 / K11's forward skeleton (128 x 64 x 32, im2col in the loader's address arithmetic, padding reads
+ * zero, groups in the grid; 1-d and 2-d layers: unit depth / height) with K16's planes: a_m^2 and fma(mu_w, mu_w, sigma_w^2) are
+ * formed in fp32 as they are staged, both variance contractions add into one accumulator set, every addend of v is >= 0.
+ * compute: BNN_COMPUTE_F32 = v_mfma_f32_16x16x4_f32; BNN_COMPUTE_BF16 = every plane rounded to bf16 (RNE) into LDS,
+ * v_mfma_f32_16x16x32_bf16, fp32 accumulate.  No sample axis, no rng, no atomics, no split reduction: identical calls give
+ * identical bits.  Graph-capturable; every error is returned before anything is launched.
+ *
+ * a_m: (B, C, D, H, W) fp32; a_v: the same shape or NULL (a deterministic input).  mu_w, s2_w: (O, C / groups, KD, KH, KW) fp32
+ * (s2 = bnn_lrt_prepare's sigma^2); mu_b, s2_b: (O) fp32, both or neither.  out_m, out_v: (B, O, OD, OH, OW) fp32, 16-byte aligned.
+ * flags: 0, BNN_FLAG_RELU (bnn_moments_relu's function in the epilogue) or BNN_FLAG_ELU (bnn_moments_elu's, with elu_alpha;
+ * elu_alpha is not read otherwise).  shape->B == 0 returns BNN_OK after the checks.
+ * Errors: BNN_E_NULL (a pointer, the shape, one bias tensor without the other), BNN_E_SHAPE (extents, groups not dividing the
+ * channels), BNN_E_DTYPE (compute), BNN_E_RANGE (K7's index ranges: a tensor of 2^31 elements or more, so B O P < 2^32;
+ * groups > 65535; elu_alpha negative or not finite), BNN_E_UNSUPPORTED (an unknown flag; RELU and ELU together), BNN_E_ALIGN
+ * (4 bytes; 16 bytes for out_m and out_v). */
+int bnn_conv3d_moments_forward(const float *a_m, const float *a_v, const float *mu_w, const float *s2_w, const float *mu_b,
+                               const float *s2_b, float *out_m, float *out_v, const bnn_conv3d_shape_t *shape, int compute,
+                               int flags, float elu_alpha, void *stream);
+/* ELU (x > 0: x; else alpha (exp(x) - 1)) of a Gaussian N(m, v) by moment matching.  With s = sqrt(v), al = m / s, Phi / phi the
+ * standard normal cdf / pdf, Phi_c = Phi(-al), E_k = exp(k m + k^2 v / 2) Phi(-al - k s), P1 = s (al Phi + phi),
+ * N1 = E_1 - Phi_c, N2 = E_2 - 2 E_1 + Phi_c:
+ *     mean' = P1 + alpha N1
+ *     var'  = v (Phi + al^2 Phi Phi_c + al phi (Phi_c - Phi) - phi^2) + alpha^2 (N2 - N1^2) - 2 alpha P1 N1,   clamped at 0
+ * (the ReLU's variance, the negative part's, and their cross term: m^2 is never subtracted from m^2 + v), evaluated in fp64 on
+ * fp32 inputs and rounded to fp32 at the end.  v == 0 gives (elu(m), 0).  n elements, in place allowed.  The device function is
+ * bnn_conv3d_moments_forward's epilogue's: same bits.  Errors: BNN_E_NULL, BNN_E_SHAPE (n < 0), BNN_E_RANGE (alpha negative or
+ * not finite), BNN_E_ALIGN. */
+int bnn_moments_elu(const float *m, const float *v, float *out_m, float *out_v, int64_t n, float alpha, void *stream);
 
 #ifdef __cplusplus
 }
