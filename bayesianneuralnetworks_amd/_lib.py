@@ -231,6 +231,9 @@ SIGNATURES = {
     "bnn_moments_sample": (_int, [_p, _p, _p, _i64, _i64, _int, _rngp, _int, _p]),
     "bnn_conv3d_moments_forward": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, ctypes.c_float, _p]),
     "bnn_moments_elu": (_int, [_p, _p, _p, _p, _i64, ctypes.c_float, _p]),
+    "bnn_moments_backward_input": (_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
+    "bnn_moments_backward_weight": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
+    "bnn_moments_relu_backward": (_int, [_p, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
 _lib = None

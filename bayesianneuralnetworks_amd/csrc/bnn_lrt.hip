@@ -200,6 +200,13 @@ static int lrt_launch(const char *who, const LrtArgs &A, int compute, unsigned g
     return check_launch(who);
 }
 
+int lrt_bias_grad_launch(const char *who, const float *g_m, const float *g_v, int64_t M, int64_t N, const float *rho_b, float *g_mu_b,
+                         float *g_rho_b, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_lrt_bias_grad, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, st, g_m, g_v, M, (int)N, rho_b, g_mu_b, g_rho_b);
+    return check_launch(who);
+}
+
 }  // namespace bnn
 
 using namespace bnn;
@@ -345,9 +352,7 @@ int bnn_lrt_backward_weight(const void *x, int64_t ldx, const float *g_m, const 
     A.out = g_mu_w; A.out2 = g_rho_w; A.e1 = rho_w;
     int rc = lrt_launch<LRT_WGRAD>(who, A, compute, 1u, (hipStream_t)stream);
     if (rc || !bias) return rc;
-    hipLaunchKernelGGL(k_lrt_bias_grad, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, (hipStream_t)stream, g_m, g_v, M, (int)N,
-                       rho_b, g_mu_b, g_rho_b);
-    return check_launch(who);
+    return lrt_bias_grad_launch(who, g_m, g_v, M, N, rho_b, g_mu_b, g_rho_b, (hipStream_t)stream);
 }
 
 }  // extern "C"

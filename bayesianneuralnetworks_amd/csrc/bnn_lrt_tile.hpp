@@ -1,4 +1,5 @@
-// bnn_lrt_tile.hpp -- the 64 x 64 register-staged contraction tile of K10 (bnn_lrt.hip) and K16 (bnn_moments.hip).
+// bnn_lrt_tile.hpp -- the 64 x 64 register-staged contraction tile of K10 (bnn_lrt.hip), K16 (bnn_moments.hip) and K18
+// (bnn_moments_bwd.hip: three accumulator sets, lrt_mfma_block3).
 // One tile computes contractions that share an operand pass: acc1 += P0 Q0^T and acc2 += P1 Q1^T [+ P2 Q2^T], where a plane of an
 // operand is a tensor or is derived from the operand's other planes in fp32 as the loader writes LDS (lrt_stage).  P sits in the
 // MFMA's A position, so a lane's four accumulator registers are four CONSECUTIVE elements of the output's contiguous dimension i
@@ -157,6 +158,46 @@ __device__ __forceinline__ void lrt_mfma_block(f32x4 (&acc1)[2][2], f32x4 (&acc2
         }
     }
 }
+
+// Three accumulator sets (K18, bnn_moments_bwd.hip): three P planes against two Q planes, Q's second plane serving twice --
+//     acc1 += P0 Q0^T,   acc2 += P1 Q1^T,   acc3 += P2 Q1^T
+// per kk the plane-0 and plane-1 MFMAs of every (a, b), then the plane-2 ones, as lrt_mfma_block orders them.  48 accumulator
+// registers per lane; LDS holds 3 + 2 planes.
+template <typename T, int BK, int LDK>
+__device__ __forceinline__ void lrt_mfma_block3(f32x4 (&acc1)[2][2], f32x4 (&acc2)[2][2], f32x4 (&acc3)[2][2], const T *lp, const T *lq)
+{
+    constexpr int PL = kLrtTile * LDK;
+    constexpr int KS = sizeof(T) == 2 ? 32 : 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pr = ((wave >> 1) * 32 + (lane & 15)) * LDK, qr = ((wave & 1) * 32 + (lane & 15)) * LDK;
+#pragma unroll
+    for (int kk = 0; kk < BK / KS; ++kk) {
+        const int ko = kk * KS + (KS / 4) * (lane >> 4);
+        decltype(lrt_frag(lp)) fp[3][2], fq[2][2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) fp[pl][a] = lrt_frag(lp + pl * PL + pr + a * 16 * LDK + ko);
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) fq[pl][a] = lrt_frag(lq + pl * PL + qr + a * 16 * LDK + ko);
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                acc1[a][b] = lrt_mfma(fp[0][a], fq[0][b], acc1[a][b]);
+                acc2[a][b] = lrt_mfma(fp[1][a], fq[1][b], acc2[a][b]);
+            }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc3[a][b] = lrt_mfma(fp[2][a], fq[1][b], acc3[a][b]);
+    }
+}
+
+// bnn_lrt.hip: the bias gradients of K10 and K18, k_lrt_bias_grad on (M, N) g_m / g_v (no checks)
+int lrt_bias_grad_launch(const char *who, const float *g_m, const float *g_v, int64_t M, int64_t N, const float *rho_b, float *g_mu_b,
+                         float *g_rho_b, hipStream_t st);
 
 // Epilogue: MFMA tile (a, b) of a lane holds out[j][i .. i + 3], i = i0 + 32 wi + 16 a + 4 (lane >> 4), j = j0 + 32 wj + 16 b +
 // (lane & 15); ni of the four lie inside I.  false: none does.

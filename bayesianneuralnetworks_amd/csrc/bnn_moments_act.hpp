@@ -11,21 +11,52 @@ namespace bnn {
 //     var'  = v (Phi + alpha^2 Phi Phi_c + alpha phi (Phi_c - Phi) - phi^2),   Phi_c = Phi(-alpha),   clamped at 0
 // (E[y^2] - mean'^2 with m^2 never subtracted from m^2 + v).  Beyond |alpha| = 40 Phi_c and phi are zero in fp32 and the form is
 // its own limit: the input passes (alpha > 0) or (0, 0) comes out; v == 0 (alpha infinite or 0 / 0) takes that branch too.
+// The terms are one function (moments_relu_terms) that the forward and its backward (moments_relu_bwd_dev) both evaluate.
+struct ReluTerms { float s, alpha, cdf, cdc, pdf, mean, r; };      // mean = mean', r = the bracket of var' (var' = max(v r, 0))
+
+// false: the limit branch (|alpha| >= 40, v == 0, NaN), where only s and alpha are set
+__device__ __forceinline__ bool moments_relu_terms(float m, float v, ReluTerms &t)
+{
+    t.s = sqrtf(v);
+    t.alpha = m / t.s;
+    if (!(fabsf(t.alpha) < 40.0f)) return false;
+    t.cdf = 0.5f * erfcf(-0.70710678118654752f * t.alpha);
+    t.cdc = 0.5f * erfcf(0.70710678118654752f * t.alpha);
+    t.pdf = 0.39894228040143268f * expf(-0.5f * t.alpha * t.alpha);
+    t.mean = t.s * (t.alpha * t.cdf + t.pdf);
+    t.r = t.cdf + t.alpha * t.alpha * t.cdf * t.cdc + t.alpha * t.pdf * (t.cdc - t.cdf) - t.pdf * t.pdf;
+    return true;
+}
+
 __device__ __forceinline__ void moments_relu_dev(float m, float v, float &om, float &ov)
 {
-    const float s = sqrtf(v);
-    const float alpha = m / s;
-    if (!(fabsf(alpha) < 40.0f)) {
+    ReluTerms t;
+    if (!moments_relu_terms(m, v, t)) {
         om = fmaxf(m, 0.0f);
         ov = m > 0.0f ? v : 0.0f;
         return;
     }
-    const float cdf = 0.5f * erfcf(-0.70710678118654752f * alpha);
-    const float cdc = 0.5f * erfcf(0.70710678118654752f * alpha);
-    const float pdf = 0.39894228040143268f * expf(-0.5f * alpha * alpha);
-    om = s * (alpha * cdf + pdf);
-    const float r = cdf + alpha * alpha * cdf * cdc + alpha * pdf * (cdc - cdf) - pdf * pdf;
-    ov = fmaxf(v * r, 0.0f);
+    om = t.mean;
+    ov = fmaxf(v * t.r, 0.0f);
+}
+
+// Backward of moments_relu_dev (K18): (g_m, g_v) from the gradients (gm', gv') of its two outputs, on the forward's own terms:
+//     d mean'/d m = Phi                    d mean'/d v = phi / (2 s)
+//     d var'/d m  = 2 mean' Phi(-alpha)    d var'/d v  = Phi - mean' phi / s
+// Where the forward clamped var' (v r < 0, decided on the forward's r) the gv' terms are absent.  The limit branch passes both
+// gradients for m > 0 and nothing otherwise, which is also the convention at v == 0.
+__device__ __forceinline__ void moments_relu_bwd_dev(float m, float v, float gom, float gov, float &gm, float &gv)
+{
+    ReluTerms t;
+    if (!moments_relu_terms(m, v, t)) {
+        gm = m > 0.0f ? gom : 0.0f;
+        gv = m > 0.0f ? gov : 0.0f;
+        return;
+    }
+    const float ps = t.pdf / t.s;
+    if (v * t.r < 0.0f) gov = 0.0f;
+    gm = gom * t.cdf + gov * (2.0f * t.mean * t.cdc);
+    gv = gom * (0.5f * ps) + gov * (t.cdf - t.mean * ps);
 }
 
 // ELU (x > 0: x; else a (exp(x) - 1)) of a Gaussian pre-activation N(m, v) by moment matching.  The positive part is the ReLU's;

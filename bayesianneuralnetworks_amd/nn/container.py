@@ -72,8 +72,10 @@ class MomentReLU(torch.nn.ReLU):
 
     def forward(self, x):
         from .. import ops
-        return _moment_twin_forward(self, torch.nn.ReLU, x,
-                                    lambda mom: ops.moments_relu(mom) if mom.mean.is_cuda else ops.moments_relu_f64(mom))
+        ctx = _mc.moments_current()
+        track = ctx is not None and ctx.track                          # forward_moments: keep the graph
+        return _moment_twin_forward(self, torch.nn.ReLU, x, lambda mom: ops.moments_relu(mom, track) if mom.mean.is_cuda
+                                    else ops.moments_relu_f64(mom, track))
 
 
 class MomentELU(torch.nn.ELU):
@@ -406,20 +408,63 @@ class BayesianNetworkModule(Module):
         """propagation='moments': what a predictive_* tail reads -- the (S, *rows, C) outputs drawn from the propagated moments
         by ONE bnn_moments_sample launch, independent across outputs, on a model-level noise stream (its id is taken at first
         use, so that a model's layers keep theirs; the key is recorded as model.moment_key).  CPU: torch.randn."""
+        self._moment_refusals(who, kl)
+        mom = self.predictive_moments(x, *args, **kwargs)
+        return self._sample_link(mom, samples, sample0, False)
+
+    def _sample_link(self, mom, samples, sample0, track):
+        """`samples` draws from the output moments on the model's moment stream, through the link the moments carry."""
         from .. import ops
         from .._rng import DrawKey, default_generator, generator_for, new_stream_id
         from . import _settings
-        self._moment_refusals(who, kl)
-        mom = self.predictive_moments(x, *args, **kwargs)
         link = (lambda ys: torch.softmax(ys, -1)) if mom.link == 'softmax' else (lambda ys: ys)
         if not mom.mean.is_cuda:
-            return link(ops.moments_sample(mom, None, samples))
+            return link(ops.moments_sample(mom, None, samples, track))
         if self.__dict__.get("_moment_stream") is None:
             self.__dict__["_moment_stream"] = new_stream_id()
         key = DrawKey(default_generator.seed, self.__dict__["_moment_stream"], sample0, samples, default_generator.next_epoch(),
                       gen=generator_for(_settings.get_compute()))
         self.__dict__["moment_key"] = key
-        return link(ops.moments_sample(mom, key, samples))
+        return link(ops.moments_sample(mom, key, samples, track))
+
+    def forward_moments(self, x, *args, **kwargs):
+        """Training without sampling (Wu et al. 2019): predictive_moments' ONE pass of `_forward(x)` with its autograd graph ->
+        ops.Moments(mean, var) of the output, attached to the input and to every posterior tensor.  Nothing is drawn, no key is
+        recorded; the gradient of a loss on the moments is deterministic.  Device: fp32 moments, every backward launch is HIP
+        (K18, csrc/bnn_moments_bwd.hip; the first layer's deterministic input takes K10's).  CPU: the float64 recursion under
+        torch autograd, float64 moments.  Admitted: NormalLinear, LocalReparamLinear, ReLU folded into them
+        (nn.fuse_activations) or rewritten to nn.MomentReLU (nn.moment_activations), reshapes, torch.nn.Identity, a closing
+        nn.MomentSoftmax, deterministic modules in front of the first Bayesian layer.  The conv layers, nn.MomentELU,
+        nn.MomentLinear and the Flipout / MC-dropout / multivariate-normal / evidential layers raise ops.BnnHipError.
+        Regression: mean(((y - mom.mean)^2 + mom.var) / (2 s^2)) needs no sample; classification: sample_moments."""
+        from .. import ops
+        from .dense import NormalLinear, LocalReparamLinear
+        for m in self.modules():
+            if (isinstance(m, BayesianModule) and type(m) not in (NormalLinear, LocalReparamLinear)) or isinstance(m, (MomentELU, MomentLinear)):
+                raise ops.BnnHipError("forward_moments: %s has no moment backward; training without sampling supports "
+                                      "NormalLinear / LocalReparamLinear, ReLU (folded, or nn.MomentReLU), reshaping modules, "
+                                      "torch.nn.Identity and a closing nn.MomentSoftmax" % type(m).__name__)
+        with _mc.MomentContext(track=True):
+            try:
+                y = self._forward(x, *args, **kwargs)
+            except (TypeError, AttributeError) as e:
+                raise ops.BnnHipError("forward_moments: a module of this network cannot take a mean and a variance (%s); %s"
+                                      % (e, _MOMENTS_SUPPORTED)) from e
+        if torch.is_tensor(y):
+            y = ops.Moments(y, None)
+        if not isinstance(y, ops.Moments):
+            raise ops.BnnHipError("forward_moments: _forward returned %s; %s" % (type(y).__name__, _MOMENTS_SUPPORTED))
+        return y
+
+    def sample_moments(self, mom, samples=None, sample0=0):
+        """`samples` (default self.samples) independent draws from forward_moments' output, (S, *rows, C), differentiable in
+        the moments: ONE bnn_moments_sample launch on the model's moment stream (a fresh epoch per call, the key recorded as
+        model.moment_key; its backward re-creates eps from that key), torch.softmax applied when the moments carry
+        link='softmax'.  Classification trains on these cheap sampled outputs with the usual cross-entropy."""
+        from .. import ops
+        if not isinstance(mom, ops.Moments):
+            raise TypeError("sample_moments: expected an ops.Moments, got %s" % type(mom).__name__)
+        return self._sample_link(mom, self.samples if samples is None else samples, sample0, True)
 
     def _tail_inputs(self, who, x, samples, sample0, moments, kl, kwargs):
         """The (S, *rows, C) outputs a predictive_* tail reads.  `moments`: drawn from the propagated moments (_moment_outputs).

@@ -111,16 +111,18 @@ class _NormalSampling:
         deterministic input) or an ops.Moments -> the ops.Moments of the output, with the moment-matched ReLU when
         nn.fuse_activations folded one into the layer (activation == 'relu').  Device: ops.moments_linear (bnn_moments_forward,
         hidden moments fp32 in both compute modes); CPU: the same recursion in float64 (ops.moments_linear_f64).  Nothing is
-        drawn, no draw epoch is consumed, draw_key / noise_key stay as they are; the result is detached (inference only)."""
+        drawn, no draw epoch is consumed, draw_key / noise_key stay as they are; the result is detached unless the context
+        tracks (BayesianNetworkModule.forward_moments: training without sampling)."""
         mom = x if isinstance(x, ops.Moments) else ops.Moments(x, None)
         if not torch.is_tensor(mom.mean):
             raise TypeError("%s takes a tensor or ops.Moments in a moment pass, got %s" % (type(self).__name__, type(x).__name__))
         ops._refuse_link(mom, type(self).__name__)
         b = self.bias is not None
         args = (self.weight.mean, self.weight.scale, self.bias.mean if b else None, self.bias.scale if b else None)
+        track = _mc.moments_current().track
         if not mom.mean.is_cuda:
-            return ops.moments_linear_f64(mom, *args, relu=self.activation == 'relu')
-        return ops.moments_linear(mom, *args, relu=self.activation == 'relu', compute=self._compute_mode())
+            return ops.moments_linear_f64(mom, *args, relu=self.activation == 'relu', track=track)
+        return ops.moments_linear(mom, *args, relu=self.activation == 'relu', compute=self._compute_mode(), track=track)
 
     def _mc_plan(self, x, sample):
         """-> (S, sample0, shared_x, rows_per_sample) for the current MC context."""

@@ -984,7 +984,114 @@ def _as_moments(a, who):
     raise TypeError("%s: expected a tensor or ops.Moments, got %s" % (who, type(a).__name__))
 
 
-def moments_linear(a, mu_w, rho_w, mu_b, rho_b, relu=False, compute="f32"):
+def _tracking(track):
+    """track=True asks a moment call for its autograd graph; it has one when grad mode is on."""
+    return bool(track) and torch.is_grad_enabled()
+
+
+class _MomentsLinear(torch.autograd.Function):
+    """(m, v) of ops.moments_linear's pre-activation with a backward (K18): a deterministic input (av None) takes K10's two
+    backward launches (bnn_lrt_backward_input / _weight with x = a_m), an input that carries a variance the three-contraction
+    ones of csrc/bnn_moments_bwd.hip.  am, av: (B, K) fp32, contiguous; the posterior tensors contiguous."""
+
+    @staticmethod
+    def forward(ctx, am, av, mu_w, rho_w, mu_b, rho_b, code):
+        B, K = am.shape
+        N = mu_w.shape[0]
+        dev = am.device
+        s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
+        out_m = torch.empty((B, N), dtype=torch.float32, device=dev)
+        out_v = torch.empty((B, N), dtype=torch.float32, device=dev)
+        check(_lib.load().bnn_moments_forward(ptr(am), ptr(av), K, ptr(mu_w), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(out_m), ptr(out_v),
+                                              B, N, K, code, 0, stream_ptr(dev)), "bnn_moments_forward")
+        ctx.save_for_backward(am, av, mu_w, rho_w, rho_b if mu_b is not None else None, s2_w)
+        ctx.code = code
+        return out_m, out_v
+
+    @staticmethod
+    def backward(ctx, g_m, g_v):
+        am, av, mu_w, rho_w, rho_b, s2_w = ctx.saved_tensors
+        code = ctx.code
+        B, K = am.shape
+        N = mu_w.shape[0]
+        dev = am.device
+        lib = _lib.load()
+        g_m, g_v = g_m.contiguous(), g_v.contiguous()
+        g_am = g_av = g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
+        if ctx.needs_input_grad[0] or (av is not None and ctx.needs_input_grad[1]):
+            g_am = torch.empty_like(am)
+            if av is None:
+                check(lib.bnn_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(mu_w), ptr(s2_w), ptr(am), K, ptr(g_am), B, N, K, code, 0,
+                                                 stream_ptr(dev)), "bnn_lrt_backward_input")
+            else:
+                g_av = torch.empty_like(av)
+                check(lib.bnn_moments_backward_input(ptr(g_m), ptr(g_v), ptr(mu_w), ptr(s2_w), ptr(am), K, ptr(g_am), ptr(g_av),
+                                                     B, N, K, code, 0, stream_ptr(dev)), "bnn_moments_backward_input")
+        need_b = rho_b is not None and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or need_b:
+            g_mu_w, g_rho_w = torch.empty_like(mu_w), torch.empty_like(rho_w)
+            if need_b:
+                g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
+            pb = ptr(rho_b) if need_b else None
+            if av is None:
+                check(lib.bnn_lrt_backward_weight(ptr(am), K, ptr(g_m), ptr(g_v), ptr(rho_w), ptr(g_mu_w), ptr(g_rho_w), pb,
+                                                  ptr(g_mu_b), ptr(g_rho_b), B, N, K, code, 0, stream_ptr(dev)),
+                      "bnn_lrt_backward_weight")
+            else:
+                check(lib.bnn_moments_backward_weight(ptr(am), ptr(av), K, ptr(g_m), ptr(g_v), ptr(mu_w), ptr(rho_w), ptr(g_mu_w),
+                                                      ptr(g_rho_w), pb, ptr(g_mu_b), ptr(g_rho_b), B, N, K, code, 0, stream_ptr(dev)),
+                      "bnn_moments_backward_weight")
+        return g_am, g_av, g_mu_w, g_rho_w, g_mu_b, g_rho_b, None
+
+
+class _MomentsRelu(torch.autograd.Function):
+    """bnn_moments_relu out of place with bnn_moments_relu_backward behind it; m, v fp32, contiguous."""
+
+    @staticmethod
+    def forward(ctx, m, v):
+        om, ov = torch.empty_like(m), torch.empty_like(v)
+        check(_lib.load().bnn_moments_relu(ptr(m), ptr(v), ptr(om), ptr(ov), m.numel(), stream_ptr(m.device)), "bnn_moments_relu")
+        ctx.save_for_backward(m, v)
+        return om, ov
+
+    @staticmethod
+    def backward(ctx, g_om, g_ov):
+        m, v = ctx.saved_tensors
+        g_om, g_ov = g_om.contiguous(), g_ov.contiguous()
+        g_m, g_v = torch.empty_like(m), torch.empty_like(v)
+        check(_lib.load().bnn_moments_relu_backward(ptr(m), ptr(v), ptr(g_om), ptr(g_ov), ptr(g_m), ptr(g_v), m.numel(),
+                                                    stream_ptr(m.device)), "bnn_moments_relu_backward")
+        return g_m, g_v
+
+
+class _MomentsSample(torch.autograd.Function):
+    """bnn_moments_sample with K10's noise launch as its backward: g_m = sum_s gy_s, g_v = sum_s gy_s eps_s / (2 sqrt(v + 1e-16)),
+    eps re-created from the key (bnn_lrt_backward_epilogue on a shared input -- index for index the forward's eps)."""
+
+    @staticmethod
+    def forward(ctx, m, v, key, S):
+        N = m.shape[-1]
+        rows = m.numel() // N
+        y = torch.empty((S,) + tuple(m.shape), dtype=torch.float32, device=m.device)
+        r = _rng_struct(key, m.device)
+        check(_lib.load().bnn_moments_sample(ptr(m), ptr(v), ptr(y), rows, N, S, ctypes.byref(r), 0, stream_ptr(m.device)),
+              "bnn_moments_sample")
+        ctx.save_for_backward(v)
+        ctx.key, ctx.S, ctx.rows = key, S, rows
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        v, = ctx.saved_tensors
+        gy = gy.contiguous()
+        g_m, g_v = torch.empty_like(v), torch.empty_like(v)
+        r = _rng_struct(ctx.key, v.device)
+        check(_lib.load().bnn_lrt_backward_epilogue(ptr(gy), ptr(v), ptr(g_m), ptr(g_v), ctx.rows, v.shape[-1], ctx.S, 1,
+                                                    ctypes.byref(r), 0, stream_ptr(v.device)), "bnn_lrt_backward_epilogue")
+        return g_m, g_v, None, None
+
+
+def moments_linear(a, mu_w, rho_w, mu_b, rho_b, relu=False, compute="f32", track=False):
     """Mean and variance of a dense layer's pre-activation for independent Gaussian weights, from the mean and variance of its
     input (bnn_lrt_prepare + bnn_moments_forward, csrc/bnn_moments.hip) -> Moments, fp32 (*rows, N):
 
@@ -992,14 +1099,18 @@ def moments_linear(a, mu_w, rho_w, mu_b, rho_b, relu=False, compute="f32"):
 
     a: a device tensor (a deterministic input: the second term is absent) or a Moments.  relu: the moment-matched ReLU of
     moments_relu in the launch's epilogue (the same bits).  A bf16 `a` is read as it is in the 'bf16' mode (deterministic input
-    only).  Inference only: nothing is drawn, no key is touched, the result is detached whatever the grad mode."""
+    only).  Nothing is drawn, no key is touched.  track=False (inference): the result is detached whatever the grad mode.
+    track=True with grad mode on (training without sampling, K18): the result is attached to the graph of `a` and the four
+    posterior tensors; the backward is HIP (csrc/bnn_moments_bwd.hip; K10's launches for a deterministic input); `a` is fp32."""
     mom = _as_moments(a, "moments_linear")
     code = _compute_code(compute)
-    am = mom.mean.detach()
-    av = None if mom.var is None else mom.var.detach()
-    mu_w, rho_w = mu_w.detach().contiguous(), rho_w.detach().contiguous()
+    tracked = _tracking(track)
+    keep = (lambda t: t) if tracked else (lambda t: t.detach())
+    am = keep(mom.mean)
+    av = None if mom.var is None else keep(mom.var)
+    mu_w, rho_w = keep(mu_w).contiguous(), keep(rho_w).contiguous()
     if mu_b is not None:
-        mu_b, rho_b = mu_b.detach().contiguous(), rho_b.detach().contiguous()
+        mu_b, rho_b = keep(mu_b).contiguous(), keep(rho_b).contiguous()
     _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b)
     N, K = mu_w.shape
     if am.dim() < 1 or am.shape[-1] != K:
@@ -1015,6 +1126,15 @@ def moments_linear(a, mu_w, rho_w, mu_b, rho_b, relu=False, compute="f32"):
     B = am.shape[0]
     if B > 64 * 65535:
         raise BnnHipError("moments_linear: %d rows (at most %d)" % (B, 64 * 65535))
+    if tracked:
+        # the same launches' bits, the ReLU as bnn_moments_relu behind the contraction instead of in its epilogue (one device
+        # function): the backward needs the pre-activation
+        if _bf(am):
+            raise BnnHipError("moments_linear: track=True takes an fp32 input")
+        m, v = _MomentsLinear.apply(am, av, mu_w, rho_w, mu_b, rho_b, code)
+        if relu:
+            m, v = _MomentsRelu.apply(m, v)
+        return Moments(m.reshape(lead + (N,)), v.reshape(lead + (N,)))
     dev = am.device
     s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
     out_m = torch.empty((B, N), dtype=torch.float32, device=dev)
@@ -1025,11 +1145,19 @@ def moments_linear(a, mu_w, rho_w, mu_b, rho_b, relu=False, compute="f32"):
     return Moments(out_m.reshape(lead + (N,)), out_v.reshape(lead + (N,)))
 
 
-def moments_relu(mom):
+def moments_relu(mom, track=False):
     """ReLU of Gaussian activations by moment matching (bnn_moments_relu) -> Moments: with s = sqrt(v), alpha = m / s,
     mean' = s (alpha Phi + phi), var' = v (Phi + alpha^2 Phi Phi(-alpha) + alpha phi (Phi(-alpha) - Phi) - phi^2) clamped at 0;
-    v == 0 gives (max(m, 0), 0).  A deterministic input (var None) stays one."""
+    v == 0 gives (max(m, 0), 0).  A deterministic input (var None) stays one.  track=True with grad mode on: attached to the
+    graph, the backward is bnn_moments_relu_backward (a deterministic input: torch.relu's)."""
     mom = _as_moments(mom, "moments_relu")
+    if _tracking(track):
+        if mom.var is None:
+            return Moments(torch.relu(mom.mean), None)
+        m, v = mom.mean.contiguous(), mom.var.contiguous()
+        require_cuda_f32(m, "mean")
+        require_cuda_f32(v, "var")
+        return Moments(*_MomentsRelu.apply(m, v))
     if mom.var is None:
         return Moments(torch.relu(mom.mean.detach()), None)
     m, v = mom.mean.detach().contiguous(), mom.var.detach().contiguous()
@@ -1040,15 +1168,18 @@ def moments_relu(mom):
     return Moments(om, ov)
 
 
-def moments_sample(mom, key, nsamples):
+def moments_sample(mom, key, nsamples, track=False):
     """nsamples draws of independent Gaussians with the given moments in ONE launch (bnn_moments_sample) -> (S, *shape) fp32:
     y_s[e] = m[e] + sqrt(v[e] + 1e-16) eps_s[e], e the flat index within one sample, eps_s[e] element e of the key's sample
     sample0 + s (the LRT-noise contract).  The result is what the mc_* tails read.  CPU moments: torch.randn (the key is not
-    used and may be None)."""
+    used and may be None).  track=True with grad mode on: differentiable in the moments -- the backward re-creates eps from the
+    key (bnn_lrt_backward_epilogue: g_m = sum_s gy_s, g_v = sum_s gy_s eps_s / (2 sqrt(v + 1e-16)))."""
     mom = _as_moments(mom, "moments_sample")
     S = int(nsamples)
-    m = mom.mean.detach()
-    v = torch.zeros_like(m) if mom.var is None else mom.var.detach()
+    tracked = _tracking(track)
+    keep = (lambda t: t) if tracked else (lambda t: t.detach())
+    m = keep(mom.mean)
+    v = torch.zeros_like(m) if mom.var is None else keep(mom.var)
     if not m.is_cuda:
         m64, v64 = m.double(), v.double()
         return (m64 + torch.sqrt(v64 + 1e-16) * torch.randn((S,) + tuple(m.shape), dtype=torch.float64)).to(torch.float32)
@@ -1064,6 +1195,8 @@ def moments_sample(mom, key, nsamples):
     if m.numel() >= 2 ** 32:
         raise BnnHipError("moments_sample: one sample has %d elements: the noise index is 32 bits wide" % m.numel())
     m, v = (t if _aligned16(t) else t.clone() for t in (m, v))     # (bnn_moments_sample refuses moments off a 16-B boundary)
+    if tracked:
+        return _MomentsSample.apply(m, v, key, S)
     y = torch.empty((S,) + tuple(m.shape), dtype=torch.float32, device=m.device)
     r = _rng_struct(key, m.device)
     check(_lib.load().bnn_moments_sample(ptr(m), ptr(v), ptr(y), rows, N, S, ctypes.byref(r), 0, stream_ptr(m.device)),
@@ -1071,13 +1204,22 @@ def moments_sample(mom, key, nsamples):
     return y
 
 
-def moments_relu_f64(mom):
-    """moments_relu in float64 torch."""
+def _f64(track):
+    """t -> float64, detached unless track=True with grad mode on."""
+    if _tracking(track):
+        return lambda t: t.to(torch.float64)
+    return lambda t: t.detach().to(torch.float64)
+
+
+def moments_relu_f64(mom, track=False):
+    """moments_relu in float64 torch.  track=True: not detached (plain torch autograd; at v == 0 the gradient is the stated
+    convention of moments_relu_backward_f64)."""
     mom = _as_moments(mom, "moments_relu_f64")
-    m = mom.mean.detach().to(torch.float64)
+    f64 = _f64(track)
+    m = f64(mom.mean)
     if mom.var is None:
-        return Moments(m.clamp_min(0), None)
-    v = mom.var.detach().to(torch.float64)
+        return Moments(torch.relu(m) if _tracking(track) else m.clamp_min(0), None)
+    v = f64(mom.var)
     pos = v > 0
     s = torch.sqrt(torch.where(pos, v, torch.ones_like(v)))
     al = m / s
@@ -1085,13 +1227,43 @@ def moments_relu_f64(mom):
     pdf = torch.exp(-0.5 * al * al) / math.sqrt(2.0 * math.pi)
     mean = s * (al * cdf + pdf)
     var = (v * (cdf + al * al * cdf * cdc + al * pdf * (cdc - cdf) - pdf * pdf)).clamp_min(0)
+    if _tracking(track):        # the same values; v == 0 passes both gradients where m > 0
+        return Moments(torch.where(pos, mean, torch.relu(m)), torch.where(pos, var, torch.where(m > 0, v, torch.zeros_like(v))))
     return Moments(torch.where(pos, mean, m.clamp_min(0)), torch.where(pos, var, torch.zeros_like(v)))
 
 
-def moments_linear_f64(a, mu_w, rho_w, mu_b, rho_b, relu=False):
-    """moments_linear in float64 torch (sigma = 1e-10 + softplus(rho)) -> Moments of float64 tensors."""
-    mom = _as_moments(a, "moments_linear_f64")
+def moments_relu_backward_f64(mom, g_mean, g_var):
+    """The backward of moments_relu in float64 torch, as a formula: (g_m, g_v) at the pre-activation `mom` from the gradients
+    of the two outputs.  With s = sqrt(v), alpha = m / s, Phi / phi the normal cdf / pdf and mean' the forward's mean:
+
+        g_m = g_mean Phi + g_var 2 mean' Phi(-alpha),    g_v = g_mean phi / (2 s) + g_var (Phi - mean' phi / s)
+
+    Where the forward clamped var' to 0 the g_var terms are 0; v == 0 gives g_m = g_mean [m > 0], g_v = g_var [m > 0]; a
+    deterministic input (var None) is plain ReLU: (g_mean [m > 0], None)."""
+    mom = _as_moments(mom, "moments_relu_backward_f64")
     f64 = lambda t: t.detach().to(torch.float64)         # noqa: E731
+    m, g_mean = f64(mom.mean), f64(g_mean)
+    on = (m > 0).to(torch.float64)
+    if mom.var is None:
+        return g_mean * on, None
+    v, g_var = f64(mom.var), f64(g_var)
+    pos = v > 0
+    s = torch.sqrt(torch.where(pos, v, torch.ones_like(v)))
+    al = m / s
+    cdf, cdc = 0.5 * torch.special.erfc(-al / math.sqrt(2.0)), 0.5 * torch.special.erfc(al / math.sqrt(2.0))
+    pdf = torch.exp(-0.5 * al * al) / math.sqrt(2.0 * math.pi)
+    mean = s * (al * cdf + pdf)
+    r = cdf + al * al * cdf * cdc + al * pdf * (cdc - cdf) - pdf * pdf
+    gv = torch.where(v * r < 0, torch.zeros_like(g_var), g_var)
+    g_m = g_mean * cdf + gv * (2.0 * mean * cdc)
+    g_v = g_mean * (0.5 * pdf / s) + gv * (cdf - mean * pdf / s)
+    return torch.where(pos, g_m, g_mean * on), torch.where(pos, g_v, g_var * on)
+
+
+def moments_linear_f64(a, mu_w, rho_w, mu_b, rho_b, relu=False, track=False):
+    """moments_linear in float64 torch (sigma = 1e-10 + softplus(rho)) -> Moments of float64 tensors.  track=True: not detached."""
+    mom = _as_moments(a, "moments_linear_f64")
+    f64 = _f64(track)
     sig2 = lambda rho: (1e-10 + torch.nn.functional.softplus(f64(rho))) ** 2         # noqa: E731
     am, mu, s2 = f64(mom.mean), f64(mu_w), sig2(rho_w)
     m = am @ mu.t()
@@ -1101,15 +1273,16 @@ def moments_linear_f64(a, mu_w, rho_w, mu_b, rho_b, relu=False):
     if mu_b is not None:
         m, v = m + f64(mu_b), v + sig2(rho_b)
     out = Moments(m, v)
-    return moments_relu_f64(out) if relu else out
+    return moments_relu_f64(out, track) if relu else out
 
 
-def moments_f64(a, layers):
+def moments_f64(a, layers, track=False):
     """The moment recursion of a chain of dense layers in float64 torch -- the CPU path of predictive_moments and the tests'
-    reference: a, a tensor or Moments; layers, a sequence of (mu_w, rho_w, mu_b, rho_b, relu).  -> Moments of float64 tensors."""
+    reference: a, a tensor or Moments; layers, a sequence of (mu_w, rho_w, mu_b, rho_b, relu).  -> Moments of float64 tensors.
+    track=True: not detached (torch autograd through the whole recursion)."""
     mom = _as_moments(a, "moments_f64")
     for mu_w, rho_w, mu_b, rho_b, relu in layers:
-        mom = moments_linear_f64(mom, mu_w, rho_w, mu_b, rho_b, relu)
+        mom = moments_linear_f64(mom, mu_w, rho_w, mu_b, rho_b, relu, track)
     return mom
 
 

@@ -1174,6 +1174,35 @@ int bnn_conv3d_moments_forward(const float *a_m, const float *a_v, const float *
  * not finite), BNN_E_ALIGN. */
 int bnn_moments_elu(const float *m, const float *v, float *out_m, float *out_v, int64_t n, float alpha, void *stream);
 
+/* ---- K18: training without sampling, the backward of K16's dense layer and of the moment-matched ReLU
+ * (csrc/bnn_moments_bwd.hip; ops.moments_linear(track=True), BayesianNetworkModule.forward_moments).  With G_m, G_v the (B, N)
+ * gradients with respect to m and v of bnn_moments_forward, for an input that carries a variance:
+ *     g_a_m  = G_m mu_w + 2 a_m (.) (G_v sigma_w^2)          g_a_v  = G_v (mu_w^2 + sigma_w^2)           contraction over n
+ *     g_mu_w = G_m^T a_m + 2 mu_w (.) (G_v^T a_v)            g_s2_w = G_v^T (a_m^2 + a_v)                over the rows, in row order
+ *     g_rho_w = g_s2_w 2 sigma_w sigmoid(rho_w)              g_mu_b = sum_rows G_m,  g_rho_b = (sum_rows G_v) 2 sigma_b sigmoid(rho_b)
+ * One 64 x 64 x 32 tile of K10's skeleton for both: P planes (p1, p2, fma(p1, p1, p2) -- formed in fp32 by the loader), Q planes
+ * (G_m, G_v) with G_v serving twice, three accumulator sets, out1 = acc1 + 2 x (.) acc2 and out2 = acc3 in the epilogue.
+ * compute: BNN_COMPUTE_F32 = v_mfma_f32_16x16x4_f32 (an ordered fp32 fma chain); BNN_COMPUTE_BF16 = the five planes rounded to
+ * bf16 (RNE) as they are staged, fp32 accumulate.  No atomics, no split contraction: identical calls give identical bits.
+ * A deterministic input (no a_v) has K10's backward: call bnn_lrt_backward_input / bnn_lrt_backward_weight with x = a_m.
+ * Every operand and gradient is fp32; a_m, a_v have row pitch lda; flags: 0.  Graph-capturable; errors are returned before
+ * anything is launched: BNN_E_NULL, BNN_E_SHAPE (extent < 1, lda < K), BNN_E_RANGE (rows > 64 * 65535; the weight gradient:
+ * N > 64 * 65535), BNN_E_DTYPE (compute), BNN_E_UNSUPPORTED (any flag), BNN_E_ALIGN (element; 16 bytes for the contraction
+ * outputs g_a_m, g_a_v, g_mu_w, g_rho_w).  B == 0: bnn_moments_backward_input returns BNN_OK at once, the weight gradients are
+ * stored as zeros. */
+int bnn_moments_backward_input(const float *g_m, const float *g_v, const float *mu_w, const float *s2_w, const float *a_m, int64_t lda,
+                               float *g_a_m, float *g_a_v, int64_t B, int64_t N, int64_t K, int compute, int flags, void *stream);
+/* Bias (rho_b, g_mu_b, g_rho_b all given, or all NULL): K10's second launch. */
+int bnn_moments_backward_weight(const float *a_m, const float *a_v, int64_t lda, const float *g_m, const float *g_v, const float *mu_w,
+                                const float *rho_w, float *g_mu_w, float *g_rho_w, const float *rho_b, float *g_mu_b, float *g_rho_b,
+                                int64_t B, int64_t N, int64_t K, int compute, int flags, void *stream);
+/* Backward of bnn_moments_relu at the pre-activation (m, v), on the forward's own Phi, phi and mean':
+ *     g_m = g_out_m Phi + g_out_v 2 mean' Phi(-alpha)        g_v = g_out_m phi / (2 s) + g_out_v (Phi - mean' phi / s)
+ * Where the forward clamped var' to 0 the g_out_v terms are absent; v == 0 (and |alpha| >= 40) gives g_m = g_out_m [m > 0],
+ * g_v = g_out_v [m > 0].  n elements; g_m / g_v may be g_out_m / g_out_v. */
+int bnn_moments_relu_backward(const float *m, const float *v, const float *g_out_m, const float *g_out_v, float *g_m, float *g_v,
+                              int64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
