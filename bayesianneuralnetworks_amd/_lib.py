@@ -234,6 +234,11 @@ SIGNATURES = {
     "bnn_moments_backward_input": (_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
     "bnn_moments_backward_weight": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
     "bnn_moments_relu_backward": (_int, [_p, _p, _p, _p, _p, _p, _i64, _p]),
+    "bnn_conv3d_moments_backward_input": (_int, [_p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _p]),
+    "bnn_conv3d_moments_wgrad_workspace": (_i64, [ctypes.POINTER(Conv3dShape)]),
+    "bnn_conv3d_moments_backward_weight": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _p,
+                                                  _i64, _p]),
+    "bnn_moments_elu_backward": (_int, [_p, _p, _p, _p, _p, _p, _i64, ctypes.c_float, _p]),
 }
 
 _lib = None

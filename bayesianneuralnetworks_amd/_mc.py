@@ -43,7 +43,8 @@ class MomentContext:
     NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d take a tensor (a deterministic input) or an ops.Moments and hand on
     the mean and variance of their output (ops.moments_linear, ops.moments_convNd) instead of samples.  They draw nothing and record no key.  Thread-local, like McContext, and kept apart
     from it: an MC-batched pass and a moment pass do not see each other.  track=True (BayesianNetworkModule.forward_moments):
-    the dense layers and nn.MomentReLU keep the autograd graph (ops.moments_linear(track=True)); the default is inference."""
+    the dense layers and nn.MomentReLU keep the autograd graph (ops.moments_linear(track=True)), and so do the conv layers,
+    nn.MomentELU and nn.MomentLinear (ops.moments_convNd / moments_elu / moments_affine(track=True)); the default is inference."""
 
     def __init__(self, track=False):
         self.track = bool(track)

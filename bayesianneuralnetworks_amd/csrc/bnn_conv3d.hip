@@ -982,6 +982,313 @@ __global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d(const Conv3dGeo g
     }
 }
 
+// ---- K19: the backward of K17's contraction, for training conv nets without sampling.  With G_m, G_v the (B, O, P) gradients
+// with respect to m and v above, convT the transposed contraction and the sums over (image, position) in that order:
+//     g_a_m  = convT(G_m, mu_w) + 2 a_m (.) convT(G_v, sigma_w^2)             g_a_v  = convT(G_v, mu_w^2 + sigma_w^2)
+//     g_mu_w = sum gather(a_m) G_m + 2 mu_w (.) sum gather(a_v) G_v            g_s2_w = sum gather(a_m^2 + a_v) G_v
+// K18's shape (P planes (p1, p2, fma(p1, p1, p2)), Q planes (G_m, G_v) with G_v serving twice, THREE accumulator sets: 96
+// accumulator registers per lane) on K11's backward tile and loaders:
+//   DGRAD A = gather(G_m), gather(G_v); B = mu_w^T, sigma_w^2^T and their derived plane.  acc1 = A1 B1, acc2 = A2 B2, acc3 = A2 B3.
+//         Epilogue: g_a_m = acc1 + 2 a_m acc2, g_a_v = acc3; a lane's quad runs along the input position (16-byte stores when
+//         D H W % 4 == 0).
+//   WGRAD A = gather(a_m), gather(a_v) and their derived plane; B = G_m, G_v.  acc1 = A1 B1, acc2 = A2 B2, acc3 = A3 B2.  Slabs
+//         [slab][3][O][K] on wgrad_split; k_moments_conv_wsum adds them in slab order and writes g_mu_w = S1 + 2 mu_w S2 and
+//         g_rho_w = S3 2 sigma_w sigmoid(rho_w).
+// The derived plane is formed in fp32: the bf16 mode rounds it (RNE) into an LDS plane of its own as it is staged; the fp32
+// mode forms it from the two fragments it has just read (the same value), so its LDS is K11's.  G_v is staged once and read by
+// two MFMA streams.  No sample axis, no atomics, fixed order: identical calls give identical bits.  A deterministic input
+// (a_v absent) has K11's backward (bnn_conv3d_lrt_backward_input / _weight with one image set): there is no kernel for it here.
+struct MomConvBwdArgs {
+    const float *g1, *g2;                    // G_m, G_v, (B, O, P)
+    const float *w1, *w2;                    // DGRAD: mu_w, sigma_w^2, O x K
+    const float *a_m, *a_v;                  // (B, C, D, H, W); DGRAD reads a_m alone (its epilogue)
+    float *out, *out2;                       // DGRAD: g_a_m, g_a_v; WGRAD: out = slab base
+    int32_t nslab, chunk;                    // WGRAD: slabs per group, reduction positions per slab (% C3_BK == 0)
+};
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d_bwd(const Conv3dGeo g, const MomConvBwdArgs a)
+{
+    static_assert(MODE == C3_DGRAD || MODE == C3_WGRAD, "the forward is k_moments_conv3d");
+    constexpr int LDK = Op<T>::LDK;
+    constexpr bool BF = sizeof(T) == 2, WG = MODE == C3_WGRAD;
+    constexpr int NA = BF && WG ? 3 : 2, NB = BF && !WG ? 3 : 2;     // planes in LDS (the derived one: bf16 only)
+    __shared__ __attribute__((aligned(16))) T As[NA * C3_BM * LDK];
+    __shared__ __attribute__((aligned(16))) T Bs[NB * C3_BN * LDK];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave & 1, wn = wave >> 1;
+
+    // the block's (group, slab)
+    int z = blockIdx.z, slab = 0;
+    if (WG) { slab = z % a.nslab; z /= a.nslab; }
+    const int grp = z;
+
+    const int32_t M = WG ? g.K : g.B * g.Pin;
+    const int32_t N = WG ? g.Ng : g.Cg;
+    const int32_t m0 = blockIdx.x * C3_BM, n0 = blockIdx.y * C3_BN;
+    int32_t rbeg = 0, rend = WG ? g.B * g.P : g.Ng * g.T;
+    if (WG) {
+        rbeg = slab * a.chunk;
+        rend = min(rend, rbeg + a.chunk);
+    }
+
+    // ---- A loader: row ar of the tile, reduction offsets ah * 16 .. + 15 of each k-tile
+    const int ar = tid & (C3_BM - 1);
+    const int ah = __builtin_amdgcn_readfirstlane(tid >> 7);
+    const int32_t am = m0 + ar;
+    const bool arow = am < M;
+    int32_t abase = 0, z0 = 0, z1 = 0, z2 = 0;   // DGRAD: gather origin of the row; WGRAD: its tap
+    if (!WG && arow) {
+        const uint32_t b = fdiv(am, g.fPin), p = am - b * g.Pin;
+        const uint32_t q = fdiv(p, g.fW), iw = p - q * g.W, id = fdiv(q, g.fH), ih = q - id * g.H;
+        z0 = id + g.pd; z1 = ih + g.ph; z2 = iw + g.pw;
+        abase = (b * g.O + grp * g.Ng) * g.P;
+    } else if (WG && arow) {
+        const uint32_t c = fdiv(am, g.fT), t = am - c * g.T;
+        const uint32_t q = fdiv(t, g.fKW), kw = t - q * g.KW, kd = fdiv(q, g.fKH), kh = q - kd * g.KH;
+        z0 = kd * g.dd - g.pd; z1 = kh * g.dh - g.ph; z2 = kw * g.dw - g.pw;
+        abase = (grp * g.Cg + c) * g.Pin;
+    }
+
+    // v, v2: DGRAD gather(G_m), gather(G_v); WGRAD gather(a_m), gather(a_v)
+    auto fetch_a = [&](int32_t r0, float (&v)[16], float (&v2)[16]) {
+        const int32_t r = r0 + ah * 16;
+        if (WG) {
+            // reduction index = output position (b, od, oh, ow), stepped with carries
+            uint32_t b = 0, od = 0, oh = 0, ow = 0;
+            if (r < rend) {
+                b = fdiv(r, g.fP);
+                const uint32_t p = r - b * g.P, q = fdiv(p, g.fOW);
+                ow = p - q * g.OW; od = fdiv(q, g.fOH); oh = q - od * g.OH;
+            }
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int32_t id = (int32_t)(od * g.sd) + z0, ih = (int32_t)(oh * g.sh) + z1, iw = (int32_t)(ow * g.sw) + z2;
+                const bool ok = arow && r + j < rend && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H &&
+                                (uint32_t)iw < (uint32_t)g.W;
+                const int64_t off = (int64_t)b * g.C * g.Pin + abase + (id * g.H + ih) * g.W + iw;
+                v[j] = ok ? a.a_m[off] : 0.f;
+                v2[j] = ok ? a.a_v[off] : 0.f;
+                if (++ow == (uint32_t)g.OW) { ow = 0; if (++oh == (uint32_t)g.OH) { oh = 0; if (++od == (uint32_t)g.OD) { od = 0; ++b; } } }
+            }
+            return;
+        }
+        // reduction index = (output channel, kd, kh, kw), stepped with carries
+        uint32_t c = 0, kd = 0, kh = 0, kw = 0;
+        if (r < rend) {
+            c = fdiv(r, g.fT);
+            const uint32_t t = r - c * g.T, q = fdiv(t, g.fKW);
+            kw = t - q * g.KW; kd = fdiv(q, g.fKH); kh = q - kd * g.KH;
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            bool ok = arow && r + j < rend;
+            const int32_t nd = z0 - (int32_t)kd * g.dd, nh = z1 - (int32_t)kh * g.dh, nw = z2 - (int32_t)kw * g.dw;
+            ok = ok && nd >= 0 && nh >= 0 && nw >= 0;
+            const uint32_t od = fdiv(ok ? nd : 0, g.fsd), oh = fdiv(ok ? nh : 0, g.fsh), ow = fdiv(ok ? nw : 0, g.fsw);
+            ok = ok && (int32_t)(od * g.sd) == nd && (int32_t)(oh * g.sh) == nh && (int32_t)(ow * g.sw) == nw &&
+                 od < (uint32_t)g.OD && oh < (uint32_t)g.OH && ow < (uint32_t)g.OW;
+            const int32_t off = abase + (int32_t)c * g.P + (int32_t)((od * g.OH + oh) * g.OW + ow);
+            v[j] = ok ? a.g1[off] : 0.f;
+            v2[j] = ok ? a.g2[off] : 0.f;
+            if (++kw == (uint32_t)g.KW) { kw = 0; if (++kh == (uint32_t)g.KH) { kh = 0; if (++kd == (uint32_t)g.KD) { kd = 0; ++c; } } }
+        }
+    };
+
+    // ---- B loader: reduction offset bk of each k-tile, rows bn + 8 i of the tile
+    const int bk = tid & (C3_BK - 1), bn = tid >> 5;
+    auto fetch_b = [&](int32_t r0, float (&v)[8], float (&v2)[8]) {
+        const int32_t r = r0 + bk;
+        const bool rok = r < rend;
+        if (WG) {
+            uint32_t b = 0, p = 0;
+            if (rok) { b = fdiv(r, g.fP); p = r - b * g.P; }
+            const int64_t o0 = ((int64_t)b * g.O + (int64_t)grp * g.Ng) * g.P + p;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int32_t n = n0 + bn + 8 * i;
+                const bool ok = rok && n < N;
+                v[i] = ok ? a.g1[o0 + (int64_t)n * g.P] : 0.f;
+                v2[i] = ok ? a.g2[o0 + (int64_t)n * g.P] : 0.f;
+            }
+            return;
+        }
+        // r = (o, tap): w[o][c][tap], read transposed
+        const int64_t wb = (int64_t)grp * g.Ng * g.K;
+        const uint32_t o = fdiv(rok ? r : 0, g.fT);
+        const int32_t roff = (int32_t)(o * g.K + (r - o * g.T));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int32_t n = n0 + bn + 8 * i;
+            const bool ok = rok && n < N;
+            v[i] = ok ? a.w1[wb + (int64_t)n * g.T + roff] : 0.f;
+            v2[i] = ok ? a.w2[wb + (int64_t)n * g.T + roff] : 0.f;
+        }
+    };
+
+    // the derived plane in fp32, then rounded as the plain copies (bf16 mode; the fp32 mode forms it from the fragments)
+    auto store_tiles = [&](const float (&va)[16], const float (&va2)[16], const float (&vb)[8], const float (&vb2)[8]) {
+        T *pa = As + ar * LDK + ah * 16;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            st_lds(pa + j, va[j]);
+            st_lds(pa + C3_BM * LDK + j, va2[j]);
+            if constexpr (NA == 3) st_lds(pa + 2 * C3_BM * LDK + j, __builtin_fmaf(va[j], va[j], va2[j]));
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            T *pb = Bs + (bn + 8 * i) * LDK + bk;
+            st_lds(pb, vb[i]);
+            st_lds(pb + C3_BN * LDK, vb2[i]);
+            if constexpr (NB == 3) st_lds(pb + 2 * C3_BN * LDK, __builtin_fmaf(vb[i], vb[i], vb2[i]));
+        }
+    };
+
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    f32x4 acc[3][4][2];
+#pragma unroll
+    for (int h = 0; h < 3; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int ntile = rend > rbeg ? (rend - rbeg + C3_BK - 1) / C3_BK : 0;
+    float va[16], va2[16], vb[8], vb2[8];
+    if (ntile > 0) { fetch_a(rbeg, va, va2); fetch_b(rbeg, vb, vb2); }
+    for (int step = 0; step < ntile; ++step) {
+        __syncthreads();                                // the previous tile's fragment reads are done
+        store_tiles(va, va2, vb, vb2);
+        __syncthreads();
+        if (step + 1 < ntile) {                         // the next tile's loads fly under this tile's MFMAs
+            fetch_a(rbeg + (step + 1) * C3_BK, va, va2);
+            fetch_b(rbeg + (step + 1) * C3_BK, vb, vb2);
+        }
+        if constexpr (BF) {
+            typedef short s16x8 __attribute__((ext_vector_type(8)));
+            // stream h: A plane, B plane -- (0, 0), (1, 1), then G_v's plane again with the derived one
+#pragma unroll
+            for (int h = 0; h < 3; ++h) {
+                const int ha = h < 2 ? h : (WG ? 2 : 1), hb = h < 2 ? h : (WG ? 1 : 2);
+                const T *A = As + ha * C3_BM * LDK, *Bt = Bs + hb * C3_BN * LDK;
+                s16x8 fa[4], fb[2];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    fa[i] = *reinterpret_cast<const s16x8 *>(A + (wm * 64 + i * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    fb[j] = *reinterpret_cast<const s16x8 *>(Bt + (wn * 32 + j * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[h][i][j], 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < C3_BK / 4; ++kk) {
+                float fa[3][4], fb[3][2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) fa[h][i] = A[(wm * 64 + i * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) fb[h][j] = Bt[(wn * 32 + j * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) fa[2][i] = WG ? __builtin_fmaf(fa[0][i], fa[0][i], fa[1][i]) : fa[1][i];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) fb[2][j] = WG ? fb[1][j] : __builtin_fmaf(fb[0][j], fb[0][j], fb[1][j]);
+#pragma unroll
+                for (int h = 0; h < 3; ++h)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[h][i], fb[h][j], acc[h][i][j], 0, 0, 0);
+            }
+        }
+    }
+
+    // ---- epilogue: lane holds C[(lane >> 4) * 4 + q][lane & 15] of each 16 x 16 block
+    if constexpr (WG) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
+            if (n >= N) continue;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int32_t m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + q;
+                    if (m >= M) continue;
+                    // slab [slab][3][o][k]
+                    const int64_t plane = (int64_t)g.O * g.K, e = ((int64_t)slab * 3 * g.O + grp * g.Ng + n) * g.K + m;
+                    a.out[e] = acc[0][i][j][q];
+                    a.out[e + plane] = acc[1][i][j][q];
+                    a.out[e + 2 * plane] = acc[2][i][j][q];
+                }
+        }
+    } else {
+        // a lane's quad runs along the input position: with Pin % 4 == 0 it is four consecutive elements of one image and channel
+        const bool vec = (g.Pin & 3) == 0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
+            if (n >= N) continue;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int32_t mq = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
+                if (mq >= M) continue;
+                auto elem = [&](uint32_t m) {
+                    const uint32_t b = fdiv(m, g.fPin);
+                    return (b * (uint32_t)g.C + (uint32_t)(grp * g.Cg + n)) * (uint32_t)g.Pin + (m - b * (uint32_t)g.Pin);
+                };
+                if (vec) {
+                    const uint32_t e0 = elem(mq);
+                    float r1[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) r1[q] = __builtin_fmaf(2.0f * a.a_m[e0 + q], acc[1][i][j][q], acc[0][i][j][q]);
+                    *reinterpret_cast<float4 *>(a.out + e0) = make_float4(r1[0], r1[1], r1[2], r1[3]);
+                    *reinterpret_cast<float4 *>(a.out2 + e0) =
+                        make_float4(acc[2][i][j][0], acc[2][i][j][1], acc[2][i][j][2], acc[2][i][j][3]);
+                } else {
+                    const int nq = M - mq < 4 ? M - mq : 4;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        if (q >= nq) continue;
+                        const uint32_t e = elem(mq + q);
+                        a.out[e] = __builtin_fmaf(2.0f * a.a_m[e], acc[1][i][j][q], acc[0][i][j][q]);
+                        a.out2[e] = acc[2][i][j][q];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// g_mu_w[e] = S1 + 2 mu_w[e] S2, g_rho_w[e] = S3 2 sigma sigmoid(rho_w[e]); S1, S2, S3 the sums of the three slab planes in slab order
+__global__ __launch_bounds__(256) void k_moments_conv_wsum(const float *__restrict__ slabs, int nslab, const float *__restrict__ mu,
+                                                          const float *__restrict__ rho, float *__restrict__ g_mu,
+                                                          float *__restrict__ g_rho, int64_t n)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    for (int k = 0; k < nslab; ++k) {
+        const float *p = slabs + (int64_t)k * 3 * n + e;
+        s1 += p[0];
+        s2 += p[n];
+        s3 += p[2 * n];
+    }
+    const float r = rho[e];
+    g_mu[e] = __builtin_fmaf(2.0f * mu[e], s2, s1);
+    g_rho[e] = s3 * (2.0f * sigma_lrt(r) * dsigma_lrt(r));
+}
+
 static int conv3d_geo(const char *who, const bnn_conv3d_shape_t *sh, int nsamples, int compute, Conv3dGeo &g)
 {
     if (!sh) { set_error("%s: NULL shape", who); return BNN_E_NULL; }
@@ -1419,6 +1726,112 @@ int bnn_conv3d_moments_forward(const float *a_m, const float *a_v, const float *
         if (a_v) hipLaunchKernelGGL((k_moments_conv3d<float, true>), grid, block, 0, st, g, a);
         else hipLaunchKernelGGL((k_moments_conv3d<float, false>), grid, block, 0, st, g, a);
     }
+    return check_launch(who);
+}
+
+// ---- K19 entries (the backward of bnn_conv3d_moments_forward for an input that carries a variance) ----------------------------
+// the shape with B == 0 admitted (every other check runs on one image) and the grid's y range
+static int momb_conv_geo(const char *who, const bnn_conv3d_shape_t *shape, int compute, Conv3dGeo &g, bool &empty)
+{
+    if (!shape) { set_error("%s: NULL shape", who); return BNN_E_NULL; }
+    bnn_conv3d_shape_t sh = *shape;
+    empty = sh.B == 0;
+    if (empty) sh.B = 1;
+    const int rc = conv3d_geo(who, &sh, 1, compute, g);
+    if (rc) return rc;
+    if ((g.Ng + C3_BN - 1) / C3_BN > 65535 || (g.Cg + C3_BN - 1) / C3_BN > 65535) {
+        set_error("%s: more than 64 * 65535 channels per group", who);
+        return BNN_E_RANGE;
+    }
+    return BNN_OK;
+}
+
+int bnn_conv3d_moments_backward_input(const float *g_m, const float *g_v, const float *mu_w, const float *s2_w, const float *a_m,
+                                      float *g_a_m, float *g_a_v, const bnn_conv3d_shape_t *shape, int compute, void *stream)
+{
+    const char *who = "bnn_conv3d_moments_backward_input";
+    Conv3dGeo g;
+    bool empty;
+    const int rc = momb_conv_geo(who, shape, compute, g, empty);
+    if (rc) return rc;
+    if (!g_m || !g_v || !mu_w || !s2_w || !a_m || !g_a_m) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if (!g_a_v) {
+        set_error("%s: NULL g_a_v (a deterministic input takes bnn_conv3d_lrt_backward_input with nsets = 1)", who);
+        return BNN_E_NULL;
+    }
+    if (mis4(g_m) || mis4(g_v) || mis4(mu_w) || mis4(s2_w) || mis4(a_m) || mis16(g_a_m) || mis16(g_a_v)) {
+        set_error("%s: misaligned pointer (g_a_m and g_a_v: 16 bytes)", who);
+        return BNN_E_ALIGN;
+    }
+    if (empty) return BNN_OK;
+    MomConvBwdArgs a{};
+    a.g1 = g_m; a.g2 = g_v; a.w1 = mu_w; a.w2 = s2_w; a.a_m = a_m; a.out = g_a_m; a.out2 = g_a_v;
+    const dim3 grid((unsigned)(((int64_t)g.B * g.Pin + C3_BM - 1) / C3_BM), (unsigned)((g.Cg + C3_BN - 1) / C3_BN), (unsigned)g.groups);
+    const dim3 block(C3_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_moments_conv3d_bwd<uint16_t, C3_DGRAD>), grid, block, 0, st, g, a);
+    else hipLaunchKernelGGL((k_moments_conv3d_bwd<float, C3_DGRAD>), grid, block, 0, st, g, a);
+    return check_launch(who);
+}
+
+int64_t bnn_conv3d_moments_wgrad_workspace(const bnn_conv3d_shape_t *shape)
+{
+    Conv3dGeo g;
+    bool empty;
+    if (momb_conv_geo("bnn_conv3d_moments_wgrad_workspace", shape, BNN_COMPUTE_F32, g, empty)) return -1;
+    int nslab, chunk;
+    wgrad_split(g, 1, nslab, chunk);
+    return (int64_t)nslab * 3 * g.O * g.K * (int64_t)sizeof(float);
+}
+
+int bnn_conv3d_moments_backward_weight(const float *a_m, const float *a_v, const float *g_m, const float *g_v, const float *mu_w,
+                                       const float *rho_w, float *g_mu_w, float *g_rho_w, const float *rho_b, float *g_mu_b,
+                                       float *g_rho_b, const bnn_conv3d_shape_t *shape, int compute, void *workspace,
+                                       int64_t workspace_bytes, void *stream)
+{
+    const char *who = "bnn_conv3d_moments_backward_weight";
+    Conv3dGeo g;
+    bool empty;
+    int rc = momb_conv_geo(who, shape, compute, g, empty);
+    if (rc) return rc;
+    const bool bias = rho_b || g_mu_b || g_rho_b;
+    if (!a_m || !g_m || !g_v || !mu_w || !rho_w || !g_mu_w || !g_rho_w || (bias && (!rho_b || !g_mu_b || !g_rho_b))) {
+        set_error("%s: NULL pointer (rho_b, g_mu_b and g_rho_b: all or none)", who);
+        return BNN_E_NULL;
+    }
+    if (!a_v) {
+        set_error("%s: NULL a_v (a deterministic input takes bnn_conv3d_lrt_backward_weight with nsets = 1)", who);
+        return BNN_E_NULL;
+    }
+    if (mis4(a_m) || mis4(a_v) || mis4(g_m) || mis4(g_v) || mis4(mu_w) || mis4(rho_w) || mis16(g_mu_w) || mis16(g_rho_w) ||
+        mis4(rho_b) || mis4(g_mu_b) || mis4(g_rho_b) || mis4(workspace)) {
+        set_error("%s: misaligned pointer (g_mu_w and g_rho_w: 16 bytes)", who);
+        return BNN_E_ALIGN;
+    }
+    int nslab, chunk;
+    wgrad_split(g, 1, nslab, chunk);
+    const int64_t n = (int64_t)g.O * g.K;
+    if (!workspace || workspace_bytes < (int64_t)nslab * 3 * n * (int64_t)sizeof(float)) {
+        set_error("%s: workspace of bnn_conv3d_moments_wgrad_workspace bytes needed", who);
+        return BNN_E_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (empty) nslab = 0;                         // no images: no slab is written, the reduce stores zeros
+    else {
+        MomConvBwdArgs a{};
+        a.a_m = a_m; a.a_v = a_v; a.g1 = g_m; a.g2 = g_v; a.out = static_cast<float *>(workspace);
+        a.nslab = nslab; a.chunk = chunk;
+        const dim3 grid((unsigned)((g.K + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN), (unsigned)(g.groups * nslab));
+        const dim3 block(C3_THREADS);
+        if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_moments_conv3d_bwd<uint16_t, C3_WGRAD>), grid, block, 0, st, g, a);
+        else hipLaunchKernelGGL((k_moments_conv3d_bwd<float, C3_WGRAD>), grid, block, 0, st, g, a);
+        if ((rc = check_launch(who))) return rc;
+    }
+    hipLaunchKernelGGL(k_moments_conv_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
+                       nslab, mu_w, rho_w, g_mu_w, g_rho_w, n);
+    if ((rc = check_launch(who)) || !bias) return rc;
+    hipLaunchKernelGGL(k_lrt_conv_bias_grad, dim3((unsigned)g.O), dim3(256), 0, st, g_m, g_v, (int64_t)(empty ? 0 : g.B), g.O, g.P, rho_b,
+                       g_mu_b, g_rho_b);
     return check_launch(who);
 }
 

@@ -1,6 +1,7 @@
 // bnn_moments_act.hpp -- moment-matched activations of a Gaussian pre-activation N(m, v): the device functions that the fused
 // epilogues (k_moments, bnn_moments.hip; k_moments_conv3d, bnn_conv3d.hip) and the standalone elementwise launches
-// (k_moments_relu, k_moments_elu) both call, so that fused and standalone agree bit for bit.
+// (k_moments_relu, k_moments_elu) both call, so that fused and standalone agree bit for bit; and their backwards
+// (k_moments_relu_bwd, k_moments_elu_bwd, bnn_moments_bwd.hip).
 #pragma once
 #include "bnn_device.hpp"
 
@@ -101,6 +102,49 @@ __device__ __forceinline__ void moments_elu_dev(float mf, float vf, float a_elu,
     const double n1 = e1 - cdc, n2 = e2 - 2.0 * e1 + cdc;
     om = (float)(p1 + a * n1);
     ov = (float)fmax(v * r + a * a * (n2 - n1 * n1) - 2.0 * a * p1 * n1, 0.0);
+}
+
+// Backward of moments_elu_dev (K19): (g_m, g_v) from the gradients (gm', gv') of its two outputs.  With d_m E f = E f' and
+// d_v E f = E f'' / 2 for f = elu and f = elu^2 (f' jumps by 1 - a at 0, where x has the density phi / s):
+//     d mean'/d m = Phi + a E_1                           d mean'/d v = (a E_1 + (1 - a) phi / s) / 2
+//     d var'/d m  = 2 P1 + 2 a^2 (E_2 - E_1) - 2 mean' (Phi + a E_1)
+//     d var'/d v  = Phi + a^2 (2 E_2 - E_1) - mean' (a E_1 + (1 - a) phi / s)
+// (a = 0: moments_relu_bwd_dev's).  For large negative alpha d var'/d m tends to 2 a^2 (E_2 - E_1^2) through a cancellation of
+// the forward's N2 - N1^2 kind: fp64, as the forward.  The forward keeps its own code (its bits and registers are pinned), so
+// the terms are evaluated again here, through the same X_k = erfcx loop.  Where the forward clamped var' (decided on the
+// forward's own sum) the gv' terms are absent.  v == 0 (and a NaN v) takes the limits, m == 0 on the positive side:
+//     g_m = gm' elu'(m),   g_v = gv' elu'(m)^2 + gm' a exp(m) [m < 0] / 2
+__device__ __forceinline__ void moments_elu_bwd_dev(float mf, float vf, float a_elu, float gom, float gov, float &gm, float &gv)
+{
+    const double m = (double)mf, v = (double)vf, a = (double)a_elu;
+    if (!(vf > 0.0f)) {
+        const double d = mf < 0.0f ? a * exp(m) : 1.0;
+        gm = (float)((double)gom * d);
+        gv = (float)((double)gov * d * d + (mf < 0.0f ? 0.5 * d * (double)gom : 0.0));
+        return;
+    }
+    const double s = sqrt(v), alpha = m / s;
+    double x0 = 0.0, x1 = 0.0, x2 = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k) {
+        x0 = x1;
+        x1 = x2;
+        x2 = erfcx(0.70710678118654752 * fabs(alpha + (double)k * s));
+    }
+    const double g = exp(-0.5 * alpha * alpha);
+    const double h0 = 0.5 * g * x0, h1 = 0.5 * g * x1, h2 = 0.5 * g * x2;
+    const double cdc = alpha >= 0.0 ? h0 : 1.0 - h0, cdf = alpha >= 0.0 ? 1.0 - h0 : h0;
+    const double pdf = 0.39894228040143268 * g;
+    const double e1 = alpha + s >= 0.0 ? h1 : exp(m + 0.5 * v) - h1;
+    const double e2 = alpha + 2.0 * s >= 0.0 ? h2 : exp(2.0 * (m + v)) - h2;
+    const double p1 = s * (alpha * cdf + pdf);
+    const double r = cdf + alpha * alpha * cdf * cdc + alpha * pdf * (cdc - cdf) - pdf * pdf;
+    const double n1 = e1 - cdc, n2 = e2 - 2.0 * e1 + cdc;
+    const double mean = p1 + a * n1;
+    const double go_v = v * r + a * a * (n2 - n1 * n1) - 2.0 * a * p1 * n1 < 0.0 ? 0.0 : (double)gov;
+    const double dm = cdf + a * e1, dv = a * e1 + (1.0 - a) * pdf / s;
+    gm = (float)((double)gom * dm + go_v * (2.0 * p1 + 2.0 * a * a * (e2 - e1) - 2.0 * mean * dm));
+    gv = (float)((double)gom * (0.5 * dv) + go_v * (cdf + a * a * (2.0 * e2 - e1) - mean * dv));
 }
 
 }  // namespace bnn

@@ -14,6 +14,8 @@
 // v_mfma_f32_16x16x4_f32.  No atomics, no split contraction: identical calls give identical bits.
 // A deterministic input (a_v NULL) has K10's backward: the host calls bnn_lrt_backward_input / _weight, there is no kernel here.
 // k_moments_relu_bwd: the backward of the moment-matched ReLU on the forward's own terms (bnn_moments_act.hpp).
+// k_moments_elu_bwd (K19): the same for the moment-matched ELU, in fp64 like its forward.  The conv layers' contraction backward is
+// k_moments_conv3d_bwd in bnn_conv3d.hip.
 #include "bnn_lrt_tile.hpp"
 #include "bnn_moments_act.hpp"
 
@@ -100,6 +102,18 @@ __global__ __launch_bounds__(256) void k_moments_relu_bwd(const float *m, const 
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
         float a, b;
         moments_relu_bwd_dev(m[t], v[t], gom[t], gov[t], a, b);
+        gm[t] = a;
+        gv[t] = b;
+    }
+}
+
+// the same for the moment-matched ELU (K19; moments_elu_bwd_dev evaluates in fp64, like the forward)
+__global__ __launch_bounds__(256) void k_moments_elu_bwd(const float *m, const float *v, const float *gom, const float *gov, float *gm,
+                                                         float *gv, int64_t n, float alpha)
+{
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
+        float a, b;
+        moments_elu_bwd_dev(m[t], v[t], alpha, gom[t], gov[t], a, b);
         gm[t] = a;
         gv[t] = b;
     }
@@ -202,6 +216,26 @@ int bnn_moments_relu_backward(const float *m, const float *v, const float *g_out
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_moments_relu_bwd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m, v, g_out_m, g_out_v, g_m, g_v, n);
+    return check_launch(who);
+}
+
+int bnn_moments_elu_backward(const float *m, const float *v, const float *g_out_m, const float *g_out_v, float *g_m, float *g_v,
+                             int64_t n, float alpha, void *stream)
+{
+    const char *who = "bnn_moments_elu_backward";
+    if (!m || !v || !g_out_m || !g_out_v || !g_m || !g_v) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
+    if (n < 0) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
+    if (!(alpha >= 0.0f) || alpha > 3.0e38f) { set_error("%s: alpha must be finite and >= 0", who); return BNN_E_RANGE; }
+    if (misaligned(m, 3) || misaligned(v, 3) || misaligned(g_out_m, 3) || misaligned(g_out_v, 3) || misaligned(g_m, 3) ||
+        misaligned(g_v, 3)) {
+        set_error("%s: misaligned pointer", who);
+        return BNN_E_ALIGN;
+    }
+    if (n == 0) return BNN_OK;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_moments_elu_bwd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m, v, g_out_m, g_out_v, g_m, g_v, n,
+                       alpha);
     return check_launch(who);
 }
 

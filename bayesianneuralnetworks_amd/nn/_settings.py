@@ -48,6 +48,25 @@ def keyed_mvn_enabled():
     return _keyed_mvn
 
 
+_conv_moment_training = False
+
+
+def conv_moment_training(enable=True):
+    """Opt-in (default off) for training conv nets without sampling (K19): with it on, BayesianNetworkModule.forward_moments also
+    admits NormalConv1d / 2d / 3d, LocalReparamConv1d / 2d / 3d, nn.MomentELU and nn.MomentLinear -- their moment layers keep the
+    autograd graph, and every backward launch is HIP (k_moments_conv3d_bwd, bnn_moments_elu_backward; K11's launches for a
+    deterministic input, K18's for MomentLinear).  With it off forward_moments refuses exactly what it refused before, with the
+    same messages.  Flipout, MC-dropout, multivariate-normal and evidential layers stay refused either way.  Making it the
+    default is a separate step: tests/test_moment_backward.py::test_forward_moments_refuses_what_has_no_backward pins the
+    refusal of NormalConv2d and MomentELU."""
+    global _conv_moment_training
+    _conv_moment_training = bool(enable)
+
+
+def conv_moment_training_enabled():
+    return _conv_moment_training
+
+
 def fuse_activations(module, bf16_activations=False, fuse_head=False):
     """Opt-in graph rewrite inside every torch.nn.Sequential:
 

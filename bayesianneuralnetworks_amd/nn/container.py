@@ -87,8 +87,10 @@ class MomentELU(torch.nn.ELU):
 
     def forward(self, x):
         from .. import ops
-        return _moment_twin_forward(self, torch.nn.ELU, x,
-                                    lambda mom: ops.moments_elu(mom, self.alpha) if mom.mean.is_cuda else ops.moments_elu_f64(mom, self.alpha))
+        ctx = _mc.moments_current()
+        track = ctx is not None and ctx.track                          # forward_moments: keep the graph
+        return _moment_twin_forward(self, torch.nn.ELU, x, lambda mom: ops.moments_elu(mom, self.alpha, track) if mom.mean.is_cuda
+                                    else ops.moments_elu_f64(mom, self.alpha, track))
 
 
 class MomentLinear(torch.nn.Linear):
@@ -102,9 +104,11 @@ class MomentLinear(torch.nn.Linear):
         from . import _settings
         if not isinstance(x, ops.Moments):
             return torch.nn.Linear.forward(self, x)
+        ctx = _mc.moments_current()
+        track = ctx is not None and ctx.track                          # forward_moments: keep the graph
         if not x.mean.is_cuda:
-            return ops.moments_affine_f64(x, self.weight, self.bias)
-        return ops.moments_affine(x, self.weight, self.bias, compute=_settings.get_compute())
+            return ops.moments_affine_f64(x, self.weight, self.bias, track)
+        return ops.moments_affine(x, self.weight, self.bias, compute=_settings.get_compute(), track=track)
 
 
 class MomentSoftmax(torch.nn.Softmax):
@@ -436,14 +440,24 @@ class BayesianNetworkModule(Module):
         (nn.fuse_activations) or rewritten to nn.MomentReLU (nn.moment_activations), reshapes, torch.nn.Identity, a closing
         nn.MomentSoftmax, deterministic modules in front of the first Bayesian layer.  The conv layers, nn.MomentELU,
         nn.MomentLinear and the Flipout / MC-dropout / multivariate-normal / evidential layers raise ops.BnnHipError.
+        With nn.conv_moment_training() switched on (K19) NormalConv1d / 2d / 3d, LocalReparamConv1d / 2d / 3d, nn.MomentELU and
+        nn.MomentLinear are admitted too: the conv backward is k_moments_conv3d_bwd (csrc/bnn_conv3d.hip; K11's launches for a
+        deterministic input), the ELU's bnn_moments_elu_backward, MomentLinear's K18's two launches; the other layers stay refused.
         Regression: mean(((y - mom.mean)^2 + mom.var) / (2 s^2)) needs no sample; classification: sample_moments."""
         from .. import ops
+        from . import _settings
         from .dense import NormalLinear, LocalReparamLinear
+        from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
+        convs_on = _settings.conv_moment_training_enabled()
+        admitted = (NormalLinear, LocalReparamLinear) + ((NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d,
+                                                           LocalReparamConv2d, LocalReparamConv3d) if convs_on else ())
         for m in self.modules():
-            if (isinstance(m, BayesianModule) and type(m) not in (NormalLinear, LocalReparamLinear)) or isinstance(m, (MomentELU, MomentLinear)):
+            if (isinstance(m, BayesianModule) and type(m) not in admitted) or (not convs_on and isinstance(m, (MomentELU, MomentLinear))):
                 raise ops.BnnHipError("forward_moments: %s has no moment backward; training without sampling supports "
                                       "NormalLinear / LocalReparamLinear, ReLU (folded, or nn.MomentReLU), reshaping modules, "
-                                      "torch.nn.Identity and a closing nn.MomentSoftmax" % type(m).__name__)
+                                      "torch.nn.Identity and a closing nn.MomentSoftmax%s" % (type(m).__name__, (
+                                          ", and (nn.conv_moment_training) NormalConv / LocalReparamConv 1d / 2d / 3d, nn.MomentELU "
+                                          "and nn.MomentLinear") if convs_on else ""))
         with _mc.MomentContext(track=True):
             try:
                 y = self._forward(x, *args, **kwargs)

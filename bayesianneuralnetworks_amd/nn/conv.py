@@ -60,7 +60,7 @@ def _conv_forward_moments(layer, x):
     (layer._moment_act; the twin module then passes the result through).  Device: ops.moments_convNd
     (bnn_conv3d_moments_forward, fp32 moments in both compute modes); CPU: the same recursion in float64
     (ops.moments_convNd_f64).  Nothing is drawn, no draw epoch is consumed, draw_key / noise_key stay as they are; the result
-    is detached (inference only)."""
+    is detached in an inference pass and keeps its autograd graph in a tracked one (BayesianNetworkModule.forward_moments, K19)."""
     mom = x if isinstance(x, ops.Moments) else ops.Moments(x, None)
     if not torch.is_tensor(mom.mean):
         raise TypeError("%s takes a tensor or ops.Moments in a moment pass, got %s" % (type(layer).__name__, type(x).__name__))
@@ -75,10 +75,12 @@ def _conv_forward_moments(layer, x):
     b = layer.bias is not None
     args = (layer.weight.mean, layer.weight.scale, layer.bias.mean if b else None, layer.bias.scale if b else None,
             layer.stride, layer.padding, layer.dilation, layer.groups)
+    ctx = _mc.moments_current()
+    track = ctx is not None and ctx.track                              # forward_moments: keep the graph (K19)
     if not mom.mean.is_cuda:
-        out = ops.moments_convNd_f64(mom, *args, activation=act)
+        out = ops.moments_convNd_f64(mom, *args, activation=act, track=track)
     else:
-        out = ops.moments_convNd(mom, *args, activation=act, compute=layer._compute_mode())
+        out = ops.moments_convNd(mom, *args, activation=act, compute=layer._compute_mode(), track=track)
     out._act = act
     return out
 

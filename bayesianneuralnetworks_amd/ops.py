@@ -1308,7 +1308,132 @@ def _moment_activation(activation, who):
     raise ValueError("%s: activation must be None, 'relu' or ('elu', alpha), got %r" % (who, activation))
 
 
-def moments_convNd(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, groups=1, activation=None, compute="f32"):
+class _MomentsConv(torch.autograd.Function):
+    """(m, v) of ops.moments_convNd's pre-activation with a backward (K19): a deterministic input (av None) takes K11's backward
+    launches (bnn_conv3d_lrt_backward_input / _weight with one image set and x = a_m), an input that carries a variance the
+    three-contraction ones of csrc/bnn_conv3d.hip (k_moments_conv3d_bwd).  am, av: (B, C, *spatial) fp32, contiguous; the
+    posterior tensors contiguous; sh: the bnn_conv3d_shape_t of the call, out_shape the output's."""
+
+    @staticmethod
+    def forward(ctx, am, av, mu_w, rho_w, mu_b, rho_b, sh, out_shape, code):
+        dev = am.device
+        s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
+        out_m = torch.empty(out_shape, dtype=torch.float32, device=dev)
+        out_v = torch.empty_like(out_m)
+        check(_lib.load().bnn_conv3d_moments_forward(ptr(am), ptr(av), ptr(mu_w), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(out_m),
+                                                     ptr(out_v), ctypes.byref(sh), code, 0, 0.0, stream_ptr(dev)),
+              "bnn_conv3d_moments_forward")
+        ctx.save_for_backward(am, av, mu_w, rho_w, rho_b if mu_b is not None else None, s2_w)
+        ctx.code, ctx.sh = code, sh
+        return out_m, out_v
+
+    @staticmethod
+    def backward(ctx, g_m, g_v):
+        am, av, mu_w, rho_w, rho_b, s2_w = ctx.saved_tensors
+        code, sh = ctx.code, ctx.sh
+        dev = am.device
+        lib, st = _lib.load(), stream_ptr(dev)
+        g_m, g_v = g_m.contiguous(), g_v.contiguous()
+        g_am = g_av = g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
+        if ctx.needs_input_grad[0] or (av is not None and ctx.needs_input_grad[1]):
+            g_am = torch.empty_like(am)
+            if av is None:
+                check(lib.bnn_conv3d_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(mu_w), ptr(s2_w), ptr(am), ptr(g_am), ctypes.byref(sh),
+                                                        1, code, st), "bnn_conv3d_lrt_backward_input")
+            else:
+                g_av = torch.empty_like(av)
+                check(lib.bnn_conv3d_moments_backward_input(ptr(g_m), ptr(g_v), ptr(mu_w), ptr(s2_w), ptr(am), ptr(g_am), ptr(g_av),
+                                                            ctypes.byref(sh), code, st), "bnn_conv3d_moments_backward_input")
+        need_b = rho_b is not None and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or need_b:
+            g_mu_w, g_rho_w = torch.empty_like(mu_w), torch.empty_like(rho_w)
+            if need_b:
+                g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
+            pb = ptr(rho_b) if need_b else None
+            if av is None:
+                nb = lib.bnn_conv3d_lrt_backward_weight_workspace_bytes(ctypes.byref(sh), 1)
+                ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)          # this call's own slabs
+                check(lib.bnn_conv3d_lrt_backward_weight(ptr(am), ptr(g_m), ptr(g_v), ptr(rho_w), ptr(g_mu_w), ptr(g_rho_w), pb,
+                                                         ptr(g_mu_b), ptr(g_rho_b), ctypes.byref(sh), 1, code, ptr(ws), nb, st),
+                      "bnn_conv3d_lrt_backward_weight")
+            else:
+                nb = lib.bnn_conv3d_moments_wgrad_workspace(ctypes.byref(sh))
+                ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)
+                check(lib.bnn_conv3d_moments_backward_weight(ptr(am), ptr(av), ptr(g_m), ptr(g_v), ptr(mu_w), ptr(rho_w), ptr(g_mu_w),
+                                                             ptr(g_rho_w), pb, ptr(g_mu_b), ptr(g_rho_b), ctypes.byref(sh), code,
+                                                             ptr(ws), nb, st), "bnn_conv3d_moments_backward_weight")
+        return g_am, g_av, g_mu_w, g_rho_w, g_mu_b, g_rho_b, None, None, None
+
+
+class _MomentsElu(torch.autograd.Function):
+    """bnn_moments_elu out of place with bnn_moments_elu_backward behind it; m, v fp32, contiguous."""
+
+    @staticmethod
+    def forward(ctx, m, v, alpha):
+        om, ov = torch.empty_like(m), torch.empty_like(v)
+        check(_lib.load().bnn_moments_elu(ptr(m), ptr(v), ptr(om), ptr(ov), m.numel(), alpha, stream_ptr(m.device)), "bnn_moments_elu")
+        ctx.save_for_backward(m, v)
+        ctx.alpha = alpha
+        return om, ov
+
+    @staticmethod
+    def backward(ctx, g_om, g_ov):
+        m, v = ctx.saved_tensors
+        g_om, g_ov = g_om.contiguous(), g_ov.contiguous()
+        g_m, g_v = torch.empty_like(m), torch.empty_like(v)
+        check(_lib.load().bnn_moments_elu_backward(ptr(m), ptr(v), ptr(g_om), ptr(g_ov), ptr(g_m), ptr(g_v), m.numel(), ctx.alpha,
+                                                   stream_ptr(m.device)), "bnn_moments_elu_backward")
+        return g_m, g_v, None
+
+
+class _MomentsAffine(torch.autograd.Function):
+    """ops.moments_affine on moments that carry a variance, with K18's two backward launches behind it: the input gradient with
+    the zero sigma^2 plane (g_a_m = G_m w, g_a_v = G_v w^2), the weight gradient with a zero rho whose g_rho_w is discarded
+    (g_w = G_m^T a_m + 2 w (.) G_v^T a_v; the bias sums ride along: g_b = sum G_m).  am, av (B, K), w (N, K), b (N) or None."""
+
+    @staticmethod
+    def forward(ctx, am, av, w, b, code):
+        B, K = am.shape
+        N = w.shape[0]
+        dev = am.device
+        z_w = torch.zeros_like(w)
+        z_b = None if b is None else torch.zeros_like(b)
+        out_m = torch.empty((B, N), dtype=torch.float32, device=dev)
+        out_v = torch.empty((B, N), dtype=torch.float32, device=dev)
+        check(_lib.load().bnn_moments_forward(ptr(am), ptr(av), K, ptr(w), ptr(z_w), ptr(b), ptr(z_b), ptr(out_m), ptr(out_v),
+                                              B, N, K, code, 0, stream_ptr(dev)), "bnn_moments_forward")
+        ctx.save_for_backward(am, av, w)
+        ctx.code, ctx.bias = code, b is not None
+        return out_m, out_v
+
+    @staticmethod
+    def backward(ctx, g_m, g_v):
+        am, av, w = ctx.saved_tensors
+        code = ctx.code
+        B, K = am.shape
+        N = w.shape[0]
+        dev = am.device
+        lib, st = _lib.load(), stream_ptr(dev)
+        g_m, g_v = g_m.contiguous(), g_v.contiguous()
+        g_am = g_av = g_w = g_b = None
+        zero = torch.zeros_like(w)                  # sigma^2 = 0 for the input gradient, rho = 0 for the weight gradient's chain
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            g_am, g_av = torch.empty_like(am), torch.empty_like(av)
+            check(lib.bnn_moments_backward_input(ptr(g_m), ptr(g_v), ptr(w), ptr(zero), ptr(am), K, ptr(g_am), ptr(g_av), B, N, K,
+                                                 code, 0, st), "bnn_moments_backward_input")
+        need_b = ctx.bias and ctx.needs_input_grad[3]
+        if ctx.needs_input_grad[2] or need_b:
+            g_w, scrap = torch.empty_like(w), torch.empty_like(w)
+            zb = sb = None
+            if need_b:
+                g_b = torch.empty(N, dtype=torch.float32, device=dev)
+                zb, sb = torch.zeros_like(g_b), torch.empty_like(g_b)
+            check(lib.bnn_moments_backward_weight(ptr(am), ptr(av), K, ptr(g_m), ptr(g_v), ptr(w), ptr(zero), ptr(g_w), ptr(scrap),
+                                                  ptr(zb), ptr(g_b), ptr(sb), B, N, K, code, 0, st), "bnn_moments_backward_weight")
+        return g_am, g_av, g_w, g_b, None
+
+
+def moments_convNd(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, groups=1, activation=None, compute="f32", track=False):
     """Mean and variance of a convolution's pre-activation for independent Gaussian weights, from the mean and variance of its
     input, elements independent (bnn_lrt_prepare + bnn_conv3d_moments_forward, csrc/bnn_conv3d.hip; the dimension is the
     weight's, 1-d and 2-d as unit depth / height) -> Moments, fp32 (B, O, *out_spatial):
@@ -1316,18 +1441,24 @@ def moments_convNd(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, group
         m = convNd(a_m, mu_w) + mu_b,    v = convNd(a_m^2, sigma_w^2) + convNd(a_v, mu_w^2 + sigma_w^2) + sigma_b^2
 
     a: a device tensor (B, C, *spatial) (a deterministic input: the second term is absent) or a Moments.  activation: None,
-    'relu' or ('elu', alpha) -- moments_relu / moments_elu in the launch's epilogue (the same bits).  Inference only: nothing is
-    drawn, no key is touched, the result is detached.  Raises BnnHipError for a call the kernel refuses: no torch fallback."""
+    'relu' or ('elu', alpha) -- moments_relu / moments_elu in the launch's epilogue (the same bits).  Nothing is drawn, no key is
+    touched.  track=False (inference): the result is detached whatever the grad mode.  track=True with grad mode on (training
+    without sampling, K19): the result is attached to the graph of `a` and the four posterior tensors; the backward is HIP
+    (k_moments_conv3d_bwd; K11's launches for a deterministic input), and an activation runs as its standalone launch behind the
+    contraction (one device function: the same bits), because its backward needs the pre-activation.  Raises BnnHipError for a
+    call the kernel refuses: no torch fallback."""
     who = "moments_convNd"
     mom = _as_moments(a, who)
     _refuse_link(mom, who)
     act, alpha = _moment_activation(activation, who)
     code = _compute_code(compute)
-    am = mom.mean.detach().contiguous()
-    av = None if mom.var is None else mom.var.detach().contiguous()
-    mu_w, rho_w = mu_w.detach().contiguous(), rho_w.detach().contiguous()
+    tracked = _tracking(track)
+    keep = (lambda t: t) if tracked else (lambda t: t.detach())
+    am = keep(mom.mean).contiguous()
+    av = None if mom.var is None else keep(mom.var).contiguous()
+    mu_w, rho_w = keep(mu_w).contiguous(), keep(rho_w).contiguous()
     if mu_b is not None:
-        mu_b, rho_b = mu_b.detach().contiguous(), rho_b.detach().contiguous()
+        mu_b, rho_b = keep(mu_b).contiguous(), keep(rho_b).contiguous()
     _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b)
     require_cuda_f32(am, "a.mean")
     if av is not None:
@@ -1341,6 +1472,13 @@ def moments_convNd(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, group
     sh, out3 = _conv3d_shape((B,) + img, w5, st, pd, dl, groups)
     out_sp = out3[3 - nd:]
     dev = am.device
+    if tracked:
+        m, v = _MomentsConv.apply(am, av, mu_w, rho_w, mu_b, rho_b, sh, (B, sh.O) + out_sp, code)
+        if act == 'relu':
+            m, v = _MomentsRelu.apply(m, v)
+        elif act == 'elu':
+            m, v = _MomentsElu.apply(m, v, alpha)
+        return Moments(m, v)
     s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
     out_m = torch.empty((B, sh.O) + out_sp, dtype=torch.float32, device=dev)
     out_v = torch.empty_like(out_m)
@@ -1351,21 +1489,25 @@ def moments_convNd(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, group
     return Moments(out_m, out_v)
 
 
-def moments_affine(a, w, b, compute="f32"):
+def moments_affine(a, w, b, compute="f32", track=False):
     """A DETERMINISTIC dense layer (torch.nn.Linear behind a Bayesian layer, as in the CIFAR10 example) in a moment pass:
     m = a_m w^T + b, v = a_v (w^2)^T -- exact for independent inputs.  It is bnn_moments_forward with sigma_w^2 = 0 (the planes
     w, 0, fma(w, w, 0)), so K16's tile, bounds and both compute modes apply; no operand launch.  a: a tensor or a Moments
-    (*rows, K); w (N, K); b (N) or None -> Moments, fp32 (*rows, N); a deterministic input stays one (var None).  Detached."""
+    (*rows, K); w (N, K); b (N) or None -> Moments, fp32 (*rows, N); a deterministic input stays one (var None).  track=False:
+    detached.  track=True with grad mode on: attached to `a`, w and b; the backward is K18's two launches (a zero sigma^2 plane
+    for the input gradient, a zero rho and a discarded g_rho for the weight gradient); a deterministic input is plain torch."""
     who = "moments_affine"
     mom = _as_moments(a, who)
     _refuse_link(mom, who)
-    w = w.detach().contiguous()
-    b = None if b is None else b.detach().contiguous()
+    tracked = _tracking(track)
+    keep = (lambda t: t) if tracked else (lambda t: t.detach())
+    w = keep(w).contiguous()
+    b = None if b is None else keep(b).contiguous()
     if mom.var is None:
-        return Moments(torch.nn.functional.linear(mom.mean.detach(), w, b), None)
+        return Moments(torch.nn.functional.linear(keep(mom.mean), w, b), None)
     code = _compute_code(compute)
     N, K = w.shape
-    am, av = mom.mean.detach(), mom.var.detach()
+    am, av = keep(mom.mean), keep(mom.var)
     if am.dim() < 1 or am.shape[-1] != K:
         raise BnnHipError("%s: input has %s features, weight expects %d" % (who, am.shape[-1] if am.dim() else "no", K))
     lead = tuple(am.shape[:-1])
@@ -1375,6 +1517,9 @@ def moments_affine(a, w, b, compute="f32"):
     B = am.shape[0]
     if B > 64 * 65535:
         raise BnnHipError("%s: %d rows (at most %d)" % (who, B, 64 * 65535))
+    if tracked:
+        m, v = _MomentsAffine.apply(am, av, w, b, code)
+        return Moments(m.reshape(lead + (N,)), v.reshape(lead + (N,)))
     dev = am.device
     z_w = torch.zeros_like(w)
     z_b = None if b is None else torch.zeros_like(b)
@@ -1385,42 +1530,40 @@ def moments_affine(a, w, b, compute="f32"):
     return Moments(out_m.reshape(lead + (N,)), out_v.reshape(lead + (N,)))
 
 
-def moments_affine_f64(a, w, b):
-    """moments_affine in float64 torch."""
+def moments_affine_f64(a, w, b, track=False):
+    """moments_affine in float64 torch.  track=True: not detached."""
     mom = _as_moments(a, "moments_affine_f64")
     _refuse_link(mom, "moments_affine_f64")
-    f64 = lambda t: t.detach().to(torch.float64)         # noqa: E731
+    f64 = _f64(track)
     m = torch.nn.functional.linear(f64(mom.mean), f64(w), None if b is None else f64(b))
     return Moments(m, None if mom.var is None else f64(mom.var) @ (f64(w) * f64(w)).t())
 
 
-def moments_elu(mom, alpha=1.0):
+def moments_elu(mom, alpha=1.0, track=False):
     """ELU of Gaussian activations by moment matching (bnn_moments_elu; the formulas are include/bnn_hip.h's, evaluated in fp64
-    on the device and rounded to fp32) -> Moments.  v == 0 gives (elu(m), 0).  A deterministic input (var None) stays one."""
+    on the device and rounded to fp32) -> Moments.  v == 0 gives (elu(m), 0).  A deterministic input (var None) stays one.
+    track=True with grad mode on: attached to the graph, the backward is bnn_moments_elu_backward (a deterministic input:
+    torch's elu)."""
     mom = _as_moments(mom, "moments_elu")
     _refuse_link(mom, "moments_elu")
     _, alpha = _moment_activation(('elu', alpha), "moments_elu")
+    tracked = _tracking(track)
+    keep = (lambda t: t) if tracked else (lambda t: t.detach())
     if mom.var is None:
-        return Moments(torch.nn.functional.elu(mom.mean.detach(), alpha), None)
-    m, v = mom.mean.detach().contiguous(), mom.var.detach().contiguous()
+        return Moments(torch.nn.functional.elu(keep(mom.mean), alpha), None)
+    m, v = keep(mom.mean).contiguous(), keep(mom.var).contiguous()
     require_cuda_f32(m, "mean")
     require_cuda_f32(v, "var")
+    if tracked:
+        return Moments(*_MomentsElu.apply(m, v, alpha))
     om, ov = torch.empty_like(m), torch.empty_like(v)
     check(_lib.load().bnn_moments_elu(ptr(m), ptr(v), ptr(om), ptr(ov), m.numel(), alpha, stream_ptr(m.device)), "bnn_moments_elu")
     return Moments(om, ov)
 
 
-def moments_elu_f64(mom, alpha=1.0):
-    """moments_elu in float64 torch: the closed form of include/bnn_hip.h (the variance as the ReLU part's, the negative part's
-    and their cross term; E_k through erfcx where alpha + k s >= 0, so that nothing overflows)."""
-    mom = _as_moments(mom, "moments_elu_f64")
-    a = float(alpha)
-    m = mom.mean.detach().to(torch.float64)
-    if mom.var is None:
-        return Moments(torch.nn.functional.elu(m, a), None)
-    v = mom.var.detach().to(torch.float64)
-    pos = v > 0
-    vs = torch.where(pos, v, torch.ones_like(v))
+def _elu_terms_f64(m, vs):
+    """The terms of the moment-matched ELU's closed form at float64 (m, vs), vs > 0: -> (s, alpha, Phi, Phi_c, phi, E_1, E_2, P1,
+    r), r the ReLU's variance bracket; E_k through erfcx where alpha + k s >= 0, so that nothing overflows."""
     s = torch.sqrt(vs)
     al = m / s
     r2 = math.sqrt(2.0)
@@ -1435,20 +1578,77 @@ def moments_elu_f64(mom, alpha=1.0):
 
     e1, e2 = e_k(1.0), e_k(2.0)
     p1 = s * (al * cdf + pdf)
+    return s, al, cdf, cdc, pdf, e1, e2, p1, cdf + al * al * cdf * cdc + al * pdf * (cdc - cdf) - pdf * pdf
+
+
+def moments_elu_f64(mom, alpha=1.0, track=False):
+    """moments_elu in float64 torch: the closed form of include/bnn_hip.h (the variance as the ReLU part's, the negative part's
+    and their cross term; E_k through erfcx where alpha + k s >= 0, so that nothing overflows).  track=True: not detached (plain
+    torch autograd; at v == 0 the gradient is the stated convention of moments_elu_backward_f64)."""
+    mom = _as_moments(mom, "moments_elu_f64")
+    a = float(alpha)
+    f64 = _f64(track)
+    m = f64(mom.mean)
+    if mom.var is None:
+        return Moments(torch.nn.functional.elu(m, a), None)
+    v = f64(mom.var)
+    pos = v > 0
+    vs = torch.where(pos, v, torch.ones_like(v))
+    s, al, cdf, cdc, pdf, e1, e2, p1, r = _elu_terms_f64(m, vs)
     n1, n2 = e1 - cdc, e2 - 2.0 * e1 + cdc
     mean = p1 + a * n1
-    var = (vs * (cdf + al * al * cdf * cdc + al * pdf * (cdc - cdf) - pdf * pdf) + a * a * (n2 - n1 * n1) - 2.0 * a * p1 * n1).clamp_min(0)
+    var = (vs * r + a * a * (n2 - n1 * n1) - 2.0 * a * p1 * n1).clamp_min(0)
+    if _tracking(track):
+        # the same values; v == 0 takes the limits: d mean'/d v = a exp(m) [m < 0] / 2, d var'/d v = elu'(m)^2, elu'(0) = 1
+        md = m.detach()
+        d = torch.where(md < 0, a * torch.exp(md.clamp_max(0)), torch.ones_like(md))
+        elu = torch.where(m < 0, a * torch.expm1(m.clamp_max(0)), m)
+        return Moments(torch.where(pos, mean, elu + v * torch.where(md < 0, 0.5 * d, torch.zeros_like(d))),
+                       torch.where(pos, var, v * d * d))
     return Moments(torch.where(pos, mean, torch.nn.functional.elu(m, a)), torch.where(pos, var, torch.zeros_like(v)))
 
 
-def moments_convNd_f64(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, groups=1, activation=None):
+def moments_elu_backward_f64(mom, g_mean, g_var, alpha=1.0):
+    """The backward of moments_elu in float64 torch, as a formula: (g_m, g_v) at the pre-activation `mom` from the gradients of
+    the two outputs.  In include/bnn_hip.h's symbols (a = alpha of the ELU, al = m / s, mean' the forward's mean):
+
+        d mean'/d m = Phi + a E_1                        d mean'/d v = (a E_1 + (1 - a) phi / s) / 2
+        d var'/d m  = 2 P1 + 2 a^2 (E_2 - E_1) - 2 mean' (Phi + a E_1)
+        d var'/d v  = Phi + a^2 (2 E_2 - E_1) - mean' (a E_1 + (1 - a) phi / s)
+
+    (d_m E f = E f', d_v E f = E f'' / 2; a = 0: moments_relu_backward_f64's).  Where the forward clamped var' to 0 the g_var
+    terms are 0; v == 0 takes the limits, g_m = g_mean elu'(m), g_v = g_var elu'(m)^2 + g_mean a exp(m) [m < 0] / 2 with
+    elu'(0) = 1; a deterministic input (var None) is plain ELU: (g_mean elu'(m), None)."""
+    mom = _as_moments(mom, "moments_elu_backward_f64")
+    a = float(alpha)
+    f64 = lambda t: t.detach().to(torch.float64)         # noqa: E731
+    m, g_mean = f64(mom.mean), f64(g_mean)
+    neg = m < 0
+    d = torch.where(neg, a * torch.exp(m.clamp_max(0)), torch.ones_like(m))
+    if mom.var is None:
+        return g_mean * d, None
+    v, g_var = f64(mom.var), f64(g_var)
+    pos = v > 0
+    vs = torch.where(pos, v, torch.ones_like(v))
+    s, al, cdf, cdc, pdf, e1, e2, p1, r = _elu_terms_f64(m, vs)
+    n1, n2 = e1 - cdc, e2 - 2.0 * e1 + cdc
+    mean = p1 + a * n1
+    gv = torch.where(vs * r + a * a * (n2 - n1 * n1) - 2.0 * a * p1 * n1 < 0, torch.zeros_like(g_var), g_var)
+    dm, dv = cdf + a * e1, a * e1 + (1.0 - a) * pdf / s
+    g_m = g_mean * dm + gv * (2.0 * p1 + 2.0 * a * a * (e2 - e1) - 2.0 * mean * dm)
+    g_v = g_mean * (0.5 * dv) + gv * (cdf + a * a * (2.0 * e2 - e1) - mean * dv)
+    zero = torch.zeros_like(m)
+    return torch.where(pos, g_m, g_mean * d), torch.where(pos, g_v, g_var * d * d + g_mean * torch.where(neg, 0.5 * d, zero))
+
+
+def moments_convNd_f64(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, groups=1, activation=None, track=False):
     """moments_convNd in float64 torch (two / three torch.nn.functional.convNd calls on the CPU; sigma = 1e-10 + softplus(rho))
-    -> Moments of float64 tensors."""
+    -> Moments of float64 tensors.  track=True: not detached (torch autograd through the convolutions and the activation)."""
     who = "moments_convNd_f64"
     mom = _as_moments(a, who)
     _refuse_link(mom, who)
     act, alpha = _moment_activation(activation, who)
-    f64 = lambda t: t.detach().to(torch.float64)         # noqa: E731
+    f64 = _f64(track)
     sig2 = lambda rho: (1e-10 + torch.nn.functional.softplus(f64(rho))) ** 2         # noqa: E731
     nd = mu_w.dim() - 2
     if nd not in (1, 2, 3):
@@ -1462,8 +1662,8 @@ def moments_convNd_f64(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, g
         v = v + conv(f64(mom.var), mu * mu + s2, None, *geo)
     out = Moments(m, v)
     if act == 'relu':
-        return moments_relu_f64(out)
-    return moments_elu_f64(out, alpha) if act == 'elu' else out
+        return moments_relu_f64(out, track)
+    return moments_elu_f64(out, alpha, track) if act == 'elu' else out
 
 
 class _PlainLinear(torch.autograd.Function):

@@ -1203,6 +1203,46 @@ int bnn_moments_backward_weight(const float *a_m, const float *a_v, int64_t lda,
 int bnn_moments_relu_backward(const float *m, const float *v, const float *g_out_m, const float *g_out_v, float *g_m, float *g_v,
                               int64_t n, void *stream);
 
+/* ---- K19: training conv nets without sampling, the backward of K17's contraction and of the moment-matched ELU
+ * (csrc/bnn_conv3d.hip, csrc/bnn_moments_bwd.hip; ops.moments_convNd(track=True), ops.moments_elu(track=True)).  With G_m, G_v the
+ * (B, O, OD, OH, OW) gradients with respect to m and v of bnn_conv3d_moments_forward, convT the transposed contraction and the
+ * sums over (image, position) in that order, for an input that carries a variance:
+ *     g_a_m  = convT(G_m, mu_w) + 2 a_m (.) convT(G_v, sigma_w^2)        g_a_v  = convT(G_v, mu_w^2 + sigma_w^2)
+ *     g_mu_w = sum gather(a_m) G_m + 2 mu_w (.) sum gather(a_v) G_v       g_s2_w = sum gather(a_m^2 + a_v) G_v
+ *     g_rho_w = g_s2_w 2 sigma_w sigmoid(rho_w)              g_mu_b = sum G_m,  g_rho_b = (sum G_v) 2 sigma_b sigmoid(rho_b)
+ * K18's planes and three accumulator sets on K11's backward tile (128 x 64 x 32, gather and transposed-weight address
+ * arithmetic, groups in the grid, 1-d / 2-d layers as unit axes); the derived plane fma(p1, p1, p2) is formed in fp32 before any
+ * rounding.  compute: BNN_COMPUTE_F32 = v_mfma_f32_16x16x4_f32; BNN_COMPUTE_BF16 = the planes rounded to bf16 (RNE) into LDS,
+ * v_mfma_f32_16x16x32_bf16, fp32 accumulate.  The weight gradient splits (image, position) into slabs [slab][3][O][K] in the
+ * workspace (bnn_conv3d_moments_wgrad_workspace bytes, the call's own) and a second launch adds them in slab order; the bias sums
+ * are K11's launch.  No atomics, fixed order: identical calls give identical bits.  A deterministic input (no a_v) has K11's
+ * backward: call bnn_conv3d_lrt_backward_input / bnn_conv3d_lrt_backward_weight with nsets = 1 and x = a_m.
+ * Every operand and gradient is fp32 and dense: a_m, a_v, g_a_m, g_a_v (B, C, D, H, W); mu_w, s2_w, rho_w, g_mu_w, g_rho_w
+ * (O, C / groups, KD, KH, KW); rho_b, g_mu_b, g_rho_b (O), all given or all NULL.  Graph-capturable; errors are returned before
+ * anything is launched: BNN_E_NULL (a pointer, the shape, part of a bias; a NULL a_v / g_a_v names K11's entry), BNN_E_SHAPE,
+ * BNN_E_DTYPE (compute), BNN_E_RANGE (bnn_conv3d_moments_forward's ranges; more than 64 * 65535 channels per group),
+ * BNN_E_UNSUPPORTED (a workspace that is NULL or too small), BNN_E_ALIGN (element; 16 bytes for the contraction outputs g_a_m,
+ * g_a_v, g_mu_w, g_rho_w).  shape->B == 0: bnn_conv3d_moments_backward_input returns BNN_OK after the checks, the weight and
+ * bias gradients are stored as zeros. */
+int bnn_conv3d_moments_backward_input(const float *g_m, const float *g_v, const float *mu_w, const float *s2_w, const float *a_m,
+                                      float *g_a_m, float *g_a_v, const bnn_conv3d_shape_t *shape, int compute, void *stream);
+/* Bytes of workspace bnn_conv3d_moments_backward_weight needs for this shape, or -1 for a shape it refuses. */
+int64_t bnn_conv3d_moments_wgrad_workspace(const bnn_conv3d_shape_t *shape);
+int bnn_conv3d_moments_backward_weight(const float *a_m, const float *a_v, const float *g_m, const float *g_v, const float *mu_w,
+                                       const float *rho_w, float *g_mu_w, float *g_rho_w, const float *rho_b, float *g_mu_b,
+                                       float *g_rho_b, const bnn_conv3d_shape_t *shape, int compute, void *workspace,
+                                       int64_t workspace_bytes, void *stream);
+/* Backward of bnn_moments_elu at the pre-activation (m, v), v > 0, in that entry's symbols (mean' its first result):
+ *     d mean'/d m = Phi + alpha E_1                    d mean'/d v = (alpha E_1 + (1 - alpha) phi / s) / 2
+ *     d var'/d m  = 2 P1 + 2 alpha^2 (E_2 - E_1) - 2 mean' (Phi + alpha E_1)
+ *     d var'/d v  = Phi + alpha^2 (2 E_2 - E_1) - mean' (alpha E_1 + (1 - alpha) phi / s)
+ * (g_m, g_v) = the two columns applied to (g_out_m, g_out_v); fp64 on fp32 inputs, rounded to fp32 at the end.  Where the forward
+ * clamped var' to 0 the g_out_v terms are absent.  v == 0: g_m = g_out_m elu'(m), g_v = g_out_v elu'(m)^2 + g_out_m alpha exp(m)
+ * [m < 0] / 2, with elu'(0) = 1.  n elements; g_m / g_v may be g_out_m / g_out_v.  Errors: BNN_E_NULL, BNN_E_SHAPE (n < 0),
+ * BNN_E_RANGE (alpha negative or not finite), BNN_E_ALIGN. */
+int bnn_moments_elu_backward(const float *m, const float *v, const float *g_out_m, const float *g_out_v, float *g_m, float *g_v,
+                             int64_t n, float alpha, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
