@@ -1,15 +1,12 @@
-// bnn_conv3d.hip -- NormalConv3d (pytorch_bayesian/nn/conv.py:122-142) on drawn weights as implicit GEMMs, forward and backward.
+// bnn_conv3d.hip -- NormalConv3d (pytorch_bayesian/nn/conv.py:122-142) on drawn weights as implicit GEMMs, forward and backward,
+// and the conv kernels that reuse its tile: Flipout (K9), local reparameterization (K11), moment propagation (K17, K19).
 //
-// One tile skeleton serves the three contractions (C[m][n] = sum_r A(m, r) B(n, r), 128 x 64 x 32 tiles, 4 waves of 64 x 32):
-//   FWD   m = (b, od, oh, ow), n = o,        r = (c, kd, kh, kw): A gathered from x (im2col in the loader's address arithmetic,
-//         padding reads zero), B = the sample's drawn weight row.  Epilogue: + drawn bias, fp32 NCDHW store.
-//   DGRAD m = (b, id, ih, iw), n = c,        r = (o, kd, kh, kw): A gathered from gy (taps no stride step reaches read zero),
-//         B = the same weights read transposed.  A shared input sums its S samples inside the reduction loop, in sample order.
-//   WGRAD m = (c, kd, kh, kw), n = o,        r = (b, od, oh, ow): A = the forward's gather of x, B = gy.  The long reduction is
-//         split into slabs (gridDim.z); k_conv3d_slab_sum adds the slabs in slab order.
-// bf16 compute: operands rounded to bf16 as they are written to LDS, v_mfma_f32_16x16x32_bf16.  fp32: v_mfma_f32_16x16x4_f32, the
-// reduction a k-ordered fp32 fma chain per tile.  Every sum is in a fixed order and there are no atomics: two identical calls
-// give identical bits.  Indices inside one sample are 32-bit (the host refuses a per-sample tensor of 2^31 elements or more).
+// The tile -- the three contractions FWD / DGRAD / WGRAD, their gathers, the MFMA blocks, the prefetch loop, the epilogue's
+// lane map -- is bnn_conv3d_tile.hpp; a kernel here says which tensors its LDS planes are and what its epilogue computes.
+// K7 (k_conv3d): A = the gather, B = the sample's drawn weight row (FWD, DGRAD) or gy (WGRAD).  FWD adds the drawn bias; DGRAD
+// with a shared input sums its S samples inside the reduction loop, in sample order; WGRAD's slabs (gridDim.z) are added in
+// slab order by k_conv3d_slab_sum.  Every sum is in a fixed order and there are no atomics: two identical calls give identical
+// bits.  The host refuses a per-sample tensor of 2^31 elements or more.
 //
 // FLIP (FlipOutNormalConv3d, pytorch_bayesian/nn/conv.py:237-251, groups == 1): every tile runs TWO contractions on one pass over
 // the gathers -- the mean weights, and the stddev weights with the per-example signs applied as the second copy of an operand is
@@ -19,38 +16,12 @@
 //   DGRAD A2 = gy (.) R_s[b][o]; at the end of each sample acc += S_s[b][c] acc2, acc2 = 0 (a shared input: in sample order).
 //   WGRAD A2 = x (.) S_s[b][c], B2 = gy (.) R_s[b][o]; both partials to slabs [slab][s][mean | stddev][O][K], then
 //         k_conv3d_flip_wsum adds slabs and samples in a fixed order and applies softplus'.
-#include "bnn_device.hpp"
+#include "bnn_conv3d_tile.hpp"
 #include "bnn_moments_act.hpp"
 
 #include <algorithm>
 
 namespace bnn {
-
-constexpr int C3_BM = 128, C3_BN = 64, C3_BK = 32, C3_THREADS = 256;
-enum { C3_FWD = 0, C3_DGRAD = 1, C3_WGRAD = 2 };
-
-// n / d for n < 2^31 by multiply-high and shift (d >= 1)
-struct FastDiv { uint32_t d, mul, shift; };
-
-static FastDiv make_div(uint32_t d)
-{
-    FastDiv f;
-    f.d = d;
-    uint32_t s = 0;
-    while (s < 32 && (1ull << s) < d) ++s;
-    f.shift = s;
-    f.mul = (uint32_t)(((1ull << 32) * ((1ull << s) - d)) / d + 1);
-    return f;
-}
-
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv &f) { return (__umulhi(n, f.mul) + n) >> f.shift; }
-
-struct Conv3dGeo {
-    int32_t B, C, D, H, W, O, KD, KH, KW, OD, OH, OW;
-    int32_t sd, sh, sw, pd, ph, pw, dd, dh, dw, groups, Cg, Ng;
-    int32_t T, K, P, Pin;                    // taps, Cg * taps, OD OH OW, D H W
-    FastDiv fOW, fOH, fP, fW, fH, fPin, fKW, fKH, fT, fsd, fsh, fsw;
-};
 
 struct Conv3dArgs {
     const float *x; int64_t x_ss;            // fp32 NCDHW, sample stride (0: shared)
@@ -63,22 +34,6 @@ struct Conv3dArgs {
     int64_t w_std;                           // FLIP: element offset of the stddev row in w
 };
 
-template <typename T> struct Op;
-template <> struct Op<float> {
-    static constexpr int LDK = C3_BK + 4;
-    __device__ static float ld(const void *p, int64_t i) { return static_cast<const float *>(p)[i]; }
-};
-template <> struct Op<uint16_t> {
-    static constexpr int LDK = C3_BK + 8;    // 80-B rows: the 16-B fragment reads stay aligned
-    __device__ static float ld(const void *p, int64_t i)
-    {
-        return __uint_as_float((uint32_t)static_cast<const uint16_t *>(p)[i] << 16);
-    }
-};
-
-__device__ __forceinline__ void st_lds(float *p, float v) { *p = v; }
-__device__ __forceinline__ void st_lds(uint16_t *p, float v) { *p = f2bf(v); }
-
 template <typename T, int MODE, bool FLIP = false>
 __global__ __launch_bounds__(C3_THREADS) void k_conv3d(const Conv3dGeo g, const Conv3dArgs a)
 {
@@ -88,273 +43,103 @@ __global__ __launch_bounds__(C3_THREADS) void k_conv3d(const Conv3dGeo g, const 
     __shared__ __attribute__((aligned(16))) T Bs[NT * C3_BN * LDK];
     const int32_t OC = g.O + g.C;            // FLIP: one example's signs
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave & 1, wn = wave >> 1;
-
-    // the block's (sample, group, slab)
-    int z = blockIdx.z, slab = 0;
-    if (MODE == C3_WGRAD) { slab = z % a.nslab; z /= a.nslab; }
-    const int grp = z % g.groups;
-    const int s = z / g.groups;              // DGRAD with a shared input: 0 (the samples are summed below)
-
-    const int32_t M = MODE == C3_FWD ? g.B * g.P : MODE == C3_DGRAD ? g.B * g.Pin : g.K;
-    const int32_t N = MODE == C3_DGRAD ? g.Cg : g.Ng;
-    const int32_t m0 = blockIdx.x * C3_BM, n0 = blockIdx.y * C3_BN;
-    int32_t rbeg = 0, rend = MODE == C3_FWD ? g.K : MODE == C3_DGRAD ? g.Ng * g.T : g.B * g.P;
-    if (MODE == C3_WGRAD) {
-        rbeg = slab * a.chunk;
-        rend = min(rend, rbeg + a.chunk);
-    }
+    const C3Tile t = c3_tile();
+    const C3Block k = c3_block<MODE>(g, a.nslab);
+    const int s = k.s, grp = k.grp;          // s: DGRAD with a shared input: 0 (the samples are summed in the loop)
+    const C3Extents e = c3_extents<MODE>(g, k.slab, a.chunk);
     const int nsum = (MODE == C3_DGRAD && a.shared) ? a.S : 1;
+    const C3Row row = c3_row_origin<MODE>(g, t.m0 + t.ar, e.M, grp);
+    // FLIP: the row's signs -- FWD S_s[b][.], DGRAD R_s[b][.] (indexed by the reduction's channel), WGRAD S_s[.][c] (by its image)
+    const int32_t arow_sg = MODE == C3_FWD ? row.idx * OC + g.O : MODE == C3_DGRAD ? row.idx * OC : g.O + row.idx;
 
-    // ---- A loader: row ar of the tile, reduction offsets ah * 16 .. + 15 of each k-tile
-    const int ar = tid & (C3_BM - 1);
-    const int ah = __builtin_amdgcn_readfirstlane(tid >> 7);
-    const int32_t am = m0 + ar;
-    const bool arow = am < M;
-    int32_t abase = 0, z0 = 0, z1 = 0, z2 = 0;   // FWD / DGRAD: gather origin of the row; WGRAD: its tap
-    int32_t arow_sg = 0;                          // FLIP: FWD / DGRAD the row's example b (O + C); WGRAD O + the row's channel
-    if (MODE == C3_FWD && arow) {
-        const uint32_t b = fdiv(am, g.fP), p = am - b * g.P;
-        arow_sg = (int32_t)b * OC + g.O;
-        const uint32_t q = fdiv(p, g.fOW), ow = p - q * g.OW, od = fdiv(q, g.fOH), oh = q - od * g.OH;
-        z0 = od * g.sd - g.pd; z1 = oh * g.sh - g.ph; z2 = ow * g.sw - g.pw;
-        abase = (b * g.C + grp * g.Cg) * g.Pin;
-    } else if (MODE == C3_DGRAD && arow) {
-        const uint32_t b = fdiv(am, g.fPin), p = am - b * g.Pin;
-        const uint32_t q = fdiv(p, g.fW), iw = p - q * g.W, id = fdiv(q, g.fH), ih = q - id * g.H;
-        arow_sg = (int32_t)b * OC;
-        z0 = id + g.pd; z1 = ih + g.ph; z2 = iw + g.pw;
-        abase = (b * g.O + grp * g.Ng) * g.P;
-    } else if (MODE == C3_WGRAD && arow) {
-        const uint32_t c = fdiv(am, g.fT), t = am - c * g.T;
-        const uint32_t q = fdiv(t, g.fKW), kw = t - q * g.KW, kd = fdiv(q, g.fKH), kh = q - kd * g.KH;
-        arow_sg = g.O + (int32_t)c;
-        z0 = kd * g.dd - g.pd; z1 = kh * g.dh - g.ph; z2 = kw * g.dw - g.pw;
-        abase = (grp * g.Cg + c) * g.Pin;
-    }
-
-    auto fetch_a = [&](int sm, int32_t r0, float (&v)[16], float (&sa)[16]) {
-        int32_t r = r0 + ah * 16;
+    float va[16], sa[16], vb[8], vb2[8];          // sa, vb2: FLIP only (dead otherwise)
+    auto fetch = [&](int sm, int32_t r0) {
         const float *sgs = FLIP ? a.sg + (int64_t)(s + sm) * a.sg_ss + arow_sg : nullptr;
-        if (MODE == C3_WGRAD) {
-            // reduction index = output position (b, od, oh, ow), stepped with carries
+        if constexpr (MODE == C3_WGRAD) {
             const float *x = a.x + (int64_t)s * a.x_ss;
-            uint32_t b = 0, od = 0, oh = 0, ow = 0;
-            if (r < rend) {
-                b = fdiv(r, g.fP);
-                const uint32_t p = r - b * g.P, q = fdiv(p, g.fOW);
-                ow = p - q * g.OW; od = fdiv(q, g.fOH); oh = q - od * g.OH;
-            }
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int32_t id = (int32_t)(od * g.sd) + z0, ih = (int32_t)(oh * g.sh) + z1, iw = (int32_t)(ow * g.sw) + z2;
-                const bool ok = arow && r + j < rend && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H &&
-                                (uint32_t)iw < (uint32_t)g.W;
-                v[j] = ok ? x[(int64_t)b * g.C * g.Pin + abase + (id * g.H + ih) * g.W + iw] : 0.f;
+            c3_gather_positions(g, row, r0 + t.ah * 16, e.rend, [&](int j, bool ok, int64_t off, uint32_t b) {
+                va[j] = ok ? x[off] : 0.f;
                 if constexpr (FLIP) sa[j] = ok ? sgs[(int32_t)b * OC] : 0.f;
-                if (++ow == (uint32_t)g.OW) { ow = 0; if (++oh == (uint32_t)g.OH) { oh = 0; if (++od == (uint32_t)g.OD) { od = 0; ++b; } } }
-            }
-            return;
-        }
-        // reduction index = (channel, kd, kh, kw), stepped with carries
-        const float *src = MODE == C3_FWD ? a.x + (int64_t)s * a.x_ss : a.gy + (int64_t)(s + sm) * g.B * g.O * g.P;
-        uint32_t c = 0, kd = 0, kh = 0, kw = 0;
-        if (r < rend) {
-            c = fdiv(r, g.fT);
-            const uint32_t t = r - c * g.T, q = fdiv(t, g.fKW);
-            kw = t - q * g.KW; kd = fdiv(q, g.fKH); kh = q - kd * g.KH;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            bool ok = arow && r + j < rend;
-            int32_t off = 0;
-            if (MODE == C3_FWD) {
-                const int32_t id = z0 + (int32_t)kd * g.dd, ih = z1 + (int32_t)kh * g.dh, iw = z2 + (int32_t)kw * g.dw;
-                ok = ok && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H && (uint32_t)iw < (uint32_t)g.W;
-                off = (int32_t)c * g.Pin + (id * g.H + ih) * g.W + iw;
-            } else {
-                const int32_t nd = z0 - (int32_t)kd * g.dd, nh = z1 - (int32_t)kh * g.dh, nw = z2 - (int32_t)kw * g.dw;
-                ok = ok && nd >= 0 && nh >= 0 && nw >= 0;
-                const uint32_t od = fdiv(ok ? nd : 0, g.fsd), oh = fdiv(ok ? nh : 0, g.fsh), ow = fdiv(ok ? nw : 0, g.fsw);
-                ok = ok && (int32_t)(od * g.sd) == nd && (int32_t)(oh * g.sh) == nh && (int32_t)(ow * g.sw) == nw &&
-                     od < (uint32_t)g.OD && oh < (uint32_t)g.OH && ow < (uint32_t)g.OW;
-                off = (int32_t)c * g.P + (int32_t)((od * g.OH + oh) * g.OW + ow);
-            }
-            v[j] = ok ? src[abase + off] : 0.f;
-            if constexpr (FLIP) sa[j] = ok ? sgs[c] : 0.f;
-            if (++kw == (uint32_t)g.KW) { kw = 0; if (++kh == (uint32_t)g.KH) { kh = 0; if (++kd == (uint32_t)g.KD) { kd = 0; ++c; } } }
+            });
+            const float *gy = a.gy + (int64_t)s * g.B * g.O * g.P;
+            const float *rs = FLIP ? a.sg + (int64_t)s * a.sg_ss : nullptr;
+            c3_grad_rows(g, t, e.N, grp, r0 + t.bk, e.rend, [&](int i, bool ok, int64_t off, uint32_t b, int32_t n) {
+                vb[i] = ok ? gy[off] : 0.f;
+                if constexpr (FLIP) vb2[i] = ok ? vb[i] * rs[(int64_t)b * OC + n] : 0.f;
+            });
+        } else {
+            const float *src = MODE == C3_FWD ? a.x + (int64_t)s * a.x_ss : a.gy + (int64_t)(s + sm) * g.B * g.O * g.P;
+            c3_gather_taps<MODE>(g, row, r0 + t.ah * 16, e.rend, [&](int j, bool ok, int32_t off, uint32_t c) {
+                va[j] = ok ? src[off] : 0.f;
+                if constexpr (FLIP) sa[j] = ok ? sgs[c] : 0.f;
+            });
+            const int64_t ws = (int64_t)(s + sm) * a.w_ss;
+            c3_weight_rows<MODE>(g, t, e.N, grp, r0 + t.bk, e.rend, [&](int i, bool ok, int64_t off) {
+                vb[i] = ok ? Op<T>::ld(a.w, ws + off) : 0.f;
+                if constexpr (FLIP) vb2[i] = ok ? Op<T>::ld(a.w, a.w_std + ws + off) : 0.f;
+            });
         }
     };
 
-    // ---- B loader: reduction offset bk of each k-tile, rows bn + 8 i of the tile
-    const int bk = tid & (C3_BK - 1), bn = tid >> 5;
-    auto fetch_b = [&](int sm, int32_t r0, float (&v)[8], float (&v2)[8]) {
-        const int32_t r = r0 + bk;
-        const bool rok = r < rend;
-        if (MODE == C3_WGRAD) {
-            uint32_t b = 0, p = 0;
-            if (rok) { b = fdiv(r, g.fP); p = r - b * g.P; }
-            const float *gy = a.gy + ((int64_t)s * g.B + b) * g.O * g.P + (int64_t)grp * g.Ng * g.P + p;
-            const float *rs = FLIP ? a.sg + (int64_t)s * a.sg_ss + (int64_t)b * OC : nullptr;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int32_t n = n0 + bn + 8 * i;
-                v[i] = (rok && n < N) ? gy[(int64_t)n * g.P] : 0.f;
-                if constexpr (FLIP) v2[i] = (rok && n < N) ? v[i] * rs[n] : 0.f;
-            }
-            return;
-        }
-        const int64_t wb = (int64_t)(s + sm) * a.w_ss + (int64_t)grp * g.Ng * g.K;
-        int32_t roff = r;                               // FWD: w[o][r]
-        int32_t nstride = g.K;
-        if (MODE == C3_DGRAD) {                         // r = (o, tap): w[o][c][tap]
-            const uint32_t o = fdiv(rok ? r : 0, g.fT);
-            roff = (int32_t)(o * g.K + (r - o * g.T));
-            nstride = g.T;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int32_t n = n0 + bn + 8 * i;
-            v[i] = (rok && n < N) ? Op<T>::ld(a.w, wb + (int64_t)n * nstride + roff) : 0.f;
-            if constexpr (FLIP) v2[i] = (rok && n < N) ? Op<T>::ld(a.w, a.w_std + wb + (int64_t)n * nstride + roff) : 0.f;
-        }
-    };
-
-    auto store_tiles = [&](const float (&va)[16], const float (&sa)[16], const float (&vb)[8], const float (&vb2)[8]) {
-        T *pa = As + ar * LDK + ah * 16;
+    auto store = [&]() {
+        T *pa = c3_lds_a(As, t), *pb = c3_lds_b(Bs, t);
 #pragma unroll
         for (int j = 0; j < 16; ++j) st_lds(pa + j, va[j]);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) st_lds(Bs + (bn + 8 * i) * LDK + bk, vb[i]);
+        for (int i = 0; i < 8; ++i) st_lds(pb + 8 * i * LDK, vb[i]);
         if constexpr (FLIP) {
-            T *pa2 = pa + C3_BM * LDK;
 #pragma unroll
-            for (int j = 0; j < 16; ++j) st_lds(pa2 + j, va[j] * sa[j]);          // x +-1: exact, then rounded as the plain copy
+            for (int j = 0; j < 16; ++j) st_lds(pa + C3_BM * LDK + j, va[j] * sa[j]);   // x +-1: exact, then rounded as the plain copy
 #pragma unroll
-            for (int i = 0; i < 8; ++i) st_lds(Bs + (C3_BN + bn + 8 * i) * LDK + bk, vb2[i]);
+            for (int i = 0; i < 8; ++i) st_lds(pb + (C3_BN + 8 * i) * LDK, vb2[i]);
         }
     };
 
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc[NT][4][2];
-#pragma unroll
-    for (int h = 0; h < NT; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    c3_zero(acc);
+    auto compute = [&]() { c3_mfma_planes<T, NT, NT>(acc, As, Bs, t); };
 
-    // FLIP DGRAD: acc += S_smp[b][c] acc2 at the end of sample smp's reduction (lane rows m, columns n = c as in the epilogue)
-    auto fold = [&](int smp) {
-        const float *sgs = a.sg + (int64_t)smp * a.sg_ss + g.O;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int32_t m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + q;
-                    const bool ok = m < M && n < N;
-                    const float sgn = ok ? sgs[(int32_t)fdiv(ok ? m : 0, g.fPin) * OC + n] : 0.f;
+    if constexpr (FLIP && MODE == C3_DGRAD) {
+        // acc += S_smp[b][c] acc2 at the end of sample smp's reduction (lane rows m, columns n = c as in the epilogue); the
+        // elements outside (M, N) hold zeros in both sets
+        auto fold = [&](int sm) {
+            const float *sgs = a.sg + (int64_t)(s + sm) * a.sg_ss + g.O;
+            c3_each_col(t, e.N, [&](int j, int32_t n) {
+                c3_each_row(t, e.M, [&](int i, int q, int32_t m) {
+                    const float sgn = sgs[(int32_t)fdiv(m, g.fPin) * OC + n];
                     acc[0][i][j][q] = __builtin_fmaf(sgn, acc[NT - 1][i][j][q], acc[0][i][j][q]);
                     acc[NT - 1][i][j][q] = 0.f;
-                }
-        }
-    };
-
-    const int ntile = rend > rbeg ? (rend - rbeg + C3_BK - 1) / C3_BK : 0;
-    const int nstep = nsum * ntile;
-    float va[16], sa[16], vb[8], vb2[8];          // sa, vb2: FLIP only (dead otherwise)
-    if (nstep > 0) { fetch_a(0, rbeg, va, sa); fetch_b(0, rbeg, vb, vb2); }
-    for (int step = 0; step < nstep; ++step) {
-        __syncthreads();                                // the previous tile's fragment reads are done
-        store_tiles(va, sa, vb, vb2);
-        __syncthreads();
-        if (step + 1 < nstep) {                         // the next tile's loads fly under this tile's MFMAs
-            const int nx = step + 1, sm = nx / ntile;
-            const int32_t r0 = rbeg + (nx - sm * ntile) * C3_BK;
-            fetch_a(sm, r0, va, sa);
-            fetch_b(sm, r0, vb, vb2);
-        }
-        if constexpr (sizeof(T) == 2) {
-            typedef short s16x8 __attribute__((ext_vector_type(8)));
-#pragma unroll
-            for (int h = 0; h < NT; ++h) {
-                const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
-                s16x8 fa[4], fb[2];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    fa[i] = *reinterpret_cast<const s16x8 *>(A + (wm * 64 + i * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    fb[j] = *reinterpret_cast<const s16x8 *>(Bt + (wn * 32 + j * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[h][i][j], 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < C3_BK / 4; ++kk) {
-#pragma unroll
-                for (int h = 0; h < NT; ++h) {
-                    const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
-                    float fa[4], fb[2];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) fa[i] = A[(wm * 64 + i * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) fb[j] = Bt[(wn * 32 + j * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-                            acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[h][i][j], 0, 0, 0);
-                }
-            }
-        }
-        if constexpr (FLIP && MODE == C3_DGRAD)
-            if ((step + 1) % ntile == 0) fold(s + step / ntile);
+                });
+            });
+        };
+        c3_pipeline(nsum, e.rbeg, e.rend, fetch, store, compute, fold);
+    } else {
+        c3_pipeline(nsum, e.rbeg, e.rend, fetch, store, compute);
     }
 
-    // ---- epilogue: lane holds C[(lane >> 4) * 4 + q][lane & 15] of each 16 x 16 block
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
-        if (n >= N) continue;
+    c3_each_col(t, e.N, [&](int j, int32_t n) {
         float bias = 0.f;
         if (MODE == C3_FWD && a.bias) bias = a.bias[(int64_t)s * a.b_ss + grp * g.Ng + n];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int32_t m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + q;
-                if (m >= M) continue;
-                const float v = acc[0][i][j][q];
-                if (MODE == C3_FWD && FLIP) {
-                    const uint32_t b = fdiv(m, g.fP), p = m - b * g.P;
-                    const float r = a.sg[(int64_t)s * a.sg_ss + (int32_t)b * OC + n];
-                    a.out[(int64_t)s * g.B * g.O * g.P + (b * g.O + n) * g.P + p] = __builtin_fmaf(r, acc[NT - 1][i][j][q], v);
-                } else if (MODE == C3_WGRAD && FLIP) {
-                    // slab [slab][s][mean | stddev][o][k]
-                    const int64_t e = (((int64_t)slab * a.S + s) * 2 * g.O + n) * g.K + m;
-                    a.out[e] = v;
-                    a.out[e + (int64_t)g.O * g.K] = acc[NT - 1][i][j][q];
-                } else if (MODE == C3_FWD) {
-                    const uint32_t b = fdiv(m, g.fP), p = m - b * g.P;
-                    a.out[(int64_t)s * g.B * g.O * g.P + (b * g.O + grp * g.Ng + n) * g.P + p] = v + bias;
-                } else if (MODE == C3_DGRAD) {
-                    const uint32_t b = fdiv(m, g.fPin), p = m - b * g.Pin;
-                    a.out[(int64_t)s * g.B * g.C * g.Pin + (b * g.C + grp * g.Cg + n) * g.Pin + p] = v;
-                } else {
-                    // slab [slab][s][o][k] (gw itself when there is one slab)
-                    a.out[(((int64_t)slab * a.S + s) * g.O + grp * g.Ng + n) * g.K + m] = v;
-                }
+        c3_each_row(t, e.M, [&](int i, int q, int32_t m) {
+            const float v = acc[0][i][j][q];
+            if (MODE == C3_FWD && FLIP) {
+                const float r = a.sg[(int64_t)s * a.sg_ss + (int32_t)fdiv(m, g.fP) * OC + n];
+                a.out[(int64_t)s * g.B * g.O * g.P + c3_elem(m, g.fP, g.P, g.O, n)] = __builtin_fmaf(r, acc[NT - 1][i][j][q], v);
+            } else if (MODE == C3_WGRAD && FLIP) {
+                // slab [slab][s][mean | stddev][o][k]
+                const int64_t el = (((int64_t)k.slab * a.S + s) * 2 * g.O + n) * g.K + m;
+                a.out[el] = v;
+                a.out[el + (int64_t)g.O * g.K] = acc[NT - 1][i][j][q];
+            } else if (MODE == C3_FWD) {
+                a.out[(int64_t)s * g.B * g.O * g.P + c3_elem(m, g.fP, g.P, g.O, grp * g.Ng + n)] = v + bias;
+            } else if (MODE == C3_DGRAD) {
+                a.out[(int64_t)s * g.B * g.C * g.Pin + c3_elem(m, g.fPin, g.Pin, g.C, grp * g.Cg + n)] = v;
+            } else {
+                // slab [slab][s][o][k] (gw itself when there is one slab)
+                a.out[(((int64_t)k.slab * a.S + s) * g.O + grp * g.Ng + n) * g.K + m] = v;
             }
-    }
+        });
+    });
 }
 
 // gw[e] = sum of the slabs in slab order
@@ -412,9 +197,9 @@ __global__ __launch_bounds__(256) void k_conv3d_bias_grad(const float *__restric
 
 // ---- K11: the local-reparameterization conv tile (LocalReparamConv1d / 2d / 3d, nn/conv.py) -------------------------------
 // m = conv(x, mu_w) + mu_b, v = conv(x^2, sigma_w^2) + sigma_b^2, y_s = m + sqrt(v + 1e-16) eps_s with one eps per output element
-// and MC sample (LRT-conv noise contract, include/bnn_hip.h).  The tile is k_conv3d's with TWO contractions on one pass over the
-// gathers, like its Flipout instantiation; the second copy of an operand is its square (taken in fp32, then rounded as the plain
-// copy) or a second tensor:
+// and MC sample (LRT-conv noise contract, include/bnn_hip.h).  The tile (bnn_conv3d_tile.hpp) with TWO contractions on one pass
+// over the gathers, like K7's Flipout instantiation; the second copy of an operand is its square (taken in fp32, then rounded as
+// the plain copy) or a second tensor:
 //   FWD   A = gather(x), A2 = A^2; B = mu_w, B2 = sigma_w^2.  Epilogue: v (stored for the backward) and the S samples -- a shared
 //         input is contracted ONCE and the workgroup stores S tiles; a per-sample input has the sample in the grid.
 //   DGRAD A = gather(g_m), A2 = gather(g_v); B, B2 = the same weights read transposed.  Epilogue: acc + 2 x acc2.
@@ -440,230 +225,66 @@ __global__ __launch_bounds__(C3_THREADS) void k_lrt_conv3d(const Conv3dGeo g, co
     __shared__ __attribute__((aligned(16))) T As[2 * C3_BM * LDK];
     __shared__ __attribute__((aligned(16))) T Bs[2 * C3_BN * LDK];
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave & 1, wn = wave >> 1;
-
-    // the block's (sample or set, group, slab)
-    int z = blockIdx.z, slab = 0;
-    if (MODE == C3_WGRAD) { slab = z % a.nslab; z /= a.nslab; }
-    const int grp = z % g.groups;
-    const int s = z / g.groups;              // FWD with a shared input, WGRAD: 0
-
-    const int32_t M = MODE == C3_FWD ? g.B * g.P : MODE == C3_DGRAD ? g.B * g.Pin : g.K;
-    const int32_t N = MODE == C3_DGRAD ? g.Cg : g.Ng;
-    const int32_t m0 = blockIdx.x * C3_BM, n0 = blockIdx.y * C3_BN;
-    int32_t rbeg = 0, rend = MODE == C3_FWD ? g.K : MODE == C3_DGRAD ? g.Ng * g.T : g.B * g.P;
-    if (MODE == C3_WGRAD) {
-        rbeg = slab * a.chunk;
-        rend = min(rend, rbeg + a.chunk);
-    }
+    const C3Tile t = c3_tile();
+    const C3Block k = c3_block<MODE>(g, a.nslab);
+    const int s = k.s, grp = k.grp;          // s: the sample or image set; FWD with a shared input, WGRAD: 0
+    const C3Extents e = c3_extents<MODE>(g, k.slab, a.chunk);
     const int nsum = MODE == C3_WGRAD ? a.S : 1;
     const int64_t gset = (int64_t)g.B * g.O * g.P;       // one image set of g_m / g_v / y
+    const C3Row row = c3_row_origin<MODE>(g, t.m0 + t.ar, e.M, grp);
 
-    // ---- A loader: row ar of the tile, reduction offsets ah * 16 .. + 15 of each k-tile
-    const int ar = tid & (C3_BM - 1);
-    const int ah = __builtin_amdgcn_readfirstlane(tid >> 7);
-    const int32_t am = m0 + ar;
-    const bool arow = am < M;
-    int32_t abase = 0, z0 = 0, z1 = 0, z2 = 0;   // FWD / DGRAD: gather origin of the row; WGRAD: its tap
-    if (MODE == C3_FWD && arow) {
-        const uint32_t b = fdiv(am, g.fP), p = am - b * g.P;
-        const uint32_t q = fdiv(p, g.fOW), ow = p - q * g.OW, od = fdiv(q, g.fOH), oh = q - od * g.OH;
-        z0 = od * g.sd - g.pd; z1 = oh * g.sh - g.ph; z2 = ow * g.sw - g.pw;
-        abase = (b * g.C + grp * g.Cg) * g.Pin;
-    } else if (MODE == C3_DGRAD && arow) {
-        const uint32_t b = fdiv(am, g.fPin), p = am - b * g.Pin;
-        const uint32_t q = fdiv(p, g.fW), iw = p - q * g.W, id = fdiv(q, g.fH), ih = q - id * g.H;
-        z0 = id + g.pd; z1 = ih + g.ph; z2 = iw + g.pw;
-        abase = (b * g.O + grp * g.Ng) * g.P;
-    } else if (MODE == C3_WGRAD && arow) {
-        const uint32_t c = fdiv(am, g.fT), t = am - c * g.T;
-        const uint32_t q = fdiv(t, g.fKW), kw = t - q * g.KW, kd = fdiv(q, g.fKH), kh = q - kd * g.KH;
-        z0 = kd * g.dd - g.pd; z1 = kh * g.dh - g.ph; z2 = kw * g.dw - g.pw;
-        abase = (grp * g.Cg + c) * g.Pin;
-    }
-
-    // v: the plain copy; v2: DGRAD only, the second tensor (FWD / WGRAD square v as they store it)
-    auto fetch_a = [&](int sm, int32_t r0, float (&v)[16], float (&v2)[16]) {
-        int32_t r = r0 + ah * 16;
-        if (MODE == C3_WGRAD) {
-            // reduction index = output position (b, od, oh, ow) of image set sm, stepped with carries
-            const float *x = a.x + (int64_t)sm * a.x_ss;
-            uint32_t b = 0, od = 0, oh = 0, ow = 0;
-            if (r < rend) {
-                b = fdiv(r, g.fP);
-                const uint32_t p = r - b * g.P, q = fdiv(p, g.fOW);
-                ow = p - q * g.OW; od = fdiv(q, g.fOH); oh = q - od * g.OH;
-            }
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int32_t id = (int32_t)(od * g.sd) + z0, ih = (int32_t)(oh * g.sh) + z1, iw = (int32_t)(ow * g.sw) + z2;
-                const bool ok = arow && r + j < rend && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H &&
-                                (uint32_t)iw < (uint32_t)g.W;
-                v[j] = ok ? x[(int64_t)b * g.C * g.Pin + abase + (id * g.H + ih) * g.W + iw] : 0.f;
-                if (++ow == (uint32_t)g.OW) { ow = 0; if (++oh == (uint32_t)g.OH) { oh = 0; if (++od == (uint32_t)g.OD) { od = 0; ++b; } } }
-            }
-            return;
-        }
-        // reduction index = (channel, kd, kh, kw), stepped with carries
-        const float *src = MODE == C3_FWD ? a.x + (int64_t)s * a.x_ss : a.g1 + (int64_t)s * gset;
-        const float *src2 = MODE == C3_FWD ? nullptr : a.g2 + (int64_t)s * gset;
-        uint32_t c = 0, kd = 0, kh = 0, kw = 0;
-        if (r < rend) {
-            c = fdiv(r, g.fT);
-            const uint32_t t = r - c * g.T, q = fdiv(t, g.fKW);
-            kw = t - q * g.KW; kd = fdiv(q, g.fKH); kh = q - kd * g.KH;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            bool ok = arow && r + j < rend;
-            int32_t off = 0;
-            if (MODE == C3_FWD) {
-                const int32_t id = z0 + (int32_t)kd * g.dd, ih = z1 + (int32_t)kh * g.dh, iw = z2 + (int32_t)kw * g.dw;
-                ok = ok && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H && (uint32_t)iw < (uint32_t)g.W;
-                off = (int32_t)c * g.Pin + (id * g.H + ih) * g.W + iw;
-            } else {
-                const int32_t nd = z0 - (int32_t)kd * g.dd, nh = z1 - (int32_t)kh * g.dh, nw = z2 - (int32_t)kw * g.dw;
-                ok = ok && nd >= 0 && nh >= 0 && nw >= 0;
-                const uint32_t od = fdiv(ok ? nd : 0, g.fsd), oh = fdiv(ok ? nh : 0, g.fsh), ow = fdiv(ok ? nw : 0, g.fsw);
-                ok = ok && (int32_t)(od * g.sd) == nd && (int32_t)(oh * g.sh) == nh && (int32_t)(ow * g.sw) == nw &&
-                     od < (uint32_t)g.OD && oh < (uint32_t)g.OH && ow < (uint32_t)g.OW;
-                off = (int32_t)c * g.P + (int32_t)((od * g.OH + oh) * g.OW + ow);
-            }
-            v[j] = ok ? src[abase + off] : 0.f;
-            if constexpr (MODE == C3_DGRAD) v2[j] = ok ? src2[abase + off] : 0.f;
-            if (++kw == (uint32_t)g.KW) { kw = 0; if (++kh == (uint32_t)g.KH) { kh = 0; if (++kd == (uint32_t)g.KD) { kd = 0; ++c; } } }
+    // va: the plain copy; va2: DGRAD only, the second tensor (FWD / WGRAD square va as they store it)
+    float va[16], va2[16], vb[8], vb2[8];
+    auto fetch = [&](int sm, int32_t r0) {
+        if constexpr (MODE == C3_WGRAD) {
+            const float *x = a.x + (int64_t)sm * a.x_ss;           // image set sm
+            c3_gather_positions(g, row, r0 + t.ah * 16, e.rend,
+                                [&](int j, bool ok, int64_t off, uint32_t) { va[j] = ok ? x[off] : 0.f; });
+            c3_grad_rows(g, t, e.N, grp, r0 + t.bk, e.rend, [&](int i, bool ok, int64_t off, uint32_t, int32_t) {
+                vb[i] = ok ? a.g1[(int64_t)sm * gset + off] : 0.f;
+                vb2[i] = ok ? a.g2[(int64_t)sm * gset + off] : 0.f;
+            });
+        } else {
+            const float *src = MODE == C3_FWD ? a.x + (int64_t)s * a.x_ss : a.g1 + (int64_t)s * gset;
+            const float *src2 = MODE == C3_FWD ? nullptr : a.g2 + (int64_t)s * gset;
+            c3_gather_taps<MODE>(g, row, r0 + t.ah * 16, e.rend, [&](int j, bool ok, int32_t off, uint32_t) {
+                va[j] = ok ? src[off] : 0.f;
+                if constexpr (MODE == C3_DGRAD) va2[j] = ok ? src2[off] : 0.f;
+            });
+            c3_weight_rows<MODE>(g, t, e.N, grp, r0 + t.bk, e.rend, [&](int i, bool ok, int64_t off) {
+                vb[i] = ok ? a.w1[off] : 0.f;
+                vb2[i] = ok ? a.w2[off] : 0.f;
+            });
         }
     };
 
-    // ---- B loader: reduction offset bk of each k-tile, rows bn + 8 i of the tile
-    const int bk = tid & (C3_BK - 1), bn = tid >> 5;
-    auto fetch_b = [&](int sm, int32_t r0, float (&v)[8], float (&v2)[8]) {
-        const int32_t r = r0 + bk;
-        const bool rok = r < rend;
-        if (MODE == C3_WGRAD) {
-            uint32_t b = 0, p = 0;
-            if (rok) { b = fdiv(r, g.fP); p = r - b * g.P; }
-            const int64_t o0 = (int64_t)sm * gset + ((int64_t)b * g.O + (int64_t)grp * g.Ng) * g.P + p;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int32_t n = n0 + bn + 8 * i;
-                const bool ok = rok && n < N;
-                v[i] = ok ? a.g1[o0 + (int64_t)n * g.P] : 0.f;
-                v2[i] = ok ? a.g2[o0 + (int64_t)n * g.P] : 0.f;
-            }
-            return;
-        }
-        const int64_t wb = (int64_t)grp * g.Ng * g.K;
-        int32_t roff = r;                               // FWD: w[o][r]
-        int32_t nstride = g.K;
-        if (MODE == C3_DGRAD) {                         // r = (o, tap): w[o][c][tap]
-            const uint32_t o = fdiv(rok ? r : 0, g.fT);
-            roff = (int32_t)(o * g.K + (r - o * g.T));
-            nstride = g.T;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int32_t n = n0 + bn + 8 * i;
-            const bool ok = rok && n < N;
-            v[i] = ok ? a.w1[wb + (int64_t)n * nstride + roff] : 0.f;
-            v2[i] = ok ? a.w2[wb + (int64_t)n * nstride + roff] : 0.f;
-        }
-    };
-
-    auto store_tiles = [&](const float (&va)[16], const float (&va2)[16], const float (&vb)[8], const float (&vb2)[8]) {
-        T *pa = As + ar * LDK + ah * 16, *pa2 = pa + C3_BM * LDK;
+    auto store = [&]() {
+        T *pa = c3_lds_a(As, t), *pb = c3_lds_b(Bs, t);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             st_lds(pa + j, va[j]);
-            st_lds(pa2 + j, MODE == C3_DGRAD ? va2[j] : va[j] * va[j]);      // the square in fp32, then rounded as the plain copy
+            st_lds(pa + C3_BM * LDK + j, MODE == C3_DGRAD ? va2[j] : va[j] * va[j]);   // the square in fp32, then rounded as the plain copy
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            st_lds(Bs + (bn + 8 * i) * LDK + bk, vb[i]);
-            st_lds(Bs + (C3_BN + bn + 8 * i) * LDK + bk, vb2[i]);
+            st_lds(pb + 8 * i * LDK, vb[i]);
+            st_lds(pb + (C3_BN + 8 * i) * LDK, vb2[i]);
         }
     };
 
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc[2][4][2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    c3_zero(acc);
+    c3_pipeline(nsum, e.rbeg, e.rend, fetch, store, [&]() { c3_mfma_planes<T, 2, 2>(acc, As, Bs, t); });
 
-    const int ntile = rend > rbeg ? (rend - rbeg + C3_BK - 1) / C3_BK : 0;
-    const int nstep = nsum * ntile;
-    float va[16], va2[16], vb[8], vb2[8];          // va2: DGRAD only (dead otherwise)
-    if (nstep > 0) { fetch_a(0, rbeg, va, va2); fetch_b(0, rbeg, vb, vb2); }
-    for (int step = 0; step < nstep; ++step) {
-        __syncthreads();                                // the previous tile's fragment reads are done
-        store_tiles(va, va2, vb, vb2);
-        __syncthreads();
-        if (step + 1 < nstep) {                         // the next tile's loads fly under this tile's MFMAs
-            const int nx = step + 1, sm = nx / ntile;
-            const int32_t r0 = rbeg + (nx - sm * ntile) * C3_BK;
-            fetch_a(sm, r0, va, va2);
-            fetch_b(sm, r0, vb, vb2);
-        }
-        if constexpr (sizeof(T) == 2) {
-            typedef short s16x8 __attribute__((ext_vector_type(8)));
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
-                s16x8 fa[4], fb[2];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    fa[i] = *reinterpret_cast<const s16x8 *>(A + (wm * 64 + i * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    fb[j] = *reinterpret_cast<const s16x8 *>(Bt + (wn * 32 + j * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[h][i][j], 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < C3_BK / 4; ++kk) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
-                    float fa[4], fb[2];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) fa[i] = A[(wm * 64 + i * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) fb[j] = Bt[(wn * 32 + j * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-                            acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[h][i][j], 0, 0, 0);
-                }
-            }
-        }
-    }
-
-    // ---- epilogue: lane holds C[(lane >> 4) * 4 + q][lane & 15] of each 16 x 16 block
     if constexpr (MODE == C3_FWD) {
         // a lane's quad runs along the output position p: with P % 4 == 0 it is one aligned eps quad of one image and channel
-        const bool vec = (g.P & 3) == 0;
+        const bool vec = c3_vec(g.P);
         const uint32_t ed = rng_epoch_dev(a.rng);
         const int ns = a.shared ? a.S : 1;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
-            if (n >= N) continue;
+        c3_each_col(t, e.N, [&](int j, int32_t n) {
             const int32_t o = grp * g.Ng + n;
             const float mb = a.b1 ? a.b1[o] : 0.f, sb = a.b1 ? a.b2[o] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int32_t mq = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
-                if (mq >= M) continue;
+            c3_each_quad(t, e.M, [&](int i, int32_t mq) {
                 float r1[4], r2[4], sd[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -671,60 +292,46 @@ __global__ __launch_bounds__(C3_THREADS) void k_lrt_conv3d(const Conv3dGeo g, co
                     r2[q] = acc[1][i][j][q] + sb;
                     sd[q] = sqrtf(r2[q] + 1e-16f);
                 }
-                // element (b O + o) P + p of output row m = b P + p
-                auto elem = [&](uint32_t m) {
-                    const uint32_t b = fdiv(m, g.fP);
-                    return (b * (uint32_t)g.O + (uint32_t)o) * (uint32_t)g.P + (m - b * (uint32_t)g.P);
-                };
                 if (vec) {
-                    const uint32_t e0 = elem(mq);          // the quad stays inside one image and channel
+                    const uint32_t e0 = c3_elem(mq, g.fP, g.P, g.O, o);          // the quad stays inside one image and channel
                     if (a.out2) *reinterpret_cast<float4 *>(a.out2 + (int64_t)s * gset + e0) = make_float4(r2[0], r2[1], r2[2], r2[3]);
-                    for (int t = 0; t < ns; ++t) {
-                        const int smp = a.shared ? t : s;
+                    for (int u = 0; u < ns; ++u) {
+                        const int smp = a.shared ? u : s;
                         const float4 e4 = eps4(a.rng, ed, e0 >> 2, a.rng.sample0 + (uint32_t)smp);
                         *reinterpret_cast<float4 *>(a.out + (int64_t)smp * gset + e0) =
                             make_float4(__builtin_fmaf(sd[0], e4.x, r1[0]), __builtin_fmaf(sd[1], e4.y, r1[1]),
                                         __builtin_fmaf(sd[2], e4.z, r1[2]), __builtin_fmaf(sd[3], e4.w, r1[3]));
                     }
                 } else {
-                    uint32_t e[4];
+                    uint32_t el[4];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) e[q] = elem(min(mq + q, M - 1));
-                    const int nq = M - mq < 4 ? M - mq : 4;
+                    for (int q = 0; q < 4; ++q) el[q] = c3_elem(min(mq + q, e.M - 1), g.fP, g.P, g.O, o);
+                    const int nq = e.M - mq < 4 ? e.M - mq : 4;
                     if (a.out2)
-                        for (int q = 0; q < nq; ++q) a.out2[(int64_t)s * gset + e[q]] = r2[q];
-                    for (int t = 0; t < ns; ++t) {
-                        const int smp = a.shared ? t : s;
+                        for (int q = 0; q < nq; ++q) a.out2[(int64_t)s * gset + el[q]] = r2[q];
+                    for (int u = 0; u < ns; ++u) {
+                        const int smp = a.shared ? u : s;
                         for (int q = 0; q < nq; ++q)
-                            a.out[(int64_t)smp * gset + e[q]] =
-                                __builtin_fmaf(sd[q], eps1(a.rng, ed, (uint64_t)e[q], a.rng.sample0 + (uint32_t)smp), r1[q]);
+                            a.out[(int64_t)smp * gset + el[q]] =
+                                __builtin_fmaf(sd[q], eps1(a.rng, ed, (uint64_t)el[q], a.rng.sample0 + (uint32_t)smp), r1[q]);
                     }
                 }
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
-        if (n >= N) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int32_t m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + q;
-                if (m >= M) continue;
+            });
+        });
+    } else {
+        c3_each_col(t, e.N, [&](int j, int32_t n) {
+            c3_each_row(t, e.M, [&](int i, int q, int32_t m) {
                 if (MODE == C3_DGRAD) {
-                    const uint32_t b = fdiv(m, g.fPin), p = m - b * g.Pin;
-                    const int64_t idx = (int64_t)s * a.x_ss + (b * g.C + grp * g.Cg + n) * g.Pin + p;
+                    const int64_t idx = (int64_t)s * a.x_ss + c3_elem(m, g.fPin, g.Pin, g.C, grp * g.Cg + n);
                     a.out[idx] = __builtin_fmaf(2.0f * a.x[idx], acc[1][i][j][q], acc[0][i][j][q]);
                 } else {
                     // slab [slab][mean | variance][o][k]
-                    const int64_t e = (((int64_t)slab * 2) * g.O + grp * g.Ng + n) * g.K + m;
-                    a.out[e] = acc[0][i][j][q];
-                    a.out[e + (int64_t)g.O * g.K] = acc[1][i][j][q];
+                    const int64_t el = (((int64_t)k.slab * 2) * g.O + grp * g.Ng + n) * g.K + m;
+                    a.out[el] = acc[0][i][j][q];
+                    a.out[el + (int64_t)g.O * g.K] = acc[1][i][j][q];
                 }
-            }
+            });
+        });
     }
 }
 
@@ -776,11 +383,11 @@ __global__ __launch_bounds__(256) void k_lrt_conv_bias_grad(const float *__restr
 // BayesianNetworkModule.predictive_moments).  Input and output hold a mean and a variance per element, independent across elements:
 //     m = conv(a_m, mu_w) + mu_b
 //     v = conv(a_m^2, sigma_w^2) + conv(a_v, mu_w^2 + sigma_w^2) + sigma_b^2          (second term absent for a deterministic input)
-// Every addend of v is non-negative.  K11's forward tile (128 x 64 x 32, im2col in the loader, padding reads zero, groups in the
-// grid) with K16's planes: A planes a_m, a_m^2, [a_v]; B planes mu_w, sigma_w^2, [fma(mu_w, mu_w, sigma_w^2)], the derived planes
-// formed in fp32 as they are staged (before any bf16 rounding).  Both variance contractions add into ONE accumulator set: a lane
-// holds K11's 64 accumulator registers.  Epilogue: + mu_b / + sigma_b^2, then moments_relu_dev or moments_elu_dev
-// (bnn_moments_act.hpp: the standalone launches' functions, so fused and standalone agree bit for bit); fp32 (B, O, P) stores.
+// Every addend of v is non-negative.  The tile's FWD contraction (groups in the grid) with K16's planes: A planes a_m, a_m^2,
+// [a_v]; B planes mu_w, sigma_w^2, [fma(mu_w, mu_w, sigma_w^2)], the derived planes formed in fp32 as they are staged (before any
+// bf16 rounding).  Both variance contractions add into ONE accumulator set: a lane holds K11's 64 accumulator registers.
+// Epilogue: + mu_b / + sigma_b^2, then moments_relu_dev or moments_elu_dev (bnn_moments_act.hpp: the standalone launches'
+// functions, so fused and standalone agree bit for bit); fp32 (B, O, P) stores.
 // No sample axis, no rng, no atomics, no split reduction: identical calls give identical bits.
 struct MomConvArgs {
     const float *a_m, *a_v;                  // (B, C, D, H, W); a_v NULL in the deterministic instantiation
@@ -799,67 +406,26 @@ __global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d(const Conv3dGeo g
     __shared__ __attribute__((aligned(16))) T As[NPL * C3_BM * LDK];
     __shared__ __attribute__((aligned(16))) T Bs[NPL * C3_BN * LDK];
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave & 1, wn = wave >> 1;
-    const int grp = blockIdx.z;
+    const C3Tile t = c3_tile();
+    const int grp = c3_block<C3_FWD>(g, 1).grp;
+    const C3Extents e = c3_extents<C3_FWD>(g, 0, 0);
+    const C3Row row = c3_row_origin<C3_FWD>(g, t.m0 + t.ar, e.M, grp);
 
-    const int32_t M = g.B * g.P, N = g.Ng;
-    const int32_t m0 = blockIdx.x * C3_BM, n0 = blockIdx.y * C3_BN;
-    const int32_t rend = g.K;
-
-    // ---- A loader: row ar of the tile, reduction offsets ah * 16 .. + 15 of each k-tile
-    const int ar = tid & (C3_BM - 1);
-    const int ah = __builtin_amdgcn_readfirstlane(tid >> 7);
-    const int32_t am = m0 + ar;
-    const bool arow = am < M;
-    int32_t abase = 0, z0 = 0, z1 = 0, z2 = 0;       // gather origin of the row
-    if (arow) {
-        const uint32_t b = fdiv(am, g.fP), p = am - b * g.P;
-        const uint32_t q = fdiv(p, g.fOW), ow = p - q * g.OW, od = fdiv(q, g.fOH), oh = q - od * g.OH;
-        z0 = od * g.sd - g.pd; z1 = oh * g.sh - g.ph; z2 = ow * g.sw - g.pw;
-        abase = (b * g.C + grp * g.Cg) * g.Pin;
-    }
-
-    // v: a_m; v2: a_v (VAR only; dead otherwise).  Reduction index = (channel, kd, kh, kw), stepped with carries
-    auto fetch_a = [&](int32_t r0, float (&v)[16], float (&v2)[16]) {
-        const int32_t r = r0 + ah * 16;
-        uint32_t c = 0, kd = 0, kh = 0, kw = 0;
-        if (r < rend) {
-            c = fdiv(r, g.fT);
-            const uint32_t t = r - c * g.T, q = fdiv(t, g.fKW);
-            kw = t - q * g.KW; kd = fdiv(q, g.fKH); kh = q - kd * g.KH;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int32_t id = z0 + (int32_t)kd * g.dd, ih = z1 + (int32_t)kh * g.dh, iw = z2 + (int32_t)kw * g.dw;
-            const bool ok = arow && r + j < rend && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H &&
-                            (uint32_t)iw < (uint32_t)g.W;
-            const int32_t off = abase + (int32_t)c * g.Pin + (id * g.H + ih) * g.W + iw;
-            v[j] = ok ? a.a_m[off] : 0.f;
-            if constexpr (VAR) v2[j] = ok ? a.a_v[off] : 0.f;
-            if (++kw == (uint32_t)g.KW) { kw = 0; if (++kh == (uint32_t)g.KH) { kh = 0; if (++kd == (uint32_t)g.KD) { kd = 0; ++c; } } }
-        }
-    };
-
-    // ---- B loader: reduction offset bk of each k-tile, rows bn + 8 i of the tile (w[o][r])
-    const int bk = tid & (C3_BK - 1), bn = tid >> 5;
-    const int64_t wb = (int64_t)grp * g.Ng * g.K;
-    auto fetch_b = [&](int32_t r0, float (&v)[8], float (&v2)[8]) {
-        const int32_t r = r0 + bk;
-        const bool rok = r < rend;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int32_t n = n0 + bn + 8 * i;
-            const bool ok = rok && n < N;
-            v[i] = ok ? a.w1[wb + (int64_t)n * g.K + r] : 0.f;
-            v2[i] = ok ? a.w2[wb + (int64_t)n * g.K + r] : 0.f;
-        }
+    float va[16], va2[16], vb[8], vb2[8];            // va2: a_v (VAR only; dead otherwise)
+    auto fetch = [&](int, int32_t r0) {
+        c3_gather_taps<C3_FWD>(g, row, r0 + t.ah * 16, e.rend, [&](int j, bool ok, int32_t off, uint32_t) {
+            va[j] = ok ? a.a_m[off] : 0.f;
+            if constexpr (VAR) va2[j] = ok ? a.a_v[off] : 0.f;
+        });
+        c3_weight_rows<C3_FWD>(g, t, e.N, grp, r0 + t.bk, e.rend, [&](int i, bool ok, int64_t off) {
+            vb[i] = ok ? a.w1[off] : 0.f;
+            vb2[i] = ok ? a.w2[off] : 0.f;
+        });
     };
 
     // the derived planes in fp32, then rounded as the plain copies
-    auto store_tiles = [&](const float (&va)[16], const float (&va2)[16], const float (&vb)[8], const float (&vb2)[8]) {
-        T *pa = As + ar * LDK + ah * 16;
+    auto store = [&]() {
+        T *pa = c3_lds_a(As, t), *pb = c3_lds_b(Bs, t);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             st_lds(pa + j, va[j]);
@@ -868,86 +434,22 @@ __global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d(const Conv3dGeo g
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            T *pb = Bs + (bn + 8 * i) * LDK + bk;
-            st_lds(pb, vb[i]);
-            st_lds(pb + C3_BN * LDK, vb2[i]);
-            if constexpr (VAR) st_lds(pb + 2 * C3_BN * LDK, __builtin_fmaf(vb[i], vb[i], vb2[i]));
+            st_lds(pb + 8 * i * LDK, vb[i]);
+            st_lds(pb + (C3_BN + 8 * i) * LDK, vb2[i]);
+            if constexpr (VAR) st_lds(pb + (2 * C3_BN + 8 * i) * LDK, __builtin_fmaf(vb[i], vb[i], vb2[i]));
         }
     };
 
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc[2][4][2];                              // [mean | variance]: planes 1 and 2 both add into acc[1]
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    c3_zero(acc);
+    c3_pipeline(1, e.rbeg, e.rend, fetch, store, [&]() { c3_mfma_planes<T, NPL, 2>(acc, As, Bs, t); });
 
-    const int ntile = (rend + C3_BK - 1) / C3_BK;
-    float va[16], va2[16], vb[8], vb2[8];
-    fetch_a(0, va, va2);
-    fetch_b(0, vb, vb2);
-    for (int step = 0; step < ntile; ++step) {
-        __syncthreads();                                // the previous tile's fragment reads are done
-        store_tiles(va, va2, vb, vb2);
-        __syncthreads();
-        if (step + 1 < ntile) {                         // the next tile's loads fly under this tile's MFMAs
-            fetch_a((step + 1) * C3_BK, va, va2);
-            fetch_b((step + 1) * C3_BK, vb, vb2);
-        }
-        if constexpr (sizeof(T) == 2) {
-            typedef short s16x8 __attribute__((ext_vector_type(8)));
-#pragma unroll
-            for (int h = 0; h < NPL; ++h) {
-                const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
-                s16x8 fa[4], fb[2];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    fa[i] = *reinterpret_cast<const s16x8 *>(A + (wm * 64 + i * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    fb[j] = *reinterpret_cast<const s16x8 *>(Bt + (wn * 32 + j * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[h ? 1 : 0][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[h ? 1 : 0][i][j], 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < C3_BK / 4; ++kk) {
-#pragma unroll
-                for (int h = 0; h < NPL; ++h) {
-                    const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
-                    float fa[4], fb[2];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) fa[i] = A[(wm * 64 + i * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) fb[j] = Bt[(wn * 32 + j * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-                            acc[h ? 1 : 0][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[h ? 1 : 0][i][j], 0, 0, 0);
-                }
-            }
-        }
-    }
-
-    // ---- epilogue: lane holds C[(lane >> 4) * 4 + q][lane & 15] of each 16 x 16 block; a lane's quad runs along the output
-    // position p: with P % 4 == 0 it is four consecutive elements of one image and channel
-    const bool vec = (g.P & 3) == 0;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
-        if (n >= N) continue;
+    // a lane's quad runs along the output position p: with P % 4 == 0 it is four consecutive elements of one image and channel
+    const bool vec = c3_vec(g.P);
+    c3_each_col(t, e.N, [&](int j, int32_t n) {
         const int32_t o = grp * g.Ng + n;
         const float mb = a.b1 ? a.b1[o] : 0.f, sb = a.b1 ? a.b2[o] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int32_t mq = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
-            if (mq >= M) continue;
+        c3_each_quad(t, e.M, [&](int i, int32_t mq) {
             float r1[4], r2[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -961,25 +463,20 @@ __global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d(const Conv3dGeo g
 #pragma unroll 1
                 for (int q = 0; q < 4; ++q) moments_elu_dev(r1[q], r2[q], a.elu_alpha, r1[q], r2[q]);
             }
-            // element (b O + o) P + p of output row m = b P + p
-            auto elem = [&](uint32_t m) {
-                const uint32_t b = fdiv(m, g.fP);
-                return (b * (uint32_t)g.O + (uint32_t)o) * (uint32_t)g.P + (m - b * (uint32_t)g.P);
-            };
             if (vec) {
-                const uint32_t e0 = elem(mq);              // the quad stays inside one image and channel
+                const uint32_t e0 = c3_elem(mq, g.fP, g.P, g.O, o);              // the quad stays inside one image and channel
                 *reinterpret_cast<float4 *>(a.out_m + e0) = make_float4(r1[0], r1[1], r1[2], r1[3]);
                 *reinterpret_cast<float4 *>(a.out_v + e0) = make_float4(r2[0], r2[1], r2[2], r2[3]);
             } else {
-                const int nq = M - mq < 4 ? M - mq : 4;
+                const int nq = e.M - mq < 4 ? e.M - mq : 4;
                 for (int q = 0; q < nq; ++q) {
-                    const uint32_t e = elem(mq + q);
-                    a.out_m[e] = r1[q];
-                    a.out_v[e] = r2[q];
+                    const uint32_t el = c3_elem(mq + q, g.fP, g.P, g.O, o);
+                    a.out_m[el] = r1[q];
+                    a.out_v[el] = r2[q];
                 }
             }
-        }
-    }
+        });
+    });
 }
 
 // ---- K19: the backward of K17's contraction, for training conv nets without sampling.  With G_m, G_v the (B, O, P) gradients
@@ -987,7 +484,7 @@ __global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d(const Conv3dGeo g
 //     g_a_m  = convT(G_m, mu_w) + 2 a_m (.) convT(G_v, sigma_w^2)             g_a_v  = convT(G_v, mu_w^2 + sigma_w^2)
 //     g_mu_w = sum gather(a_m) G_m + 2 mu_w (.) sum gather(a_v) G_v            g_s2_w = sum gather(a_m^2 + a_v) G_v
 // K18's shape (P planes (p1, p2, fma(p1, p1, p2)), Q planes (G_m, G_v) with G_v serving twice, THREE accumulator sets: 96
-// accumulator registers per lane) on K11's backward tile and loaders:
+// accumulator registers per lane) on the tile's DGRAD and WGRAD contractions:
 //   DGRAD A = gather(G_m), gather(G_v); B = mu_w^T, sigma_w^2^T and their derived plane.  acc1 = A1 B1, acc2 = A2 B2, acc3 = A2 B3.
 //         Epilogue: g_a_m = acc1 + 2 a_m acc2, g_a_v = acc3; a lane's quad runs along the input position (16-byte stores when
 //         D H W % 4 == 0).
@@ -1016,121 +513,39 @@ __global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d_bwd(const Conv3dG
     __shared__ __attribute__((aligned(16))) T As[NA * C3_BM * LDK];
     __shared__ __attribute__((aligned(16))) T Bs[NB * C3_BN * LDK];
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave & 1, wn = wave >> 1;
+    const C3Tile t = c3_tile();
+    const C3Block k = c3_block<MODE>(g, a.nslab);
+    const int grp = k.grp;
+    const C3Extents e = c3_extents<MODE>(g, k.slab, a.chunk);
+    const C3Row row = c3_row_origin<MODE>(g, t.m0 + t.ar, e.M, grp);
 
-    // the block's (group, slab)
-    int z = blockIdx.z, slab = 0;
-    if (WG) { slab = z % a.nslab; z /= a.nslab; }
-    const int grp = z;
-
-    const int32_t M = WG ? g.K : g.B * g.Pin;
-    const int32_t N = WG ? g.Ng : g.Cg;
-    const int32_t m0 = blockIdx.x * C3_BM, n0 = blockIdx.y * C3_BN;
-    int32_t rbeg = 0, rend = WG ? g.B * g.P : g.Ng * g.T;
-    if (WG) {
-        rbeg = slab * a.chunk;
-        rend = min(rend, rbeg + a.chunk);
-    }
-
-    // ---- A loader: row ar of the tile, reduction offsets ah * 16 .. + 15 of each k-tile
-    const int ar = tid & (C3_BM - 1);
-    const int ah = __builtin_amdgcn_readfirstlane(tid >> 7);
-    const int32_t am = m0 + ar;
-    const bool arow = am < M;
-    int32_t abase = 0, z0 = 0, z1 = 0, z2 = 0;   // DGRAD: gather origin of the row; WGRAD: its tap
-    if (!WG && arow) {
-        const uint32_t b = fdiv(am, g.fPin), p = am - b * g.Pin;
-        const uint32_t q = fdiv(p, g.fW), iw = p - q * g.W, id = fdiv(q, g.fH), ih = q - id * g.H;
-        z0 = id + g.pd; z1 = ih + g.ph; z2 = iw + g.pw;
-        abase = (b * g.O + grp * g.Ng) * g.P;
-    } else if (WG && arow) {
-        const uint32_t c = fdiv(am, g.fT), t = am - c * g.T;
-        const uint32_t q = fdiv(t, g.fKW), kw = t - q * g.KW, kd = fdiv(q, g.fKH), kh = q - kd * g.KH;
-        z0 = kd * g.dd - g.pd; z1 = kh * g.dh - g.ph; z2 = kw * g.dw - g.pw;
-        abase = (grp * g.Cg + c) * g.Pin;
-    }
-
-    // v, v2: DGRAD gather(G_m), gather(G_v); WGRAD gather(a_m), gather(a_v)
-    auto fetch_a = [&](int32_t r0, float (&v)[16], float (&v2)[16]) {
-        const int32_t r = r0 + ah * 16;
-        if (WG) {
-            // reduction index = output position (b, od, oh, ow), stepped with carries
-            uint32_t b = 0, od = 0, oh = 0, ow = 0;
-            if (r < rend) {
-                b = fdiv(r, g.fP);
-                const uint32_t p = r - b * g.P, q = fdiv(p, g.fOW);
-                ow = p - q * g.OW; od = fdiv(q, g.fOH); oh = q - od * g.OH;
-            }
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int32_t id = (int32_t)(od * g.sd) + z0, ih = (int32_t)(oh * g.sh) + z1, iw = (int32_t)(ow * g.sw) + z2;
-                const bool ok = arow && r + j < rend && (uint32_t)id < (uint32_t)g.D && (uint32_t)ih < (uint32_t)g.H &&
-                                (uint32_t)iw < (uint32_t)g.W;
-                const int64_t off = (int64_t)b * g.C * g.Pin + abase + (id * g.H + ih) * g.W + iw;
-                v[j] = ok ? a.a_m[off] : 0.f;
-                v2[j] = ok ? a.a_v[off] : 0.f;
-                if (++ow == (uint32_t)g.OW) { ow = 0; if (++oh == (uint32_t)g.OH) { oh = 0; if (++od == (uint32_t)g.OD) { od = 0; ++b; } } }
-            }
-            return;
-        }
-        // reduction index = (output channel, kd, kh, kw), stepped with carries
-        uint32_t c = 0, kd = 0, kh = 0, kw = 0;
-        if (r < rend) {
-            c = fdiv(r, g.fT);
-            const uint32_t t = r - c * g.T, q = fdiv(t, g.fKW);
-            kw = t - q * g.KW; kd = fdiv(q, g.fKH); kh = q - kd * g.KH;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            bool ok = arow && r + j < rend;
-            const int32_t nd = z0 - (int32_t)kd * g.dd, nh = z1 - (int32_t)kh * g.dh, nw = z2 - (int32_t)kw * g.dw;
-            ok = ok && nd >= 0 && nh >= 0 && nw >= 0;
-            const uint32_t od = fdiv(ok ? nd : 0, g.fsd), oh = fdiv(ok ? nh : 0, g.fsh), ow = fdiv(ok ? nw : 0, g.fsw);
-            ok = ok && (int32_t)(od * g.sd) == nd && (int32_t)(oh * g.sh) == nh && (int32_t)(ow * g.sw) == nw &&
-                 od < (uint32_t)g.OD && oh < (uint32_t)g.OH && ow < (uint32_t)g.OW;
-            const int32_t off = abase + (int32_t)c * g.P + (int32_t)((od * g.OH + oh) * g.OW + ow);
-            v[j] = ok ? a.g1[off] : 0.f;
-            v2[j] = ok ? a.g2[off] : 0.f;
-            if (++kw == (uint32_t)g.KW) { kw = 0; if (++kh == (uint32_t)g.KH) { kh = 0; if (++kd == (uint32_t)g.KD) { kd = 0; ++c; } } }
-        }
-    };
-
-    // ---- B loader: reduction offset bk of each k-tile, rows bn + 8 i of the tile
-    const int bk = tid & (C3_BK - 1), bn = tid >> 5;
-    auto fetch_b = [&](int32_t r0, float (&v)[8], float (&v2)[8]) {
-        const int32_t r = r0 + bk;
-        const bool rok = r < rend;
-        if (WG) {
-            uint32_t b = 0, p = 0;
-            if (rok) { b = fdiv(r, g.fP); p = r - b * g.P; }
-            const int64_t o0 = ((int64_t)b * g.O + (int64_t)grp * g.Ng) * g.P + p;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int32_t n = n0 + bn + 8 * i;
-                const bool ok = rok && n < N;
-                v[i] = ok ? a.g1[o0 + (int64_t)n * g.P] : 0.f;
-                v2[i] = ok ? a.g2[o0 + (int64_t)n * g.P] : 0.f;
-            }
-            return;
-        }
-        // r = (o, tap): w[o][c][tap], read transposed
-        const int64_t wb = (int64_t)grp * g.Ng * g.K;
-        const uint32_t o = fdiv(rok ? r : 0, g.fT);
-        const int32_t roff = (int32_t)(o * g.K + (r - o * g.T));
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int32_t n = n0 + bn + 8 * i;
-            const bool ok = rok && n < N;
-            v[i] = ok ? a.w1[wb + (int64_t)n * g.T + roff] : 0.f;
-            v2[i] = ok ? a.w2[wb + (int64_t)n * g.T + roff] : 0.f;
+    // va, va2: DGRAD gather(G_m), gather(G_v); WGRAD gather(a_m), gather(a_v)
+    float va[16], va2[16], vb[8], vb2[8];
+    auto fetch = [&](int, int32_t r0) {
+        if constexpr (WG) {
+            c3_gather_positions(g, row, r0 + t.ah * 16, e.rend, [&](int j, bool ok, int64_t off, uint32_t) {
+                va[j] = ok ? a.a_m[off] : 0.f;
+                va2[j] = ok ? a.a_v[off] : 0.f;
+            });
+            c3_grad_rows(g, t, e.N, grp, r0 + t.bk, e.rend, [&](int i, bool ok, int64_t off, uint32_t, int32_t) {
+                vb[i] = ok ? a.g1[off] : 0.f;
+                vb2[i] = ok ? a.g2[off] : 0.f;
+            });
+        } else {
+            c3_gather_taps<MODE>(g, row, r0 + t.ah * 16, e.rend, [&](int j, bool ok, int32_t off, uint32_t) {
+                va[j] = ok ? a.g1[off] : 0.f;
+                va2[j] = ok ? a.g2[off] : 0.f;
+            });
+            c3_weight_rows<MODE>(g, t, e.N, grp, r0 + t.bk, e.rend, [&](int i, bool ok, int64_t off) {
+                vb[i] = ok ? a.w1[off] : 0.f;
+                vb2[i] = ok ? a.w2[off] : 0.f;
+            });
         }
     };
 
     // the derived plane in fp32, then rounded as the plain copies (bf16 mode; the fp32 mode forms it from the fragments)
-    auto store_tiles = [&](const float (&va)[16], const float (&va2)[16], const float (&vb)[8], const float (&vb2)[8]) {
-        T *pa = As + ar * LDK + ah * 16;
+    auto store = [&]() {
+        T *pa = c3_lds_a(As, t), *pb = c3_lds_b(Bs, t);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             st_lds(pa + j, va[j]);
@@ -1139,52 +554,24 @@ __global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d_bwd(const Conv3dG
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            T *pb = Bs + (bn + 8 * i) * LDK + bk;
-            st_lds(pb, vb[i]);
-            st_lds(pb + C3_BN * LDK, vb2[i]);
-            if constexpr (NB == 3) st_lds(pb + 2 * C3_BN * LDK, __builtin_fmaf(vb[i], vb[i], vb2[i]));
+            st_lds(pb + 8 * i * LDK, vb[i]);
+            st_lds(pb + (C3_BN + 8 * i) * LDK, vb2[i]);
+            if constexpr (NB == 3) st_lds(pb + (2 * C3_BN + 8 * i) * LDK, __builtin_fmaf(vb[i], vb[i], vb2[i]));
         }
     };
 
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc[3][4][2];
-#pragma unroll
-    for (int h = 0; h < 3; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int ntile = rend > rbeg ? (rend - rbeg + C3_BK - 1) / C3_BK : 0;
-    float va[16], va2[16], vb[8], vb2[8];
-    if (ntile > 0) { fetch_a(rbeg, va, va2); fetch_b(rbeg, vb, vb2); }
-    for (int step = 0; step < ntile; ++step) {
-        __syncthreads();                                // the previous tile's fragment reads are done
-        store_tiles(va, va2, vb, vb2);
-        __syncthreads();
-        if (step + 1 < ntile) {                         // the next tile's loads fly under this tile's MFMAs
-            fetch_a(rbeg + (step + 1) * C3_BK, va, va2);
-            fetch_b(rbeg + (step + 1) * C3_BK, vb, vb2);
-        }
+    c3_zero(acc);
+    auto compute = [&]() {
         if constexpr (BF) {
-            typedef short s16x8 __attribute__((ext_vector_type(8)));
             // stream h: A plane, B plane -- (0, 0), (1, 1), then G_v's plane again with the derived one
 #pragma unroll
             for (int h = 0; h < 3; ++h) {
                 const int ha = h < 2 ? h : (WG ? 2 : 1), hb = h < 2 ? h : (WG ? 1 : 2);
-                const T *A = As + ha * C3_BM * LDK, *Bt = Bs + hb * C3_BN * LDK;
-                s16x8 fa[4], fb[2];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    fa[i] = *reinterpret_cast<const s16x8 *>(A + (wm * 64 + i * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    fb[j] = *reinterpret_cast<const s16x8 *>(Bt + (wn * 32 + j * 16 + (lane & 15)) * LDK + (lane >> 4) * 8);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[h][i][j], 0, 0, 0);
+                typename Op<T>::frag fa[4], fb[2];
+                c3_frag_a<T>(fa, As + ha * C3_BM * LDK, t, 0);
+                c3_frag_b<T>(fb, Bs + hb * C3_BN * LDK, t, 0);
+                c3_mfma<T>(acc[h], fa, fb);
             }
         } else {
 #pragma unroll
@@ -1192,63 +579,37 @@ __global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d_bwd(const Conv3dG
                 float fa[3][4], fb[3][2];
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const T *A = As + h * C3_BM * LDK, *Bt = Bs + h * C3_BN * LDK;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) fa[h][i] = A[(wm * 64 + i * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) fb[h][j] = Bt[(wn * 32 + j * 16 + (lane & 15)) * LDK + kk * 4 + (lane >> 4)];
+                    c3_frag_a<T>(fa[h], As + h * C3_BM * LDK, t, kk);
+                    c3_frag_b<T>(fb[h], Bs + h * C3_BN * LDK, t, kk);
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) fa[2][i] = WG ? __builtin_fmaf(fa[0][i], fa[0][i], fa[1][i]) : fa[1][i];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) fb[2][j] = WG ? fb[1][j] : __builtin_fmaf(fb[0][j], fb[0][j], fb[1][j]);
 #pragma unroll
-                for (int h = 0; h < 3; ++h)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-                            acc[h][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[h][i], fb[h][j], acc[h][i][j], 0, 0, 0);
+                for (int h = 0; h < 3; ++h) c3_mfma<T>(acc[h], fa[h], fb[h]);
             }
         }
-    }
+    };
+    c3_pipeline(1, e.rbeg, e.rend, fetch, store, compute);
 
-    // ---- epilogue: lane holds C[(lane >> 4) * 4 + q][lane & 15] of each 16 x 16 block
     if constexpr (WG) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
-            if (n >= N) continue;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int32_t m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + q;
-                    if (m >= M) continue;
-                    // slab [slab][3][o][k]
-                    const int64_t plane = (int64_t)g.O * g.K, e = ((int64_t)slab * 3 * g.O + grp * g.Ng + n) * g.K + m;
-                    a.out[e] = acc[0][i][j][q];
-                    a.out[e + plane] = acc[1][i][j][q];
-                    a.out[e + 2 * plane] = acc[2][i][j][q];
-                }
-        }
+        c3_each_col(t, e.N, [&](int j, int32_t n) {
+            c3_each_row(t, e.M, [&](int i, int q, int32_t m) {
+                // slab [slab][3][o][k]
+                const int64_t plane = (int64_t)g.O * g.K, el = ((int64_t)k.slab * 3 * g.O + grp * g.Ng + n) * g.K + m;
+                a.out[el] = acc[0][i][j][q];
+                a.out[el + plane] = acc[1][i][j][q];
+                a.out[el + 2 * plane] = acc[2][i][j][q];
+            });
+        });
     } else {
         // a lane's quad runs along the input position: with Pin % 4 == 0 it is four consecutive elements of one image and channel
-        const bool vec = (g.Pin & 3) == 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int32_t n = n0 + wn * 32 + j * 16 + (lane & 15);
-            if (n >= N) continue;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int32_t mq = m0 + wm * 64 + i * 16 + (lane >> 4) * 4;
-                if (mq >= M) continue;
-                auto elem = [&](uint32_t m) {
-                    const uint32_t b = fdiv(m, g.fPin);
-                    return (b * (uint32_t)g.C + (uint32_t)(grp * g.Cg + n)) * (uint32_t)g.Pin + (m - b * (uint32_t)g.Pin);
-                };
+        const bool vec = c3_vec(g.Pin);
+        c3_each_col(t, e.N, [&](int j, int32_t n) {
+            c3_each_quad(t, e.M, [&](int i, int32_t mq) {
                 if (vec) {
-                    const uint32_t e0 = elem(mq);
+                    const uint32_t e0 = c3_elem(mq, g.fPin, g.Pin, g.C, grp * g.Cg + n);
                     float r1[4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) r1[q] = __builtin_fmaf(2.0f * a.a_m[e0 + q], acc[1][i][j][q], acc[0][i][j][q]);
@@ -1256,17 +617,17 @@ __global__ __launch_bounds__(C3_THREADS) void k_moments_conv3d_bwd(const Conv3dG
                     *reinterpret_cast<float4 *>(a.out2 + e0) =
                         make_float4(acc[2][i][j][0], acc[2][i][j][1], acc[2][i][j][2], acc[2][i][j][3]);
                 } else {
-                    const int nq = M - mq < 4 ? M - mq : 4;
+                    const int nq = e.M - mq < 4 ? e.M - mq : 4;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         if (q >= nq) continue;
-                        const uint32_t e = elem(mq + q);
-                        a.out[e] = __builtin_fmaf(2.0f * a.a_m[e], acc[1][i][j][q], acc[0][i][j][q]);
-                        a.out2[e] = acc[2][i][j][q];
+                        const uint32_t el = c3_elem(mq + q, g.fPin, g.Pin, g.C, grp * g.Cg + n);
+                        a.out[el] = __builtin_fmaf(2.0f * a.a_m[el], acc[1][i][j][q], acc[0][i][j][q]);
+                        a.out2[el] = acc[2][i][j][q];
                     }
                 }
-            }
-        }
+            });
+        });
     }
 }
 
@@ -1349,8 +710,6 @@ static int check_w(const char *who, const void *w, int64_t w_ss, const Conv3dGeo
     return BNN_OK;
 }
 
-static bool mis4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-
 // slabs of the weight gradient's reduction: about 1024 workgroups in all, at most 16 slabs, whole k-tiles each
 static void wgrad_split(const Conv3dGeo &g, int nsamples, int &nslab, int &chunk)
 {
@@ -1365,11 +724,23 @@ static void wgrad_split(const Conv3dGeo &g, int nsamples, int &nslab, int &chunk
     nslab = (int)((R + chunk - 1) / chunk);
 }
 
-template <int MODE, bool FLIP = false>
-static void launch(const Conv3dGeo &g, const Conv3dArgs &a, int compute, dim3 grid, hipStream_t st)
+// One launch of a tile kernel, the compute mode's instantiation of the pair: x over the rows of the mode's contraction, y over
+// its columns (c3_extents), z = nz, what the kernel's c3_block decodes.
+template <int MODE, typename Args>
+static void launch_tile(void (*kbf16)(Conv3dGeo, Args), void (*kf32)(Conv3dGeo, Args), const Conv3dGeo &g, const Args &a, int compute,
+                        int64_t nz, hipStream_t st)
 {
-    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_conv3d<uint16_t, MODE, FLIP>), grid, dim3(C3_THREADS), 0, st, g, a);
-    else hipLaunchKernelGGL((k_conv3d<float, MODE, FLIP>), grid, dim3(C3_THREADS), 0, st, g, a);
+    const int64_t M = MODE == C3_FWD ? (int64_t)g.B * g.P : MODE == C3_DGRAD ? (int64_t)g.B * g.Pin : g.K;
+    const int32_t N = MODE == C3_DGRAD ? g.Cg : g.Ng;
+    const dim3 grid((unsigned)((M + C3_BM - 1) / C3_BM), (unsigned)((N + C3_BN - 1) / C3_BN), (unsigned)nz);
+    const auto kernel = compute == BNN_COMPUTE_BF16 ? kbf16 : kf32;
+    hipLaunchKernelGGL(kernel, grid, dim3(C3_THREADS), 0, st, g, a);
+}
+
+template <int MODE, bool FLIP = false>
+static void launch(const Conv3dGeo &g, const Conv3dArgs &a, int compute, int64_t nz, hipStream_t st)
+{
+    launch_tile<MODE>(k_conv3d<uint16_t, MODE, FLIP>, k_conv3d<float, MODE, FLIP>, g, a, compute, nz, st);
 }
 
 // the Flipout entries' shared checks: K7's index ranges (conv3d_geo), groups == 1, the signs' layout
@@ -1389,7 +760,7 @@ static int check_signs(const char *who, const float *sg, int64_t sg_ss, const Co
         set_error("%s: bad sign sample stride", who);
         return BNN_E_SHAPE;
     }
-    if (mis4(sg)) { set_error("%s: misaligned signs", who); return BNN_E_ALIGN; }
+    if (misaligned(sg, 3)) { set_error("%s: misaligned signs", who); return BNN_E_ALIGN; }
     return BNN_OK;
 }
 
@@ -1400,14 +771,35 @@ static int64_t flip_w_std(const Conv3dGeo &g, int compute)
     return compute == BNN_COMPUTE_BF16 ? (n + 7) / 8 * 8 : n;
 }
 
-// K11 (LocalReparamConv1d / 2d / 3d): the entries' shared pieces
-static bool mis16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-
+// K11 (LocalReparamConv1d / 2d / 3d)
 template <int MODE>
-static void lrt_conv_launch(const Conv3dGeo &g, const LrtConvArgs &a, int compute, dim3 grid, hipStream_t st)
+static void lrt_conv_launch(const Conv3dGeo &g, const LrtConvArgs &a, int compute, int64_t nz, hipStream_t st)
 {
-    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_lrt_conv3d<uint16_t, MODE>), grid, dim3(C3_THREADS), 0, st, g, a);
-    else hipLaunchKernelGGL((k_lrt_conv3d<float, MODE>), grid, dim3(C3_THREADS), 0, st, g, a);
+    launch_tile<MODE>(k_lrt_conv3d<uint16_t, MODE>, k_lrt_conv3d<float, MODE>, g, a, compute, nz, st);
+}
+
+// K17: the instantiation with the a_v planes for an input that carries a variance
+static void mom_conv_launch(const Conv3dGeo &g, const MomConvArgs &a, int compute, hipStream_t st)
+{
+    if (a.a_v) launch_tile<C3_FWD>(k_moments_conv3d<uint16_t, true>, k_moments_conv3d<float, true>, g, a, compute, g.groups, st);
+    else launch_tile<C3_FWD>(k_moments_conv3d<uint16_t, false>, k_moments_conv3d<float, false>, g, a, compute, g.groups, st);
+}
+
+// K19
+template <int MODE>
+static void mom_conv_bwd_launch(const Conv3dGeo &g, const MomConvBwdArgs &a, int compute, int64_t nz, hipStream_t st)
+{
+    launch_tile<MODE>(k_moments_conv3d_bwd<uint16_t, MODE>, k_moments_conv3d_bwd<float, MODE>, g, a, compute, nz, st);
+}
+
+// K17 / K19: the shape with B == 0 admitted (every check runs on one image; the entry launches no tile)
+static int conv3d_geo_b0(const char *who, const bnn_conv3d_shape_t *shape, int compute, Conv3dGeo &g, bool &empty)
+{
+    if (!shape) { set_error("%s: NULL shape", who); return BNN_E_NULL; }
+    bnn_conv3d_shape_t sh = *shape;
+    empty = sh.B == 0;
+    if (empty) sh.B = 1;
+    return conv3d_geo(who, &sh, 1, compute, g);
 }
 
 }  // namespace bnn
@@ -1427,12 +819,11 @@ int bnn_conv3d_forward_drawn(const float *x, int64_t x_sample_stride, const void
     if (!x || !y) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
     if ((rc = check_w(who, w, w_sample_stride, g, nsamples, compute))) return rc;
     if (x_sample_stride < 0 || b_sample_stride < 0) { set_error("%s: negative sample stride", who); return BNN_E_SHAPE; }
-    if (mis4(x) || mis4(y) || mis4(b)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    if (misaligned(x, 3) || misaligned(y, 3) || misaligned(b, 3)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
     Conv3dArgs a{};
     a.x = x; a.x_ss = x_sample_stride; a.w = w; a.w_ss = w_sample_stride; a.bias = b; a.b_ss = b_sample_stride; a.out = y;
     a.S = nsamples; a.shared = x_sample_stride == 0;
-    const dim3 grid((unsigned)(((int64_t)g.B * g.P + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN), (unsigned)(nsamples * g.groups));
-    launch<C3_FWD>(g, a, compute, grid, (hipStream_t)stream);
+    launch<C3_FWD>(g, a, compute, nsamples * g.groups, (hipStream_t)stream);
     return check_launch(who);
 }
 
@@ -1445,12 +836,10 @@ int bnn_conv3d_backward_input(const float *gy, const void *w, int64_t w_sample_s
     if (rc) return rc;
     if (!gy || !gx) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
     if ((rc = check_w(who, w, w_sample_stride, g, nsamples, compute))) return rc;
-    if (mis4(gy) || mis4(gx)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    if (misaligned(gy, 3) || misaligned(gx, 3)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
     Conv3dArgs a{};
     a.gy = gy; a.w = w; a.w_ss = w_sample_stride; a.out = gx; a.S = nsamples; a.shared = shared_x ? 1 : 0;
-    const dim3 grid((unsigned)(((int64_t)g.B * g.Pin + C3_BM - 1) / C3_BM), (unsigned)((g.Cg + C3_BN - 1) / C3_BN),
-                    (unsigned)((shared_x ? 1 : nsamples) * g.groups));
-    launch<C3_DGRAD>(g, a, compute, grid, (hipStream_t)stream);
+    launch<C3_DGRAD>(g, a, compute, (shared_x ? 1 : nsamples) * g.groups, (hipStream_t)stream);
     return check_launch(who);
 }
 
@@ -1473,7 +862,10 @@ int bnn_conv3d_backward_weight(const float *x, int64_t x_sample_stride, const fl
     if (rc) return rc;
     if (!gy || (gw && !x) || (!gw && !gb)) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
     if (x_sample_stride < 0) { set_error("%s: negative sample stride", who); return BNN_E_SHAPE; }
-    if (mis4(x) || mis4(gy) || mis4(gw) || mis4(gb) || mis4(workspace)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    if (misaligned(x, 3) || misaligned(gy, 3) || misaligned(gw, 3) || misaligned(gb, 3) || misaligned(workspace, 3)) {
+        set_error("%s: misaligned pointer", who);
+        return BNN_E_ALIGN;
+    }
     hipStream_t st = (hipStream_t)stream;
     if (gw) {
         int nslab, chunk;
@@ -1486,8 +878,7 @@ int bnn_conv3d_backward_weight(const float *x, int64_t x_sample_stride, const fl
         Conv3dArgs a{};
         a.x = x; a.x_ss = x_sample_stride; a.gy = gy; a.out = nslab > 1 ? static_cast<float *>(workspace) : gw;
         a.S = nsamples; a.nslab = nslab; a.chunk = chunk;
-        const dim3 grid((unsigned)((g.K + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN), (unsigned)(nsamples * g.groups * nslab));
-        launch<C3_WGRAD>(g, a, compute, grid, st);
+        launch<C3_WGRAD>(g, a, compute, nsamples * g.groups * nslab, st);
         if ((rc = check_launch(who))) return rc;
         if (nslab > 1) {
             hipLaunchKernelGGL(k_conv3d_slab_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace), n,
@@ -1513,12 +904,11 @@ int bnn_conv3d_flipout_forward(const float *x, int64_t x_sample_stride, const vo
     if ((rc = check_w(who, w, 0, g, nsamples, compute))) return rc;
     if ((rc = check_signs(who, signs, sign_sample_stride, g, nsamples))) return rc;
     if (x_sample_stride < 0) { set_error("%s: negative sample stride", who); return BNN_E_SHAPE; }
-    if (mis4(x) || mis4(y)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    if (misaligned(x, 3) || misaligned(y, 3)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
     Conv3dArgs a{};
     a.x = x; a.x_ss = x_sample_stride; a.w = w; a.w_std = flip_w_std(g, compute); a.out = y;
     a.sg = signs; a.sg_ss = sign_sample_stride; a.S = nsamples; a.shared = x_sample_stride == 0;
-    const dim3 grid((unsigned)(((int64_t)g.B * g.P + C3_BM - 1) / C3_BM), (unsigned)((g.O + C3_BN - 1) / C3_BN), (unsigned)nsamples);
-    launch<C3_FWD, true>(g, a, compute, grid, (hipStream_t)stream);
+    launch<C3_FWD, true>(g, a, compute, nsamples, (hipStream_t)stream);
     return check_launch(who);
 }
 
@@ -1532,13 +922,11 @@ int bnn_conv3d_flipout_backward_input(const float *gy, const void *w, const floa
     if (!gy || !gx) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
     if ((rc = check_w(who, w, 0, g, nsamples, compute))) return rc;
     if ((rc = check_signs(who, signs, sign_sample_stride, g, nsamples))) return rc;
-    if (mis4(gy) || mis4(gx)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    if (misaligned(gy, 3) || misaligned(gx, 3)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
     Conv3dArgs a{};
     a.gy = gy; a.w = w; a.w_std = flip_w_std(g, compute); a.out = gx; a.S = nsamples; a.shared = shared_x ? 1 : 0;
     a.sg = signs; a.sg_ss = sign_sample_stride;
-    const dim3 grid((unsigned)(((int64_t)g.B * g.Pin + C3_BM - 1) / C3_BM), (unsigned)((g.C + C3_BN - 1) / C3_BN),
-                    (unsigned)(shared_x ? 1 : nsamples));
-    launch<C3_DGRAD, true>(g, a, compute, grid, (hipStream_t)stream);
+    launch<C3_DGRAD, true>(g, a, compute, shared_x ? 1 : nsamples, (hipStream_t)stream);
     return check_launch(who);
 }
 
@@ -1563,7 +951,7 @@ int bnn_conv3d_flipout_backward_weight(const float *x, int64_t x_sample_stride, 
     if (!x || !gy || !rho || !g_mean || !g_scale) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
     if ((rc = check_signs(who, signs, sign_sample_stride, g, nsamples))) return rc;
     if (x_sample_stride < 0) { set_error("%s: negative sample stride", who); return BNN_E_SHAPE; }
-    if (mis4(x) || mis4(gy) || mis4(rho) || mis4(g_mean) || mis4(g_scale) || mis4(workspace)) {
+    if (misaligned(x, 3) || misaligned(gy, 3) || misaligned(rho, 3) || misaligned(g_mean, 3) || misaligned(g_scale, 3) || misaligned(workspace, 3)) {
         set_error("%s: misaligned pointer", who);
         return BNN_E_ALIGN;
     }
@@ -1578,8 +966,7 @@ int bnn_conv3d_flipout_backward_weight(const float *x, int64_t x_sample_stride, 
     Conv3dArgs a{};
     a.x = x; a.x_ss = x_sample_stride; a.gy = gy; a.out = static_cast<float *>(workspace);
     a.S = nsamples; a.nslab = nslab; a.chunk = chunk; a.sg = signs; a.sg_ss = sign_sample_stride;
-    const dim3 grid((unsigned)((g.K + C3_BM - 1) / C3_BM), (unsigned)((g.O + C3_BN - 1) / C3_BN), (unsigned)(nsamples * nslab));
-    launch<C3_WGRAD, true>(g, a, compute, grid, st);
+    launch<C3_WGRAD, true>(g, a, compute, nsamples * nslab, st);
     if ((rc = check_launch(who))) return rc;
     hipLaunchKernelGGL(k_conv3d_flip_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
                        nslab, nsamples, rho, g_mean, g_scale, n);
@@ -1599,7 +986,8 @@ int bnn_conv3d_lrt_forward(const float *x, int64_t x_sample_stride, const float 
     if (!rng) { set_error("%s: NULL rng", who); return BNN_E_NULL; }
     if (x_sample_stride < 0) { set_error("%s: negative sample stride", who); return BNN_E_SHAPE; }
     if ((rc = check_rng(rng, nsamples))) { set_error("%s: bad rng", who); return rc; }
-    if (mis4(x) || mis4(mu_w) || mis4(s2_w) || mis4(mu_b) || mis4(s2_b) || mis16(y) || mis16(v_out)) {
+    if (misaligned(x, 3) || misaligned(mu_w, 3) || misaligned(s2_w, 3) || misaligned(mu_b, 3) || misaligned(s2_b, 3) ||
+        misaligned(y, 15) || misaligned(v_out, 15)) {
         set_error("%s: misaligned pointer (y and v: 16 bytes)", who);
         return BNN_E_ALIGN;
     }
@@ -1607,9 +995,7 @@ int bnn_conv3d_lrt_forward(const float *x, int64_t x_sample_stride, const float 
     a.x = x; a.x_ss = x_sample_stride; a.w1 = mu_w; a.w2 = s2_w; a.b1 = mu_b; a.b2 = s2_b; a.out = y; a.out2 = v_out;
     a.S = nsamples; a.shared = x_sample_stride == 0;
     a.rng = make_rng(rng);
-    const dim3 grid((unsigned)(((int64_t)g.B * g.P + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN),
-                    (unsigned)((a.shared ? 1 : nsamples) * g.groups));
-    lrt_conv_launch<C3_FWD>(g, a, compute, grid, (hipStream_t)stream);
+    lrt_conv_launch<C3_FWD>(g, a, compute, (a.shared ? 1 : nsamples) * g.groups, (hipStream_t)stream);
     return check_launch(who);
 }
 
@@ -1621,12 +1007,13 @@ int bnn_conv3d_lrt_backward_input(const float *g_m, const float *g_v, const floa
     int rc = conv3d_geo(who, shape, nsets, compute, g);
     if (rc) return rc;
     if (!g_m || !g_v || !mu_w || !s2_w || !x || !gx) { set_error("%s: NULL pointer", who); return BNN_E_NULL; }
-    if (mis4(g_m) || mis4(g_v) || mis4(mu_w) || mis4(s2_w) || mis4(x) || mis4(gx)) { set_error("%s: misaligned pointer", who); return BNN_E_ALIGN; }
+    if (misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(mu_w, 3) || misaligned(s2_w, 3) || misaligned(x, 3) || misaligned(gx, 3)) {
+        set_error("%s: misaligned pointer", who);
+        return BNN_E_ALIGN;
+    }
     LrtConvArgs a{};
     a.g1 = g_m; a.g2 = g_v; a.w1 = mu_w; a.w2 = s2_w; a.x = x; a.x_ss = (int64_t)g.B * g.C * g.Pin; a.out = gx; a.S = nsets;
-    const dim3 grid((unsigned)(((int64_t)g.B * g.Pin + C3_BM - 1) / C3_BM), (unsigned)((g.Cg + C3_BN - 1) / C3_BN),
-                    (unsigned)(nsets * g.groups));
-    lrt_conv_launch<C3_DGRAD>(g, a, compute, grid, (hipStream_t)stream);
+    lrt_conv_launch<C3_DGRAD>(g, a, compute, nsets * g.groups, (hipStream_t)stream);
     return check_launch(who);
 }
 
@@ -1653,8 +1040,8 @@ int bnn_conv3d_lrt_backward_weight(const float *x, const float *g_m, const float
         set_error("%s: NULL pointer", who);
         return BNN_E_NULL;
     }
-    if (mis4(x) || mis4(g_m) || mis4(g_v) || mis4(rho_w) || mis4(g_mu_w) || mis4(g_rho_w) || mis4(rho_b) || mis4(g_mu_b) ||
-        mis4(g_rho_b) || mis4(workspace)) {
+    if (misaligned(x, 3) || misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(rho_w, 3) || misaligned(g_mu_w, 3) ||
+        misaligned(g_rho_w, 3) || misaligned(rho_b, 3) || misaligned(g_mu_b, 3) || misaligned(g_rho_b, 3) || misaligned(workspace, 3)) {
         set_error("%s: misaligned pointer", who);
         return BNN_E_ALIGN;
     }
@@ -1669,8 +1056,7 @@ int bnn_conv3d_lrt_backward_weight(const float *x, const float *g_m, const float
     LrtConvArgs a{};
     a.x = x; a.x_ss = (int64_t)g.B * g.C * g.Pin; a.g1 = g_m; a.g2 = g_v; a.out = static_cast<float *>(workspace);
     a.S = nsets; a.nslab = nslab; a.chunk = chunk;
-    const dim3 grid((unsigned)((g.K + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN), (unsigned)(g.groups * nslab));
-    lrt_conv_launch<C3_WGRAD>(g, a, compute, grid, st);
+    lrt_conv_launch<C3_WGRAD>(g, a, compute, g.groups * nslab, st);
     if ((rc = check_launch(who))) return rc;
     hipLaunchKernelGGL(k_lrt_conv_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
                        nslab, rho_w, g_mu_w, g_rho_w, n);
@@ -1686,12 +1072,9 @@ int bnn_conv3d_moments_forward(const float *a_m, const float *a_v, const float *
                                int flags, float elu_alpha, void *stream)
 {
     const char *who = "bnn_conv3d_moments_forward";
-    if (!shape) { set_error("%s: NULL shape", who); return BNN_E_NULL; }
-    bnn_conv3d_shape_t sh = *shape;
-    const bool empty = sh.B == 0;               // no images: every other check still runs, nothing is launched
-    if (empty) sh.B = 1;
     Conv3dGeo g;
-    const int rc = conv3d_geo(who, &sh, 1, compute, g);
+    bool empty;                                 // no images: every other check still runs, nothing is launched
+    const int rc = conv3d_geo_b0(who, shape, compute, g, empty);
     if (rc) return rc;
     if (!a_m || !mu_w || !s2_w || !out_m || !out_v || (mu_b == nullptr) != (s2_b == nullptr)) {
         set_error("%s: NULL pointer (mu_b and s2_b: both or neither)", who);
@@ -1706,7 +1089,8 @@ int bnn_conv3d_moments_forward(const float *a_m, const float *a_v, const float *
         set_error("%s: elu_alpha must be finite and >= 0", who);
         return BNN_E_RANGE;
     }
-    if (mis4(a_m) || mis4(a_v) || mis4(mu_w) || mis4(s2_w) || mis4(mu_b) || mis4(s2_b) || mis16(out_m) || mis16(out_v)) {
+    if (misaligned(a_m, 3) || misaligned(a_v, 3) || misaligned(mu_w, 3) || misaligned(s2_w, 3) || misaligned(mu_b, 3) ||
+        misaligned(s2_b, 3) || misaligned(out_m, 15) || misaligned(out_v, 15)) {
         set_error("%s: misaligned pointer (out_m and out_v: 16 bytes)", who);
         return BNN_E_ALIGN;
     }
@@ -1716,28 +1100,15 @@ int bnn_conv3d_moments_forward(const float *a_m, const float *a_v, const float *
     a.a_m = a_m; a.a_v = a_v; a.w1 = mu_w; a.w2 = s2_w; a.b1 = mu_b; a.b2 = s2_b; a.out_m = out_m; a.out_v = out_v;
     a.act = flags & (BNN_FLAG_RELU | BNN_FLAG_ELU);
     a.elu_alpha = elu_alpha;
-    const dim3 grid((unsigned)(((int64_t)g.B * g.P + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN), (unsigned)g.groups);
-    const dim3 block(C3_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (compute == BNN_COMPUTE_BF16) {
-        if (a_v) hipLaunchKernelGGL((k_moments_conv3d<uint16_t, true>), grid, block, 0, st, g, a);
-        else hipLaunchKernelGGL((k_moments_conv3d<uint16_t, false>), grid, block, 0, st, g, a);
-    } else {
-        if (a_v) hipLaunchKernelGGL((k_moments_conv3d<float, true>), grid, block, 0, st, g, a);
-        else hipLaunchKernelGGL((k_moments_conv3d<float, false>), grid, block, 0, st, g, a);
-    }
+    mom_conv_launch(g, a, compute, (hipStream_t)stream);
     return check_launch(who);
 }
 
 // ---- K19 entries (the backward of bnn_conv3d_moments_forward for an input that carries a variance) ----------------------------
-// the shape with B == 0 admitted (every other check runs on one image) and the grid's y range
+// the shape with B == 0 admitted and the grid's y range
 static int momb_conv_geo(const char *who, const bnn_conv3d_shape_t *shape, int compute, Conv3dGeo &g, bool &empty)
 {
-    if (!shape) { set_error("%s: NULL shape", who); return BNN_E_NULL; }
-    bnn_conv3d_shape_t sh = *shape;
-    empty = sh.B == 0;
-    if (empty) sh.B = 1;
-    const int rc = conv3d_geo(who, &sh, 1, compute, g);
+    const int rc = conv3d_geo_b0(who, shape, compute, g, empty);
     if (rc) return rc;
     if ((g.Ng + C3_BN - 1) / C3_BN > 65535 || (g.Cg + C3_BN - 1) / C3_BN > 65535) {
         set_error("%s: more than 64 * 65535 channels per group", who);
@@ -1759,18 +1130,15 @@ int bnn_conv3d_moments_backward_input(const float *g_m, const float *g_v, const 
         set_error("%s: NULL g_a_v (a deterministic input takes bnn_conv3d_lrt_backward_input with nsets = 1)", who);
         return BNN_E_NULL;
     }
-    if (mis4(g_m) || mis4(g_v) || mis4(mu_w) || mis4(s2_w) || mis4(a_m) || mis16(g_a_m) || mis16(g_a_v)) {
+    if (misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(mu_w, 3) || misaligned(s2_w, 3) || misaligned(a_m, 3) ||
+        misaligned(g_a_m, 15) || misaligned(g_a_v, 15)) {
         set_error("%s: misaligned pointer (g_a_m and g_a_v: 16 bytes)", who);
         return BNN_E_ALIGN;
     }
     if (empty) return BNN_OK;
     MomConvBwdArgs a{};
     a.g1 = g_m; a.g2 = g_v; a.w1 = mu_w; a.w2 = s2_w; a.a_m = a_m; a.out = g_a_m; a.out2 = g_a_v;
-    const dim3 grid((unsigned)(((int64_t)g.B * g.Pin + C3_BM - 1) / C3_BM), (unsigned)((g.Cg + C3_BN - 1) / C3_BN), (unsigned)g.groups);
-    const dim3 block(C3_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_moments_conv3d_bwd<uint16_t, C3_DGRAD>), grid, block, 0, st, g, a);
-    else hipLaunchKernelGGL((k_moments_conv3d_bwd<float, C3_DGRAD>), grid, block, 0, st, g, a);
+    mom_conv_bwd_launch<C3_DGRAD>(g, a, compute, g.groups, (hipStream_t)stream);
     return check_launch(who);
 }
 
@@ -1803,8 +1171,9 @@ int bnn_conv3d_moments_backward_weight(const float *a_m, const float *a_v, const
         set_error("%s: NULL a_v (a deterministic input takes bnn_conv3d_lrt_backward_weight with nsets = 1)", who);
         return BNN_E_NULL;
     }
-    if (mis4(a_m) || mis4(a_v) || mis4(g_m) || mis4(g_v) || mis4(mu_w) || mis4(rho_w) || mis16(g_mu_w) || mis16(g_rho_w) ||
-        mis4(rho_b) || mis4(g_mu_b) || mis4(g_rho_b) || mis4(workspace)) {
+    if (misaligned(a_m, 3) || misaligned(a_v, 3) || misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(mu_w, 3) ||
+        misaligned(rho_w, 3) || misaligned(g_mu_w, 15) || misaligned(g_rho_w, 15) || misaligned(rho_b, 3) || misaligned(g_mu_b, 3) ||
+        misaligned(g_rho_b, 3) || misaligned(workspace, 3)) {
         set_error("%s: misaligned pointer (g_mu_w and g_rho_w: 16 bytes)", who);
         return BNN_E_ALIGN;
     }
@@ -1821,10 +1190,7 @@ int bnn_conv3d_moments_backward_weight(const float *a_m, const float *a_v, const
         MomConvBwdArgs a{};
         a.a_m = a_m; a.a_v = a_v; a.g1 = g_m; a.g2 = g_v; a.out = static_cast<float *>(workspace);
         a.nslab = nslab; a.chunk = chunk;
-        const dim3 grid((unsigned)((g.K + C3_BM - 1) / C3_BM), (unsigned)((g.Ng + C3_BN - 1) / C3_BN), (unsigned)(g.groups * nslab));
-        const dim3 block(C3_THREADS);
-        if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_moments_conv3d_bwd<uint16_t, C3_WGRAD>), grid, block, 0, st, g, a);
-        else hipLaunchKernelGGL((k_moments_conv3d_bwd<float, C3_WGRAD>), grid, block, 0, st, g, a);
+        mom_conv_bwd_launch<C3_WGRAD>(g, a, compute, g.groups * nslab, st);
         if ((rc = check_launch(who))) return rc;
     }
     hipLaunchKernelGGL(k_moments_conv_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
