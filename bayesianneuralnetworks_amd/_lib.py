@@ -21,6 +21,9 @@ FLAG_X_BF16 = 2
 E_ALIGN, E_UNSUPPORTED, E_DEVICE = -4, -6, -7     # BNN_E_ALIGN, BNN_E_UNSUPPORTED, BNN_E_DEVICE (include/bnn_hip.h)
 FLAG_Y_BF16 = 4
 FLAG_ELU = 8                                     # BNN_FLAG_ELU (bnn_conv3d_moments_forward)
+POOL_MAX, POOL_AVG = 0, 1                        # BNN_POOL_MAX, BNN_POOL_AVG (bnn_moments_pool3d_forward / _backward)
+POOL_FLAG_VALID_DIVISOR = 1                      # BNN_POOL_FLAG_VALID_DIVISOR
+POOL_WINDOW_CAP = 64                             # elements per pooling window (csrc/bnn_moments_pool.hip: kPoolWindowCap)
 UNC_LOGITS, UNC_PROBS = 0, 1                     # BNN_UNC_* (bnn_mc_uncertainty)
 REG_VALUES, REG_MEAN_LOGVAR, REG_MEAN_VAR = 0, 1, 2     # BNN_REG_* (bnn_mc_regression)
 
@@ -85,6 +88,13 @@ class Conv3dShape(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in
                 ("B", "C", "D", "H", "W", "O", "KD", "KH", "KW", "stride_d", "stride_h", "stride_w",
                  "pad_d", "pad_h", "pad_w", "dil_d", "dil_h", "dil_w", "groups")]
+
+
+class Pool3dShape(ctypes.Structure):
+    """bnn_pool3d_shape_t"""
+    _fields_ = [(n, ctypes.c_int64) for n in
+                ("B", "C", "D", "H", "W", "KD", "KH", "KW", "stride_d", "stride_h", "stride_w",
+                 "pad_d", "pad_h", "pad_w", "dil_d", "dil_h", "dil_w")]
 
 
 class MvnTensor(ctypes.Structure):
@@ -239,6 +249,9 @@ SIGNATURES = {
     "bnn_conv3d_moments_backward_weight": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _p,
                                                   _i64, _p]),
     "bnn_moments_elu_backward": (_int, [_p, _p, _p, _p, _p, _p, _i64, ctypes.c_float, _p]),
+    "bnn_moments_pool3d_forward": (_int, [_p, _p, _p, _p, ctypes.POINTER(Pool3dShape), _int, _int, _p]),
+    "bnn_moments_pool3d_backward": (_int, [_p, _p, _p, _p, _p, _p, ctypes.POINTER(Pool3dShape), _int, _int, _p]),
+    "bnn_moments_batchnorm": (_int, [_p, _p, _p, _p, _p, _p, ctypes.c_float, _p, _p, _i64, _i64, _i64, _p]),
 }
 
 _lib = None

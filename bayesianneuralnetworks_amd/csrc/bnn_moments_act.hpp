@@ -1,7 +1,8 @@
 // bnn_moments_act.hpp -- moment-matched activations of a Gaussian pre-activation N(m, v): the device functions that the fused
 // epilogues (k_moments, bnn_moments.hip; k_moments_conv3d, bnn_conv3d.hip) and the standalone elementwise launches
 // (k_moments_relu, k_moments_elu) both call, so that fused and standalone agree bit for bit; and their backwards
-// (k_moments_relu_bwd, k_moments_elu_bwd, bnn_moments_bwd.hip).
+// (k_moments_relu_bwd, k_moments_elu_bwd, bnn_moments_bwd.hip).  K20: the moment-matched maximum of two Gaussians, the step a
+// max-pooling window is folded with, and its backward (k_moments_pool3d, k_moments_pool3d_bwd, bnn_moments_pool.hip).
 #pragma once
 #include "bnn_device.hpp"
 
@@ -145,6 +146,79 @@ __device__ __forceinline__ void moments_elu_bwd_dev(float mf, float vf, float a_
     const double dm = cdf + a * e1, dv = a * e1 + (1.0 - a) * pdf / s;
     gm = (float)((double)gom * dm + go_v * (2.0 * p1 + 2.0 * a * a * (e2 - e1) - 2.0 * mean * dm));
     gv = (float)((double)gom * (0.5 * dv) + go_v * (cdf + a * a * (2.0 * e2 - e1) - mean * dv));
+}
+
+// Maximum of two independent Gaussians N(m1, v1), N(m2, v2) by moment matching (K20; Clark 1961), the step a max-pooling window
+// is folded with.  theta^2 = v1 + v2, d = m1 - m2, alpha = d / theta, Phi = Phi(alpha), Phi_c = Phi(-alpha), phi = phi(alpha):
+//     mean' = m1 Phi + m2 Phi_c + theta phi
+//     var'  = v1 Phi + v2 Phi_c + d^2 Phi Phi_c + d theta phi (Phi_c - Phi) - theta^2 phi^2,   clamped at 0
+// -- the ReLU's form above with (m2, v2) = (0, 0): m^2 is never subtracted from m^2 + v, and what cancels is relative to d^2, not
+// to v, so the step works in fp64 like the ELU (the running maximum of a window stays fp64 until the window's one rounding).
+// The smaller tail is 0.5 erfc(|alpha| / sqrt 2) and the other one its complement; beyond |alpha| = 39 tail and phi are zero in
+// fp64 and the larger input passes exactly.  theta^2 == 0 (both variances zero; a NaN takes this branch too) is the plain
+// maximum: the larger element's (m, v), the first one on a tie.
+struct MaxTerms { double theta, d, cdf, cdc, pdf, sum; bool plain; };      // sum: var' before its clamp
+
+__device__ __forceinline__ void moments_max_terms(double m1, double v1, double m2, double v2, MaxTerms &t)
+{
+    const double th2 = v1 + v2;
+    t.plain = !(th2 > 0.0);
+    if (t.plain) return;
+    t.theta = sqrt(th2);
+    t.d = m1 - m2;
+    const double alpha = t.d / t.theta;
+    const double h = 0.5 * erfc(0.70710678118654752 * fabs(alpha));
+    t.cdc = alpha >= 0.0 ? h : 1.0 - h;
+    t.cdf = alpha >= 0.0 ? 1.0 - h : h;
+    t.pdf = 0.39894228040143268 * exp(-0.5 * alpha * alpha);
+    const double tp = t.theta * t.pdf;
+    t.sum = v1 * t.cdf + v2 * t.cdc + t.d * t.d * t.cdf * t.cdc + t.d * tp * (t.cdc - t.cdf) - tp * tp;
+}
+
+// (m1, v1) <- the moment-matched maximum of (m1, v1) and (m2, v2)
+__device__ __forceinline__ void moments_max_step(double &m1, double &v1, double m2, double v2)
+{
+    MaxTerms t;
+    moments_max_terms(m1, v1, m2, v2, t);
+    if (t.plain) {
+        if (m2 > m1) { m1 = m2; v1 = v2; }
+        return;
+    }
+    m1 = m1 * t.cdf + m2 * t.cdc + t.theta * t.pdf;
+    v1 = fmax(t.sum, 0.0);
+}
+
+// Backward of moments_max_step on the same terms: from (gm, gv), the gradients of its two results, the gradients of the second
+// operand (g2m, g2v); (gm, gv) become those of the first.  With M = mean' (m1 - M = d Phi_c - theta phi, m2 - M = -d Phi -
+// theta phi: the shifted forms, nothing of the size of the means cancels):
+//     d mean'/d m1 = Phi          d mean'/d m2 = Phi_c          d mean'/d v1 = d mean'/d v2 = phi / (2 theta)
+//     d var'/d m1  = 2 Phi (d Phi_c - theta phi) + 2 v1 phi / theta
+//     d var'/d m2  = -2 Phi_c (d Phi + theta phi) + 2 v2 phi / theta
+//     d var'/d v1  = Phi + alpha v2 phi / theta^2 - (d Phi + theta phi) phi / theta
+//     d var'/d v2  = Phi_c - alpha v1 phi / theta^2 + (d Phi_c - theta phi) phi / theta
+// Where the step clamped var' (decided on its own sum) the gv terms are absent; the plain maximum sends both gradients to the
+// element it took.
+__device__ __forceinline__ void moments_max_step_bwd(double m1, double v1, double m2, double v2, double &gm, double &gv, double &g2m,
+                                                     double &g2v)
+{
+    MaxTerms t;
+    moments_max_terms(m1, v1, m2, v2, t);
+    if (t.plain) {
+        const bool second = m2 > m1;
+        g2m = second ? gm : 0.0;
+        g2v = second ? gv : 0.0;
+        if (second) { gm = 0.0; gv = 0.0; }
+        return;
+    }
+    const double go_v = t.sum < 0.0 ? 0.0 : gv;
+    const double pt = t.pdf / t.theta, tp = t.theta * t.pdf, apt = t.d * pt / (t.theta * t.theta);      // alpha phi / theta^2
+    const double up = t.d * t.cdf + tp, dn = t.d * t.cdc - tp;                                          // M - m2, m1 - M
+    const double g1m = gm * t.cdf + go_v * (2.0 * t.cdf * dn + 2.0 * v1 * pt);
+    const double g1v = gm * (0.5 * pt) + go_v * (t.cdf + v2 * apt - up * pt);
+    g2m = gm * t.cdc + go_v * (-2.0 * t.cdc * up + 2.0 * v2 * pt);
+    g2v = gm * (0.5 * pt) + go_v * (t.cdc - v1 * apt + dn * pt);
+    gm = g1m;
+    gv = g1v;
 }
 
 }  // namespace bnn

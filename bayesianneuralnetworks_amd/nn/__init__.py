@@ -1,5 +1,8 @@
 from .container import BayesianModule, BayesianNetworkModule
 from .container import MomentReLU, MomentELU, MomentLinear, MomentSoftmax   # (not in __all__: that list is the reference's)
+from .container import (MomentMaxPool1d, MomentMaxPool2d, MomentMaxPool3d, MomentAvgPool1d, MomentAvgPool2d, MomentAvgPool3d,
+                        MomentAdaptiveAvgPool1d, MomentAdaptiveAvgPool2d, MomentAdaptiveAvgPool3d,
+                        MomentBatchNorm1d, MomentBatchNorm2d, MomentBatchNorm3d)   # (K20; not in __all__ either)
 from .core import WeightNormal, WeightMultivariateNormal
 from .dense import (BayesianLinear, NormalLinear, MultivariateNormalLinear, FlipoutNormalLinear,
                     NormalInverseGaussianLinear, MCDropoutLinear,

@@ -130,6 +130,11 @@ def moment_activations(module):
     * a `torch.nn.Linear` that lies behind a Bayesian layer of the same Sequential (the CIFAR10 example has one) becomes an
       `nn.MomentLinear` IN PLACE (the module is re-classed: its parameters and hooks are its own): a deterministic dense layer
       that hands moments on, m = a_m w^T + b, v = a_v (w^2)^T.
+    * likewise behind a Bayesian layer of the same Sequential (K20), and re-classed in place in the same way: `torch.nn.MaxPool1d /
+      2d / 3d`, `AvgPool1d / 2d / 3d`, `AdaptiveAvgPool1d / 2d / 3d` and `BatchNorm1d / 2d / 3d` become `nn.MomentMaxPool*`,
+      `nn.MomentAvgPool*`, `nn.MomentAdaptiveAvgPool*` and `nn.MomentBatchNorm*` (their parent on tensors; a BatchNorm keeps its
+      parameters and buffers).  In front of the first Bayesian layer they stay what they are.  A pool directly behind a conv
+      layer gets that layer's plain moments (no activation is fused in front of it).
     * a twin directly behind a NormalConv1d / 2d / 3d or LocalReparamConv1d / 2d / 3d is made known to that layer
       (`_moment_act`, a __dict__ entry, not a submodule): in a moment pass the activation runs in the conv launch's epilogue
       (the standalone launch's bits) and the twin passes the result through.  Behind a dense layer the twins use the
@@ -137,7 +142,7 @@ def moment_activations(module):
 
     Idempotent; state_dict keys are unchanged (the activations have no state).  Returns the number of modules replaced."""
     import torch
-    from .container import BayesianModule, MomentReLU, MomentELU, MomentLinear, MomentSoftmax
+    from .container import BayesianModule, MomentReLU, MomentELU, MomentLinear, MomentSoftmax, _MOMENT_RECLASS
     from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
     convs = (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
     replaced = 0
@@ -149,6 +154,9 @@ def moment_activations(module):
             twin = None
             if type(child) is torch.nn.Linear and behind:
                 child.__class__ = MomentLinear
+                replaced += 1
+            elif type(child) in _MOMENT_RECLASS and behind:
+                child.__class__ = _MOMENT_RECLASS[type(child)]
                 replaced += 1
             behind = behind or isinstance(child, BayesianModule)
             if type(child) is torch.nn.ReLU:

@@ -43,7 +43,8 @@ class _Single:
 _MOMENTS_SUPPORTED = ("moment propagation supports NormalLinear / LocalReparamLinear, ReLU folded into them by "
                       "nn.fuse_activations, NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d, the activations "
                       "nn.moment_activations rewrites (ReLU, ELU, a torch.nn.Linear behind a Bayesian layer, and a Softmax over the last "
-                      "axis that ends the network), "
+                      "axis that ends the network; behind a Bayesian layer also MaxPool / AvgPool / AdaptiveAvgPool 1d / 2d / 3d and an "
+                      "eval-mode BatchNorm1d / 2d / 3d), "
                       "reshaping modules such as torch.nn.Flatten, and torch.nn.Identity")
 
 
@@ -124,6 +125,157 @@ class MomentSoftmax(torch.nn.Softmax):
         if self.dim not in (-1, x.dim() - 1):
             raise ops.BnnHipError("MomentSoftmax: softmax over axis %r of %d; only the last axis is supported" % (self.dim, x.dim()))
         return ops.Moments(x.mean, x.var, link='softmax')
+
+
+def _moment_track():
+    ctx = _mc.moments_current()
+    return ctx is not None and ctx.track                               # forward_moments: keep the graph
+
+
+def _moment_pool_forward(self, x, nd, op, kernel_size, stride, padding, dilation, count_include_pad):
+    """An ops.Moments through a pooling twin (K20): ops.moments_pool on the device, ops.moments_pool_f64 on the CPU; one item
+    (C, *spatial) is a batch of one, as for its parent."""
+    from .. import ops
+    who = type(self).__name__
+    ops._refuse_link(x, who)
+    if getattr(self, "ceil_mode", False):
+        raise ops.BnnHipError("%s: ceil_mode=True is not supported in a moment pass" % who)
+    if getattr(self, "return_indices", False):
+        raise ops.BnnHipError("%s: return_indices=True is not supported in a moment pass (a Gaussian maximum has no index)" % who)
+    if getattr(self, "divisor_override", None) is not None:
+        raise ops.BnnHipError("%s: divisor_override is not supported in a moment pass" % who)
+    if x.dim() not in (nd + 1, nd + 2):
+        raise ops.BnnHipError("%s: moments of shape %s (expected %d or %d axes)" % (who, tuple(x.shape), nd + 1, nd + 2))
+    one = x.dim() == nd + 1
+    if one:
+        x = ops.Moments(x.mean.unsqueeze(0), None if x.var is None else x.var.unsqueeze(0))
+    if kernel_size is None:                                            # adaptive: the average pool with kernel = stride = in / out
+        out = self.output_size if isinstance(self.output_size, (tuple, list)) else (self.output_size,) * nd
+        out = tuple(n if o is None else int(o) for o, n in zip(out, x.shape[2:]))
+        if len(out) != nd or any(o < 1 or n % o for o, n in zip(out, x.shape[2:])):
+            raise ops.BnnHipError("%s: the input extents %s are no multiple of the output extents %s: only then is adaptive "
+                                  "average pooling a pooling with one window size" % (who, tuple(x.shape[2:]), out))
+        kernel_size = stride = tuple(n // o for o, n in zip(out, x.shape[2:]))
+    fn = ops.moments_pool if x.mean.is_cuda else ops.moments_pool_f64
+    y = fn(x, op, kernel_size, stride, padding, dilation, count_include_pad, _moment_track())
+    if one:
+        y = ops.Moments(y.mean.squeeze(0), None if y.var is None else y.var.squeeze(0))
+    return y
+
+
+def _max_pool_twin(parent, nd):
+    def forward(self, x):
+        from .. import ops
+        if not isinstance(x, ops.Moments):
+            return parent.forward(self, x)
+        return _moment_pool_forward(self, x, nd, 'max', self.kernel_size, self.stride, self.padding, self.dilation, True)
+    return forward
+
+
+def _avg_pool_twin(parent, nd):
+    def forward(self, x):
+        from .. import ops
+        if not isinstance(x, ops.Moments):
+            return parent.forward(self, x)
+        return _moment_pool_forward(self, x, nd, 'avg', self.kernel_size, self.stride, self.padding, 1, self.count_include_pad)
+    return forward
+
+
+def _adaptive_avg_pool_twin(parent, nd):
+    def forward(self, x):
+        from .. import ops
+        if not isinstance(x, ops.Moments):
+            return parent.forward(self, x)
+        return _moment_pool_forward(self, x, nd, 'avg', None, None, 0, 1, True)
+    return forward
+
+
+def _batchnorm_twin(parent):
+    def forward(self, x):
+        from .. import ops
+        if not isinstance(x, ops.Moments):
+            return parent.forward(self, x)
+        if _moment_track():
+            raise ops.BnnHipError("forward_moments: %s has no moment backward" % type(self).__name__)
+        return ops.moments_batchnorm(x, self) if x.mean.is_cuda else ops.moments_batchnorm_f64(x, self)
+    return forward
+
+
+class MomentMaxPool1d(torch.nn.MaxPool1d):
+    """torch.nn.MaxPool1d that also takes an ops.Moments inside a moment pass (ops.moments_pool / moments_pool_f64: the window
+    folded pairwise with the moment-matched maximum of two Gaussians); on tensors it is its parent.  nn.moment_activations
+    re-classes a MaxPool1d behind a Bayesian layer in place.  ceil_mode and return_indices are refused in a moment pass."""
+    forward = _max_pool_twin(torch.nn.MaxPool1d, 1)
+
+
+class MomentMaxPool2d(torch.nn.MaxPool2d):
+    """MomentMaxPool1d for torch.nn.MaxPool2d."""
+    forward = _max_pool_twin(torch.nn.MaxPool2d, 2)
+
+
+class MomentMaxPool3d(torch.nn.MaxPool3d):
+    """MomentMaxPool1d for torch.nn.MaxPool3d."""
+    forward = _max_pool_twin(torch.nn.MaxPool3d, 3)
+
+
+class MomentAvgPool1d(torch.nn.AvgPool1d):
+    """torch.nn.AvgPool1d that also takes an ops.Moments inside a moment pass (mean' = sum m / n, var' = sum v / n^2: exact for
+    independent elements); on tensors it is its parent.  ceil_mode is refused in a moment pass."""
+    forward = _avg_pool_twin(torch.nn.AvgPool1d, 1)
+
+
+class MomentAvgPool2d(torch.nn.AvgPool2d):
+    """MomentAvgPool1d for torch.nn.AvgPool2d; divisor_override is refused in a moment pass."""
+    forward = _avg_pool_twin(torch.nn.AvgPool2d, 2)
+
+
+class MomentAvgPool3d(torch.nn.AvgPool3d):
+    """MomentAvgPool1d for torch.nn.AvgPool3d; divisor_override is refused in a moment pass."""
+    forward = _avg_pool_twin(torch.nn.AvgPool3d, 3)
+
+
+class MomentAdaptiveAvgPool1d(torch.nn.AdaptiveAvgPool1d):
+    """torch.nn.AdaptiveAvgPool1d that also takes an ops.Moments inside a moment pass: the average pool with kernel = stride =
+    in / out, refused where the input extent is no multiple of the output extent.  On tensors it is its parent."""
+    forward = _adaptive_avg_pool_twin(torch.nn.AdaptiveAvgPool1d, 1)
+
+
+class MomentAdaptiveAvgPool2d(torch.nn.AdaptiveAvgPool2d):
+    """MomentAdaptiveAvgPool1d for torch.nn.AdaptiveAvgPool2d."""
+    forward = _adaptive_avg_pool_twin(torch.nn.AdaptiveAvgPool2d, 2)
+
+
+class MomentAdaptiveAvgPool3d(torch.nn.AdaptiveAvgPool3d):
+    """MomentAdaptiveAvgPool1d for torch.nn.AdaptiveAvgPool3d."""
+    forward = _adaptive_avg_pool_twin(torch.nn.AdaptiveAvgPool3d, 3)
+
+
+class MomentBatchNorm1d(torch.nn.BatchNorm1d):
+    """torch.nn.BatchNorm1d that also takes an ops.Moments inside a moment pass: in eval mode, with running statistics, the
+    per-channel affine map of ops.moments_batchnorm / moments_batchnorm_f64; training mode is refused (the batch statistics of a
+    random activation are not part of the recursion), and so is forward_moments (no backward).  On tensors it is its parent."""
+    forward = _batchnorm_twin(torch.nn.BatchNorm1d)
+
+
+class MomentBatchNorm2d(torch.nn.BatchNorm2d):
+    """MomentBatchNorm1d for torch.nn.BatchNorm2d."""
+    forward = _batchnorm_twin(torch.nn.BatchNorm2d)
+
+
+class MomentBatchNorm3d(torch.nn.BatchNorm3d):
+    """MomentBatchNorm1d for torch.nn.BatchNorm3d."""
+    forward = _batchnorm_twin(torch.nn.BatchNorm3d)
+
+
+# torch class -> its twin: what nn.moment_activations re-classes in place behind a Bayesian layer
+_MOMENT_RECLASS = {
+    torch.nn.MaxPool1d: MomentMaxPool1d, torch.nn.MaxPool2d: MomentMaxPool2d, torch.nn.MaxPool3d: MomentMaxPool3d,
+    torch.nn.AvgPool1d: MomentAvgPool1d, torch.nn.AvgPool2d: MomentAvgPool2d, torch.nn.AvgPool3d: MomentAvgPool3d,
+    torch.nn.AdaptiveAvgPool1d: MomentAdaptiveAvgPool1d, torch.nn.AdaptiveAvgPool2d: MomentAdaptiveAvgPool2d,
+    torch.nn.AdaptiveAvgPool3d: MomentAdaptiveAvgPool3d,
+    torch.nn.BatchNorm1d: MomentBatchNorm1d, torch.nn.BatchNorm2d: MomentBatchNorm2d, torch.nn.BatchNorm3d: MomentBatchNorm3d,
+}
+_MOMENT_BATCHNORMS = (MomentBatchNorm1d, MomentBatchNorm2d, MomentBatchNorm3d)
 
 
 def _moments_asked(propagation, who, kl=None):
@@ -371,7 +523,9 @@ class BayesianNetworkModule(Module):
         moments are exact for a deterministic input; the correlation between the positions of an output map is dropped).
         Supported: those layers, ReLU folded into the dense ones by nn.fuse_activations, what nn.moment_activations rewrites
         (ReLU, ELU, a torch.nn.Linear behind a Bayesian layer, a Softmax over the last axis that ends the network: the result
-        then carries link='softmax' and holds the LOGIT moments), modules that only reshape (torch.nn.Flatten, x.view),
+        then carries link='softmax' and holds the LOGIT moments; K20: max / average / adaptive average pooling 1d / 2d / 3d and
+        an eval-mode BatchNorm1d / 2d / 3d behind a Bayesian layer -- ops.moments_pool, ops.moments_batchnorm), modules that only
+        reshape (torch.nn.Flatten, x.view),
         torch.nn.Identity, and any deterministic module in FRONT of the first Bayesian layer; anything else raises
         ops.BnnHipError.  A `_forward` that
         returns a plain tensor gives it back with var None.  CPU tensors: the same recursion in float64 (ops.moments_f64),
@@ -443,6 +597,8 @@ class BayesianNetworkModule(Module):
         With nn.conv_moment_training() switched on (K19) NormalConv1d / 2d / 3d, LocalReparamConv1d / 2d / 3d, nn.MomentELU and
         nn.MomentLinear are admitted too: the conv backward is k_moments_conv3d_bwd (csrc/bnn_conv3d.hip; K11's launches for a
         deterministic input), the ELU's bnn_moments_elu_backward, MomentLinear's K18's two launches; the other layers stay refused.
+        The pooling twins nn.MomentMaxPool / MomentAvgPool / MomentAdaptiveAvgPool 1d / 2d / 3d (K20) are admitted with no switch:
+        their backward is bnn_moments_pool3d_backward; nn.MomentBatchNorm1d / 2d / 3d has no backward and is refused by name.
         Regression: mean(((y - mom.mean)^2 + mom.var) / (2 s^2)) needs no sample; classification: sample_moments."""
         from .. import ops
         from . import _settings
@@ -451,6 +607,11 @@ class BayesianNetworkModule(Module):
         convs_on = _settings.conv_moment_training_enabled()
         admitted = (NormalLinear, LocalReparamLinear) + ((NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d,
                                                            LocalReparamConv2d, LocalReparamConv3d) if convs_on else ())
+        for m in self.modules():
+            if isinstance(m, _MOMENT_BATCHNORMS):                                   # (named first, whatever else the network holds)
+                raise ops.BnnHipError("forward_moments: %s has no moment backward (K20 propagates moments through an eval-mode "
+                                      "BatchNorm for inference only); the pooling twins nn.MomentMaxPool / MomentAvgPool / "
+                                      "MomentAdaptiveAvgPool 1d / 2d / 3d have one" % type(m).__name__)
         for m in self.modules():
             if (isinstance(m, BayesianModule) and type(m) not in admitted) or (not convs_on and isinstance(m, (MomentELU, MomentLinear))):
                 raise ops.BnnHipError("forward_moments: %s has no moment backward; training without sampling supports "

@@ -10,6 +10,7 @@ Every function here requires CUDA (HIP) tensors and raises BnnHipError otherwise
 import collections
 import contextlib
 import ctypes
+import itertools
 import math
 import os
 import threading
@@ -1664,6 +1665,261 @@ def moments_convNd_f64(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, g
     if act == 'relu':
         return moments_relu_f64(out, track)
     return moments_elu_f64(out, alpha, track) if act == 'elu' else out
+
+
+# --------------------------------------------------------------------------- K20: moments through pooling and eval-mode BatchNorm
+def _pool_geometry(who, mom, op, kernel_size, stride, padding, dilation):
+    """The per-axis geometry of one pooling call on (B, C, *spatial) moments, 1 to 3 spatial axes -> (nd, kernel, stride,
+    padding, dilation, out_spatial); stride None = the kernel (torch's default); the output extents by torch's floor rule.
+    BnnHipError for what bnn_moments_pool3d_forward refuses (the same conditions, checked here so that the CPU route refuses
+    them too)."""
+    if op not in ('max', 'avg'):
+        raise ValueError("%s: op must be 'max' or 'avg', got %r" % (who, op))
+    nd = mom.dim() - 2
+    if nd not in (1, 2, 3):
+        raise BnnHipError("%s: the moments must be (B, C, *spatial) with 1, 2 or 3 spatial axes, got %s" % (who, tuple(mom.shape)))
+
+    def axes(val, name):
+        t = tuple(int(x) for x in val) if isinstance(val, (tuple, list)) else (int(val),) * nd
+        if len(t) == 1 and nd > 1:
+            t = t * nd
+        if len(t) != nd:
+            raise BnnHipError("%s: %s has %d entries for %d spatial axes" % (who, name, len(t), nd))
+        return t
+
+    k = axes(kernel_size, "kernel_size")
+    s = k if stride is None else axes(stride, "stride")
+    p, d = axes(padding, "padding"), axes(dilation, "dilation")
+    if min(mom.shape) < 1 or min(k) < 1 or min(s) < 1 or min(d) < 1 or min(p) < 0:
+        raise BnnHipError("%s: an extent below 1 (shape %s, kernel %s, stride %s, padding %s, dilation %s)"
+                          % (who, tuple(mom.shape), k, s, p, d))
+    if any(2 * pi > ki for pi, ki in zip(p, k)):
+        raise BnnHipError("%s: padding %s above half the kernel %s" % (who, p, k))
+    if math.prod(k) > _lib.POOL_WINDOW_CAP:
+        raise BnnHipError("%s: a window of %d elements (at most %d)" % (who, math.prod(k), _lib.POOL_WINDOW_CAP))
+    out = tuple((n + 2 * pi - di * (ki - 1) - 1) // si + 1 for n, ki, si, pi, di in zip(mom.shape[2:], k, s, p, d))
+    if min(out) < 1:
+        raise BnnHipError("%s: the window %s (dilation %s) is larger than the padded input %s" % (who, k, d, tuple(mom.shape[2:])))
+    for n, o, ki, si, pi, di in zip(mom.shape[2:], out, k, s, p, d):
+        for oi in set(range(min(o, pi + 1))) | set(range(max(0, o - pi - 1), o)):
+            if not any(0 <= oi * si - pi + j * di < n for j in range(ki)):
+                raise BnnHipError("%s: a window lies in the padding alone (kernel %s, padding %s, dilation %s)" % (who, k, p, d))
+    return nd, k, s, p, d, out
+
+
+def _pool3d_shape(shape, k, s, p, d):
+    """bnn_pool3d_shape_t of a (B, C, *spatial) call: 1-d and 2-d pooling as unit depth / height."""
+    pad3 = lambda t, one: (one,) * (3 - len(t)) + tuple(t)          # noqa: E731
+    D, H, W = pad3(tuple(shape[2:]), 1)
+    (KD, KH, KW), (sd, sh, sw), (pd, ph, pw), (dd, dh, dw) = pad3(k, 1), pad3(s, 1), pad3(p, 0), pad3(d, 1)
+    return _lib.Pool3dShape(B=int(shape[0]), C=int(shape[1]), D=D, H=H, W=W, KD=KD, KH=KH, KW=KW, stride_d=sd, stride_h=sh,
+                            stride_w=sw, pad_d=pd, pad_h=ph, pad_w=pw, dil_d=dd, dil_h=dh, dil_w=dw)
+
+
+class _MomentsPool(torch.autograd.Function):
+    """bnn_moments_pool3d_forward with bnn_moments_pool3d_backward behind it (the backward folds the windows again from the
+    saved inputs); m, v fp32, contiguous, (B, C, *spatial)."""
+
+    @staticmethod
+    def forward(ctx, m, v, sh, out_shape, code, flags):
+        om = torch.empty(out_shape, dtype=torch.float32, device=m.device)
+        ov = torch.empty_like(om)
+        check(_lib.load().bnn_moments_pool3d_forward(ptr(m), ptr(v), ptr(om), ptr(ov), ctypes.byref(sh), code, flags,
+                                                     stream_ptr(m.device)), "bnn_moments_pool3d_forward")
+        ctx.save_for_backward(m, v)
+        ctx.sh, ctx.code, ctx.flags = sh, code, flags
+        return om, ov
+
+    @staticmethod
+    def backward(ctx, g_om, g_ov):
+        m, v = ctx.saved_tensors
+        g_om, g_ov = g_om.contiguous(), g_ov.contiguous()
+        g_m, g_v = torch.empty_like(m), torch.empty_like(v)
+        check(_lib.load().bnn_moments_pool3d_backward(ptr(m), ptr(v), ptr(g_om), ptr(g_ov), ptr(g_m), ptr(g_v), ctypes.byref(ctx.sh),
+                                                      ctx.code, ctx.flags, stream_ptr(m.device)), "bnn_moments_pool3d_backward")
+        return g_m, g_v, None, None, None, None
+
+
+def _plain_pool(mean, op, nd, k, s, p, d, count_include_pad):
+    """A deterministic input (var None) stays one: torch's own pooling of the mean."""
+    if op == 'max':
+        return (torch.nn.functional.max_pool1d, torch.nn.functional.max_pool2d, torch.nn.functional.max_pool3d)[nd - 1](mean, k, s, p, d)
+    if any(di != 1 for di in d):
+        raise BnnHipError("moments_pool: torch's average pooling has no dilation (deterministic input)")
+    return (torch.nn.functional.avg_pool1d, torch.nn.functional.avg_pool2d, torch.nn.functional.avg_pool3d)[nd - 1](
+        mean, k, s, p, False, count_include_pad)
+
+
+def moments_pool(mom, op, kernel_size, stride=None, padding=0, dilation=1, count_include_pad=True, track=False):
+    """Max or average pooling of Gaussian activations (bnn_moments_pool3d_forward, csrc/bnn_moments_pool.hip) -> Moments, fp32
+    (B, C, *out_spatial); mom (B, C, *spatial) with 1 to 3 spatial axes; op 'max' or 'avg'; kernel_size, stride (None: the
+    kernel), padding, dilation per axis or one number.
+      'max': the window is folded pairwise with the moment-matched maximum of two Gaussians (Clark 1961; include/bnn_hip.h has the
+        formulas), offsets ascending in (depth, height, width), padded positions skipped: exact for a window of two, moment
+        matching of the running maximum beyond.  theta^2 == 0 is the plain maximum.
+      'avg': mean' = sum m / n, var' = sum v / n^2 over the valid positions, n the window size (count_include_pad) or the valid
+        count: exact for independent elements.
+    A deterministic input (var None) stays one (torch's pooling of the mean).  track=True with grad mode on: attached to the
+    graph, the backward is bnn_moments_pool3d_backward -- bit-reproducible for windows that do not overlap, fp32 atomics (an
+    order-dependent sum) for overlapping ones."""
+    who = "moments_pool"
+    mom = _as_moments(mom, who)
+    _refuse_link(mom, who)
+    nd, k, s, p, d, out_sp = _pool_geometry(who, mom, op, kernel_size, stride, padding, dilation)
+    tracked = _tracking(track)
+    keep = (lambda t: t) if tracked else (lambda t: t.detach())
+    if mom.var is None:
+        return Moments(_plain_pool(keep(mom.mean), op, nd, k, s, p, d, bool(count_include_pad)), None)
+    m, v = keep(mom.mean).contiguous(), keep(mom.var).contiguous()
+    require_cuda_f32(m, "mean")
+    require_cuda_f32(v, "var")
+    out_shape = tuple(m.shape[:2]) + out_sp
+    if max(m.numel(), math.prod(out_shape)) >= 1 << 32:
+        raise BnnHipError("%s: %d elements: the element index is 32 bits wide" % (who, m.numel()))
+    sh = _pool3d_shape(m.shape, k, s, p, d)
+    code = _lib.POOL_MAX if op == 'max' else _lib.POOL_AVG
+    flags = 0 if (op == 'max' or count_include_pad) else _lib.POOL_FLAG_VALID_DIVISOR
+    if tracked:
+        return Moments(*_MomentsPool.apply(m, v, sh, out_shape, code, flags))
+    om = torch.empty(out_shape, dtype=torch.float32, device=m.device)
+    ov = torch.empty_like(om)
+    check(_lib.load().bnn_moments_pool3d_forward(ptr(m), ptr(v), ptr(om), ptr(ov), ctypes.byref(sh), code, flags, stream_ptr(m.device)),
+          "bnn_moments_pool3d_forward")
+    return Moments(om, ov)
+
+
+def _max_pair_f64(m1, v1, m2, v2):
+    """The moment-matched maximum of two independent Gaussians in float64 torch (include/bnn_hip.h, K20); theta^2 == 0: the
+    plain maximum, the first operand on a tie (torch.where, so that autograd sends both gradients to the element taken)."""
+    th2 = v1 + v2
+    plain = ~(th2 > 0)
+    ths = torch.where(plain, torch.ones_like(th2), th2)
+    th = torch.sqrt(ths)
+    d = m1 - m2
+    al = d / th
+    r2 = math.sqrt(2.0)
+    cdf, cdc = 0.5 * torch.special.erfc(-al / r2), 0.5 * torch.special.erfc(al / r2)
+    pdf = torch.exp(-0.5 * al * al) / math.sqrt(2.0 * math.pi)
+    mean = m1 * cdf + m2 * cdc + th * pdf
+    var = (v1 * cdf + v2 * cdc + d * d * cdf * cdc + d * th * pdf * (cdc - cdf) - ths * pdf * pdf).clamp_min(0)
+    second = m2 > m1
+    return torch.where(plain, torch.where(second, m2, m1), mean), torch.where(plain, torch.where(second, v2, v1), var)
+
+
+def moments_pool_f64(mom, op, kernel_size, stride=None, padding=0, dilation=1, count_include_pad=True, track=False):
+    """moments_pool in float64 torch -- the CPU route and the tests' reference: the same fold in the same order, one strided view
+    of the padded planes per window offset.  track=True: not detached (plain torch autograd)."""
+    who = "moments_pool_f64"
+    mom = _as_moments(mom, who)
+    _refuse_link(mom, who)
+    nd, k, s, p, d, out_sp = _pool_geometry(who, mom, op, kernel_size, stride, padding, dilation)
+    f64 = _f64(track)
+    if mom.var is None:
+        return Moments(_plain_pool(f64(mom.mean), op, nd, k, s, p, d, bool(count_include_pad)), None)
+    ok = torch.ones(tuple(mom.shape[2:]), dtype=torch.bool, device=mom.mean.device)
+    geo = (k, s, p, d, out_sp)
+    return _pool_fold_f64(_pool_windows(f64(mom.mean), *geo), _pool_windows(f64(mom.var), *geo), _pool_windows(ok, *geo), op,
+                          float(math.prod(k)) if count_include_pad else None)
+
+
+def _pool_windows(t, k, s, p, d, out_sp):
+    """The windows of a pooling call, one strided view of the zero-padded t (..., *spatial) per window offset, offsets ascending
+    in row-major order: entry j holds, for every output position, the element its window has at offset j."""
+    return _pool_windows_of_padded(torch.nn.functional.pad(t, [q for pi in reversed(p) for q in (pi, pi)]), k, s, p, d, out_sp)
+
+
+def _pool_windows_of_padded(pt, k, s, p, d, out_sp):
+    """_pool_windows of a tensor that is padded already."""
+    return [pt[(Ellipsis,) + tuple(slice(o * di, o * di + si * (n - 1) + 1, si) for o, di, si, n in zip(off, d, s, out_sp))]
+            for off in itertools.product(*[range(ki) for ki in k])]
+
+
+def _pool_fold_f64(ms, vs, valids, op, divisor):
+    """The fold of moments_pool_f64 over the per-offset views of _pool_windows (means, variances, validity masks) -> Moments;
+    divisor: the average's n, None = the valid count."""
+    rm = rv = started = None
+    count = 0.0
+    for xm, xv, valid in zip(ms, vs, valids):
+        if op == 'avg':
+            rm, rv = (xm, xv) if rm is None else (rm + xm, rv + xv)            # (the padding holds zeros)
+            count = count + valid
+        elif rm is None:
+            rm, rv, started = xm, xv, valid
+        else:
+            nm, nv = _max_pair_f64(rm, rv, xm, xv)
+            rm = torch.where(valid, torch.where(started, nm, xm), rm)
+            rv = torch.where(valid, torch.where(started, nv, xv), rv)
+            started = started | valid
+    if op == 'avg':
+        n = count if divisor is None else divisor
+        return Moments(rm / n, rv / (n * n))
+    return Moments(rm, rv)
+
+
+def _batchnorm_operands(bn, who):
+    """(gamma, beta, running_mean, running_var, eps) of an eval-mode BatchNorm module, or the five given as a tuple."""
+    if isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
+        if bn.training:
+            raise BnnHipError("%s: %s is in training mode: the batch statistics of a random activation are not part of the "
+                              "moment recursion (call .eval())" % (who, type(bn).__name__))
+        if bn.running_mean is None or bn.running_var is None:
+            raise BnnHipError("%s: %s has no running statistics (track_running_stats=False)" % (who, type(bn).__name__))
+        return bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps)
+    if isinstance(bn, (tuple, list)) and len(bn) == 5:
+        return tuple(bn[:4]) + (float(bn[4]),)
+    raise TypeError("%s: expected a BatchNorm module or (gamma, beta, running_mean, running_var, eps), got %s" % (who, type(bn).__name__))
+
+
+def moments_batchnorm(mom, bn):
+    """Eval-mode BatchNorm of Gaussian activations (bnn_moments_batchnorm) -> Moments, fp32: per channel (axis 1)
+    a = gamma / sqrt(running_var + eps), m' = a (m - running_mean) + beta, v' = a^2 v.  bn: a torch BatchNorm module in eval mode
+    with running statistics, or (gamma, beta, running_mean, running_var, eps) with gamma / beta None for affine=False.  Forward
+    only (detached).  A deterministic input (var None) stays one."""
+    who = "moments_batchnorm"
+    mom = _as_moments(mom, who)
+    _refuse_link(mom, who)
+    gamma, beta, rmean, rvar, eps = _batchnorm_operands(bn, who)
+    if mom.dim() < 2 or mom.shape[1] != rmean.numel():
+        raise BnnHipError("%s: moments %s for %d channels" % (who, tuple(mom.shape), rmean.numel()))
+    if not (0.0 <= eps < float("inf")):
+        raise BnnHipError("%s: eps must be finite and >= 0, got %r" % (who, eps))
+    if mom.var is None:
+        return Moments(torch.nn.functional.batch_norm(mom.mean.detach(), rmean, rvar, gamma, beta, False, 0.0, eps).detach(), None)
+    m, v = mom.mean.detach().contiguous(), mom.var.detach().contiguous()
+    require_cuda_f32(m, "mean")
+    require_cuda_f32(v, "var")
+    par = [None if t is None else t.detach().contiguous() for t in (gamma, beta, rmean, rvar)]
+    for t, name in zip(par, ("gamma", "beta", "running_mean", "running_var")):
+        if t is not None:
+            require_cuda_f32(t, name)
+    if m.numel() >= 1 << 32:
+        raise BnnHipError("%s: %d elements: the element index is 32 bits wide" % (who, m.numel()))
+    om, ov = torch.empty_like(m), torch.empty_like(v)
+    B, C = m.shape[0], m.shape[1]
+    if m.numel():
+        check(_lib.load().bnn_moments_batchnorm(ptr(m), ptr(v), ptr(par[0]), ptr(par[1]), ptr(par[2]), ptr(par[3]), eps, ptr(om), ptr(ov),
+                                                B, C, m.numel() // (B * C), stream_ptr(m.device)), "bnn_moments_batchnorm")
+    return Moments(om, ov)
+
+
+def moments_batchnorm_f64(mom, bn):
+    """moments_batchnorm in float64 torch (detached)."""
+    who = "moments_batchnorm_f64"
+    mom = _as_moments(mom, who)
+    _refuse_link(mom, who)
+    gamma, beta, rmean, rvar, eps = _batchnorm_operands(bn, who)
+    if mom.dim() < 2 or mom.shape[1] != rmean.numel():
+        raise BnnHipError("%s: moments %s for %d channels" % (who, tuple(mom.shape), rmean.numel()))
+    f64 = lambda t: t.detach().to(torch.float64)          # noqa: E731
+    shp = (1, -1) + (1,) * (mom.dim() - 2)
+    a = 1.0 / torch.sqrt(f64(rvar) + eps)
+    if gamma is not None:
+        a = a * f64(gamma)
+    a = a.reshape(shp)
+    m = a * (f64(mom.mean) - f64(rmean).reshape(shp))
+    if beta is not None:
+        m = m + f64(beta).reshape(shp)
+    return Moments(m, None if mom.var is None else a * a * f64(mom.var))
 
 
 class _PlainLinear(torch.autograd.Function):

@@ -1243,6 +1243,50 @@ int bnn_conv3d_moments_backward_weight(const float *a_m, const float *a_v, const
 int bnn_moments_elu_backward(const float *m, const float *v, const float *g_out_m, const float *g_out_v, float *g_m, float *g_v,
                              int64_t n, float alpha, void *stream);
 
+/* ---- K20: moments through pooling and eval-mode BatchNorm (csrc/bnn_moments_pool.hip, csrc/bnn_moments_act.hpp;
+ * ops.moments_pool, ops.moments_batchnorm).  Elements are independent Gaussians.
+ * Max pooling folds a window pairwise with the moment-matched maximum of two Gaussians (Clark 1961): with theta^2 = v1 + v2,
+ * d = m1 - m2, alpha = d / theta, Phi = Phi at alpha, Phi_c = Phi at -alpha, phi the density at alpha,
+ *     mean' = m1 Phi + m2 Phi_c + theta phi
+ *     var'  = v1 Phi + v2 Phi_c + d^2 Phi Phi_c + d theta phi [Phi_c - Phi] - theta^2 phi^2,   clamped at 0
+ * (the pair ((m, v), (0, 0)) is the function of bnn_moments_relu); exact for two elements, moment matching of the running
+ * maximum beyond.  The fold order is part of the contract: window offsets ascending in depth, height, width (row-major); padded
+ * positions are skipped and the first valid element starts the fold.  theta^2 == 0 is the plain maximum: the larger element's
+ * mean and variance, the running value on a tie; the backward sends both gradients to that element.  fp64 on fp32 inputs, one
+ * rounding to fp32 per output.  Average pooling: mean' = sum m / n, var' = sum v / n^2 over the valid positions, n the window
+ * size, or the valid count with BNN_POOL_FLAG_VALID_DIVISOR.
+ * Tensors are fp32 and dense: m, v, g_m, g_v [B, C, D, H, W]; out_m, out_v, g_out_m, g_out_v [B, C, OD, OH, OW] with the output
+ * extents floor((I + 2 pad - dil (K - 1) - 1) / stride) + 1 per axis; 1-d and 2-d pooling are unit depth / height.  Every operand
+ * may lie on its element (all loads and stores are one element wide).  A window holds at most 64 elements (the backward keeps
+ * the fold's prefix states in LDS).  The backward folds the window again from m, v (nothing is kept from the forward call),
+ * zeroes g_m and g_v on the stream with a launch of its own (skipped where the windows tile the input exactly), and writes windows that do not overlap (stride >= dil (K - 1) + 1 on every axis) with plain
+ * stores: identical calls give identical bits.  Overlapping windows are accumulated with fp32 atomics, whose order is not fixed:
+ * there a gradient may differ between identical calls by the rounding of an fp32 sum of at most prod ceil(extent / stride) terms.
+ * Graph-capturable; errors are returned before anything is launched: BNN_E_NULL, BNN_E_SHAPE (an extent < 1, a negative padding,
+ * an empty output), BNN_E_RANGE (padding above half the kernel; a window of more than 64 elements or one that lies in the padding
+ * alone; 2^32 elements or more, an extent of 2^31 or more), BNN_E_UNSUPPORTED (an unknown op or flag), BNN_E_ALIGN. */
+typedef struct {
+    int64_t B, C, D, H, W;
+    int64_t KD, KH, KW;
+    int64_t stride_d, stride_h, stride_w;
+    int64_t pad_d, pad_h, pad_w;
+    int64_t dil_d, dil_h, dil_w;
+} bnn_pool3d_shape_t;
+enum { BNN_POOL_MAX = 0, BNN_POOL_AVG = 1 };
+enum { BNN_POOL_FLAG_VALID_DIVISOR = 1 };     /* average pooling: divide by the number of valid positions (count_include_pad=False) */
+int bnn_moments_pool3d_forward(const float *m, const float *v, float *out_m, float *out_v, const bnn_pool3d_shape_t *shape, int op,
+                               int flags, void *stream);
+int bnn_moments_pool3d_backward(const float *m, const float *v, const float *g_out_m, const float *g_out_v, float *g_m, float *g_v,
+                                const bnn_pool3d_shape_t *shape, int op, int flags, void *stream);
+/* Eval-mode BatchNorm as a per-channel affine map of the moments: a = gamma / sqrt[running_var + eps],
+ * m' = a [m - running_mean] + beta, v' = a^2 v, a formed per element in the launch (fp32).  m, v, out_m, out_v: B x C x inner
+ * elements, channel c = [e / inner] mod C; gamma, beta, running_mean, running_var: C; gamma / beta NULL mean 1 / 0.  In place
+ * allowed.  Errors: BNN_E_NULL, BNN_E_SHAPE (an extent < 1), BNN_E_RANGE (2^32 elements or more; eps negative or not finite),
+ * BNN_E_ALIGN. */
+int bnn_moments_batchnorm(const float *m, const float *v, const float *gamma, const float *beta, const float *running_mean,
+                          const float *running_var, float eps, float *out_m, float *out_v, int64_t B, int64_t C, int64_t inner,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif
