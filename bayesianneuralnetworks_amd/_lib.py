@@ -252,6 +252,10 @@ SIGNATURES = {
     "bnn_moments_pool3d_forward": (_int, [_p, _p, _p, _p, ctypes.POINTER(Pool3dShape), _int, _int, _p]),
     "bnn_moments_pool3d_backward": (_int, [_p, _p, _p, _p, _p, _p, ctypes.POINTER(Pool3dShape), _int, _int, _p]),
     "bnn_moments_batchnorm": (_int, [_p, _p, _p, _p, _p, _p, ctypes.c_float, _p, _p, _i64, _i64, _i64, _p]),
+    "bnn_mvn_moments_prepare": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p]),
+    "bnn_mvn_moments_forward": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "bnn_moments_head_cov": (_int, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "bnn_moments_sample_cov": (_int, [_p, _p, _p, _i64, _i64, _int, _rngp, _int, _p]),
 }
 
 _lib = None

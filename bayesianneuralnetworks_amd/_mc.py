@@ -44,10 +44,14 @@ class MomentContext:
     the mean and variance of their output (ops.moments_linear, ops.moments_convNd) instead of samples.  They draw nothing and record no key.  Thread-local, like McContext, and kept apart
     from it: an MC-batched pass and a moment pass do not see each other.  track=True (BayesianNetworkModule.forward_moments):
     the dense layers and nn.MomentReLU keep the autograd graph (ops.moments_linear(track=True)), and so do the conv layers,
-    nn.MomentELU and nn.MomentLinear (ops.moments_convNd / moments_elu / moments_affine(track=True)); the default is inference."""
+    nn.MomentELU and nn.MomentLinear (ops.moments_convNd / moments_elu / moments_affine(track=True)); the default is inference.
+    covariance=True (predictive_moments(covariance=True), K21): a dense layer of at most 32 outputs attaches to the Moments it
+    returns what the outputs' covariance needs (ops.head_operands); the pass resolves it when that layer turns out to be the head."""
 
-    def __init__(self, track=False):
+    def __init__(self, track=False, covariance=False):
         self.track = bool(track)
+        self.covariance = bool(covariance)
+        self.last_dense = None          # (type name, outputs) of the last dense layer a covariance pass went through
 
     def __enter__(self):
         self.prev = getattr(_state, "moments", None)

@@ -8,7 +8,7 @@
 // sample0, P or the grid.  Only the lower triangle of `scale` is read.
 #include <cmath>
 
-#include "bnn_device.hpp"
+#include "bnn_mvn_dev.hpp"
 
 namespace bnn {
 
@@ -19,25 +19,7 @@ constexpr int kMvnLdsBytes = 64 * 1024;     // dynamic LDS per workgroup: the dr
 constexpr int kMvnMaxSamplesPerPass = 16;
 constexpr int kMvnTargetBlocks = 2048;      // parts per row: about 8 workgroups per CU over the whole launch
 
-// softplus(x), torch's (beta 1, threshold 20), to a few ulp relative for every x: log1p(e) = ln(u) e / (u - 1), u = 1 + e
-// (the rounding of u cancels; log1p(e) = e when u == 1) on the native exp2 / log2 / rcp units.  The draw, its backward and
-// the KL all take L or V from THIS function.
-__device__ __forceinline__ float mvn_softplus(float x)
-{
-    const float e = __builtin_amdgcn_exp2f(x * 1.44269504088896341f);
-    const float u = 1.0f + e;
-    const float d = u - 1.0f;
-    float sp = __builtin_amdgcn_logf(u) * 0.693147180559945309f * (e * __builtin_amdgcn_rcpf(d));
-    sp = (d == 0.0f) ? e : sp;
-    return x > 20.0f ? x : sp;
-}
-
-// V[i][j] = softplus(scale) + (i == j ? 1e-10 : 0) -- WeightMultivariateNormal.variance on the lower triangle
-__device__ __forceinline__ float mvn_v(float s, bool diag)
-{
-    const float v = mvn_softplus(s);
-    return diag ? v + 1e-10f : v;
-}
+// mvn_softplus / mvn_v / mvn_l (bnn_mvn_dev.hpp): the draw, its backward and the KL all take L or V from THOSE functions.
 
 struct MvnDev {
     const float *mu, *scale;
@@ -181,7 +163,7 @@ __global__ __launch_bounds__(kMvnThreads) void k_mvn_draw(MvnLaunch P)
                 mvn_load4(srow, j0, i, K, vec, v);
                 float l[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) l[k] = (j0 + k <= i) ? __builtin_sqrtf(mvn_v(v[k], j0 + k == i)) : 0.f;
+                for (int k = 0; k < 4; ++k) l[k] = (j0 + k <= i) ? mvn_l(v[k], j0 + k == i) : 0.f;
                 const float *uq = u_lds + j0;
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
@@ -270,7 +252,7 @@ __global__ __launch_bounds__(kMvnThreads) void k_mvn_draw_bwd(MvnLaunch P)
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             if (j0 + k <= i) {
-                                const float l = __builtin_sqrtf(mvn_v(v[k], j0 + k == i));
+                                const float l = mvn_l(v[k], j0 + k == i);
                                 a[k] = a[k] * (dsoftplus(v[k]) / (2.0f * l));
                             } else {
                                 a[k] = 0.f;

@@ -41,7 +41,7 @@ class _Single:
 
 
 _MOMENTS_SUPPORTED = ("moment propagation supports NormalLinear / LocalReparamLinear, ReLU folded into them by "
-                      "nn.fuse_activations, NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d, the activations "
+                      "nn.fuse_activations, MultivariateNormalLinear (inference only), NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d, the activations "
                       "nn.moment_activations rewrites (ReLU, ELU, a torch.nn.Linear behind a Bayesian layer, and a Softmax over the last "
                       "axis that ends the network; behind a Bayesian layer also MaxPool / AvgPool / AdaptiveAvgPool 1d / 2d / 3d and an "
                       "eval-mode BatchNorm1d / 2d / 3d), "
@@ -108,8 +108,14 @@ class MomentLinear(torch.nn.Linear):
         ctx = _mc.moments_current()
         track = ctx is not None and ctx.track                          # forward_moments: keep the graph
         if not x.mean.is_cuda:
-            return ops.moments_affine_f64(x, self.weight, self.bias, track)
-        return ops.moments_affine(x, self.weight, self.bias, compute=_settings.get_compute(), track=track)
+            out = ops.moments_affine_f64(x, self.weight, self.bias, track)
+        else:
+            out = ops.moments_affine(x, self.weight, self.bias, compute=_settings.get_compute(), track=track)
+        if ctx is not None and ctx.covariance:                           # a covariance pass (K21): should this layer be the head
+            ctx.last_dense = (type(self).__name__, self.out_features)
+            if self.out_features <= ops.HEAD_COV_MAX_N:
+                out._head = ops.head_operands(x, self.weight)
+        return out
 
 
 class MomentSoftmax(torch.nn.Softmax):
@@ -124,7 +130,9 @@ class MomentSoftmax(torch.nn.Softmax):
         ops._refuse_link(x, "MomentSoftmax")
         if self.dim not in (-1, x.dim() - 1):
             raise ops.BnnHipError("MomentSoftmax: softmax over axis %r of %d; only the last axis is supported" % (self.dim, x.dim()))
-        return ops.Moments(x.mean, x.var, link='softmax')
+        out = ops.Moments(x.mean, x.var, link='softmax', cov=x.cov)      # the one module that keeps a covariance (K21)
+        out._head = x._head
+        return out
 
 
 def _moment_track():
@@ -278,9 +286,14 @@ _MOMENT_RECLASS = {
 _MOMENT_BATCHNORMS = (MomentBatchNorm1d, MomentBatchNorm2d, MomentBatchNorm3d)
 
 
-def _moments_asked(propagation, who, kl=None):
-    """propagation == 'moments'?  ValueError for anything but 'samples' / 'moments' (and then no KL is left pending)."""
+def _moments_asked(propagation, who, kl=None, covariance=False):
+    """propagation == 'moments'?  ValueError for anything but 'samples' / 'moments', and for covariance=True (K21: correlated
+    draws from the head's covariance) without propagation='moments' (and then no KL is left pending)."""
     if propagation == 'samples':
+        if covariance:
+            from .. import ops
+            ops._kl_uncarry(kl)
+            raise ValueError("%s: covariance=True needs propagation='moments' (stochastic forwards are correlated as they are)" % who)
         return False
     if propagation == 'moments':
         return True
@@ -357,7 +370,7 @@ class BayesianNetworkModule(Module):
         return list(ys.unbind(0))
 
     def predictive_mean(self, x, samples=None, sample0=0, out=None, scale=None, advance=None, kl=None, *args,
-                        propagation='samples', **kwargs):
+                        propagation='samples', covariance=False, **kwargs):
         """scale (default 1 / samples) * sum over the MC samples of `_forward(x)` -- torch.stack(preds).mean(0) of
         examples/MNIST/uncertainty.py:50 -- as the tail of ONE batched pass: the caller wants the mean, not the samples, so a
         hidden layer may run fused with the classifier head behind it (nn.fuse_activations; bnn_dense_forward_head) and the
@@ -367,8 +380,8 @@ class BayesianNetworkModule(Module):
         if samples is None:
             samples = self.samples
         tail = self.mc_batched and _on_device(x)                    # the device launch reduces; else the sum below
-        if _moments_asked(propagation, "predictive_mean"):
-            ys = self._moment_outputs("predictive_mean", x, samples, sample0, kl, args, kwargs)
+        if _moments_asked(propagation, "predictive_mean", None, covariance):
+            ys = self._moment_outputs("predictive_mean", x, samples, sample0, kl, args, kwargs, covariance)
             tail, kl = ys.is_cuda, None                             # _moment_outputs has taken kl
             if not tail:
                 _refuse_cpu_tails("predictive_mean", "advance is a tail", advance)
@@ -379,7 +392,8 @@ class BayesianNetworkModule(Module):
         scale = (1.0 / samples) if scale is None else scale
         return ops.mc_mean(ys, out=out, scale=scale, advance=advance, kl=kl) if tail else _scaled_sum(ys, scale, out)
 
-    def predictive_uncertainty(self, x, samples=None, sample0=0, *, inputs, advance=None, kl=None, propagation='samples', **kwargs):
+    def predictive_uncertainty(self, x, samples=None, sample0=0, *, inputs, advance=None, kl=None, propagation='samples',
+                               covariance=False, **kwargs):
         """Predictive mean and uncertainty of `samples` MC draws of `_forward(x)` -> ops.PredictiveUncertainty(mean, total,
         aleatoric, epistemic): total = H(mean), aleatoric = mean over samples of H(p_s), epistemic = total - aleatoric (the
         mutual information, BALD).  inputs: 'logits' (p_s = softmax of the outputs) or 'probs' (outputs used as given, e.g. a
@@ -389,18 +403,21 @@ class BayesianNetworkModule(Module):
           other CUDA:         forward_stacked (the serial loop), then the same launch;
           CPU:                forward_stacked, then ops.uncertainty_f64 (the same formulas in float64).
         propagation='moments': the `samples` logits are drawn from ONE sampling-free pass (predictive_moments; _moment_outputs)
-        instead of `samples` stochastic forwards; the tail is the same."""
+        instead of `samples` stochastic forwards; the tail is the same.  covariance=True (with propagation='moments' only, else
+        ValueError; the same keyword on predictive_mean / _score / _regression / _regression_score): the logits are drawn
+        CORRELATED from the head's N x N covariance (predictive_moments(covariance=True), bnn_moments_sample_cov) -- the mutual
+        information depends on how the logits move together; the default draws them independent, as before."""
         from .. import ops
         ops._unc_kind(inputs, "predictive_uncertainty", kl)         # before a draw is consumed
-        moments = _moments_asked(propagation, "predictive_uncertainty", kl)
+        moments = _moments_asked(propagation, "predictive_uncertainty", kl, covariance)
         if not _on_device(x):
             _refuse_cpu_tails("predictive_uncertainty", "advance / kl are tails", advance, kl)
-            return ops.uncertainty_f64(self._tail_inputs("predictive_uncertainty", x, samples, sample0, moments, kl, kwargs), inputs)
-        y = self._tail_inputs("predictive_uncertainty", x, samples, sample0, moments, kl, kwargs)
+            return ops.uncertainty_f64(self._tail_inputs("predictive_uncertainty", x, samples, sample0, moments, kl, kwargs, covariance), inputs)
+        y = self._tail_inputs("predictive_uncertainty", x, samples, sample0, moments, kl, kwargs, covariance)
         return ops.mc_uncertainty(y, inputs, advance=advance, kl=kl)
 
     def predictive_score(self, x, target, samples=None, sample0=0, *, inputs, state=None, advance=None, propagation='samples',
-                         **kwargs):
+                         covariance=False, **kwargs):
         """`samples` MC draws of `_forward(x)` scored against the labels `target` (int64, one per row) -> ops.PredictiveScore(mean,
         nll, expected_nll, brier, confidence, prediction, entropy): nll = -ln mean[y] of the MC predictive, expected_nll the mean
         per-sample NLL (the ELBO's data term), brier, the confidence max_c mean[c] with its class, and H(mean).  inputs: 'logits'
@@ -414,20 +431,21 @@ class BayesianNetworkModule(Module):
         propagation='moments': as predictive_uncertainty."""
         from .. import ops
         ops._unc_kind(inputs, "predictive_score")                   # before a draw is consumed
-        moments = _moments_asked(propagation, "predictive_score")
+        moments = _moments_asked(propagation, "predictive_score", None, covariance)
         if not _on_device(x):
             _refuse_cpu_tails("predictive_score", "advance is a tail", advance)
             _refuse_device_state("predictive_score", state, ops.ScoreState)
             cb, eb = (state.conf_bins, state.ent_bins) if state is not None else (15, 20)
-            ys = self._tail_inputs("predictive_score", x, samples, sample0, moments, None, kwargs)
+            ys = self._tail_inputs("predictive_score", x, samples, sample0, moments, None, kwargs, covariance)
             out, vec = ops.score_f64(ys, target, inputs, cb, eb)
             if state is not None:
                 state.add_(vec)
             return out
-        y = self._tail_inputs("predictive_score", x, samples, sample0, moments, None, kwargs)
+        y = self._tail_inputs("predictive_score", x, samples, sample0, moments, None, kwargs, covariance)
         return ops.mc_score(y, target, inputs, state=state, advance=advance)
 
-    def predictive_regression(self, x, samples=None, sample0=0, *, outputs, advance=None, kl=None, propagation='samples', **kwargs):
+    def predictive_regression(self, x, samples=None, sample0=0, *, outputs, advance=None, kl=None, propagation='samples',
+                              covariance=False, **kwargs):
         """Predictive mean and variance decomposition of `samples` MC draws of a real-valued `_forward(x)` ->
         ops.PredictiveRegression(mean, total, aleatoric, epistemic), each (*rows, D): the moments of the equal-weight mixture of
         the per-sample predictives -- aleatoric = mean of the per-sample variances, epistemic = variance of the per-sample means,
@@ -442,13 +460,13 @@ class BayesianNetworkModule(Module):
         moments ARE the answer (mean, total = epistemic = var, aleatoric = 0), `samples` is not used and nothing is drawn."""
         from .. import ops
         ops._reg_kind(outputs, "predictive_regression", kl)         # before a draw is consumed
-        moments = _moments_asked(propagation, "predictive_regression", kl)
+        moments = _moments_asked(propagation, "predictive_regression", kl, covariance)
         if moments and outputs == 'values':
             if advance is not None:
                 raise ops.BnnHipError("predictive_regression: outputs='values' with propagation='moments' has no tail launch "
                                       "to run `advance` in")
             self._moment_refusals("predictive_regression", kl)
-            mom = self.predictive_moments(x, **kwargs)
+            mom = self.predictive_moments(x, covariance=covariance, **kwargs)
             if mom.link is not None:
                 raise ops.BnnHipError("predictive_regression: outputs='values' with propagation='moments' reads the propagated "
                                       "moments as they are; this network ends in a %s link" % mom.link)
@@ -456,12 +474,12 @@ class BayesianNetworkModule(Module):
             return ops.PredictiveRegression(mom.mean, var, torch.zeros_like(mom.mean), var.clone())
         if not _on_device(x):
             _refuse_cpu_tails("predictive_regression", "advance / kl are tails", advance, kl)
-            return ops.regression_f64(self._tail_inputs("predictive_regression", x, samples, sample0, moments, kl, kwargs), outputs)
-        y = self._tail_inputs("predictive_regression", x, samples, sample0, moments, kl, kwargs)
+            return ops.regression_f64(self._tail_inputs("predictive_regression", x, samples, sample0, moments, kl, kwargs, covariance), outputs)
+        y = self._tail_inputs("predictive_regression", x, samples, sample0, moments, kl, kwargs, covariance)
         return ops.mc_regression(y, outputs, advance=advance, kl=kl)
 
     def predictive_regression_score(self, x, target, samples=None, sample0=0, *, outputs, state=None, advance=None,
-                                    propagation='samples', **kwargs):
+                                    propagation='samples', covariance=False, **kwargs):
         """`samples` MC draws of a real-valued `_forward(x)` scored against the targets `target` (*rows, D) ->
         ops.RegressionScore(mean, variance, sq_err, nll, gaussian_nll, crps, pit), each (*rows, D): the proper scores of the MC
         predictive -- the equal-weight mixture of the per-sample Gaussians -- and its probability integral transform.  outputs:
@@ -477,17 +495,17 @@ class BayesianNetworkModule(Module):
         propagation='moments': as predictive_uncertainty."""
         from .. import ops
         ops._reg_kind(outputs, "predictive_regression_score")       # before a draw is consumed
-        moments = _moments_asked(propagation, "predictive_regression_score")
+        moments = _moments_asked(propagation, "predictive_regression_score", None, covariance)
         if not _on_device(x):
             _refuse_cpu_tails("predictive_regression_score", "advance is a tail", advance)
             _refuse_device_state("predictive_regression_score", state, ops.RegressionScoreState)
             bins = state.pit_bins if state is not None else 20
-            ys = self._tail_inputs("predictive_regression_score", x, samples, sample0, moments, None, kwargs)
+            ys = self._tail_inputs("predictive_regression_score", x, samples, sample0, moments, None, kwargs, covariance)
             out, mat = ops.regression_score_f64(ys, target, outputs, bins)
             if state is not None:
                 state.add_(mat)
             return out
-        y = self._tail_inputs("predictive_regression_score", x, samples, sample0, moments, None, kwargs)
+        y = self._tail_inputs("predictive_regression_score", x, samples, sample0, moments, None, kwargs, covariance)
         return ops.mc_regression_score(y, target, outputs, state=state, advance=advance)
 
     def predictive_evidential(self, x, samples=None, sample0=0, **kwargs):
@@ -511,14 +529,14 @@ class BayesianNetworkModule(Module):
             return ops.evidential_f64(*ys)
         return ops.mc_evidential(*ys)
 
-    def predictive_moments(self, x, *args, **kwargs):
+    def predictive_moments(self, x, *args, covariance=False, **kwargs):
         """Sampling-free inference: ONE pass of `_forward(x)` that carries a mean and a variance per activation through the
         network (moment propagation: Frey & Hinton 1999; Hernandez-Lobato & Adams 2015; Wu et al. 2019) -> ops.Moments(mean, var)
         of the output, fp32.  Every NormalLinear / LocalReparamLinear runs as ops.moments_linear (one bnn_moments_forward launch
         beside its operand launch, both compute modes; ReLU folded by nn.fuse_activations is moment-matched in that launch); the
         cost does not depend on a sample count and no mc_batched is needed.  With ONE hidden ReLU layer every output's marginal
         mean and variance are exact; from the second hidden layer on the recursion treats a layer's inputs as independent
-        Gaussians (the usual diagonal-covariance approximation), and the outputs' covariances are not carried at all.
+        Gaussians (the usual diagonal-covariance approximation); the outputs' covariance is carried only with covariance=True (below).
         NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d run as ops.moments_convNd (K17: per output element the marginal
         moments are exact for a deterministic input; the correlation between the positions of an output map is dropped).
         Supported: those layers, ReLU folded into the dense ones by nn.fuse_activations, what nn.moment_activations rewrites
@@ -530,16 +548,25 @@ class BayesianNetworkModule(Module):
         ops.BnnHipError.  A `_forward` that
         returns a plain tensor gives it back with var None.  CPU tensors: the same recursion in float64 (ops.moments_f64),
         rounded to fp32 at the end.  Inference only: nothing is drawn, no draw epoch is consumed, no key is recorded, and the
-        result is detached whatever the grad mode."""
+        result is detached whatever the grad mode.
+        K21: MultivariateNormalLinear (the CIFAR10 example's head) runs as ops.moments_mvn_linear -- the exact moments of its own
+        sampler (uniform noise through the element-wise square root of the triangle) for independent inputs.  covariance=True:
+        the result also carries cov (*rows, N, N), the covariance of the N outputs of a row, from ONE bnn_moments_head_cov launch:
+        the outputs of a dense head share their input, Cov(y_o, y_p) = sum_k E[w_ok] E[w_pk] Var[a_k] (+ an MVN head's bias
+        covariance).  With one hidden layer and a deterministic input the hidden activations are independent and cov is exact.
+        The network must end in a dense layer of at most 32 outputs (NormalLinear, LocalReparamLinear, nn.MomentLinear,
+        MultivariateNormalLinear), with nothing but a closing nn.MomentSoftmax behind it; otherwise ops.BnnHipError says why.
+        ops.moments_sample and the predictive_* tails (covariance=True) draw correlated outputs from it.  Not covered: the backward
+        of any of this, Flipout and MC-dropout layers, covariance between hidden activations or conv positions, non-default priors."""
         from .. import ops
-        from .dense import NormalLinear, LocalReparamLinear
+        from .dense import NormalLinear, LocalReparamLinear, MultivariateNormalLinear
         from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
-        admitted = (NormalLinear, LocalReparamLinear, NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d,
-                    LocalReparamConv2d, LocalReparamConv3d)
+        admitted = (NormalLinear, LocalReparamLinear, MultivariateNormalLinear, NormalConv1d, NormalConv2d, NormalConv3d,
+                    LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
         for m in self.modules():
             if isinstance(m, BayesianModule) and type(m) not in admitted:
                 raise ops.BnnHipError("predictive_moments: %s is not supported; %s" % (type(m).__name__, _MOMENTS_SUPPORTED))
-        with torch.no_grad(), _mc.MomentContext():
+        with torch.no_grad(), _mc.MomentContext(covariance=covariance) as mctx:
             try:
                 y = self._forward(x, *args, **kwargs)
             except (TypeError, AttributeError) as e:
@@ -549,8 +576,23 @@ class BayesianNetworkModule(Module):
             y = ops.Moments(y.detach(), None)
         if not isinstance(y, ops.Moments):
             raise ops.BnnHipError("predictive_moments: _forward returned %s; %s" % (type(y).__name__, _MOMENTS_SUPPORTED))
+        if covariance:
+            if y._head is None:
+                dense = mctx.last_dense
+                if dense is None:
+                    why = "its last layer is not dense: the pass went through no dense layer at all"
+                elif dense[1] > ops.HEAD_COV_MAX_N and y.dim() and y.shape[-1] == dense[1]:
+                    why = "its head %s has %d outputs" % dense
+                else:
+                    why = ("something stands behind its last dense layer %s (a folded ReLU, an activation or another module): the "
+                           "covariance is carried at the head only" % dense[0])
+                raise ops.BnnHipError("predictive_moments: covariance=True needs the network to end in a dense layer of at most %d outputs "
+                                      "(NormalLinear, LocalReparamLinear, nn.MomentLinear, MultivariateNormalLinear; a closing "
+                                      "nn.MomentSoftmax may follow); %s" % (ops.HEAD_COV_MAX_N, why))
+            y = ops.moments_resolve_cov(y)
         if not y.mean.is_cuda:
-            return ops.Moments(y.mean.to(torch.float32), None if y.var is None else y.var.to(torch.float32), y.link)
+            return ops.Moments(y.mean.to(torch.float32), None if y.var is None else y.var.to(torch.float32), y.link,
+                               cov=None if y.cov is None else y.cov.to(torch.float32))
         return y
 
     def _moment_refusals(self, who, kl):
@@ -562,12 +604,12 @@ class BayesianNetworkModule(Module):
             raise ops.BnnHipError("%s: propagation='moments' has no fused head: this network was rewritten with "
                                   "nn.fuse_activations(fuse_head=True), whose hidden layer hands on partial logits" % who)
 
-    def _moment_outputs(self, who, x, samples, sample0, kl, args, kwargs):
+    def _moment_outputs(self, who, x, samples, sample0, kl, args, kwargs, covariance=False):
         """propagation='moments': what a predictive_* tail reads -- the (S, *rows, C) outputs drawn from the propagated moments
         by ONE bnn_moments_sample launch, independent across outputs, on a model-level noise stream (its id is taken at first
         use, so that a model's layers keep theirs; the key is recorded as model.moment_key).  CPU: torch.randn."""
         self._moment_refusals(who, kl)
-        mom = self.predictive_moments(x, *args, **kwargs)
+        mom = self.predictive_moments(x, *args, covariance=covariance, **kwargs)
         return self._sample_link(mom, samples, sample0, False)
 
     def _sample_link(self, mom, samples, sample0, track):
@@ -639,16 +681,19 @@ class BayesianNetworkModule(Module):
         from .. import ops
         if not isinstance(mom, ops.Moments):
             raise TypeError("sample_moments: expected an ops.Moments, got %s" % type(mom).__name__)
+        if mom.cov is not None:
+            raise ops.BnnHipError("sample_moments: moments that carry a covariance have no backward; ops.moments_sample draws from them "
+                                  "at inference")
         return self._sample_link(mom, self.samples if samples is None else samples, sample0, True)
 
-    def _tail_inputs(self, who, x, samples, sample0, moments, kl, kwargs):
+    def _tail_inputs(self, who, x, samples, sample0, moments, kl, kwargs, covariance=False):
         """The (S, *rows, C) outputs a predictive_* tail reads.  `moments`: drawn from the propagated moments (_moment_outputs).
         Else `samples` stochastic forwards: for x on the device with mc_batched one batched pass whose fused head, if any, hands
         on its partials (ops.HeadPartials); otherwise the stacked outputs of the serial loop."""
         if samples is None:
             samples = self.samples
         if moments:
-            return self._moment_outputs(who, x, samples, sample0, kl, (), kwargs)
+            return self._moment_outputs(who, x, samples, sample0, kl, (), kwargs, covariance)
         if self.mc_batched and _on_device(x):
             return self._forward_batched_stacked(x, samples, sample0, _lazy_head=True, **kwargs)
         return self.forward_stacked(x, samples, sample0, **kwargs)

@@ -10,7 +10,8 @@ bnn_dense_forward_dropout / bnn_mc_dropout) and keeps F.dropout elsewhere.  Flip
 with keyed signs per MC sample in that pass (bnn_draw_multi kind BNN_DRAW_FLIPOUT).  MultivariateNormalLinear keeps the
 reference's torch expression unless nn.keyed_mvn_draws() is on: then in that pass every MC sample gets a keyed draw of its own
 (bnn_mvn_draw, then the HIP linear).  Inside BayesianNetworkModule.predictive_moments (a _mc.MomentContext) NormalLinear and
-LocalReparamLinear draw nothing: they take and return a mean and a variance per activation (ops.moments_linear, K16).  The evidential head is outside the HIP scope and runs as PyTorch-ROCm
+LocalReparamLinear draw nothing: they take and return a mean and a variance per activation (ops.moments_linear, K16), and so does
+MultivariateNormalLinear (ops.moments_mvn_linear, K21: the exact moments of its uniform-noise sampler).  The evidential head is outside the HIP scope and runs as PyTorch-ROCm
 ops with the reference's semantics so that its examples keep working.
 """
 import math
@@ -119,10 +120,18 @@ class _NormalSampling:
         ops._refuse_link(mom, type(self).__name__)
         b = self.bias is not None
         args = (self.weight.mean, self.weight.scale, self.bias.mean if b else None, self.bias.scale if b else None)
-        track = _mc.moments_current().track
+        ctx = _mc.moments_current()
+        track = ctx.track
         if not mom.mean.is_cuda:
-            return ops.moments_linear_f64(mom, *args, relu=self.activation == 'relu', track=track)
-        return ops.moments_linear(mom, *args, relu=self.activation == 'relu', compute=self._compute_mode(), track=track)
+            out = ops.moments_linear_f64(mom, *args, relu=self.activation == 'relu', track=track)
+        else:
+            out = ops.moments_linear(mom, *args, relu=self.activation == 'relu', compute=self._compute_mode(), track=track)
+        if ctx.covariance:
+            # a covariance pass (K21): should this layer be the head, its outputs share the input -- the biases are independent
+            ctx.last_dense = (type(self).__name__, self.weight.mean.shape[0])
+            if self.activation is None and self.weight.mean.shape[0] <= ops.HEAD_COV_MAX_N:
+                out._head = ops.head_operands(mom, self.weight.mean)
+        return out
 
     def _mc_plan(self, x, sample):
         """-> (S, sample0, shared_x, rows_per_sample) for the current MC context."""
@@ -526,11 +535,50 @@ class MultivariateNormalLinear(BayesianLinear):
             self.sampled = (self.weight.sampled, None)
 
     def forward(self, x, sample=True):
+        if _mc.moments_current() is not None:
+            return self._forward_moments(x)                              # predictive_moments: moments in, moments out, no draw
         if _settings.keyed_mvn_enabled() and isinstance(x, torch.Tensor) and x.is_cuda and _mc.current() is not None:
             return self._forward_keyed(x, sample, _mc.current())
         if sample:
             self.sample()
         return torch.nn.functional.linear(x, *self.sampled)
+
+    def _posterior(self):
+        b = self.bias is not None
+        return (self.weight.mean, self.weight.scale, self.bias.mean if b else None, self.bias.scale if b else None)
+
+    def _moments_prepared(self, cpu=False):
+        """ops.mvn_moments_prepare's four outputs for the layer's posterior (CPU input: mvn_moments_prepare_f64's), computed again
+        only when a parameter has changed (repeated inference batches pay one launch)."""
+        ps = [p for p in self._posterior() if p is not None]
+        tag = (cpu,) + tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in ps)
+        cached = self.__dict__.get("_moments_cache")
+        if cached is None or cached[0] != tag:
+            cached = (tag, (ops.mvn_moments_prepare_f64 if cpu else ops.mvn_moments_prepare)(*self._posterior()))
+            self.__dict__["_moments_cache"] = cached
+        return cached[1]
+
+    def _forward_moments(self, x):
+        """The layer inside a moment pass (K21): x a tensor (a deterministic input) or an ops.Moments -> the ops.Moments of the
+        output under the layer's own sampler (uniform noise through the element-wise square root of the triangle) -- exact for
+        independent input elements.  Device: ops.moments_mvn_linear (bnn_mvn_moments_forward, the prepare launch cached on the
+        layer); CPU: ops.moments_mvn_linear_f64.  Inference only: a tracking pass (forward_moments) raises ops.BnnHipError.  In a
+        covariance pass a layer of at most 32 outputs leaves the operands of its outputs' covariance on the result."""
+        mom = x if isinstance(x, ops.Moments) else ops.Moments(x, None)
+        if not torch.is_tensor(mom.mean):
+            raise TypeError("%s takes a tensor or ops.Moments in a moment pass, got %s" % (type(self).__name__, type(x).__name__))
+        ops._refuse_link(mom, type(self).__name__)
+        ctx = _mc.moments_current()
+        if ctx.track:
+            raise ops.BnnHipError("%s has no moment backward (inference only)" % type(self).__name__)
+        cpu = not mom.mean.is_cuda
+        prepared = self._moments_prepared(cpu)
+        out = (ops.moments_mvn_linear_f64 if cpu else ops.moments_mvn_linear)(mom, *self._posterior(), prepared=prepared)
+        if ctx.covariance:
+            ctx.last_dense = (type(self).__name__, self.weight.mean.shape[0])
+            if self.weight.mean.shape[0] <= ops.HEAD_COV_MAX_N:
+                out._head = ops.head_operands(mom, prepared[0], prepared[3])
+        return out
 
     def _mvn_keys(self, ctx, sample):
         """sample: fresh keys for the pass's S samples, recorded as weight.draw_key / bias.draw_key.  sample=False: the recorded

@@ -941,18 +941,26 @@ class Moments:
     deterministic input (every variance zero), as the first Bayesian layer of a network sees.  It reshapes like a tensor (shape,
     size, dim, view, reshape, flatten -- each applied to mean and var alike), so torch.nn.Flatten and `x.view(x.size(0), -1)`
     work on it unchanged.  link: None, or 'softmax' when the moments are those of logits whose softmax ends the network
-    (nn.MomentSoftmax): the predictive_* tails apply it to the sampled logits, and no layer takes such moments."""
-    __slots__ = ("mean", "var", "link", "_act")     # _act: the activation the producing conv launch fused (the twin behind it passes)
+    (nn.MomentSoftmax): the predictive_* tails apply it to the sampled logits, and no layer takes such moments.  cov: None, or
+    the (*rows, N, N) covariance of the N outputs of a row (K21: predictive_moments(covariance=True) at a dense head; its diagonal
+    is var).  Nothing propagates a covariance: every reshape, layer and activation hands on moments without one; only
+    nn.MomentSoftmax keeps it, and moments_sample draws correlated outputs from it."""
+    # _act: the activation the producing conv launch fused (the twin behind it passes); _head: a dense layer's HeadOperands while
+    # a covariance pass runs (dropped and kept as cov is)
+    __slots__ = ("mean", "var", "link", "_act", "cov", "_head")
 
-    def __init__(self, mean, var=None, link=None):
+    def __init__(self, mean, var=None, link=None, cov=None):
         if var is not None and var.shape != mean.shape:
             raise ValueError("Moments: mean %s and var %s differ in shape" % (tuple(mean.shape), tuple(var.shape)))
         if link not in (None, 'softmax'):
             raise ValueError("Moments: link must be None or 'softmax', got %r" % (link,))
-        self.mean, self.var, self.link, self._act = mean, var, link, None
+        if cov is not None and (mean.dim() < 1 or tuple(cov.shape) != tuple(mean.shape) + (mean.shape[-1],)):
+            raise ValueError("Moments: cov %s is not mean's shape %s with its last axis repeated" % (tuple(cov.shape), tuple(mean.shape)))
+        self.mean, self.var, self.link, self._act, self.cov, self._head = mean, var, link, None, cov, None
 
     def __repr__(self):
-        return "Moments(mean=%r, var=%r%s)" % (self.mean, self.var, "" if self.link is None else ", link=%r" % self.link)
+        return "Moments(mean=%r, var=%r%s%s)" % (self.mean, self.var, "" if self.link is None else ", link=%r" % self.link,
+                                                 "" if self.cov is None else ", cov=%r" % (self.cov,))
 
     def _both(self, fn):
         return Moments(fn(self.mean), None if self.var is None else fn(self.var), self.link)
@@ -1174,9 +1182,14 @@ def moments_sample(mom, key, nsamples, track=False):
     y_s[e] = m[e] + sqrt(v[e] + 1e-16) eps_s[e], e the flat index within one sample, eps_s[e] element e of the key's sample
     sample0 + s (the LRT-noise contract).  The result is what the mc_* tails read.  CPU moments: torch.randn (the key is not
     used and may be None).  track=True with grad mode on: differentiable in the moments -- the backward re-creates eps from the
-    key (bnn_lrt_backward_epilogue: g_m = sum_s gy_s, g_v = sum_s gy_s eps_s / (2 sqrt(v + 1e-16)))."""
+    key (bnn_lrt_backward_epilogue: g_m = sum_s gy_s, g_v = sum_s gy_s eps_s / (2 sqrt(v + 1e-16))).
+    Moments that carry a covariance (mom.cov, K21) are drawn correlated: y_s[b, :] = m[b, :] + Lc_b eps_s[b, :] with Lc_b the
+    lower Cholesky factor of cov[b] in float64 (bnn_moments_sample_cov; the same eps on the same key; CPU: cholesky_pivot_f64 and
+    torch.randn).  Inference only: track=True with grad mode on raises BnnHipError."""
     mom = _as_moments(mom, "moments_sample")
     S = int(nsamples)
+    if mom.cov is not None:
+        return _moments_sample_cov(mom, key, S, track)
     tracked = _tracking(track)
     keep = (lambda t: t) if tracked else (lambda t: t.detach())
     m = keep(mom.mean)
@@ -1920,6 +1933,250 @@ def moments_batchnorm_f64(mom, bn):
     if beta is not None:
         m = m + f64(beta).reshape(shp)
     return Moments(m, None if mom.var is None else a * a * f64(mom.var))
+
+
+# --------------------------------------------------------------------------- K21: the head of a moment pass (MVN layer, covariance)
+HEAD_COV_MAX_N = 32                     # outputs of a head whose covariance is carried (csrc/bnn_moments_head.hip: kCovMaxN)
+MVN_MOMENTS_MAX_K = 4096                # input features of a MultivariateNormalLinear in a moment pass (kHeadMaxK)
+
+# What the covariance of a dense layer's outputs needs beside their variance (include/bnn_hip.h, K21): the input's variance
+# a_v (rows, K) or None (a deterministic input), the weights' means E (N, K) and the bias covariance C_b (N, N) or None.
+HeadOperands = collections.namedtuple("HeadOperands", ("a_v", "E", "C_b"))
+
+
+def head_operands(mom_in, E, C_b=None):
+    """HeadOperands of a dense layer with weight means E whose input was `mom_in` (a Moments), detached."""
+    K = E.shape[-1]
+    a_v = None if mom_in.var is None else mom_in.var.detach().reshape(-1, K)
+    return HeadOperands(a_v, E.detach(), None if C_b is None else C_b.detach())
+
+
+def _mvn_check(mu_w, scale_w, mu_b, scale_b, who):
+    if mu_w.dim() != 2 or tuple(scale_w.shape) != tuple(mu_w.shape) + (mu_w.shape[1],):
+        raise BnnHipError("%s: weight mean %s with scale %s (expected (O, K) and (O, K, K))" % (who, tuple(mu_w.shape), tuple(scale_w.shape)))
+    O, K = mu_w.shape
+    if (mu_b is None) != (scale_b is None):
+        raise BnnHipError("%s: the bias mean and scale come together" % who)
+    if mu_b is not None and (tuple(mu_b.shape) != (O,) or tuple(scale_b.shape) != (O, O)):
+        raise BnnHipError("%s: bias mean %s with scale %s (expected (%d,) and (%d, %d))" % (who, tuple(mu_b.shape), tuple(scale_b.shape), O, O, O))
+    if K > MVN_MOMENTS_MAX_K or (mu_b is not None and O > MVN_MOMENTS_MAX_K):
+        raise BnnHipError("%s: %d input features / %d outputs with a bias (at most %d)" % (who, K, O, MVN_MOMENTS_MAX_K))
+    return O, K
+
+
+def mvn_moments_prepare(mu_w, scale_w, mu_b, scale_b):
+    """The input-independent part of MultivariateNormalLinear's moments in ONE launch (bnn_mvn_moments_prepare) -> (E_w, G_w, E_b,
+    C_b): the weights' means under the layer's uniform-noise sampler, E_w^2 + their variances, the bias mean and the bias
+    covariance (None, None without a bias).  Detached; the formulas are moments_mvn_linear's."""
+    who = "mvn_moments_prepare"
+    O, K = _mvn_check(mu_w, scale_w, mu_b, scale_b, who)
+    ts = [t.detach().contiguous() for t in (mu_w, scale_w)] + ([t.detach().contiguous() for t in (mu_b, scale_b)] if mu_b is not None else [])
+    for t in ts:
+        require_cuda_f32(t, "posterior")
+    dev = ts[0].device
+    E_w, G_w = torch.empty((O, K), dtype=torch.float32, device=dev), torch.empty((O, K), dtype=torch.float32, device=dev)
+    E_b = C_b = None
+    if mu_b is not None:
+        E_b, C_b = torch.empty((O,), dtype=torch.float32, device=dev), torch.empty((O, O), dtype=torch.float32, device=dev)
+    check(_lib.load().bnn_mvn_moments_prepare(ptr(ts[0]), ptr(ts[1]), ptr(ts[2]) if mu_b is not None else None,
+                                              ptr(ts[3]) if mu_b is not None else None, ptr(E_w), ptr(G_w), ptr(E_b), ptr(C_b), O, K,
+                                              stream_ptr(dev)), "bnn_mvn_moments_prepare")
+    return E_w, G_w, E_b, C_b
+
+
+def moments_mvn_linear(a, mu_w, scale_w, mu_b, scale_b, track=False, prepared=None):
+    """Mean and variance of MultivariateNormalLinear's output from the mean and variance of its input -> Moments, fp32 (*rows, O)
+    (bnn_mvn_moments_prepare + bnn_mvn_moments_forward, csrc/bnn_moments_head.hip).  The layer draws w_o = mu_o + L_o u with
+    uniform u ~ U[0, 1)^K and L = sqrt(tril(softplus(scale)) + 1e-10 I) element by element, so
+
+        E_w[o,k] = mu[o,k] + 1/2 sum_{j<=k} L[o,k,j],  D[o,k] = 1/12 sum_{j<=k} L[o,k,j]^2,  E_b = mu_b + 1/2 L_b 1,  C_b = L_b L_b^T / 12
+        m[b,o] = sum_k a_m[b,k] E_w[o,k] + E_b[o]
+        v[b,o] = 1/12 sum_j (sum_{k>=j} a_m[b,k] L[o,k,j])^2 + sum_k a_v[b,k] (E_w[o,k]^2 + D[o,k]) + C_b[o,o]
+
+    -- exact for independent input elements.  a: a device tensor (a deterministic input) or a Moments; prepared: the result of
+    mvn_moments_prepare on the same posterior (a layer caches it).  Inference only: track=True raises BnnHipError."""
+    who = "moments_mvn_linear"
+    if track:
+        raise BnnHipError("%s: MultivariateNormalLinear has no moment backward (inference only)" % who)
+    mom = _as_moments(a, who)
+    _refuse_link(mom, who)
+    O, K = _mvn_check(mu_w, scale_w, mu_b, scale_b, who)
+    am = mom.mean.detach()
+    if am.dim() < 1 or am.shape[-1] != K:
+        raise BnnHipError("%s: input has %s features, weight expects %d" % (who, am.shape[-1] if am.dim() else "no", K))
+    lead = tuple(am.shape[:-1])
+    am = am.reshape(-1, K).float().contiguous()
+    require_cuda_f32(am, "a.mean")
+    av = None
+    if mom.var is not None:
+        av = mom.var.detach().reshape(-1, K).contiguous()
+        require_cuda_f32(av, "a.var")
+    B = am.shape[0]
+    if B > 64 * 65535:
+        raise BnnHipError("%s: %d rows (at most %d)" % (who, B, 64 * 65535))
+    E_w, G_w, E_b, C_b = prepared if prepared is not None else mvn_moments_prepare(mu_w, scale_w, mu_b, scale_b)
+    scale_w = scale_w.detach().contiguous()
+    dev = am.device
+    out_m = torch.empty((B, O), dtype=torch.float32, device=dev)
+    out_v = torch.empty((B, O), dtype=torch.float32, device=dev)
+    check(_lib.load().bnn_mvn_moments_forward(ptr(am), ptr(av), K, ptr(scale_w), ptr(E_w), ptr(G_w), ptr(E_b), ptr(C_b), ptr(out_m),
+                                              ptr(out_v), B, O, K, stream_ptr(dev)), "bnn_mvn_moments_forward")
+    return Moments(out_m.reshape(lead + (O,)), out_v.reshape(lead + (O,)))
+
+
+def mvn_factor_f64(scale):
+    """L = sqrt(tril(softplus(scale)) + 1e-10 I) element by element, in float64 (WeightMultivariateNormal.stddev); zero above the
+    diagonal."""
+    s = scale.detach().to(torch.float64)
+    return torch.sqrt(torch.tril(torch.nn.functional.softplus(s)) + 1e-10 * torch.eye(s.shape[-1], dtype=torch.float64, device=s.device))
+
+
+def mvn_moments_prepare_f64(mu_w, scale_w, mu_b, scale_b):
+    """mvn_moments_prepare in float64 torch -> (E_w, G_w, E_b, C_b)."""
+    _mvn_check(mu_w, scale_w, mu_b, scale_b, "mvn_moments_prepare_f64")
+    L = mvn_factor_f64(scale_w)
+    E_w = mu_w.detach().to(torch.float64) + 0.5 * L.sum(-1)
+    G_w = E_w * E_w + (L * L).sum(-1) / 12.0
+    if mu_b is None:
+        return E_w, G_w, None, None
+    Lb = mvn_factor_f64(scale_b)
+    return E_w, G_w, mu_b.detach().to(torch.float64) + 0.5 * Lb.sum(-1), Lb @ Lb.t() / 12.0
+
+
+def moments_mvn_linear_f64(a, mu_w, scale_w, mu_b, scale_b, track=False, prepared=None):
+    """moments_mvn_linear in float64 torch -> Moments of float64 tensors (detached).  prepared: (E_w, G_w, E_b, C_b) to use in place
+    of mvn_moments_prepare_f64's (the tests hand in the device's own, so that the forward is compared on its own)."""
+    who = "moments_mvn_linear_f64"
+    if track:
+        raise BnnHipError("%s: MultivariateNormalLinear has no moment backward (inference only)" % who)
+    mom = _as_moments(a, who)
+    _refuse_link(mom, who)
+    f64 = lambda t: None if t is None else t.detach().to(torch.float64)          # noqa: E731
+    E_w, G_w, E_b, C_b = [f64(t) for t in prepared] if prepared is not None else mvn_moments_prepare_f64(mu_w, scale_w, mu_b, scale_b)
+    L = mvn_factor_f64(scale_w)
+    am = f64(mom.mean)
+    m = am @ E_w.t()
+    t = torch.einsum('...k,okj->...oj', am, L)
+    v = (t * t).sum(-1) / 12.0
+    if mom.var is not None:
+        v = v + f64(mom.var) @ G_w.t()
+    if E_b is not None:
+        m, v = m + E_b, v + torch.diagonal(C_b)
+    return Moments(m, v)
+
+
+def moments_head_cov(head, var):
+    """The covariance of a dense head's outputs per row (ONE bnn_moments_head_cov launch) -> (rows, N, N) fp32:
+
+        cov[b,o,p] = sum_k E[o,k] E[p,k] a_v[b,k] + C_b[o,p]   (o != p),        cov[b,o,o] = var[b,o]
+
+    head: a HeadOperands (a_v (rows, K) or None, E (N, K), C_b (N, N) or None); var (rows, N), the head's output variance.  Both
+    triangles hold the same bits and the diagonal holds var's.  N <= 32."""
+    who = "moments_head_cov"
+    a_v, E, C_b = head
+    var = var.detach().contiguous()
+    require_cuda_f32(var, "var")
+    if var.dim() != 2:
+        raise BnnHipError("%s: var must be (rows, N), got %s" % (who, tuple(var.shape)))
+    B, N = var.shape
+    if N > HEAD_COV_MAX_N:
+        raise BnnHipError("%s: %d outputs (at most %d)" % (who, N, HEAD_COV_MAX_N))
+    E = E.detach().float().contiguous()
+    require_cuda_f32(E, "E")
+    K = E.shape[1]
+    if E.shape[0] != N:
+        raise BnnHipError("%s: E %s for %d outputs" % (who, tuple(E.shape), N))
+    if a_v is not None:
+        a_v = a_v.detach().contiguous()
+        require_cuda_f32(a_v, "a_v")
+        if tuple(a_v.shape) != (B, K):
+            raise BnnHipError("%s: a_v %s, expected %s" % (who, tuple(a_v.shape), (B, K)))
+    if C_b is not None:
+        C_b = C_b.detach().contiguous()
+        require_cuda_f32(C_b, "C_b")
+        if tuple(C_b.shape) != (N, N):
+            raise BnnHipError("%s: C_b %s, expected %s" % (who, tuple(C_b.shape), (N, N)))
+    cov = torch.empty((B, N, N), dtype=torch.float32, device=var.device)
+    check(_lib.load().bnn_moments_head_cov(ptr(a_v), K, ptr(E), ptr(C_b), ptr(var), ptr(cov), B, N, K, stream_ptr(var.device)),
+          "bnn_moments_head_cov")
+    return cov
+
+
+def moments_head_cov_f64(head, var):
+    """moments_head_cov in float64 torch -> (rows, N, N) float64."""
+    a_v, E, C_b = head
+    f64 = lambda t: t.detach().to(torch.float64)          # noqa: E731
+    var = f64(var)
+    B, N = var.shape
+    if N > HEAD_COV_MAX_N:
+        raise BnnHipError("moments_head_cov_f64: %d outputs (at most %d)" % (N, HEAD_COV_MAX_N))
+    cov = torch.zeros((B, N, N), dtype=torch.float64, device=var.device)
+    if a_v is not None:
+        E = f64(E)
+        cov = cov + torch.einsum('ok,pk,bk->bop', E, E, f64(a_v))
+    if C_b is not None:
+        cov = cov + f64(C_b)
+    idx = torch.arange(N, device=var.device)
+    cov[:, idx, idx] = var
+    return cov
+
+
+def moments_resolve_cov(mom, who="predictive_moments"):
+    """Moments whose producing dense layer left its HeadOperands (a covariance pass) -> the same moments with cov (*rows, N, N):
+    ONE bnn_moments_head_cov launch on the device, moments_head_cov_f64 on the CPU."""
+    head = mom._head
+    if head is None:
+        raise BnnHipError("%s: these moments carry no head operands" % who)
+    N = mom.shape[-1]
+    lead = tuple(mom.shape[:-1])
+    var = (torch.zeros_like(mom.mean) if mom.var is None else mom.var).reshape(-1, N)
+    cov = moments_head_cov(head, var) if mom.mean.is_cuda else moments_head_cov_f64(head, var)
+    return Moments(mom.mean, mom.var, mom.link, cov=cov.reshape(lead + (N, N)))
+
+
+def cholesky_pivot_f64(cov):
+    """The lower Cholesky factor of (..., N, N) covariances in float64, column by column in a plain loop, with
+    bnn_moments_sample_cov's pivot rule: a pivot <= 0 gives a zero column (a direction without variance -- a semi-definite
+    covariance, or one made so by rounding).  Only the lower triangle is read."""
+    A = cov.detach().to(torch.float64)
+    N = A.shape[-1]
+    L = torch.zeros_like(A)
+    for j in range(N):
+        s = A[..., j:, j] - (L[..., j:, :j] * L[..., j:j + 1, :j]).sum(-1)
+        pos = s[..., 0] > 0
+        d = torch.sqrt(torch.where(pos, s[..., 0], torch.ones_like(s[..., 0])))
+        L[..., j, j] = torch.where(pos, d, torch.zeros_like(d))
+        if j + 1 < N:
+            L[..., j + 1:, j] = torch.where(pos.unsqueeze(-1), s[..., 1:] / d.unsqueeze(-1), torch.zeros_like(s[..., 1:]))
+    return L
+
+
+def _moments_sample_cov(mom, key, S, track):
+    """moments_sample for moments that carry a covariance."""
+    who = "moments_sample"
+    if _tracking(track):
+        raise BnnHipError("%s: moments that carry a covariance have no backward (sample_moments / track=True)" % who)
+    m, cov = mom.mean.detach(), mom.cov.detach()
+    N = m.shape[-1]
+    if not m.is_cuda:
+        Lc = cholesky_pivot_f64(cov)
+        eps = torch.randn((S,) + tuple(m.shape), dtype=torch.float64)
+        return (m.to(torch.float64) + torch.einsum('...ik,s...k->s...i', Lc, eps)).to(torch.float32)
+    m, cov = m.contiguous(), cov.contiguous()
+    require_cuda_f32(m, "mean")
+    require_cuda_f32(cov, "cov")
+    if N > HEAD_COV_MAX_N:
+        raise BnnHipError("%s: a covariance over %d outputs (at most %d)" % (who, N, HEAD_COV_MAX_N))
+    if S < 1 or S > 0xFFFF:
+        raise BnnHipError("%s: %d MC samples (1 .. 65535)" % (who, S))
+    if m.numel() >= 2 ** 32:
+        raise BnnHipError("%s: one sample has %d elements: the noise index is 32 bits wide" % (who, m.numel()))
+    rows = m.numel() // N
+    y = torch.empty((S,) + tuple(m.shape), dtype=torch.float32, device=m.device)
+    r = _rng_struct(key, m.device)
+    check(_lib.load().bnn_moments_sample_cov(ptr(m), ptr(cov), ptr(y), rows, N, S, ctypes.byref(r), 0, stream_ptr(m.device)),
+          "bnn_moments_sample_cov")
+    return y
 
 
 class _PlainLinear(torch.autograd.Function):

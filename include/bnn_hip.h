@@ -1287,6 +1287,46 @@ int bnn_moments_batchnorm(const float *m, const float *v, const float *gamma, co
                           const float *running_var, float eps, float *out_m, float *out_v, int64_t B, int64_t C, int64_t inner,
                           void *stream);
 
+/* ---- K21: the head of a sampling-free pass (csrc/bnn_moments_head.hip; ops.moments_mvn_linear, ops.moments_head_cov,
+ * ops.moments_sample on moments that carry a covariance).  Inference only, fp32 in both compute modes, no atomics and no split
+ * reductions: every sum is one ascending fp32 fma chain and identical calls give identical bits.  Graph-capturable; every error is
+ * returned before anything is launched.  Every operand may lie on its element (all loads and stores are one element wide).
+ *
+ * MultivariateNormalLinear draws w_o = mu_o + L_o u with UNIFORM u ~ U[0, 1)^K and L = sqrt[tril[softplus[scale]] + 1e-10 I] taken
+ * element by element (L is lower-triangular; the bits of L are bnn_mvn_draw's, one device function); its bias is one row of O
+ * elements with an O x O factor L_b.  So per weight row o
+ *     E_w[o,k] = mu[o,k] + 1/2 sum_{j<=k} L[o,k,j]      D[o,k] = 1/12 sum_{j<=k} L[o,k,j]^2      G_w = E_w^2 + D
+ *     E_b      = mu_b + 1/2 L_b 1                        C_b    = L_b L_b^T / 12   [O x O]
+ * and for an input with independent elements of mean a_m and variance a_v (a_v NULL: a deterministic input)
+ *     m[b,o] = sum_k a_m[b,k] E_w[o,k] + E_b[o]
+ *     v[b,o] = 1/12 sum_j [sum_{k>=j} a_m[b,k] L[o,k,j]]^2 + sum_k a_v[b,k] G_w[o,k] + C_b[o,o]
+ * the exact mean and variance of the layer's output (no Gaussian assumption).
+ *
+ * bnn_mvn_moments_prepare: ONE launch, independent of the input.  mu_w [O, K], scale_w [O, K, K] (its upper triangles are never
+ * read), mu_b [O], scale_b [O, O] -> E_w, G_w [O, K], E_b [O], C_b [O, O] (both triangles, from one computed value).  mu_b, scale_b,
+ * E_b, C_b: all given or all NULL.  Row sums run in ascending j.  K <= 4096, O < 2^15 (with a bias O <= 4096), O K < 2^31.
+ * bnn_mvn_moments_forward: ONE launch.  a_m, a_v [B, K] with row pitch lda; out_m, out_v [B, O].  L is formed from scale_w on the
+ * fly; E_b, C_b both or neither.  K <= 4096, B <= 64 * 65535 (BNN_E_RANGE beyond). */
+int bnn_mvn_moments_prepare(const float *mu_w, const float *scale_w, const float *mu_b, const float *scale_b, float *E_w, float *G_w,
+                            float *E_b, float *C_b, int64_t O, int64_t K, void *stream);
+int bnn_mvn_moments_forward(const float *a_m, const float *a_v, int64_t lda, const float *scale_w, const float *E_w, const float *G_w,
+                            const float *E_b, const float *C_b, float *out_m, float *out_v, int64_t B, int64_t O, int64_t K,
+                            void *stream);
+/* The N x N covariance of a dense head's outputs per batch row, for inputs with independent elements of variance a_v:
+ *     cov[b,o,p] = sum_k [E[o,k] E[p,k]] a_v[b,k] + C_b[o,p]   (o != p)        cov[b,o,o] = var[b,o]
+ * E [N, K] the weights' means (an MVN head: E_w; a Gaussian head: mu_w; a deterministic one: w), C_b [N, N] the bias covariance or
+ * NULL (no bias term), var [B, N] the head's output variance, cov [B, N, N].  Both triangles are written from one computed value and
+ * the diagonal is var's bits.  a_v NULL (a deterministic input): the off-diagonal is C_b's (E may be NULL).  N <= 32, B < 2^31. */
+int bnn_moments_head_cov(const float *a_v, int64_t lda, const float *E, const float *C_b, const float *var, float *cov, int64_t B,
+                         int64_t N, int64_t K, void *stream);
+/* y_s[b,:] = m[b,:] + Lc_b eps_s[b,:], s = 0 .. nsamples - 1, ONE launch: Lc_b the lower Cholesky factor of cov[b] (its lower
+ * triangle is read), computed in fp64 from the fp32 cov; a pivot <= 0 gives a zero column (a direction without variance: a
+ * semi-definite covariance, or one made so by rounding).  The product is accumulated in fp64 and m + Lc eps is rounded once to fp32.
+ * eps_s[b,n] is element e = b N + n of the key's sample sample0 + s (the LRT-noise contract above): bnn_moments_sample's values on
+ * the same key.  m [rows, N], cov [rows, N, N], y [nsamples, rows, N].  N <= 32, rows N < 2^32, nsamples <= 65535; flags is 0. */
+int bnn_moments_sample_cov(const float *m, const float *cov, float *y, int64_t rows, int64_t N, int nsamples, const bnn_rng_t *rng,
+                           int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
