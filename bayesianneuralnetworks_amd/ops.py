@@ -2116,6 +2116,8 @@ def moments_head_cov_f64(head, var):
         cov = cov + torch.einsum('ok,pk,bk->bop', E, E, f64(a_v))
     if C_b is not None:
         cov = cov + f64(C_b)
+    # symmetric bit for bit, whatever order the BLAS behind einsum multiplies E[o] a_v E[p] in (x + y == y + x exactly)
+    cov = 0.5 * (cov + cov.transpose(-1, -2))
     idx = torch.arange(N, device=var.device)
     cov[:, idx, idx] = var
     return cov

@@ -468,8 +468,12 @@ FWD_CASES = {
 @pytest.mark.parametrize("S", [1, 4, 8, 33])
 @pytest.mark.parametrize("name", sorted(FWD_CASES))
 def test_forward_matches_float64_on_the_keys_eps(dev, name, S, shared, bias, mode):
-    case = FWD_CASES[name]
     assert FWD_CASES["peraxis2d"].P % 2 == 1 and (FWD_CASES["peraxis2d"].B * FWD_CASES["peraxis2d"].P) % 64 != 0
+    check_forward(dev, FWD_CASES[name], name, S, shared, bias, mode)
+
+
+def check_forward(dev, case, name, S, shared, bias, mode):
+    """One forward of `case` (named `name` in messages) against float64 on the key's eps, every element."""
     params = case.params(bias, 11)
     g = torch.Generator().manual_seed(12)
     x = torch.randn(*((case.B,) if shared else (S, case.B)), case.C, *case.sp, generator=g)
@@ -575,7 +579,11 @@ BWD_CASES = {
 @pytest.mark.parametrize("name", sorted(BWD_CASES))
 def test_backward_matches_float64_on_the_keys_eps(dev, name, S, shared, bias, mode):
     """All five gradients, every element; image 1 of the batch is all zero (v = sigma_b^2 there, and v = 0 without bias)."""
-    case = BWD_CASES[name]
+    check_backward(dev, BWD_CASES[name], name, S, shared, bias, mode)
+
+
+def check_backward(dev, case, name, S, shared, bias, mode):
+    """One backward of `case` (named `name` in messages) against float64 on the key's eps -> the device's gradients."""
     params = case.params(bias, 31)
     g = torch.Generator().manual_seed(32)
     x = torch.randn(*((case.B,) if shared else (S, case.B)), case.C, *case.sp, generator=g)
@@ -601,7 +609,7 @@ def test_backward_matches_float64_on_the_keys_eps(dev, name, S, shared, bias, mo
         want = torch.autograd.grad((yr * gy.double()).sum(), ref)
         for n, a, w in zip(names, got, want):
             assert_within(a, w, scaled_bound(w), "g %s %s S=%d f32" % (n, name, S))
-        return
+        return got
     x64, xsq, mu64, s2, mb, s2b = operands64(case, x, mu_w, rho_w, mu_b, rho_b, mode, dev)
     v = case.conv(xsq, s2, s2b)                                          # every term >= 0: v is its own sum |a| |b|
     gy64 = gy.double()
@@ -621,6 +629,7 @@ def test_backward_matches_float64_on_the_keys_eps(dev, name, S, shared, bias, mo
                       rnd=lambda t, beta: round_hidden(t, beta)[:2], betas=(flat(beta_m), flat(beta_v)))
     for n, a, (w, bound) in zip(names, got, want):
         assert_within(a.reshape(w.shape), w, bound + 1e-30, "g %s %s S=%d bf16" % (n, name, S))
+    return got
 
 
 @gpu

@@ -475,18 +475,24 @@ def backward_case(name, bias):
     """CPU operands of one case: (a_m, a_v, G_m, G_v, mu_w, rho_w, rho_b, geo); a_v with exact zeros, G of both signs."""
     key = (name, bias)
     if key not in _case_cache:
-        xs, O, kernel, stride, padding, dilation, groups, has_bias = ALL_CASES[name]
-        mu_w, rho_w, _, rho_b = conv_params(O, xs[1] // groups, kernel, bias and has_bias, 11)
-        mom = conv_input(xs, True, 12)
-        a_v = mom.var.clone()
-        a_v[a_v < 0.02] = 0.0                                  # a fifth of the variances are exact zeros
-        a_v[0, 0] = 0.0                                         # and one whole channel of one image
-        geo = (stride, padding, dilation, groups)
-        out = convnd(len(kernel))(mom.mean, mu_w, None, *geo)
-        g = torch.Generator().manual_seed(13)
-        G_m, G_v = torch.randn(out.shape, generator=g), torch.randn(out.shape, generator=g)
-        _case_cache[key] = (mom.mean, a_v, G_m, G_v, mu_w, rho_w, rho_b, geo)
+        _case_cache[key] = backward_operands(ALL_CASES[name], bias)
     return _case_cache[key]
+
+
+def backward_operands(spec, bias):
+    """backward_case's operands for a geometry given as CASES' tuple (input shape, O, kernel, stride, padding, dilation, groups,
+    has a bias)."""
+    xs, O, kernel, stride, padding, dilation, groups, has_bias = spec
+    mu_w, rho_w, _, rho_b = conv_params(O, xs[1] // groups, kernel, bias and has_bias, 11)
+    mom = conv_input(xs, True, 12)
+    a_v = mom.var.clone()
+    a_v[a_v < 0.02] = 0.0                                  # a fifth of the variances are exact zeros
+    a_v[0, 0] = 0.0                                         # and one whole channel of one image
+    geo = (stride, padding, dilation, groups)
+    out = convnd(len(kernel))(mom.mean, mu_w, None, *geo)
+    g = torch.Generator().manual_seed(13)
+    G_m, G_v = torch.randn(out.shape, generator=g), torch.randn(out.shape, generator=g)
+    return (mom.mean, a_v, G_m, G_v, mu_w, rho_w, rho_b, geo)
 
 
 def backward_device(dev, mode, a_m, a_v, G_m, G_v, mu_w, rho_w, rho_b, geo, ws_off=0):
