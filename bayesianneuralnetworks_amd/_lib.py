@@ -256,6 +256,8 @@ SIGNATURES = {
     "bnn_mvn_moments_forward": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "bnn_moments_head_cov": (_int, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "bnn_moments_sample_cov": (_int, [_p, _p, _p, _i64, _i64, _int, _rngp, _int, _p]),
+    "bnn_moments_dropout": (_int, [_p, _p, _p, _p, _i64, ctypes.c_float, _int, ctypes.c_float, _p]),
+    "bnn_moments_dropout_backward": (_int, [_p, _p, _p, _p, _p, _p, _i64, ctypes.c_float, _int, ctypes.c_float, _p]),
 }
 
 _lib = None

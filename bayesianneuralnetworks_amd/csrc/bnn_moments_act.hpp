@@ -148,6 +148,90 @@ __device__ __forceinline__ void moments_elu_bwd_dev(float mf, float vf, float a_
     gv = (float)((double)gom * (0.5 * dv) + go_v * (cdf + a * a * (2.0 * e2 - e1) - mean * dv));
 }
 
+// MC dropout behind a Gaussian pre-activation z ~ N(m, v), pushed through the activation f that follows in ONE step (K22):
+// y = f(b z / q) with b ~ Bernoulli(q) independent of z, q = 1 - p, f(0) = 0 (the identity, ReLU, ELU), so y = b f(z / q).  With
+// (M, V) the moments of f at the Gaussian N(m / q, v / q^2) -- moments_relu_dev / moments_elu_dev; the identity's are the input:
+//     mean' = q M
+//     var'  = q V + q p M^2
+// (the mixture of the spike at 0 and f's distribution: both addends >= 0, E[y^2] - mean'^2 is never formed).  Exact for a Gaussian
+// and for a deterministic z (v == 0, through the activations' own limit branches, which a NaN takes too).  act: 0, BNN_FLAG_RELU or
+// BNN_FLAG_ELU -- a constant where the kernels call this.  The identity and the ReLU work in fp32; the ELU scales its input and
+// recombines its results in fp64, as moments_elu_dev works inside.  p == 0 is the activation alone, its bits; p == 1 is (0, 0) and
+// nothing is divided by q.
+__device__ __forceinline__ void moments_act_dev(float m, float v, int act, float a_elu, float &om, float &ov)
+{
+    if (act == BNN_FLAG_RELU) moments_relu_dev(m, v, om, ov);
+    else if (act == BNN_FLAG_ELU) moments_elu_dev(m, v, a_elu, om, ov);
+    else { om = m; ov = v; }
+}
+
+__device__ __forceinline__ void moments_dropout_dev(float m, float v, float p, int act, float a_elu, float &om, float &ov)
+{
+    if (p == 0.0f) {
+        moments_act_dev(m, v, act, a_elu, om, ov);
+        return;
+    }
+    if (p >= 1.0f) {
+        om = 0.0f;
+        ov = 0.0f;
+        return;
+    }
+    float M, V;
+    if (act == BNN_FLAG_ELU) {
+        const double q = 1.0 - (double)p;
+        moments_elu_dev((float)((double)m / q), (float)((double)v / (q * q)), a_elu, M, V);
+        om = (float)(q * (double)M);
+        ov = (float)(q * (double)V + q * (double)p * (double)M * (double)M);
+        return;
+    }
+    const float q = 1.0f - p;
+    moments_act_dev(m / q, v / (q * q), act, a_elu, M, V);
+    om = q * M;
+    ov = q * V + q * p * M * M;
+}
+
+// Backward of moments_dropout_dev: (g_m, g_v) from the gradients (gm', gv') of its two outputs.  With (M, V) as above,
+//     gM = q gm' + 2 q p M gv',    gV = q gv'
+// go through the activation's own backward at (m / q, v / q^2) (moments_relu_bwd_dev / moments_elu_bwd_dev; the identity passes
+// them), and g_m = g_mi / q, g_v = g_vi / q^2.  M is the forward's, evaluated again.  p == 0: the activation's backward alone, its
+// bits; p == 1: zeros.
+__device__ __forceinline__ void moments_act_bwd_dev(float m, float v, int act, float a_elu, float gom, float gov, float &gm, float &gv)
+{
+    if (act == BNN_FLAG_RELU) moments_relu_bwd_dev(m, v, gom, gov, gm, gv);
+    else if (act == BNN_FLAG_ELU) moments_elu_bwd_dev(m, v, a_elu, gom, gov, gm, gv);
+    else { gm = gom; gv = gov; }
+}
+
+__device__ __forceinline__ void moments_dropout_bwd_dev(float m, float v, float p, int act, float a_elu, float gom, float gov, float &gm,
+                                                        float &gv)
+{
+    if (p == 0.0f) {
+        moments_act_bwd_dev(m, v, act, a_elu, gom, gov, gm, gv);
+        return;
+    }
+    if (p >= 1.0f) {
+        gm = 0.0f;
+        gv = 0.0f;
+        return;
+    }
+    float M, V, gmi, gvi;
+    if (act == BNN_FLAG_ELU) {
+        const double q = 1.0 - (double)p;
+        const float mi = (float)((double)m / q), vi = (float)((double)v / (q * q));
+        moments_elu_dev(mi, vi, a_elu, M, V);
+        const float gM = (float)(q * (double)gom + 2.0 * q * (double)p * (double)M * (double)gov), gV = (float)(q * (double)gov);
+        moments_elu_bwd_dev(mi, vi, a_elu, gM, gV, gmi, gvi);
+        gm = (float)((double)gmi / q);
+        gv = (float)((double)gvi / (q * q));
+        return;
+    }
+    const float q = 1.0f - p, mi = m / q, vi = v / (q * q);
+    moments_act_dev(mi, vi, act, a_elu, M, V);
+    moments_act_bwd_dev(mi, vi, act, a_elu, q * gom + 2.0f * q * p * M * gov, q * gov, gmi, gvi);
+    gm = gmi / q;
+    gv = gvi / (q * q);
+}
+
 // Maximum of two independent Gaussians N(m1, v1), N(m2, v2) by moment matching (K20; Clark 1961), the step a max-pooling window
 // is folded with.  theta^2 = v1 + v2, d = m1 - m2, alpha = d / theta, Phi = Phi(alpha), Phi_c = Phi(-alpha), phi = phi(alpha):
 //     mean' = m1 Phi + m2 Phi_c + theta phi

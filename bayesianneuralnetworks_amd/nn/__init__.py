@@ -15,6 +15,7 @@ from .loss import KLDivergence, Entropy, NormalInverseGaussianLoss, NormalInvers
 from .loss import GaussianNLL   # (not in __all__ either)
 from ._settings import set_compute, get_compute, fuse_activations, fuse_kl_gradient, keyed_mvn_draws, moment_activations
 from ._settings import conv_moment_training, conv_moment_training_enabled
+from ._settings import moment_estimator_layers, moment_estimator_layers_enabled
 
 # the names pytorch_bayesian/nn/__init__.py:7-35 exports
 __all__ = [

@@ -56,7 +56,8 @@ def conv_moment_training(enable=True):
     admits NormalConv1d / 2d / 3d, LocalReparamConv1d / 2d / 3d, nn.MomentELU and nn.MomentLinear -- their moment layers keep the
     autograd graph, and every backward launch is HIP (k_moments_conv3d_bwd, bnn_moments_elu_backward; K11's launches for a
     deterministic input, K18's for MomentLinear).  With it off forward_moments refuses exactly what it refused before, with the
-    same messages.  Flipout, MC-dropout, multivariate-normal and evidential layers stay refused either way.  Making it the
+    same messages.  Multivariate-normal and evidential layers stay refused either way; Flipout and MC-dropout layers
+    unless nn.moment_estimator_layers() is on (K22).  Making it the
     default is a separate step: tests/test_moment_backward.py::test_forward_moments_refuses_what_has_no_backward pins the
     refusal of NormalConv2d and MomentELU."""
     global _conv_moment_training
@@ -65,6 +66,29 @@ def conv_moment_training(enable=True):
 
 def conv_moment_training_enabled():
     return _conv_moment_training
+
+
+_moment_estimator_layers = False
+
+
+def moment_estimator_layers(enable=True):
+    """Opt-in (default off) for sampling-free passes through the layers whose randomness is an estimator's rather than a weight
+    posterior's draw (K22): with it on, BayesianNetworkModule.predictive_moments and the predictive_* methods with
+    propagation='moments' admit MCDropoutLinear, MCDropoutConv1d / 2d / 3d, FlipoutNormalLinear and FlipOutNormalConv1d / 2d / 3d;
+    forward_moments admits the dense ones, and the conv ones when nn.conv_moment_training() is on as well.  An MC-dropout layer
+    runs its contraction on the moments (ops.moments_affine / ops.moments_conv_affine; its own linear / conv on a deterministic
+    input) and then ONE bnn_moments_dropout launch that pushes the mask through the activation nn.moment_activations found
+    behind it -- exact, where moment-matching the mask in front of a ReLU / ELU is not; directly in front of an
+    nn.MomentSoftmax it hands on the pre-dropout moments with dropout = p and the predictive_* tails mask the drawn logits.  A
+    Flipout layer runs its Normal* parent's moment pass on the same parameters (no bias).  With it off every refusal and every
+    message stays what it was.  Making it the default is a separate step:
+    tests/test_moment_conv_backward.py pins forward_moments' refusals of these layers by name."""
+    global _moment_estimator_layers
+    _moment_estimator_layers = bool(enable)
+
+
+def moment_estimator_layers_enabled():
+    return _moment_estimator_layers
 
 
 def fuse_activations(module, bf16_activations=False, fuse_head=False):
@@ -138,13 +162,23 @@ def moment_activations(module):
     * a twin directly behind a NormalConv1d / 2d / 3d or LocalReparamConv1d / 2d / 3d is made known to that layer
       (`_moment_act`, a __dict__ entry, not a submodule): in a moment pass the activation runs in the conv launch's epilogue
       (the standalone launch's bits) and the twin passes the result through.  Behind a dense layer the twins use the
-      standalone launches.
+      standalone launches.  FlipOutNormalConv1d / 2d / 3d are told in the same way.
+    * a twin directly behind an MCDropoutLinear or MCDropoutConv1d / 2d / 3d is made known to that layer as well (K22,
+      nn.moment_estimator_layers): in a moment pass the layer's ONE bnn_moments_dropout launch pushes its mask through that
+      activation and the twin passes the result through; an `nn.MomentSoftmax` directly behind it is recorded as 'softmax' --
+      the layer then hands on its pre-dropout moments and the softmax keeps the mask for the predictive_* tails (dropout = p).
+      Anything else behind the layer clears the entry.  After changing such a Sequential call this function again: a stale
+      entry raises ops.BnnHipError in the pass.
 
     Idempotent; state_dict keys are unchanged (the activations have no state).  Returns the number of modules replaced."""
     import torch
     from .container import BayesianModule, MomentReLU, MomentELU, MomentLinear, MomentSoftmax, _MOMENT_RECLASS
     from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
-    convs = (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
+    from .conv import (FlipOutNormalConv1d, FlipOutNormalConv2d, FlipOutNormalConv3d, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d)
+    from .dense import MCDropoutLinear
+    convs = (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d,
+             FlipOutNormalConv1d, FlipOutNormalConv2d, FlipOutNormalConv3d)
+    dropouts = (MCDropoutLinear, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d)
     replaced = 0
     for m in module.modules():
         if not isinstance(m, torch.nn.Sequential):
@@ -176,4 +210,15 @@ def moment_activations(module):
                     la.__dict__["_moment_act"] = lb._moment_spec()
                 else:
                     la.__dict__.pop("_moment_act", None)
+            elif type(la) in dropouts:
+                # K22: the mask goes through the activation behind the layer in the layer's own launch; a softmax cannot take
+                # it (softmax(0) != 0), so there the layer hands the mask on to the predictive_* tails
+                if isinstance(lb, (MomentReLU, MomentELU)):
+                    la.__dict__["_moment_act"] = lb._moment_spec()
+                elif isinstance(lb, MomentSoftmax):
+                    la.__dict__["_moment_act"] = 'softmax'
+                else:
+                    la.__dict__.pop("_moment_act", None)
+        if mods and type(mods[-1]) in dropouts:
+            mods[-1].__dict__.pop("_moment_act", None)
     return replaced

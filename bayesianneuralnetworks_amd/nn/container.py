@@ -48,10 +48,44 @@ _MOMENTS_SUPPORTED = ("moment propagation supports NormalLinear / LocalReparamLi
                       "reshaping modules such as torch.nn.Flatten, and torch.nn.Identity")
 
 
+_MOMENTS_SUPPORTED_K22 = ("; with nn.moment_estimator_layers switched on also MCDropoutLinear, MCDropoutConv1d / 2d / 3d (the mask "
+                          "pushed through the ReLU / ELU behind the layer, or handed to the tail in front of a closing Softmax), "
+                          "FlipoutNormalLinear and FlipOutNormalConv1d / 2d / 3d")
+
+
+def _estimator_layers():
+    """The layer classes nn.moment_estimator_layers admits to a moment pass (K22); () while the switch is off."""
+    from . import _settings
+    if not _settings.moment_estimator_layers_enabled():
+        return ()
+    from .dense import MCDropoutLinear, FlipoutNormalLinear
+    from .conv import (MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d, FlipOutNormalConv1d, FlipOutNormalConv2d,
+                       FlipOutNormalConv3d)
+    return (MCDropoutLinear, FlipoutNormalLinear, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d, FlipOutNormalConv1d,
+            FlipOutNormalConv2d, FlipOutNormalConv3d)
+
+
+def _refuse_pending(y, who):
+    """The output of a moment pass must not carry a mask that no nn.MomentSoftmax took over (K22)."""
+    if y._pending is not None:
+        from .. import ops
+        raise ops.BnnHipError("%s: the network's output carries the pending mask (dropout=%r) of an MC-dropout layer that "
+                              "nn.moment_activations found in front of an nn.MomentSoftmax, and no such softmax followed: call "
+                              "nn.moment_activations again after changing a Sequential" % (who, y._pending))
+
+
+def _moments_supported():
+    """_MOMENTS_SUPPORTED, naming the K22 layers while nn.moment_estimator_layers is on."""
+    return _MOMENTS_SUPPORTED + (_MOMENTS_SUPPORTED_K22 if _estimator_layers() else "")
+
+
 def _moment_twin_forward(self, parent, x, apply):
     """forward of nn.MomentReLU / MomentELU: a tensor takes the parent's forward (its bits, on every sampling path); an
     ops.Moments is moment-matched by `apply` -- unless the conv launch that produced it already ran this activation in its
-    epilogue (nn.moment_activations told that layer; the Moments says which activation it carries)."""
+    epilogue (nn.moment_activations told that layer; the Moments says which activation it carries).  Moments that an MC-dropout
+    layer folded its mask into with NO activation (K22: _act == 'identity' -- nn.moment_activations never told that layer about
+    this module) are refused: a dropped unit is a spike at zero, and the Gaussian recursion of this module on mask-matched moments
+    would be the wrong answer, silently."""
     from .. import ops
     if not isinstance(x, ops.Moments):
         return parent.forward(self, x)
@@ -127,10 +161,15 @@ class MomentSoftmax(torch.nn.Softmax):
         from .. import ops
         if not isinstance(x, ops.Moments):
             return torch.nn.Softmax.forward(self, x)
-        ops._refuse_link(x, "MomentSoftmax")
+        pending, x._pending = x._pending, None                            # (K22) the mask of the MC-dropout layer in front
+        try:
+            ops._refuse_link(x, "MomentSoftmax")
+        finally:
+            x._pending = pending
         if self.dim not in (-1, x.dim() - 1):
             raise ops.BnnHipError("MomentSoftmax: softmax over axis %r of %d; only the last axis is supported" % (self.dim, x.dim()))
-        out = ops.Moments(x.mean, x.var, link='softmax', cov=x.cov)      # the one module that keeps a covariance (K21)
+        # the one module that keeps a covariance (K21) and a pending mask (K22: dropout = p, applied to the drawn logits)
+        out = ops.Moments(x.mean, x.var, link='softmax', cov=x.cov, dropout=pending)
         out._head = x._head
         return out
 
@@ -467,6 +506,11 @@ class BayesianNetworkModule(Module):
                                       "to run `advance` in")
             self._moment_refusals("predictive_regression", kl)
             mom = self.predictive_moments(x, covariance=covariance, **kwargs)
+            if mom.dropout is not None:
+                raise ops.BnnHipError("predictive_regression: outputs='values' with propagation='moments' reads the propagated "
+                                      "moments as they are; these are the PRE-dropout moments of an MC-dropout head whose mask "
+                                      "(dropout=%r) is still to be applied to samples, in front of a %s link"
+                                      % (mom.dropout, mom.link))
             if mom.link is not None:
                 raise ops.BnnHipError("predictive_regression: outputs='values' with propagation='moments' reads the propagated "
                                       "moments as they are; this network ends in a %s link" % mom.link)
@@ -556,29 +600,50 @@ class BayesianNetworkModule(Module):
         covariance).  With one hidden layer and a deterministic input the hidden activations are independent and cov is exact.
         The network must end in a dense layer of at most 32 outputs (NormalLinear, LocalReparamLinear, nn.MomentLinear,
         MultivariateNormalLinear), with nothing but a closing nn.MomentSoftmax behind it; otherwise ops.BnnHipError says why.
-        ops.moments_sample and the predictive_* tails (covariance=True) draw correlated outputs from it.  Not covered: the backward
-        of any of this, Flipout and MC-dropout layers, covariance between hidden activations or conv positions, non-default priors."""
+        ops.moments_sample and the predictive_* tails (covariance=True) draw correlated outputs from it.
+        K22, with nn.moment_estimator_layers() switched on (off by default: these layers are then refused as before):
+        MCDropoutLinear and MCDropoutConv1d / 2d / 3d run their deterministic contraction on the moments (ops.moments_affine /
+        ops.moments_conv_affine; the layer's own linear / conv on a deterministic input) and then ONE bnn_moments_dropout launch
+        that pushes the mask through the ReLU / ELU nn.moment_activations found behind the layer (the identity without one):
+        mean' = q M, var' = q V + q p M^2 with (M, V) the activation's moments at N(m / q, v / q^2) -- exact for a Gaussian
+        pre-activation and for a deterministic one, so a net of the Titanic example's shape has exact logit moments.  An
+        MC-dropout layer directly in front of the closing nn.MomentSoftmax hands on its PRE-dropout moments and the result carries
+        dropout = p: the predictive_* tails mask the drawn logits (keyed masks on a model-level stream, model.moment_mask_key).
+        FlipoutNormalLinear runs NormalLinear's pass on its parameters (its sign sampler's own marginal mean and variance);
+        FlipOutNormalConv1d / 2d / 3d run NormalConv's, the moments of the weight posterior N(mu, sigma^2) that KLDivergence
+        regularises (the reference's conv sign sampler shares one sign per input channel across the kernel taps, so its own
+        marginal variance, sum_c (sum_tap x sigma)^2, differs from the posterior's sum x^2 sigma^2).  covariance=True is refused
+        at a head of these kinds.
+        Not covered: the backward of K21, covariance between hidden activations or conv positions, non-default priors, the
+        evidential head."""
         from .. import ops
         from .dense import NormalLinear, LocalReparamLinear, MultivariateNormalLinear
         from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
         admitted = (NormalLinear, LocalReparamLinear, MultivariateNormalLinear, NormalConv1d, NormalConv2d, NormalConv3d,
-                    LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
+                    LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d) + _estimator_layers()
         for m in self.modules():
             if isinstance(m, BayesianModule) and type(m) not in admitted:
-                raise ops.BnnHipError("predictive_moments: %s is not supported; %s" % (type(m).__name__, _MOMENTS_SUPPORTED))
+                raise ops.BnnHipError("predictive_moments: %s is not supported; %s" % (type(m).__name__, _moments_supported()))
         with torch.no_grad(), _mc.MomentContext(covariance=covariance) as mctx:
             try:
                 y = self._forward(x, *args, **kwargs)
             except (TypeError, AttributeError) as e:
                 raise ops.BnnHipError("predictive_moments: a module of this network cannot take a mean and a variance (%s); %s"
-                                      % (e, _MOMENTS_SUPPORTED)) from e
+                                      % (e, _moments_supported())) from e
         if torch.is_tensor(y):
             y = ops.Moments(y.detach(), None)
         if not isinstance(y, ops.Moments):
-            raise ops.BnnHipError("predictive_moments: _forward returned %s; %s" % (type(y).__name__, _MOMENTS_SUPPORTED))
+            raise ops.BnnHipError("predictive_moments: _forward returned %s; %s" % (type(y).__name__, _moments_supported()))
+        _refuse_pending(y, "predictive_moments")
         if covariance:
             if y._head is None:
                 dense = mctx.last_dense
+                from .dense import MOMENT_ESTIMATOR_LAYERS
+                if dense is not None and dense[0] in MOMENT_ESTIMATOR_LAYERS:
+                    raise ops.BnnHipError("predictive_moments: covariance=True is not covered at a %s head: an MC-dropout layer's "
+                                          "outputs are uncorrelated only through masks that the covariance launch does not know, and "
+                                          "a Flipout layer's outputs share their signs (K21 carries the covariance of NormalLinear, "
+                                          "LocalReparamLinear, nn.MomentLinear and MultivariateNormalLinear heads)" % dense[0])
                 if dense is None:
                     why = "its last layer is not dense: the pass went through no dense layer at all"
                 elif dense[1] > ops.HEAD_COV_MAX_N and y.dim() and y.shape[-1] == dense[1]:
@@ -592,7 +657,7 @@ class BayesianNetworkModule(Module):
             y = ops.moments_resolve_cov(y)
         if not y.mean.is_cuda:
             return ops.Moments(y.mean.to(torch.float32), None if y.var is None else y.var.to(torch.float32), y.link,
-                               cov=None if y.cov is None else y.cov.to(torch.float32))
+                               cov=None if y.cov is None else y.cov.to(torch.float32), dropout=y.dropout)
         return y
 
     def _moment_refusals(self, who, kl):
@@ -618,14 +683,29 @@ class BayesianNetworkModule(Module):
         from .._rng import DrawKey, default_generator, generator_for, new_stream_id
         from . import _settings
         link = (lambda ys: torch.softmax(ys, -1)) if mom.link == 'softmax' else (lambda ys: ys)
+        p = mom.dropout                      # K22: the mask of an MC-dropout head, applied to the drawn logits in front of the link
         if not mom.mean.is_cuda:
-            return link(ops.moments_sample(mom, None, samples, track))
+            ys = ops.moments_sample(mom, None, samples, track)
+            if p is not None:                # F.dropout's mask and scale, one mask per sample, row and logit
+                ys = ys * (torch.rand(ys.shape) >= p).to(ys.dtype) * (0.0 if p >= 1.0 else 1.0 / (1.0 - p))
+            return link(ys)
         if self.__dict__.get("_moment_stream") is None:
             self.__dict__["_moment_stream"] = new_stream_id()
         key = DrawKey(default_generator.seed, self.__dict__["_moment_stream"], sample0, samples, default_generator.next_epoch(),
                       gen=generator_for(_settings.get_compute()))
         self.__dict__["moment_key"] = key
-        return link(ops.moments_sample(mom, key, samples, track))
+        ys = ops.moments_sample(mom, key, samples, track)
+        if p is not None:
+            # the keyed masks of the mask contract on a model-level stream of its own (taken at first use), the key on the moment
+            # key's seed, epoch and sample0: sample s = row // rows of the (S * rows, ...) stack; bnn_mc_dropout_backward when tracked
+            if self.__dict__.get("_moment_mask_stream") is None:
+                self.__dict__["_moment_mask_stream"] = new_stream_id()
+            mkey = DrawKey(key.seed, self.__dict__["_moment_mask_stream"], sample0, samples, key.epoch_host, gen=key.gen)
+            self.__dict__["moment_mask_key"] = mkey
+            flat = ys.reshape((-1,) + tuple(ys.shape[2:])) if ys.dim() > 2 else ys
+            flat = flat if track and torch.is_grad_enabled() else flat.detach()
+            ys = ops.mc_dropout(flat, p, mkey, shared=False).reshape(ys.shape)
+        return link(ys)
 
     def forward_moments(self, x, *args, **kwargs):
         """Training without sampling (Wu et al. 2019): predictive_moments' ONE pass of `_forward(x)` with its autograd graph ->
@@ -641,6 +721,10 @@ class BayesianNetworkModule(Module):
         deterministic input), the ELU's bnn_moments_elu_backward, MomentLinear's K18's two launches; the other layers stay refused.
         The pooling twins nn.MomentMaxPool / MomentAvgPool / MomentAdaptiveAvgPool 1d / 2d / 3d (K20) are admitted with no switch:
         their backward is bnn_moments_pool3d_backward; nn.MomentBatchNorm1d / 2d / 3d has no backward and is refused by name.
+        With nn.moment_estimator_layers() switched on (K22) MCDropoutLinear and FlipoutNormalLinear are admitted, and nn.MomentELU
+        with them; MCDropoutConv / FlipOutNormalConv 1d / 2d / 3d when nn.conv_moment_training() is on as well.  The mask's
+        backward is bnn_moments_dropout_backward, the deterministic contractions' K18's / K19's launches with a zero sigma^2
+        plane; a mask handed to sample_moments (an MC-dropout head in front of the softmax) has bnn_mc_dropout_backward.
         Regression: mean(((y - mom.mean)^2 + mom.var) / (2 s^2)) needs no sample; classification: sample_moments."""
         from .. import ops
         from . import _settings
@@ -649,13 +733,18 @@ class BayesianNetworkModule(Module):
         convs_on = _settings.conv_moment_training_enabled()
         admitted = (NormalLinear, LocalReparamLinear) + ((NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d,
                                                            LocalReparamConv2d, LocalReparamConv3d) if convs_on else ())
+        # K22 (nn.moment_estimator_layers): the dense estimator layers, and their conv forms with nn.conv_moment_training
+        admitted += tuple(c for c in _estimator_layers() if convs_on or "Conv" not in c.__name__)
         for m in self.modules():
             if isinstance(m, _MOMENT_BATCHNORMS):                                   # (named first, whatever else the network holds)
                 raise ops.BnnHipError("forward_moments: %s has no moment backward (K20 propagates moments through an eval-mode "
                                       "BatchNorm for inference only); the pooling twins nn.MomentMaxPool / MomentAvgPool / "
                                       "MomentAdaptiveAvgPool 1d / 2d / 3d have one" % type(m).__name__)
         for m in self.modules():
-            if (isinstance(m, BayesianModule) and type(m) not in admitted) or (not convs_on and isinstance(m, (MomentELU, MomentLinear))):
+            # (K22: with nn.moment_estimator_layers on, nn.MomentELU is admitted without nn.conv_moment_training -- behind an
+            # MC-dropout layer it only passes on what bnn_moments_dropout computed, elsewhere its backward is K19's launch)
+            if (isinstance(m, BayesianModule) and type(m) not in admitted) or (
+                    not convs_on and isinstance(m, (MomentLinear,) if _estimator_layers() else (MomentELU, MomentLinear))):
                 raise ops.BnnHipError("forward_moments: %s has no moment backward; training without sampling supports "
                                       "NormalLinear / LocalReparamLinear, ReLU (folded, or nn.MomentReLU), reshaping modules, "
                                       "torch.nn.Identity and a closing nn.MomentSoftmax%s" % (type(m).__name__, (
@@ -666,11 +755,12 @@ class BayesianNetworkModule(Module):
                 y = self._forward(x, *args, **kwargs)
             except (TypeError, AttributeError) as e:
                 raise ops.BnnHipError("forward_moments: a module of this network cannot take a mean and a variance (%s); %s"
-                                      % (e, _MOMENTS_SUPPORTED)) from e
+                                      % (e, _moments_supported())) from e
         if torch.is_tensor(y):
             y = ops.Moments(y, None)
         if not isinstance(y, ops.Moments):
-            raise ops.BnnHipError("forward_moments: _forward returned %s; %s" % (type(y).__name__, _MOMENTS_SUPPORTED))
+            raise ops.BnnHipError("forward_moments: _forward returned %s; %s" % (type(y).__name__, _moments_supported()))
+        _refuse_pending(y, "forward_moments")
         return y
 
     def sample_moments(self, mom, samples=None, sample0=0):

@@ -19,7 +19,7 @@ from ..utils import _single, _pair, _triple
 from .container import BayesianModule
 from .core import WeightNormal
 from .dense import (_NormalSampling, _init_normal_posterior, _mc_dropout_plan, _mc_dropout_key, _flipout_plan, _flipout_mc_key,
-                    _lrt_noise_plan)
+                    _lrt_noise_plan, _mc_dropout_forward_moments)
 
 
 class BayesianConvNd(BayesianModule):
@@ -357,6 +357,12 @@ class FlipOutNormalConvNd(NormalConvNd):
 
     def forward(self, x, sample=True):
         # conv.py:182-196 (1d), 213-227 (2d), 244-258 (3d)
+        if _mc.moments_current() is not None:
+            # a moment pass (nn.moment_estimator_layers, K22): the moments of the layer's weight posterior N(mu, sigma^2), the
+            # distribution KLDivergence regularises -- bit for bit NormalConvNd's pass, no bias.  (The reference's conv sign
+            # sampler shares one sign per input channel across the kernel taps, so its own marginal variance is
+            # sum_c (sum_tap x sigma)^2 rather than sum x^2 sigma^2: it differs from the posterior's.)
+            return _conv_forward_moments(self, x)
         plan = _flipout_plan(self, x)
         if plan is not None:
             return self._forward_mc(x, sample, *plan)
@@ -480,6 +486,17 @@ def _mcdropout(name, conv_cls):
             self.bias = self.conv.bias
 
         def forward(self, x, sample=True):
+            if _mc.moments_current() is not None:                       # a moment pass (K22): moments in, moments out, no mask
+                c = self.conv
+                if c.padding_mode != 'zeros' or isinstance(c.padding, str):
+                    raise ops.BnnHipError("%s: a moment pass takes zero padding given as numbers, got padding=%r, padding_mode=%r"
+                                          % (type(self).__name__, c.padding, c.padding_mode))
+                geo = (c.stride, c.padding, c.dilation, c.groups)
+                return _mc_dropout_forward_moments(
+                    self, x, sample, c,
+                    lambda mom, track: ops.moments_conv_affine(mom, c.weight, c.bias, *geo, compute=_settings.get_compute(),
+                                                               track=track),
+                    lambda mom, track: ops.moments_conv_affine_f64(mom, c.weight, c.bias, *geo, track=track))
             plan = _mc_dropout_plan(self, x, sample)
             if plan is None:
                 return torch.nn.functional.dropout(self.conv(x), self.drop_prob, sample, False)

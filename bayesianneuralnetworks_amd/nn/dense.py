@@ -454,6 +454,15 @@ class FlipoutNormalLinear(NormalLinear):
         return (self.R, self.S)
 
     def forward(self, x, sample=True):
+        ctx = _mc.moments_current()
+        if ctx is not None:
+            # a moment pass (nn.moment_estimator_layers, K22): under the layer's own sign sampler an output's marginal mean and
+            # variance are NormalLinear's on the same parameters (E[S_k S_k'] = 0 removes the cross terms); no bias.  The
+            # covariance between outputs is not NormalLinear's (the signs are shared), so this layer is no covariance head.
+            out = self._forward_moments(x)
+            if ctx.covariance:
+                out._head = None
+            return out
         plan = _flipout_plan(self, x)
         if plan is not None:
             return self._forward_mc(x, sample, *plan)
@@ -672,6 +681,51 @@ def _mc_dropout_key(layer, ctx):
     return key
 
 
+MOMENT_ESTIMATOR_LAYERS = ("MCDropoutLinear", "MCDropoutConv1d", "MCDropoutConv2d", "MCDropoutConv3d", "FlipoutNormalLinear",
+                           "FlipOutNormalConv1d", "FlipOutNormalConv2d", "FlipOutNormalConv3d")     # nn.moment_estimator_layers (K22)
+
+
+def _mc_dropout_forward_moments(layer, x, sample, plain, contract, contract_f64):
+    """An MC-dropout layer inside a moment pass (_mc.MomentContext, nn.moment_estimator_layers; K22): x a tensor (a deterministic
+    input) or an ops.Moments -> the ops.Moments of the layer's output.  The contraction is deterministic: `contract` on the
+    device (ops.moments_affine / moments_conv_affine), `contract_f64` on the CPU, the layer's own `plain` module on a
+    deterministic device input.  Then the mask: ONE ops.moments_dropout launch that pushes it through the activation
+    nn.moment_activations found behind the layer (layer._moment_act; the twin then passes the result through; none: the
+    identity, and an activation twin that meets such moments raises) -- exact for Gaussian pre-activations, where moment-matching the mask in front of a ReLU / ELU is not.  Directly
+    in front of an nn.MomentSoftmax (softmax(0) != 0: nothing to fold into) the PRE-dropout moments go on with the mask pending,
+    and the softmax hands them to the predictive_* tails with dropout = p.  sample=False applies no dropout, as elsewhere.
+    Nothing is drawn and no key is recorded."""
+    mom = x if isinstance(x, ops.Moments) else ops.Moments(x, None)
+    name = type(layer).__name__
+    if not torch.is_tensor(mom.mean):
+        raise TypeError("%s takes a tensor or ops.Moments in a moment pass, got %s" % (name, type(x).__name__))
+    ops._refuse_link(mom, name)
+    ops.check_drop_prob(layer.drop_prob)
+    p = float(layer.drop_prob)
+    ctx = _mc.moments_current()
+    track = ctx.track
+    cuda = mom.mean.is_cuda
+    if not cuda:
+        pre = contract_f64(mom, track)
+    elif mom.var is None:
+        pre = ops.Moments(plain(mom.mean) if ops._tracking(track) else plain(mom.mean).detach(), None)
+    else:
+        pre = contract(mom, track)
+    if ctx.covariance:
+        ctx.last_dense = (name, pre.shape[-1] if pre.dim() else 0)
+    if not sample:
+        return pre
+    act = layer.__dict__.get("_moment_act")
+    if act == 'softmax':
+        pre._pending = p
+        return pre
+    out = ops.moments_dropout(pre, p, act, track) if cuda else ops.moments_dropout_f64(pre, p, act, track)
+    # what the mask was pushed through: the twin behind passes a matching spec and refuses every other one -- 'identity' among
+    # them, so that a hand-placed nn.MomentReLU / MomentELU the layer was never told about cannot moment-match the masked output
+    out._act = 'identity' if act is None else act
+    return out
+
+
 class MCDropoutLinear(BayesianModule):
     """dense.py:165-179: dropout stays active while `sample` is true.
 
@@ -698,6 +752,12 @@ class MCDropoutLinear(BayesianModule):
         return self._w_bf16[1]
 
     def forward(self, x, sample=True):
+        if _mc.moments_current() is not None:                           # a moment pass (K22): moments in, moments out, no mask
+            w, b = self.linear.weight, self.linear.bias
+            return _mc_dropout_forward_moments(
+                self, x, sample, self.linear,
+                lambda mom, track: ops.moments_affine(mom, w, b, compute=_settings.get_compute(), track=track),
+                lambda mom, track: ops.moments_affine_f64(mom, w, b, track))
         plan = _mc_dropout_plan(self, x, sample)
         if plan is None:
             return torch.nn.functional.dropout(self.linear(x), self.drop_prob, sample, False)

@@ -944,26 +944,40 @@ class Moments:
     (nn.MomentSoftmax): the predictive_* tails apply it to the sampled logits, and no layer takes such moments.  cov: None, or
     the (*rows, N, N) covariance of the N outputs of a row (K21: predictive_moments(covariance=True) at a dense head; its diagonal
     is var).  Nothing propagates a covariance: every reshape, layer and activation hands on moments without one; only
-    nn.MomentSoftmax keeps it, and moments_sample draws correlated outputs from it."""
-    # _act: the activation the producing conv launch fused (the twin behind it passes); _head: a dense layer's HeadOperands while
-    # a covariance pass runs (dropped and kept as cov is)
-    __slots__ = ("mean", "var", "link", "_act", "cov", "_head")
+    nn.MomentSoftmax keeps it, and moments_sample draws correlated outputs from it.  dropout: None, or the p of an MC-dropout mask
+    that is still to be applied to SAMPLES of these moments (K22: an MC-dropout head in front of a softmax, whose mask cannot be
+    folded into the moments because softmax(0) != 0); the moments are then the pre-dropout ones, and it is only ever set together
+    with link='softmax'.  Reshapes keep it; the predictive_* tails mask the drawn logits."""
+    # _act: the activation the producing launch applied (a conv launch's epilogue, or an MC-dropout layer's moments_dropout; the
+    # twin behind it passes; 'identity': an MC-dropout layer's mask with no activation, which the activation twins refuse); _head: a dense layer's HeadOperands while a covariance pass runs (dropped and kept as cov is);
+    # _pending: the p of an MC-dropout layer's mask on its way to the nn.MomentSoftmax directly behind it
+    __slots__ = ("mean", "var", "link", "_act", "cov", "_head", "dropout", "_pending")
 
-    def __init__(self, mean, var=None, link=None, cov=None):
+    def __init__(self, mean, var=None, link=None, cov=None, dropout=None):
         if var is not None and var.shape != mean.shape:
             raise ValueError("Moments: mean %s and var %s differ in shape" % (tuple(mean.shape), tuple(var.shape)))
         if link not in (None, 'softmax'):
             raise ValueError("Moments: link must be None or 'softmax', got %r" % (link,))
         if cov is not None and (mean.dim() < 1 or tuple(cov.shape) != tuple(mean.shape) + (mean.shape[-1],)):
             raise ValueError("Moments: cov %s is not mean's shape %s with its last axis repeated" % (tuple(cov.shape), tuple(mean.shape)))
+        if dropout is not None:
+            if link != 'softmax':
+                raise ValueError("Moments: dropout is the mask of an MC-dropout head in front of a softmax: it needs link='softmax'")
+            check_drop_prob(dropout)
         self.mean, self.var, self.link, self._act, self.cov, self._head = mean, var, link, None, cov, None
+        self.dropout, self._pending = dropout, None
 
     def __repr__(self):
-        return "Moments(mean=%r, var=%r%s%s)" % (self.mean, self.var, "" if self.link is None else ", link=%r" % self.link,
-                                                 "" if self.cov is None else ", cov=%r" % (self.cov,))
+        return "Moments(mean=%r, var=%r%s%s%s)" % (self.mean, self.var, "" if self.link is None else ", link=%r" % self.link,
+                                                   "" if self.cov is None else ", cov=%r" % (self.cov,),
+                                                   "" if self.dropout is None else ", dropout=%r" % (self.dropout,))
 
     def _both(self, fn):
-        return Moments(fn(self.mean), None if self.var is None else fn(self.var), self.link)
+        out = Moments(fn(self.mean), None if self.var is None else fn(self.var), self.link, dropout=self.dropout)
+        out._pending = self._pending
+        if self._act == 'identity':                  # (K22) a reshape does not make a masked output Gaussian
+            out._act = self._act
+        return out
 
     @property
     def shape(self):
@@ -1306,6 +1320,10 @@ def _refuse_link(mom, who):
     if mom.link is not None:
         raise BnnHipError("%s: the input carries link=%r: nn.MomentSoftmax must end the network (nothing propagates moments "
                           "through a softmax)" % (who, mom.link))
+    if mom._pending is not None:
+        raise BnnHipError("%s: the input carries the pending mask (dropout=%r) of an MC-dropout layer that nn.moment_activations "
+                          "found directly in front of an nn.MomentSoftmax, and this module is not that softmax: call "
+                          "nn.moment_activations again after changing a Sequential" % (who, mom._pending))
 
 
 def _moment_activation(activation, who):
@@ -1678,6 +1696,235 @@ def moments_convNd_f64(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, g
     if act == 'relu':
         return moments_relu_f64(out, track)
     return moments_elu_f64(out, alpha, track) if act == 'elu' else out
+
+
+# --------------------------------------------------------------------------- K22: MC dropout (and deterministic convs) in a moment pass
+_ACT_FLAGS = {None: 0, 'relu': _lib.FLAG_RELU, 'elu': _lib.FLAG_ELU}
+
+
+class _MomentsDropout(torch.autograd.Function):
+    """bnn_moments_dropout out of place with bnn_moments_dropout_backward behind it; m fp32, contiguous; v the same or None (a
+    deterministic input: no gradient of a variance)."""
+
+    @staticmethod
+    def forward(ctx, m, v, p, flag, alpha):
+        om, ov = torch.empty_like(m), torch.empty_like(m)
+        check(_lib.load().bnn_moments_dropout(ptr(m), ptr(v), ptr(om), ptr(ov), m.numel(), p, flag, alpha, stream_ptr(m.device)),
+              "bnn_moments_dropout")
+        ctx.save_for_backward(m, v)
+        ctx.p, ctx.flag, ctx.alpha = p, flag, alpha
+        return om, ov
+
+    @staticmethod
+    def backward(ctx, g_om, g_ov):
+        m, v = ctx.saved_tensors
+        g_om, g_ov = g_om.contiguous(), g_ov.contiguous()
+        g_m = torch.empty_like(m)
+        g_v = None if v is None else torch.empty_like(v)
+        check(_lib.load().bnn_moments_dropout_backward(ptr(m), ptr(v), ptr(g_om), ptr(g_ov), ptr(g_m), ptr(g_v), m.numel(), ctx.p,
+                                                       ctx.flag, ctx.alpha, stream_ptr(m.device)), "bnn_moments_dropout_backward")
+        return g_m, g_v, None, None, None
+
+
+def moments_dropout(mom, p, activation=None, track=False):
+    """An MC-dropout mask behind Gaussian activations, pushed through the activation that follows in ONE step
+    (bnn_moments_dropout) -> Moments.  For z ~ N(m, v), an independent mask b ~ Bernoulli(q), q = 1 - p, and an activation f with
+    f(0) = 0 (activation: None, 'relu' or ('elu', alpha)) the layer hands on f(b z / q) = b f(z / q); with (M, V) the moments of f at
+    N(m / q, v / q^2) (moments_relu / moments_elu there):
+
+        mean' = q M,    var' = q V + q p M^2
+
+    exact for a Gaussian z and for a deterministic one: a dropped unit is a spike at zero, not a Gaussian, so the mask is NOT
+    moment-matched in front of the activation.  A deterministic input (var None) comes out with the variance q p f(m / q)^2.
+    p == 0 is the activation alone (its bits), p == 1 gives zeros.  track=True with grad mode on: attached to the graph, the
+    backward is bnn_moments_dropout_backward."""
+    who = "moments_dropout"
+    mom = _as_moments(mom, who)
+    _refuse_link(mom, who)
+    act, alpha = _moment_activation(activation, who)
+    check_drop_prob(p)
+    p = float(p)
+    tracked = _tracking(track)
+    keep = (lambda t: t) if tracked else (lambda t: t.detach())
+    m = keep(mom.mean).contiguous()
+    v = None if mom.var is None else keep(mom.var).contiguous()
+    require_cuda_f32(m, "mean")
+    if v is not None:
+        require_cuda_f32(v, "var")
+    if tracked:
+        return Moments(*_MomentsDropout.apply(m, v, p, _ACT_FLAGS[act], alpha))
+    om, ov = torch.empty_like(m), torch.empty_like(m)
+    check(_lib.load().bnn_moments_dropout(ptr(m), ptr(v), ptr(om), ptr(ov), m.numel(), p, _ACT_FLAGS[act], alpha, stream_ptr(m.device)),
+          "bnn_moments_dropout")
+    return Moments(om, ov)
+
+
+def _act_f64(mom, act, alpha, track):
+    if act == 'relu':
+        return moments_relu_f64(mom, track)
+    return moments_elu_f64(mom, alpha, track) if act == 'elu' else mom
+
+
+def moments_dropout_f64(mom, p, activation=None, track=False):
+    """moments_dropout in float64 torch: moments_relu_f64 / moments_elu_f64 at (m / q, v / q^2), then mean' = q M,
+    var' = q V + q p M^2 -> Moments of float64 tensors; the result always carries a variance.  track=True: not detached (plain torch
+    autograd through the activation's closed form, with its conventions at v == 0)."""
+    who = "moments_dropout_f64"
+    mom = _as_moments(mom, who)
+    _refuse_link(mom, who)
+    act, alpha = _moment_activation(activation, who)
+    check_drop_prob(p)
+    p = float(p)
+    q = 1.0 - p
+    f64 = _f64(track)
+    m = f64(mom.mean)
+    v = None if mom.var is None else f64(mom.var)
+    never = torch.zeros_like(m, dtype=torch.bool)            # torch.where(never, t, 0): zeros that stay in t's graph, zero gradients
+    if p == 0.0:
+        out = _act_f64(Moments(m, v), act, alpha, track)
+        return Moments(out.mean, torch.where(never, out.mean, torch.zeros_like(m)) if out.var is None else out.var)
+    if p == 1.0:
+        return Moments(torch.where(never, m, torch.zeros_like(m)), torch.where(never, m if v is None else v, torch.zeros_like(m)))
+    inner = _act_f64(Moments(m / q, None if v is None else v / (q * q)), act, alpha, track)
+    M = inner.mean
+    var = q * p * M * M
+    return Moments(q * M, var if inner.var is None else q * inner.var + var)
+
+
+def moments_dropout_backward_f64(mom, g_mean, g_var, p, activation=None):
+    """The backward of moments_dropout in float64 torch, as a formula: (g_m, g_v) at the pre-dropout `mom` from the gradients of the
+    two outputs.  With M the activation's mean at (m / q, v / q^2):
+
+        gM = q g_mean + 2 q p M g_var,    gV = q g_var
+
+    through moments_relu_backward_f64 / moments_elu_backward_f64 there (the identity passes them) to (g_mi, g_vi);
+    g_m = g_mi / q, g_v = g_vi / q^2.  p == 1 gives zeros; a deterministic input (var None) gives (g_m, None)."""
+    who = "moments_dropout_backward_f64"
+    mom = _as_moments(mom, who)
+    act, alpha = _moment_activation(activation, who)
+    check_drop_prob(p)
+    p = float(p)
+    q = 1.0 - p
+    f64 = lambda t: t.detach().to(torch.float64)         # noqa: E731
+    m, g_mean, g_var = f64(mom.mean), f64(g_mean), f64(g_var)
+    v = None if mom.var is None else f64(mom.var)
+    if p == 1.0:
+        return torch.zeros_like(m), None if v is None else torch.zeros_like(m)
+    inner = Moments(m / q, None if v is None else v / (q * q))
+    M = _act_f64(inner, act, alpha, False).mean
+    gM, gV = q * g_mean + 2.0 * q * p * M * g_var, q * g_var
+    if act == 'relu':
+        g_mi, g_vi = moments_relu_backward_f64(inner, gM, gV)
+    elif act == 'elu':
+        g_mi, g_vi = moments_elu_backward_f64(inner, gM, gV, alpha)
+    else:
+        g_mi, g_vi = gM, gV
+    return g_mi / q, None if v is None else g_vi / (q * q)
+
+
+class _MomentsConvAffine(torch.autograd.Function):
+    """ops.moments_conv_affine on moments that carry a variance, with K19's backward launches behind it, as _MomentsAffine has
+    K18's: the input gradient with the zero sigma^2 plane, the weight gradient with a zero rho whose g_rho_w is discarded (the bias
+    sum rides along).  am, av (B, C, *spatial), w (O, C / groups, *kernel), b (O) or None, all fp32 and contiguous."""
+
+    @staticmethod
+    def forward(ctx, am, av, w, b, sh, out_shape, code):
+        dev = am.device
+        z_w = torch.zeros_like(w)
+        z_b = None if b is None else torch.zeros_like(b)
+        out_m = torch.empty(out_shape, dtype=torch.float32, device=dev)
+        out_v = torch.empty_like(out_m)
+        check(_lib.load().bnn_conv3d_moments_forward(ptr(am), ptr(av), ptr(w), ptr(z_w), ptr(b), ptr(z_b), ptr(out_m), ptr(out_v),
+                                                     ctypes.byref(sh), code, 0, 0.0, stream_ptr(dev)), "bnn_conv3d_moments_forward")
+        ctx.save_for_backward(am, av, w)
+        ctx.code, ctx.sh, ctx.bias = code, sh, b is not None
+        return out_m, out_v
+
+    @staticmethod
+    def backward(ctx, g_m, g_v):
+        am, av, w = ctx.saved_tensors
+        code, sh = ctx.code, ctx.sh
+        dev = am.device
+        lib, st = _lib.load(), stream_ptr(dev)
+        g_m, g_v = g_m.contiguous(), g_v.contiguous()
+        g_am = g_av = g_w = g_b = None
+        zero = torch.zeros_like(w)                  # sigma^2 = 0 for the input gradient, rho = 0 for the weight gradient's chain
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            g_am, g_av = torch.empty_like(am), torch.empty_like(av)
+            check(lib.bnn_conv3d_moments_backward_input(ptr(g_m), ptr(g_v), ptr(w), ptr(zero), ptr(am), ptr(g_am), ptr(g_av),
+                                                        ctypes.byref(sh), code, st), "bnn_conv3d_moments_backward_input")
+        need_b = ctx.bias and ctx.needs_input_grad[3]
+        if ctx.needs_input_grad[2] or need_b:
+            g_w, scrap = torch.empty_like(w), torch.empty_like(w)
+            zb = sb = None
+            if need_b:
+                g_b = torch.empty(w.shape[0], dtype=torch.float32, device=dev)
+                zb, sb = torch.zeros_like(g_b), torch.empty_like(g_b)
+            nb = lib.bnn_conv3d_moments_wgrad_workspace(ctypes.byref(sh))
+            ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)
+            check(lib.bnn_conv3d_moments_backward_weight(ptr(am), ptr(av), ptr(g_m), ptr(g_v), ptr(w), ptr(zero), ptr(g_w), ptr(scrap),
+                                                         ptr(zb), ptr(g_b), ptr(sb), ctypes.byref(sh), code, ptr(ws), nb, st),
+                  "bnn_conv3d_moments_backward_weight")
+        return g_am, g_av, g_w, g_b, None, None, None
+
+
+def _plain_conv(nd):
+    return (torch.nn.functional.conv1d, torch.nn.functional.conv2d, torch.nn.functional.conv3d)[nd - 1]
+
+
+def moments_conv_affine(a, w, b, stride, padding, dilation, groups=1, compute="f32", track=False):
+    """A DETERMINISTIC convolution (the torch conv inside an MCDropoutConv layer) in a moment pass: m = convNd(a_m, w) + b,
+    v = convNd(a_v, w^2) -- exact for independent inputs.  It is bnn_conv3d_moments_forward with sigma_w^2 = 0, exactly as
+    moments_affine is bnn_moments_forward with it, so K17's tile, bounds and both compute modes apply.  a: a tensor or a Moments
+    (B, C, *spatial); w (O, C / groups, *kernel); b (O) or None -> Moments, fp32; a deterministic input stays one (var None, the
+    torch convolution).  track=False: detached.  track=True with grad mode on: attached to `a`, w and b; the backward is K19's
+    launches (a zero sigma^2 plane for the input gradient, a zero rho and a discarded g_rho for the weight gradient)."""
+    who = "moments_conv_affine"
+    mom = _as_moments(a, who)
+    _refuse_link(mom, who)
+    tracked = _tracking(track)
+    keep = (lambda t: t) if tracked else (lambda t: t.detach())
+    w = keep(w).contiguous()
+    b = None if b is None else keep(b).contiguous()
+    nd = w.dim() - 2
+    if nd not in (1, 2, 3) or mom.mean.dim() != nd + 2:
+        raise BnnHipError("%s: input must be (B, C, ...) with %d spatial axes for a weight of shape %s, got %s"
+                          % (who, nd, tuple(w.shape), tuple(mom.mean.shape)))
+    if mom.var is None:
+        return Moments(_plain_conv(nd)(keep(mom.mean), w, b, tuple(stride), tuple(padding), tuple(dilation), int(groups)), None)
+    code = _compute_code(compute)
+    am, av = keep(mom.mean).contiguous(), keep(mom.var).contiguous()
+    for t, n in ((am, "a.mean"), (av, "a.var"), (w, "weight")) + (((b, "bias"),) if b is not None else ()):
+        require_cuda_f32(t, n)
+    img, w5, st, pd, dl = _lrt_conv_views(am.shape, w.shape, stride, padding, dilation)
+    B = int(am.shape[0])
+    sh, out3 = _conv3d_shape((B,) + img, w5, st, pd, dl, groups)
+    out_shape = (B, sh.O) + out3[3 - nd:]
+    if tracked:
+        return Moments(*_MomentsConvAffine.apply(am, av, w, b, sh, out_shape, code))
+    dev = am.device
+    z_w = torch.zeros_like(w)
+    z_b = None if b is None else torch.zeros_like(b)
+    out_m = torch.empty(out_shape, dtype=torch.float32, device=dev)
+    out_v = torch.empty_like(out_m)
+    check(_lib.load().bnn_conv3d_moments_forward(ptr(am), ptr(av), ptr(w), ptr(z_w), ptr(b), ptr(z_b), ptr(out_m), ptr(out_v),
+                                                 ctypes.byref(sh), code, 0, 0.0, stream_ptr(dev)), "bnn_conv3d_moments_forward")
+    return Moments(out_m, out_v)
+
+
+def moments_conv_affine_f64(a, w, b, stride, padding, dilation, groups=1, track=False):
+    """moments_conv_affine in float64 torch.  track=True: not detached."""
+    who = "moments_conv_affine_f64"
+    mom = _as_moments(a, who)
+    _refuse_link(mom, who)
+    f64 = _f64(track)
+    nd = w.dim() - 2
+    if nd not in (1, 2, 3):
+        raise BnnHipError("%s: weight must be (O, C / groups, *kernel) with 1, 2 or 3 kernel axes, got %s" % (who, tuple(w.shape)))
+    geo = (tuple(stride), tuple(padding), tuple(dilation), int(groups))
+    w64 = f64(w)
+    m = _plain_conv(nd)(f64(mom.mean), w64, None if b is None else f64(b), *geo)
+    return Moments(m, None if mom.var is None else _plain_conv(nd)(f64(mom.var), w64 * w64, None, *geo))
 
 
 # --------------------------------------------------------------------------- K20: moments through pooling and eval-mode BatchNorm

@@ -1327,6 +1327,31 @@ int bnn_moments_head_cov(const float *a_v, int64_t lda, const float *E, const fl
 int bnn_moments_sample_cov(const float *m, const float *cov, float *y, int64_t rows, int64_t N, int nsamples, const bnn_rng_t *rng,
                            int flags, void *stream);
 
+/* ---- K22: MC dropout in a sampling-free pass, folded through the activation behind it (csrc/bnn_moments_dropout.hip,
+ * csrc/bnn_moments_act.hpp; ops.moments_dropout).  An MC-dropout layer hands on y = f(b z / q): z ~ N(m, v) its pre-dropout output,
+ * b ~ Bernoulli(q) an independent mask, q = 1 - p, f the activation behind it with f(0) = 0 (act: 0 = identity, BNN_FLAG_RELU,
+ * BNN_FLAG_ELU with alpha; alpha is not read otherwise).  Since f(b z / q) = b f(z / q), with (M, V) the moments of f at the Gaussian
+ * N(m / q, v / q^2) -- bnn_moments_relu's / bnn_moments_elu's functions there, the identity's are the input --
+ *     mean' = q M        var' = q V + q p M^2
+ * exact for a Gaussian z and for a deterministic one (v == 0; a NaN v takes the same limit branches): a dropped unit is a spike at
+ * zero, not a Gaussian, and the activation is applied to the spike.  Identity and ReLU in fp32; the ELU scales its input and
+ * recombines its results in fp64 around bnn_moments_elu's fp64 evaluation.  p == 0 gives the activation's own bits, p == 1 gives
+ * (0, 0) and divides nothing by q.  v NULL: a deterministic input, every variance zero (out_v is still written: q p f(m / q)^2).
+ * n elements, one element per load and store (every operand may lie on its element), in place allowed (out_m == m, out_v == v).
+ * No scratch, no atomics: identical calls give identical bits.  Graph-capturable; errors are returned before anything is launched:
+ * BNN_E_NULL, BNN_E_RANGE (n < 0; p outside [0, 1] or NaN; an unknown act; alpha negative or not finite with BNN_FLAG_ELU),
+ * BNN_E_ALIGN. */
+int bnn_moments_dropout(const float *m, const float *v, float *out_m, float *out_v, int64_t n, float p, int act, float alpha,
+                        void *stream);
+/* Backward of bnn_moments_dropout at the pre-dropout (m, v): with M as above (evaluated again),
+ *     gM = q g_out_m + 2 q p M g_out_v        gV = q g_out_v
+ * go through the activation's backward at (m / q, v / q^2) (bnn_moments_relu_backward's / bnn_moments_elu_backward's functions,
+ * their clamp and v == 0 conventions; the identity passes them) to (g_mi, g_vi), and g_m = g_mi / q, g_v = g_vi / q^2.  p == 0: the
+ * activation's backward, its bits; p == 1: zeros.  v NULL: a deterministic input, and g_v may then be NULL (it is written when
+ * given).  g_m / g_v may be g_out_m / g_out_v.  Errors: as bnn_moments_dropout. */
+int bnn_moments_dropout_backward(const float *m, const float *v, const float *g_out_m, const float *g_out_v, float *g_m, float *g_v,
+                                 int64_t n, float p, int act, float alpha, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
