@@ -31,4 +31,7 @@ def kl_grad64(mu, rho, prior, n_tensors, n_batches, upstream):
     w = np.where(rho > 20.0, 0.0, e / ((1.0 + e) * np.log1p(e)))
     w2 = np.where(rho > 20.0, 0.0, 1.0 - dsoftplus64(rc))
     c = 28.0 + 2.0 * np.abs(rho) * (w + w2)
-    return g_mu, g_rho, 8.0 * U * np.abs(g_mu), c * U * abs(sc) * (sg / ps ** 2 + 1.0 / sg) * ds
+    # dsoftplus below 2^-126 (rho < -87.3) is flushed or loses bits in fp32 whatever computes it, and the factor in front of it
+    # (1 / sigma = 1e10 for a collapsed posterior) scales that loss back into the normal range: TINY times the factor, there only
+    mag = abs(sc) * (sg / ps ** 2 + 1.0 / sg)
+    return g_mu, g_rho, 8.0 * U * np.abs(g_mu), c * U * mag * ds + np.where(ds < TINY, mag * TINY, 0.0)

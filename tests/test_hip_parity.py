@@ -1398,9 +1398,21 @@ def test_prune_normal_on_device(env):
         frac = (L.weight.scale == -30).float().mean().item()
         assert abs(frac - 0.5) < 0.02
         assert bool(((L.weight.scale == -30) == (L.weight.mean == 0)).all())
-    y = net(torch.randn(7, 12, device=dev))
-    assert len(y) == 2 and torch.isfinite(y[0]).all()
-    assert torch.isfinite(KLDivergence()(net))
+    # the pruned model's keyed forward is the float64 forward on the same eps, and its KL float64 torch's (1e-6 relative):
+    # sigma(-30) = 1e-10 + 9.4e-14 in half of every tensor, where `finite` would pass a sigma of 0 or of 1e-10 alike
+    import posterior_range as tpr
+    net.mc_batched = True
+    x = torch.randn(7, 12, generator=gen)
+    y = net(x.to(dev))
+    assert len(y) == 2
+    layers = [net.layers[0], net.layers[2]]
+    p64 = [[t.detach().double().cpu() for t in (L.weight.mean, L.weight.scale, L.bias.mean, L.bias.scale)] for L in layers]
+    want = tpr.ref_forward("normal_f32", net, x.double(), p64, 2, dev)
+    assert_close_scaled(N(torch.stack(y)), want.numpy(), what="pruned net forward")
+    kl64 = sum(torch.distributions.kl_divergence(torch.distributions.Normal(mu, tpr.sg_torch(rho)), torch.distributions.Normal(*tpr.PRIOR)).mean()
+               for q in p64 for mu, rho in (q[:2], q[2:])) / 4
+    kl = KLDivergence()(net).item()
+    assert abs(kl - kl64.item()) <= 1e-6 * abs(kl64.item()), (kl, kl64.item())
     net2 = Net().to(dev)
     net2.load_state_dict(net.state_dict())
     assert torch.equal(net2.layers[0].weight.scale, net.layers[0].weight.scale)

@@ -227,11 +227,11 @@ def test_mvn_draw_is_positional(which):
 
 
 # ===================================================================================================== ops.linear_sampled
-def linear_plan(M, K, N, mode, shared, x_bf16, y_bf16, relu, al):
+def linear_plan(M, K, N, mode, shared, x_bf16, y_bf16, relu, al, S=S):
     """What ops._SampledLinear runs for a call whose input requires a gradient, from its own dispatch conditions and the host
     checks of the entries it calls (csrc/bnn_gemm.hip linear_common / bnn_linear_backward_input_sampled, csrc/bnn_linear_bwd.hip
     bnn_linear_backward_narrow_sampled) -> (bwdref spec, forward launches, backward launches).  al: which of 'mu', 'rho', 'x',
-    'gy' start on 16 bytes ('x8': x on 8)."""
+    'gy' start on 16 bytes ('x8': x on 8).  S: the number of MC samples (this module's, unless the caller runs another)."""
     bf = mode == "bf16"
     dense = bf and K % 8 == 0 and al["mu"]
     if dense:

@@ -377,9 +377,10 @@ GPU_CFGS = {
 }
 
 
-def device_step(cfg, seed):
+def device_step(cfg, seed, prepare=None, kl_c=KL_C):
     """One forward + backward on the device with every layer's operands captured -> ([op per layer], [got per layer], launches of
-    the backward)."""
+    the backward).  prepare(net): applied to the network on the device before the step (tests/test_posterior_range.py prunes it);
+    kl_c: the KL term's weight in the loss (0: the likelihood's gradient alone)."""
     import bayesianneuralnetworks_amd as bnn
     from bayesianneuralnetworks_amd import ops
     from bayesianneuralnetworks_amd.nn import NormalLinear, KLDivergence, BayesianNetworkModule, fuse_activations, fuse_kl_gradient
@@ -423,6 +424,8 @@ def device_step(cfg, seed):
     net = net.to(dev)
     seeded.pin_streams(net, 4000 + 16 * seed)
     net.mc_batched = True
+    if prepare is not None:
+        prepare(net)
     layers = [m for m in net.layers if isinstance(m, NormalLinear)]
     for m in layers:
         m.compute = mode
@@ -444,7 +447,7 @@ def device_step(cfg, seed):
     fuse_kl_gradient(True)
     try:
         ys = net.forward_stacked(x, S)
-        loss = (ys * gy0).sum() + KL_C * KLDivergence(number_of_batches=N_BATCHES)(net)
+        loss = (ys * gy0).sum() + kl_c * KLDivergence(number_of_batches=N_BATCHES)(net)
         n0 = lib.bnn_launch_count()
         loss.backward()
         torch.cuda.synchronize()
@@ -454,21 +457,21 @@ def device_step(cfg, seed):
         for h in handles:
             h.remove()
     try:
-        return _collect(cfg, plan, layers, cap, launches, dev)
+        return _collect(cfg, plan, layers, cap, launches, dev, kl_c)
     finally:                                                # (the draws above are re-created from the keys before the state goes back)
         default_generator._seed, default_generator._torch_seed, default_generator.epoch_host = saved_gen
         for cell, was in saved_cells:
             cell.copy_(was)
 
 
-def _collect(cfg, plan, layers, cap, launches, dev):
+def _collect(cfg, plan, layers, cap, launches, dev, kl_c=KL_C):
     """The captured operands and the gradients of device_step's backward, on the CPU."""
     from bayesianneuralnetworks_amd import ops
     dims, B, S = cfg["dims"], cfg["B"], cfg["S"]
     L = len(dims) - 1
     assert not ops._tls.kl_pending, "a parked KL gradient was left behind"
     _lib.check_device(dev)
-    kl = dict(up=float(np.float32(KL_C)), T=2 * L, n_batches=float(N_BATCHES), prior_w=PRIOR, prior_b=PRIOR)
+    kl = dict(up=float(np.float32(kl_c)), T=2 * L, n_batches=float(N_BATCHES), prior_w=PRIOR, prior_b=PRIOR)
     ops_, gots = [], []
     for i, (m, p) in enumerate(zip(layers, plan)):
         K, N = dims[i], dims[i + 1]

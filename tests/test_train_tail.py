@@ -71,6 +71,7 @@ import numpy as np
 import pytest
 import torch
 
+import posterior_range
 from bayesianneuralnetworks_amd import _lib, ops, optim
 from klref import softplus64, dsoftplus64, kl_grad64              # noqa: F401  (tests/golden, shared with test_train_step.py)
 
@@ -91,6 +92,7 @@ ADAM_GSCALE = [1.0, 1e-6]
 ADAM_N = 3001
 ADAM_CASES = [(hp, t, s) for hp in ADAM_HP for t in ADAM_T for s in ADAM_GSCALE]
 KL_CORNERS = [-30.0, -1e-3, 0.0, 19.5, 20.0, 20.5]
+KL_CORNERS += [v for v in posterior_range.FIXED if v not in KL_CORNERS]      # every fixed value of the posterior-range grid
 KL_PRIORS = [(0.0, 0.1), (0.3, 1.0)]
 MUTANTS = ["no_bc2", "no_bc1", "t_plus_1", "eps_before_bc2", "eps_in_sqrt", "adamw", "b2_for_m"]
 
