@@ -110,6 +110,11 @@ class MvnKlTensor(ctypes.Structure):
                 ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("prior_mu", ctypes.c_float), ("prior_sigma", ctypes.c_float)]
 
 
+class VdTensor(ctypes.Structure):
+    """bnn_vd_tensor_t"""
+    _fields_ = [("theta", ctypes.c_void_p), ("log_sigma2", ctypes.c_void_p), ("n", ctypes.c_int64)]
+
+
 _p = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
@@ -258,6 +263,11 @@ SIGNATURES = {
     "bnn_moments_sample_cov": (_int, [_p, _p, _p, _i64, _i64, _int, _rngp, _int, _p]),
     "bnn_moments_dropout": (_int, [_p, _p, _p, _p, _i64, ctypes.c_float, _int, ctypes.c_float, _p]),
     "bnn_moments_dropout_backward": (_int, [_p, _p, _p, _p, _p, _p, _i64, ctypes.c_float, _int, ctypes.c_float, _p]),
+    "bnn_vd_prepare": (_int, [_p, _p, _i64, _p, _p, _i64, ctypes.c_float, _p, _p, _p, _p]),
+    "bnn_vd_backward_weight": (_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
+    "bnn_vd_kl_workspace_bytes": (_i64, [ctypes.POINTER(VdTensor), _int]),
+    "bnn_vd_kl_forward": (_int, [ctypes.POINTER(VdTensor), _int, _p, _p, _p]),
+    "bnn_vd_kl_backward": (_int, [ctypes.POINTER(VdTensor), _int, _p, ctypes.POINTER(_p), ctypes.POINTER(_p), _int, _p]),
 }
 
 _lib = None

@@ -4,9 +4,10 @@ from .container import (MomentMaxPool1d, MomentMaxPool2d, MomentMaxPool3d, Momen
                         MomentAdaptiveAvgPool1d, MomentAdaptiveAvgPool2d, MomentAdaptiveAvgPool3d,
                         MomentBatchNorm1d, MomentBatchNorm2d, MomentBatchNorm3d)   # (K20; not in __all__ either)
 from .core import WeightNormal, WeightMultivariateNormal
+from .core import WeightVariationalDropout   # (not in __all__: that list is the reference's)
 from .dense import (BayesianLinear, NormalLinear, MultivariateNormalLinear, FlipoutNormalLinear,
                     NormalInverseGaussianLinear, MCDropoutLinear,
-                    LocalReparamLinear)   # (not in __all__: that list is the reference's)
+                    LocalReparamLinear, VariationalDropoutLinear)   # (not in __all__: that list is the reference's)
 from .conv import (BayesianConvNd, NormalConvNd, NormalConv1d, NormalConv2d, NormalConv3d,
                    FlipOutNormalConvNd, FlipOutNormalConv1d, FlipOutNormalConv2d, FlipOutNormalConv3d,
                    MCDropoutConvNd, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d,

@@ -40,7 +40,7 @@ class _Single:
         return traverse(self.layer, fn, *args, **kwargs)
 
 
-_MOMENTS_SUPPORTED = ("moment propagation supports NormalLinear / LocalReparamLinear, ReLU folded into them by "
+_MOMENTS_SUPPORTED = ("moment propagation supports NormalLinear / LocalReparamLinear / VariationalDropoutLinear (the last for inference only), ReLU folded into them by "
                       "nn.fuse_activations, MultivariateNormalLinear (inference only), NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d, the activations "
                       "nn.moment_activations rewrites (ReLU, ELU, a torch.nn.Linear behind a Bayesian layer, and a Softmax over the last "
                       "axis that ends the network; behind a Bayesian layer also MaxPool / AvgPool / AdaptiveAvgPool 1d / 2d / 3d and an "
@@ -390,6 +390,17 @@ class BayesianNetworkModule(Module):
         from .loss import KLDivergence
         return KLDivergence(number_of_batches)(self)
 
+    def sparsity(self):
+        """(dropped, total) over every VariationalDropoutLinear of the network: the weights with log_alpha above the layer's
+        threshold (3.0 where it is None), and all of them -- layer.sparsity()'s count, summed."""
+        from .dense import VariationalDropoutLinear
+        dropped = total = 0
+        for m in self.modules():
+            if isinstance(m, VariationalDropoutLinear):
+                d, t = m._dropped()
+                dropped, total = dropped + d, total + t
+        return dropped, total
+
     def forward(self, x, samples=None, *args, **kwargs):
         if samples is None:
             samples = self.samples
@@ -617,9 +628,9 @@ class BayesianNetworkModule(Module):
         Not covered: the backward of K21, covariance between hidden activations or conv positions, non-default priors, the
         evidential head."""
         from .. import ops
-        from .dense import NormalLinear, LocalReparamLinear, MultivariateNormalLinear
+        from .dense import NormalLinear, LocalReparamLinear, MultivariateNormalLinear, VariationalDropoutLinear
         from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
-        admitted = (NormalLinear, LocalReparamLinear, MultivariateNormalLinear, NormalConv1d, NormalConv2d, NormalConv3d,
+        admitted = (NormalLinear, LocalReparamLinear, VariationalDropoutLinear, MultivariateNormalLinear, NormalConv1d, NormalConv2d, NormalConv3d,
                     LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d) + _estimator_layers()
         for m in self.modules():
             if isinstance(m, BayesianModule) and type(m) not in admitted:

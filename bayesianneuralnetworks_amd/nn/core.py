@@ -111,6 +111,51 @@ class WeightNormal(Module):
         return self
 
 
+class WeightVariationalDropout(Module):
+    """The posterior of sparse variational dropout (Molchanov, Ashukha, Vetrov 2017; not a reference class): N(mean, sigma^2) per
+    weight in the additive parametrisation -- Parameters `mean` (theta) and `log_sigma2` = ln sigma^2 -- under a log-uniform
+    prior.  log_alpha = clamp(log_sigma2 - ln(mean^2), -8, 8) measures how much noise a weight carries relative to its size
+    (mean = 0: +8); training with KLDivergence drives it up for every weight the data does not need, and a weight with
+    log_alpha above a threshold (3: alpha > 20) can be dropped.  Nothing is drawn from it: VariationalDropoutLinear samples its
+    pre-activations (local reparameterization), so there is no .sampled."""
+
+    def __init__(self, *channels):
+        super().__init__()
+        self.mean = Parameter(torch.zeros(*channels))
+        self.log_sigma2 = Parameter(torch.full(tuple(channels), -10.0))
+
+    @property
+    def device(self):
+        return self.mean.device
+
+    @property
+    def requires_grad(self):
+        return self.mean.requires_grad
+
+    @property
+    def variance(self):
+        return torch.exp(self.log_sigma2)
+
+    @property
+    def stddev(self):
+        return torch.exp(0.5 * self.log_sigma2)
+
+    @property
+    def dist(self):
+        return Normal(self.mean, self.stddev)
+
+    @property
+    def log_alpha(self):
+        return ops.vd_log_alpha(self.mean, self.log_sigma2)
+
+    @property
+    def shape(self):
+        return self.size()
+
+    def size(self, *dims):
+        return self.mean.size(*dims)
+
+
 class WeightMultivariateNormal(Module):
     """Per-row full-covariance posterior, core.py:48-92.
     Keeps the reference's quirks: uniform noise (core.py:91) and the element-wise sqrt of

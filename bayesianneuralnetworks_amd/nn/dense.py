@@ -391,6 +391,151 @@ class LocalReparamLinear(_NormalSampling, BayesianLinear):
         return y.reshape(S * per, *lead, N)
 
 
+class VariationalDropoutLinear(BayesianLinear):
+    """Sparse variational dropout (Molchanov, Ashukha, Vetrov 2017; not a reference name): a dense layer that learns which of its
+    weights to drop.  Every weight has the posterior N(theta, sigma^2) -- `weight` is a WeightVariationalDropout with Parameters
+    mean (theta) and log_sigma2 -- and a log-uniform prior; the pre-activation is sampled by local reparameterization,
+
+        m = x theta^T + mu_b,   v = x^2 exp(log_sigma2)^T + sigma_b^2,   y_s = m + sqrt(v + 1e-16) eps_s,   eps_s ~ N(0, 1)
+
+    and KLDivergence / .kl_divergence() add the log-uniform KL of the weight (ops.vd_kl; no prior argument: the prior is fixed)
+    beside the Gaussian KL of the bias against `bias_prior`.  Training drives log_alpha = log_sigma2 - ln(theta^2) up for every
+    weight the data does not need; prune.PruneLogAlpha, layer.threshold and layer.sparsity() then need only a threshold on it.
+    `bias` is None or a WeightNormal, as LocalReparamLinear's; state_dict keys weight.mean, weight.log_sigma2, bias.mean,
+    bias.scale.  Initialisation: the mean as NormalLinear's, log_sigma2 = -10.
+
+    Device input: bnn_vd_prepare + bnn_lrt_forward, both compute modes, bf16 activations in the bf16 mode; the backward is HIP
+    (bnn_lrt_backward_epilogue, bnn_lrt_backward_input, bnn_vd_backward_weight).  In a BayesianNetworkModule's MC-batched pass all S
+    samples run in ONE contraction launch; noise_key and sample=False mean what they mean on LocalReparamLinear (the LRT-noise
+    contract of include/bnn_hip.h).  CPU tensors: the expression above in torch with torch.randn_like.
+
+    threshold (an attribute, default None): with a float every path -- the sampling forward, the MC-batched pass, the moment
+    pass -- drops the weights with log_alpha > threshold (theta = 0 and variance 0).  The mask is for inference: a call that would
+    need a gradient of a posterior tensor while a threshold is set raises ops.BnnHipError.  sparsity() is the fraction of weights
+    with log_alpha > threshold (3.0 while threshold is None).
+
+    Inside BayesianNetworkModule.predictive_moments the layer is NormalLinear's moment layer on the variance plane
+    exp(log_sigma2) (bnn_moments_forward) and honours activation == 'relu'; a tracking pass (forward_moments) raises
+    ops.BnnHipError: there is no moment backward.  Out of scope: conv variants, nn.fuse_activations / fuse_head and the draw plan
+    (both select NormalLinear by exact type), the multiplicative parametrisation, distributed.forward_sharded's KL sharding."""
+
+    compute = None      # None -> module-wide default (nn.set_compute)
+    activation = None   # 'relu': honoured in a moment pass
+    out_dtype = None    # torch.bfloat16: emit a bf16 hidden activation (bf16 compute mode only)
+
+    def __init__(self, in_features, out_features, bias=True, bias_prior=Normal(0, .1), threshold=None):
+        BayesianModule.__init__(self, in_features, out_features, None, bias_prior)     # the weight's prior is the log-uniform one
+        from .core import WeightVariationalDropout
+        from .._rng import new_stream_id
+        self.weight = WeightVariationalDropout(out_features, in_features)
+        if bias:
+            self.bias = WeightNormal(out_features)
+        else:
+            self.register_parameter('bias', None)
+        self.threshold = threshold
+        self._noise_stream = new_stream_id()        # the layer's eps stream
+        self.noise_key = None                       # DrawKey of the last device call
+        self._noise_shape = None                    # (rows per sample, out_features) of that call
+        self._cpu_eps = None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        init.kaiming_uniform_(self.weight.mean, a=math.sqrt(5))
+        init.constant_(self.weight.log_sigma2, -10.0)
+        if self.bias is not None:
+            fan_in, _ = init._calculate_fan_in_and_fan_out(self.weight.mean)
+            bound = 1 / math.sqrt(fan_in)
+            init.uniform_(self.bias.mean, -bound, bound)
+            init.normal_(self.bias.scale, -2.0, 0.15)
+
+    def _compute_mode(self):
+        return self.compute or _settings.get_compute()
+
+    def _posterior(self):
+        b = self.bias is not None
+        return (self.weight.mean, self.weight.log_sigma2, self.bias.mean if b else None, self.bias.scale if b else None)
+
+    def _threshold(self):
+        return None if self.threshold is None else float(self.threshold)
+
+    def sparsity(self):
+        """The fraction of weights with log_alpha > threshold (3.0 while threshold is None)."""
+        dropped, total = self._dropped()
+        return dropped / total
+
+    def _dropped(self):
+        thr = 3.0 if self.threshold is None else float(self.threshold)
+        w = self.weight
+        if w.mean.is_cuda:
+            dropped = int(ops.vd_dropped(w.mean, w.log_sigma2, thr).item())
+        else:
+            with torch.no_grad():
+                dropped = int((ops.vd_log_alpha(w.mean.double(), w.log_sigma2.double()) > thr).sum().item())   # fp64, as the kernel
+        return dropped, w.mean.numel()
+
+    def _forward_moments(self, x):
+        mom = x if isinstance(x, ops.Moments) else ops.Moments(x, None)
+        if not torch.is_tensor(mom.mean):
+            raise TypeError("%s takes a tensor or ops.Moments in a moment pass, got %s" % (type(self).__name__, type(x).__name__))
+        ops._refuse_link(mom, type(self).__name__)
+        ctx = _mc.moments_current()
+        if ctx.track:
+            raise ops.BnnHipError("%s has no moment backward (inference only)" % type(self).__name__)
+        relu = self.activation == 'relu'
+        if not mom.mean.is_cuda:
+            out = ops.moments_linear_vd_f64(mom, *self._posterior(), relu=relu, threshold=self._threshold())
+        else:
+            out = ops.moments_linear_vd(mom, *self._posterior(), relu=relu, compute=self._compute_mode(),
+                                        threshold=self._threshold())
+        if ctx.covariance:
+            ctx.last_dense = (type(self).__name__, self.weight.mean.shape[0])       # (no covariance is carried at this layer)
+        return out
+
+    def forward(self, x, sample=True):
+        if _mc.moments_current() is not None:
+            return self._forward_moments(x)                              # predictive_moments: moments in, moments out, no noise
+        thr = self._threshold()
+        theta, ls2, mu_b, rho_b = self._posterior()
+        if not x.is_cuda:
+            ops._vd_refuse_masked_grad(type(self).__name__, thr, theta, ls2, mu_b, rho_b)
+            s2 = self.weight.variance
+            if thr is not None:
+                keep = ~(self.weight.log_alpha > thr)
+                theta, s2 = theta * keep, s2 * keep
+            m = torch.nn.functional.linear(x, theta, mu_b)
+            v = torch.nn.functional.linear(x * x, s2, self.bias.variance if self.bias is not None else None)
+            if sample:
+                self._cpu_eps = torch.randn_like(m)
+            elif self._cpu_eps is None or self._cpu_eps.shape != m.shape:
+                raise RuntimeError("sample=False: no noise of shape %s was drawn by an earlier call" % (tuple(m.shape),))
+            return m + torch.sqrt(v + 1e-16) * self._cpu_eps
+        if x.dim() == 1:
+            return self.forward(x.unsqueeze(0), sample).squeeze(0)
+        from .._rng import DrawKey
+        S, s0, shared, per = _lrt_noise_plan(x)
+        mode = self._compute_mode()
+        lead = x.shape[1:-1]
+        K = x.shape[-1]
+        N = theta.shape[0]
+        x2 = x.reshape(-1, K) if shared else x.reshape(S, -1, K)
+        shape = (x2.shape[-2], N)
+        if sample:
+            self.noise_key = DrawKey(default_generator.seed, self._noise_stream, s0, S, default_generator.next_epoch(),
+                                     gen=generator_for(mode))
+            self._noise_shape = shape
+        key = self.noise_key
+        if key is None or self._noise_shape != shape:
+            raise RuntimeError("sample=False: %s noise recorded, this call needs %s per sample"
+                               % ("no" if key is None else "a %s" % (self._noise_shape,), shape))
+        if key.nsamples != S:
+            if S != 1:
+                raise RuntimeError("sample=False: the recorded noise has %d MC samples, this call needs %d" % (key.nsamples, S))
+            key = key.last_sample()
+        odt = torch.bfloat16 if (self.out_dtype == torch.bfloat16 and mode == "bf16") else torch.float32
+        y = ops.linear_vd(x2, theta, ls2, mu_b, rho_b, key, shared, mode, out_dtype=odt, threshold=thr)
+        return y.reshape(S * per, *lead, N)
+
+
 def _flipout_plan(layer, x):
     """Inside a BayesianNetworkModule's MC-batched pass (an McContext) on a device tensor: -> (ctx, shared), shared = x holds the
     un-replicated batch (ctx.base_batch rows) rather than S * B rows (sample = row // B).  None: the reference's torch.rand signs

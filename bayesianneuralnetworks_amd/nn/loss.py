@@ -17,7 +17,7 @@ from torch.distributions.kl import kl_divergence
 from .. import ops
 from ..utils import apply_wb
 from . import _settings
-from .core import WeightNormal, WeightMultivariateNormal
+from .core import WeightNormal, WeightMultivariateNormal, WeightVariationalDropout
 from .dense import MultivariateNormalLinear
 
 
@@ -42,8 +42,21 @@ def _hip_mvn_prior(param, prior):
     return ops.mvn_isotropic(prior)
 
 
+def _vd_kl_mean(param):
+    """The mean log-uniform KL of one WeightVariationalDropout (0-d): ops.vd_kl on the device, the torch expression on the CPU."""
+    if param.mean.is_cuda:
+        return ops.vd_kl([param.mean], [param.log_sigma2])[0]
+    return ops.vd_kl_elements(param.mean, param.log_sigma2).mean()
+
+
 class KLDivergence(Module):
-    """loss.py:11-38: mean over all weight/bias tensors of mean(KL(q || prior)), / n_batches."""
+    """loss.py:11-38: mean over all weight/bias tensors of mean(KL(q || prior)), / n_batches.
+
+    A WeightVariationalDropout (nn.VariationalDropoutLinear's weight) contributes the mean over its elements of the KL to the
+    log-uniform prior (Molchanov et al. 2017's approximation; the layer's prior argument is not read for it), averaged in like
+    every other tensor: the reference's convention -- mean over tensors of per-tensor means, / n_batches -- is kept.  On the
+    device all such tensors of a model go through ONE ops.vd_kl call (bnn_vd_kl_forward), each in its place in the list, and the
+    Gaussian tensors beside them (the layers' biases) through ONE bnn_kl_forward call."""
 
     def __init__(self, number_of_batches=1):
         super().__init__()
@@ -56,6 +69,8 @@ class KLDivergence(Module):
 
     def compute_kl(self, param, module, type):
         """loss.py:16-28 for one tensor -> its mean KL (0-d tensor)."""
+        if isinstance(param, WeightVariationalDropout):
+            return _vd_kl_mean(param)
         prior = self._prior_of(module, type)
         sn = _scalar_normal(prior)
         if isinstance(param, WeightNormal) and param.mean.is_cuda and sn is not None:
@@ -76,8 +91,15 @@ class KLDivergence(Module):
         if entries is None:
             # loss.py:34-36
             raise ValueError('KLDivergence was not able to find BayasianModules')
-        fused, other, mvn = [], [], []
+        fused, other, mvn, vd = [], [], [], []
         for param, module, type in entries:
+            if isinstance(param, WeightVariationalDropout):
+                if param.mean.is_cuda:
+                    vd.append((len(other), param))
+                    other.append(None)
+                else:
+                    other.append(_vd_kl_mean(param))
+                continue
             prior = self._prior_of(module, type)
             sn = _scalar_normal(prior)
             iso = _hip_mvn_prior(param, prior)
@@ -93,6 +115,17 @@ class KLDivergence(Module):
             kls = ops.mvn_kl([p.mean for _, p, _ in mvn], [p.scale for _, p, _ in mvn], [iso for _, _, iso in mvn])
             for k, (i, _, _) in enumerate(mvn):
                 other[i] = kls[k]
+        if vd:
+            # every variational-dropout tensor in ONE bnn_vd_kl_forward call, in its place in the list
+            kls = ops.vd_kl([p.mean for _, p in vd], [p.log_sigma2 for _, p in vd])
+            for k, (i, _) in enumerate(vd):
+                other[i] = kls[k]
+            if fused:
+                # the Gaussian tensors beside them (the layers' biases) still take ONE bnn_kl_forward call: at n_batches = 1 its
+                # scalar is the mean over those tensors of their per-tensor means, which enters the mean over all tensors with
+                # their number as its weight
+                fm = ops.kl_normal_scalar([p.mean for p, _ in fused], [p.scale for p, _ in fused], [sn for _, sn in fused], 1.0)
+                return (torch.stack(other).sum() + len(fused) * fm) / ((len(other) + len(fused)) * self.n_batches)
         if fused and not other:
             return ops.kl_normal_scalar([p.mean for p, _ in fused], [p.scale for p, _ in fused],
                                         [sn for _, sn in fused], self.n_batches)

@@ -1314,6 +1314,269 @@ def moments_f64(a, layers, track=False):
     return mom
 
 
+# --------------------------------------------------------------------------- K23: sparse variational dropout
+VD_K1, VD_K2, VD_K3 = 0.63576, 1.87320, 1.48695         # Molchanov et al. 2017, eq. 14
+VD_CLAMP = 8.0
+
+
+def vd_log_alpha(theta, log_sigma2):
+    """clamp(log_sigma2 - ln(theta^2), -8, 8) in torch, in the dtype given (theta = 0: +8) -- the CPU path and the references.
+    Differentiable: 0 where the clamp is active, and theta = 0 is taken out of the logarithm so that it gets 0 there, not 0 / 0."""
+    zero = theta == 0
+    la = torch.clamp(log_sigma2 - 2.0 * torch.log(torch.abs(torch.where(zero, torch.ones_like(theta), theta))), -VD_CLAMP, VD_CLAMP)
+    return torch.where(zero, torch.full_like(la, VD_CLAMP), la)
+
+
+def vd_kl_elements(theta, log_sigma2):
+    """The element-wise KL to the log-uniform prior in torch (differentiable): k1 sigmoid(-(k2 + k3 log_alpha)) + 0.5
+    log1p(exp(-log_alpha)).  The clamp's gradient is 0 where it is active; theta = 0 lies there and gets exactly 0."""
+    la = vd_log_alpha(theta, log_sigma2)
+    return VD_K1 * torch.sigmoid(-(VD_K2 + VD_K3 * la)) + 0.5 * torch.log1p(torch.exp(-la))
+
+
+def _vd_prepare_raw(theta, log_sigma2, rho_b, threshold=None):
+    """-> (theta plane, s2 plane, s2_b, count): one bnn_vd_prepare launch.  threshold None: theta itself, s2 = exp(log_sigma2),
+    count None.  A float: the masked planes (elements with log_alpha > threshold zeroed) and their number, a 0-d int64 tensor."""
+    s2_w = torch.empty_like(log_sigma2)
+    s2_b = torch.empty_like(rho_b) if rho_b is not None else None
+    masked = threshold is not None
+    th_out = torch.empty_like(theta) if masked else None
+    count = torch.empty((), dtype=torch.int64, device=theta.device) if masked else None
+    check(_lib.load().bnn_vd_prepare(ptr(theta), ptr(log_sigma2), theta.numel(), ptr(rho_b), ptr(s2_b),
+                                     rho_b.numel() if rho_b is not None else 0, float(threshold) if masked else math.inf,
+                                     ptr(th_out), ptr(s2_w), ptr(count), stream_ptr(theta.device)), "bnn_vd_prepare")
+    return (th_out if masked else theta), s2_w, s2_b, count
+
+
+def _vd_check_posterior(theta, log_sigma2, mu_b, rho_b):
+    require_cuda_f32(theta, "weight.mean")
+    require_cuda_f32(log_sigma2, "weight.log_sigma2")
+    if theta.shape != log_sigma2.shape or theta.dim() != 2:
+        raise BnnHipError("linear_vd: weight.mean %s and weight.log_sigma2 %s must be one (N, K) shape"
+                          % (tuple(theta.shape), tuple(log_sigma2.shape)))
+    if mu_b is not None:
+        require_cuda_f32(mu_b, "bias.mean")
+        require_cuda_f32(rho_b, "bias.scale")
+
+
+def _vd_refuse_masked_grad(who, threshold, *posterior):
+    if threshold is not None and torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in posterior):
+        raise BnnHipError("%s: a threshold is set (%r) and a posterior tensor requires a gradient: the mask is for inference -- "
+                          "run under torch.no_grad(), or set layer.threshold = None to train" % (who, threshold))
+
+
+class _VdLinear(torch.autograd.Function):
+    """_LrtLinear on the posterior N(theta, exp(log_sigma2)) (VariationalDropoutLinear): bnn_vd_prepare + bnn_lrt_forward; backward
+    bnn_lrt_backward_epilogue, bnn_lrt_backward_input and bnn_vd_backward_weight (csrc/bnn_vd.hip) -- no torch matmul."""
+
+    @staticmethod
+    def forward(ctx, x, theta, ls2, mu_b, rho_b, key, shared_x, compute, out_dtype, track, threshold):
+        x = x.contiguous()
+        require_cuda_act(x, "x")
+        if (x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16) and compute != _lib.COMPUTE_BF16:
+            raise BnnHipError("bf16 activations need compute mode 'bf16'")
+        _vd_check_posterior(theta, ls2, mu_b, rho_b)
+        S = key.nsamples
+        B, K = x.shape[-2], x.shape[-1]
+        N = theta.shape[0]
+        if not shared_x and (x.dim() != 3 or x.shape[0] != S):
+            raise BnnHipError("linear_vd: a per-sample input must be (S, B, K) with S = %d, got %s" % (S, tuple(x.shape)))
+        why = lrt_eligible(x, theta, B, S)
+        if why is not None:
+            raise BnnHipError("linear_vd: " + why)
+        dev = x.device
+        needs_grad = track and any(ctx.needs_input_grad[:5])
+        if track and threshold is not None and any(ctx.needs_input_grad[1:5]):
+            raise BnnHipError("linear_vd: a threshold is set (%r) and a posterior tensor requires a gradient: the mask is for "
+                              "inference" % (threshold,))
+        th, s2_w, s2_b, _ = _vd_prepare_raw(theta, ls2, rho_b if mu_b is not None else None, threshold)
+        y = torch.empty((S, B, N), dtype=out_dtype, device=dev)
+        v = torch.empty((B, N) if shared_x else (S, B, N), dtype=torch.float32, device=dev) if needs_grad else None
+        flags = (_lib.FLAG_X_BF16 if _bf(x) else 0) | (_lib.FLAG_Y_BF16 if out_dtype == torch.bfloat16 else 0)
+        r = _rng_struct(key, dev)
+        check(_lib.load().bnn_lrt_forward(ptr(x), K, ptr(th), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(y), ptr(v), B, N, K, S,
+                                          1 if shared_x else 0, ctypes.byref(r), compute, flags, stream_ptr(dev)), "bnn_lrt_forward")
+        if needs_grad:
+            # (th: with a threshold the masked plane -- then only the input's gradient is ever asked for, through the masked layer)
+            ctx.save_for_backward(x, th, ls2, rho_b if mu_b is not None else None, s2_w, v)
+        ctx.key, ctx.shared_x, ctx.compute = key, shared_x, compute
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, theta, ls2, rho_b, s2_w, v = ctx.saved_tensors
+        S, compute, shared = ctx.key.nsamples, ctx.compute, ctx.shared_x
+        N, K = theta.shape
+        B = x.shape[-2]
+        M = B if shared else S * B
+        dev = gy.device
+        lib = _lib.load()
+        gy = gy.contiguous()
+        if compute != _lib.COMPUTE_BF16 and gy.dtype != torch.float32:
+            gy = gy.float()
+        g_m = torch.empty((M, N), dtype=torch.float32, device=dev)
+        g_v = torch.empty((M, N), dtype=torch.float32, device=dev)
+        r = _rng_struct(ctx.key, dev)
+        check(lib.bnn_lrt_backward_epilogue(ptr(gy), ptr(v), ptr(g_m), ptr(g_v), B, N, S, 1 if shared else 0, ctypes.byref(r),
+                                            _lib.FLAG_X_BF16 if _bf(gy) else 0, stream_ptr(dev)), "bnn_lrt_backward_epilogue")
+        xflag = _lib.FLAG_X_BF16 if _bf(x) else 0
+        gx = g_theta = g_ls2 = g_mu_b = g_rho_b = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            check(lib.bnn_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(theta), ptr(s2_w), ptr(x), K, ptr(gx), M, N, K, compute,
+                                             xflag | (_lib.FLAG_Y_BF16 if _bf(x) else 0), stream_ptr(dev)), "bnn_lrt_backward_input")
+        need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or need_b:
+            g_theta, g_ls2 = torch.empty_like(theta), torch.empty_like(ls2)
+            if need_b:
+                g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
+            check(lib.bnn_vd_backward_weight(ptr(x), K, ptr(g_m), ptr(g_v), ptr(ls2), ptr(g_theta), ptr(g_ls2),
+                                             ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), M, N, K, compute, xflag,
+                                             stream_ptr(dev)), "bnn_vd_backward_weight")
+        return gx, g_theta, g_ls2, g_mu_b, g_rho_b, None, None, None, None, None, None
+
+
+def linear_vd(x, theta, log_sigma2, mu_b, rho_b, key, shared_x, compute="f32", out_dtype=torch.float32, threshold=None):
+    """VariationalDropoutLinear on the device: -> (S, B, N), S = key.nsamples; y_s = m + sqrt(v + 1e-16) eps_s with m = x theta^T +
+    mu_b, v = x^2 exp(log_sigma2)^T + sigma_b^2; sample s uses eps[b N + n] of the key's sample sample0 + s (the LRT-noise
+    contract).  threshold: a float drops the weights with log_alpha > threshold (theta = 0, variance 0: bnn_vd_prepare's masked
+    planes) -- inference only: a call that would need a gradient of a posterior tensor raises BnnHipError.  Calls the kernel
+    refuses raise BnnHipError (lrt_eligible's reason): no torch fallback."""
+    _vd_refuse_masked_grad("linear_vd", threshold, theta, log_sigma2, mu_b, rho_b)
+    return _VdLinear.apply(x, theta.contiguous(), log_sigma2.contiguous(),
+                           None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
+                           key, shared_x, _compute_code(compute), out_dtype, torch.is_grad_enabled(),
+                           None if threshold is None else float(threshold))
+
+
+def vd_dropped(theta, log_sigma2, threshold):
+    """The number of elements with log_alpha > threshold, a 0-d int64 device tensor (bnn_vd_prepare's count)."""
+    theta, log_sigma2 = theta.detach().contiguous(), log_sigma2.detach().contiguous()
+    require_cuda_f32(theta, "theta")
+    require_cuda_f32(log_sigma2, "log_sigma2")
+    return _vd_prepare_raw(theta, log_sigma2, None, float(threshold))[3]
+
+
+def moments_linear_vd(a, theta, log_sigma2, mu_b, rho_b, relu=False, compute="f32", threshold=None):
+    """moments_linear for a VariationalDropoutLinear: the same launch (bnn_moments_forward) on the variance plane
+    exp(log_sigma2), masked by `threshold` as linear_vd masks it (bnn_vd_prepare) -> Moments, fp32, detached.  Inference only."""
+    mom = _as_moments(a, "moments_linear_vd")
+    code = _compute_code(compute)
+    am = mom.mean.detach()
+    av = None if mom.var is None else mom.var.detach()
+    theta, log_sigma2 = theta.detach().contiguous(), log_sigma2.detach().contiguous()
+    if mu_b is not None:
+        mu_b, rho_b = mu_b.detach().contiguous(), rho_b.detach().contiguous()
+    _vd_check_posterior(theta, log_sigma2, mu_b, rho_b)
+    N, K = theta.shape
+    if am.dim() < 1 or am.shape[-1] != K:
+        raise BnnHipError("moments_linear_vd: input has %s features, weight expects %d" % (am.shape[-1] if am.dim() else "no", K))
+    lead = tuple(am.shape[:-1])
+    am = am.reshape(-1, K).contiguous()
+    require_cuda_act(am, "a.mean")
+    if am.dtype == torch.bfloat16 and (code != _lib.COMPUTE_BF16 or av is not None):
+        raise BnnHipError("moments_linear_vd: a bf16 input needs compute mode 'bf16' and no variance (hidden moments are fp32)")
+    if av is not None:
+        av = av.reshape(-1, K).contiguous()
+        require_cuda_f32(av, "a.var")
+    B = am.shape[0]
+    if B > 64 * 65535:
+        raise BnnHipError("moments_linear_vd: %d rows (at most %d)" % (B, 64 * 65535))
+    dev = am.device
+    th, s2_w, s2_b, _ = _vd_prepare_raw(theta, log_sigma2, rho_b if mu_b is not None else None, threshold)
+    out_m = torch.empty((B, N), dtype=torch.float32, device=dev)
+    out_v = torch.empty((B, N), dtype=torch.float32, device=dev)
+    flags = (_lib.FLAG_RELU if relu else 0) | (_lib.FLAG_X_BF16 if _bf(am) else 0)
+    check(_lib.load().bnn_moments_forward(ptr(am), ptr(av), K, ptr(th), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(out_m), ptr(out_v),
+                                          B, N, K, code, flags, stream_ptr(dev)), "bnn_moments_forward")
+    return Moments(out_m.reshape(lead + (N,)), out_v.reshape(lead + (N,)))
+
+
+def moments_linear_vd_f64(a, theta, log_sigma2, mu_b, rho_b, relu=False, threshold=None):
+    """moments_linear_vd in float64 torch (the CPU path and the tests' reference) -> Moments of float64 tensors, detached."""
+    mom = _as_moments(a, "moments_linear_vd_f64")
+    f64 = _f64(False)
+    am, th, ls2 = f64(mom.mean), f64(theta), f64(log_sigma2)
+    s2 = torch.exp(ls2)
+    if threshold is not None:
+        keep = ~(vd_log_alpha(th, ls2) > float(threshold))
+        th, s2 = th * keep, s2 * keep
+    m = am @ th.t()
+    v = (am * am) @ s2.t()
+    if mom.var is not None:
+        v = v + f64(mom.var) @ (th * th + s2).t()
+    if mu_b is not None:
+        m, v = m + f64(mu_b), v + (1e-10 + torch.nn.functional.softplus(f64(rho_b))) ** 2
+    out = Moments(m, v)
+    return moments_relu_f64(out, False) if relu else out
+
+
+def _vd_descs(thetas, ls2s):
+    arr = (_lib.VdTensor * len(thetas))()
+    for i, (t, l) in enumerate(zip(thetas, ls2s)):
+        arr[i].theta, arr[i].log_sigma2, arr[i].n = t.data_ptr(), l.data_ptr(), t.numel()
+    return arr
+
+
+_vd_count_cache = {}
+
+
+def _vd_counts(ns, device):
+    """The element counts of a vd_kl call as an fp32 device tensor, uploaded once per (sizes, device)."""
+    key = (ns, device.type, device.index)
+    c = _vd_count_cache.get(key)
+    if c is None:
+        c = _vd_count_cache[key] = torch.tensor([float(n) for n in ns], dtype=torch.float32, device=device)
+    return c
+
+
+class _VdKL(torch.autograd.Function):
+    """out[t] = mean over the elements of tensor t of the log-uniform KL: bnn_vd_kl_forward (per-tensor sums, two launches), / n_t;
+    bnn_vd_kl_backward.  The gradient is returned, never parked (FUSE_KL_GRADIENT covers WeightNormal only)."""
+
+    @staticmethod
+    def forward(ctx, T, *params):
+        thetas, ls2s = [p.detach() for p in params[:T]], [p.detach() for p in params[T:]]
+        for t, l in zip(thetas, ls2s):
+            require_cuda_f32(t, "theta")
+            require_cuda_f32(l, "log_sigma2")
+            if t.numel() != l.numel() or t.numel() < 1:
+                raise BnnHipError("vd_kl: theta and log_sigma2 must have the same, non-zero number of elements")
+        dev = thetas[0].device
+        arr = _vd_descs(thetas, ls2s)
+        nbytes = _lib.load().bnn_vd_kl_workspace_bytes(arr, T)
+        if nbytes < 0:
+            raise BnnHipError("bnn_vd_kl_workspace_bytes: bad tensors (1 .. 128 non-empty tensors)")
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)            # per call: concurrent KLs never share it
+        sums = torch.empty(T, dtype=torch.float32, device=dev)
+        check(_lib.load().bnn_vd_kl_forward(arr, T, ptr(sums), ptr(ws), stream_ptr(dev)), "bnn_vd_kl_forward")
+        ctx.save_for_backward(*params)
+        ctx.T = T
+        return sums / _vd_counts(tuple(t.numel() for t in thetas), dev)
+
+    @staticmethod
+    def backward(ctx, g):
+        params = ctx.saved_tensors
+        T = ctx.T
+        thetas, ls2s = params[:T], params[T:]
+        g_th = [torch.empty_like(t) for t in thetas]
+        g_ls = [torch.empty_like(l) for l in ls2s]
+        arr = _vd_descs(thetas, ls2s)
+        up = g.contiguous().float()
+        gt = (ctypes.c_void_p * T)(*[t.data_ptr() for t in g_th])
+        gl = (ctypes.c_void_p * T)(*[t.data_ptr() for t in g_ls])
+        check(_lib.load().bnn_vd_kl_backward(arr, T, ptr(up), gt, gl, 0, stream_ptr(up.device)), "bnn_vd_kl_backward")
+        return (None,) + tuple(g_th) + tuple(g_ls)
+
+
+def vd_kl(thetas, log_sigma2s):
+    """-> (T,) fp32: each tensor's mean KL to the log-uniform prior (Molchanov et al. 2017's approximation on the clamped
+    log_alpha), differentiable -- KLDivergence.compute_kl of a WeightVariationalDropout.  At most 128 tensors per call."""
+    if len(thetas) != len(log_sigma2s) or not thetas:
+        raise BnnHipError("vd_kl: one log_sigma2 per theta, at least one tensor")
+    return _VdKL.apply(len(thetas), *[t.contiguous() for t in thetas], *[l.contiguous() for l in log_sigma2s])
+
+
 # --------------------------------------------------------------------------- K17: moment propagation through convolutions and ELU
 def _refuse_link(mom, who):
     """Moments that carry a link are the network's output: a softmax must end the network."""
