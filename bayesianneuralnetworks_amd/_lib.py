@@ -268,6 +268,8 @@ SIGNATURES = {
     "bnn_vd_kl_workspace_bytes": (_i64, [ctypes.POINTER(VdTensor), _int]),
     "bnn_vd_kl_forward": (_int, [ctypes.POINTER(VdTensor), _int, _p, _p, _p]),
     "bnn_vd_kl_backward": (_int, [ctypes.POINTER(VdTensor), _int, _p, ctypes.POINTER(_p), ctypes.POINTER(_p), _int, _p]),
+    "bnn_conv3d_vd_backward_weight": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p,
+                                             _i64, _p]),
 }
 
 _lib = None

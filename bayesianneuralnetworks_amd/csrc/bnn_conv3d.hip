@@ -352,6 +352,27 @@ __global__ __launch_bounds__(256) void k_lrt_conv_wsum(const float *__restrict__
     g_rho[e] = gv * (2.0f * sigma_lrt(r) * dsigma_lrt(r));
 }
 
+// K24 (VariationalDropoutConv1d / 2d / 3d): the same slabs, added in the same slab order -- g_theta has k_lrt_conv_wsum's g_mu bits --
+// with the chain of the posterior N(theta, exp(log_sigma2)): g_log_sigma2[e] = (sum of the variance slabs) expf(log_sigma2[e])
+// (one 2-u expf and one product: 3 u + 2 u^2 relative; where expf would be a denormal, the fp64 product rounded once)
+__global__ __launch_bounds__(256) void k_vd_conv_wsum(const float *__restrict__ slabs, int nslab, const float *__restrict__ ls2,
+                                                     float *__restrict__ g_theta, float *__restrict__ g_ls2, int64_t n)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    float gm = 0.f, gv = 0.f;
+    for (int k = 0; k < nslab; ++k) {
+        const float *p = slabs + (int64_t)k * 2 * n + e;
+        gm += p[0];
+        gv += p[n];
+    }
+    g_theta[e] = gm;
+    // below ln 2^-126 = -87.3 expf(l) is a denormal: its error is a quantum, not 2 u of it, and the product would carry |gv|
+    // quanta.  There the product is formed in fp64 and rounded once, so that the result is within one quantum as well.
+    const float l = ls2[e];
+    g_ls2[e] = l < -87.0f ? (float)((double)gv * exp((double)l)) : gv * expf(l);
+}
+
 // g_mu_b[o] = sum over (image, position) of g_m, g_rho_b[o] = (the same sum of g_v) 2 sigma_b sigmoid(rho_b): one workgroup per
 // o, fixed strided partials (images in order) and a fixed tree.  rows = every image of every set.
 __global__ __launch_bounds__(256) void k_lrt_conv_bias_grad(const float *__restrict__ g_m, const float *__restrict__ g_v, int64_t rows,
@@ -1060,6 +1081,48 @@ int bnn_conv3d_lrt_backward_weight(const float *x, const float *g_m, const float
     if ((rc = check_launch(who))) return rc;
     hipLaunchKernelGGL(k_lrt_conv_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
                        nslab, rho_w, g_mu_w, g_rho_w, n);
+    if ((rc = check_launch(who)) || !bias) return rc;
+    hipLaunchKernelGGL(k_lrt_conv_bias_grad, dim3((unsigned)g.O), dim3(256), 0, st, g_m, g_v, (int64_t)nsets * g.B, g.O, g.P, rho_b,
+                       g_mu_b, g_rho_b);
+    return check_launch(who);
+}
+
+// ---- K24 entry (VariationalDropoutConv1d / 2d / 3d): K11's slab launch and bias launch, k_vd_conv_wsum between them ----------
+int bnn_conv3d_vd_backward_weight(const float *x, const float *g_m, const float *g_v, const float *log_sigma2, float *g_theta,
+                                  float *g_log_sigma2, const float *rho_b, float *g_mu_b, float *g_rho_b,
+                                  const bnn_conv3d_shape_t *shape, int nsets, int compute, void *workspace,
+                                  int64_t workspace_bytes, void *stream)
+{
+    const char *who = "bnn_conv3d_vd_backward_weight";
+    Conv3dGeo g;
+    int rc = conv3d_geo(who, shape, nsets, compute, g);
+    if (rc) return rc;
+    const bool bias = rho_b || g_mu_b || g_rho_b;
+    if (!x || !g_m || !g_v || !log_sigma2 || !g_theta || !g_log_sigma2 || (bias && (!rho_b || !g_mu_b || !g_rho_b))) {
+        set_error("%s: NULL pointer", who);
+        return BNN_E_NULL;
+    }
+    if (misaligned(x, 3) || misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(log_sigma2, 3) || misaligned(g_theta, 3) ||
+        misaligned(g_log_sigma2, 3) || misaligned(rho_b, 3) || misaligned(g_mu_b, 3) || misaligned(g_rho_b, 3) ||
+        misaligned(workspace, 3)) {
+        set_error("%s: misaligned pointer", who);
+        return BNN_E_ALIGN;
+    }
+    int nslab, chunk;
+    wgrad_split(g, 1, nslab, chunk);           // one image set: every slab walks all of them
+    const int64_t n = (int64_t)g.O * g.K;
+    if (!workspace || workspace_bytes < (int64_t)nslab * 2 * n * (int64_t)sizeof(float)) {
+        set_error("%s: workspace of bnn_conv3d_lrt_backward_weight_workspace_bytes bytes needed", who);
+        return BNN_E_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    LrtConvArgs a{};
+    a.x = x; a.x_ss = (int64_t)g.B * g.C * g.Pin; a.g1 = g_m; a.g2 = g_v; a.out = static_cast<float *>(workspace);
+    a.S = nsets; a.nslab = nslab; a.chunk = chunk;
+    lrt_conv_launch<C3_WGRAD>(g, a, compute, g.groups * nslab, st);
+    if ((rc = check_launch(who))) return rc;
+    hipLaunchKernelGGL(k_vd_conv_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
+                       nslab, log_sigma2, g_theta, g_log_sigma2, n);
     if ((rc = check_launch(who)) || !bias) return rc;
     hipLaunchKernelGGL(k_lrt_conv_bias_grad, dim3((unsigned)g.O), dim3(256), 0, st, g_m, g_v, (int64_t)nsets * g.B, g.O, g.P, rho_b,
                        g_mu_b, g_rho_b);

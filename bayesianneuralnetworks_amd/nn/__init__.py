@@ -11,7 +11,9 @@ from .dense import (BayesianLinear, NormalLinear, MultivariateNormalLinear, Flip
 from .conv import (BayesianConvNd, NormalConvNd, NormalConv1d, NormalConv2d, NormalConv3d,
                    FlipOutNormalConvNd, FlipOutNormalConv1d, FlipOutNormalConv2d, FlipOutNormalConv3d,
                    MCDropoutConvNd, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d,
-                   LocalReparamConvNd, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)   # (not in __all__ either)
+                   LocalReparamConvNd, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d,   # (not in __all__ either)
+                   VariationalDropoutConvNd, VariationalDropoutConv1d, VariationalDropoutConv2d,
+                   VariationalDropoutConv3d)                                                         # (nor these)
 from .loss import KLDivergence, Entropy, NormalInverseGaussianLoss, NormalInverseGaussianUncertainty
 from .loss import GaussianNLL   # (not in __all__ either)
 from ._settings import set_compute, get_compute, fuse_activations, fuse_kl_gradient, keyed_mvn_draws, moment_activations

@@ -162,7 +162,7 @@ def moment_activations(module):
     * a twin directly behind a NormalConv1d / 2d / 3d or LocalReparamConv1d / 2d / 3d is made known to that layer
       (`_moment_act`, a __dict__ entry, not a submodule): in a moment pass the activation runs in the conv launch's epilogue
       (the standalone launch's bits) and the twin passes the result through.  Behind a dense layer the twins use the
-      standalone launches.  FlipOutNormalConv1d / 2d / 3d are told in the same way.
+      standalone launches.  FlipOutNormalConv1d / 2d / 3d and VariationalDropoutConv1d / 2d / 3d are told in the same way.
     * a twin directly behind an MCDropoutLinear or MCDropoutConv1d / 2d / 3d is made known to that layer as well (K22,
       nn.moment_estimator_layers): in a moment pass the layer's ONE bnn_moments_dropout launch pushes its mask through that
       activation and the twin passes the result through; an `nn.MomentSoftmax` directly behind it is recorded as 'softmax' --
@@ -175,9 +175,11 @@ def moment_activations(module):
     from .container import BayesianModule, MomentReLU, MomentELU, MomentLinear, MomentSoftmax, _MOMENT_RECLASS
     from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
     from .conv import (FlipOutNormalConv1d, FlipOutNormalConv2d, FlipOutNormalConv3d, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d)
+    from .conv import VariationalDropoutConv1d, VariationalDropoutConv2d, VariationalDropoutConv3d
     from .dense import MCDropoutLinear
     convs = (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d,
-             FlipOutNormalConv1d, FlipOutNormalConv2d, FlipOutNormalConv3d)
+             FlipOutNormalConv1d, FlipOutNormalConv2d, FlipOutNormalConv3d,
+             VariationalDropoutConv1d, VariationalDropoutConv2d, VariationalDropoutConv3d)
     dropouts = (MCDropoutLinear, MCDropoutConv1d, MCDropoutConv2d, MCDropoutConv3d)
     replaced = 0
     for m in module.modules():

@@ -41,7 +41,8 @@ class _Single:
 
 
 _MOMENTS_SUPPORTED = ("moment propagation supports NormalLinear / LocalReparamLinear / VariationalDropoutLinear (the last for inference only), ReLU folded into them by "
-                      "nn.fuse_activations, MultivariateNormalLinear (inference only), NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d, the activations "
+                      "nn.fuse_activations, MultivariateNormalLinear (inference only), NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d, "
+                      "VariationalDropoutConv1d / 2d / 3d (inference only), the activations "
                       "nn.moment_activations rewrites (ReLU, ELU, a torch.nn.Linear behind a Bayesian layer, and a Softmax over the last "
                       "axis that ends the network; behind a Bayesian layer also MaxPool / AvgPool / AdaptiveAvgPool 1d / 2d / 3d and an "
                       "eval-mode BatchNorm1d / 2d / 3d), "
@@ -391,12 +392,13 @@ class BayesianNetworkModule(Module):
         return KLDivergence(number_of_batches)(self)
 
     def sparsity(self):
-        """(dropped, total) over every VariationalDropoutLinear of the network: the weights with log_alpha above the layer's
-        threshold (3.0 where it is None), and all of them -- layer.sparsity()'s count, summed."""
+        """(dropped, total) over every VariationalDropoutLinear and VariationalDropoutConv1d / 2d / 3d of the network: the weights
+        with log_alpha above the layer's threshold (3.0 where it is None), and all of them -- layer.sparsity()'s count, summed."""
         from .dense import VariationalDropoutLinear
+        from .conv import VariationalDropoutConvNd
         dropped = total = 0
         for m in self.modules():
-            if isinstance(m, VariationalDropoutLinear):
+            if isinstance(m, (VariationalDropoutLinear, VariationalDropoutConvNd)):
                 d, t = m._dropped()
                 dropped, total = dropped + d, total + t
         return dropped, total
@@ -593,7 +595,9 @@ class BayesianNetworkModule(Module):
         mean and variance are exact; from the second hidden layer on the recursion treats a layer's inputs as independent
         Gaussians (the usual diagonal-covariance approximation); the outputs' covariance is carried only with covariance=True (below).
         NormalConv1d / 2d / 3d and LocalReparamConv1d / 2d / 3d run as ops.moments_convNd (K17: per output element the marginal
-        moments are exact for a deterministic input; the correlation between the positions of an output map is dropped).
+        moments are exact for a deterministic input; the correlation between the positions of an output map is dropped);
+        VariationalDropoutLinear and VariationalDropoutConv1d / 2d / 3d as ops.moments_linear_vd / ops.moments_convNd_vd (K23, K24:
+        the same launches on the planes theta and exp(log_sigma2), masked by the layer's threshold).
         Supported: those layers, ReLU folded into the dense ones by nn.fuse_activations, what nn.moment_activations rewrites
         (ReLU, ELU, a torch.nn.Linear behind a Bayesian layer, a Softmax over the last axis that ends the network: the result
         then carries link='softmax' and holds the LOGIT moments; K20: max / average / adaptive average pooling 1d / 2d / 3d and
@@ -629,9 +633,11 @@ class BayesianNetworkModule(Module):
         evidential head."""
         from .. import ops
         from .dense import NormalLinear, LocalReparamLinear, MultivariateNormalLinear, VariationalDropoutLinear
-        from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d)
+        from .conv import (NormalConv1d, NormalConv2d, NormalConv3d, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d,
+                           VariationalDropoutConv1d, VariationalDropoutConv2d, VariationalDropoutConv3d)
         admitted = (NormalLinear, LocalReparamLinear, VariationalDropoutLinear, MultivariateNormalLinear, NormalConv1d, NormalConv2d, NormalConv3d,
-                    LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d) + _estimator_layers()
+                    LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d, VariationalDropoutConv1d, VariationalDropoutConv2d,
+                    VariationalDropoutConv3d) + _estimator_layers()
         for m in self.modules():
             if isinstance(m, BayesianModule) and type(m) not in admitted:
                 raise ops.BnnHipError("predictive_moments: %s is not supported; %s" % (type(m).__name__, _moments_supported()))

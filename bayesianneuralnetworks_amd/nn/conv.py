@@ -9,9 +9,14 @@ MC-batched device pass their signs are keyed per MC sample (bnn_conv2d_flipout_f
 variants run their torch conv once and apply the keyed masks of a network's MC-batched device pass in HIP (bnn_mc_dropout).
 LocalReparamConv1d / 2d / 3d (not reference names) sample the Gaussian pre-activation instead of the weights: one operand launch
 and ONE paired-contraction launch for all S samples (bnn_conv3d_lrt_forward; 1-d and 2-d as unit depth / height), HIP backward.
+VariationalDropoutConv1d / 2d / 3d (not reference names either) are sparse variational dropout on those kernels: the posterior
+N(theta, exp(log_sigma2)) under a log-uniform prior (bnn_vd_prepare, bnn_conv3d_vd_backward_weight; K24).
 """
+import math
+
 import torch
 from torch.distributions import Normal
+from torch.nn import init
 
 from .. import _mc, ops
 from . import _settings
@@ -298,6 +303,189 @@ def _local_reparam(name, ntuple, op, nd):
 LocalReparamConv1d = _local_reparam('LocalReparamConv1d', _single, torch.nn.functional.conv1d, 1)
 LocalReparamConv2d = _local_reparam('LocalReparamConv2d', _pair, torch.nn.functional.conv2d, 2)
 LocalReparamConv3d = _local_reparam('LocalReparamConv3d', _triple, torch.nn.functional.conv3d, 3)
+
+
+class VariationalDropoutConvNd(BayesianConvNd):
+    """Sparse variational dropout for convolutions (Molchanov, Ashukha, Vetrov 2017; not a reference name; the conv variant of
+    VariationalDropoutLinear): a conv layer that learns which of its weights -- and with them which whole filters -- to drop.
+    Every weight has the posterior N(theta, sigma^2) -- `weight` is a WeightVariationalDropout (out, in / groups, *kernel) with
+    Parameters mean (theta) and log_sigma2 -- and a log-uniform prior; the pre-activation is sampled by local
+    reparameterization as LocalReparamConvNd samples it,
+
+        m   = convNd(x,   theta,           mu_b,      stride, padding, dilation, groups)
+        v   = convNd(x^2, exp(log_sigma2), sigma_b^2, stride, padding, dilation, groups)
+        y_s = m + sqrt(v + 1e-16) eps_s,        eps_s ~ N(0, 1), one per output element and MC sample
+
+    and KLDivergence / .kl_divergence() add the log-uniform KL of the weight (ops.vd_kl: every such tensor of a model, dense and
+    conv, in one call; no prior argument: the prior is fixed) beside the Gaussian KL of the bias against `bias_prior`.  `bias` is
+    None or a WeightNormal; state_dict keys weight.mean, weight.log_sigma2, bias.mean, bias.scale.  Initialisation: the mean as
+    NormalConvNd's, log_sigma2 = -10, the bias as VariationalDropoutLinear's.
+
+    Device input: bnn_vd_prepare + bnn_conv3d_lrt_forward (both compute modes; 1-d and 2-d layers on unit depth / height), fp32
+    input and output; the backward is HIP (bnn_lrt_backward_epilogue, bnn_conv3d_lrt_backward_input,
+    bnn_conv3d_vd_backward_weight); no torch conv and no torch fallback (BnnHipError with the kernel's reason).  In a
+    BayesianNetworkModule's MC-batched pass a layer that sees the shared batch contracts m and v ONCE for all S samples, one that
+    sees S B rows contracts per sample; noise_key and sample=False mean what they mean on LocalReparamConvNd (the LRT-conv noise
+    contract of include/bnn_hip.h).  CPU tensors: the expression above in torch with torch.randn_like.
+
+    threshold (an attribute, default None): with a float every path -- the sampling forward, the MC-batched pass, the moment
+    pass -- drops the weights with log_alpha > threshold (theta = 0 and variance 0).  The mask is for inference: a call that would
+    need a gradient of a posterior tensor while a threshold is set raises ops.BnnHipError.  sparsity() is the fraction of weights
+    with log_alpha > threshold (3.0 while threshold is None), filter_sparsity() the fraction of output filters ALL of whose
+    weights are: a filter that can be taken out of the layer.
+
+    Inside BayesianNetworkModule.predictive_moments the layer is NormalConvNd's moment layer on the planes theta and
+    exp(log_sigma2) (ops.moments_convNd_vd: bnn_conv3d_moments_forward, the ELU / ReLU nn.moment_activations found behind it in
+    the epilogue); a tracking pass (forward_moments) raises ops.BnnHipError: there is no moment backward.  The network draw plan
+    and nn.fuse_activations select by exact type and pass this layer by.  Out of scope: bf16 activations (K11 takes fp32), the
+    multiplicative parametrisation, compacting a pruned model into smaller layers, distributed.forward_sharded's KL sharding."""
+
+    compute = None      # None -> module-wide default (nn.set_compute)
+    _op = None
+    _nd = 0
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, bias_prior, threshold):
+        from .core import WeightVariationalDropout
+        from .._rng import new_stream_id
+        # the weight's prior is the log-uniform one; BayesianConvNd would build the bias from the weight's class
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, False, groups, False,
+                         WeightVariationalDropout, None, bias_prior)
+        if bias:
+            del self._parameters['bias']            # (registered as None by the base class, whose reset_parameters set the weight)
+            self.bias = WeightNormal(out_channels)
+            self._reset_bias()
+        self.threshold = threshold
+        self._noise_stream = new_stream_id()        # the layer's eps stream
+        self.noise_key = None                       # DrawKey of the last device call
+        self._noise_shape = None                    # one sample's INPUT shape (B, C, *spatial) of that call
+        self._cpu_eps = None
+
+    def _reset_bias(self):
+        fan_in, _ = init._calculate_fan_in_and_fan_out(self.weight.mean)
+        bound = 1 / math.sqrt(fan_in)
+        init.uniform_(self.bias.mean, -bound, bound)
+        init.normal_(self.bias.scale, -2.0, 0.15)
+
+    def reset_parameters(self):
+        init.kaiming_uniform_(self.weight.mean, a=math.sqrt(5))
+        init.constant_(self.weight.log_sigma2, -10.0)
+        if self.bias is not None:
+            self._reset_bias()
+
+    def _compute_mode(self):
+        return self.compute or _settings.get_compute()
+
+    def _posterior(self):
+        b = self.bias is not None
+        return (self.weight.mean, self.weight.log_sigma2, self.bias.mean if b else None, self.bias.scale if b else None)
+
+    def _threshold(self):
+        return None if self.threshold is None else float(self.threshold)
+
+    def _dropped_mask(self):
+        """The weights with log_alpha > threshold (3.0 while threshold is None), a bool tensor of the weight's shape: on the device
+        read off bnn_vd_prepare's masked plane (ops.vd_dropped_mask), on the CPU the float64 expression -- one rule, the kernels'."""
+        thr = 3.0 if self.threshold is None else float(self.threshold)
+        w = self.weight
+        with torch.no_grad():
+            if w.mean.is_cuda:
+                return ops.vd_dropped_mask(w.mean, w.log_sigma2, thr)
+            return ops.vd_log_alpha(w.mean.double(), w.log_sigma2.double()) > thr
+
+    def _dropped(self):
+        return int(self._dropped_mask().sum().item()), self.weight.mean.numel()
+
+    def sparsity(self):
+        """The fraction of weights with log_alpha > threshold (3.0 while threshold is None)."""
+        dropped, total = self._dropped()
+        return dropped / total
+
+    def filter_sparsity(self):
+        """The fraction of output filters all of whose weights have log_alpha > threshold (3.0 while threshold is None)."""
+        mask = self._dropped_mask()
+        return int(mask.reshape(mask.shape[0], -1).all(dim=1).sum().item()) / mask.shape[0]
+
+    def _forward_moments(self, x):
+        mom = x if isinstance(x, ops.Moments) else ops.Moments(x, None)
+        if not torch.is_tensor(mom.mean):
+            raise TypeError("%s takes a tensor or ops.Moments in a moment pass, got %s" % (type(self).__name__, type(x).__name__))
+        ops._refuse_link(mom, type(self).__name__)
+        if _mc.moments_current().track:
+            raise ops.BnnHipError("%s has no moment backward (inference only)" % type(self).__name__)
+        if mom.mean.dim() == self._nd + 1:
+            out = self._forward_moments(ops.Moments(mom.mean.unsqueeze(0), None if mom.var is None else mom.var.unsqueeze(0)))
+            res = ops.Moments(out.mean.squeeze(0), out.var.squeeze(0))
+            res._act = out._act
+            return res
+        act = self.__dict__.get("_moment_act")
+        args = self._posterior() + (self.stride, self.padding, self.dilation, self.groups)
+        if not mom.mean.is_cuda:
+            out = ops.moments_convNd_vd_f64(mom, *args, activation=act, threshold=self._threshold())
+        else:
+            out = ops.moments_convNd_vd(mom, *args, activation=act, compute=self._compute_mode(), threshold=self._threshold())
+        out._act = act
+        return out
+
+    def forward(self, x, sample=True):
+        if _mc.moments_current() is not None:
+            return self._forward_moments(x)                              # predictive_moments: moments in, moments out, no noise
+        conv = type(self)._op
+        geo = (self.stride, self.padding, self.dilation, self.groups)
+        thr = self._threshold()
+        theta, ls2, mu_b, rho_b = self._posterior()
+        if not x.is_cuda:
+            ops._vd_refuse_masked_grad(type(self).__name__, thr, theta, ls2, mu_b, rho_b)
+            s2 = self.weight.variance
+            if thr is not None:
+                keep = ~(self.weight.log_alpha > thr)
+                theta, s2 = theta * keep, s2 * keep
+            m = conv(x, theta, mu_b, *geo)
+            v = conv(x * x, s2, self.bias.variance if self.bias is not None else None, *geo)
+            if sample:
+                self._cpu_eps = torch.randn_like(m)
+            elif self._cpu_eps is None or self._cpu_eps.shape != m.shape:
+                raise RuntimeError("sample=False: no noise of shape %s was drawn by an earlier call" % (tuple(m.shape),))
+            return m + torch.sqrt(v + 1e-16) * self._cpu_eps
+        if x.dim() == self._nd + 1:
+            return self.forward(x.unsqueeze(0), sample).squeeze(0)
+        from .._rng import DrawKey, default_generator, generator_for
+        S, s0, shared, per = _lrt_noise_plan(x)
+        mode = self._compute_mode()
+        xs = x if shared else x.reshape(S, per, *x.shape[1:])
+        shape = (per,) + tuple(x.shape[1:])
+        if sample:
+            self.noise_key = DrawKey(default_generator.seed, self._noise_stream, s0, S, default_generator.next_epoch(),
+                                     gen=generator_for(mode))
+            self._noise_shape = shape
+        key = self.noise_key
+        if key is None or self._noise_shape != shape:
+            raise RuntimeError("sample=False: %s noise recorded, this call has %s per sample"
+                               % ("no" if key is None else "an input of %s gave the" % (self._noise_shape,), shape))
+        if key.nsamples != S:
+            if S != 1:
+                raise RuntimeError("sample=False: the recorded noise has %d MC samples, this call needs %d" % (key.nsamples, S))
+            key = key.last_sample()
+        y = ops.convNd_vd(xs, theta, ls2, mu_b, rho_b, key, shared, *geo, mode, threshold=thr)
+        return y.reshape(S * per, *y.shape[2:])
+
+
+def _variational_dropout(name, ntuple, op, nd):
+    class _VariationalDropout(VariationalDropoutConvNd):
+        _op = staticmethod(op)
+        _nd = nd
+
+        def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
+                     groups=1, bias=True, bias_prior=Normal(0, .1), threshold=None):
+            super().__init__(in_channels, out_channels, ntuple(kernel_size), ntuple(stride), ntuple(padding),
+                             ntuple(dilation), groups, bias, bias_prior, threshold)
+    _VariationalDropout.__name__ = _VariationalDropout.__qualname__ = name
+    _VariationalDropout.__doc__ = "VariationalDropoutConvNd with %d spatial ax%s." % (nd, "is" if nd == 1 else "es")
+    return _VariationalDropout
+
+
+VariationalDropoutConv1d = _variational_dropout('VariationalDropoutConv1d', _single, torch.nn.functional.conv1d, 1)
+VariationalDropoutConv2d = _variational_dropout('VariationalDropoutConv2d', _pair, torch.nn.functional.conv2d, 2)
+VariationalDropoutConv3d = _variational_dropout('VariationalDropoutConv3d', _triple, torch.nn.functional.conv3d, 3)
 
 
 def _flipout_conv2d_device(layer, x, R, S, view, stride, padding, dilation):

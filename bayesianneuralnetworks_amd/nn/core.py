@@ -116,8 +116,8 @@ class WeightVariationalDropout(Module):
     weight in the additive parametrisation -- Parameters `mean` (theta) and `log_sigma2` = ln sigma^2 -- under a log-uniform
     prior.  log_alpha = clamp(log_sigma2 - ln(mean^2), -8, 8) measures how much noise a weight carries relative to its size
     (mean = 0: +8); training with KLDivergence drives it up for every weight the data does not need, and a weight with
-    log_alpha above a threshold (3: alpha > 20) can be dropped.  Nothing is drawn from it: VariationalDropoutLinear samples its
-    pre-activations (local reparameterization), so there is no .sampled."""
+    log_alpha above a threshold (3: alpha > 20) can be dropped.  Nothing is drawn from it: VariationalDropoutLinear and
+    VariationalDropoutConv1d / 2d / 3d sample their pre-activations (local reparameterization), so there is no .sampled."""
 
     def __init__(self, *channels):
         super().__init__()

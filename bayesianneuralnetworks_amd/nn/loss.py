@@ -52,8 +52,8 @@ def _vd_kl_mean(param):
 class KLDivergence(Module):
     """loss.py:11-38: mean over all weight/bias tensors of mean(KL(q || prior)), / n_batches.
 
-    A WeightVariationalDropout (nn.VariationalDropoutLinear's weight) contributes the mean over its elements of the KL to the
-    log-uniform prior (Molchanov et al. 2017's approximation; the layer's prior argument is not read for it), averaged in like
+    A WeightVariationalDropout (the weight of nn.VariationalDropoutLinear and of nn.VariationalDropoutConv1d / 2d / 3d, whatever
+    its shape) contributes the mean over its elements of the KL to the log-uniform prior (Molchanov et al. 2017's approximation; the layer's prior argument is not read for it), averaged in like
     every other tensor: the reference's convention -- mean over tensors of per-tensor means, / n_batches -- is kept.  On the
     device all such tensors of a model go through ONE ops.vd_kl call (bnn_vd_kl_forward), each in its place in the list, and the
     Gaussian tensors beside them (the layers' biases) through ONE bnn_kl_forward call."""

@@ -1348,10 +1348,15 @@ def _vd_prepare_raw(theta, log_sigma2, rho_b, threshold=None):
     return (th_out if masked else theta), s2_w, s2_b, count
 
 
-def _vd_check_posterior(theta, log_sigma2, mu_b, rho_b):
+def _vd_check_posterior(theta, log_sigma2, mu_b, rho_b, conv=False):
+    """conv: the weight of a VariationalDropoutConvNd, (O, C / groups, *kernel) with 1, 2 or 3 kernel axes, in place of (N, K)."""
     require_cuda_f32(theta, "weight.mean")
     require_cuda_f32(log_sigma2, "weight.log_sigma2")
-    if theta.shape != log_sigma2.shape or theta.dim() != 2:
+    if conv:
+        if theta.shape != log_sigma2.shape or theta.dim() not in (3, 4, 5):
+            raise BnnHipError("conv_vd: weight.mean %s and weight.log_sigma2 %s must be one (O, C / groups, *kernel) shape with "
+                              "1, 2 or 3 kernel axes" % (tuple(theta.shape), tuple(log_sigma2.shape)))
+    elif theta.shape != log_sigma2.shape or theta.dim() != 2:
         raise BnnHipError("linear_vd: weight.mean %s and weight.log_sigma2 %s must be one (N, K) shape"
                           % (tuple(theta.shape), tuple(log_sigma2.shape)))
     if mu_b is not None:
@@ -1455,6 +1460,19 @@ def vd_dropped(theta, log_sigma2, threshold):
     require_cuda_f32(theta, "theta")
     require_cuda_f32(log_sigma2, "log_sigma2")
     return _vd_prepare_raw(theta, log_sigma2, None, float(threshold))[3]
+
+
+def vd_dropped_mask(theta, log_sigma2, threshold):
+    """The elements with log_alpha > threshold as a bool device tensor of theta's shape, read off bnn_vd_prepare's masked theta
+    plane (one launch; a host-side report, not hot-path work).  Below the clamp's +8 a masked element is exactly a zero of that
+    plane: theta = 0 has log_alpha = +8 and is masked, every kept element keeps its non-zero theta.  From +8 on nothing exceeds
+    the threshold."""
+    theta, log_sigma2 = theta.detach().contiguous(), log_sigma2.detach().contiguous()
+    require_cuda_f32(theta, "theta")
+    require_cuda_f32(log_sigma2, "log_sigma2")
+    if float(threshold) >= VD_CLAMP:
+        return torch.zeros_like(theta, dtype=torch.bool)
+    return _vd_prepare_raw(theta, log_sigma2, None, float(threshold))[0] == 0
 
 
 def moments_linear_vd(a, theta, log_sigma2, mu_b, rho_b, relu=False, compute="f32", threshold=None):
@@ -1959,6 +1977,70 @@ def moments_convNd_f64(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, g
     if act == 'relu':
         return moments_relu_f64(out, track)
     return moments_elu_f64(out, alpha, track) if act == 'elu' else out
+
+
+def moments_convNd_vd(a, theta, log_sigma2, mu_b, rho_b, stride, padding, dilation, groups=1, activation=None, compute="f32",
+                      threshold=None):
+    """moments_convNd for a VariationalDropoutConvNd (K24): the same launch (bnn_conv3d_moments_forward, the activation in its
+    epilogue) on the planes of bnn_vd_prepare -- theta and exp(log_sigma2), masked by `threshold` as convNd_vd masks them ->
+    Moments, fp32 (B, O, *out_spatial), detached.  Inference only: there is no moment backward for this posterior."""
+    who = "moments_convNd_vd"
+    mom = _as_moments(a, who)
+    _refuse_link(mom, who)
+    act, alpha = _moment_activation(activation, who)
+    code = _compute_code(compute)
+    am = mom.mean.detach().contiguous()
+    av = None if mom.var is None else mom.var.detach().contiguous()
+    theta, log_sigma2 = theta.detach().contiguous(), log_sigma2.detach().contiguous()
+    if mu_b is not None:
+        mu_b, rho_b = mu_b.detach().contiguous(), rho_b.detach().contiguous()
+    _vd_check_posterior(theta, log_sigma2, mu_b, rho_b, conv=True)
+    require_cuda_f32(am, "a.mean")
+    if av is not None:
+        require_cuda_f32(av, "a.var")
+    nd = theta.dim() - 2
+    if am.dim() != nd + 2:
+        raise BnnHipError("%s: input must be (B, C, ...) with %d spatial axes for a weight of shape %s, got %s"
+                          % (who, nd, tuple(theta.shape), tuple(am.shape)))
+    img, w5, st, pd, dl = _lrt_conv_views(am.shape, theta.shape, stride, padding, dilation)
+    B = int(am.shape[0])
+    sh, out3 = _conv3d_shape((B,) + img, w5, st, pd, dl, groups)
+    out_sp = out3[3 - nd:]
+    dev = am.device
+    th, s2_w, s2_b, _ = _vd_prepare_raw(theta, log_sigma2, rho_b if mu_b is not None else None, threshold)
+    out_m = torch.empty((B, sh.O) + out_sp, dtype=torch.float32, device=dev)
+    out_v = torch.empty_like(out_m)
+    check(_lib.load().bnn_conv3d_moments_forward(ptr(am), ptr(av), ptr(th), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(out_m),
+                                                 ptr(out_v), ctypes.byref(sh), code, _ACT_FLAGS[act], alpha, stream_ptr(dev)),
+          "bnn_conv3d_moments_forward")
+    return Moments(out_m, out_v)
+
+
+def moments_convNd_vd_f64(a, theta, log_sigma2, mu_b, rho_b, stride, padding, dilation, groups=1, activation=None, threshold=None):
+    """moments_convNd_vd in float64 torch (the CPU path and the tests' reference) -> Moments of float64 tensors, detached."""
+    who = "moments_convNd_vd_f64"
+    mom = _as_moments(a, who)
+    _refuse_link(mom, who)
+    act, alpha = _moment_activation(activation, who)
+    f64 = _f64(False)
+    nd = theta.dim() - 2
+    if nd not in (1, 2, 3):
+        raise BnnHipError("%s: weight must be (O, C / groups, *kernel) with 1, 2 or 3 kernel axes, got %s" % (who, tuple(theta.shape)))
+    conv = (torch.nn.functional.conv1d, torch.nn.functional.conv2d, torch.nn.functional.conv3d)[nd - 1]
+    geo = (tuple(stride), tuple(padding), tuple(dilation), int(groups))
+    am, th, ls2 = f64(mom.mean), f64(theta), f64(log_sigma2)
+    s2 = torch.exp(ls2)
+    if threshold is not None:
+        keep = ~(vd_log_alpha(th, ls2) > float(threshold))
+        th, s2 = th * keep, s2 * keep
+    m = conv(am, th, None if mu_b is None else f64(mu_b), *geo)
+    v = conv(am * am, s2, None if mu_b is None else (1e-10 + torch.nn.functional.softplus(f64(rho_b))) ** 2, *geo)
+    if mom.var is not None:
+        v = v + conv(f64(mom.var), th * th + s2, None, *geo)
+    out = Moments(m, v)
+    if act == 'relu':
+        return moments_relu_f64(out, False)
+    return moments_elu_f64(out, alpha, False) if act == 'elu' else out
 
 
 # --------------------------------------------------------------------------- K22: MC dropout (and deterministic convs) in a moment pass
@@ -3672,6 +3754,89 @@ def convNd_lrt(x, mu_w, rho_w, mu_b, rho_b, key, shared_x, stride, padding, dila
                           None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
                           key, bool(shared_x), (tuple(stride), tuple(padding), tuple(dilation), int(groups)),
                           _compute_code(compute), torch.is_grad_enabled())
+
+
+# --------------------------------------------------------------------------- K24: sparse variational dropout, convolutions
+class _VdConv(torch.autograd.Function):
+    """_LrtConv on the posterior N(theta, exp(log_sigma2)) (VariationalDropoutConvNd): bnn_vd_prepare + bnn_conv3d_lrt_forward, 2
+    launches; backward bnn_lrt_backward_epilogue, bnn_conv3d_lrt_backward_input and bnn_conv3d_vd_backward_weight (K11's slabs,
+    k_vd_conv_wsum, the bias sums) -- 5 launches with a bias, 4 without, no torch conv."""
+
+    @staticmethod
+    def forward(ctx, x, theta, ls2, mu_b, rho_b, key, shared_x, conv_args, compute, track, threshold):
+        require_cuda_f32(x, "x")
+        _vd_check_posterior(theta, ls2, mu_b, rho_b, conv=True)
+        stride, padding, dilation, groups = conv_args
+        S = key.nsamples
+        why = conv_lrt_eligible(x, theta, S, shared_x, stride, padding, dilation, groups)
+        if why is not None:
+            raise BnnHipError("conv_vd: " + why)
+        if track and threshold is not None and any(ctx.needs_input_grad[1:5]):
+            raise BnnHipError("conv_vd: a threshold is set (%r) and a posterior tensor requires a gradient: the mask is for "
+                              "inference" % (threshold,))
+        nd = theta.dim() - 2
+        img, w5, st, pd, dl = _lrt_conv_views(x.shape, theta.shape, stride, padding, dilation)
+        B = int(x.shape[-nd - 2])
+        sh, out3 = _conv3d_shape((B,) + img, w5, st, pd, dl, groups)
+        out_sp = out3[3 - nd:]
+        dev = x.device
+        needs_grad = track and any(ctx.needs_input_grad[:5])
+        th, s2_w, s2_b, _ = _vd_prepare_raw(theta, ls2, rho_b if mu_b is not None else None, threshold)
+        y = torch.empty((S, B, sh.O) + out_sp, dtype=torch.float32, device=dev)
+        v = torch.empty(((B, sh.O) if shared_x else (S, B, sh.O)) + out_sp, dtype=torch.float32, device=dev) if needs_grad else None
+        r = _rng_struct(key, dev)
+        check(_lib.load().bnn_conv3d_lrt_forward(ptr(x), 0 if shared_x else x[0].numel(), ptr(th), ptr(s2_w), ptr(mu_b), ptr(s2_b),
+                                                 ptr(y), ptr(v), ctypes.byref(sh), S, ctypes.byref(r), compute, stream_ptr(dev)),
+              "bnn_conv3d_lrt_forward")
+        if needs_grad:
+            # (th: with a threshold the masked plane -- then only the input's gradient is ever asked for, through the masked layer)
+            ctx.save_for_backward(x, th, ls2, rho_b if mu_b is not None else None, s2_w, v)
+        ctx.key, ctx.shared_x, ctx.compute, ctx.sh = key, shared_x, compute, sh
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, theta, ls2, rho_b, s2_w, v = ctx.saved_tensors
+        S, compute, shared, sh = ctx.key.nsamples, ctx.compute, ctx.shared_x, ctx.sh
+        dev = gy.device
+        lib, st = _lib.load(), stream_ptr(dev)
+        gy = gy.contiguous().float()
+        nsets = 1 if shared else S
+        g_m, g_v = torch.empty_like(v), torch.empty_like(v)
+        r = _rng_struct(ctx.key, dev)
+        check(lib.bnn_lrt_backward_epilogue(ptr(gy), ptr(v), ptr(g_m), ptr(g_v), sh.B, v[0].numel() if shared else v[0][0].numel(),
+                                            S, 1 if shared else 0, ctypes.byref(r), 0, st), "bnn_lrt_backward_epilogue")
+        gx = g_theta = g_ls2 = g_mu_b = g_rho_b = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            check(lib.bnn_conv3d_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(theta), ptr(s2_w), ptr(x), ptr(gx), ctypes.byref(sh),
+                                                    nsets, compute, st), "bnn_conv3d_lrt_backward_input")
+        need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or need_b:
+            g_theta, g_ls2 = torch.empty_like(theta), torch.empty_like(ls2)
+            if need_b:
+                g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
+            nb = lib.bnn_conv3d_lrt_backward_weight_workspace_bytes(ctypes.byref(sh), nsets)
+            ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)          # this call's own slabs
+            check(lib.bnn_conv3d_vd_backward_weight(ptr(x), ptr(g_m), ptr(g_v), ptr(ls2), ptr(g_theta), ptr(g_ls2),
+                                                    ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), ctypes.byref(sh),
+                                                    nsets, compute, ptr(ws), nb, st), "bnn_conv3d_vd_backward_weight")
+        return gx, g_theta, g_ls2, g_mu_b, g_rho_b, None, None, None, None, None, None
+
+
+def convNd_vd(x, theta, log_sigma2, mu_b, rho_b, key, shared_x, stride, padding, dilation, groups=1, compute="f32", threshold=None):
+    """VariationalDropoutConv{1,2,3}d on the device (the dimension is the weight's): convNd_lrt on the posterior
+    N(theta, exp(log_sigma2)) -- x (B, C, *spatial) shared by the key's S samples (shared_x) or (S, B, C, *spatial) ->
+    (S, B, O, *out_spatial) fp32, y_s = m + sqrt(v + 1e-16) eps_s with m = convNd(x, theta, mu_b), v = convNd(x^2,
+    exp(log_sigma2), sigma_b^2); sample s uses eps[(b O + o) P + p] of the key's sample sample0 + s (the LRT-conv noise contract).
+    threshold: a float drops the weights with log_alpha > threshold (theta = 0, variance 0: bnn_vd_prepare's masked planes) --
+    inference only: a call that would need a gradient of a posterior tensor raises BnnHipError.  Raises BnnHipError (with
+    conv_lrt_eligible's reason) for a call the kernel refuses: no torch fallback."""
+    _vd_refuse_masked_grad("convNd_vd", threshold, theta, log_sigma2, mu_b, rho_b)
+    return _VdConv.apply(x.contiguous(), theta.contiguous(), log_sigma2.contiguous(),
+                         None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
+                         key, bool(shared_x), (tuple(stride), tuple(padding), tuple(dilation), int(groups)),
+                         _compute_code(compute), torch.is_grad_enabled(), None if threshold is None else float(threshold))
 
 
 # --------------------------------------------------------------------------- Flipout conv3d (FlipOutNormalConv3d on the device)

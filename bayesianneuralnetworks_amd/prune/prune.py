@@ -1,6 +1,6 @@
 """Signal-to-noise pruning (pytorch_bayesian/prune/prune.py:5-22).  On the device the score log N(0; mu, sigma) is
 a HIP kernel (bnn_prune_score); the top-k selection and the masked assignment are torch ops on the device.
-PruneLogAlpha is the threshold rule of sparse variational dropout (nn.VariationalDropoutLinear)."""
+PruneLogAlpha is the threshold rule of sparse variational dropout (nn.VariationalDropoutLinear, nn.VariationalDropoutConv1d / 2d / 3d)."""
 import torch
 
 from ..utils import apply_wb

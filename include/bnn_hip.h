@@ -1395,6 +1395,26 @@ int bnn_vd_kl_forward(const bnn_vd_tensor_t *tensors, int ntensors, float *out, 
 int bnn_vd_kl_backward(const bnn_vd_tensor_t *tensors, int ntensors, const float *upstream, float *const *g_theta,
                        float *const *g_log_sigma2, int accumulate, void *stream);
 
+/* ---- K24: sparse variational dropout for convolutions (VariationalDropoutConv1d / 2d / 3d, bayesianneuralnetworks_amd/nn/conv.py;
+ * csrc/bnn_conv3d.hip).  No call site in the reference.  K23's posterior N(theta, exp(log_sigma2)) on K11's layer: the weight is
+ * (O, C / groups, KD, KH, KW), bnn_vd_prepare writes its planes (a flat tensor of any shape), and bnn_conv3d_lrt_forward (the
+ * LRT-conv noise contract, as written), bnn_lrt_backward_epilogue, bnn_conv3d_lrt_backward_input and bnn_conv3d_moments_forward
+ * take (theta, s2) for (mu_w, s2_w) unchanged; the optional Gaussian bias (mu_b, rho_b) is K11's; the KL is K23's.
+ *
+ * bnn_conv3d_lrt_backward_weight for this posterior.  The slab launch is K11's own (the same kernel, grid and workspace:
+ * bnn_conv3d_lrt_backward_weight_workspace_bytes), so the slabs hold the same bits; the reduce launch adds them in slab order
+ * and writes g_theta = sum of the mean slabs -- bit for bit K11's g_mu_w on the same x, g_m, g_v -- and
+ * g_log_sigma2 = (sum of the variance slabs) expf(log_sigma2), d exp(l) / dl = exp(l): within 3 u + 2 u^2 of the product in exact
+ * arithmetic, and below log_sigma2 = -87, where expf returns a denormal, the fp64 product rounded once (one quantum, 2^-149, of
+ * a denormal result; u of a normal one).  Bias (rho_b, g_mu_b, g_rho_b all given,
+ * or all NULL): K11's third launch.  Two launches without a bias, three with one.  Fixed orders, no atomics: identical calls
+ * give identical bits.  Errors (nothing launched) as bnn_conv3d_lrt_backward_weight: BNN_E_NULL, BNN_E_SHAPE, BNN_E_DTYPE (an
+ * unknown compute), BNN_E_RANGE (K7's ranges), BNN_E_ALIGN (4 bytes), BNN_E_UNSUPPORTED (workspace NULL or too small). */
+int bnn_conv3d_vd_backward_weight(const float *x, const float *g_m, const float *g_v, const float *log_sigma2, float *g_theta,
+                                  float *g_log_sigma2, const float *rho_b, float *g_mu_b, float *g_rho_b,
+                                  const bnn_conv3d_shape_t *shape, int nsets, int compute, void *workspace,
+                                  int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
