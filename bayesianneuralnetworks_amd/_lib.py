@@ -270,6 +270,9 @@ SIGNATURES = {
     "bnn_vd_kl_backward": (_int, [ctypes.POINTER(VdTensor), _int, _p, ctypes.POINTER(_p), ctypes.POINTER(_p), _int, _p]),
     "bnn_conv3d_vd_backward_weight": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(Conv3dShape), _int, _int, _p,
                                              _i64, _p]),
+    "bnn_lstm_step_forward": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _int, _p]),
+    "bnn_lstm_step_backward": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _int,
+                                      _p]),
 }
 
 _lib = None

@@ -14,6 +14,7 @@ from .conv import (BayesianConvNd, NormalConvNd, NormalConv1d, NormalConv2d, Nor
                    LocalReparamConvNd, LocalReparamConv1d, LocalReparamConv2d, LocalReparamConv3d,   # (not in __all__ either)
                    VariationalDropoutConvNd, VariationalDropoutConv1d, VariationalDropoutConv2d,
                    VariationalDropoutConv3d)                                                         # (nor these)
+from .recurrent import NormalLSTM   # (K25; not in __all__ either)
 from .loss import KLDivergence, Entropy, NormalInverseGaussianLoss, NormalInverseGaussianUncertainty
 from .loss import GaussianNLL   # (not in __all__ either)
 from ._settings import set_compute, get_compute, fuse_activations, fuse_kl_gradient, keyed_mvn_draws, moment_activations

@@ -2817,6 +2817,184 @@ def linear_plain(x, w, b, shared_x, compute="f32"):
                               shared_x, _compute_code(compute))
 
 
+# --------------------------------------------------------------------------- K25: the Bayesian LSTM cell (nn.NormalLSTM)
+LSTM_TILE_ROWS, LSTM_TILE_UNITS = 16, 16        # csrc/bnn_lstm.hip: L_TR rows of a sample x L_TU hidden units per workgroup
+
+
+def _at(t, elements):
+    """Device pointer `elements` fp32 elements into t (a step of a (S, rows, T, .) buffer, addressed with a row pitch)."""
+    return ctypes.c_void_p(t.data_ptr() + 4 * elements)
+
+
+class _LstmSaved:
+    """What the backward of one LSTM forward needs: the input, the two column blocks of the drawn weights, every step's hidden
+    and cell state and gate activations (the tensors travel through ctx.save_for_backward, in this order)."""
+    __slots__ = ("x", "wx", "wh", "hs", "cs", "gates", "shared_x")
+
+    def __init__(self, x, wx, wh, hs, cs, gates, shared_x):
+        self.x, self.wx, self.wh, self.hs, self.cs, self.gates, self.shared_x = x, wx, wh, hs, cs, gates, shared_x
+
+
+def _lstm_forward_raw(x, w, b, shared_x, want_grad):
+    """The recurrence on given weights.  x: (rows, T, I) shared by the samples or (S, rows, T, I); w: (S, 4 H, I + H), columns
+    [0, I) on x_t and [I, I + H) on h_{t-1}, rows in gate order i, f, g, o; b: (S, 4 H) or None -- fp32, contiguous.
+    -> hs (S, rows, T, H), and (wx, wh, cs, gates) when a backward will follow (None otherwise).  One bnn_linear_forward for the input projection of all
+    steps, then T bnn_lstm_step_forward launches; nothing in the loop allocates or synchronises."""
+    S, H4, IH = w.shape
+    H = H4 // 4
+    I = IH - H
+    rows, T = x.shape[-3], x.shape[-2]
+    if H4 != 4 * H or I < 1 or x.shape[-1] != I:
+        raise BnnHipError("lstm: input has %d features, weight (%d, %d) expects %d" % (x.shape[-1], H4, IH, I))
+    if rows < 1 or T < 1:
+        raise BnnHipError("lstm: needs at least one row and one time step, got rows = %d, T = %d" % (rows, T))
+    dev = x.device
+    lib = _lib.load()
+    st = stream_ptr(dev)
+    wx, wh = w[:, :, :I].contiguous(), w[:, :, I:].contiguous()         # the existing contractions take a weight row pitch of K
+    M = rows * T
+    gx = torch.empty((S, rows, T, H4), dtype=torch.float32, device=dev)
+    check(lib.bnn_linear_forward(ptr(x), 0 if shared_x else M * I, I, ptr(wx), H4 * I, ptr(b), H4, ptr(gx), M * H4, H4,
+                                 M, H4, I, S, _lib.COMPUTE_F32, 0, st), "bnn_linear_forward")
+    hs = torch.empty((S, rows, T, H), dtype=torch.float32, device=dev)
+    if want_grad:
+        cs = torch.empty((S, rows, T, H), dtype=torch.float32, device=dev)
+        gates = torch.empty((S, rows, T, H4), dtype=torch.float32, device=dev)
+    else:
+        cs, gates = torch.empty((2, S, rows, H), dtype=torch.float32, device=dev), None
+    for t in range(T):
+        if want_grad:
+            c_prev, c, ldc = (_at(cs, (t - 1) * H) if t else None), _at(cs, t * H), T * H
+        else:                                                               # inference: two cell-state buffers take turns
+            c_prev, c, ldc = (_at(cs, ((t - 1) % 2) * S * rows * H) if t else None), _at(cs, (t % 2) * S * rows * H), H
+        check(lib.bnn_lstm_step_forward(_at(gx, t * H4), T * H4, ptr(wh), H4 * H, _at(hs, (t - 1) * H) if t else None, T * H,
+                                        c_prev, ldc, _at(hs, t * H), T * H, c, ldc,
+                                        _at(gates, t * H4) if want_grad else None, T * H4, rows, H, S, st), "bnn_lstm_step_forward")
+    return hs, ((wx, wh, cs, gates) if want_grad else None)
+
+
+def _lstm_backward_raw(sv, gy, need_x, need_w, need_b):
+    """gy: (S, rows, T, H), or (S, rows, H) when only the last hidden state left the layer -> (g_x, g_w (S, 4 H, I + H), g_b (S, 4 H)),
+    None where not needed.  T bnn_lstm_step_backward launches from t = T - 1 down leave dG (S, rows, T, 4 H); every sum over time
+    then runs once over T * rows rows on the linear layer's entries."""
+    S, rows, T, H = sv.hs.shape
+    H4, I = 4 * H, sv.wx.shape[2]
+    M = rows * T
+    dev = gy.device
+    lib = _lib.load()
+    st = stream_ptr(dev)
+    dg = torch.empty((S, rows, T, H4), dtype=torch.float32, device=dev)
+    carry = torch.empty((2, 2, S, rows, H), dtype=torch.float32, device=dev)        # [g_h | g_c][t % 2]
+    n = S * rows * H
+    g_h, g_c = (_at(carry, 0), _at(carry, n)), (_at(carry, 2 * n), _at(carry, 3 * n))
+    seq = gy.dim() == 4
+    for t in range(T - 1, -1, -1):
+        last = t == T - 1
+        g_h_out = _at(gy, t * H) if seq else (ptr(gy) if last else None)
+        check(lib.bnn_lstm_step_backward(_at(sv.gates, t * H4), T * H4, _at(sv.cs, (t - 1) * H) if t else None, T * H,
+                                         _at(sv.cs, t * H), T * H, g_h_out, T * H if seq else H,
+                                         None if last else g_h[(t + 1) % 2], None if last else g_c[(t + 1) % 2],
+                                         ptr(sv.wh), H4 * H, _at(dg, t * H4), T * H4, g_h[t % 2], g_c[t % 2],
+                                         rows, H, S, st), "bnn_lstm_step_backward")
+    dg = dg.view(S, M, H4)
+    g_x = g_w = g_b = None
+    if need_w:
+        g_wx = _wgrad_plain_raw(sv.x, 0 if sv.shared_x else M * I, dg, M, H4, I, S)
+        h_prev = torch.zeros_like(sv.hs)                                            # h_{t-1} per (row, step): h_{-1} = 0
+        h_prev[:, :, 1:] = sv.hs[:, :, :-1]
+        g_wh = _wgrad_plain_raw(h_prev, M * H, dg, M, H4, H, S)
+        g_w = torch.cat((g_wx, g_wh), dim=2)
+    if need_b:
+        g_b = _colsum_raw(dg)
+    if need_x:
+        g_x = _dgrad_plain_raw(dg, sv.wx, torch.float32)                            # (S, M, I)
+        g_x = _sum_samples(g_x).view(rows, T, I) if sv.shared_x else g_x.view(S, rows, T, I)
+    return g_x, g_w, g_b
+
+
+def _lstm_check_input(x, shared_x, S):
+    require_cuda_f32(x, "x")
+    if x.dim() != (3 if shared_x else 4) or (not shared_x and x.shape[0] != S):
+        raise BnnHipError("lstm: x must be (rows, T, I) for a shared input or (S, rows, T, I), got %s for S = %d" % (tuple(x.shape), S))
+
+
+def _lstm_output(hs, return_sequences):
+    return hs if return_sequences else hs[:, :, -1].contiguous()
+
+
+class _LstmSampled(torch.autograd.Function):
+    """NormalLSTM on its posterior: w (S, 4 H, I + H) and b (S, 4 H) drawn by bnn_sample_affine_philox on the keys -- ONE draw per
+    MC sample for all T steps -- then _lstm_forward_raw.  Backward: _lstm_backward_raw, then bnn_sample_affine_bwd on the keys."""
+
+    @staticmethod
+    def forward(ctx, x, mu_w, rho_w, mu_b, rho_b, key_w, key_b, shared_x, return_sequences, track):
+        S = key_w.nsamples
+        _lstm_check_input(x, shared_x, S)
+        w = _sample_affine_philox_raw(mu_w, rho_w, key_w)
+        b = _sample_affine_philox_raw(mu_b, rho_b, key_b) if mu_b is not None else None
+        want_grad = track and any(ctx.needs_input_grad[:5])
+        hs, kept = _lstm_forward_raw(x, w, b, shared_x, want_grad)
+        ctx.key_w, ctx.key_b, ctx.shared_x = key_w, key_b, shared_x
+        if kept is not None:
+            ctx.save_for_backward(x, kept[0], kept[1], hs, kept[2], kept[3], rho_w, rho_b)
+        return _lstm_output(hs, return_sequences)
+
+    @staticmethod
+    def backward(ctx, gy):
+        rho_w, rho_b = ctx.saved_tensors[6:]
+        sv, S = _LstmSaved(*ctx.saved_tensors[:6], ctx.shared_x), ctx.key_w.nsamples
+        need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        g_x, g_w, g_b = _lstm_backward_raw(sv, gy.contiguous().float(), ctx.needs_input_grad[0], need_w, need_b)
+        g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
+        if need_w:
+            g_mu_w, g_rho_w = _sample_affine_bwd_raw(g_w, rho_w, rho_w.numel(), S, key=ctx.key_w)
+        if need_b:
+            g_mu_b, g_rho_b = _sample_affine_bwd_raw(g_b, rho_b, rho_b.numel(), S, key=ctx.key_b)
+        return g_x, g_mu_w, g_rho_w, g_mu_b, g_rho_b, None, None, None, None, None
+
+
+class _LstmPlain(torch.autograd.Function):
+    """The same recurrence and the same kernels on given weights w (S, 4 H, I + H), b (S, 4 H) or None."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, shared_x, return_sequences, track):
+        require_cuda_f32(w, "w")
+        if b is not None:
+            require_cuda_f32(b, "b")
+        _lstm_check_input(x, shared_x, w.shape[0])
+        want_grad = track and any(ctx.needs_input_grad[:3])
+        hs, kept = _lstm_forward_raw(x, w, b, shared_x, want_grad)
+        ctx.has_b, ctx.shared_x = b is not None, shared_x
+        if kept is not None:
+            ctx.save_for_backward(x, kept[0], kept[1], hs, kept[2], kept[3])
+        return _lstm_output(hs, return_sequences)
+
+    @staticmethod
+    def backward(ctx, gy):
+        sv = _LstmSaved(*ctx.saved_tensors, ctx.shared_x)
+        g_x, g_w, g_b = _lstm_backward_raw(sv, gy.contiguous().float(), ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                           ctx.has_b and ctx.needs_input_grad[2])
+        return g_x, g_w, g_b, None, None, None
+
+
+def lstm_sampled(x, mu_w, rho_w, mu_b, rho_b, key_w, key_b, shared_x, return_sequences=True):
+    """The Bayesian LSTM layer (K25) on a device input: x (rows, T, I) shared by the key's S samples, or (S, rows, T, I) -> the hidden
+    states (S, rows, T, H), or the last one (S, rows, H).  fp32 operands and accumulation in both compute modes."""
+    for t, n in ((mu_w, "weight.mean"), (rho_w, "weight.scale")):
+        if not t.is_cuda:
+            raise BnnHipError("%s must be a CUDA/HIP tensor" % n)
+    return _LstmSampled.apply(x.contiguous(), mu_w.contiguous(), rho_w.contiguous(),
+                              None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
+                              key_w, key_b, bool(shared_x), bool(return_sequences), torch.is_grad_enabled())
+
+
+def lstm_plain(x, w, b, shared_x, return_sequences=True):
+    """lstm_sampled's recurrence on explicit weights w (S, 4 H, I + H), b (S, 4 H) or None (weights assigned through .sampled)."""
+    return _LstmPlain.apply(x.contiguous(), w.contiguous(), None if b is None else b.contiguous(), bool(shared_x),
+                            bool(return_sequences), torch.is_grad_enabled())
+
+
 # --------------------------------------------------------------------------- MC dropout
 def check_drop_prob(p):
     """F.dropout's argument check (same ValueError)."""

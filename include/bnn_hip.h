@@ -1415,6 +1415,50 @@ int bnn_conv3d_vd_backward_weight(const float *x, const float *g_m, const float 
                                   const bnn_conv3d_shape_t *shape, int nsets, int compute, void *workspace,
                                   int64_t workspace_bytes, void *stream);
 
+/* ---- K25: the Bayesian LSTM cell, one time step per launch (nn.NormalLSTM, bayesianneuralnetworks_amd/nn/recurrent.py;
+ * csrc/bnn_lstm.hip).  No call site in the reference: it has no recurrent layer (Fortunato et al. 2017, "Bayesian Recurrent
+ * Neural Networks").  One weight draw per MC sample serves every step of that sample; the draw is K1's
+ * (bnn_sample_affine_philox on a (4 H, I + H) tensor) and neither entry reads rho.  For sample s, row r, hidden unit j:
+ *     G[q]  = gx[s][r][q H + j] + sum_k h_prev[s][r][k] w_h[s][q H + j][k]        q = 0 .. 3: the gates i, f, g, o (torch's order)
+ *     c     = sigmoid(G[1]) c_prev + sigmoid(G[0]) tanh(G[2]),     h = sigmoid(G[3]) tanh(c)
+ * gx is the input projection x_t W_x^T + b of the step, computed for all steps beforehand (bnn_linear_forward).
+ * Every (S, rows, .) operand with a pitch argument has row r of sample s at base + (s * rows + r) * pitch: a step is read from
+ * and written into a (S, rows, T, .) buffer in place with base + t * width and pitch T * width.  w_h: (4 H, H) row-major per
+ * sample, sample s at w_h + s * w_sample_stride.  Operands without a pitch are contiguous (S, rows, H).
+ * Numerics: fp32 operands and fp32 accumulation (v_mfma_f32_16x16x4_f32), whatever the compute mode of the caller.  The
+ * accumulation order of an output element depends on H alone -- not on nsamples, rows or the grid -- and there are no atomics:
+ * identical calls give identical bits, and sample s of a batched call has the bits of a one-sample call on that sample's
+ * operands.  With u = 2^-24 the device sigmoid has relative error <= 4 u and tanh absolute error <= 5 u (csrc/bnn_lstm.hip);
+ * neither overflows for |G| <= 88.
+ * Alignment: every pointer on its element (BNN_E_ALIGN otherwise).  16-byte loads of h_prev and w_h (forward), of the pointwise
+ * operands and stores of dg and g_c_prev (backward), when H % 4 == 0 and those pointers and pitches are multiples of 16 bytes;
+ * element accesses otherwise -- the same bits.
+ * Errors (nothing launched): BNN_E_NULL; BNN_E_SHAPE: rows, H or nsamples < 1, a pitch below its row length (4 H for gx, gates
+ * and dg, H for the states), w_sample_stride < 4 H H; BNN_E_RANGE: rows >= 2^31, H > 16 * 65535, nsamples > 65535, a pitch
+ * >= 2^31 or nsamples * rows * pitch (nsamples * w_sample_stride) > 2^62; BNN_E_ALIGN.
+ *
+ * bnn_lstm_step_forward: writes h and c, and -- gates != NULL, when a backward will follow -- the four gate ACTIVATIONS
+ * sigmoid(G[0]), sigmoid(G[1]), tanh(G[2]), sigmoid(G[3]) at gates[s][r][q H + j].  h_prev = c_prev = NULL (together): zeros, the
+ * first step.  No output may overlap an input.  One launch: a workgroup (one wave) owns 16 rows x 16 units of a sample. */
+int bnn_lstm_step_forward(const float *gx, int64_t ldgx, const float *w_h, int64_t w_sample_stride,
+                          const float *h_prev, int64_t ldh_prev, const float *c_prev, int64_t ldc_prev,
+                          float *h, int64_t ldh, float *c, int64_t ldc, float *gates, int64_t ldgates,
+                          int64_t rows, int64_t H, int nsamples, void *stream);
+/* bnn_lstm_step_backward: the backward of that step.  With gh = g_h_out + g_h_in (the gradient reaching h_t from the layer's
+ * output at step t and from step t + 1; either may be NULL = zeros, g_h_in and g_c_in together), the saved activations i, f, g, o
+ * of gates, and tc = tanh(c):
+ *     dc       = g_c_in + gh o (1 - tc^2)
+ *     dg[0..3] = dc g i (1 - i),  dc c_prev f (1 - f),  dc i (1 - g^2),  gh tc o (1 - o)           at dg[s][r][q H + j]
+ *     g_c_prev = dc f,      g_h_prev[s][r][k] = sum_n dg[s][r][n] w_h[s][n][k]                      n over all 4 H gate rows
+ * c_prev = NULL: zeros (the first step).  g_h_in, g_c_in, g_h_prev, g_c_prev: contiguous (S, rows, H); no output may overlap an
+ * input (carry the two gradients in two buffers each).  One launch: a workgroup owns 16 rows x 16 output units, forms dg for
+ * its rows itself (pointwise), and the workgroup of unit block 0 stores dg and g_c_prev. */
+int bnn_lstm_step_backward(const float *gates, int64_t ldgates, const float *c_prev, int64_t ldc_prev,
+                           const float *c, int64_t ldc, const float *g_h_out, int64_t ldg_h_out,
+                           const float *g_h_in, const float *g_c_in, const float *w_h, int64_t w_sample_stride,
+                           float *dg, int64_t lddg, float *g_h_prev, float *g_c_prev,
+                           int64_t rows, int64_t H, int nsamples, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
