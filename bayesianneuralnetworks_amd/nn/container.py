@@ -11,6 +11,7 @@ from torch.nn import Module
 
 from .. import _mc
 from ..utils import _item_or_list, traverse
+from ..utils.utils import deepcopy_detached
 
 
 class BayesianModule(Module):
@@ -22,6 +23,8 @@ class BayesianModule(Module):
         self.bias_prior = bias_prior if bias_prior else prior   # container.py:12
         self.in_channels = in_channels
         self.out_channels = out_channels
+
+    __deepcopy__ = deepcopy_detached           # (a MultivariateNormalLinear's .sampled carries its graph)
 
     def kl_divergence(self, number_of_batches=1):
         """Convenience BASELINE.json's north_star names (the reference has only the module form, loss.py:11-38):

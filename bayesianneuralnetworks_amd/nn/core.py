@@ -14,6 +14,7 @@ from torch.distributions import Normal, MultivariateNormal
 
 from .. import ops
 from .._rng import default_generator, new_stream_id, DrawKey
+from ..utils.utils import deepcopy_detached
 
 
 class WeightNormal(Module):
@@ -27,6 +28,8 @@ class WeightNormal(Module):
         self._key = None
         self._explicit = None
         self.sample()                      # core.py:15: `.sampled` exists from construction
+
+    __deepcopy__ = deepcopy_detached           # (_explicit carries its graph)
 
     # ---- reference properties (core.py:17-42)
     @property
@@ -171,6 +174,8 @@ class WeightMultivariateNormal(Module):
         self.draw_key = None            # DrawKey of the last keyed draw
         self._mvn_stream = None
         self.sample()
+
+    __deepcopy__ = deepcopy_detached           # (.sampled carries its graph)
 
     def fresh_key(self, nsamples, sample0, epoch, gen):
         """A DrawKey for a keyed draw of nsamples samples (not recorded)."""

@@ -703,7 +703,12 @@ class MultivariateNormalLinear(BayesianLinear):
 
     def _moments_prepared(self, cpu=False):
         """ops.mvn_moments_prepare's four outputs for the layer's posterior (CPU input: mvn_moments_prepare_f64's), computed again
-        only when a parameter has changed (repeated inference batches pay one launch)."""
+        only when a parameter has changed (repeated inference batches pay one launch).  "Changed" is what the parameters' autograd
+        version counters say ("State that outlives a call")."""
+        if not cpu and torch.cuda.is_current_stream_capturing():
+            # a captured pass is replayed on whatever the parameters hold THEN, and a replay advances no version: the prepare
+            # launch goes into the graph, and the cache keeps what it held for the eager callers
+            return ops.mvn_moments_prepare(*self._posterior())
         ps = [p for p in self._posterior() if p is not None]
         tag = (cpu,) + tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in ps)
         cached = self.__dict__.get("_moments_cache")
@@ -889,8 +894,12 @@ class MCDropoutLinear(BayesianModule):
         self._w_bf16 = None
 
     def _weight_bf16(self):
-        """The weight as the dense kernel's bf16 operand, converted again only when the weight has changed."""
+        """The weight as the dense kernel's bf16 operand, converted again only when the weight has changed -- by its autograd version
+        counter (DESIGN.md, "State that outlives a call")."""
         w = self.linear.weight
+        if torch.cuda.is_current_stream_capturing():
+            # a replay reads the weight of ITS time and advances no version: the conversion is part of the graph
+            return ops.mean_bf16(w.detach())
         tag = (w.data_ptr(), w._version, tuple(w.shape))
         if self._w_bf16 is None or self._w_bf16[0] != tag:
             self._w_bf16 = (tag, ops.mean_bf16(w.detach()))

@@ -10,6 +10,7 @@ Every function here requires CUDA (HIP) tensors and raises BnnHipError otherwise
 import collections
 import contextlib
 import ctypes
+import functools
 import itertools
 import math
 import os
@@ -507,15 +508,18 @@ def _linear_sampled_raw(x2, x_sample_stride, M, mu_w, rho_w, mu_b, rho_b, key_w,
 
 
 class _ThreadState(threading.local):
-    """Per-thread hand-over state (two threads driving two models must not see each other's):
+    """Per-thread hand-over state of the forward (two threads driving two models must not see each other's):
     kl_carry   -- a KlDeferred whose first pass waits for a narrow layer's launch to carry it (kl_normal_begin(carry=True));
-    kl_pending -- KL gradients parked for the layers' weight-gradient launches (FUSE_KL_GRADIENT), keyed by the mean's
-                  storage; a backward pass runs its nodes on the thread that called backward() for its device."""
+    last_split -- draw_layers(split=...): the three planes of the activation that rode in the last launch.
+    kl_pending is NOT per thread: a backward pass runs a device's nodes on the autograd engine's thread for that device, not on
+    the thread that called backward(), so one dict serves every thread (what a caller reads after backward() is what the pass
+    used) and every entry names its pass instead (see _KlPending)."""
+
+    kl_pending = {}     # KL gradients parked for the layers' weight-gradient launches (FUSE_KL_GRADIENT), keyed by the mean's storage
 
     def __init__(self):
         self.kl_carry = None
-        self.kl_pending = {}
-        self.last_split = None      # draw_layers(split=...): the three planes of the activation that rode in the last launch
+        self.last_split = None
 
 
 _tls = _ThreadState()
@@ -542,21 +546,32 @@ def _aligned16(*ts):
 # weight-gradient kernel adds the closed-form KL gradient in its final store (no bnn_kl_backward pass, no
 # autograd accumulation add per parameter).  Entries nobody picked up (parity-mode layers, unused layers, a
 # KL node that happened to run after the layers) are flushed at the end of the pass by an engine callback.
+# Every entry carries the id of its backward pass (autograd's graph task): the engine runs no queued callback of
+# a pass that raised, so such a pass leaves its entries behind -- a later pass does not take them (_kl_take), does
+# not flush them (_kl_flush) and overwrites them when its own KL node parks for the same tensor.
 # OPT-IN (nn.fuse_kl_gradient(True)): parking returns no gradient from the KL node itself, which is only right when
 # the pass accumulates into .grad (loss.backward()); torch.autograd.grad(kl, params) needs the default path.
 FUSE_KL_GRADIENT = False
 
 
 class _KlPending:
-    __slots__ = ("up", "scale", "prior", "mu", "rho")
+    __slots__ = ("up", "scale", "prior", "mu", "rho", "task")
 
-    def __init__(self, up, scale, prior, mu, rho):
-        self.up, self.scale, self.prior, self.mu, self.rho = up, scale, prior, mu, rho
+    def __init__(self, up, scale, prior, mu, rho, task):
+        self.up, self.scale, self.prior, self.mu, self.rho, self.task = up, scale, prior, mu, rho, task
 
 
 def _kl_take(mu):
+    """The entry parked for `mu` by the KL node of the backward pass that is running, or None."""
     pend = _tls.kl_pending
-    return pend.pop((mu.device.index, mu.data_ptr()), None) if pend else None
+    if not pend:
+        return None
+    key = (mu.device.index, mu.data_ptr())
+    e = pend.get(key)
+    if e is None or e.task != torch._C._current_graph_task_id():
+        return None
+    del pend[key]
+    return e
 
 
 def _kl_fuse_struct(ent_w, ent_b):
@@ -573,13 +588,15 @@ def _kl_fuse_struct(ent_w, ent_b):
     return k
 
 
-def _kl_flush():
-    """Engine callback at the end of a backward pass: KL gradients of the tensors no layer picked up."""
+def _kl_flush(task):
+    """Engine callback at the end of backward pass `task`: KL gradients of the tensors no layer picked up."""
     pend = _tls.kl_pending
-    if not pend:
+    ents = [(k, e) for k, e in list(pend.items()) if e.task == task]
+    if not ents:
         return
-    ents = list(pend.values())
-    pend.clear()
+    for k, _ in ents:
+        del pend[k]
+    ents = [e for _, e in ents]
     lib = _lib.load()
     for e in ents:
         g_mu, g_rho = torch.empty_like(e.mu), torch.empty_like(e.rho)
@@ -4324,12 +4341,15 @@ class _KLNormal(torch.autograd.Function):
             up2 = g_out[T:T + 1].contiguous()
             up = up2 if up is None else up + up2
         up = up.contiguous()
+        pend, task = _tls.kl_pending, torch._C._current_graph_task_id()
+        keys = [(m.device.index, m.data_ptr()) for m in mus]
         if FUSE_KL_GRADIENT and all(m.is_leaf and r.is_leaf for m, r in zip(mus, rhos)) and \
-                not any((m.device.index, m.data_ptr()) in _tls.kl_pending for m in mus):   # (two KL terms on one tensor: no parking)
-            # park the gradient for the layers' weight-gradient launches (see _ThreadState above)
-            for m, r, pr in zip(mus, rhos, ctx.priors):
-                _tls.kl_pending[(m.device.index, m.data_ptr())] = _KlPending(up, 1.0 / (m.numel() * T * ctx.n_batches), pr, m, r)
-            torch.autograd.Variable._execution_engine.queue_callback(_kl_flush)
+                not any(k in pend and pend[k].task == task for k in keys):   # (two KL terms of THIS pass on one tensor: no parking)
+            # park the gradient for the layers' weight-gradient launches (see _KlPending above); what an earlier pass that
+            # raised left under the same key is overwritten
+            for k, m, r, pr in zip(keys, mus, rhos, ctx.priors):
+                pend[k] = _KlPending(up, 1.0 / (m.numel() * T * ctx.n_batches), pr, m, r, task)
+            torch.autograd.Variable._execution_engine.queue_callback(functools.partial(_kl_flush, task))
             return (None, None, None) + (None,) * (2 * T)
         g_mu = [torch.empty_like(m) for m in mus]
         g_rho = [torch.empty_like(r) for r in rhos]

@@ -32,9 +32,37 @@ class Adam(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
 
     @torch.no_grad()
+    def ensure_state(self):
+        """Create the moments of every parameter that requires a gradient, and every group's step counter, now -- what the first
+        step() would do.  For a step that is to be CAPTURED before any eager step has run: tensors created inside a capture live
+        in the graph, and the fill that zeroes them is replayed with it (step() refuses to create them there)."""
+        for group in self.param_groups:
+            ps = [p for p in group["params"] if p.requires_grad]
+            for p in ps:
+                if not self.state[p]:
+                    self._new_state(p)
+            if ps and "step" not in group:
+                group["step"] = torch.zeros(1, dtype=torch.float32, device=ps[0].device)
+
+    def _new_state(self, p):
+        st = self.state[p]
+        st["exp_avg"] = torch.zeros_like(p)
+        st["exp_avg_sq"] = torch.zeros_like(p)
+        return st
+
+    @staticmethod
+    def _refuse_state_in_capture():
+        if torch.cuda.is_current_stream_capturing():
+            raise BnnHipError("optim.Adam: this step would create its moments or its step counter inside a graph capture, where every "
+                              "replay zeroes them again; run one eager step first, or call ensure_state() before the capture")
+
+    @torch.no_grad()
     def step(self, closure=None, advance=None):
         """advance (optional, a device epoch cell of _rng.EpsGenerator.epoch_dev): bumped by one in the step's last launch
-        -- the fresh-noise step of a captured training step without a launch of its own (last parameter group only)."""
+        -- the fresh-noise step of a captured training step without a launch of its own (last parameter group only).
+        The launch writes the parameters, the moments and the step counter through raw pointers; their autograd version counters
+        are advanced here (host-only, nothing is added to a capture), so that whatever keys on a parameter's version -- autograd's
+        check of saved tensors, the layers' operand caches -- sees the step."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -55,14 +83,19 @@ class Adam(torch.optim.Optimizer):
                     raise BnnHipError("optim.Adam: gradients must be contiguous fp32")
                 st = self.state[p]
                 if not st:
-                    st["exp_avg"] = torch.zeros_like(p)
-                    st["exp_avg_sq"] = torch.zeros_like(p)
+                    self._refuse_state_in_capture()
+                    st = self._new_state(p)
                 arr[i].p, arr[i].g = p.data_ptr(), g.data_ptr()
                 arr[i].m, arr[i].v, arr[i].n = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
             if "step" not in group:
+                self._refuse_state_in_capture()
                 group["step"] = torch.zeros(1, dtype=torch.float32, device=dev)
             adv = advance if (advance is not None and gi == len(groups) - 1) else None
             check(lib.bnn_adam_step_advance(arr, len(ps), float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]),
                                             float(group["eps"]), float(group["weight_decay"]), ptr(group["step"]),
                                             ptr(adv) if adv is not None else None, 1, stream_ptr(dev)), "bnn_adam_step")
+            written = list(ps)
+            for p in ps:
+                written += (self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"])
+            torch.autograd.graph.increment_version(written + [group["step"]])
         return loss

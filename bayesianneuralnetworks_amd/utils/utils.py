@@ -1,7 +1,9 @@
 """Plumbing helpers with the behaviour of pytorch_bayesian/utils/utils.py (reference
 file:line cited per function).  Pure Python, no compute."""
+import copy
 from collections.abc import Iterable
 
+import torch
 from torch.nn import ModuleDict, ModuleList, Sequential
 
 
@@ -61,3 +63,23 @@ def traverse(module, fn, *args, **kwargs):
         if isinstance(out, list) and out:
             return out
     return None
+
+
+def _detached(value):
+    if torch.is_tensor(value):
+        return value if value.is_leaf else value.detach()
+    if isinstance(value, (tuple, list)):
+        return type(value)(_detached(v) for v in value)
+    return value
+
+
+def deepcopy_detached(self, memo):
+    """`__deepcopy__` of the modules that keep a draw (WeightNormal._explicit, WeightMultivariateNormal.sampled, a layer's
+    .sampled / R / S): a CPU draw is mean + stddev * eps WITH its autograd graph, and torch refuses to deep-copy a tensor that is
+    not a leaf -- a freshly built model could not be copied.  The copy keeps the draw's values, detached; everything else is
+    copied as copy.deepcopy copies a Module."""
+    new = self.__class__.__new__(self.__class__)
+    memo[id(self)] = new
+    for k, v in self.__dict__.items():
+        new.__dict__[k] = copy.deepcopy(_detached(v), memo)
+    return new

@@ -432,3 +432,43 @@ def test_rows_pitch_reads_the_strides_off_the_view():
     assert ops.rows_pitch(torch.zeros(8, 128, dtype=torch.bfloat16)[:, ::2], 64) is None        # element stride 2
     assert ops.rows_pitch(torch.zeros(1, 64, dtype=torch.bfloat16).expand(4, 64).unsqueeze(1), 64) is None   # samples overlap (stride 0)
     assert ops.rows_regular(buf[:, :, :1200], 1200) and not ops.rows_regular(torch.zeros(3, 64), 64)
+
+
+def test_deepcopy_of_a_fresh_model():
+    """copy.deepcopy of a model that has never run: the draws the posteriors keep from construction (`.sampled`, on the CPU a
+    tensor WITH its autograd graph, which torch refuses to deep-copy) arrive detached, with their values; parameters, stream ids and
+    recorded keys are the copy's own; the original is untouched and still trains through its draw."""
+    import copy
+
+    class Net(BayesianNetworkModule):
+        def __init__(self):
+            super().__init__(6, 3, samples=2)
+            self.layers = torch.nn.Sequential(NormalLinear(6, 5), torch.nn.ReLU(), bnn.nn.LocalReparamLinear(5, 4), torch.nn.ReLU(),
+                                              MultivariateNormalLinear(4, 3))
+
+        def _forward(self, x):
+            return self.layers(x)
+
+    torch.manual_seed(0)
+    net = Net()
+    w0 = net.layers[0].weight
+    assert w0.sampled.grad_fn is not None and net.layers[4].sampled[0].grad_fn is not None      # what used to make deepcopy raise
+    twin = copy.deepcopy(net)
+    for (n, p), (m, q) in zip(net.named_parameters(), twin.named_parameters()):
+        assert n == m and torch.equal(p, q) and p.data_ptr() != q.data_ptr() and q.is_leaf and q.requires_grad
+    t0 = twin.layers[0].weight
+    assert torch.equal(t0.sampled, w0.sampled) and t0.sampled.grad_fn is None and w0.sampled.grad_fn is not None
+    for a, b in zip(twin.layers[4].sampled, net.layers[4].sampled):
+        assert torch.equal(a, b) and a.grad_fn is None
+    assert t0._stream == w0._stream and twin.layers[2]._noise_stream == net.layers[2]._noise_stream
+    assert twin.layers[4].weight_prior is not net.layers[4].weight_prior
+    x = torch.randn(3, 6)
+    torch.manual_seed(1)
+    a = torch.stack(net(x))
+    torch.manual_seed(1)
+    b = torch.stack(twin(x))
+    assert torch.equal(a, b)
+    b.sum().backward()
+    assert all(p.grad is None for p in net.parameters()) and all(q.grad is not None for q in twin.parameters())
+    net.layers[0](x, sample=False).sum().backward()                 # the original's construction-time draw still carries its graph
+    assert net.layers[0].weight.mean.grad is not None
