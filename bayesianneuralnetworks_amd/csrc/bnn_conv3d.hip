@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void k_conv3d_bias_grad(const float *__restric
 //         input is contracted ONCE and the workgroup stores S tiles; a per-sample input has the sample in the grid.
 //   DGRAD A = gather(g_m), A2 = gather(g_v); B, B2 = the same weights read transposed.  Epilogue: acc + 2 x acc2.
 //   WGRAD A = gather(x), A2 = A^2; B = g_m, B2 = g_v.  Every slab adds its share of the positions of every image set in set order;
-//         both partials to slabs [slab][mean | variance][O][K], k_lrt_conv_wsum adds the slabs and applies d sigma^2 / d rho.
+//         both partials to slabs [slab][mean | variance][O][K], k_lrt_conv_wsum<CHAIN> adds the slabs and applies the posterior's chain factor.
 // The weights (mu_w, sigma_w^2) are fp32 in memory in both modes; the bf16 mode rounds them, like every operand, as they are
 // written to LDS.
 struct LrtConvArgs {
@@ -335,9 +335,12 @@ __global__ __launch_bounds__(C3_THREADS) void k_lrt_conv3d(const Conv3dGeo g, co
     }
 }
 
-// g_mu_w[e] = sum of the mean slabs in slab order, g_rho_w[e] = (sum of the variance slabs) 2 sigma sigmoid(rho_w[e])
-__global__ __launch_bounds__(256) void k_lrt_conv_wsum(const float *__restrict__ slabs, int nslab, const float *__restrict__ rho,
-                                                      float *__restrict__ g_mu, float *__restrict__ g_rho, int64_t n)
+// K11 and K24: g_mean[e] = sum of the mean slabs in slab order, g_par[e] = CHAIN(sum of the variance slabs, par[e]) -- the
+// posterior's chain factor (bnn_device.hpp): ChainRho on rho_w (LocalReparamConvNd), ChainLogSigma2 on log_sigma2
+// (VariationalDropoutConvNd).  The slab sums do not depend on it: g_theta of the one has g_mu_w's bits of the other.
+template <typename CHAIN>
+__global__ __launch_bounds__(256) void k_lrt_conv_wsum(const float *__restrict__ slabs, int nslab, const float *__restrict__ par,
+                                                      float *__restrict__ g_mean, float *__restrict__ g_par, int64_t n)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
@@ -347,30 +350,9 @@ __global__ __launch_bounds__(256) void k_lrt_conv_wsum(const float *__restrict__
         gm += p[0];
         gv += p[n];
     }
-    const float r = rho[e];
-    g_mu[e] = gm;
-    g_rho[e] = gv * (2.0f * sigma_lrt(r) * dsigma_lrt(r));
-}
-
-// K24 (VariationalDropoutConv1d / 2d / 3d): the same slabs, added in the same slab order -- g_theta has k_lrt_conv_wsum's g_mu bits --
-// with the chain of the posterior N(theta, exp(log_sigma2)): g_log_sigma2[e] = (sum of the variance slabs) expf(log_sigma2[e])
-// (one 2-u expf and one product: 3 u + 2 u^2 relative; where expf would be a denormal, the fp64 product rounded once)
-__global__ __launch_bounds__(256) void k_vd_conv_wsum(const float *__restrict__ slabs, int nslab, const float *__restrict__ ls2,
-                                                     float *__restrict__ g_theta, float *__restrict__ g_ls2, int64_t n)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-    float gm = 0.f, gv = 0.f;
-    for (int k = 0; k < nslab; ++k) {
-        const float *p = slabs + (int64_t)k * 2 * n + e;
-        gm += p[0];
-        gv += p[n];
-    }
-    g_theta[e] = gm;
-    // below ln 2^-126 = -87.3 expf(l) is a denormal: its error is a quantum, not 2 u of it, and the product would carry |gv|
-    // quanta.  There the product is formed in fp64 and rounded once, so that the result is within one quantum as well.
-    const float l = ls2[e];
-    g_ls2[e] = l < -87.0f ? (float)((double)gv * exp((double)l)) : gv * expf(l);
+    const float p = par[e];
+    g_mean[e] = gm;
+    g_par[e] = CHAIN::apply(gv, p);
 }
 
 // g_mu_b[o] = sum over (image, position) of g_m, g_rho_b[o] = (the same sum of g_v) 2 sigma_b sigmoid(rho_b): one workgroup per
@@ -799,6 +781,47 @@ static void lrt_conv_launch(const Conv3dGeo &g, const LrtConvArgs &a, int comput
     launch_tile<MODE>(k_lrt_conv3d<uint16_t, MODE>, k_lrt_conv3d<float, MODE>, g, a, compute, nz, st);
 }
 
+// K11 / K24: the weight gradient of a local-reparameterization conv layer -- the checks, the paired slabs, their reduce with the
+// posterior's CHAIN, the bias sums.  par_w: rho_w or log_sigma2; g_mean_w / g_par_w: the gradients of the weight's mean and of par_w.
+template <typename CHAIN>
+static int lrt_conv_backward_weight(const char *who, const float *x, const float *g_m, const float *g_v, const float *par_w,
+                                    float *g_mean_w, float *g_par_w, const float *rho_b, float *g_mu_b, float *g_rho_b,
+                                    const bnn_conv3d_shape_t *shape, int nsets, int compute, void *workspace, int64_t workspace_bytes,
+                                    hipStream_t st)
+{
+    Conv3dGeo g;
+    int rc = conv3d_geo(who, shape, nsets, compute, g);
+    if (rc) return rc;
+    const bool bias = rho_b || g_mu_b || g_rho_b;
+    if (!x || !g_m || !g_v || !par_w || !g_mean_w || !g_par_w || (bias && (!rho_b || !g_mu_b || !g_rho_b))) {
+        set_error("%s: NULL pointer", who);
+        return BNN_E_NULL;
+    }
+    if (misaligned(x, 3) || misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(par_w, 3) || misaligned(g_mean_w, 3) ||
+        misaligned(g_par_w, 3) || misaligned(rho_b, 3) || misaligned(g_mu_b, 3) || misaligned(g_rho_b, 3) || misaligned(workspace, 3)) {
+        set_error("%s: misaligned pointer", who);
+        return BNN_E_ALIGN;
+    }
+    int nslab, chunk;
+    wgrad_split(g, 1, nslab, chunk);           // one image set: every slab walks all of them
+    const int64_t n = (int64_t)g.O * g.K;
+    if (!workspace || workspace_bytes < (int64_t)nslab * 2 * n * (int64_t)sizeof(float)) {
+        set_error("%s: workspace of bnn_conv3d_lrt_backward_weight_workspace_bytes bytes needed", who);
+        return BNN_E_UNSUPPORTED;
+    }
+    LrtConvArgs a{};
+    a.x = x; a.x_ss = (int64_t)g.B * g.C * g.Pin; a.g1 = g_m; a.g2 = g_v; a.out = static_cast<float *>(workspace);
+    a.S = nsets; a.nslab = nslab; a.chunk = chunk;
+    lrt_conv_launch<C3_WGRAD>(g, a, compute, g.groups * nslab, st);
+    if ((rc = check_launch(who))) return rc;
+    hipLaunchKernelGGL(k_lrt_conv_wsum<CHAIN>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                       static_cast<const float *>(workspace), nslab, par_w, g_mean_w, g_par_w, n);
+    if ((rc = check_launch(who)) || !bias) return rc;
+    hipLaunchKernelGGL(k_lrt_conv_bias_grad, dim3((unsigned)g.O), dim3(256), 0, st, g_m, g_v, (int64_t)nsets * g.B, g.O, g.P, rho_b,
+                       g_mu_b, g_rho_b);
+    return check_launch(who);
+}
+
 // K17: the instantiation with the a_v planes for an input that carries a variance
 static void mom_conv_launch(const Conv3dGeo &g, const MomConvArgs &a, int compute, hipStream_t st)
 {
@@ -1052,81 +1075,19 @@ int bnn_conv3d_lrt_backward_weight(const float *x, const float *g_m, const float
                                    const bnn_conv3d_shape_t *shape, int nsets, int compute, void *workspace,
                                    int64_t workspace_bytes, void *stream)
 {
-    const char *who = "bnn_conv3d_lrt_backward_weight";
-    Conv3dGeo g;
-    int rc = conv3d_geo(who, shape, nsets, compute, g);
-    if (rc) return rc;
-    const bool bias = rho_b || g_mu_b || g_rho_b;
-    if (!x || !g_m || !g_v || !rho_w || !g_mu_w || !g_rho_w || (bias && (!rho_b || !g_mu_b || !g_rho_b))) {
-        set_error("%s: NULL pointer", who);
-        return BNN_E_NULL;
-    }
-    if (misaligned(x, 3) || misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(rho_w, 3) || misaligned(g_mu_w, 3) ||
-        misaligned(g_rho_w, 3) || misaligned(rho_b, 3) || misaligned(g_mu_b, 3) || misaligned(g_rho_b, 3) || misaligned(workspace, 3)) {
-        set_error("%s: misaligned pointer", who);
-        return BNN_E_ALIGN;
-    }
-    int nslab, chunk;
-    wgrad_split(g, 1, nslab, chunk);           // one image set: every slab walks all of them
-    const int64_t n = (int64_t)g.O * g.K;
-    if (!workspace || workspace_bytes < (int64_t)nslab * 2 * n * (int64_t)sizeof(float)) {
-        set_error("%s: workspace of bnn_conv3d_lrt_backward_weight_workspace_bytes bytes needed", who);
-        return BNN_E_UNSUPPORTED;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    LrtConvArgs a{};
-    a.x = x; a.x_ss = (int64_t)g.B * g.C * g.Pin; a.g1 = g_m; a.g2 = g_v; a.out = static_cast<float *>(workspace);
-    a.S = nsets; a.nslab = nslab; a.chunk = chunk;
-    lrt_conv_launch<C3_WGRAD>(g, a, compute, g.groups * nslab, st);
-    if ((rc = check_launch(who))) return rc;
-    hipLaunchKernelGGL(k_lrt_conv_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
-                       nslab, rho_w, g_mu_w, g_rho_w, n);
-    if ((rc = check_launch(who)) || !bias) return rc;
-    hipLaunchKernelGGL(k_lrt_conv_bias_grad, dim3((unsigned)g.O), dim3(256), 0, st, g_m, g_v, (int64_t)nsets * g.B, g.O, g.P, rho_b,
-                       g_mu_b, g_rho_b);
-    return check_launch(who);
+    return lrt_conv_backward_weight<ChainRho>("bnn_conv3d_lrt_backward_weight", x, g_m, g_v, rho_w, g_mu_w, g_rho_w, rho_b, g_mu_b,
+                                              g_rho_b, shape, nsets, compute, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-// ---- K24 entry (VariationalDropoutConv1d / 2d / 3d): K11's slab launch and bias launch, k_vd_conv_wsum between them ----------
+// ---- K24 entry (VariationalDropoutConv1d / 2d / 3d): K11's launches, the slab reduce with the chain factor of log_sigma2 --------
 int bnn_conv3d_vd_backward_weight(const float *x, const float *g_m, const float *g_v, const float *log_sigma2, float *g_theta,
                                   float *g_log_sigma2, const float *rho_b, float *g_mu_b, float *g_rho_b,
                                   const bnn_conv3d_shape_t *shape, int nsets, int compute, void *workspace,
                                   int64_t workspace_bytes, void *stream)
 {
-    const char *who = "bnn_conv3d_vd_backward_weight";
-    Conv3dGeo g;
-    int rc = conv3d_geo(who, shape, nsets, compute, g);
-    if (rc) return rc;
-    const bool bias = rho_b || g_mu_b || g_rho_b;
-    if (!x || !g_m || !g_v || !log_sigma2 || !g_theta || !g_log_sigma2 || (bias && (!rho_b || !g_mu_b || !g_rho_b))) {
-        set_error("%s: NULL pointer", who);
-        return BNN_E_NULL;
-    }
-    if (misaligned(x, 3) || misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(log_sigma2, 3) || misaligned(g_theta, 3) ||
-        misaligned(g_log_sigma2, 3) || misaligned(rho_b, 3) || misaligned(g_mu_b, 3) || misaligned(g_rho_b, 3) ||
-        misaligned(workspace, 3)) {
-        set_error("%s: misaligned pointer", who);
-        return BNN_E_ALIGN;
-    }
-    int nslab, chunk;
-    wgrad_split(g, 1, nslab, chunk);           // one image set: every slab walks all of them
-    const int64_t n = (int64_t)g.O * g.K;
-    if (!workspace || workspace_bytes < (int64_t)nslab * 2 * n * (int64_t)sizeof(float)) {
-        set_error("%s: workspace of bnn_conv3d_lrt_backward_weight_workspace_bytes bytes needed", who);
-        return BNN_E_UNSUPPORTED;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    LrtConvArgs a{};
-    a.x = x; a.x_ss = (int64_t)g.B * g.C * g.Pin; a.g1 = g_m; a.g2 = g_v; a.out = static_cast<float *>(workspace);
-    a.S = nsets; a.nslab = nslab; a.chunk = chunk;
-    lrt_conv_launch<C3_WGRAD>(g, a, compute, g.groups * nslab, st);
-    if ((rc = check_launch(who))) return rc;
-    hipLaunchKernelGGL(k_vd_conv_wsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float *>(workspace),
-                       nslab, log_sigma2, g_theta, g_log_sigma2, n);
-    if ((rc = check_launch(who)) || !bias) return rc;
-    hipLaunchKernelGGL(k_lrt_conv_bias_grad, dim3((unsigned)g.O), dim3(256), 0, st, g_m, g_v, (int64_t)nsets * g.B, g.O, g.P, rho_b,
-                       g_mu_b, g_rho_b);
-    return check_launch(who);
+    return lrt_conv_backward_weight<ChainLogSigma2>("bnn_conv3d_vd_backward_weight", x, g_m, g_v, log_sigma2, g_theta, g_log_sigma2,
+                                                    rho_b, g_mu_b, g_rho_b, shape, nsets, compute, workspace, workspace_bytes,
+                                                    (hipStream_t)stream);
 }
 
 // ---- K17 entry (moment propagation through NormalConv / LocalReparamConv 1d / 2d / 3d) ---------------------------------------

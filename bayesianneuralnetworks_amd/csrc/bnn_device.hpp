@@ -367,6 +367,22 @@ __device__ __forceinline__ float dsigma_lrt(float rho)
     return rho > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-rho));
 }
 
+// K10 / K11 / K23 / K24: the chain factor of a posterior's variance plane -- gv, the gradient at sigma^2, times d sigma^2 / d
+// (the parameter behind it).  The ONE thing the weight-gradient epilogues of the local-reparameterization layers (k_lrt's
+// LRT_WGRAD, k_lrt_conv_wsum) differ in between the posteriors; they take it as a template parameter.
+struct ChainRho {               // N(mu, sigma_lrt(rho)^2): 2 sigma sigmoid(rho)
+    __device__ static float apply(float gv, float rho) { return gv * (2.0f * sigma_lrt(rho) * dsigma_lrt(rho)); }
+};
+
+struct ChainLogSigma2 {         // N(theta, exp(l)): exp(l) -- one 2-u expf and one product, 3 u + 2 u^2 relative
+    // below ln 2^-126 = -87.3 expf(l) is a denormal: its error is a quantum, not 2 u of it, and the product would carry |gv|
+    // quanta.  There the product is formed in fp64 and rounded once, so that the result is within one quantum as well.
+    __device__ static float apply(float gv, float l)
+    {
+        return l < -87.0f ? (float)((double)gv * exp((double)l)) : gv * expf(l);
+    }
+};
+
 // fp32 -> bf16 bits, round-to-nearest-even, NaN kept NaN (v_cvt_pk_bf16_f32).
 __device__ __forceinline__ uint16_t f2bf(float v)
 {

@@ -8,7 +8,9 @@
 // or the square of the first:
 //     forward          P = (mu_w, sigma_w^2)        Q = (x, x^2)          y[b][n]   = acc1 + mu_b + sqrt(acc2 + sigma_b^2 + 1e-16) eps
 //     input gradient   P = (mu_w, sigma_w^2)^T      Q = (g_m, g_v)        gx[b][k]  = acc1 + 2 x[b][k] acc2
-//     weight gradient  P = (x, x^2)^T               Q = (g_m, g_v)^T      g_mu[n][k] = acc1,  g_rho[n][k] = acc2 2 sigma sigmoid(rho)
+//     weight gradient  P = (x, x^2)^T               Q = (g_m, g_v)^T      g_mu[n][k] = acc1,  g_rho[n][k] = CHAIN(acc2, rho[n][k])
+// CHAIN is the posterior's chain factor (bnn_device.hpp): ChainRho here, 2 sigma sigmoid(rho); ChainLogSigma2 for K23's posterior
+// N(theta, exp(log_sigma2)) (bnn_vd.hip), whose weight gradient is the same tile, the same host function (lrt_backward_weight).
 // The forward asks for one aligned eps quad per lane, MFMA tile and sample.  BK = 64 (bf16) / 32 (fp32).
 #include "bnn_lrt_tile.hpp"
 
@@ -23,8 +25,8 @@ struct LrtArgs {
     int32_t I, J, C;            // output extents (i: contiguous in memory) and the contraction length
     int32_t x_bf16;             // the activation operand (Q of the forward, P of the weight gradient) is bf16
     void *out;                  // y / gx / g_mu
-    float *out2;                // v (forward, may be NULL) / g_rho
-    const float *e1, *e2;       // forward: mu_b, sigma_b^2 (both or neither); weight gradient: e1 = rho_w
+    float *out2;                // v (forward, may be NULL) / g_rho or g_log_sigma2
+    const float *e1, *e2;       // forward: mu_b, sigma_b^2 (both or neither); weight gradient: e1 = rho_w or log_sigma2
     const void *x;              // input gradient: the layer input (2 x g)
     int64_t ldx;
     int32_t out_bf16;           // forward: y is bf16; input gradient: gx is bf16
@@ -32,8 +34,8 @@ struct LrtArgs {
     RngDev rng;
 };
 
-// T = float (fp32 compute, BK = 32) or uint16_t (bf16 compute, BK = 64)
-template <typename T, int MODE>
+// T = float (fp32 compute, BK = 32) or uint16_t (bf16 compute, BK = 64); CHAIN: the weight gradient's epilogue only
+template <typename T, int MODE, typename CHAIN = ChainRho>
 __global__ __launch_bounds__(kLrtThreads) void k_lrt(const LrtArgs A)
 {
     constexpr bool BF = sizeof(T) == 2;
@@ -110,10 +112,7 @@ __global__ __launch_bounds__(kLrtThreads) void k_lrt(const LrtArgs A)
                 lrt_store4(A.out, A.out_bf16 != 0, o, g, vec, q.ni);
             } else {
                 float g[4];
-                for (int r = 0; r < q.ni; ++r) {
-                    const float rho = A.e1[o + r];
-                    g[r] = r2[r] * (2.0f * sigma_lrt(rho) * dsigma_lrt(rho));
-                }
+                for (int r = 0; r < q.ni; ++r) g[r] = CHAIN::apply(r2[r], A.e1[o + r]);
                 lrt_store4x2(reinterpret_cast<float *>(A.out) + o, r1, A.out2 + o, g, vec, q.ni);
             }
         }
@@ -191,12 +190,12 @@ __global__ __launch_bounds__(256) void k_lrt_bias_grad(const float *__restrict__
     }
 }
 
-template <int MODE>
+template <int MODE, typename CHAIN = ChainRho>
 static int lrt_launch(const char *who, const LrtArgs &A, int compute, unsigned gz, hipStream_t st)
 {
     const dim3 g((unsigned)((A.I + kLrtTile - 1) / kLrtTile), (unsigned)((A.J + kLrtTile - 1) / kLrtTile), gz), b(kLrtThreads);
-    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_lrt<uint16_t, MODE>), g, b, 0, st, A);
-    else hipLaunchKernelGGL((k_lrt<float, MODE>), g, b, 0, st, A);
+    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL((k_lrt<uint16_t, MODE, CHAIN>), g, b, 0, st, A);
+    else hipLaunchKernelGGL((k_lrt<float, MODE, CHAIN>), g, b, 0, st, A);
     return check_launch(who);
 }
 
@@ -206,6 +205,47 @@ int lrt_bias_grad_launch(const char *who, const float *g_m, const float *g_v, in
     hipLaunchKernelGGL(k_lrt_bias_grad, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, st, g_m, g_v, M, (int)N, rho_b, g_mu_b, g_rho_b);
     return check_launch(who);
 }
+
+// The weight gradient of a local-reparameterization dense layer, K10's entry and K23's (bnn_vd.hip): the checks, the LRT_WGRAD
+// tile with the posterior's CHAIN in its epilogue, the bias sums.  par_w: rho_w or log_sigma2; g_mean_w / g_par_w: the gradients of
+// the weight's mean and of par_w.
+template <typename CHAIN>
+int lrt_backward_weight(const char *who, const void *x, int64_t ldx, const float *g_m, const float *g_v, const float *par_w,
+                        float *g_mean_w, float *g_par_w, const float *rho_b, float *g_mu_b, float *g_rho_b, int64_t M, int64_t N,
+                        int64_t K, int compute, int flags, hipStream_t st)
+{
+    const bool bias = rho_b || g_mu_b || g_rho_b;
+    if (!x || !g_m || !g_v || !par_w || !g_mean_w || !g_par_w || (bias && (!rho_b || !g_mu_b || !g_rho_b))) {
+        set_error("%s: NULL pointer", who);
+        return BNN_E_NULL;
+    }
+    if (N < 1 || K < 1 || M < 0 || ldx < K) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
+    if (M > 0x7FFFFFFF || N > (int64_t)kLrtTile * 65535 || K > 0x7FFFFFFF) { set_error("%s: extent outside the supported range", who); return BNN_E_RANGE; }
+    if (compute != BNN_COMPUTE_F32 && compute != BNN_COMPUTE_BF16) { set_error("%s: unknown compute mode", who); return BNN_E_DTYPE; }
+    if ((flags & BNN_FLAG_X_BF16) && compute != BNN_COMPUTE_BF16) {
+        set_error("%s: bf16 activations need the bf16 compute mode", who);
+        return BNN_E_UNSUPPORTED;
+    }
+    if (misaligned(x, (flags & BNN_FLAG_X_BF16) ? 1 : 3) || misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(par_w, 3) ||
+        misaligned(g_mean_w, 15) || misaligned(g_par_w, 15) || misaligned(rho_b, 3) || misaligned(g_mu_b, 3) || misaligned(g_rho_b, 3)) {
+        set_error("%s: misaligned pointer (the two weight gradients: 16 bytes)", who);
+        return BNN_E_ALIGN;
+    }
+    LrtArgs A{};
+    A.p1 = x; A.p2 = nullptr; A.ldp = ldx;
+    A.q1 = g_m; A.q2 = g_v; A.ldq = N;
+    A.I = (int32_t)K; A.J = (int32_t)N; A.C = (int32_t)M;        // M == 0: no k-tile runs, the gradients are stored as zeros
+    A.x_bf16 = (flags & BNN_FLAG_X_BF16) ? 1 : 0;
+    A.out = g_mean_w; A.out2 = g_par_w; A.e1 = par_w;
+    const int rc = lrt_launch<LRT_WGRAD, CHAIN>(who, A, compute, 1u, st);
+    if (rc || !bias) return rc;
+    return lrt_bias_grad_launch(who, g_m, g_v, M, N, rho_b, g_mu_b, g_rho_b, st);
+}
+
+// bnn_vd.hip's (ChainRho's is bnn_lrt_backward_weight's, below)
+template int lrt_backward_weight<ChainLogSigma2>(const char *, const void *, int64_t, const float *, const float *, const float *,
+                                                 float *, float *, const float *, float *, float *, int64_t, int64_t, int64_t, int, int,
+                                                 hipStream_t);
 
 }  // namespace bnn
 
@@ -326,33 +366,8 @@ int bnn_lrt_backward_weight(const void *x, int64_t ldx, const float *g_m, const 
                             float *g_rho_w, const float *rho_b, float *g_mu_b, float *g_rho_b, int64_t M, int64_t N, int64_t K,
                             int compute, int flags, void *stream)
 {
-    const char *who = "bnn_lrt_backward_weight";
-    const bool bias = rho_b || g_mu_b || g_rho_b;
-    if (!x || !g_m || !g_v || !rho_w || !g_mu_w || !g_rho_w || (bias && (!rho_b || !g_mu_b || !g_rho_b))) {
-        set_error("%s: NULL pointer", who);
-        return BNN_E_NULL;
-    }
-    if (N < 1 || K < 1 || M < 0 || ldx < K) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
-    if (M > 0x7FFFFFFF || N > (int64_t)kLrtTile * 65535 || K > 0x7FFFFFFF) { set_error("%s: extent outside the supported range", who); return BNN_E_RANGE; }
-    if (compute != BNN_COMPUTE_F32 && compute != BNN_COMPUTE_BF16) { set_error("%s: unknown compute mode", who); return BNN_E_DTYPE; }
-    if ((flags & BNN_FLAG_X_BF16) && compute != BNN_COMPUTE_BF16) {
-        set_error("%s: bf16 activations need the bf16 compute mode", who);
-        return BNN_E_UNSUPPORTED;
-    }
-    if (misaligned(x, (flags & BNN_FLAG_X_BF16) ? 1 : 3) || misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(rho_w, 3) ||
-        misaligned(g_mu_w, 15) || misaligned(g_rho_w, 15) || misaligned(rho_b, 3) || misaligned(g_mu_b, 3) || misaligned(g_rho_b, 3)) {
-        set_error("%s: misaligned pointer (g_mu_w, g_rho_w: 16 bytes)", who);
-        return BNN_E_ALIGN;
-    }
-    LrtArgs A{};
-    A.p1 = x; A.p2 = nullptr; A.ldp = ldx;
-    A.q1 = g_m; A.q2 = g_v; A.ldq = N;
-    A.I = (int32_t)K; A.J = (int32_t)N; A.C = (int32_t)M;        // M == 0: no k-tile runs, the gradients are stored as zeros
-    A.x_bf16 = (flags & BNN_FLAG_X_BF16) ? 1 : 0;
-    A.out = g_mu_w; A.out2 = g_rho_w; A.e1 = rho_w;
-    int rc = lrt_launch<LRT_WGRAD>(who, A, compute, 1u, (hipStream_t)stream);
-    if (rc || !bias) return rc;
-    return lrt_bias_grad_launch(who, g_m, g_v, M, N, rho_b, g_mu_b, g_rho_b, (hipStream_t)stream);
+    return lrt_backward_weight<ChainRho>("bnn_lrt_backward_weight", x, ldx, g_m, g_v, rho_w, g_mu_w, g_rho_w, rho_b, g_mu_b, g_rho_b,
+                                         M, N, K, compute, flags, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -199,6 +199,13 @@ __device__ __forceinline__ void lrt_mfma_block3(f32x4 (&acc1)[2][2], f32x4 (&acc
 int lrt_bias_grad_launch(const char *who, const float *g_m, const float *g_v, int64_t M, int64_t N, const float *rho_b, float *g_mu_b,
                          float *g_rho_b, hipStream_t st);
 
+// bnn_lrt.hip: the weight gradient of K10 (CHAIN = ChainRho, par_w = rho_w) and K23 (ChainLogSigma2, par_w = log_sigma2) -- every
+// check of the two entries, k_lrt<T, LRT_WGRAD, CHAIN>, the bias sums.  Instantiated there for these two.
+template <typename CHAIN>
+int lrt_backward_weight(const char *who, const void *x, int64_t ldx, const float *g_m, const float *g_v, const float *par_w,
+                        float *g_mean_w, float *g_par_w, const float *rho_b, float *g_mu_b, float *g_rho_b, int64_t M, int64_t N,
+                        int64_t K, int compute, int flags, hipStream_t st);
+
 // Epilogue: MFMA tile (a, b) of a lane holds out[j][i .. i + 3], i = i0 + 32 wi + 16 a + 4 (lane >> 4), j = j0 + 32 wj + 16 b +
 // (lane & 15); ni of the four lie inside I.  false: none does.
 struct LrtQuad { int i, j, ni; };

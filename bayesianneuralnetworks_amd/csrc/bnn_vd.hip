@@ -4,8 +4,8 @@
 // the layer is K10's layer on another variance plane (m = x theta^T + mu_b, v = x^2 s2^T + sigma_b^2, y_s = m + sqrt(v + 1e-16)
 // eps_s; bnn_lrt_forward, bnn_lrt_backward_epilogue, bnn_lrt_backward_input and bnn_moments_forward take s2 unchanged).  New here:
 //     bnn_vd_prepare           s2 (and the bias variance) in one launch; with a threshold the masked planes and their count
-//     bnn_vd_backward_weight   K10's weight-gradient tile, P = (x, x^2)^T, Q = (g_m, g_v)^T, with the epilogue
-//                              g_theta = acc1, g_log_sigma2 = acc2 exp(log_sigma2)
+//     bnn_vd_backward_weight   K10's weight-gradient tile and host function (k_lrt's LRT_WGRAD, lrt_backward_weight) with this
+//                              posterior's chain factor: g_theta = acc1, g_log_sigma2 = acc2 exp(log_sigma2) (ChainLogSigma2)
 //     bnn_vd_kl_forward        sum_e KL_e per tensor, KL_e = k1 sigmoid(-(k2 + k3 log_alpha)) + 0.5 log1p(exp(-log_alpha))
 //     bnn_vd_kl_backward       its gradient in theta and log_sigma2
 // log_alpha and everything derived from it is evaluated in fp64 on the device (as bnn_moments_elu evaluates its moments):
@@ -87,69 +87,6 @@ __global__ __launch_bounds__(256) void k_vd_prepare(const float *__restrict__ th
             if (c) atomicAdd(count_out, (unsigned long long)c);
         }
     }
-}
-
-// ---- weight gradient: k_lrt's LRT_WGRAD tile (bnn_lrt.hip) with this posterior's epilogue.  P = (x, x^2)^T, Q = (g_m, g_v)^T;
-// out[n][k .. k + 3]: g_theta = acc1, g_log_sigma2 = acc2 exp(log_sigma2).  T = float (BK = 32) or uint16_t (bf16 compute, BK = 64).
-struct VdWgradArgs {
-    const void *x;              // (M, K), row pitch ldx; fp32 or bf16
-    const float *g_m, *g_v;     // (M, N)
-    int64_t ldx, ldq;
-    int32_t I, J, C;            // K, N, M
-    int32_t x_bf16;
-    const float *ls2;           // (N, K)
-    float *g_theta, *g_ls2;     // (N, K)
-};
-
-template <typename T>
-__global__ __launch_bounds__(kLrtThreads) void k_vd_wgrad(const VdWgradArgs A)
-{
-    constexpr bool BF = sizeof(T) == 2;
-    constexpr int BK = BF ? 64 : 32;
-    constexpr int LDK = BF ? BK + 8 : BK + 1;
-    constexpr int EPT = BK / 4;
-    __shared__ __attribute__((aligned(16))) T lds[4 * kLrtTile * LDK];
-    T *lp = lds, *lq = lds + 2 * kLrtTile * LDK;
-
-    const int i0 = blockIdx.x * kLrtTile, j0 = blockIdx.y * kLrtTile;
-    const bool p_bf = A.x_bf16 != 0;
-
-    f32x4 acc1[2][2], acc2[2][2];
-    lrt_zero(acc1, acc2);
-    float rp1[EPT], rp2[EPT] = {}, rq1[EPT], rq2[EPT];
-    auto fetch = [&](int c0) {
-        lrt_fetch<true, BK>(rp1, A.x, p_bf, A.ldx, i0, A.I, c0, A.C);
-        lrt_fetch<true, BK>(rq1, A.g_m, false, A.ldq, j0, A.J, c0, A.C);
-        lrt_fetch<true, BK>(rq2, A.g_v, false, A.ldq, j0, A.J, c0, A.C);
-    };
-    fetch(0);
-    for (int c0 = 0; c0 < A.C; c0 += BK) {
-        if constexpr (BF) {
-            lrt_stage2<T, true, true, true, false, 2, BK, LDK>(lp, lq, rp1, rp2, rq1, rq2);
-        } else {
-            lrt_stage<T, true, true, 2, BK, LDK>(lp, rp1, rp2);
-            lrt_stage<T, true, false, 2, BK, LDK>(lq, rq1, rq2);
-        }
-        __syncthreads();
-        if (c0 + BK < A.C) fetch(c0 + BK);
-        lrt_mfma_block<T, 2, BK, LDK>(acc1, acc2, lp, lq);
-        __syncthreads();
-    }
-
-    const bool vec = (A.I & 3) == 0;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            LrtQuad q;
-            if (!lrt_quad(q, a, b, A.I, A.J)) continue;
-            const float r1[4] = {acc1[a][b][0], acc1[a][b][1], acc1[a][b][2], acc1[a][b][3]};
-            const float r2[4] = {acc2[a][b][0], acc2[a][b][1], acc2[a][b][2], acc2[a][b][3]};
-            const int64_t o = (int64_t)q.j * A.I + q.i;
-            float g[4];
-            for (int r = 0; r < q.ni; ++r) g[r] = r2[r] * expf(A.ls2[o + r]);
-            lrt_store4x2(A.g_theta + o, r1, A.g_ls2 + o, g, vec, q.ni);
-        }
 }
 
 // ---- KL: K3's launch pair on this posterior.  First pass: 2048-scalar workgroups, a thread adds eight consecutive elements in index
@@ -296,41 +233,16 @@ int bnn_vd_prepare(const float *theta, const float *log_sigma2, int64_t n_w, con
     return check_launch(who);
 }
 
+// K10's weight gradient with this posterior's chain factor: lrt_backward_weight (bnn_lrt.hip) is the whole entry -- the checks,
+// k_lrt<T, LRT_WGRAD, ChainLogSigma2> and the bias sums; g_theta has bnn_lrt_backward_weight's g_mu_w bits on the same x, g_m, g_v.
+// ChainLogSigma2 (bnn_device.hpp) is the chain factor of K24's slab reduce as well: where log_sigma2 < -87, expf a denormal,
+// g_log_sigma2 is the fp64 product rounded once (this entry multiplied by the denormal expf before it shared that code).
 int bnn_vd_backward_weight(const void *x, int64_t ldx, const float *g_m, const float *g_v, const float *log_sigma2, float *g_theta,
                            float *g_log_sigma2, const float *rho_b, float *g_mu_b, float *g_rho_b, int64_t M, int64_t N, int64_t K,
                            int compute, int flags, void *stream)
 {
-    const char *who = "bnn_vd_backward_weight";
-    const bool bias = rho_b || g_mu_b || g_rho_b;
-    if (!x || !g_m || !g_v || !log_sigma2 || !g_theta || !g_log_sigma2 || (bias && (!rho_b || !g_mu_b || !g_rho_b))) {
-        set_error("%s: NULL pointer", who);
-        return BNN_E_NULL;
-    }
-    if (N < 1 || K < 1 || M < 0 || ldx < K) { set_error("%s: bad extent", who); return BNN_E_SHAPE; }
-    if (M > 0x7FFFFFFF || N > (int64_t)kLrtTile * 65535 || K > 0x7FFFFFFF) { set_error("%s: extent outside the supported range", who); return BNN_E_RANGE; }
-    if (compute != BNN_COMPUTE_F32 && compute != BNN_COMPUTE_BF16) { set_error("%s: unknown compute mode", who); return BNN_E_DTYPE; }
-    if ((flags & BNN_FLAG_X_BF16) && compute != BNN_COMPUTE_BF16) {
-        set_error("%s: bf16 activations need the bf16 compute mode", who);
-        return BNN_E_UNSUPPORTED;
-    }
-    if (misaligned(x, (flags & BNN_FLAG_X_BF16) ? 1 : 3) || misaligned(g_m, 3) || misaligned(g_v, 3) || misaligned(log_sigma2, 3) ||
-        misaligned(g_theta, 15) || misaligned(g_log_sigma2, 15) || misaligned(rho_b, 3) || misaligned(g_mu_b, 3) || misaligned(g_rho_b, 3)) {
-        set_error("%s: misaligned pointer (g_theta, g_log_sigma2: 16 bytes)", who);
-        return BNN_E_ALIGN;
-    }
-    VdWgradArgs A{};
-    A.x = x; A.ldx = ldx;
-    A.g_m = g_m; A.g_v = g_v; A.ldq = N;
-    A.I = (int32_t)K; A.J = (int32_t)N; A.C = (int32_t)M;        // M == 0: no k-tile runs, the gradients are stored as zeros
-    A.x_bf16 = (flags & BNN_FLAG_X_BF16) ? 1 : 0;
-    A.ls2 = log_sigma2; A.g_theta = g_theta; A.g_ls2 = g_log_sigma2;
-    const dim3 g((unsigned)((A.I + kLrtTile - 1) / kLrtTile), (unsigned)((A.J + kLrtTile - 1) / kLrtTile)), b(kLrtThreads);
-    hipStream_t st = (hipStream_t)stream;
-    if (compute == BNN_COMPUTE_BF16) hipLaunchKernelGGL(k_vd_wgrad<uint16_t>, g, b, 0, st, A);
-    else hipLaunchKernelGGL(k_vd_wgrad<float>, g, b, 0, st, A);
-    const int rc = check_launch(who);
-    if (rc || !bias) return rc;
-    return lrt_bias_grad_launch(who, g_m, g_v, M, N, rho_b, g_mu_b, g_rho_b, st);
+    return lrt_backward_weight<ChainLogSigma2>("bnn_vd_backward_weight", x, ldx, g_m, g_v, log_sigma2, g_theta, g_log_sigma2, rho_b,
+                                               g_mu_b, g_rho_b, M, N, K, compute, flags, (hipStream_t)stream);
 }
 
 int64_t bnn_vd_kl_workspace_bytes(const bnn_vd_tensor_t *tensors, int ntensors)

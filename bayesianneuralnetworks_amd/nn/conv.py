@@ -24,7 +24,7 @@ from ..utils import _single, _pair, _triple
 from .container import BayesianModule
 from .core import WeightNormal
 from .dense import (_NormalSampling, _init_normal_posterior, _mc_dropout_plan, _mc_dropout_key, _flipout_plan, _flipout_mc_key,
-                    _lrt_noise_plan, _mc_dropout_forward_moments)
+                    _lrt_noise_plan, _mc_dropout_forward_moments, _LrtNoise, _CONV_WORDING)
 
 
 class BayesianConvNd(BayesianModule):
@@ -203,7 +203,7 @@ class NormalConv3d(NormalConvNd):
         return y.reshape(S * per, *y.shape[2:])
 
 
-class LocalReparamConvNd(_NormalSampling, BayesianConvNd):
+class LocalReparamConvNd(_LrtNoise, _NormalSampling, BayesianConvNd):
     """The local-reparameterization estimator of NormalConvNd's posterior (Kingma, Salimans, Welling 2015; the conv variant of
     LocalReparamLinear).  With independent Gaussian w and b every output element of the convolution is Gaussian, so the layer
     samples IT instead of the weights:
@@ -235,11 +235,7 @@ class LocalReparamConvNd(_NormalSampling, BayesianConvNd):
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, prior):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, False, groups, bias, WeightNormal, prior)
-        from .._rng import new_stream_id
-        self._noise_stream = new_stream_id()        # the layer's own eps stream, beside those of its two posterior tensors
-        self.noise_key = None                       # DrawKey of the last device call
-        self._noise_shape = None                    # one sample's INPUT shape (B, C, *spatial) of that call (it fixes the output's)
-        self._cpu_eps = None
+        self._init_noise()                          # (_noise_shape: one sample's INPUT shape (B, C, *spatial); it fixes the output's)
 
     def reset_parameters(self):
         _init_normal_posterior(self)
@@ -257,30 +253,13 @@ class LocalReparamConvNd(_NormalSampling, BayesianConvNd):
             has_b = self.bias is not None
             m = conv(x, self.weight.mean, self.bias.mean if has_b else None, *geo)
             v = conv(x * x, self.weight.variance, self.bias.variance if has_b else None, *geo)
-            if sample:
-                self._cpu_eps = torch.randn_like(m)
-            elif self._cpu_eps is None or self._cpu_eps.shape != m.shape:
-                raise RuntimeError("sample=False: no noise of shape %s was drawn by an earlier call" % (tuple(m.shape),))
-            return m + torch.sqrt(v + 1e-16) * self._cpu_eps
+            return self._cpu_sample(m, v, sample)
         if x.dim() == self._nd + 1:
             return self.forward(x.unsqueeze(0), sample).squeeze(0)
-        from .._rng import DrawKey, default_generator, generator_for
         S, s0, shared, per = _lrt_noise_plan(x)
         mode = self._compute_mode()
         xs = x if shared else x.reshape(S, per, *x.shape[1:])
-        if sample:
-            self.noise_key = DrawKey(default_generator.seed, self._noise_stream, s0, S, default_generator.next_epoch(),
-                                     gen=generator_for(mode))
-            self._noise_shape = (per,) + tuple(x.shape[1:])
-        key = self.noise_key
-        shape = (per,) + tuple(x.shape[1:])
-        if key is None or self._noise_shape != shape:
-            raise RuntimeError("sample=False: %s noise recorded, this call has %s per sample"
-                               % ("no" if key is None else "an input of %s gave the" % (self._noise_shape,), shape))
-        if key.nsamples != S:
-            if S != 1:
-                raise RuntimeError("sample=False: the recorded noise has %d MC samples, this call needs %d" % (key.nsamples, S))
-            key = key.last_sample()
+        key = self._call_key(sample, (per,) + tuple(x.shape[1:]), S, s0, mode, _CONV_WORDING)
         y = ops.convNd_lrt(xs, self.weight.mean, self.weight.scale,
                            self.bias.mean if self.bias is not None else None,
                            self.bias.scale if self.bias is not None else None, key, shared, *geo, mode)
@@ -305,7 +284,7 @@ LocalReparamConv2d = _local_reparam('LocalReparamConv2d', _pair, torch.nn.functi
 LocalReparamConv3d = _local_reparam('LocalReparamConv3d', _triple, torch.nn.functional.conv3d, 3)
 
 
-class VariationalDropoutConvNd(BayesianConvNd):
+class VariationalDropoutConvNd(_LrtNoise, BayesianConvNd):
     """Sparse variational dropout for convolutions (Molchanov, Ashukha, Vetrov 2017; not a reference name; the conv variant of
     VariationalDropoutLinear): a conv layer that learns which of its weights -- and with them which whole filters -- to drop.
     Every weight has the posterior N(theta, sigma^2) -- `weight` is a WeightVariationalDropout (out, in / groups, *kernel) with
@@ -346,7 +325,6 @@ class VariationalDropoutConvNd(BayesianConvNd):
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, bias_prior, threshold):
         from .core import WeightVariationalDropout
-        from .._rng import new_stream_id
         # the weight's prior is the log-uniform one; BayesianConvNd would build the bias from the weight's class
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, False, groups, False,
                          WeightVariationalDropout, None, bias_prior)
@@ -355,10 +333,7 @@ class VariationalDropoutConvNd(BayesianConvNd):
             self.bias = WeightNormal(out_channels)
             self._reset_bias()
         self.threshold = threshold
-        self._noise_stream = new_stream_id()        # the layer's eps stream
-        self.noise_key = None                       # DrawKey of the last device call
-        self._noise_shape = None                    # one sample's INPUT shape (B, C, *spatial) of that call
-        self._cpu_eps = None
+        self._init_noise()                          # (_noise_shape: one sample's INPUT shape (B, C, *spatial))
 
     def _reset_bias(self):
         fan_in, _ = init._calculate_fan_in_and_fan_out(self.weight.mean)
@@ -441,30 +416,13 @@ class VariationalDropoutConvNd(BayesianConvNd):
                 theta, s2 = theta * keep, s2 * keep
             m = conv(x, theta, mu_b, *geo)
             v = conv(x * x, s2, self.bias.variance if self.bias is not None else None, *geo)
-            if sample:
-                self._cpu_eps = torch.randn_like(m)
-            elif self._cpu_eps is None or self._cpu_eps.shape != m.shape:
-                raise RuntimeError("sample=False: no noise of shape %s was drawn by an earlier call" % (tuple(m.shape),))
-            return m + torch.sqrt(v + 1e-16) * self._cpu_eps
+            return self._cpu_sample(m, v, sample)
         if x.dim() == self._nd + 1:
             return self.forward(x.unsqueeze(0), sample).squeeze(0)
-        from .._rng import DrawKey, default_generator, generator_for
         S, s0, shared, per = _lrt_noise_plan(x)
         mode = self._compute_mode()
         xs = x if shared else x.reshape(S, per, *x.shape[1:])
-        shape = (per,) + tuple(x.shape[1:])
-        if sample:
-            self.noise_key = DrawKey(default_generator.seed, self._noise_stream, s0, S, default_generator.next_epoch(),
-                                     gen=generator_for(mode))
-            self._noise_shape = shape
-        key = self.noise_key
-        if key is None or self._noise_shape != shape:
-            raise RuntimeError("sample=False: %s noise recorded, this call has %s per sample"
-                               % ("no" if key is None else "an input of %s gave the" % (self._noise_shape,), shape))
-        if key.nsamples != S:
-            if S != 1:
-                raise RuntimeError("sample=False: the recorded noise has %d MC samples, this call needs %d" % (key.nsamples, S))
-            key = key.last_sample()
+        key = self._call_key(sample, (per,) + tuple(x.shape[1:]), S, s0, mode, _CONV_WORDING)
         y = ops.convNd_vd(xs, theta, ls2, mu_b, rho_b, key, shared, *geo, mode, threshold=thr)
         return y.reshape(S * per, *y.shape[2:])
 

@@ -22,7 +22,7 @@ from torch.distributions import Normal
 from torch.distributions.multivariate_normal import MultivariateNormal
 
 from .. import _mc, ops
-from .._rng import default_generator, generator_for
+from .._rng import DrawKey, default_generator, generator_for, new_stream_id
 from . import _settings
 from .container import BayesianModule
 from .core import WeightNormal, WeightMultivariateNormal
@@ -310,7 +310,49 @@ def _lrt_noise_plan(x):
                        % (x.shape[0], ctx.base_batch, ctx.base_batch * ctx.samples))
 
 
-class LocalReparamLinear(_NormalSampling, BayesianLinear):
+_DENSE_WORDING = ("a %s", "needs")                          # sample=False on another shape: the dense layers' words, the convs'
+_CONV_WORDING = ("an input of %s gave the", "has")
+
+
+class _LrtNoise:
+    """The noise state of a local-reparameterization layer (LocalReparamLinear / ConvNd, VariationalDropoutLinear / ConvNd): the
+    layer's own eps stream, the DrawKey of its last device call with what one sample of that call looked like, the eps of its
+    last CPU call."""
+
+    def _init_noise(self):
+        self._noise_stream = new_stream_id()        # the layer's own eps stream, beside those of its posterior tensors
+        self.noise_key = None                       # DrawKey of the last device call
+        self._noise_shape = None                    # one sample of that call: dense (rows, out_features), conv the INPUT's shape
+        self._cpu_eps = None
+
+    def _call_key(self, sample, shape, S, sample0, mode, wording):
+        """-> the DrawKey of a device call of S samples from sample0 on, `shape` per sample: a fresh one, recorded (sample), or the
+        recorded one (sample=False; its last sample where a single pass follows an S-sample call).  wording: how the layer words
+        a shape that does not match, (the recorded one, the verb of this call's)."""
+        if sample:
+            self.noise_key = DrawKey(default_generator.seed, self._noise_stream, sample0, S, default_generator.next_epoch(),
+                                     gen=generator_for(mode))
+            self._noise_shape = shape
+        key = self.noise_key
+        if key is None or self._noise_shape != shape:
+            raise RuntimeError("sample=False: %s noise recorded, this call %s %s per sample"
+                               % ("no" if key is None else wording[0] % (self._noise_shape,), wording[1], shape))
+        if key.nsamples != S:
+            if S != 1:
+                raise RuntimeError("sample=False: the recorded noise has %d MC samples, this call needs %d" % (key.nsamples, S))
+            key = key.last_sample()
+        return key
+
+    def _cpu_sample(self, m, v, sample):
+        """m + sqrt(v + 1e-16) eps on CPU tensors: eps drawn here (sample) or the last call's."""
+        if sample:
+            self._cpu_eps = torch.randn_like(m)
+        elif self._cpu_eps is None or self._cpu_eps.shape != m.shape:
+            raise RuntimeError("sample=False: no noise of shape %s was drawn by an earlier call" % (tuple(m.shape),))
+        return m + torch.sqrt(v + 1e-16) * self._cpu_eps
+
+
+class LocalReparamLinear(_LrtNoise, _NormalSampling, BayesianLinear):
     """The local-reparameterization estimator of NormalLinear's posterior (Kingma, Salimans, Welling 2015): with independent
     Gaussian w and b the pre-activation is Gaussian per output element, so the layer samples IT instead of the weights:
 
@@ -338,11 +380,7 @@ class LocalReparamLinear(_NormalSampling, BayesianLinear):
 
     def __init__(self, in_features, out_features, bias=True, prior=Normal(0, .1)):
         super().__init__(in_features, out_features, bias, WeightNormal, prior)
-        from .._rng import new_stream_id
-        self._noise_stream = new_stream_id()        # the layer's own eps stream, beside those of its two posterior tensors
-        self.noise_key = None                       # DrawKey of the last device call
-        self._noise_shape = None                    # (rows per sample, out_features) of that call
-        self._cpu_eps = None
+        self._init_noise()
 
     def reset_parameters(self):
         _init_normal_posterior(self)
@@ -357,33 +395,16 @@ class LocalReparamLinear(_NormalSampling, BayesianLinear):
         if not x.is_cuda:
             m = torch.nn.functional.linear(x, self.weight.mean, self.bias.mean if self.bias is not None else None)
             v = torch.nn.functional.linear(x * x, self.weight.variance, self.bias.variance if self.bias is not None else None)
-            if sample:
-                self._cpu_eps = torch.randn_like(m)
-            elif self._cpu_eps is None or self._cpu_eps.shape != m.shape:
-                raise RuntimeError("sample=False: no noise of shape %s was drawn by an earlier call" % (tuple(m.shape),))
-            return m + torch.sqrt(v + 1e-16) * self._cpu_eps
+            return self._cpu_sample(m, v, sample)
         if x.dim() == 1:
             return self.forward(x.unsqueeze(0), sample).squeeze(0)
-        from .._rng import DrawKey
         S, s0, shared, per = self._noise_plan(x)
         mode = self._compute_mode()
         lead = x.shape[1:-1]
         K = x.shape[-1]
         N = self.weight.mean.shape[0]
         x2 = x.reshape(-1, K) if shared else x.reshape(S, -1, K)
-        shape = (x2.shape[-2], N)
-        if sample:
-            self.noise_key = DrawKey(default_generator.seed, self._noise_stream, s0, S, default_generator.next_epoch(),
-                                     gen=generator_for(mode))
-            self._noise_shape = shape
-        key = self.noise_key
-        if key is None or self._noise_shape != shape:
-            raise RuntimeError("sample=False: %s noise recorded, this call needs %s per sample"
-                               % ("no" if key is None else "a %s" % (self._noise_shape,), shape))
-        if key.nsamples != S:
-            if S != 1:
-                raise RuntimeError("sample=False: the recorded noise has %d MC samples, this call needs %d" % (key.nsamples, S))
-            key = key.last_sample()
+        key = self._call_key(sample, (x2.shape[-2], N), S, s0, mode, _DENSE_WORDING)
         odt = torch.bfloat16 if (self.out_dtype == torch.bfloat16 and mode == "bf16") else torch.float32
         y = ops.linear_lrt(x2, self.weight.mean, self.weight.scale,
                            self.bias.mean if self.bias is not None else None,
@@ -391,7 +412,7 @@ class LocalReparamLinear(_NormalSampling, BayesianLinear):
         return y.reshape(S * per, *lead, N)
 
 
-class VariationalDropoutLinear(BayesianLinear):
+class VariationalDropoutLinear(_LrtNoise, BayesianLinear):
     """Sparse variational dropout (Molchanov, Ashukha, Vetrov 2017; not a reference name): a dense layer that learns which of its
     weights to drop.  Every weight has the posterior N(theta, sigma^2) -- `weight` is a WeightVariationalDropout with Parameters
     mean (theta) and log_sigma2 -- and a log-uniform prior; the pre-activation is sampled by local reparameterization,
@@ -426,17 +447,13 @@ class VariationalDropoutLinear(BayesianLinear):
     def __init__(self, in_features, out_features, bias=True, bias_prior=Normal(0, .1), threshold=None):
         BayesianModule.__init__(self, in_features, out_features, None, bias_prior)     # the weight's prior is the log-uniform one
         from .core import WeightVariationalDropout
-        from .._rng import new_stream_id
         self.weight = WeightVariationalDropout(out_features, in_features)
         if bias:
             self.bias = WeightNormal(out_features)
         else:
             self.register_parameter('bias', None)
         self.threshold = threshold
-        self._noise_stream = new_stream_id()        # the layer's eps stream
-        self.noise_key = None                       # DrawKey of the last device call
-        self._noise_shape = None                    # (rows per sample, out_features) of that call
-        self._cpu_eps = None
+        self._init_noise()
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -504,33 +521,16 @@ class VariationalDropoutLinear(BayesianLinear):
                 theta, s2 = theta * keep, s2 * keep
             m = torch.nn.functional.linear(x, theta, mu_b)
             v = torch.nn.functional.linear(x * x, s2, self.bias.variance if self.bias is not None else None)
-            if sample:
-                self._cpu_eps = torch.randn_like(m)
-            elif self._cpu_eps is None or self._cpu_eps.shape != m.shape:
-                raise RuntimeError("sample=False: no noise of shape %s was drawn by an earlier call" % (tuple(m.shape),))
-            return m + torch.sqrt(v + 1e-16) * self._cpu_eps
+            return self._cpu_sample(m, v, sample)
         if x.dim() == 1:
             return self.forward(x.unsqueeze(0), sample).squeeze(0)
-        from .._rng import DrawKey
         S, s0, shared, per = _lrt_noise_plan(x)
         mode = self._compute_mode()
         lead = x.shape[1:-1]
         K = x.shape[-1]
         N = theta.shape[0]
         x2 = x.reshape(-1, K) if shared else x.reshape(S, -1, K)
-        shape = (x2.shape[-2], N)
-        if sample:
-            self.noise_key = DrawKey(default_generator.seed, self._noise_stream, s0, S, default_generator.next_epoch(),
-                                     gen=generator_for(mode))
-            self._noise_shape = shape
-        key = self.noise_key
-        if key is None or self._noise_shape != shape:
-            raise RuntimeError("sample=False: %s noise recorded, this call needs %s per sample"
-                               % ("no" if key is None else "a %s" % (self._noise_shape,), shape))
-        if key.nsamples != S:
-            if S != 1:
-                raise RuntimeError("sample=False: the recorded noise has %d MC samples, this call needs %d" % (key.nsamples, S))
-            key = key.last_sample()
+        key = self._call_key(sample, (x2.shape[-2], N), S, s0, mode, _DENSE_WORDING)
         odt = torch.bfloat16 if (self.out_dtype == torch.bfloat16 and mode == "bf16") else torch.float32
         y = ops.linear_vd(x2, theta, ls2, mu_b, rho_b, key, shared, mode, out_dtype=odt, threshold=thr)
         return y.reshape(S * per, *lead, N)

@@ -865,8 +865,9 @@ def _lrt_prepare_raw(rho_w, rho_b):
     return s2_w, s2_b
 
 
-def _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b):
-    """The four posterior tensors of a K10 / K16 dense call: fp32, contiguous, on the device."""
+def _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b, conv=False):
+    """The four posterior tensors of a K10 / K11 / K16 call: fp32, contiguous, on the device (conv: the weight's shape is the
+    geometry's to check)."""
     require_cuda_f32(mu_w, "weight.mean")
     require_cuda_f32(rho_w, "weight.scale")
     if mu_b is not None:
@@ -874,46 +875,70 @@ def _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b):
         require_cuda_f32(rho_b, "bias.scale")
 
 
+# What a local-reparameterization call needs to know of its weight posterior (the bias is Gaussian in both): two instances,
+# _GAUSSIAN here (N(mu, sigma(rho)^2): LocalReparamLinear / ConvNd) and _LOG_SIGMA2 at K23 (N(theta, exp(log_sigma2)):
+# VariationalDropoutLinear / ConvNd).
+#   name                 the error prefix: linear_<name>, conv_<name>
+#   prepare              (mean, par, rho_b, threshold) -> (mean plane, s2_w, s2_b): the operand launch
+#   check                (mean, par, mu_b, rho_b, conv): dtype, layout and shape of the posterior tensors
+#   wgrad, conv_wgrad    the weight-gradient entries of the dense and the conv layer, (x, g_m, g_v, par) -> (g_mean, g_par, bias)
+_LrtPosterior = collections.namedtuple("_LrtPosterior", ("name", "prepare", "check", "wgrad", "conv_wgrad"))
+
+_GAUSSIAN = _LrtPosterior("lrt", lambda mu_w, rho_w, rho_b, threshold: (mu_w,) + _lrt_prepare_raw(rho_w, rho_b), _lrt_check_posterior,
+                          "bnn_lrt_backward_weight", "bnn_conv3d_lrt_backward_weight")
+
+
+def _lrt_refuse_masked_grad(who, ctx, track, threshold):
+    if track and threshold is not None and any(ctx.needs_input_grad[1:5]):
+        raise BnnHipError("%s: a threshold is set (%r) and a posterior tensor requires a gradient: the mask is for "
+                          "inference" % (who, threshold))
+
+
 class _LrtLinear(torch.autograd.Function):
-    """y_s = m + sqrt(v + 1e-16) eps_s, m = x mu_w^T + mu_b, v = x^2 (sigma_w^2)^T + sigma_b^2 (LocalReparamLinear): one
-    operand launch + one contraction launch for all S samples.  Backward: eps re-created from the key in one elementwise launch
-    (g_m, g_v from the saved v), then the paired input- and weight-gradient contractions (csrc/bnn_lrt.hip) -- no torch matmul."""
+    """y_s = m + sqrt(v + 1e-16) eps_s, m = x mean_w^T + mu_b, v = x^2 (s2_w)^T + sigma_b^2 (LocalReparamLinear,
+    VariationalDropoutLinear): the posterior's operand launch (post.prepare: s2_w, sigma_b^2, with a threshold the masked planes)
+    + one contraction launch for all S samples.  Backward: eps re-created from the key in one elementwise launch (g_m, g_v from
+    the saved v), then the paired input- and weight-gradient contractions (csrc/bnn_lrt.hip; post.wgrad) -- no torch matmul."""
 
     @staticmethod
-    def forward(ctx, x, mu_w, rho_w, mu_b, rho_b, key, shared_x, compute, out_dtype, track):
+    def forward(ctx, x, mean_w, par_w, mu_b, rho_b, key, shared_x, compute, out_dtype, track, post, threshold):
         # x: (B, K) shared by all samples, or (S, B, K); fp32 or (bf16 compute mode) bf16
+        who = "linear_" + post.name
         x = x.contiguous()
         require_cuda_act(x, "x")
         if (x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16) and compute != _lib.COMPUTE_BF16:
             raise BnnHipError("bf16 activations need compute mode 'bf16'")
-        _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b)
+        post.check(mean_w, par_w, mu_b, rho_b)
         S = key.nsamples
         B, K = x.shape[-2], x.shape[-1]
-        N = mu_w.shape[0]
+        N = mean_w.shape[0]
         if not shared_x and (x.dim() != 3 or x.shape[0] != S):
-            raise BnnHipError("linear_lrt: a per-sample input must be (S, B, K) with S = %d, got %s" % (S, tuple(x.shape)))
-        why = lrt_eligible(x, mu_w, B, S)
+            raise BnnHipError("%s: a per-sample input must be (S, B, K) with S = %d, got %s" % (who, S, tuple(x.shape)))
+        why = lrt_eligible(x, mean_w, B, S)
         if why is not None:
-            raise BnnHipError("linear_lrt: " + why)
+            raise BnnHipError(who + ": " + why)
         dev = x.device
         needs_grad = track and any(ctx.needs_input_grad[:5])
-        s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
+        _lrt_refuse_masked_grad(who, ctx, track, threshold)
+        mean, s2_w, s2_b = post.prepare(mean_w, par_w, rho_b if mu_b is not None else None, threshold)
         y = torch.empty((S, B, N), dtype=out_dtype, device=dev)
         v = torch.empty((B, N) if shared_x else (S, B, N), dtype=torch.float32, device=dev) if needs_grad else None
         flags = (_lib.FLAG_X_BF16 if _bf(x) else 0) | (_lib.FLAG_Y_BF16 if out_dtype == torch.bfloat16 else 0)
         r = _rng_struct(key, dev)
-        check(_lib.load().bnn_lrt_forward(ptr(x), K, ptr(mu_w), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(y), ptr(v), B, N, K, S,
+        check(_lib.load().bnn_lrt_forward(ptr(x), K, ptr(mean), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(y), ptr(v), B, N, K, S,
                                           1 if shared_x else 0, ctypes.byref(r), compute, flags, stream_ptr(dev)), "bnn_lrt_forward")
         if needs_grad:
-            ctx.save_for_backward(x, mu_w, rho_w, rho_b if mu_b is not None else None, s2_w, v)
-        ctx.key, ctx.shared_x, ctx.compute = key, shared_x, compute
+            # (mean: with a threshold the masked plane -- then only the input's gradient is ever asked for, through the masked layer)
+            ctx.save_for_backward(x, mean, par_w, rho_b if mu_b is not None else None, s2_w, v)
+        ctx.post, ctx.key, ctx.shared_x, ctx.compute = post, key, shared_x, compute
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, mu_w, rho_w, rho_b, s2_w, v = ctx.saved_tensors
+        x, mean_w, par_w, rho_b, s2_w, v = ctx.saved_tensors
         S, compute, shared = ctx.key.nsamples, ctx.compute, ctx.shared_x
-        N, K = mu_w.shape
+        need = ctx.needs_input_grad
+        N, K = mean_w.shape
         B = x.shape[-2]
         M = B if shared else S * B
         dev = gy.device
@@ -927,28 +952,33 @@ class _LrtLinear(torch.autograd.Function):
         check(lib.bnn_lrt_backward_epilogue(ptr(gy), ptr(v), ptr(g_m), ptr(g_v), B, N, S, 1 if shared else 0, ctypes.byref(r),
                                             _lib.FLAG_X_BF16 if _bf(gy) else 0, stream_ptr(dev)), "bnn_lrt_backward_epilogue")
         xflag = _lib.FLAG_X_BF16 if _bf(x) else 0
-        gx = g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
-        if ctx.needs_input_grad[0]:
+        gx = g_mean_w = g_par_w = g_mu_b = g_rho_b = None
+        if need[0]:
             gx = torch.empty_like(x)
-            check(lib.bnn_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(mu_w), ptr(s2_w), ptr(x), K, ptr(gx), M, N, K, compute,
+            check(lib.bnn_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(mean_w), ptr(s2_w), ptr(x), K, ptr(gx), M, N, K, compute,
                                              xflag | (_lib.FLAG_Y_BF16 if _bf(x) else 0), stream_ptr(dev)), "bnn_lrt_backward_input")
-        need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or need_b:
-            g_mu_w, g_rho_w = torch.empty_like(mu_w), torch.empty_like(rho_w)
+        need_b = rho_b is not None and (need[3] or need[4])
+        if need[1] or need[2] or need_b:
+            g_mean_w, g_par_w = torch.empty_like(mean_w), torch.empty_like(par_w)
             if need_b:
                 g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
-            check(lib.bnn_lrt_backward_weight(ptr(x), K, ptr(g_m), ptr(g_v), ptr(rho_w), ptr(g_mu_w), ptr(g_rho_w),
-                                              ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), M, N, K, compute, xflag,
-                                              stream_ptr(dev)), "bnn_lrt_backward_weight")
-        return gx, g_mu_w, g_rho_w, g_mu_b, g_rho_b, None, None, None, None, None
+            check(getattr(lib, ctx.post.wgrad)(ptr(x), K, ptr(g_m), ptr(g_v), ptr(par_w), ptr(g_mean_w), ptr(g_par_w),
+                                               ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), M, N, K, compute, xflag,
+                                               stream_ptr(dev)), ctx.post.wgrad)
+        return gx, g_mean_w, g_par_w, g_mu_b, g_rho_b, None, None, None, None, None, None, None
+
+
+def _linear_lrt(post, x, mean_w, par_w, mu_b, rho_b, key, shared_x, compute, out_dtype, threshold=None):
+    return _LrtLinear.apply(x, mean_w.contiguous(), par_w.contiguous(),
+                            None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
+                            key, shared_x, _compute_code(compute), out_dtype, torch.is_grad_enabled(), post,
+                            None if threshold is None else float(threshold))
 
 
 def linear_lrt(x, mu_w, rho_w, mu_b, rho_b, key, shared_x, compute="f32", out_dtype=torch.float32):
     """LocalReparamLinear on the device: -> (S, B, N), S = key.nsamples; sample s uses eps[b N + n] of the key's sample
     sample0 + s.  Raises BnnHipError (with lrt_eligible's reason) for a call the kernel refuses: no torch fallback."""
-    return _LrtLinear.apply(x, mu_w.contiguous(), rho_w.contiguous(),
-                            None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
-                            key, shared_x, _compute_code(compute), out_dtype, torch.is_grad_enabled())
+    return _linear_lrt(_GAUSSIAN, x, mu_w, rho_w, mu_b, rho_b, key, shared_x, compute, out_dtype)
 
 
 # --------------------------------------------------------------------------- K16: moment propagation (sampling-free inference)
@@ -1142,41 +1172,47 @@ def moments_linear(a, mu_w, rho_w, mu_b, rho_b, relu=False, compute="f32", track
     only).  Nothing is drawn, no key is touched.  track=False (inference): the result is detached whatever the grad mode.
     track=True with grad mode on (training without sampling, K18): the result is attached to the graph of `a` and the four
     posterior tensors; the backward is HIP (csrc/bnn_moments_bwd.hip; K10's launches for a deterministic input); `a` is fp32."""
-    mom = _as_moments(a, "moments_linear")
+    return _moments_linear("moments_linear", _GAUSSIAN, a, mu_w, rho_w, mu_b, rho_b, relu, compute, track)
+
+
+def _moments_linear(who, post, a, mu_w, par_w, mu_b, rho_b, relu, compute, track, threshold=None):
+    """moments_linear / moments_linear_vd: the input's preparation, the checks and the untracked launch on the planes of
+    post.prepare; track (the Gaussian posterior only) hands over to _MomentsLinear."""
+    mom = _as_moments(a, who)
     code = _compute_code(compute)
     tracked = _tracking(track)
     keep = (lambda t: t) if tracked else (lambda t: t.detach())
     am = keep(mom.mean)
     av = None if mom.var is None else keep(mom.var)
-    mu_w, rho_w = keep(mu_w).contiguous(), keep(rho_w).contiguous()
+    mu_w, par_w = keep(mu_w).contiguous(), keep(par_w).contiguous()
     if mu_b is not None:
         mu_b, rho_b = keep(mu_b).contiguous(), keep(rho_b).contiguous()
-    _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b)
+    post.check(mu_w, par_w, mu_b, rho_b)
     N, K = mu_w.shape
     if am.dim() < 1 or am.shape[-1] != K:
-        raise BnnHipError("moments_linear: input has %s features, weight expects %d" % (am.shape[-1] if am.dim() else "no", K))
+        raise BnnHipError("%s: input has %s features, weight expects %d" % (who, am.shape[-1] if am.dim() else "no", K))
     lead = tuple(am.shape[:-1])
     am = am.reshape(-1, K).contiguous()
     require_cuda_act(am, "a.mean")
     if am.dtype == torch.bfloat16 and (code != _lib.COMPUTE_BF16 or av is not None):
-        raise BnnHipError("moments_linear: a bf16 input needs compute mode 'bf16' and no variance (hidden moments are fp32)")
+        raise BnnHipError("%s: a bf16 input needs compute mode 'bf16' and no variance (hidden moments are fp32)" % who)
     if av is not None:
         av = av.reshape(-1, K).contiguous()
         require_cuda_f32(av, "a.var")
     B = am.shape[0]
     if B > 64 * 65535:
-        raise BnnHipError("moments_linear: %d rows (at most %d)" % (B, 64 * 65535))
+        raise BnnHipError("%s: %d rows (at most %d)" % (who, B, 64 * 65535))
     if tracked:
         # the same launches' bits, the ReLU as bnn_moments_relu behind the contraction instead of in its epilogue (one device
         # function): the backward needs the pre-activation
         if _bf(am):
-            raise BnnHipError("moments_linear: track=True takes an fp32 input")
-        m, v = _MomentsLinear.apply(am, av, mu_w, rho_w, mu_b, rho_b, code)
+            raise BnnHipError("%s: track=True takes an fp32 input" % who)
+        m, v = _MomentsLinear.apply(am, av, mu_w, par_w, mu_b, rho_b, code)
         if relu:
             m, v = _MomentsRelu.apply(m, v)
         return Moments(m.reshape(lead + (N,)), v.reshape(lead + (N,)))
     dev = am.device
-    s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
+    mu_w, s2_w, s2_b = post.prepare(mu_w, par_w, rho_b if mu_b is not None else None, threshold)
     out_m = torch.empty((B, N), dtype=torch.float32, device=dev)
     out_v = torch.empty((B, N), dtype=torch.float32, device=dev)
     flags = (_lib.FLAG_RELU if relu else 0) | (_lib.FLAG_X_BF16 if _bf(am) else 0)
@@ -1307,16 +1343,24 @@ def moments_relu_backward_f64(mom, g_mean, g_var):
 
 def moments_linear_f64(a, mu_w, rho_w, mu_b, rho_b, relu=False, track=False):
     """moments_linear in float64 torch (sigma = 1e-10 + softplus(rho)) -> Moments of float64 tensors.  track=True: not detached."""
-    mom = _as_moments(a, "moments_linear_f64")
     f64 = _f64(track)
-    sig2 = lambda rho: (1e-10 + torch.nn.functional.softplus(f64(rho))) ** 2         # noqa: E731
-    am, mu, s2 = f64(mom.mean), f64(mu_w), sig2(rho_w)
+    return _moments_linear_planes_f64(_as_moments(a, "moments_linear_f64"), f64(mu_w), _sigma2_f64(f64(rho_w)), mu_b, rho_b, relu, track)
+
+
+def _sigma2_f64(rho):
+    return (1e-10 + torch.nn.functional.softplus(rho)) ** 2
+
+
+def _moments_linear_planes_f64(mom, mu, s2, mu_b, rho_b, relu, track):
+    """The dense moment layer in float64 on the weight's mean and variance planes (float64 already); the bias is Gaussian."""
+    f64 = _f64(track)
+    am = f64(mom.mean)
     m = am @ mu.t()
     v = (am * am) @ s2.t()
     if mom.var is not None:
         v = v + f64(mom.var) @ (mu * mu + s2).t()
     if mu_b is not None:
-        m, v = m + f64(mu_b), v + sig2(rho_b)
+        m, v = m + f64(mu_b), v + _sigma2_f64(f64(rho_b))
     out = Moments(m, v)
     return moments_relu_f64(out, track) if relu else out
 
@@ -1387,75 +1431,8 @@ def _vd_refuse_masked_grad(who, threshold, *posterior):
                           "run under torch.no_grad(), or set layer.threshold = None to train" % (who, threshold))
 
 
-class _VdLinear(torch.autograd.Function):
-    """_LrtLinear on the posterior N(theta, exp(log_sigma2)) (VariationalDropoutLinear): bnn_vd_prepare + bnn_lrt_forward; backward
-    bnn_lrt_backward_epilogue, bnn_lrt_backward_input and bnn_vd_backward_weight (csrc/bnn_vd.hip) -- no torch matmul."""
-
-    @staticmethod
-    def forward(ctx, x, theta, ls2, mu_b, rho_b, key, shared_x, compute, out_dtype, track, threshold):
-        x = x.contiguous()
-        require_cuda_act(x, "x")
-        if (x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16) and compute != _lib.COMPUTE_BF16:
-            raise BnnHipError("bf16 activations need compute mode 'bf16'")
-        _vd_check_posterior(theta, ls2, mu_b, rho_b)
-        S = key.nsamples
-        B, K = x.shape[-2], x.shape[-1]
-        N = theta.shape[0]
-        if not shared_x and (x.dim() != 3 or x.shape[0] != S):
-            raise BnnHipError("linear_vd: a per-sample input must be (S, B, K) with S = %d, got %s" % (S, tuple(x.shape)))
-        why = lrt_eligible(x, theta, B, S)
-        if why is not None:
-            raise BnnHipError("linear_vd: " + why)
-        dev = x.device
-        needs_grad = track and any(ctx.needs_input_grad[:5])
-        if track and threshold is not None and any(ctx.needs_input_grad[1:5]):
-            raise BnnHipError("linear_vd: a threshold is set (%r) and a posterior tensor requires a gradient: the mask is for "
-                              "inference" % (threshold,))
-        th, s2_w, s2_b, _ = _vd_prepare_raw(theta, ls2, rho_b if mu_b is not None else None, threshold)
-        y = torch.empty((S, B, N), dtype=out_dtype, device=dev)
-        v = torch.empty((B, N) if shared_x else (S, B, N), dtype=torch.float32, device=dev) if needs_grad else None
-        flags = (_lib.FLAG_X_BF16 if _bf(x) else 0) | (_lib.FLAG_Y_BF16 if out_dtype == torch.bfloat16 else 0)
-        r = _rng_struct(key, dev)
-        check(_lib.load().bnn_lrt_forward(ptr(x), K, ptr(th), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(y), ptr(v), B, N, K, S,
-                                          1 if shared_x else 0, ctypes.byref(r), compute, flags, stream_ptr(dev)), "bnn_lrt_forward")
-        if needs_grad:
-            # (th: with a threshold the masked plane -- then only the input's gradient is ever asked for, through the masked layer)
-            ctx.save_for_backward(x, th, ls2, rho_b if mu_b is not None else None, s2_w, v)
-        ctx.key, ctx.shared_x, ctx.compute = key, shared_x, compute
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, theta, ls2, rho_b, s2_w, v = ctx.saved_tensors
-        S, compute, shared = ctx.key.nsamples, ctx.compute, ctx.shared_x
-        N, K = theta.shape
-        B = x.shape[-2]
-        M = B if shared else S * B
-        dev = gy.device
-        lib = _lib.load()
-        gy = gy.contiguous()
-        if compute != _lib.COMPUTE_BF16 and gy.dtype != torch.float32:
-            gy = gy.float()
-        g_m = torch.empty((M, N), dtype=torch.float32, device=dev)
-        g_v = torch.empty((M, N), dtype=torch.float32, device=dev)
-        r = _rng_struct(ctx.key, dev)
-        check(lib.bnn_lrt_backward_epilogue(ptr(gy), ptr(v), ptr(g_m), ptr(g_v), B, N, S, 1 if shared else 0, ctypes.byref(r),
-                                            _lib.FLAG_X_BF16 if _bf(gy) else 0, stream_ptr(dev)), "bnn_lrt_backward_epilogue")
-        xflag = _lib.FLAG_X_BF16 if _bf(x) else 0
-        gx = g_theta = g_ls2 = g_mu_b = g_rho_b = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            check(lib.bnn_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(theta), ptr(s2_w), ptr(x), K, ptr(gx), M, N, K, compute,
-                                             xflag | (_lib.FLAG_Y_BF16 if _bf(x) else 0), stream_ptr(dev)), "bnn_lrt_backward_input")
-        need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or need_b:
-            g_theta, g_ls2 = torch.empty_like(theta), torch.empty_like(ls2)
-            if need_b:
-                g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
-            check(lib.bnn_vd_backward_weight(ptr(x), K, ptr(g_m), ptr(g_v), ptr(ls2), ptr(g_theta), ptr(g_ls2),
-                                             ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), M, N, K, compute, xflag,
-                                             stream_ptr(dev)), "bnn_vd_backward_weight")
-        return gx, g_theta, g_ls2, g_mu_b, g_rho_b, None, None, None, None, None, None
+_LOG_SIGMA2 = _LrtPosterior("vd", lambda theta, ls2, rho_b, threshold: _vd_prepare_raw(theta, ls2, rho_b, threshold)[:3],
+                            _vd_check_posterior, "bnn_vd_backward_weight", "bnn_conv3d_vd_backward_weight")
 
 
 def linear_vd(x, theta, log_sigma2, mu_b, rho_b, key, shared_x, compute="f32", out_dtype=torch.float32, threshold=None):
@@ -1465,10 +1442,7 @@ def linear_vd(x, theta, log_sigma2, mu_b, rho_b, key, shared_x, compute="f32", o
     planes) -- inference only: a call that would need a gradient of a posterior tensor raises BnnHipError.  Calls the kernel
     refuses raise BnnHipError (lrt_eligible's reason): no torch fallback."""
     _vd_refuse_masked_grad("linear_vd", threshold, theta, log_sigma2, mu_b, rho_b)
-    return _VdLinear.apply(x, theta.contiguous(), log_sigma2.contiguous(),
-                           None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
-                           key, shared_x, _compute_code(compute), out_dtype, torch.is_grad_enabled(),
-                           None if threshold is None else float(threshold))
+    return _linear_lrt(_LOG_SIGMA2, x, theta, log_sigma2, mu_b, rho_b, key, shared_x, compute, out_dtype, threshold)
 
 
 def vd_dropped(theta, log_sigma2, threshold):
@@ -1495,55 +1469,23 @@ def vd_dropped_mask(theta, log_sigma2, threshold):
 def moments_linear_vd(a, theta, log_sigma2, mu_b, rho_b, relu=False, compute="f32", threshold=None):
     """moments_linear for a VariationalDropoutLinear: the same launch (bnn_moments_forward) on the variance plane
     exp(log_sigma2), masked by `threshold` as linear_vd masks it (bnn_vd_prepare) -> Moments, fp32, detached.  Inference only."""
-    mom = _as_moments(a, "moments_linear_vd")
-    code = _compute_code(compute)
-    am = mom.mean.detach()
-    av = None if mom.var is None else mom.var.detach()
-    theta, log_sigma2 = theta.detach().contiguous(), log_sigma2.detach().contiguous()
-    if mu_b is not None:
-        mu_b, rho_b = mu_b.detach().contiguous(), rho_b.detach().contiguous()
-    _vd_check_posterior(theta, log_sigma2, mu_b, rho_b)
-    N, K = theta.shape
-    if am.dim() < 1 or am.shape[-1] != K:
-        raise BnnHipError("moments_linear_vd: input has %s features, weight expects %d" % (am.shape[-1] if am.dim() else "no", K))
-    lead = tuple(am.shape[:-1])
-    am = am.reshape(-1, K).contiguous()
-    require_cuda_act(am, "a.mean")
-    if am.dtype == torch.bfloat16 and (code != _lib.COMPUTE_BF16 or av is not None):
-        raise BnnHipError("moments_linear_vd: a bf16 input needs compute mode 'bf16' and no variance (hidden moments are fp32)")
-    if av is not None:
-        av = av.reshape(-1, K).contiguous()
-        require_cuda_f32(av, "a.var")
-    B = am.shape[0]
-    if B > 64 * 65535:
-        raise BnnHipError("moments_linear_vd: %d rows (at most %d)" % (B, 64 * 65535))
-    dev = am.device
-    th, s2_w, s2_b, _ = _vd_prepare_raw(theta, log_sigma2, rho_b if mu_b is not None else None, threshold)
-    out_m = torch.empty((B, N), dtype=torch.float32, device=dev)
-    out_v = torch.empty((B, N), dtype=torch.float32, device=dev)
-    flags = (_lib.FLAG_RELU if relu else 0) | (_lib.FLAG_X_BF16 if _bf(am) else 0)
-    check(_lib.load().bnn_moments_forward(ptr(am), ptr(av), K, ptr(th), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(out_m), ptr(out_v),
-                                          B, N, K, code, flags, stream_ptr(dev)), "bnn_moments_forward")
-    return Moments(out_m.reshape(lead + (N,)), out_v.reshape(lead + (N,)))
+    return _moments_linear("moments_linear_vd", _LOG_SIGMA2, a, theta, log_sigma2, mu_b, rho_b, relu, compute, False, threshold)
 
 
 def moments_linear_vd_f64(a, theta, log_sigma2, mu_b, rho_b, relu=False, threshold=None):
     """moments_linear_vd in float64 torch (the CPU path and the tests' reference) -> Moments of float64 tensors, detached."""
-    mom = _as_moments(a, "moments_linear_vd_f64")
-    f64 = _f64(False)
-    am, th, ls2 = f64(mom.mean), f64(theta), f64(log_sigma2)
+    th, s2 = _vd_planes_f64(theta, log_sigma2, threshold)
+    return _moments_linear_planes_f64(_as_moments(a, "moments_linear_vd_f64"), th, s2, mu_b, rho_b, relu, False)
+
+
+def _vd_planes_f64(theta, log_sigma2, threshold):
+    """theta and exp(log_sigma2) in float64, detached, the elements with log_alpha > threshold zeroed in both."""
+    th, ls2 = theta.detach().to(torch.float64), log_sigma2.detach().to(torch.float64)
     s2 = torch.exp(ls2)
     if threshold is not None:
         keep = ~(vd_log_alpha(th, ls2) > float(threshold))
         th, s2 = th * keep, s2 * keep
-    m = am @ th.t()
-    v = (am * am) @ s2.t()
-    if mom.var is not None:
-        v = v + f64(mom.var) @ (th * th + s2).t()
-    if mu_b is not None:
-        m, v = m + f64(mu_b), v + (1e-10 + torch.nn.functional.softplus(f64(rho_b))) ** 2
-    out = Moments(m, v)
-    return moments_relu_f64(out, False) if relu else out
+    return th, s2
 
 
 def _vd_descs(thetas, ls2s):
@@ -1777,7 +1719,14 @@ def moments_convNd(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, group
     (k_moments_conv3d_bwd; K11's launches for a deterministic input), and an activation runs as its standalone launch behind the
     contraction (one device function: the same bits), because its backward needs the pre-activation.  Raises BnnHipError for a
     call the kernel refuses: no torch fallback."""
-    who = "moments_convNd"
+    return _moments_convNd("moments_convNd", _GAUSSIAN, a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, groups, activation,
+                           compute, track)
+
+
+def _moments_convNd(who, post, a, mu_w, par_w, mu_b, rho_b, stride, padding, dilation, groups, activation, compute, track,
+                    threshold=None):
+    """moments_convNd / moments_convNd_vd: the input's preparation, the checks and the untracked launch on the planes of
+    post.prepare; track (the Gaussian posterior only) hands over to _MomentsConv."""
     mom = _as_moments(a, who)
     _refuse_link(mom, who)
     act, alpha = _moment_activation(activation, who)
@@ -1786,10 +1735,10 @@ def moments_convNd(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, group
     keep = (lambda t: t) if tracked else (lambda t: t.detach())
     am = keep(mom.mean).contiguous()
     av = None if mom.var is None else keep(mom.var).contiguous()
-    mu_w, rho_w = keep(mu_w).contiguous(), keep(rho_w).contiguous()
+    mu_w, par_w = keep(mu_w).contiguous(), keep(par_w).contiguous()
     if mu_b is not None:
         mu_b, rho_b = keep(mu_b).contiguous(), keep(rho_b).contiguous()
-    _lrt_check_posterior(mu_w, rho_w, mu_b, rho_b)
+    post.check(mu_w, par_w, mu_b, rho_b, conv=True)
     require_cuda_f32(am, "a.mean")
     if av is not None:
         require_cuda_f32(av, "a.var")
@@ -1803,18 +1752,17 @@ def moments_convNd(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, group
     out_sp = out3[3 - nd:]
     dev = am.device
     if tracked:
-        m, v = _MomentsConv.apply(am, av, mu_w, rho_w, mu_b, rho_b, sh, (B, sh.O) + out_sp, code)
+        m, v = _MomentsConv.apply(am, av, mu_w, par_w, mu_b, rho_b, sh, (B, sh.O) + out_sp, code)
         if act == 'relu':
             m, v = _MomentsRelu.apply(m, v)
         elif act == 'elu':
             m, v = _MomentsElu.apply(m, v, alpha)
         return Moments(m, v)
-    s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
+    mu_w, s2_w, s2_b = post.prepare(mu_w, par_w, rho_b if mu_b is not None else None, threshold)
     out_m = torch.empty((B, sh.O) + out_sp, dtype=torch.float32, device=dev)
     out_v = torch.empty_like(out_m)
-    flags = {None: 0, 'relu': _lib.FLAG_RELU, 'elu': _lib.FLAG_ELU}[act]
     check(_lib.load().bnn_conv3d_moments_forward(ptr(am), ptr(av), ptr(mu_w), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(out_m),
-                                                 ptr(out_v), ctypes.byref(sh), code, flags, alpha, stream_ptr(dev)),
+                                                 ptr(out_v), ctypes.byref(sh), code, _ACT_FLAGS[act], alpha, stream_ptr(dev)),
           "bnn_conv3d_moments_forward")
     return Moments(out_m, out_v)
 
@@ -1974,20 +1922,25 @@ def moments_elu_backward_f64(mom, g_mean, g_var, alpha=1.0):
 def moments_convNd_f64(a, mu_w, rho_w, mu_b, rho_b, stride, padding, dilation, groups=1, activation=None, track=False):
     """moments_convNd in float64 torch (two / three torch.nn.functional.convNd calls on the CPU; sigma = 1e-10 + softplus(rho))
     -> Moments of float64 tensors.  track=True: not detached (torch autograd through the convolutions and the activation)."""
-    who = "moments_convNd_f64"
+    f64 = _f64(track)
+    return _moments_convNd_planes_f64("moments_convNd_f64", a, f64(mu_w), _sigma2_f64(f64(rho_w)), mu_b, rho_b, stride, padding,
+                                      dilation, groups, activation, track)
+
+
+def _moments_convNd_planes_f64(who, a, mu, s2, mu_b, rho_b, stride, padding, dilation, groups, activation, track):
+    """The conv moment layer in float64 on the weight's mean and variance planes (float64 already); the bias is Gaussian."""
     mom = _as_moments(a, who)
     _refuse_link(mom, who)
     act, alpha = _moment_activation(activation, who)
     f64 = _f64(track)
-    sig2 = lambda rho: (1e-10 + torch.nn.functional.softplus(f64(rho))) ** 2         # noqa: E731
-    nd = mu_w.dim() - 2
+    nd = mu.dim() - 2
     if nd not in (1, 2, 3):
-        raise BnnHipError("%s: weight must be (O, C / groups, *kernel) with 1, 2 or 3 kernel axes, got %s" % (who, tuple(mu_w.shape)))
+        raise BnnHipError("%s: weight must be (O, C / groups, *kernel) with 1, 2 or 3 kernel axes, got %s" % (who, tuple(mu.shape)))
     conv = (torch.nn.functional.conv1d, torch.nn.functional.conv2d, torch.nn.functional.conv3d)[nd - 1]
     geo = (tuple(stride), tuple(padding), tuple(dilation), int(groups))
-    am, mu, s2 = f64(mom.mean), f64(mu_w), sig2(rho_w)
+    am = f64(mom.mean)
     m = conv(am, mu, None if mu_b is None else f64(mu_b), *geo)
-    v = conv(am * am, s2, None if mu_b is None else sig2(rho_b), *geo)
+    v = conv(am * am, s2, None if mu_b is None else _sigma2_f64(f64(rho_b)), *geo)
     if mom.var is not None:
         v = v + conv(f64(mom.var), mu * mu + s2, None, *geo)
     out = Moments(m, v)
@@ -2001,63 +1954,15 @@ def moments_convNd_vd(a, theta, log_sigma2, mu_b, rho_b, stride, padding, dilati
     """moments_convNd for a VariationalDropoutConvNd (K24): the same launch (bnn_conv3d_moments_forward, the activation in its
     epilogue) on the planes of bnn_vd_prepare -- theta and exp(log_sigma2), masked by `threshold` as convNd_vd masks them ->
     Moments, fp32 (B, O, *out_spatial), detached.  Inference only: there is no moment backward for this posterior."""
-    who = "moments_convNd_vd"
-    mom = _as_moments(a, who)
-    _refuse_link(mom, who)
-    act, alpha = _moment_activation(activation, who)
-    code = _compute_code(compute)
-    am = mom.mean.detach().contiguous()
-    av = None if mom.var is None else mom.var.detach().contiguous()
-    theta, log_sigma2 = theta.detach().contiguous(), log_sigma2.detach().contiguous()
-    if mu_b is not None:
-        mu_b, rho_b = mu_b.detach().contiguous(), rho_b.detach().contiguous()
-    _vd_check_posterior(theta, log_sigma2, mu_b, rho_b, conv=True)
-    require_cuda_f32(am, "a.mean")
-    if av is not None:
-        require_cuda_f32(av, "a.var")
-    nd = theta.dim() - 2
-    if am.dim() != nd + 2:
-        raise BnnHipError("%s: input must be (B, C, ...) with %d spatial axes for a weight of shape %s, got %s"
-                          % (who, nd, tuple(theta.shape), tuple(am.shape)))
-    img, w5, st, pd, dl = _lrt_conv_views(am.shape, theta.shape, stride, padding, dilation)
-    B = int(am.shape[0])
-    sh, out3 = _conv3d_shape((B,) + img, w5, st, pd, dl, groups)
-    out_sp = out3[3 - nd:]
-    dev = am.device
-    th, s2_w, s2_b, _ = _vd_prepare_raw(theta, log_sigma2, rho_b if mu_b is not None else None, threshold)
-    out_m = torch.empty((B, sh.O) + out_sp, dtype=torch.float32, device=dev)
-    out_v = torch.empty_like(out_m)
-    check(_lib.load().bnn_conv3d_moments_forward(ptr(am), ptr(av), ptr(th), ptr(s2_w), ptr(mu_b), ptr(s2_b), ptr(out_m),
-                                                 ptr(out_v), ctypes.byref(sh), code, _ACT_FLAGS[act], alpha, stream_ptr(dev)),
-          "bnn_conv3d_moments_forward")
-    return Moments(out_m, out_v)
+    return _moments_convNd("moments_convNd_vd", _LOG_SIGMA2, a, theta, log_sigma2, mu_b, rho_b, stride, padding, dilation, groups,
+                           activation, compute, False, threshold)
 
 
 def moments_convNd_vd_f64(a, theta, log_sigma2, mu_b, rho_b, stride, padding, dilation, groups=1, activation=None, threshold=None):
     """moments_convNd_vd in float64 torch (the CPU path and the tests' reference) -> Moments of float64 tensors, detached."""
-    who = "moments_convNd_vd_f64"
-    mom = _as_moments(a, who)
-    _refuse_link(mom, who)
-    act, alpha = _moment_activation(activation, who)
-    f64 = _f64(False)
-    nd = theta.dim() - 2
-    if nd not in (1, 2, 3):
-        raise BnnHipError("%s: weight must be (O, C / groups, *kernel) with 1, 2 or 3 kernel axes, got %s" % (who, tuple(theta.shape)))
-    conv = (torch.nn.functional.conv1d, torch.nn.functional.conv2d, torch.nn.functional.conv3d)[nd - 1]
-    geo = (tuple(stride), tuple(padding), tuple(dilation), int(groups))
-    am, th, ls2 = f64(mom.mean), f64(theta), f64(log_sigma2)
-    s2 = torch.exp(ls2)
-    if threshold is not None:
-        keep = ~(vd_log_alpha(th, ls2) > float(threshold))
-        th, s2 = th * keep, s2 * keep
-    m = conv(am, th, None if mu_b is None else f64(mu_b), *geo)
-    v = conv(am * am, s2, None if mu_b is None else (1e-10 + torch.nn.functional.softplus(f64(rho_b))) ** 2, *geo)
-    if mom.var is not None:
-        v = v + conv(f64(mom.var), th * th + s2, None, *geo)
-    out = Moments(m, v)
-    if act == 'relu':
-        return moments_relu_f64(out, False)
-    return moments_elu_f64(out, alpha, False) if act == 'elu' else out
+    th, s2 = _vd_planes_f64(theta, log_sigma2, threshold)
+    return _moments_convNd_planes_f64("moments_convNd_vd_f64", a, th, s2, mu_b, rho_b, stride, padding, dilation, groups, activation,
+                                      False)
 
 
 # --------------------------------------------------------------------------- K22: MC dropout (and deterministic convs) in a moment pass
@@ -3875,45 +3780,46 @@ def conv_lrt_eligible(x, mu_w, nsamples, shared_x, stride, padding, dilation, gr
 
 
 class _LrtConv(torch.autograd.Function):
-    """y_s = m + sqrt(v + 1e-16) eps_s, m = convNd(x, mu_w, mu_b), v = convNd(x^2, sigma_w^2, sigma_b^2) (LocalReparamConvNd): one
-    operand launch + one paired-contraction launch for all S samples (csrc/bnn_conv3d.hip, k_lrt_conv3d).  Backward: eps re-created
-    from the key in one elementwise launch (g_m, g_v from the saved v; K10's, with N = O P), the paired input-gradient launch, the
-    paired weight-gradient slabs + their reduce, the bias sums -- 5 launches with a bias, 4 without, no torch conv."""
+    """y_s = m + sqrt(v + 1e-16) eps_s, m = convNd(x, mean_w, mu_b), v = convNd(x^2, s2_w, sigma_b^2) (LocalReparamConvNd,
+    VariationalDropoutConvNd): the posterior's operand launch (post.prepare: s2_w, sigma_b^2, with a threshold the masked planes) +
+    one paired-contraction launch for all S samples (csrc/bnn_conv3d.hip, k_lrt_conv3d).  Backward: eps re-created from the key in
+    one elementwise launch (g_m, g_v from the saved v; K10's, with N = O P), the paired input-gradient launch, the paired
+    weight-gradient slabs + their reduce, the bias sums (post.conv_wgrad) -- 5 launches with a bias, 4 without, no torch conv."""
 
     @staticmethod
-    def forward(ctx, x, mu_w, rho_w, mu_b, rho_b, key, shared_x, conv_args, compute, track):
-        for t, n in ((x, "x"), (mu_w, "weight.mean"), (rho_w, "weight.scale")):
-            require_cuda_f32(t, n)
-        if mu_b is not None:
-            require_cuda_f32(mu_b, "bias.mean")
-            require_cuda_f32(rho_b, "bias.scale")
+    def forward(ctx, x, mean_w, par_w, mu_b, rho_b, key, shared_x, conv_args, compute, track, post, threshold):
+        who = "conv_" + post.name
+        require_cuda_f32(x, "x")
+        post.check(mean_w, par_w, mu_b, rho_b, conv=True)
         stride, padding, dilation, groups = conv_args
         S = key.nsamples
-        why = conv_lrt_eligible(x, mu_w, S, shared_x, stride, padding, dilation, groups)
+        why = conv_lrt_eligible(x, mean_w, S, shared_x, stride, padding, dilation, groups)
         if why is not None:
-            raise BnnHipError("conv_lrt: " + why)
-        nd = mu_w.dim() - 2
-        img, w5, st, pd, dl = _lrt_conv_views(x.shape, mu_w.shape, stride, padding, dilation)
+            raise BnnHipError(who + ": " + why)
+        _lrt_refuse_masked_grad(who, ctx, track, threshold)
+        nd = mean_w.dim() - 2
+        img, w5, st, pd, dl = _lrt_conv_views(x.shape, mean_w.shape, stride, padding, dilation)
         B = int(x.shape[-nd - 2])
         sh, out3 = _conv3d_shape((B,) + img, w5, st, pd, dl, groups)
         out_sp = out3[3 - nd:]
         dev = x.device
         needs_grad = track and any(ctx.needs_input_grad[:5])
-        s2_w, s2_b = _lrt_prepare_raw(rho_w, rho_b if mu_b is not None else None)
+        mean, s2_w, s2_b = post.prepare(mean_w, par_w, rho_b if mu_b is not None else None, threshold)
         y = torch.empty((S, B, sh.O) + out_sp, dtype=torch.float32, device=dev)
         v = torch.empty(((B, sh.O) if shared_x else (S, B, sh.O)) + out_sp, dtype=torch.float32, device=dev) if needs_grad else None
         r = _rng_struct(key, dev)
-        check(_lib.load().bnn_conv3d_lrt_forward(ptr(x), 0 if shared_x else x[0].numel(), ptr(mu_w), ptr(s2_w), ptr(mu_b), ptr(s2_b),
+        check(_lib.load().bnn_conv3d_lrt_forward(ptr(x), 0 if shared_x else x[0].numel(), ptr(mean), ptr(s2_w), ptr(mu_b), ptr(s2_b),
                                                  ptr(y), ptr(v), ctypes.byref(sh), S, ctypes.byref(r), compute, stream_ptr(dev)),
               "bnn_conv3d_lrt_forward")
         if needs_grad:
-            ctx.save_for_backward(x, mu_w, rho_w, rho_b if mu_b is not None else None, s2_w, v)
-        ctx.key, ctx.shared_x, ctx.compute, ctx.sh = key, shared_x, compute, sh
+            # (mean: with a threshold the masked plane -- then only the input's gradient is ever asked for, through the masked layer)
+            ctx.save_for_backward(x, mean, par_w, rho_b if mu_b is not None else None, s2_w, v)
+        ctx.post, ctx.key, ctx.shared_x, ctx.compute, ctx.sh = post, key, shared_x, compute, sh
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, mu_w, rho_w, rho_b, s2_w, v = ctx.saved_tensors
+        x, mean_w, par_w, rho_b, s2_w, v = ctx.saved_tensors
         S, compute, shared, sh = ctx.key.nsamples, ctx.compute, ctx.shared_x, ctx.sh
         dev = gy.device
         lib, st = _lib.load(), stream_ptr(dev)
@@ -3923,102 +3829,39 @@ class _LrtConv(torch.autograd.Function):
         r = _rng_struct(ctx.key, dev)
         check(lib.bnn_lrt_backward_epilogue(ptr(gy), ptr(v), ptr(g_m), ptr(g_v), sh.B, v[0].numel() if shared else v[0][0].numel(),
                                             S, 1 if shared else 0, ctypes.byref(r), 0, st), "bnn_lrt_backward_epilogue")
-        gx = g_mu_w = g_rho_w = g_mu_b = g_rho_b = None
+        gx = g_mean_w = g_par_w = g_mu_b = g_rho_b = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            check(lib.bnn_conv3d_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(mu_w), ptr(s2_w), ptr(x), ptr(gx), ctypes.byref(sh),
+            check(lib.bnn_conv3d_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(mean_w), ptr(s2_w), ptr(x), ptr(gx), ctypes.byref(sh),
                                                     nsets, compute, st), "bnn_conv3d_lrt_backward_input")
         need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or need_b:
-            g_mu_w, g_rho_w = torch.empty_like(mu_w), torch.empty_like(rho_w)
+            g_mean_w, g_par_w = torch.empty_like(mean_w), torch.empty_like(par_w)
             if need_b:
                 g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
             nb = lib.bnn_conv3d_lrt_backward_weight_workspace_bytes(ctypes.byref(sh), nsets)
             ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)          # this call's own slabs
-            check(lib.bnn_conv3d_lrt_backward_weight(ptr(x), ptr(g_m), ptr(g_v), ptr(rho_w), ptr(g_mu_w), ptr(g_rho_w),
-                                                     ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), ctypes.byref(sh),
-                                                     nsets, compute, ptr(ws), nb, st), "bnn_conv3d_lrt_backward_weight")
-        return gx, g_mu_w, g_rho_w, g_mu_b, g_rho_b, None, None, None, None, None
+            check(getattr(lib, ctx.post.conv_wgrad)(ptr(x), ptr(g_m), ptr(g_v), ptr(par_w), ptr(g_mean_w), ptr(g_par_w),
+                                                    ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), ctypes.byref(sh),
+                                                    nsets, compute, ptr(ws), nb, st), ctx.post.conv_wgrad)
+        return gx, g_mean_w, g_par_w, g_mu_b, g_rho_b, None, None, None, None, None, None, None
+
+
+def _convNd_lrt(post, x, mean_w, par_w, mu_b, rho_b, key, shared_x, stride, padding, dilation, groups, compute, threshold=None):
+    return _LrtConv.apply(x.contiguous(), mean_w.contiguous(), par_w.contiguous(),
+                          None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
+                          key, bool(shared_x), (tuple(stride), tuple(padding), tuple(dilation), int(groups)),
+                          _compute_code(compute), torch.is_grad_enabled(), post, None if threshold is None else float(threshold))
 
 
 def convNd_lrt(x, mu_w, rho_w, mu_b, rho_b, key, shared_x, stride, padding, dilation, groups=1, compute="f32"):
     """LocalReparamConv{1,2,3}d on the device (the dimension is the weight's): x (B, C, *spatial) shared by the key's S samples
     (shared_x) or (S, B, C, *spatial) -> (S, B, O, *out_spatial) fp32; sample s uses eps[(b O + o) P + p] of the key's sample
     sample0 + s.  Raises BnnHipError (with conv_lrt_eligible's reason) for a call the kernel refuses: no torch fallback."""
-    return _LrtConv.apply(x.contiguous(), mu_w.contiguous(), rho_w.contiguous(),
-                          None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
-                          key, bool(shared_x), (tuple(stride), tuple(padding), tuple(dilation), int(groups)),
-                          _compute_code(compute), torch.is_grad_enabled())
+    return _convNd_lrt(_GAUSSIAN, x, mu_w, rho_w, mu_b, rho_b, key, shared_x, stride, padding, dilation, groups, compute)
 
 
 # --------------------------------------------------------------------------- K24: sparse variational dropout, convolutions
-class _VdConv(torch.autograd.Function):
-    """_LrtConv on the posterior N(theta, exp(log_sigma2)) (VariationalDropoutConvNd): bnn_vd_prepare + bnn_conv3d_lrt_forward, 2
-    launches; backward bnn_lrt_backward_epilogue, bnn_conv3d_lrt_backward_input and bnn_conv3d_vd_backward_weight (K11's slabs,
-    k_vd_conv_wsum, the bias sums) -- 5 launches with a bias, 4 without, no torch conv."""
-
-    @staticmethod
-    def forward(ctx, x, theta, ls2, mu_b, rho_b, key, shared_x, conv_args, compute, track, threshold):
-        require_cuda_f32(x, "x")
-        _vd_check_posterior(theta, ls2, mu_b, rho_b, conv=True)
-        stride, padding, dilation, groups = conv_args
-        S = key.nsamples
-        why = conv_lrt_eligible(x, theta, S, shared_x, stride, padding, dilation, groups)
-        if why is not None:
-            raise BnnHipError("conv_vd: " + why)
-        if track and threshold is not None and any(ctx.needs_input_grad[1:5]):
-            raise BnnHipError("conv_vd: a threshold is set (%r) and a posterior tensor requires a gradient: the mask is for "
-                              "inference" % (threshold,))
-        nd = theta.dim() - 2
-        img, w5, st, pd, dl = _lrt_conv_views(x.shape, theta.shape, stride, padding, dilation)
-        B = int(x.shape[-nd - 2])
-        sh, out3 = _conv3d_shape((B,) + img, w5, st, pd, dl, groups)
-        out_sp = out3[3 - nd:]
-        dev = x.device
-        needs_grad = track and any(ctx.needs_input_grad[:5])
-        th, s2_w, s2_b, _ = _vd_prepare_raw(theta, ls2, rho_b if mu_b is not None else None, threshold)
-        y = torch.empty((S, B, sh.O) + out_sp, dtype=torch.float32, device=dev)
-        v = torch.empty(((B, sh.O) if shared_x else (S, B, sh.O)) + out_sp, dtype=torch.float32, device=dev) if needs_grad else None
-        r = _rng_struct(key, dev)
-        check(_lib.load().bnn_conv3d_lrt_forward(ptr(x), 0 if shared_x else x[0].numel(), ptr(th), ptr(s2_w), ptr(mu_b), ptr(s2_b),
-                                                 ptr(y), ptr(v), ctypes.byref(sh), S, ctypes.byref(r), compute, stream_ptr(dev)),
-              "bnn_conv3d_lrt_forward")
-        if needs_grad:
-            # (th: with a threshold the masked plane -- then only the input's gradient is ever asked for, through the masked layer)
-            ctx.save_for_backward(x, th, ls2, rho_b if mu_b is not None else None, s2_w, v)
-        ctx.key, ctx.shared_x, ctx.compute, ctx.sh = key, shared_x, compute, sh
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, theta, ls2, rho_b, s2_w, v = ctx.saved_tensors
-        S, compute, shared, sh = ctx.key.nsamples, ctx.compute, ctx.shared_x, ctx.sh
-        dev = gy.device
-        lib, st = _lib.load(), stream_ptr(dev)
-        gy = gy.contiguous().float()
-        nsets = 1 if shared else S
-        g_m, g_v = torch.empty_like(v), torch.empty_like(v)
-        r = _rng_struct(ctx.key, dev)
-        check(lib.bnn_lrt_backward_epilogue(ptr(gy), ptr(v), ptr(g_m), ptr(g_v), sh.B, v[0].numel() if shared else v[0][0].numel(),
-                                            S, 1 if shared else 0, ctypes.byref(r), 0, st), "bnn_lrt_backward_epilogue")
-        gx = g_theta = g_ls2 = g_mu_b = g_rho_b = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            check(lib.bnn_conv3d_lrt_backward_input(ptr(g_m), ptr(g_v), ptr(theta), ptr(s2_w), ptr(x), ptr(gx), ctypes.byref(sh),
-                                                    nsets, compute, st), "bnn_conv3d_lrt_backward_input")
-        need_b = rho_b is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or need_b:
-            g_theta, g_ls2 = torch.empty_like(theta), torch.empty_like(ls2)
-            if need_b:
-                g_mu_b, g_rho_b = torch.empty_like(rho_b), torch.empty_like(rho_b)
-            nb = lib.bnn_conv3d_lrt_backward_weight_workspace_bytes(ctypes.byref(sh), nsets)
-            ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)          # this call's own slabs
-            check(lib.bnn_conv3d_vd_backward_weight(ptr(x), ptr(g_m), ptr(g_v), ptr(ls2), ptr(g_theta), ptr(g_ls2),
-                                                    ptr(rho_b) if need_b else None, ptr(g_mu_b), ptr(g_rho_b), ctypes.byref(sh),
-                                                    nsets, compute, ptr(ws), nb, st), "bnn_conv3d_vd_backward_weight")
-        return gx, g_theta, g_ls2, g_mu_b, g_rho_b, None, None, None, None, None, None
-
-
 def convNd_vd(x, theta, log_sigma2, mu_b, rho_b, key, shared_x, stride, padding, dilation, groups=1, compute="f32", threshold=None):
     """VariationalDropoutConv{1,2,3}d on the device (the dimension is the weight's): convNd_lrt on the posterior
     N(theta, exp(log_sigma2)) -- x (B, C, *spatial) shared by the key's S samples (shared_x) or (S, B, C, *spatial) ->
@@ -4028,10 +3871,8 @@ def convNd_vd(x, theta, log_sigma2, mu_b, rho_b, key, shared_x, stride, padding,
     inference only: a call that would need a gradient of a posterior tensor raises BnnHipError.  Raises BnnHipError (with
     conv_lrt_eligible's reason) for a call the kernel refuses: no torch fallback."""
     _vd_refuse_masked_grad("convNd_vd", threshold, theta, log_sigma2, mu_b, rho_b)
-    return _VdConv.apply(x.contiguous(), theta.contiguous(), log_sigma2.contiguous(),
-                         None if mu_b is None else mu_b.contiguous(), None if rho_b is None else rho_b.contiguous(),
-                         key, bool(shared_x), (tuple(stride), tuple(padding), tuple(dilation), int(groups)),
-                         _compute_code(compute), torch.is_grad_enabled(), None if threshold is None else float(threshold))
+    return _convNd_lrt(_LOG_SIGMA2, x, theta, log_sigma2, mu_b, rho_b, key, shared_x, stride, padding, dilation, groups, compute,
+                       threshold)
 
 
 # --------------------------------------------------------------------------- Flipout conv3d (FlipOutNormalConv3d on the device)

@@ -170,15 +170,16 @@ def test_cpu_moments_and_weight_sampling_has_the_same():
 
 
 def test_lrt_kernels_do_not_spill():
-    """Every instantiation of the paired-contraction tile (forward, input gradient, weight gradient x bf16, fp32) keeps both
-    accumulator sets in registers, and the elementwise kernels use no scratch either."""
+    """Every instantiation of the paired-contraction tile (forward, input gradient, weight gradient x bf16, fp32; the third
+    template argument is this posterior's chain factor, which only the weight gradient's epilogue uses) keeps both accumulator
+    sets in registers, and the elementwise kernels use no scratch either."""
     notes = _code_object_notes()
     kernels = {}
     for block in notes.split("- .agpr_count")[1:]:
         fields = dict(re.findall(r"\.(name|vgpr_spill_count|private_segment_fixed_size):\s+(\S+)", block))
         if "name" in fields:
             kernels[fields["name"]] = fields
-    tiles = {n: f for n, f in kernels.items() if re.match(r"_ZN3bnn5k_lrtI[tf]Li[012]EEEvNS_7LrtArgsE$", n)}
+    tiles = {n: f for n, f in kernels.items() if re.match(r"_ZN3bnn5k_lrtI[tf]Li[012]ENS_8ChainRhoEEEvNS_7LrtArgsE$", n)}
     assert len(tiles) == 6, sorted(kernels)
     rest = {n: f for n, f in kernels.items() if re.match(r"_ZN3bnn(13k_lrt_prepare|18k_lrt_bwd_epilogue|15k_lrt_bias_grad)", n)}
     assert len(rest) == 4, sorted(kernels)

@@ -321,19 +321,21 @@ def test_training_separates_signal_from_noise_inputs():
 
 
 def test_code_object_holds_the_new_kernels():
-    """Symbol names and resource notes only: both weight-gradient tiles, both operand kernels and the three KL kernels are in the
-    gfx950 code object, and none of them uses scratch."""
+    """Symbol names and resource notes only: the dense weight-gradient tile of both posteriors in both compute modes (K10's k_lrt
+    with the posterior's chain factor as its third template argument: 4 instantiations), both operand kernels and the three KL
+    kernels are in the gfx950 code object, each once, and none of them uses scratch."""
     notes = _code_object_notes()
     kernels = {}
     for block in notes.split("- .agpr_count")[1:]:
         fields = dict(re.findall(r"\.(name|vgpr_spill_count|private_segment_fixed_size):\s+(\S+)", block))
         if "name" in fields:
             kernels[fields["name"]] = fields
-    want = [r"_ZN3bnn10k_vd_wgradItEEvNS_11VdWgradArgsE$", r"_ZN3bnn10k_vd_wgradIfEEvNS_11VdWgradArgsE$", r"_ZN3bnn12k_vd_prepareILb1EEE",
-            r"_ZN3bnn12k_vd_prepareILb0EEE", r"_ZN3bnn15k_vd_kl_partialE", r"_ZN3bnn13k_vd_kl_finalE", r"_ZN3bnn16k_vd_kl_backwardE"]
+    want = [r"_ZN3bnn5k_lrtI%sLi2ENS_%sEEEvNS_7LrtArgsE$" % (t, chain) for t in "tf" for chain in ("14ChainLogSigma2", "8ChainRho")]
+    want += [r"_ZN3bnn12k_vd_prepareILb1EEE", r"_ZN3bnn12k_vd_prepareILb0EEE", r"_ZN3bnn15k_vd_kl_partialE", r"_ZN3bnn13k_vd_kl_finalE",
+             r"_ZN3bnn16k_vd_kl_backwardE"]
     for pat in want:
         found = [f for n, f in kernels.items() if re.match(pat, n)]
-        assert len(found) == 1, (pat, sorted(n for n in kernels if "vd" in n))
+        assert len(found) == 1, (pat, sorted(n for n in kernels if "vd" in n or "k_lrtI" in n))
         assert int(found[0].get("vgpr_spill_count", 0)) == 0 and int(found[0].get("private_segment_fixed_size", 0)) == 0, (pat, found[0])
 
 
@@ -637,6 +639,56 @@ def test_backward_matches_float64_on_the_keys_eps(dev, shape, shared, bias, mode
     want[2] = (w2 / s2 * c_true, b2 / s2 * c_true)
     for n, a, (w, bound) in zip(names, got, want):
         assert_within(a.reshape(w.shape), w, bound + 1e-30, "g %s %s bf16" % (n, shape))
+
+
+@gpu
+@pytest.mark.parametrize("bias", [True, False])
+def test_weight_gradient_epilogue_over_the_parameters_range(dev, bias):
+    """bnn_vd_backward_weight called directly in the fp32 mode, (M, N, K) = (33, 7, 100) -- one partial tile in each direction -- and
+    log_sigma2 from wide_grid's [-100, 20] (exp from 0 and denormals to 5e8): g_theta and the bias gradients are
+    bnn_lrt_backward_weight's on the same x, g_m, g_v bit for bit (one tile, one host function; only the chain factor differs), and
+    with t = g_v^T x^2, l = log_sigma2
+
+        |g_log_sigma2 - t64 exp(l)| <= b_t exp(l) (1 + 4 u) + 4 u |t64| exp(l) + 2^-149
+
+    test_variational_dropout_conv.py's epilogue bound (one 2-u expf and one product; below l = -87, where expf is a denormal, the
+    fp64 product rounded once: ONE quantum), with b_t the allowance test_backward_matches_float64_on_the_keys_eps gives the fp32
+    mode's contraction, scaled_bound(t64) (1e-5 of t's scale; the ordered fp32 chain over M = 33 addends stays below gamma(33)
+    sum |g_v| x^2 = 2e-6 sum |g_v| x^2, which is inside it).  Worst err / bound the MI355X run printed: g_log_sigma2 0.397
+    (with the epilogue that multiplied by the denormal expf, before the dense and the conv layer shared ChainLogSigma2:
+    9.569, at an element below -87)."""
+    M, N, K = 33, 7, 100
+    _, ls2 = wide_grid(N * K, seed=5)
+    assert ls2.min() <= -99 and ls2.max() >= 19 and ((ls2 >= -100) & (ls2 < -87)).any()
+    ls2 = ls2.reshape(N, K)
+    g = torch.Generator().manual_seed(43)
+    x = torch.randn(M, K, generator=g)
+    g_m = torch.randn(M, N, generator=g)
+    g_v = torch.randn(M, N, generator=g)
+    rho_w = -3 + 0.3 * torch.randn(N, K, generator=g)
+    rho_b = -3 + 0.3 * torch.randn(N, generator=g)
+    lib, st = _lib.load(), _lib.stream_ptr(dev)
+    xd, gmd, gvd, ld, rwd, rbd = (t.to(dev) for t in (x, g_m, g_v, ls2, rho_w, rho_b))
+    outs = {}
+    for which in ("lrt", "vd"):
+        gw, gs = torch.empty_like(ld), torch.empty_like(ld)
+        gmb, grb = (torch.empty_like(rbd), torch.empty_like(rbd)) if bias else (None, None)
+        fn = lib.bnn_lrt_backward_weight if which == "lrt" else lib.bnn_vd_backward_weight
+        n0 = lib.bnn_launch_count()
+        _lib.check(fn(_lib.ptr(xd), K, _lib.ptr(gmd), _lib.ptr(gvd), _lib.ptr(rwd if which == "lrt" else ld), _lib.ptr(gw), _lib.ptr(gs),
+                      _lib.ptr(rbd) if bias else None, _lib.ptr(gmb), _lib.ptr(grb), M, N, K, _lib.COMPUTE_F32, 0, st), which)
+        torch.cuda.synchronize()
+        assert lib.bnn_launch_count() == n0 + (2 if bias else 1)
+        outs[which] = (gw, gs, gmb, grb)
+    assert torch.equal(outs["vd"][0], outs["lrt"][0])                     # g_theta: the same tile, the same accumulation order
+    if bias:
+        assert torch.equal(outs["vd"][2], outs["lrt"][2]) and torch.equal(outs["vd"][3], outs["lrt"][3])
+    t = g_v.double().t() @ x.double() ** 2
+    b_t = scaled_bound(t)
+    c = torch.exp(ls2.double())
+    want = t * c
+    assert (want.abs()[ls2 <= -95] < 2.0 ** -126).all() and want.abs().max() > 1e8
+    assert_within(outs["vd"][1], want, b_t * c * (1 + 4 * U) + 4 * U * want.abs() + 2.0 ** -149, "g_log_sigma2, wide grid")
 
 
 def _off_boundary(t, dev, off_floats=1):

@@ -14,7 +14,7 @@ itself is held to float64 at test_variational_dropout.bound_s2 (3 u relative: oc
 one fp32 number; one quantum 2^-149 where the result is denormal).  Backward: test_lrt_conv_device.check_backward's -- fp32 mode:
 scaled_bound against float64 autograd of the formula; bf16 mode: g_m / g_v rounded as operands (bf16ref.round_hidden), the
 contractions as bilinear maps in float64 with gamma_{R+1} of sum |a| |b|, the weight gradient with at most 16 slab sums on top
-(gamma_{R+17}) -- with c_w = exp(log_sigma2) in float64 in place of 2 sigma sigmoid(rho).  The epilogue of k_vd_conv_wsum is
+(gamma_{R+17}) -- with c_w = exp(log_sigma2) in float64 in place of 2 sigma sigmoid(rho).  The epilogue of k_lrt_conv_wsum<ChainLogSigma2> is
 g_log_sigma2 = fl(t expf(l)) with t the fp32 slab sum: expf(l) = exp(l) (1 + d1), |d1| <= 2 u (1 ulp of the function), and the one
 product rounds once, (1 + d2), |d2| <= u, so fl(t expf(l)) = t exp(l) (1 + d), |d| <= 3 u + 2 u^2 < 4 u.  With |t - t64| <= b_t:
 |g - t64 exp(l)| <= b_t exp(l) (1 + 4 u) + 4 u |t64| exp(l), + 2^-149 where the product is denormal (EPI_U = 4 below; K11's own
@@ -25,7 +25,7 @@ holds over the whole range; test_epilogue_over_the_parameters_range holds it to 
 g_mu_w, bit for bit.
 
 Launches.  Forward 2 (bnn_vd_prepare, ONE contraction for all S samples); backward 1 (g_m, g_v) + 1 (input gradient) + 2 (the
-slabs, k_vd_conv_wsum) + 1 with a bias = 5 with a bias, 4 without.  One training step of SmallNet (conv - ReLU - conv(groups 2) -
+slabs, their reduce) + 1 with a bias = 5 with a bias, 4 without.  One training step of SmallNet (conv - ReLU - conv(groups 2) -
 Flatten - dense; KLDivergence + cross-entropy + optim.Adam), DESIGN.md K24: forward 3 x 2 = 6; backward 4 (the first conv has no
 input gradient) + 5 + 4 (the dense layer: K23) = 13; the log-uniform KL of the three weights 2 + 1; the Gaussian KL of the three
 biases 2 + 1; optim.Adam 2 (k_adam on all twelve tensors, the device step counter's bump): 27.
@@ -387,14 +387,15 @@ def test_training_lowers_the_loss_and_raises_the_sparsity():
 
 
 def test_code_object_holds_the_new_kernel():
-    """k_vd_conv_wsum is in the gfx950 code object, once, and uses no scratch; K11's reduce is still there beside it."""
+    """The slab reduce with this posterior's chain factor is in the gfx950 code object, once, and uses no scratch; K11's
+    instantiation is still there beside it."""
     notes = _code_object_notes()
     kernels = {}
     for block in notes.split("- .agpr_count")[1:]:
         fields = dict(re.findall(r"\.(name|vgpr_spill_count|private_segment_fixed_size):\s+(\S+)", block))
         if "name" in fields:
             kernels[fields["name"]] = fields
-    for pat in (r"_ZN3bnn14k_vd_conv_wsumE", r"_ZN3bnn15k_lrt_conv_wsumE"):
+    for pat in (r"_ZN3bnn15k_lrt_conv_wsumINS_14ChainLogSigma2EEEv", r"_ZN3bnn15k_lrt_conv_wsumINS_8ChainRhoEEEv"):
         found = [f for n, f in kernels.items() if re.match(pat, n)]
         assert len(found) == 1, (pat, sorted(n for n in kernels if "wsum" in n))
         assert int(found[0].get("vgpr_spill_count", 0)) == 0 and int(found[0].get("private_segment_fixed_size", 0)) == 0, (pat, found[0])
@@ -596,7 +597,7 @@ def test_backward_matches_float64_on_the_keys_eps(dev, name, S, shared, bias, mo
     n0 = lib.bnn_launch_count()
     got = torch.autograd.grad(y, [t for t in leaves if t is not None], gy.to(dev))
     torch.cuda.synchronize()
-    # g_m / g_v, the paired input gradient, the paired weight-gradient slabs and k_vd_conv_wsum, the bias sums: nothing else ran
+    # g_m / g_v, the paired input gradient, the paired weight-gradient slabs and their reduce, the bias sums: nothing else ran
     assert lib.bnn_launch_count() == n0 + (5 if bias else 4)
     assert all(torch.isfinite(t).all() for t in got)
     theta, ls2, mu_b, rho_b = params

@@ -1,4 +1,4 @@
-"""Training-step time of VariationalDropoutConv2d (K24, k_vd_conv_wsum of csrc/bnn_conv3d.hip) against LocalReparamConv2d (K11) on
+"""Training-step time of VariationalDropoutConv2d (K24, k_lrt_conv_wsum<ChainLogSigma2> of csrc/bnn_conv3d.hip) against LocalReparamConv2d (K11) on
 the GPU box: the LeNet tail at K19's shape -- (1024, 64, 6, 6) -> conv(64, 64, 3, stride 2, padding 1) -> ReLU -> Flatten ->
 dense(576, 10) -- S = 8, both compute modes, both nets in ONE process.  The `vd` net is VariationalDropoutConv2d +
 VariationalDropoutLinear, the `lrt` net LocalReparamConv2d + LocalReparamLinear.  A step: MC-batched forward, KLDivergence,
