@@ -35,10 +35,12 @@
 //   * fp32 parity mode: every operand as three bf16 planes, six plane-pair k-steps per k-block (bnn_dense_forward_x3).
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "bnn_device.hpp"
 #include "bnn_dma.hpp"
 #include "bnn_kl_body.hpp"
+#include "bnn_knobs.hpp"
 
 namespace bnn {
 
@@ -94,19 +96,18 @@ struct DrawLaunch {
 // waves parked 47 % of the time.)
 // LEAN (kernel k_draw_lean): the body for launches whose draws are all Philox-7 / u16, with no conv taps, no Flipout and no
 // three-plane output (the host checks, bnn_draw_multi).  A kernel's VGPR budget is the maximum over ALL its paths: the
-// tap-group transpose, Flipout, three-plane stores and the Philox-10 branch of the sample loop put k_draw_multi<1> at 110
+// tap-group transpose, Flipout, three-plane stores and the Philox-10 branch of the sample loop put k_draw_multi at 110
 // VGPRs = 4 waves per SIMD, against 56 for the lean body = 8.  The BASELINE launch is ~5000 waves: 1.2 rounds of 4096
 // slots at 4 waves per SIMD, one round of 8192 at 8.  Same code per element, same stream, same rounding -- only the paths
 // such a launch never takes are compiled out.
-template <int U, bool LEAN>
+template <bool LEAN>
 __device__ __forceinline__ void draw_multi_body(const DrawLaunch &L);
 
-template <int U>
-__global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L) { draw_multi_body<U, false>(L); }
+__global__ __launch_bounds__(256) void k_draw_multi(const DrawLaunch L) { draw_multi_body<false>(L); }
 
-__global__ __launch_bounds__(256) void k_draw_lean(const DrawLaunch L) { draw_multi_body<1, true>(L); }
+__global__ __launch_bounds__(256) void k_draw_lean(const DrawLaunch L) { draw_multi_body<true>(L); }
 
-template <int U, bool LEAN>
+template <bool LEAN>
 __device__ __forceinline__ void draw_multi_body(const DrawLaunch &L)
 {
     // The KL's workgroups come FIRST in the grid: they are short (8 or 16 scalars per thread, no sample loop) and the dispatcher
@@ -184,7 +185,7 @@ __device__ __forceinline__ void draw_multi_body(const DrawLaunch &L)
         const bool gen16 = LEAN || rng.gen == BNN_GEN_PHILOX7_U16;      // (wave-uniform)
         char *dst = t_out + ((int64_t)row * t_ld + c0) * esz2 + (int64_t)blockIdx.y * sbytes2;
         const int64_t step = sbytes2 * (int64_t)gridDim.y;
-#pragma unroll U
+#pragma unroll 1
         for (int s = (int)blockIdx.y; s < S; s += (int)gridDim.y, dst += step) {
             const uint32_t sample = rng.sample0 + (uint32_t)s;
             float4 za, zb;
@@ -388,7 +389,7 @@ __device__ __forceinline__ void draw_multi_body(const DrawLaunch &L)
         char *dst = dst0 + (int64_t)s_lo * sbytes;
         const int64_t step = sbytes * (int64_t)s_step;
         const bool gen16 = LEAN || rng.gen == BNN_GEN_PHILOX7_U16;      // (wave-uniform)
-#pragma unroll U
+#pragma unroll 1
         for (int s = s_lo; s < s_hi; s += s_step, dst += step) {
             const uint32_t sample = rng.sample0 + (uint32_t)s;
             float4 za, zb;
@@ -504,7 +505,7 @@ __device__ __forceinline__ void draw_multi_body(const DrawLaunch &L)
     const bool vec_store = t_bf16 && nval == 8 && t_taps <= 1;
     // gridDim.y > 1 (small launches: a conv weight is 18 workgroups): the samples are dealt over blockIdx.y as well -- sigma is
     // recomputed per slice, but a thread is no longer one long serial chain of S draws on a mostly idle chip
-#pragma unroll U
+#pragma unroll 1
     for (int s = s_lo; s < s_hi; s += s_step) {
         const uint32_t sample = rng.sample0 + (uint32_t)s;
         float4 za = make_float4(0.f, 0.f, 0.f, 0.f), zb = za;
@@ -609,8 +610,7 @@ struct DenseParams {
     int32_t drop_fan;
 };
 
-constexpr int kDenseLoaderPrio = 1 << 21;   // internal flag (BNN_DENSE_LOADER_PRIO=1): loader waves at priority 2 (experiment)
-constexpr int kDenseNoXcdMap = 1 << 20;     // internal flag (BNN_DENSE_XCD=0): plain sample-major block order, for A/B runs
+constexpr int kDenseNoXcdMap = 1 << 20;     // internal flag, diagnostic build (BNN_DENSE_XCD=0): plain sample-major block order
 
 // one LDS-DMA piece, scalar-base form: 64 lanes x 16 B from (base + voff) land at lds + 16 * lane
 __device__ __forceinline__ void dma_piece(const void *base, uint32_t voff, uint32_t lds)
@@ -632,11 +632,12 @@ __device__ __forceinline__ void dma_piece(const void *base, uint32_t voff, uint3
 //   <4, 5, 2, 2, 4>: 128 x 160 tile, 36 KiB per step for the same 40 MFMAs per wave, 4 stages (144 KiB) -- the BASELINE
 //                    layers: 4 x 8 x 8 = 256 workgroups (N = 1200 rounds up to 1280: the clamped rows are never stored)
 //   <4, 8, 4, 1, 3>: 256 x 128 tile for wide layers
-// DIAG (BNN_DENSE_DIAG): timing-only builds whose outputs are wrong: 1 = consumers skip reads and MFMAs, 2 = loaders skip the
-// DMA, 5 = no DMA and no per-step barriers either (2 vs 5 = what the barriers cost: layer 2 13.85 vs 11.9 us, ~200 cycles per
-// step); correct builds for A/B runs of the read interleave: 3 = one MFMA per interleaved fragment read, 4 = two.  Of these
-// the co-resident instantiation (ST = 2) is built with 6 (stamps) only: the launcher sends every other DIAG value of a tile-1
-// launch to the 4-stage kernel (tile 5), where the measurements above were taken.
+// DIAG (non-zero in the diagnostic library only, BNN_DENSE_DIAG): timing-only builds whose outputs are wrong: 1 = consumers
+// skip reads and MFMAs, 2 = loaders skip the DMA, 5 = no DMA and no per-step barriers either (2 vs 5 = what the barriers cost:
+// layer 2 13.85 vs 11.9 us, ~200 cycles per step); correct builds for A/B runs of the read interleave: 3 = one MFMA per
+// interleaved fragment read, 4 = two.  Of these the co-resident instantiation (ST = 2) is built with 6 (stamps) only: the
+// launcher sends every other DIAG value of a tile-1 launch to the 4-stage kernel (tile 5), where the measurements above were
+// taken.
 // ST = 2 is the CO-RESIDENT instantiation (<4, 5, 2, 2, 2>: the same 128 x 160 tile, 72 KiB of ring, <= 128 registers per
 // lane): two workgroups share a CU, so one workgroup's fill, epilogue and loop stalls run under the other's main loop (the
 // steps in flight of the pipelined MLP step).  Its consumers hold ONE set of fragment registers: [reads (t, h0)] [MFMAs
@@ -677,10 +678,12 @@ __global__ __launch_bounds__(512, ST == 2 ? 4 : 1) void k_dense_bf16(const Dense
     // dealt round-robin, nearly all of both operands through every L2: the 4096^2 layer in the fp32 mode moved 5.65 x its
     // algorithmic bytes over the fabric).
     const int per_s = p.ntm * p.ntn;
+    bool plain_order = false;
+    if constexpr (kDiagBuild) plain_order = (p.flags & kDenseNoXcdMap) != 0;
     int s, t;
     {
         const int L = (int)blockIdx.x;
-        if (p.flags & kDenseNoXcdMap) {
+        if (plain_order) {
             s = L / per_s;
             t = L % per_s;
         } else if (p.S % 8 == 0) {
@@ -695,7 +698,7 @@ __global__ __launch_bounds__(512, ST == 2 ? 4 : 1) void k_dense_bf16(const Dense
         }
     }
     int mt, panel;
-    if (per_s > 32 && !(p.flags & kDenseNoXcdMap)) {
+    if (per_s > 32 && !plain_order) {
         constexpr int GM = 4;
         const int grp = t / (GM * p.ntn), first = grp * GM;
         const int gm = p.ntm - first < GM ? p.ntm - first : GM;
@@ -717,7 +720,6 @@ __global__ __launch_bounds__(512, ST == 2 ? 4 : 1) void k_dense_bf16(const Dense
     if (wave >= NWV) {
         // =============================== loader ===============================
         const int lw = wave - NWV;
-        if (p.flags & kDenseLoaderPrio) __builtin_amdgcn_s_setprio(2);
         const uint32_t ring = __builtin_amdgcn_readfirstlane(lds_addr_of(lds));
         // Lane l writes position l & 7 of row l >> 3 of its piece and therefore fetches chunk (l & 7) ^ (l >> 3) of
         // that row (the image's XOR swizzle, applied on the source address).
@@ -1319,7 +1321,7 @@ struct ConvParams {
     int32_t B, C, H, Wd, O, KH, KW, sh, sw, ph, pw, dh, dw, OH, OW;
     int32_t S, IMG, ntiles;     // images per workgroup, workgroups per sample
     int32_t img_bytes;          // H * W * C * 2
-    int32_t flags;
+    int32_t flags;              // diagnostic build: BNN_CONV_DIAG; otherwise 0 and never read
     // Flipout (FLIP instantiation): W holds 2 O rows -- the means, then the stddevs -- and
     //   y[b][o] = conv(x[b], mean)[o] + R[b][o] * conv(x[b] * S[b], stddev)[o]           (conv.py:207-221)
     const float *sgn_in;        // S: B x C of +-1
@@ -1419,14 +1421,16 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
             if (k0 < nk) issue(k0);
     }
 
-    // (p.flags, BNN_CONV_DIAG: timing-only runs with wrong outputs -- 1 skips the image fill, 2 the k loop, 4 the output copy)
+    // (diagnostic build, p.flags = BNN_CONV_DIAG: timing-only runs with wrong outputs -- 1 skips the image fill, 2 the k loop, 4 the
+    // output copy)
+    auto skip = [&](int bit) { if constexpr (kDiagBuild) return (p.flags & bit) != 0; else return false; };
     // ---- phase 0: this tile's images -> LDS (bf16, channel-last, swizzled on the pixel index inside the image).
     // A thread owns one (channel pair, pixel quad) of the image layout and walks the images: its decomposition -- the only
     // integer divisions of the phase -- is computed once, every image then costs two 16-B loads and four 4-B LDS writes.
     {
         const float *xs = p.X + (int64_t)s * p.x_sample_stride + (int64_t)b0 * p.C * HW;
         const int Q = (HW + 3) >> 2, CH2 = p.C >> 1;
-        const int per_img = (p.flags & 1) ? 0 : CH2 * Q;
+        const int per_img = skip(1) ? 0 : CH2 * Q;
         if constexpr (KEYED) {
             // the samples' signs from the key: masks (bit 15 of element j set where S_s[b][8 chunk + j] = -1) and R_s as floats
             const uint32_t ed = rng_epoch_dev(p.rng);
@@ -1527,7 +1531,7 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
         for (int b = 0; b < NACC; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int fi = lane & 15, fq = lane >> 4;
 
-    const int nk_run = (p.flags & 2) ? 0 : nk;
+    const int nk_run = skip(2) ? 0 : nk;
     if (wave >= NWV) {
         // =============================== loader ===============================
         if (nk_run == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1685,7 +1689,7 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
             }
             __syncthreads();
             float *Yt = p.Y + (int64_t)(s + n) * p.y_sample_stride + (int64_t)b0 * p.O * P;
-            const int nn = (p.flags & 4) ? 0 : imgs * p.O * P;
+            const int nn = skip(4) ? 0 : imgs * p.O * P;
             if ((nn & 3) == 0 && (reinterpret_cast<uintptr_t>(Yt) & 15u) == 0) {
                 for (int i = tid; i < (nn >> 2); i += 512) reinterpret_cast<uint4 *>(Yt)[i] = reinterpret_cast<const uint4 *>(T)[i];
             } else {
@@ -1719,7 +1723,7 @@ __global__ __launch_bounds__(512, LDSB <= 80 * 1024 ? 2 : 1) void k_conv_bf16(co
     __syncthreads();
     {
         float *Yt = p.Y + (int64_t)s * p.y_sample_stride + (int64_t)b0 * p.O * P;
-        const int n = (p.flags & 4) ? 0 : imgs * p.O * P;
+        const int n = skip(4) ? 0 : imgs * p.O * P;
         if ((n & 3) == 0 && (reinterpret_cast<uintptr_t>(Yt) & 15u) == 0) {
             for (int i = tid; i < (n >> 2); i += 512) reinterpret_cast<uint4 *>(Yt)[i] = reinterpret_cast<const uint4 *>(T)[i];
         } else {
@@ -1814,7 +1818,7 @@ struct DropArgs {
 // one-workgroup-per-CU 4-stage ring that tile 1 ran before its co-resident ring: A/B runs only) -- see dense_launch
 static int dense_pick_tile(int64_t M, int64_t N, int nsamples)
 {
-    static const int force_tile = [] { const char *e = getenv("BNN_DENSE_TILE"); return e ? atoi(e) : -1; }();
+    const int force_tile = knob::dense_tile();
     int tile = (N % 80 == 0 || N < 128) ? 1 : 2;
     if (N <= 80) tile = 0;
     if (force_tile >= 0 && force_tile <= 5) tile = force_tile;
@@ -1824,6 +1828,16 @@ static int dense_pick_tile(int64_t M, int64_t N, int nsamples)
         if (tile == 3 && ((M + 63) / 64) * cols * nsamples < 128 && M > 32) tile = 4;
     }
     return tile;
+}
+
+// diagnostic build: launches the bf16-output kernel's DIAG instantiation `diag` if it is one of D...; false = nothing launched.
+// (A production build compiles none of them: the fold below is discarded.)
+template <int TM, int TN, int NWM, int NWN, int ST, bool RELU, int... D>
+static bool dense_launch_diag(int diag, dim3 g, hipStream_t st, const DenseParams &p, std::integer_sequence<int, D...>)
+{
+    if constexpr (kDiagBuild)
+        return ((diag == D && [&] { hipLaunchKernelGGL((k_dense_bf16<TM, TN, NWM, NWN, ST, 1, RELU, D>), g, dim3(512), 0, st, p); return true; }()) || ...);
+    return false;
 }
 
 static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, int64_t x_sample_stride, int64_t ldx,
@@ -1905,10 +1919,7 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
     // the dropout epilogue takes a lane's four columns as one aligned quad of the mask index: N % 4 == 0.  Otherwise the plain
     // kernel stores and the mask launch runs after it, in place, as for the narrow kernel
     const bool fused_drop = drop && N % 4 == 0;
-    static const bool no_xcd = [] { const char *e = getenv("BNN_DENSE_XCD"); return e && e[0] == '0'; }();
-    if (no_xcd) p.flags |= kDenseNoXcdMap;
-    static const bool lprio = [] { const char *e = getenv("BNN_DENSE_LOADER_PRIO"); return e && e[0] == '1'; }();
-    if (lprio) p.flags |= kDenseLoaderPrio;
+    if (knob::dense_no_xcd()) p.flags |= kDenseNoXcdMap;
     // tile: the BASELINE-shaped layers (N % 80 == 0: 1200 = 7.5 x 160) take 128 x 160 with a 4-stage ring -- 36 KiB per
     // 64-k step instead of 256 x 80's 42 for the same MFMAs, 4 x 8 x 8 = 256 workgroups; wide layers 256 x 128.
     // BNN_DENSE_TILE = 0 (256 x 80), 1 (128 x 160), 2 (256 x 128), 3 (64 x 160), 4 (32 x 160), 5 (128 x 160, one workgroup per
@@ -1932,11 +1943,10 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
     p.ntn = (int32_t)((N + bn - 1) / bn);
     const int64_t grid = (int64_t)p.ntm * p.ntn * nsamples;
     if (grid > 0x7FFFFFFF) { set_error("%s: grid too large", who); return BNN_E_RANGE; }
-    static const int diag = [] { const char *e = getenv("BNN_DENSE_DIAG"); return e ? atoi(e) : 0; }();
-    if (diag >= 6 && diag <= 9 && !head && !drop) {
-        static const uint64_t stamps = [] { const char *e = getenv("BNN_DENSE_STAMPS"); return e ? strtoull(e, nullptr, 0) : 0ull; }();
-        p.P = reinterpret_cast<float *>(stamps);
-    }
+    // (diagnostic build: a plain bf16-output launch runs the DIAG instantiation BNN_DENSE_DIAG names, dense_launch_diag)
+    const int diag = knob::dense_diag();
+    if (diag >= 6 && diag <= 9 && !head && !drop) p.P = reinterpret_cast<float *>(knob::dense_stamps());
+    if (diag == 1 || diag == 2 || diag == 5 || (diag >= 7 && diag <= 9)) BNN_WRONG_RESULTS_ONCE("BNN_DENSE_DIAG");
     const bool relu = (flags & BNN_FLAG_RELU) != 0;
     const dim3 g((unsigned)grid), blk(512);
 #define BNN_DENSE_LAUNCH(TM_, TN_, NWM_, NWN_, ST_, RELU_, DROP_) \
@@ -1946,15 +1956,7 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
         else if (head) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 3, RELU_>), g, blk, 0, st, p); \
         else if (x3 && ybf) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 2, RELU_>), g, blk, 0, st, p); \
         else if (!ybf) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 0, RELU_>), g, blk, 0, st, p); \
-        else if (diag == 1) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 1>), g, blk, 0, st, p); \
-        else if (diag == 2) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 2>), g, blk, 0, st, p); \
-        else if (diag == 3) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 3>), g, blk, 0, st, p); \
-        else if (diag == 4) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 4>), g, blk, 0, st, p); \
-        else if (diag == 5) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 5>), g, blk, 0, st, p); \
-        else if (diag == 6) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 6>), g, blk, 0, st, p); \
-        else if (diag == 7) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 7>), g, blk, 0, st, p); \
-        else if (diag == 8) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 8>), g, blk, 0, st, p); \
-        else if (diag == 9) hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_, 9>), g, blk, 0, st, p); \
+        else if (dense_launch_diag<TM_, TN_, NWM_, NWN_, ST_, RELU_>(diag, g, st, p, std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9>{})) { } \
         else hipLaunchKernelGGL((k_dense_bf16<TM_, TN_, NWM_, NWN_, ST_, 1, RELU_>), g, blk, 0, st, p); \
     } while (0)
 #define BNN_DENSE_PICK(TM_, TN_, NWM_, NWN_, ST_, DROP_) \
@@ -1965,7 +1967,7 @@ static int dense_launch(const char *who, const void *x, int64_t x_plane_stride, 
     do { \
         if (head) hipLaunchKernelGGL((k_dense_bf16<4, 5, 2, 2, 2, 3, RELU_>), g, blk, 0, st, p); \
         else if (!ybf) hipLaunchKernelGGL((k_dense_bf16<4, 5, 2, 2, 2, 0, RELU_>), g, blk, 0, st, p); \
-        else if (diag == 6) hipLaunchKernelGGL((k_dense_bf16<4, 5, 2, 2, 2, 1, RELU_, 6>), g, blk, 0, st, p); \
+        else if (dense_launch_diag<4, 5, 2, 2, 2, RELU_>(diag, g, st, p, std::integer_sequence<int, 6>{})) { } \
         else hipLaunchKernelGGL((k_dense_bf16<4, 5, 2, 2, 2, 1, RELU_>), g, blk, 0, st, p); \
     } while (0)
     if (tile == 0) BNN_DENSE_PICK(4, 5, 4, 1, 3, true);
@@ -2026,8 +2028,7 @@ int bnn_draw_multi(const bnn_draw_tensor_t *tensors, int ntensors, int nsamples,
         d.flat = (!d.spread && t.out_dtype != BNN_F32 && t.kind == 0 && t.taps <= 1 && t.cols % 8 == 0 && t.ld % 8 == 0 && al16(t.mu) && al16(t.rho)) ? 1 : 0;
         d.tapg = (t.taps > 1 && t.taps <= 256 && t.out_dtype != BNN_F32 && t.rows >= 1 && (t.cols / t.taps) % 8 == 0 && t.ld % 8 == 0 &&
                   al16(t.mu) && (t.kind == 1 || t.kind == 3 || al16(t.rho))) ? 1 : 0;
-        static const bool no_tapg = [] { const char *e = getenv("BNN_DRAW_TAPG"); return e && e[0] == '0'; }();
-        if (no_tapg) d.tapg = 0;
+        if (knob::draw_no_tapg()) d.tapg = 0;
         if (d.tapg) {
             d.spread = 0;
             const int64_t ng = 2048 / (8 * t.taps), NG = t.rows * (t.cols / t.taps / 8);
@@ -2051,7 +2052,7 @@ int bnn_draw_multi(const bnn_draw_tensor_t *tensors, int ntensors, int nsamples,
         // a KL tensor that IS one of this launch's flat draw tensors (same mu / rho, all of it): its partial sums come from the
         // draw items, which hold the posterior in registers -- no workgroups of its own, no second read of mu and rho (round 2:
         // FETCH_SIZE of the launch 36.4 MB for 19.2 MB of posterior)
-        static const bool kl_items = [] { const char *e = getenv("BNN_DRAW_KL_ITEMS"); return !(e && e[0] == '0'); }();
+        const bool kl_items = !knob::draw_no_kl_items();
         int32_t launched = 0;
         for (int j = 0; j < kl_ntensors; ++j) {
             const int32_t nb = L.kl.pg_first[j + 1] - L.kl.pg_first[j];     // (pg_first still = first_block here)
@@ -2076,24 +2077,17 @@ int bnn_draw_multi(const bnn_draw_tensor_t *tensors, int ntensors, int nsamples,
     int split = 1;
     while (split < nsamples && (int64_t)L.draw_blocks * split < 1024) split *= 2;
     if (split > nsamples) split = nsamples;
-    // BNN_DRAW_SPLIT forces the split for A/B runs (the BASELINE launch: 26.1 / 24.7 / 27.6 / 37.2 us with 1 / 2 / 4 / 8; in the
-    // pipelined bench 156 / 153 / 143 k MC-samples/s with 1 / 2 / 4)
-    static const int force_split = [] { const char *e = getenv("BNN_DRAW_SPLIT"); return e ? atoi(e) : 0; }();
-    if (force_split >= 1 && force_split <= nsamples) split = force_split;
-    static const int unroll = [] { const char *e = getenv("BNN_DRAW_UNROLL"); return e ? atoi(e) : 1; }();
+    // (diagnostic build: BNN_DRAW_SPLIT forces the split for A/B runs.  Measured, the BASELINE launch: 26.1 / 24.7 / 27.6 /
+    // 37.2 us with 1 / 2 / 4 / 8; in the pipelined bench 156 / 153 / 143 k MC-samples/s with 1 / 2 / 4)
+    if (knob::draw_split() >= 1 && knob::draw_split() <= nsamples) split = knob::draw_split();
     // the lean kernel when no tensor needs a path it compiles out (draw_multi_body: LEAN)
     bool lean = true;
     for (int i = 0; i < ntensors; ++i) {
         const DrawTensorDev &d = L.t[i];
         if (d.tapg || d.perm_taps > 1 || d.bf16 == 2 || d.kind == BNN_DRAW_FLIPOUT || (d.kind == 0 && d.rng.gen != BNN_GEN_PHILOX7_U16)) lean = false;
     }
-    static const bool no_lean = [] { const char *e = getenv("BNN_DRAW_LEAN"); return e && e[0] == '0'; }();
-    if (lean && !no_lean && unroll <= 1) hipLaunchKernelGGL(k_draw_lean, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
-    else if (unroll == 2) hipLaunchKernelGGL(k_draw_multi<2>, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
-    else if (unroll == 4) hipLaunchKernelGGL(k_draw_multi<4>, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
-    else if (unroll == 8) hipLaunchKernelGGL(k_draw_multi<8>, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
-    else
-    hipLaunchKernelGGL(k_draw_multi<1>, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
+    if (lean && !knob::draw_no_lean()) hipLaunchKernelGGL(k_draw_lean, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
+    else hipLaunchKernelGGL(k_draw_multi, dim3((unsigned)grid, (unsigned)split), dim3(256), 0, (hipStream_t)stream, L);
     return check_launch(who);
 }
 
@@ -2280,8 +2274,8 @@ static int conv_dense_launch(const float *x, int64_t x_sample_stride, const void
     p.w_plane_stride = w_plane_stride;
     p.B = sh->B; p.C = sh->C; p.H = sh->H; p.Wd = sh->W; p.O = sh->O; p.KH = sh->KH; p.KW = sh->KW;
     p.sh = sh->stride_h; p.sw = sh->stride_w; p.ph = sh->pad_h; p.pw = sh->pad_w; p.dh = sh->dil_h; p.dw = sh->dil_w;
-    static const int cdiag = [] { const char *e = getenv("BNN_CONV_DIAG"); return e ? atoi(e) : 0; }();
-    p.flags = cdiag;
+    p.flags = knob::conv_diag();
+    if (p.flags & 7) BNN_WRONG_RESULTS_ONCE("BNN_CONV_DIAG");
     p.OH = OH; p.OW = OW; p.S = nsamples; p.IMG = img; p.ntiles = (sh->B + img - 1) / img;
     p.img_bytes = (int32_t)((int64_t)sh->H * sh->W * sh->C * 2);
     if (keyed) p.rng = make_rng(rng);

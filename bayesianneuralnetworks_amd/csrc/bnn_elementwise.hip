@@ -9,11 +9,12 @@
 #include <atomic>
 
 #include "bnn_device.hpp"
+#include "bnn_knobs.hpp"
 #include "bnn_mc.hpp"
 
 namespace bnn {
 
-static thread_local char g_err[256] = "";
+static thread_local char g_err[256] = BNN_FRESH_ERROR;
 static std::atomic<uint64_t> g_launches{0};
 
 void set_error(const char *fmt, ...)

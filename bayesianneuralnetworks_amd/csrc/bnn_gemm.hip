@@ -22,6 +22,7 @@
 
 #include "bnn_device.hpp"
 #include "bnn_gemm_params.hpp"
+#include "bnn_knobs.hpp"
 
 namespace bnn {
 
@@ -430,10 +431,9 @@ static int linear_common(const float *x, int64_t x_sample_stride, int64_t ldx,
     p.vecA = xh ? 1 : (al16(x) && (ldx % 4 == 0) && (x_sample_stride % 4 == 0));
     p.vecB = (K % 4 == 0) && (sampled ? (al16(mu_w) && al16(rho_w)) : (al16(w) && w_sample_stride % 4 == 0));
     if (sampled) { p.rng_w = make_rng(rng_w); p.rng_b = make_rng(mu_b ? rng_b : nullptr); }
-    // sampler-paced kernel (bnn_linear.hip) whenever 16-B loads are legal; BNN_LINEAR_KERNEL=v1
-    // forces the generic tile kernel (A/B comparisons).
-    static const bool force_v1 = [] { const char *e = getenv("BNN_LINEAR_KERNEL"); return e && e[0] == 'v' && e[1] == '1'; }();
-    if (p.vecA && p.vecB && !force_v1) {
+    // sampler-paced kernel (bnn_linear.hip) whenever 16-B loads are legal (diagnostic build: BNN_LINEAR_KERNEL=v1
+    // forces the generic tile kernel, for A/B comparisons).
+    if (p.vecA && p.vecB && !knob::linear_force_v1()) {
         fill_workspace(p);
         if (kl) p.kl = *kl;                                     // carried by the narrow-layer launch if that is the one taken
         const int rc = dispatch_linear_v2(p, sampled, compute, (hipStream_t)stream, who);
@@ -664,8 +664,7 @@ static int conv_common(const float *x, int64_t x_sample_stride, const float *w, 
     // implicit-GEMM kernel below (any shape, no workspace).
     {
         const int64_t need = bnn_conv2d_workspace_bytes(sh, x_sample_stride == 0 ? 1 : nsamples, compute);
-        static const bool force_v1 = [] { const char *e = getenv("BNN_LINEAR_KERNEL"); return e && e[0] == 'v' && e[1] == '1'; }();
-        const bool fast = !force_v1 && need > 0 && workspace && workspace_bytes >= need && al16(workspace) && al4(y) &&
+        const bool fast = !knob::linear_force_v1() && need > 0 && workspace && workspace_bytes >= need && al16(workspace) && al4(y) &&
                           (compute == BNN_COMPUTE_F32 || compute == BNN_COMPUTE_BF16) && (flags & ~BNN_FLAG_RELU) == 0 &&
                           (sampled ? (al16(mu_w) && al16(rho_w)) : (al16(w) && w_sample_stride % 4 == 0));
         if (fast) {

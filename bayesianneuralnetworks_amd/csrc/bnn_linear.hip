@@ -32,6 +32,7 @@
 #include "bnn_device.hpp"
 #include "bnn_gemm_params.hpp"
 #include "bnn_dma.hpp"
+#include "bnn_knobs.hpp"
 
 namespace bnn {
 
@@ -738,7 +739,6 @@ static void launch_sym(GemmParams &p, hipStream_t st)
     if (p.S % 8 == 0 && p.ntn >= 8) {
         // choose the XCD grid (xa sample groups x 8/xa panel groups) with the least L2 fill per XCD:
         // weights / xb + activations / xa (a shared input counts once whatever xa is)
-        static const int force = [] { const char *e = getenv("BNN_XCD_A"); return e ? atoi(e) : -1; }();
         const double wbytes = 8.0 * p.N * p.K * (BMODE == B_PLAIN ? 0.5 * p.S : 1.0);
         const double abytes = (double)p.M * p.K * (ABF ? 2 : 4) * (p.a_sample_stride == 0 ? 1 : p.S);
         int best = 8;
@@ -750,18 +750,17 @@ static void launch_sym(GemmParams &p, hipStream_t st)
             const double cost = wbytes / xb + (p.a_sample_stride == 0 ? abytes : abytes / xa);
             if (cost < best_cost) { best_cost = cost; best = xa; }
         }
-        if (force >= 0) best = force;
+        if (knob::linear_xcd_a() >= 0) best = knob::linear_xcd_a();     // (diagnostic build: BNN_XCD_A forces it)
         if (best >= 1 && best < 8 && 8 % best == 0 && p.S % best == 0) {
             p.xcd_a = best;
             const int xb = 8 / best, ppg = (p.ntn + xb - 1) / xb;
             grid = (int64_t)8 * (p.S / best) * ppg * p.ntm;
         }
     }
-    if constexpr (BMODE == B_SAMPLED && CP == BNN_COMPUTE_BF16 && BN > 16) {
-        // diagnostic build with in-kernel stamps (tools/stamps.py): BNN_STAMPS=<device pointer>
-        static unsigned long long *dbg = [] { const char *e = getenv("BNN_STAMPS"); return e ? (unsigned long long *)strtoull(e, nullptr, 0) : nullptr; }();
-        if (dbg) {
-            p.dbg = dbg;
+    if constexpr (kDiagBuild && BMODE == B_SAMPLED && CP == BNN_COMPUTE_BF16 && BN > 16) {
+        // in-kernel stamps (tools/stamps.py): BNN_STAMPS=<device pointer>
+        if (knob::linear_stamps()) {
+            p.dbg = reinterpret_cast<unsigned long long *>(knob::linear_stamps());
             p.dbg_block = 100;
             hipLaunchKernelGGL((k_linear_sym<NW, RW, BN, CH, S, NB, BMODE, CP, ABF, true>), dim3((unsigned)grid), dim3(NW * 64), 0, st, p);
             return;
@@ -777,17 +776,11 @@ static void launch_sym(GemmParams &p, hipStream_t st)
     hipLaunchKernelGGL((k_linear_sym<NW, RW, BN, CH, S, NB, BMODE, CP, ABF>), dim3((unsigned)grid), dim3(NW * 64), 0, st, p);
 }
 
-// BNN_F32_MFMA=native: the fp32 mode on v_mfma_f32_16x16x4_f32 (exact fp32 products); default: bf16x3
-static bool f32x3_enabled()
-{
-    static const bool on = [] { const char *e = getenv("BNN_F32_MFMA"); return !(e && e[0] == 'n'); }();
-    return on;
-}
-
+// The fp32 mode runs on the bf16 MFMA with three-way operand splits (kComputeBf16x3); its input gradient, below, on
+// v_mfma_f32_16x16x4_f32.
 template <int BMODE, int CP>
 static void select_pc(GemmParams &p, hipStream_t st)
 {
-    static const int tile = [] { const char *e = getenv("BNN_TILE"); return e ? atoi(e) : 0; }();
     if constexpr (CP == BNN_COMPUTE_BF16) {
         if (p.flags & BNN_FLAG_X_BF16) {
             // bf16 activations: 2-KB stages -> a 3-stage ring and 4 chunk buffers fit easily
@@ -804,22 +797,17 @@ static void select_pc(GemmParams &p, hipStream_t st)
     }
     if (p.N <= 16) {
         // fp32 mode: the bf16 head's shape (128 x 16 tiles, 256-k chunks) on bf16x3 splits (fp32 step 0.1927 -> 0.1901 ms)
-        if (CP == BNN_COMPUTE_F32 && f32x3_enabled()) launch_sym<8, 16, 16, 8, 3, 4, BMODE, kComputeBf16x3>(p, st);
+        if constexpr (CP == BNN_COMPUTE_F32) launch_sym<8, 16, 16, 8, 3, 4, BMODE, kComputeBf16x3>(p, st);
         else launch_sym<4, 16, 16, 2, 3, 4, BMODE, CP>(p, st);
-    } else if (CP == BNN_COMPUTE_F32 && f32x3_enabled() && tile == 0) {
+    } else if constexpr (CP == BNN_COMPUTE_F32) {
         // fp32 results from the bf16 MFMA (kComputeBf16x3): 256 x 80 tiles, 64-k chunks, 2 chunk buffers (three B images)
         // (8 waves x 32 rows, which halves the B-fragment LDS reads, and 32-k chunks were measured: all within 4 %; 512 x 48
-        // tiles with 32-k chunks, which draw every weight once: 6 % slower)
+        // tiles with 32-k chunks, which draw every weight once: 6 % slower; native fp32 MFMAs on 256 x 80 tiles: 0.2749 ms per
+        // fp32 step, 80 TFLOP/s = 51 % of the fp32 MFMA peak)
         launch_sym<16, 16, 80, 2, 2, 2, BMODE, kComputeBf16x3>(p, st);
-    } else if ((CP == BNN_COMPUTE_F32 && tile != 512) || tile == 256) {
-        // fp32 is MFMA-bound: 256 x 80 tiles fill the chip (240 workgroups at the BASELINE shape)
-        // (64-k chunks, 2-stage A ring: 0.2876 -> 0.2749 ms per fp32 step against 32-k chunks / 3 stages; the kernel
-        // runs at 80 TFLOP/s = 51 % of the fp32 MFMA peak, 70 % of its per-SIMD MFMA + draw-VALU cycle count)
-        if constexpr (CP == BNN_COMPUTE_F32) launch_sym<16, 16, 80, 2, 2, 4, BMODE, CP>(p, st);
-        else launch_sym<16, 16, 80, 1, 3, 4, BMODE, CP>(p, st);
     } else {
         // bf16 is draw-bound: 512 x 48 tiles draw every weight of a sample exactly once
-        launch_sym<16, 32, 48, 2, 2, (CP == BNN_COMPUTE_F32 ? 2 : 4), BMODE, CP>(p, st);
+        launch_sym<16, 32, 48, 2, 2, 4, BMODE, CP>(p, st);
     }
 }
 

@@ -25,6 +25,7 @@
 #include "bnn_device.hpp"
 #include "bnn_gemm_params.hpp"
 #include "bnn_dma.hpp"
+#include "bnn_knobs.hpp"
 
 namespace bnn {
 
@@ -43,7 +44,7 @@ struct WgradParams {
     int64_t slab_stride;        // floats between the partials of two sample groups (nsplit > 1)
     int32_t M, N, K, S, accumulate, ntk, ntn, nsplit, xcd_map;
     int32_t vecX, vecG;         // 16-B loads legal
-    int32_t diag;               // BNN_WGRAD_DIAG (timing only, wrong results): 1 = no fragment reads / MFMAs, 2 = no LDS-DMA
+    int32_t diag;               // BNN_WGRAD_DIAG, 0 outside the diagnostic build (timing only, wrong results): 1 = no fragment reads / MFMAs, 2 = no LDS-DMA
     int32_t plain;              // 1: no draw -- out[s] = dW_s per sample (gridDim.y = S), F.linear's own gradient
     RngDev rng;
     // optional fused bias gradient (nsplit == 1 only): the workgroups of k-tile 0 also take the column sums
@@ -196,37 +197,10 @@ __device__ __forceinline__ void wgrad_bias_store(const WgradBias &Bz, const Wgra
     p.g_rho_b[n] = gr;
 }
 
-// UNCOND: draw eps for every accumulator tile, in range or not (out-of-range outputs are discarded by
-// wgrad_store) -- one straight-line block, so the independent Philox chains of the 8 tiles interleave.
-template <bool UNCOND = false>
 __device__ __forceinline__ void wgrad_sample_end(WgradAcc &A, const WgradParams &p, uint32_t edev, int s, int nb, int kb)
 {
     const int lane = threadIdx.x & 63;
     const bool k4 = (p.K & 3) == 0;              // rows start on a Philox block: one block per 4 outputs
-    if constexpr (UNCOND) {                      // (needs K % 4 == 0)
-        if (!p.plain) {
-            const uint32_t sample = p.rng.sample0 + (uint32_t)s;
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const int n = nb + b * 16 + (lane & 15), k = kb + a * 16 + 4 * (lane >> 4);
-                    const float4 z = eps4(p.rng, edev, (uint32_t)(((int64_t)n * p.K + k) >> 2), sample);
-                    A.grho[a][b][0] = fmaf(A.acc[a][b][0], z.x, A.grho[a][b][0]);
-                    A.grho[a][b][1] = fmaf(A.acc[a][b][1], z.y, A.grho[a][b][1]);
-                    A.grho[a][b][2] = fmaf(A.acc[a][b][2], z.z, A.grho[a][b][2]);
-                    A.grho[a][b][3] = fmaf(A.acc[a][b][3], z.w, A.grho[a][b][3]);
-                }
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                A.gmu[a][b] += A.acc[a][b];
-                A.acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-        return;
-    }
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -406,165 +380,30 @@ __global__ __launch_bounds__(W_NT) void k_wgrad_bf16(const WgradParams p)
     if (bias_wave) wgrad_bias_store(Bz, p, nb + 16 * wk);
 }
 
-// Same contraction for the hot case -- x and gy both bf16 in memory, M % 256 == 0, K % 8 == 0, N % 8 == 0:
-// the [32 m][cols] images ARE the memory layout, so LDS-DMA (global_load_lds_dwordx4) fills them
-// without touching registers, the XOR swizzle applied on the source side (lane l of a 1-KiB piece
-// fetches the chunk that belongs in LDS slot l).  Ring of 8 images (96 KB) handled in pairs: one barrier per
-// 64 rows, three pairs in flight per wave; wave w owns X pieces 2w, 2w+1 and G piece w of every step (rows 8w .. 8w+7).
-// The loop is instruction-bound (one wave per SIMD), so it carries no address arithmetic: DMA sources
-// are a scalar base (advanced with scalar adds) + a fixed 32-bit lane offset, LDS read addresses are
-// fixed registers + the buffer's immediate offset (loop unrolled over the ring).
-// Columns past K / N are fetched from the last legal chunk: they only feed outputs that are discarded.
-__global__ __launch_bounds__(W_NT) void k_wgrad_bf16_dma(const WgradParams p)
-{
-    constexpr int XB = W_BM * W_TK * 2, GB = W_BM * W_TN * 2, NBUF = 8, OPS = 3, BUFB = XB + GB;
-    __shared__ __attribute__((aligned(1024))) char lds[NBUF * BUFB];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wk = wave >> 1, wn = wave & 1;
-    int kt, nt;
-    if (!wgrad_tile(p, kt, nt)) return;
-    const int k0 = kt * W_TK, n0 = nt * W_TN;
-    const int s_lo = (int)((int64_t)blockIdx.y * p.S / p.nsplit), s_hi = (int)((int64_t)(blockIdx.y + 1) * p.S / p.nsplit);
-    const int msteps = p.M / W_BM;
-    const int total = (s_hi - s_lo) * msteps;
-    const uint32_t edev = rng_epoch_dev(p.rng);
-
-    // fixed lane offsets (bytes) from the scalar base of a step
-    uint32_t xoff[2], goff;
-    {
-        const int sc = lane & 15;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int row = 8 * wave + 4 * j + (lane >> 4);
-            int col = k0 + 8 * (sc ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-            col = col < p.K - 8 ? col : p.K - 8;
-            xoff[j] = (uint32_t)(((int64_t)row * p.ldx + col) * 2);
-        }
-        const int grow = 8 * wave + (lane >> 3), gsc = lane & 7;
-        int gcol = n0 + 8 * (gsc ^ ((((grow & 3) << 2) | ((grow >> 2) & 3)) & 7));
-        gcol = gcol < p.N - 8 ? gcol : p.N - 8;
-        goff = (uint32_t)(((int64_t)grow * p.ldgy + gcol) * 2);
-    }
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(lds));
-    // issue cursor: running scalar bases of the next 32-row image; a barrier covers TWO images (64 rows)
-    const char *xb = reinterpret_cast<const char *>(p.x) + (int64_t)s_lo * p.x_sample_stride * 2;
-    const char *gb = reinterpret_cast<const char *>(p.gy) + (int64_t)s_lo * p.gy_sample_stride * 2;
-    const int64_t x_img = (int64_t)W_BM * p.ldx * 2, g_img = (int64_t)W_BM * p.ldgy * 2;   // bytes per 32 rows
-    // correction when the cursor passes the last image of a sample: to the next sample's first row
-    const int64_t x_wrap = (p.x_sample_stride - (int64_t)p.M * p.ldx) * 2, g_wrap = (p.gy_sample_stride - (int64_t)p.M * p.ldgy) * 2;
-    int im = 0, left = total;                                      // images issued in this sample / images left to issue
-    auto issue_pair = [&](int pair) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const uint32_t base = lds0 + (uint32_t)(2 * pair + h) * BUFB;
-            dma16_s3(xb, xoff[0], base + (uint32_t)wave * 2048u, xb, xoff[1], base + (uint32_t)wave * 2048u + 1024u,
-                     gb, goff, base + XB + (uint32_t)wave * 1024u);
-            if (left > 1) {                                        // past the end: harmless re-fetch of the last image
-                --left;
-                xb += x_img;
-                gb += g_img;
-                if (++im == msteps) { im = 0; xb += x_wrap; gb += g_wrap; }
-            }
-        }
-    };
-
-    WgradAcc A;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) A.acc[a][b] = A.gmu[a][b] = A.grho[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const bool bias_wave = p.g_mu_b != nullptr && kt == 0;         // fused bias gradient: subtile wk of this wave's two
-    const uint32_t edev_b = bias_wave ? rng_epoch_dev(p.rng_b) : 0u;
-    WgradBias Bz;
-    wgrad_bias_init(Bz);
-    const s16x8 ones8 = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};   // bf16 1.0
-
-    const int Q = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-    // tr-read addresses in buffer 0 and in buffer 4 (the ds_read immediate offset reaches 64 KB; the ring is 96 KB)
-    const char *aptr[2][4][2], *bptr[2][2][2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int c0 = (wk * 64 + a * 16) / 8 + (pp >> 1);
-            aptr[h][a][0] = lds + h * 4 * BUFB + img_off<256>(8 * Q + q, c0) + 8 * (pp & 1);
-            aptr[h][a][1] = lds + h * 4 * BUFB + img_off<256>(8 * Q + 4 + q, c0) + 8 * (pp & 1);
-        }
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int c0 = (wn * 32 + b * 16) / 8 + (pp >> 1);
-            bptr[h][b][0] = lds + h * 4 * BUFB + XB + img_off<128>(8 * Q + q, c0) + 8 * (pp & 1);
-            bptr[h][b][1] = lds + h * 4 * BUFB + XB + img_off<128>(8 * Q + 4 + q, c0) + 8 * (pp & 1);
-        }
-    }
-    auto compute = [&](auto BUF) {
-        constexpr int h = decltype(BUF)::value / 4;
-        constexpr int o = (decltype(BUF)::value % 4) * BUFB;       // immediate offset of the ds_read
-        s16x8 af[4], bfr[2];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-            af[a] = __builtin_shufflevector(lds_tr_read(aptr[h][a][0] + o), lds_tr_read(aptr[h][a][1] + o), 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-            bfr[b] = __builtin_shufflevector(lds_tr_read(bptr[h][b][0] + o), lds_tr_read(bptr[h][b][1] + o), 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-                A.acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[a]),
-                                                                      __builtin_bit_cast(bf16x8, bfr[b]), A.acc[a][b], 0, 0, 0);
-        if (bias_wave)
-            Bz.cs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ones8),
-                                                            __builtin_bit_cast(bf16x8, wk ? bfr[1] : bfr[0]), Bz.cs, 0, 0, 0);
-    };
-
-    const int nb = n0 + wn * 32, kb = k0 + wk * 64;
-    if (total > 0) {
-        constexpr int NPAIR = NBUF / 2;
-#pragma unroll
-        for (int t = 0; t < NPAIR - 1; ++t) issue_pair(t);
-        auto step = [&](auto PAIR) {
-            constexpr int pr = decltype(PAIR)::value;
-            // this wave's pieces of the pair have landed (the next two pairs may still be in flight) ...
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"((NPAIR - 2) * 2 * OPS) : "memory");
-            __syncthreads();                                       // ... and everyone else's; the previous pair's buffers are free
-            issue_pair((pr + NPAIR - 1) % NPAIR);
-            compute(std::integral_constant<int, 2 * pr>{});
-            compute(std::integral_constant<int, 2 * pr + 1>{});
-        };
-        for (int s = s_lo; s < s_hi; ++s) {                        // msteps % NBUF == 0: every sample starts in buffer 0
-            for (int mi = 0; mi < msteps; mi += NBUF) {
-                step(std::integral_constant<int, 0>{});
-                step(std::integral_constant<int, 1>{});
-                step(std::integral_constant<int, 2>{});
-                step(std::integral_constant<int, 3>{});
-            }
-            wgrad_sample_end<true>(A, p, edev, s, nb, kb);
-            if (bias_wave) wgrad_bias_sample_end(Bz, p, edev_b, s, nb + 16 * wk);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // nothing may still be writing this LDS at exit
-    }
-    wgrad_store(A, p, nb, kb);
-    if (bias_wave) wgrad_bias_store(Bz, p, nb + 16 * wk);
-}
-
-// Two-role version of the kernel above (512 threads): waves 0..3 run the MFMA loop and nothing else; waves
-// 4..7 -- one per SIMD beside an MFMA wave -- issue ALL the LDS-DMA (with its scalar bookkeeping and the
-// vmcnt waits) and draw the eps of the CURRENT sample, one Philox block between two barriers, into a
-// 32-KB LDS image that the MFMA waves read once at the end of the sample.  Measured: 54.5 -> 48.6 us at the
-// layer-2 shape -- the MFMA loop itself drops to 29 us (no issue overhead), but a VALU-heavy wave and an
-// MFMA-heavy wave on one SIMD add up rather than overlap, so the 19 us of eps draws are not hidden (spreading
-// them evenly over all pair steps, 8 interleaved chains, measured WORSE: 65 us).  Both roles execute the same barriers: one per pair of
-// images and one (E) per sample, after the helper's last eps write; the helper's first write of the next
-// sample comes after the next pair barrier, which the MFMA waves pass only after their eps reads.
-// Round 3, what bounds the loop (BNN_WGRAD_DIAG, BNN_WGRAD_NOEPS; layer-2 shape, us): full 49.6 (24-bit stream; 48.1 on the 16-bit
-// stream with whole blocks), no eps 30.2, no eps + no fragment reads / MFMAs 29.3, no eps + no DMA 24.9, neither 12.5: the
-// 128 x 64 tile streams 288 MB through LDS per launch (x re-read 19 x, gy 10 x) and THAT is the loop; the MFMAs are 1 us of it.
-// The eps draw adds its full time wherever it runs: moved into the MFMA waves (which "wait" most of a step) -- 4 rows at 2
-// points per sample 52.8, one row at each of 4 points 55.1 (24-bit) / 49.7 (16-bit) -- it was no better than in the helpers.
-// What would help is fewer bytes per FLOP (a 128 x 128 tile: 192 MB), not a better place for the draw.
+// Same contraction for the hot case -- x and gy both bf16 in memory, M % 256 == 0, K % 8 == 0, N % 8 == 0: the
+// [32 m][cols] images ARE the memory layout, so LDS-DMA (global_load_lds_dwordx4) fills them without touching
+// registers, the XOR swizzle applied on the source side (lane l of a 1-KiB piece fetches the chunk that belongs
+// in LDS slot l).  Ring of 8 images (96 KB) handled in pairs: one barrier per 64 rows, three pairs in flight;
+// loader w owns X pieces 2w, 2w+1 and G piece w of every step (rows 8w .. 8w+7). The loop carries no address
+// arithmetic: DMA sources are a scalar base (advanced with scalar adds) + a fixed 32-bit lane offset, LDS read
+// addresses are fixed registers + the buffer's immediate offset (loop unrolled over the ring).  Columns past K /
+// N are fetched from the last legal chunk: they only feed outputs that are discarded. Two roles (512 threads):
+// waves 0..3 run the MFMA loop and nothing else; waves 4..7 -- one per SIMD beside an MFMA wave -- issue ALL the
+// LDS-DMA (with its scalar bookkeeping and the vmcnt waits) and draw the eps of the CURRENT sample, one Philox
+// block between two barriers, into a 32-KB LDS image that the MFMA waves read once at the end of the sample.
+// Measured against one role (four waves that also issue their own DMA and draw eps at the end of a sample): 54.5
+// -> 48.6 us at the layer-2 shape -- the MFMA loop itself drops to 29 us (no issue overhead), but a VALU-heavy
+// wave and an MFMA-heavy wave on one SIMD add up rather than overlap, so the 19 us of eps draws are not hidden
+// (spreading them evenly over all pair steps, 8 interleaved chains, measured WORSE: 65 us).  Both roles execute
+// the same barriers: one per pair of images and one (E) per sample, after the helper's last eps write; the
+// helper's first write of the next sample comes after the next pair barrier, which the MFMA waves pass only
+// after their eps reads.
+// Round 3, what bounds the loop (diagnostic build: BNN_WGRAD_DIAG, BNN_WGRAD_NOEPS; layer-2 shape, us): full 49.6 (24-bit
+// stream; 48.1 on the 16-bit stream with whole blocks), no eps 30.2, no eps + no fragment reads / MFMAs 29.3, no eps + no DMA
+// 24.9, neither 12.5: the 128 x 64 tile streams 288 MB through LDS per launch (x re-read 19 x, gy 10 x) and THAT is the loop;
+// the MFMAs are 1 us of it. The eps draw adds its full time wherever it runs: moved into the MFMA waves (which "wait" most of
+// a step) -- 4 rows at 2 points per sample 52.8, one row at each of 4 points 55.1 (24-bit) / 49.7 (16-bit) -- it was no better
+// than in the helpers. What would help is fewer bytes per FLOP (a 128 x 128 tile: 192 MB), not a better place for the draw.
 __global__ __launch_bounds__(2 * W_NT) void k_wgrad_bf16_dma8(const WgradParams p)
 {
     constexpr int XB = W_BM * W_TK * 2, GB = W_BM * W_TN * 2, NBUF = 8, OPS = 3, BUFB = XB + GB, NPAIR = NBUF / 2;
@@ -614,7 +453,7 @@ __global__ __launch_bounds__(2 * W_NT) void k_wgrad_bf16_dma8(const WgradParams 
         const int64_t x_wrap = (p.x_sample_stride - (int64_t)p.M * p.ldx) * 2, g_wrap = (p.gy_sample_stride - (int64_t)p.M * p.ldgy) * 2;
         int im = 0, left = total;
         auto issue_pair = [&](int pair) {
-            if (p.diag & 2) return;
+            if (p.diag & 2) return;                                // (run-time, as `p.diag & 1` below: see there)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const uint32_t base = lds0 + (uint32_t)(2 * pair + h) * BUFB;
@@ -731,6 +570,8 @@ __global__ __launch_bounds__(2 * W_NT) void k_wgrad_bf16_dma8(const WgradParams 
     auto step = [&](auto PAIR) {
         constexpr int pr = decltype(PAIR)::value;
         __syncthreads();                                           // the pair's images have landed (helper waves waited for them)
+        // (p.diag stays a run-time test in every build, fed 0 outside the diagnostic one: with both tests compiled out the
+        // register allocator ends at 182 VGPRs instead of 178, and with either one the kernel's code moves)
         if (p.diag & 1) return;
         compute(std::integral_constant<int, 2 * pr>{});
         compute(std::integral_constant<int, 2 * pr + 1>{});
@@ -1414,21 +1255,17 @@ int bnn_linear_backward_weight_sampled(const void *x, int64_t x_sample_stride, i
         p.kl_scale_w = kl->scale_w; p.kl_pm_w = kl->prior_mu_w; p.kl_ps_w = kl->prior_sigma_w;
         p.kl_scale_b = kl->scale_b; p.kl_pm_b = kl->prior_mu_b; p.kl_ps_b = kl->prior_sigma_b;
     }
-    // diagnostic only (timing split of the loop vs the eps epilogue; results are then NOT the gradient)
-    static const bool diag_noeps = [] { const char *e = getenv("BNN_WGRAD_NOEPS"); return e && e[0] == '1'; }();
-    if (diag_noeps && p.nsplit == 1) p.plain = 1;
-    static const int wdiag = [] { const char *e = getenv("BNN_WGRAD_DIAG"); return e ? atoi(e) : 0; }();
-    p.diag = wdiag;
+    // diagnostic build only (timing split of the loop vs the eps epilogue; results are then NOT the gradient)
+    if (knob::wgrad_noeps() && p.nsplit == 1) { p.plain = 1; BNN_WRONG_RESULTS_ONCE("BNN_WGRAD_NOEPS"); }
+    p.diag = knob::wgrad_diag();
+    if (p.diag & 3) BNN_WRONG_RESULTS_ONCE("BNN_WGRAD_DIAG");
     p.xcd_map = (p.ntk >= 4 && p.ntn >= 8);
     const dim3 grid(p.xcd_map ? (unsigned)(8 * ((p.ntk + 1) / 2) * ((p.ntn + 3) / 4)) : (unsigned)tiles, (unsigned)p.nsplit);
     const bool dma_ok = p.vecX && p.vecG && M % (8 * W_BM) == 0 && K % 8 == 0 && N % 8 == 0;
     if (compute == BNN_COMPUTE_F32) {
         hipLaunchKernelGGL(k_wgrad_f32, grid, dim3(W_NT), 0, st, p);
     } else if (xh && gh && dma_ok) {
-        // two-role kernel (MFMA waves + DMA / eps waves) unless BNN_WGRAD_ROLES=1 asks for the one-role one
-        static const bool one_role = [] { const char *e = getenv("BNN_WGRAD_ROLES"); return e && e[0] == '1'; }();
-        if (one_role) hipLaunchKernelGGL(k_wgrad_bf16_dma, grid, dim3(W_NT), 0, st, p);
-        else hipLaunchKernelGGL(k_wgrad_bf16_dma8, grid, dim3(2 * W_NT), 0, st, p);
+        hipLaunchKernelGGL(k_wgrad_bf16_dma8, grid, dim3(2 * W_NT), 0, st, p);
     } else if (xh && gh) {
         hipLaunchKernelGGL((k_wgrad_bf16<true, true>), grid, dim3(W_NT), 0, st, p);
     } else if (xh) {

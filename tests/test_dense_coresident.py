@@ -19,9 +19,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CO_PREFIX = "_ZN3bnn12k_dense_bf16ILi4ELi5ELi2ELi2ELi2E"     # <TM = 4, TN = 5, NWM = 2, NWN = 2, ST = 2, ...>
 
 
-def _code_object_kernels():
-    """name -> metadata fields of every kernel in the built library's gfx950 code objects."""
+def _code_object_kernels(lib_path=None):
+    """name -> metadata fields of every kernel in the gfx950 code objects of a built library (default: the loaded one)."""
     from bayesianneuralnetworks_amd import _lib
+    lib_path = lib_path or _lib.LIB_PATH
     llvm = "/opt/rocm/llvm/bin"
     tools = [os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
     if not all(os.path.exists(t) for t in tools):
@@ -29,7 +30,7 @@ def _code_object_kernels():
     notes = ""
     with tempfile.TemporaryDirectory() as d:
         fat = os.path.join(d, "fat.bin")
-        subprocess.check_call([tools[0], "--dump-section=.hip_fatbin=" + fat, _lib.LIB_PATH, os.path.join(d, "lib.so")])
+        subprocess.check_call([tools[0], "--dump-section=.hip_fatbin=" + fat, lib_path, os.path.join(d, "lib.so")])
         blob = open(fat, "rb").read()
         magic = b"__CLANG_OFFLOAD_BUNDLE__"
         starts = [m.start() for m in re.finditer(re.escape(magic), blob)]      # one bundle per translation unit
@@ -49,11 +50,18 @@ def _code_object_kernels():
     return kernels
 
 
-def test_coresident_code_objects_fit_two_workgroups_per_cu():
-    kernels = _code_object_kernels()
+DIAG_LIB = os.path.join(ROOT, "bayesianneuralnetworks_amd", "libbnn_hip_diag.so")     # make -C csrc diag; not built by build()
+
+
+@pytest.mark.parametrize("build", ["production", "diagnostic"])
+def test_coresident_code_objects_fit_two_workgroups_per_cu(build):
+    if build == "diagnostic" and not os.path.exists(DIAG_LIB):
+        pytest.skip("diagnostic library not built")
+    kernels = _code_object_kernels(DIAG_LIB if build == "diagnostic" else None)
     co = {n: f for n, f in kernels.items() if n.startswith(CO_PREFIX)}
-    # ReLU or not x {bf16, fp32, fused head} + the stamped bf16 build (BNN_DENSE_DIAG=6)
-    assert len(co) == 8, sorted(co)
+    # ReLU or not x {bf16, fp32, fused head} = 6 (dense_launch, BNN_DENSE_CO: three launches per ReLU setting); the diagnostic
+    # library adds the stamped bf16 build (BNN_DENSE_DIAG=6) of each ReLU setting: 2 x 4 = 8
+    assert len(co) == (8 if build == "diagnostic" else 6), sorted(co)
     for n, f in co.items():
         assert int(f["max_flat_workgroup_size"]) == 512, (n, f)
         assert int(f["group_segment_fixed_size"]) <= 80 * 1024, (n, f)              # two workgroups in the CU's 160 KiB

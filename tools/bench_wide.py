@@ -1,5 +1,5 @@
 """BASELINE configs[4] layer (4096 x 4096 NormalLinear, batch 4096, fp32 mode): one sampled forward launch, S MC samples.
-usage: bench_wide.py [S]   (BNN_F32_MFMA=native for the v_mfma_f32_16x16x4_f32 path)"""
+usage: bench_wide.py [S]"""
 import sys, os, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -32,4 +32,4 @@ for comp, name in ((0, "f32"), (1, "bf16"), (10, "f32 draw-once"), (11, "bf16 dr
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 5
     fl = 2.0 * S * M * N * K
-    print("4096x4096 layer, batch 4096, S=%d, %s (%s): %.3f ms = %.1f TFLOP/s" % (S, name, os.environ.get("BNN_F32_MFMA", "x3") if comp == 0 else "-", ms, fl / ms / 1e9))
+    print("4096x4096 layer, batch 4096, S=%d, %s: %.3f ms = %.1f TFLOP/s" % (S, name, ms, fl / ms / 1e9))

@@ -23,6 +23,8 @@ done
 bash tools/prof.sh r03_legs -- python3 tools/run_legs.py both
 bash tools/prof.sh r03_train -- python3 tools/bench_train.py --steps 30 --no-graph
 python3 tools/bench_train.py --steps 50 > gpurun_out/r03_train_step.json 2>/dev/null
+# BNN_DENSE_XCD, BNN_DENSE_DIAG and BNN_CONV_DIAG exist only in the diagnostic library (README.md): from here on BNN_HIP_LIB must name it
+python3 tools/diag_lib.py
 export BNN_DENSE_XCD=0
 bash tools/pmc.sh r03_wide_plain_order_fetch "FETCH_SIZE" -- python3 tools/run_wide.py
 unset BNN_DENSE_XCD
@@ -43,5 +45,6 @@ STAMP_DIAG=7 python3 tools/dense_stamps.py 1200 >> gpurun_out/r03_dense_stamps.t
 python3 tools/draw_exp2.py > gpurun_out/r03_draw_breakdown.txt 2>&1
 tools/ubench_draw > gpurun_out/r03_ubench_draw.txt 2>&1 || true
 python3 tools/conv_diag.py > gpurun_out/r03_conv_phases.txt 2>&1
+python3 tools/diag_lib.py
 for d in 1 2 4 7; do BNN_CONV_DIAG=$d python3 tools/conv_diag.py >> gpurun_out/r03_conv_phases.txt 2>&1; done
 echo done

@@ -1,8 +1,12 @@
 """Phase breakdown of k_conv_bf16 (BNN_CONV_DIAG bit 1 skips the image fill, 2 the k loop, 4 the output copy; timing-only, wrong
-outputs): graph timing of the layer call (draw launch + contraction) per configuration.   usage: BNN_CONV_DIAG=n python tools/conv_diag.py"""
+outputs; diagnostic library only): graph timing of the layer call (draw launch + contraction) per configuration.
+usage: BNN_HIP_LIB=.../libbnn_hip_diag.so BNN_CONV_DIAG=n python tools/conv_diag.py   (no BNN_CONV_DIAG: the whole call, any library)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import diag_lib
+if os.environ.get("BNN_CONV_DIAG", "0") != "0":
+    diag_lib.require("tools/conv_diag.py with BNN_CONV_DIAG")
 import bayesianneuralnetworks_amd as bnn
 from bayesianneuralnetworks_amd.nn import NormalConv2d
 from bayesianneuralnetworks_amd import _mc

@@ -1,8 +1,10 @@
 """Where a dense workgroup's time goes: s_memrealtime stamps of consumer wave 0 of every workgroup of the layer-2 launch
-(BNN_DENSE_DIAG=6 build path).   usage: python tools/dense_stamps.py [K]"""
+(BNN_DENSE_DIAG=6, diagnostic library only).   usage: BNN_HIP_LIB=.../libbnn_hip_diag.so python tools/dense_stamps.py [K]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import diag_lib
+diag_lib.require("tools/dense_stamps.py (BNN_DENSE_DIAG, BNN_DENSE_STAMPS)")
 dev = torch.device("cuda:0")
 buf = torch.zeros(4096 * 5, dtype=torch.int64, device=dev)
 os.environ["BNN_DENSE_DIAG"] = os.environ.get("STAMP_DIAG", "6")

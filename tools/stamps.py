@@ -1,7 +1,10 @@
-"""In-kernel s_memtime stamps of the fused linear kernel (diagnostic build).  GPU box only."""
+"""In-kernel s_memtime stamps of the fused linear kernel (BNN_STAMPS, diagnostic library only).  GPU box only.
+usage: BNN_HIP_LIB=.../libbnn_hip_diag.so python tools/stamps.py"""
 import sys, os, ctypes, subprocess
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import diag_lib
+diag_lib.require("tools/stamps.py (BNN_STAMPS)")
 dev = torch.device("cuda:0")
 dbg = torch.zeros(8000 * 2, dtype=torch.int64, device=dev)
 os.environ["BNN_STAMPS"] = hex(dbg.data_ptr())

@@ -1,9 +1,12 @@
 """Wide dense launches at S = 1 (the configs[4] layer: 4096 x 4096, batch 4096) with and without the XCD-contiguous, grouped tile
-order (BNN_DENSE_XCD=0 = plain order): bf16 operands and the fp32 parity mode's three-plane operands.
-usage: [BNN_DENSE_XCD=0] python tools/wide_xcd_ab.py"""
+order (BNN_DENSE_XCD=0 = plain order, diagnostic library only): bf16 operands and the fp32 parity mode's three-plane operands.
+usage: python tools/wide_xcd_ab.py; BNN_HIP_LIB=.../libbnn_hip_diag.so BNN_DENSE_XCD=0 python tools/wide_xcd_ab.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import diag_lib
+if os.environ.get("BNN_DENSE_XCD") == "0":
+    diag_lib.require("tools/wide_xcd_ab.py with BNN_DENSE_XCD=0")
 from bayesianneuralnetworks_amd import _lib, ops
 from bayesianneuralnetworks_amd._rng import DrawKey
 import bench
